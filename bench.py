@@ -1,8 +1,17 @@
 #!/usr/bin/env python
 """bench.py -- headline metric of BASELINE.json: restored 512x512 face frames/s on T=20 clips.
 
-    python bench.py --gpus 1 --steps K --warmup W [--clips B] [--precision x3|fp32|bf16]
+    python bench.py --gpus 1 --steps K --warmup W [--clips B] [--precision x3|fp32|bf16] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times K steps, writes the last step's output if --dump-outputs is given and prints the JSON
+line: the headline keys, `ms_per_step` (wall milliseconds of one timed step) and what falls out of the timing for free.
+Everything that takes runs of its own -- roofline, the other policies, the legs listed below, cpu_baseline and, under
+--gpus N, the one-video-per-GPU leg -- runs only with --full (--no-extras / --no-cpu-baseline trim --full).
+
+--dump-outputs DIR: DIR/restored_frames.npy (float32) holds the restored frames the last timed step returned -- whole when they
+fit in DUMP_BYTES, else a fixed sample of them (dump_outputs); the inputs are a pure function of the arguments, so two builds
+run with the same arguments can be compared output for output.
 
 One "step" = one pass of the hot path (KEEP.forward on the HIP engine) over one batch of synthetic input:
 B independent 20-frame 512x512 clips per GPU (config.workload, BASELINE configs[1]), inputs already resident in HBM.
@@ -12,11 +21,11 @@ collective is the one-off RCCL broadcast of the packed weights, outside the time
 
 Precision policy of `value` (default `x3`): every matrix-core operand split into two fp16 halves, three MFMAs per
 product, fp32 accumulate -- fp32-grade products on the 16-bit matrix pipe.  It passes the SAME <= 1e-3 parity tests as the
-exact-f32 policy (tests/test_gpu_net.py runs every network test on both); `dtype` says "f16x3".  The exact-f32 policy and
-the bf16 speed policy (outside the parity tolerance) are timed in the same invocation and reported beside it, each with
-its live agreement with the exact-f32 result on the same input.
+exact-f32 policy (tests/test_gpu_net.py runs every network test on both); `dtype` says "f16x3".  With --full the exact-f32
+policy and the bf16 speed policy (outside the parity tolerance) are timed in the same invocation and reported beside it,
+each with its live agreement with the exact-f32 result on the same input.
 
-Also on the JSON line:
+Also on the JSON line with --full:
   roofline       dominant kernel (conv3x3_halo_x3s_kernel, the streaming LDS-halo 3x3 convolution on split fp16): algorithmic FLOPs of
                  its launches in one step / their summed HIP-event durations (events on the launch stream), against the
                  dense fp16 MFMA peak divided by the three MFMAs every product costs (2500 / 3 TFLOP/s); `mfma_frac` is
@@ -55,6 +64,80 @@ GMFLOW_DUPLICATE_FLOP_PER_FRAME = 33.0e9   # backbone passes of interior frames 
 PEAK = {'fp32': PEAK_F32_MFMA_TFLOPS, 'bf16': PEAK_16BIT_MFMA_TFLOPS, 'x3': PEAK_16BIT_MFMA_TFLOPS / 3.0}
 DTYPE = {'fp32': 'f32', 'bf16': 'bf16', 'x3': 'f16x3'}
 PMC_FILE = os.path.join(ROOT, 'profiles', 'r06_pmc_traffic.json')
+DUMP_BYTES = 48 << 20                 # --dump-outputs: bytes written in all, over every rank
+
+
+def _s64(v):
+    """A uint64 value as the int64 with the same bits."""
+    v = int(v)
+    return v - (1 << 64) if v >= 1 << 63 else v
+
+
+def _lsr64(z, k):
+    """Logical right shift of int64 tensors that hold uint64 bit patterns."""
+    return (z >> k) & ((1 << (64 - k)) - 1)
+
+
+def _splitmix64_t(z):
+    """synth._splitmix64 on int64 tensors (two's-complement wrap-around = the uint64 arithmetic of the original)."""
+    z = z + _s64(0x9E3779B97F4A7C15)
+    z = (z ^ _lsr64(z, 30)) * _s64(0xBF58476D1CE4E5B9)
+    z = (z ^ _lsr64(z, 27)) * _s64(0x94D049BB133111EB)
+    return z ^ _lsr64(z, 31)
+
+
+def synth_clip_device(T, B, seed, phase, device):
+    """synth.synth_clip(T, B, seed=seed, phase=phase) -- the 512 x 512 texture clips -- bit for bit, computed on `device`.  The
+    NumPy original spends ~2.4 s of one host core per clip, two minutes for the 48 clips of a step.  Here the sampling grid of a
+    frame (the same for every clip: it depends on t and phase only) is computed on the host by the original's float64 operations,
+    on one row and one column; the lattice gathers, interpolation, hash noise and clipping run on the device for all clips at
+    once, one torch op per NumPy op, in the original's order (no fused forms).  tests/test_bench.py pins it to synth_clip."""
+    S = 512
+    cells, amps = (9, 17, 33), (0.5, 0.6, 0.5)
+    grid = np.arange(S, dtype=np.float64)
+    tabs = [torch.from_numpy(np.stack([np.stack([synth.uniform_pm1(f'tex:{b}:{oi}:{ch}', (S // c + 8) ** 2, seed).reshape(S // c + 8, S // c + 8)
+                                                 for ch in range(3)]) for b in range(B)])).to(device) for oi, c in enumerate(cells)]
+    idx = torch.arange(S * S, dtype=torch.int64, device=device)
+    out = torch.empty((B, T, 3, S, S), dtype=torch.float32, device=device)
+    for t in range(T):
+        X = grid - (synth.CLIP_MOTION[0] * t + phase)
+        Y = grid - (synth.CLIP_MOTION[1] * t + 0.7 * phase)
+        img = torch.zeros((B, 3, S, S), dtype=torch.float64, device=device)
+        for oi, c in enumerate(cells):
+            gx, gy = X / c + 3.0, Y / c + 3.0
+            ix, iy = np.floor(gx), np.floor(gy)
+            fx, fy = gx - ix, gy - iy
+            fx, fy = fx * fx * (3.0 - 2.0 * fx), fy * fy * (3.0 - 2.0 * fy)
+            ix = torch.from_numpy(ix.astype(np.int64)).to(device)[None, :]
+            iy = torch.from_numpy(iy.astype(np.int64)).to(device)[:, None]
+            fx = torch.from_numpy(fx).to(device)
+            fy = torch.from_numpy(fy).to(device)[:, None]
+            tb = tabs[oi]
+            top = tb[:, :, iy, ix] * (1.0 - fx) + tb[:, :, iy, ix + 1] * fx
+            bot = tb[:, :, iy + 1, ix] * (1.0 - fx) + tb[:, :, iy + 1, ix + 1] * fx
+            img += amps[oi] * (top * (1.0 - fy) + bot * fy)
+        keys = torch.tensor([[_s64(synth._name_key(f'clip:{b}:{t}:{ch}', seed)) for ch in range(3)] for b in range(B)],
+                            dtype=torch.int64, device=device)[:, :, None]
+        bits = _splitmix64_t(_splitmix64_t(idx ^ keys) + keys)
+        u = (_lsr64(bits, 40).to(torch.float64) + 0.5) * (2.0 / 16777216.0) - 1.0          # synth.uniform_pm1
+        out[:, t] = (img + 0.002 * u.view(B, 3, S, S)).clamp_(-1.0, 1.0).to(torch.float32)
+    return out
+
+
+def dump_outputs(out, path, rank, world):
+    """--dump-outputs: the restored frames the last timed step returned ([B, T, 3, 512, 512] float32, 3 GB at 48 clips) as
+    PATH/restored_frames.npy (restored_frames_rank<r>.npy per rank under --gpus N): the whole array when it fits in this rank's
+    share of DUMP_BYTES, else a fixed sample, flat and in order -- one element from each of equal runs of the flattened array, at
+    an offset drawn by a generator seeded with 0, so every run with the same --clips samples the same positions."""
+    flat = out.reshape(-1)
+    n = DUMP_BYTES // world // flat.element_size()
+    if flat.numel() > n:
+        run = -(-flat.numel() // n)
+        k = flat.numel() // run
+        pos = torch.arange(k, dtype=torch.int64) * run + torch.randint(0, run, (k,), generator=torch.Generator().manual_seed(0))
+        out = flat[pos.to(flat.device)]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, 'restored_frames.npy' if world == 1 else f'restored_frames_rank{rank}.npy'), out.cpu().numpy())
 
 
 FAKE = os.environ.get('KEEP_BENCH_FAKE_NET') == '1'     # tests/test_dist_gloo.py: the N-rank plumbing of this file on a machine without a GPU
@@ -532,10 +615,17 @@ def main():
     ap.add_argument('--precision', default=os.environ.get('KEEP_BENCH_PRECISION', 'x3'), choices=['x3', 'fp32', 'bf16'],
                     help="MFMA operand policy of `value`: x3 (split fp16, parity-grade, default), fp32 (exact f32 MFMA), "
                          "bf16 (speed policy, outside the parity tolerance)")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write the restored frames of the last timed step (or a fixed sample of them) to DIR/restored_frames.npy')
+    ap.add_argument('--full', action='store_true',
+                    help='also everything that takes runs of its own: roofline, the other policies, one clip in flight, 16 clips, '
+                         'host-memory entry, configs 3 / 4 / 5, paste-back, facelib, end to end, cpu_baseline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without cpu_baseline')
     ap.add_argument('--cpu-baseline-frames', type=int, default=int(os.environ.get('KEEP_BENCH_CPU_T', '20')))
-    ap.add_argument('--no-extras', action='store_true', help='only the headline measurement + roofline')
+    ap.add_argument('--no-extras', action='store_true', help='--full with only the headline measurement + roofline (+ cpu_baseline)')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` on its own: become the launcher -- one rank per GPU under torch.distributed.run on the
@@ -566,9 +656,8 @@ def main():
         if os.environ.get('KEEP_DIST_DEVICE') and world > 1:      # every rank on ONE device (1-GPU boxes): they share its HBM
             free_b //= world
         B = max(1, min(B, int(0.8 * free_b / (per_frame * T_CLIP))))
-        x = synth.synth_clip(T=T_CLIP, B=B, seed=1234 + rank, phase=0.37 * rank).cuda()
+        x = synth_clip_device(T_CLIP, B, seed=1234 + rank, phase=0.37 * rank, device=torch.device('cuda', local))
     B16 = min(B, 16)                  # the side legs (other policies, policy-vs-policy comparison, host-memory entry) stay at the 16 clips of rounds 1-4
-    x16 = x[:B16].contiguous()
 
     def barrier():
         _sync()
@@ -601,6 +690,8 @@ def main():
         return d, o, ev_ms, d_rank
 
     dt, out, ev_ms, d_rank = timed(x, args.warmup, args.steps)
+    if args.dump_outputs:
+        dump_outputs(out, args.dump_outputs, rank, world)
     per_rank = None
     if world > 1:
         mine = torch.tensor([B * T_CLIP * args.steps / d_rank], dtype=torch.float64,
@@ -610,7 +701,7 @@ def main():
         per_rank = [round(float(t.item()), 2) for t in allr]
 
     cfg5 = None
-    if world > 1:
+    if world > 1 and args.full:
         # BASELINE configs[4]: one 300-crop video (15 clips x 20) per GPU through the processor's uint8 entry point, nothing
         # exchanged between ranks (shard_across_ranks off); value = all ranks' crops / slowest rank's wall time
         net.shard_across_ranks = False
@@ -646,16 +737,18 @@ def main():
                        "fp32": "exact f32 MFMA: the reference arithmetic up to re-association",
                        "bf16": "operands rounded to bf16: outside the <= 1e-3 tolerance (speed policy)"}[args.precision],
             "whole_net_tflops": round(fps * FLOP_PER_FRAME_T20 / 1e12, 2),
+        }
+        if args.full:
             # the reference pushes every interior frame through GMFlow's CNN encoder twice (KA:979-984); the engine runs it once
             # per frame (net.py:_gmflow_clip): ~33 GFLOP per frame of the reference count are not executed here
-            "whole_net_tflops_executed": round(fps * (FLOP_PER_FRAME_T20 - GMFLOW_DUPLICATE_FLOP_PER_FRAME) / 1e12, 2),
-            "peak_hbm_gb": None if FAKE else round(torch.cuda.max_memory_allocated() / 1e9, 1),
-            "x3_range_fallbacks": net.x3_fallbacks,
-            "roofline": None if FAKE else conv_roofline(net, x),
-        }
+            line["whole_net_tflops_executed"] = round(fps * (FLOP_PER_FRAME_T20 - GMFLOW_DUPLICATE_FLOP_PER_FRAME) / 1e12, 2)
+        line["peak_hbm_gb"] = None if FAKE else round(torch.cuda.max_memory_allocated() / 1e9, 1)
+        line["x3_range_fallbacks"] = net.x3_fallbacks
+        if args.full:
+            line["roofline"] = None if FAKE else conv_roofline(net, x)
         if FAKE:
             line["fake_engine"] = True          # KEEP_BENCH_FAKE_NET=1: plumbing only, not a measurement
-        else:
+        elif args.full:
             # ... and the 5 of 9 taps the phase form of the Upsample convolutions does not multiply (roofline.skipped_gflop_per_step)
             line["whole_net_tflops_executed"] = round(
                 line["whole_net_tflops_executed"] - line["roofline"]["skipped_gflop_per_step"] * 1e9 / (dt / args.steps) / 1e12, 2)
@@ -667,9 +760,11 @@ def main():
             line["broadcast"] = dict(kdist.collective_library(), pieces=bcast.get("pieces"), largest_piece_mb=round(bcast.get("largest_piece_bytes", 0) / 1e6, 1),
                                      verified_identical_on_all_ranks=bcast["verified"])
             line["frames_per_s_per_rank"] = per_rank
-            line["config5_one_video_per_gpu"] = cfg5
-        extras = world == 1 and not args.no_extras and not FAKE
+            if args.full:
+                line["config5_one_video_per_gpu"] = cfg5
+        extras = args.full and world == 1 and not args.no_extras and not FAKE
         if extras:
+            x16 = x[:B16].contiguous()
             # ---- the other policies on the same input, each compared with the exact-f32 result
             out16, aux_main = net(x16, return_aux=True)
             results = {args.precision: (out16, aux_main)}
@@ -751,7 +846,7 @@ def main():
             # ---- the same two configurations through the product's own sequence entry point
             line["end_to_end_product"] = {"config3_300_frames_720p_1_face": product_leg(net, 300, 720, 1280, 1),
                                           "config4_300_frames_1080p_3_faces": product_leg(net, 300, 1080, 1920, 3)}
-        if world == 1 and not args.no_cpu_baseline and not FAKE:
+        if args.full and world == 1 and not args.no_cpu_baseline and not FAKE:
             line["cpu_baseline"] = cpu_baseline(args.cpu_baseline_frames)
         print(json.dumps(line))
     if world > 1:

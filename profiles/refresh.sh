@@ -2,7 +2,7 @@
 # Round 6: every r06_* file below comes from ONE gpurun call = one box (bench line, kernel tables, PMC traffic, census, per-shape PMC rows):
 #   on the GPU box (tools/dev/run1.sh of that call):
 #     bash tools/profile_step.sh x3 48 r6p_x3_b48 ; cp gpurun_out/r6p_x3_b48/x3_b48_pmc.json profiles/r06_pmc_traffic.json   (bench.py reads it: roofline.traffic)
-#     python bench.py > gpurun_out/r6p_bench.json
+#     python bench.py --full > $G/r6p_bench.json
 #     KEEP_AMD_GRAPH=0 KEEP_AMD_OVERLAP_MAX_CLIPS=0 PMC_COUNTERS= bash tools/profile_step.sh x3 1 r6p_x3_b1
 #     python tools/dev/conv_census.py 48 conv_x3 > gpurun_out/r6p_census_b48.txt ; ... 48 halo > r6p_census_halo_b48.txt ; ... 1 '' > r6p_census_b1.txt
 #     bash tools/dev/pmc_shapes.sh r6p_pmc_shapes > gpurun_out/r6p_pmc_shapes.txt ; python tools/dev/x3_ceiling.py > gpurun_out/r6p_ceiling.txt

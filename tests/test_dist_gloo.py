@@ -292,7 +292,7 @@ def test_bench_eight_ranks_line_over_gloo_with_the_stand_in_engine():
     env = dict(os.environ, KEEP_BENCH_FAKE_NET='1', KEEP_BCAST_CHUNK_MB='1', OMP_NUM_THREADS='1')
     env.pop('KEEP_DIST_DEVICE', None)
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '1', '--clips', '2',
-                        '--no-extras', '--no-cpu-baseline'], capture_output=True, text=True, env=env, timeout=600, cwd=root)
+                        '--full', '--no-extras', '--no-cpu-baseline'], capture_output=True, text=True, env=env, timeout=600, cwd=root)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
     assert len(lines) == 1, p.stdout[-2000:]

@@ -887,7 +887,7 @@ def test_bench_multi_rank_line_shape(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, KEEP_DIST_DEVICE='0', HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get('HSA_ENABLE_IPC_MODE_LEGACY', '0'))
     p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '1', '--warmup', '1', '--clips', '2',
-                        '--no-extras', '--no-cpu-baseline'], capture_output=True, text=True, env=env, timeout=900, cwd=root)
+                        '--full', '--no-extras', '--no-cpu-baseline'], capture_output=True, text=True, env=env, timeout=900, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]
     assert len(lines) == 1, p.stdout[-2000:]
