@@ -65,6 +65,13 @@ __device__ __forceinline__ void attn_range_scale(float amax, float& s, float& in
   inv_s = __uint_as_float((unsigned)(e - 14) << 23);
 }
 
+// window-mode roll (GM/transformer.py:75-80): shift > 0 rolls by half a window on EACH axis, (wh/2, ww/2) -- the host accepts
+// shift in {0, wh/2} only, so `shift` is the on/off switch and the row shift; the column shift follows from the window width
+__device__ __forceinline__ void win_shift(const AttnP& p, int wh, int ww, int& sy, int& sx) {
+  sy = p.shift > 0 ? wh / 2 : 0;
+  sx = p.shift > 0 ? ww / 2 : 0;
+}
+
 // window-mode: token t of window-batch bw -> (image, pixel index)
 __device__ __forceinline__ void win_decode(const AttnP& p, int bw, int t, int rot, int& img, int& pix) {
   const int k2 = p.ksplit * p.ksplit;
@@ -72,11 +79,13 @@ __device__ __forceinline__ void win_decode(const AttnP& p, int bw, int t, int ro
   const int widx = bw - img * k2;
   const int wy = widx / p.ksplit, wx = widx - wy * p.ksplit;
   const int wh = p.img_h / p.ksplit, ww = p.img_w / p.ksplit;
+  int sy, sx;
+  win_shift(p, wh, ww, sy, sx);
   // t / ww without the ~40-instruction integer division (exact for t < 65536, enforced on the host): everything else in
   // this function is block-uniform and lands on the scalar unit
   const int ty = (int)(((float)t + 0.5f) * (1.0f / (float)ww)), tx = t - ty * ww;
-  int y = wy * wh + ty + p.shift;
-  int x = wx * ww + tx + p.shift;
+  int y = wy * wh + ty + sy;
+  int x = wx * ww + tx + sx;
   if (y >= p.img_h) y -= p.img_h;
   if (x >= p.img_w) x -= p.img_w;
   pix = y * p.img_w + x;
@@ -103,7 +112,7 @@ __device__ __forceinline__ int win_region(const AttnP& p, int bw, int t) {
 // Block-uniform part of the window index math (mode 2): every token of a block lives in one window of one image, so the
 // divisions by ksplit happen once per block; per token only t / ww remains (exact float reciprocal for t < 65536).
 struct WinCtx {
-  int img, img_kv, y0, x0, wh, ww;
+  int img, img_kv, y0, x0, wh, ww, sy, sx;
   float inv_ww;
 };
 __device__ __forceinline__ WinCtx win_ctx(const AttnP& p, int bw) {
@@ -116,6 +125,7 @@ __device__ __forceinline__ WinCtx win_ctx(const AttnP& p, int bw) {
   c.ww = p.img_w / p.ksplit;
   c.y0 = wy * c.wh;
   c.x0 = wx * c.ww;
+  win_shift(p, c.wh, c.ww, c.sy, c.sx);
   c.img_kv = c.img + p.kv_rot;
   if (c.img_kv >= p.n_img) c.img_kv -= p.n_img;
   c.inv_ww = 1.0f / (float)c.ww;
@@ -126,7 +136,7 @@ __device__ __forceinline__ void win_token(const AttnP& p, const WinCtx& c, int t
   const int ty = (int)(((float)t + 0.5f) * c.inv_ww);
   const int tx = t - ty * c.ww;
   const int yr = c.y0 + ty, xr = c.x0 + tx;
-  int y = yr + p.shift, x = xr + p.shift;
+  int y = yr + c.sy, x = xr + c.sx;
   if (y >= p.img_h) y -= p.img_h;
   if (x >= p.img_w) x -= p.img_w;
   pix = y * p.img_w + x;
@@ -2398,7 +2408,9 @@ extern "C" int32_t keep_attention(const keep_attention_args* a_in, void* stream)
     const int wh = a->img_h / a->ksplit, ww = a->img_w / a->ksplit;
     KEEP_REQUIRE(a->Lq == wh * ww && a->Lk == wh * ww, "keep_attention: window mode needs Lq == Lk == window size");
     KEEP_REQUIRE(a->n_img > 0 && a->B == a->n_img * a->ksplit * a->ksplit, "keep_attention: B != n_img*ksplit^2");
-    KEEP_REQUIRE(a->shift >= 0 && a->shift < wh && a->shift < ww, "keep_attention: bad shift");
+    // the region mask (win_region / win_token) assumes a roll by half a window: shift is 0 or wh/2 (the kernels then roll the
+    // columns by ww/2, GM/transformer.py:75-80)
+    KEEP_REQUIRE(a->shift == 0 || a->shift == wh / 2, "keep_attention: shift=%d must be 0 or img_h/ksplit/2 = %d", a->shift, wh / 2);
     KEEP_REQUIRE(a->kv_rot >= 0 && a->kv_rot < a->n_img, "keep_attention: bad kv_rot");
     KEEP_REQUIRE((long)a->img_h * a->img_w <= 65536, "keep_attention: window mode supports maps of at most 65536 tokens");
   }

@@ -226,8 +226,10 @@ int32_t keep_conv2d_plan(const keep_conv2d_args* a, keep_conv2d_plan_out* out);
  *   mode 1: sparse-causal keys (KA:704-716): batch b is frame f=b%T of a clip; key/value token t of the
  *           2*seg_len keys comes from frame 0 (t<seg_len) or frame max(f-1,0) (t>=seg_len) of the same clip.
  *   mode 2: (shifted) window attention on an img_h x img_w token grid cut into ksplit x ksplit windows
- *           (GM/transformer.py:46-105): batch = image*ksplit^2 + window, tokens are window-local, rolled by
- *           `shift`; shift>0 adds the -100 cross-region mask (GM/transformer.py:19-43).  Keys/values are read
+ *           (GM/transformer.py:46-105): batch = image*ksplit^2 + window, tokens are window-local.  `shift` is 0 or
+ *           wh/2 (wh = img_h/ksplit, ww = img_w/ksplit; anything else is refused); shift>0 rolls the grid by half a
+ *           window on each axis, (wh/2, ww/2) -- non-square windows included -- and adds the -100 cross-region
+ *           mask (GM/transformer.py:19-43,75-80).  Keys/values are read
  *           from image (image + kv_rot) % n_img  (the [f0;f1] vs [f1;f0] pairing, GM/transformer.py:301-314).
  */
 typedef struct {

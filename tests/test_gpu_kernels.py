@@ -369,7 +369,8 @@ def test_attention_packed_qkv_and_peaked_softmax():
     check(o.view(B, Lt, H, D), ref_attn(q, k, v, 1.0).permute(0, 2, 1, 3), what='packed/peaked')
 
 
-def test_attention_sparse_causal_mode():
+@pytest.mark.parametrize("mma", [L.MMA_F32, L.MMA_X3], ids=["f32", "x3"])
+def test_attention_sparse_causal_mode(mma):
     """KA:704-716: keys of frame f = [tokens of frame 0 ; tokens of frame max(f-1,0)]."""
     Bc, T, Lt, H, D = 2, 3, 64, 8, 48
     inner = H * D
@@ -378,7 +379,7 @@ def test_attention_sparse_causal_mode():
     o = torch.empty(Bc * T, Lt, inner, device='cuda')
     s3 = (Lt * 3 * inner, 3 * inner, D)
     ops.attention(qd, ops.offset(qd, inner), ops.offset(qd, 2 * inner), o, B=Bc * T, H=H, Lq=Lt, Lk=2 * Lt, D=D, Dv=D,
-                  scale=D ** -0.5, q_str=s3, k_str=s3, v_str=s3, o_str=(Lt * inner, inner, D), mode=1, T=T, seg_len=Lt)
+                  scale=D ** -0.5, q_str=s3, k_str=s3, v_str=s3, o_str=(Lt * inner, inner, D), mode=1, T=T, seg_len=Lt, mma=mma)
     q, k, v = qkv.chunk(3, dim=-1)
     former = torch.arange(T) - 1
     former[0] = 0
@@ -389,11 +390,12 @@ def test_attention_sparse_causal_mode():
 
     hs = lambda t: t.reshape(t.shape[0], t.shape[1], H, D).permute(0, 2, 1, 3)  # noqa: E731
     ref = ref_attn(hs(q), hs(gather(k)), hs(gather(v)), D ** -0.5).permute(0, 2, 1, 3).reshape(Bc * T, Lt, inner)
-    check(o, ref, what='sparse causal')
+    check(o, ref, what=f'sparse causal mma={mma}')
 
 
+@pytest.mark.parametrize("mma", [L.MMA_F32, L.MMA_X3], ids=["f32", "x3"])
 @pytest.mark.parametrize("T", [2, 3, 20])
-def test_attention_temporal_strided(T):
+def test_attention_temporal_strided(T, mma):
     """KA:671-680: batch = spatial token, tokens = frames, read in place from [(f d) c]."""
     Lt, H, D = 16, 8, 48
     inner = H * D
@@ -402,14 +404,15 @@ def test_attention_temporal_strided(T):
     o = torch.empty(T, Lt, inner, device='cuda')
     st = (3 * inner, Lt * 3 * inner, D)
     ops.attention(qd, ops.offset(qd, inner), ops.offset(qd, 2 * inner), o, B=Lt, H=H, Lq=T, Lk=T, D=D, Dv=D,
-                  scale=D ** -0.5, q_str=st, k_str=st, v_str=st, o_str=(inner, Lt * inner, D))
+                  scale=D ** -0.5, q_str=st, k_str=st, v_str=st, o_str=(inner, Lt * inner, D), mma=mma)
     q, k, v = (t.permute(1, 0, 2).reshape(Lt, T, H, D).permute(0, 2, 1, 3) for t in qkv.chunk(3, dim=-1))
     ref = ref_attn(q, k, v, D ** -0.5).permute(0, 2, 1, 3).reshape(Lt, T, inner).permute(1, 0, 2)
-    check(o, ref, what=f'temporal T={T}')
+    check(o, ref, what=f'temporal T={T} mma={mma}')
 
 
+@pytest.mark.parametrize("mma", [L.MMA_F32, L.MMA_X3], ids=["f32", "x3"])
 @pytest.mark.parametrize("shift", [0, 1])
-def test_attention_swin_windows(shift):
+def test_attention_swin_windows(shift, mma):
     """GM/transformer.py:46-105 incl. roll, 2x2 windows, -100 region mask and the [f0;f1]/[f1;f0] key swap."""
     P, h8, w8, C = 2, 8, 8, 128
     n_img, Lt = 2 * P, h8 * w8
@@ -418,11 +421,12 @@ def test_attention_swin_windows(shift):
     o = torch.empty(n_img, Lt, C, device='cuda')
     s = (Lt * C, C, 0)
     ops.attention(dev(q), dev(k), dev(v), o, B=n_img * 4, H=1, Lq=Lt // 4, Lk=Lt // 4, D=C, Dv=C, scale=1 / C ** 0.5,
-                  q_str=s, k_str=s, v_str=s, o_str=s, mode=2, img_h=h8, img_w=w8, ksplit=2, shift=sh, kv_rot=P, n_img=n_img)
+                  q_str=s, k_str=s, v_str=s, o_str=s, mode=2, img_h=h8, img_w=w8, ksplit=2, shift=sh, kv_rot=P, n_img=n_img,
+                  mma=mma)
     mask = O.shift_window_mask(h8, w8, h8 // 2, w8 // 2, h8 // 4, w8 // 4)
     kr, vr = torch.cat([k[P:], k[:P]]), torch.cat([v[P:], v[:P]])
     ref = O._window_attention(q, kr, vr, 2, bool(shift), h8, w8, mask)
-    check(o, ref, what=f'swin shift={sh}')
+    check(o, ref, what=f'swin shift={sh} mma={mma}')
 
 
 # ------------------------------------------------------------------------------------------------ small kernels

@@ -495,6 +495,25 @@ def test_plan_layernorm_epilogue_rules():
         assert rc == -2 and b'ln_gamma' in lib.keep_last_error(), (bad, rc, kernel)
 
 
+def test_attention_window_shift_is_zero_or_half_a_window():
+    """keep_attention (host-side C): the region mask and the per-axis roll (wh/2, ww/2, GM/transformer.py:75-80) assume half a
+    window, so a window-mode call with any other shift is refused with KEEP_EINVAL before anything launches."""
+    from comfyui_keep_amd.engine import hiplib
+    lib = ctypes.CDLL(hiplib.LIB_PATH)
+    lib.keep_attention.restype = ctypes.c_int32
+    lib.keep_last_error.restype = ctypes.c_char_p
+    buf = (ctypes.c_float * 64)()
+    ptr = (ctypes.addressof(buf) + 63) // 64 * 64
+    h, w, C = 40, 56, 128                        # windows 20 x 28: wh/2 = 10, ww/2 = 14
+    for bad in (1, 5, 14, 19, 20, -10):
+        s = (h * w * C, C, 0)
+        a = hiplib.AttnArgs(struct_size=ctypes.sizeof(hiplib.AttnArgs), q=ptr, k=ptr, v=ptr, o=ptr, q_bs=s[0], q_ts=s[1], k_bs=s[0],
+                            k_ts=s[1], v_bs=s[0], v_ts=s[1], o_bs=s[0], o_ts=s[1], B=8, H=1, Lq=560, Lk=560, D=C, Dv=C, scale=0.1,
+                            mode=2, img_h=h, img_w=w, ksplit=2, shift=bad, kv_rot=1, n_img=2, mma=hiplib.MMA_X3)
+        assert lib.keep_attention(ctypes.byref(a), None) == -1, bad
+        assert b'shift' in lib.keep_last_error(), (bad, lib.keep_last_error())
+
+
 def test_product_never_imports_oracle():
     pkg = os.path.join(ROOT, 'comfyui-keep_amd')
     for dirpath, _, files in os.walk(pkg):

@@ -78,6 +78,31 @@ def test_flow_warp():
     close(O.flow_warp(op_input('warp_img', (2, 3, 32, 32)), op_input('warp_flow', (2, 32, 32, 2), 6.0)), OPS['warp'], 1e-6)
 
 
+def test_window_attention_nonsquare_vs_reference_golden():
+    """tests/golden/gm_window_nonsquare.npz (oracle/make_golden_gmwin.py): the reference's single_head_split_window_attention +
+    generate_shift_window_attn_mask on 12x20 and 20x12 grids.  The shifted windows roll by (wh/2, ww/2), different per axis here:
+    pins O._window_attention (the GPU window cases' reference) where a square-grid fixture cannot tell the two shifts apart,
+    and shows that a roll by wh/2 on BOTH axes is caught."""
+    g = np.load(os.path.join(GOLDEN, 'gm_window_nonsquare.npz'))
+    splits = int(g['splits'])
+    for h, w in g['grids']:
+        h, w = int(h), int(w)
+        n = 2 * h * w * 16
+        q, k, v = (torch.from_numpy((synth.uniform_pm1(f'gmwin:{name}:{h}x{w}', n, 7) * 3.0).astype(np.float32).reshape(2, h * w, 16))
+                   for name in ('q', 'k', 'v'))
+        wh, ww = h // splits, w // splits
+        assert wh // 2 != ww // 2
+        mask = O.shift_window_mask(h, w, wh, ww, wh // 2, ww // 2)
+        for shift in (0, 1):
+            ref = g[f'out_{h}x{w}_shift{shift}']
+            close(O._window_attention(q, k, v, splits, bool(shift), h, w, mask), ref, 1e-6)
+        # negative control: the same mask with the columns rolled by wh/2 instead of ww/2 is far off the reference
+        d = wh // 2 - ww // 2
+        roll = lambda t, s: torch.roll(t.view(2, h, w, 16), shifts=s, dims=2).reshape(2, h * w, 16)  # noqa: E731
+        wrong = roll(O._window_attention(roll(q, -d), roll(k, -d), roll(v, -d), splits, True, h, w, mask), d)
+        assert np.abs(wrong.numpy() - g[f'out_{h}x{w}_shift1']).max() > 0.1
+
+
 def test_gmflow64(synth_weights):
     a = synth.synth_clip(T=2, B=1, size=64, seed=99)[0]
     close(O.gmflow_forward(a[1:2], a[0:1], synth_weights), OPS['gmflow64'])
