@@ -17,15 +17,9 @@
 
 #include "keep_common.h"
 
-// (dev A/B) cache policy of the x3 attention kernel's output rows: -DKEEP_NT_ATTN_O=1 = streaming stores
-#ifndef KEEP_NT_ATTN_O
-#define KEEP_NT_ATTN_O 0
-#endif
-#if KEEP_NT_ATTN_O
-#define KEEP_ATTN_O_STORE(ptr, val) __builtin_nontemporal_store((val), (ptr))
-#else
-#define KEEP_ATTN_O_STORE(ptr, val) (*(ptr) = (val))
-#endif
+// cache policy of the x3 attention kernel's output rows: default (nt stores measured 3 ms slower per step: the merge GEMM that follows
+// reads them back at once)
+static constexpr int KEEP_NT_ATTN_O = 0;
 
 
 struct AttnP {
@@ -43,9 +37,6 @@ struct AttnP {
   int img_h, img_w, ksplit, shift, kv_rot, n_img;
   int nslices;  // dv slices per head
   unsigned flags;  // keep_attention_args.flags (KEEP_ATTN_NO_*)
-#ifdef KEEP_X3_ABLATE
-  int abl;               // dev builds: phase ablation selector (KEEP_ATTN_EXP)
-#endif
   const _Float16* kv_pack;   // KEEP_MMA_X3: packed K / V^T tile images (attn_pack_kv_x3_kernel) or NULL
   const float* q_amax;   // KEEP_MMA_X3 range probes ([B] each) or NULL
   const float* k_amax;
@@ -625,11 +616,6 @@ typedef _Float16 af16x2 __attribute__((ext_vector_type(2)));
 // operations and 20 narrow LDS writes (the phase ablation: loads 55 %, commit 25 % of the unpacked kernel's time).
 template <int WAVES, int DVT, int NQ, bool PACKED = false>
 __global__ __launch_bounds__(64 * WAVES, ((WAVES == 4 && NQ != 16) ? 2 : 1)) void attn_x3_kernel(AttnP p) {
-#ifdef KEEP_X3_ABLATE
-  const int abl = p.abl;
-#else
-  constexpr int abl = 0;
-#endif
   constexpr bool QREG = NQ > 0;             // NQ 16-wide d steps of Q live in registers (NQ = 16: D <= 256, one block per CU)
   constexpr int NQA = QREG ? NQ : 1;
   extern __shared__ __attribute__((aligned(16))) _Float16 smemx[];
@@ -916,7 +902,7 @@ __global__ __launch_bounds__(64 * WAVES, ((WAVES == 4 && NQ != 16) ? 2 : 1)) voi
         stage_vt(kt);
       }
       __syncthreads();                               // tile kt visible in LDS
-      if (PF && kt + 1 < ntiles && abl != 5) {
+      if (PF && kt + 1 < ntiles) {
         if (PACKED) {
           pk_issue(kt + 1);                          // next tile's image flies during the MFMAs below
         } else {
@@ -926,9 +912,9 @@ __global__ __launch_bounds__(64 * WAVES, ((WAVES == 4 && NQ != 16) ? 2 : 1)) voi
       }
 #pragma unroll
       for (int d8 = 0; d8 < NQA; ++d8) {
-        if (d8 * 16 < DC && abl != 1) {
-          const af16x8 kh8 = *reinterpret_cast<const af16x8*>(kp + (abl == 6 ? 0 : d8 * 16));
-          const af16x8 kl8 = *reinterpret_cast<const af16x8*>(kp + DC + (abl == 6 ? 0 : d8 * 16));
+        if (d8 * 16 < DC) {
+          const af16x8 kh8 = *reinterpret_cast<const af16x8*>(kp + d8 * 16);
+          const af16x8 kl8 = *reinterpret_cast<const af16x8*>(kp + DC + d8 * 16);
           s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl8, qfh[QREG ? d8 : 0], s, 0, 0, 0);
           s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, qfl[QREG ? d8 : 0], s, 0, 0, 0);
           s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, qfh[QREG ? d8 : 0], s, 0, 0, 0);
@@ -991,7 +977,7 @@ __global__ __launch_bounds__(64 * WAVES, ((WAVES == 4 && NQ != 16) ? 2 : 1)) voi
     float lsum = 0.f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const float pv = abl == 3 ? s[r] - m_new : (PF ? __builtin_amdgcn_exp2f(s[r] - m_new) : expf(s[r] - m_new));
+      const float pv = PF ? __builtin_amdgcn_exp2f(s[r] - m_new) : expf(s[r] - m_new);
       s[r] = pv;
       lsum += pv;
     }
@@ -1021,8 +1007,7 @@ __global__ __launch_bounds__(64 * WAVES, ((WAVES == 4 && NQ != 16) ? 2 : 1)) voi
       }
 #pragma unroll
       for (int j = 0; j < DVT; ++j) {
-        if (abl == 2) continue;
-        const _Float16* vrow = Vt + ((abl == 6 ? 0 : j) * 32 + l31) * VP + (st * 2 + lhi) * 8;
+        const _Float16* vrow = Vt + (j * 32 + l31) * VP + (st * 2 + lhi) * 8;
         const af16x8 vh8 = *reinterpret_cast<const af16x8*>(vrow), vl8 = *reinterpret_cast<const af16x8*>(vrow + 32);
         o[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pl, vh8, o[j], 0, 0, 0);
         o[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph, vl8, o[j], 0, 0, 0);
@@ -1031,13 +1016,11 @@ __global__ __launch_bounds__(64 * WAVES, ((WAVES == 4 && NQ != 16) ? 2 : 1)) voi
     }
     if (PF && kt + 1 < ntiles) {
       __syncthreads();                               // every wave is done reading tile kt
-      if (abl != 4) {
-        if (PACKED) {
-          pk_commit();
-        } else {
-          k_commit();
-          v_commit();
-        }
+      if (PACKED) {
+        pk_commit();
+      } else {
+        k_commit();
+        v_commit();
       }
     }
   }
@@ -1053,7 +1036,11 @@ __global__ __launch_bounds__(64 * WAVES, ((WAVES == 4 && NQ != 16) ? 2 : 1)) voi
 #pragma unroll
       for (int j = 0; j < DVT; ++j) {
         const int dv = dv0 + j * 32 + l31;
-        if (dv < p.Dv) KEEP_ATTN_O_STORE(p.o + base + dv, o[j][r] * il);
+        if (dv >= p.Dv) continue;
+        if (KEEP_NT_ATTN_O)
+          __builtin_nontemporal_store(o[j][r] * il, p.o + base + dv);
+        else
+          p.o[base + dv] = o[j][r] * il;
       }
     }
   }
@@ -1152,9 +1139,6 @@ static int launch_attn_x3_packed(const AttnP& p, hipStream_t st) {
     attr_set = true;
   }
   dim3 grid(cdiv(p.Lq, 128), p.H * p.nslices, p.B);
-#ifdef KEEP_X3_ABLATE
-  const_cast<AttnP&>(p).abl = KEEP_DEV_ENV("KEEP_ATTN_EXP") ? atoi(KEEP_DEV_ENV("KEEP_ATTN_EXP")) : 0;
-#endif
   hipLaunchKernelGGL((attn_x3_kernel<4, DVT, NQ, true>), grid, dim3(256), lds, st, p);
   KEEP_LAUNCH_CHECK("keep_attention(x3 packed)");
   return KEEP_OK;
@@ -1181,9 +1165,6 @@ static int launch_attn_x3_t(const AttnP& p, hipStream_t st) {
     attr_set = true;
   }
   dim3 grid(cdiv(p.Lq, WAVES * 32), p.H * p.nslices, p.B);
-#ifdef KEEP_X3_ABLATE
-  const_cast<AttnP&>(p).abl = KEEP_DEV_ENV("KEEP_ATTN_EXP") ? atoi(KEEP_DEV_ENV("KEEP_ATTN_EXP")) : 0;
-#endif
   hipLaunchKernelGGL((attn_x3_kernel<WAVES, DVT, NQ>), grid, dim3(64 * WAVES), lds, st, p);
   KEEP_LAUNCH_CHECK("keep_attention(x3)");
   return KEEP_OK;

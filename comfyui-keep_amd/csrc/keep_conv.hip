@@ -1992,7 +1992,7 @@ static int plan_conv(const keep_conv2d_args* a, ConvP& p, ConvPlan& pl) {
     return KEEP_OK;
   }
   // ---- bf16 policy: LDS-halo kernel (persistent v3; v1 when the prologue is fused into its staging step)
-  static const int halo_ver = KEEP_DEV_ENV("KEEP_HALO_VER") ? atoi(KEEP_DEV_ENV("KEEP_HALO_VER")) : 3;
+  constexpr int halo_ver = 3;
   const bool halo_geom = mma == KEEP_MMA_BF16 && is33s1 && (a->Cin % 32 == 0) && (a->Cout % 32 == 0) && tileable && same_size &&
                          (a->in_ld % 8 == 0) && ((uintptr_t)a->in % 16 == 0) && epi_al;
   if (halo_geom) {

@@ -69,12 +69,7 @@ __device__ __forceinline__ float xor32_sum(float x) {
 //   and chunk) overlaps the other's 108 MFMAs per wave.
 #define XPITCH 40   // fp16 elements per LDS row: 16 hi + 16 lo + 8 pad (80 B)
 
-// EXP (dev builds with -DKEEP_X3_ABLATE only, 0 in the product): phase ablations -- 1: no LDS fragment reads in the MFMA loop,
-// 2: no MFMAs, 3: no staging (LDS keeps stale data), 4: no global stores in the epilogue, 5: no operand fetch,
-// 6: start stagger between the two blocks of a CU, 7: library expf + IEEE division in the swish prologue, 8: s_setprio(1)
-// around the MFMA loop, 10: affine-only prologue (no transcendentals), 11: no epilogue, 12: weight DMA not waited for, 13: no
-// weight DMA, 14: halo rows computed but not written to LDS, 15: weight DMA from one 1 KB source (L1 hits), 16: no weight DMA and the
-// B fragments read from the halo rows, 17: the product kernel with the block cycle counter (KEEP_X3_CYC=1 prints it for every variant).
+// Phase ablations and the s_memtime phase timeline of this kernel: DESIGN 5.3.
 // WDMA: the 9 x 64 pre-split weight rows of a chunk go from L2 straight into LDS (buffer_load_dwordx4 ... lds, 1 KB per wave
 // instruction, no VGPR round trip, no ds_write): rows at a 64-byte pitch, the 16-byte pieces of a row XOR-swizzled by
 // (row >> 2) & 3 through the SOURCE address of each lane (an LDS-DMA destination is lane-linear), which keeps the B-fragment
@@ -87,7 +82,7 @@ __device__ __forceinline__ float xor32_sum(float x) {
 //   ([phase][Cout][9 taps][Cin/16][hi16|lo16], unused taps zero and never fetched); an item is (source tile, phase, cout block), its
 //   MFMA loop is compiled per phase (static tap list), its epilogue scatters to the stride-2 output pixels.  Tiles, halo and
 //   addressing are those of a plain 3x3 convolution on the source (p.upsample = 0, p.Ho / p.Wo = the OUTPUT extent).
-template <int TW, int PRO, bool SIMPLE_EPI, int EXP = 0, bool FASTACT = true, bool WDMA = false, bool UP2 = false>
+template <int TW, int PRO, bool SIMPLE_EPI, bool FASTACT = true, bool WDMA = false, bool UP2 = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int tiles_x, int tiles_y, int ncb, int n_items) {
   static_assert(!UP2 || (TW == 32 && WDMA && SIMPLE_EPI && PRO == KEEP_PRO_NONE), "UP2: wide tiles, DMA weights, simple epilogue, no prologue");
   constexpr int HALO_TH = 256 / TW, HALO_W = TW + 2, HALO_PIX = (HALO_TH + 2) * HALO_W;
@@ -164,19 +159,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
     }
   };
 
-  unsigned long long tacc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t0 = 0;
-#define KEEP_T(IDX)                                                   \
-  if (EXP == 9) {                                                     \
-    const unsigned long long t1 = __builtin_amdgcn_s_memtime();       \
-    tacc[IDX] += t1 - t0;                                             \
-    t0 = t1;                                                          \
-  }
   float4 hreg[HALO_IT];
   uint4 wr0, wr1, wr2, wr3, wr4, wr5, wr6, wr7, wr8;
   float4 sc4 = make_float4(1.f, 1.f, 1.f, 1.f), sh4 = make_float4(0.f, 0.f, 0.f, 0.f);
   auto fetch = [&](int ch) {
     const int c0 = ch << 4;
-    if (EXP == 5 && ch > 0) return;
 #pragma unroll
     for (int k = 0; k < HALO_IT; ++k) {
       const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, h_voff[k], c0 * 4, 0);
@@ -199,33 +186,22 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
   };
   int up_par = 0, up_mask = 0x1ff;       // UP2: phase (py * 2 + px) and tap set of the CURRENT item
   auto stage = [&]() {
-    constexpr bool FAST = FASTACT && EXP != 7;
-    if (EXP == 3) return;
-    if (WDMA && !(EXP == 5 && fetched_ch > 0) && EXP != 13 && EXP != 16) {   // weights of the chunk being staged: L2 -> LDS, in flight under the halo's VALU work below
+    if (WDMA) {      // weights of the chunk being staged: L2 -> LDS, in flight under the halo's VALU work below
       const int c0 = fetched_ch << 4;
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
         const int q = __builtin_amdgcn_readfirstlane(wave) * 9 + t;            // wave-uniform (M0 / soffset operands)
         if (UP2 && !((up_mask >> (q >> 2)) & 1)) continue;                      // a tap this phase does not use: never fetched
-        if (EXP == 15)      // every piece from the same 1 KB of the weight tensor: L1 hits, no L2 traffic
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (__attribute__((address_space(3))) void*)(wdma_base + q * 1024), 16,
-                                                   lane * 16, 0, 0, 0);
-        else
         __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (__attribute__((address_space(3))) void*)(wdma_base + q * 1024), 16,
                                                  dma_voff[t & 3], ((q >> 2) * p.Cin + c0) * 4, 0, 0);
       }
-    }
-    KEEP_T(8)
-    if (EXP == 9) {
-      asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-      KEEP_T(9)
     }
     // GroupNorm affine + activation + split of this thread's 16-byte pieces, two values per instruction where the ISA has a packed
     // form (v_pk_fma / v_pk_add / v_pk_mul / v_cvt_pk_f16_f32): VALU instructions do not overlap the matrix pipe of their SIMD
     // (tools/dev/coissue_probe.hip), so every one of them is paid in full.  Fast swish: x * rcp(1 + exp2(x * s' + t')) with the
     // -log2(e) folded into a second affine (s', t') once per chunk.
     const f32x2 sc01 = {sc4.x, sc4.y}, sc23 = {sc4.z, sc4.w}, sh01 = {sh4.x, sh4.y}, sh23 = {sh4.z, sh4.w};
-    constexpr bool FOLD = PRO == KEEP_PRO_SWISH && FAST && EXP != 10;
+    constexpr bool FOLD = PRO == KEEP_PRO_SWISH && FASTACT;
     const f32x2 nsc01 = sc01 * -1.4426950408889634f, nsc23 = sc23 * -1.4426950408889634f;
     const f32x2 nsh01 = sh01 * -1.4426950408889634f, nsh23 = sh23 * -1.4426950408889634f;
 #pragma unroll
@@ -247,12 +223,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
               const f32x2 r23 = {__builtin_amdgcn_rcpf(d23.x), __builtin_amdgcn_rcpf(d23.y)};
               v01 = y01 * r01;
               v23 = y23 * r23;
-            } else if (EXP == 10) {
-              v01 = y01;
-              v23 = y23;
             } else {
-              v01 = f32x2{pro_x3<PRO, FAST>(y01.x), pro_x3<PRO, FAST>(y01.y)};
-              v23 = f32x2{pro_x3<PRO, FAST>(y23.x), pro_x3<PRO, FAST>(y23.y)};
+              v01 = f32x2{pro_x3<PRO, FASTACT>(y01.x), pro_x3<PRO, FASTACT>(y01.y)};
+              v23 = f32x2{pro_x3<PRO, FASTACT>(y23.x), pro_x3<PRO, FASTACT>(y23.y)};
             }
           }
           if (PRO == KEEP_PRO_NONE && p.in_amax) {     // activated inputs are bounded: the host never probes them
@@ -263,10 +236,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
           const f16x2 l01 = __builtin_convertvector(v01 - __builtin_convertvector(h01, f32x2), f16x2);
           const f16x2 l23 = __builtin_convertvector(v23 - __builtin_convertvector(h23, f32x2), f16x2);
           const f16x4 hi = {h01.x, h01.y, h23.x, h23.y}, lo = {l01.x, l01.y, l23.x, l23.y};
-          if (EXP != 14 || (float)hi[0] + (float)lo[1] + (float)hi[2] + (float)lo[3] == 1.2345e-30f) {
-            *reinterpret_cast<f16x4*>(dst) = hi;
-            *reinterpret_cast<f16x4*>(dst + 16) = lo;
-          }
+          *reinterpret_cast<f16x4*>(dst) = hi;
+          *reinterpret_cast<f16x4*>(dst + 16) = lo;
         } else {      // zero padding applies to the normalised + activated tensor
           const f16x4 zero = {(_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
           *reinterpret_cast<f16x4*>(dst) = zero;
@@ -277,10 +248,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
 #define KEEP_WSTOREX(TAP, R) *reinterpret_cast<uint4*>(&Ws[((TAP) * 64 + (tid >> 2)) * XPITCH + g * 8]) = R;
     if (!WDMA) {
       KEEP_TAPS(KEEP_WSTOREX)
-    } else if (EXP != 12 && EXP != 13 && EXP != 16) {
-      KEEP_T(0)
+    } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's DMA pieces have landed (the barrier publishes them)
-      KEEP_T(10)
     }
 #undef KEEP_WSTOREX
   };
@@ -292,63 +261,37 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
   auto mma_m = [&](auto mask_c) {
     constexpr int MASK = decltype(mask_c)::value;      // taps of this instantiation (bit kh * 3 + kw)
     f16x8 ah[2], al[2], bh[2], bl[2];
-    if (EXP == 1) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        ah[i] = *reinterpret_cast<const f16x8*>(&Hs[a_base + i * XPITCH]);
-        al[i] = *reinterpret_cast<const f16x8*>(&Hs[a_base + i * XPITCH + 16]);
-        bh[i] = *reinterpret_cast<const f16x8*>(&Ws[b_base + i * 32 * XPITCH]);
-        bl[i] = *reinterpret_cast<const f16x8*>(&Ws[b_base + i * 32 * XPITCH + 16]);
-      }
-    }
-    if (EXP == 8) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int kh = 0; kh < 3; ++kh) {
 #pragma unroll
       for (int kw = 0; kw < 3; ++kw) {
         if (!((MASK >> (kh * 3 + kw)) & 1)) continue;
-        if (EXP != 1) {
 #pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            const _Float16* src = &Hs[a_base + ((i * RPT + kh) * HALO_W + kw) * XPITCH];
-            ah[i] = *reinterpret_cast<const f16x8*>(src);
-            al[i] = *reinterpret_cast<const f16x8*>(src + 16);
+        for (int i = 0; i < 2; ++i) {
+          const _Float16* src = &Hs[a_base + ((i * RPT + kh) * HALO_W + kw) * XPITCH];
+          ah[i] = *reinterpret_cast<const f16x8*>(src);
+          al[i] = *reinterpret_cast<const f16x8*>(src + 16);
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          if (WDMA) {
+            const int o = b_base + ((kh * 3 + kw) * 64 + j * 32) * 32;
+            bh[j] = *reinterpret_cast<const f16x8*>(&Ws[o]);
+            bl[j] = *reinterpret_cast<const f16x8*>(&Ws[o ^ 16]);                 // lo piece: logical + 2 -> physical slot ^ 2
+          } else {
+            const _Float16* src = &Ws[b_base + ((kh * 3 + kw) * 64 + j * 32) * XPITCH];
+            bh[j] = *reinterpret_cast<const f16x8*>(src);
+            bl[j] = *reinterpret_cast<const f16x8*>(src + 16);
           }
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
-            if (WDMA) {
-              const int o = b_base + ((kh * 3 + kw) * 64 + j * 32) * 32;
-              if (EXP == 16) {      // no weight DMA; the B fragments come from the (changing) halo rows
-                bh[j] = *reinterpret_cast<const f16x8*>(&Hs[o & 8191]);
-                bl[j] = *reinterpret_cast<const f16x8*>(&Hs[(o ^ 16) & 8191]);
-                continue;
-              }
-              bh[j] = *reinterpret_cast<const f16x8*>(&Ws[o]);
-              bl[j] = *reinterpret_cast<const f16x8*>(&Ws[o ^ 16]);                 // lo piece: logical + 2 -> physical slot ^ 2
-            } else {
-              const _Float16* src = &Ws[b_base + ((kh * 3 + kw) * 64 + j * 32) * XPITCH];
-              bh[j] = *reinterpret_cast<const f16x8*>(src);
-              bl[j] = *reinterpret_cast<const f16x8*>(src + 16);
-            }
+            MMA_X3(acc[i][j], ah[i], al[i], bh[j], bl[j])
           }
-        }
-        if (EXP == 2) {      // keep the reads alive without the matrix pipe
-#pragma unroll
-          for (int i = 0; i < 2; ++i) {
-            acc[i][0][0] += (float)ah[i][0] + (float)al[i][0];
-            acc[i][1][0] += (float)bh[i][0] + (float)bl[i][0];
-          }
-        } else {
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-              MMA_X3(acc[i][j], ah[i], al[i], bh[j], bl[j])
-            }
-        }
       }
     }
-    if (EXP == 8) __builtin_amdgcn_s_setprio(0);
   };
   auto mma = [&]() {
     if (!UP2) {
@@ -376,7 +319,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
     constexpr bool HAS_RES = decltype(res_c)::value;
     constexpr int EP = 68;
     float* et = reinterpret_cast<float*>(lds_raw) + wave * 64 * EP;
-    if (EXP == 11 && acc[0][0][0] + acc[1][1][3] + acc[0][1][7] + acc[1][0][9] != 1.2345e-30f) return 0.f;
     const float asc = p.acc_scale * item_inv;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -386,7 +328,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
         for (int r = 0; r < 16; ++r)
           et[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi) * EP + j * 32 + l31] = acc[i][j][r];      // raw: asc (a power of two) rides in the bias FMA below
     __builtin_amdgcn_s_waitcnt(0xc07f);
-    KEEP_T(11)
     const int c4 = (lane & 15) * 4, prow = lane >> 4;
     const int e_par = UP2 ? (it.n0 >> 6) / ncb_real : 0;
     const int e_n0 = UP2 ? it.n0 - e_par * p.Cout : it.n0;                    // real first cout of the block
@@ -466,11 +407,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
           for (int q = 0; q < 4; ++q) e[q] += rr[q];
         }
       }
-      if (EXP != 4 || e[0] == 1.2345e-30f) {
-        u32x4 o;
-        o.x = __float_as_uint(e[0]); o.y = __float_as_uint(e[1]); o.z = __float_as_uint(e[2]); o.w = __float_as_uint(e[3]);
-        __builtin_amdgcn_raw_buffer_store_b128(o, out_rsrc, v_out, dpix * p.out_ld * 4, KEEP_ST_AUX_HALO);
-      }
+      u32x4 o;
+      o.x = __float_as_uint(e[0]); o.y = __float_as_uint(e[1]); o.z = __float_as_uint(e[2]); o.w = __float_as_uint(e[3]);
+      __builtin_amdgcn_raw_buffer_store_b128(o, out_rsrc, v_out, dpix * p.out_ld * 4, KEEP_ST_AUX_HALO);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         s4[q] += e[q];
@@ -515,15 +454,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
   float amax_run = 0.f;
   int item = blockIdx.x;
   if (item >= n_items) return;
-  if (EXP == 6 && blockIdx.x >= gridDim.x / 2) __builtin_amdgcn_s_sleep(54);     // start stagger of the second block per CU
-  // EXP == 9: phase timeline (s_memtime) of wave 0, summed over blocks into p.ws as u64[8]:
-  // 0 stage, 1 wait at the barrier after staging, 2 fetch issue, 3 mma, 4 wait at the barrier after mma, 5 item set-up, 6 epilogue
-  const unsigned long long cyc0 = EXP != 0 ? __builtin_amdgcn_s_memtime() : 0ull;           // dev builds: shader cycles and
-  const unsigned long long rtc0 = EXP != 0 ? __builtin_amdgcn_s_memrealtime() : 0ull;       // 100 MHz ticks of the whole block
   HaloItem cur = halo_decode<TW, 4>(p, item, items_per_z, tiles_x, tiles_y, ncb);
   setup(cur);
   if (cur.ch_begin < cur.ch_end) fetch(cur.ch_begin);
-  if (EXP == 9) t0 = __builtin_amdgcn_s_memtime();
   while (true) {
     const bool valid = cur.ch_begin < cur.ch_end;
     if (p.in_amax) x3_range_scale(amax_raw, in_s, in_inv);
@@ -531,14 +464,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
       up_par = __builtin_amdgcn_readfirstlane((cur.n0 >> 6) / ncb_real);
       up_mask = up_par == 0 ? 0x01b : up_par == 1 ? 0x036 : up_par == 2 ? 0x0d8 : 0x1b0;
     }
-    if (EXP == 9) {
-      __builtin_amdgcn_s_waitcnt(0x0f70);      // vmcnt(0): operand loads landed
-      KEEP_T(7)
-    }
     if (valid) stage();
-    KEEP_T(0)
     __syncthreads();
-    KEEP_T(1)
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -548,20 +475,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
     for (int ch = cur.ch_begin; ch < cur.ch_end; ++ch) {
       const bool more = ch + 1 < cur.ch_end;
       if (more) fetch(ch + 1);
-      KEEP_T(2)
       mma();
-      KEEP_T(3)
       __syncthreads();
-      KEEP_T(4)
       if (more) {
-        if (EXP == 9) {
-          __builtin_amdgcn_s_waitcnt(0x0f70);
-          KEEP_T(7)
-        }
         stage();
-        KEEP_T(0)
         __syncthreads();
-        KEEP_T(1)
       }
     }
     const int next_item = item + gridDim.x;
@@ -574,7 +492,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
       setup(nxt);
       if (nxt.ch_begin < nxt.ch_end) fetch(nxt.ch_begin);     // in flight during the epilogue below
     }
-    KEEP_T(5)
     const float amx = p.res ? epilogue_t(cur, cur_inv, cur_bias, std::true_type{}) : epilogue_t(cur, cur_inv, cur_bias, std::false_type{});
     if (p.out_amax) {       // max|out| of the image: a wave only goes to memory when it holds a value above everything it has committed
       if (cur.n != amax_n) { // (or seen) for this image -- the per-item "read the running maximum, skip if not larger" test was a dependent
@@ -595,30 +512,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
         amax_run = fmaxf(amax_run, __uint_as_float(seen));
       }
     }
-    KEEP_T(6)
     if (!has_next) break;
     __syncthreads();
-    KEEP_T(4)
     item = next_item;
     cur = nxt;
   }
-  if (EXP != 0 && tid == 0) {
-    unsigned long long* dst = reinterpret_cast<unsigned long long*>(p.ws);
-    atomicAdd(dst + 13, __builtin_amdgcn_s_memtime() - cyc0);
-    atomicAdd(dst + 14, __builtin_amdgcn_s_memrealtime() - rtc0);
-    atomicAdd(dst + 15, 1ull);
-    if (blockIdx.x < 1024) {          // per-block start / end (100 MHz ticks) behind the 16 sums
-      dst[16 + blockIdx.x * 2] = rtc0;
-      dst[17 + blockIdx.x * 2] = __builtin_amdgcn_s_memrealtime();
-    }
-  }
-  if (EXP == 9 && tid == 0) {
-    unsigned long long* dst = reinterpret_cast<unsigned long long*>(p.ws);
-#pragma unroll
-    for (int q = 0; q < 12; ++q) atomicAdd(dst + q, tacc[q]);
-    atomicAdd(dst + 12, 1ull);
-  }
-#undef KEEP_T
 }
 
 // ------------------------------------------------------------------------------------------------ gather GEMM, split fp16
@@ -787,9 +685,7 @@ __device__ __forceinline__ void x3_gather_epilogue(const ConvP& p, f32x16 (&acc)
 
 #define XBK 32
 #define XP (2 * XBK + 8)
-#ifndef XG_ABL
-#define XG_ABL 0      // dev (tools/dev/README.md): 1 no operand split, 2 no output stores, 3 no MFMAs, 4 no A loads, 5 no B loads
-#endif
+// (Phase ablations of this kernel: DESIGN 5.4 -- its K loop is bound by the L2 -> CU operand traffic, not by MFMAs or staging VALU.)
 
 // ONE: 1x1 stride-1 unpadded convolution == a row-major GEMM: the A rows are fetched with block-relative buffer loads (rows
 // beyond M read zeros through the descriptor's range check), no im2col index arithmetic.
@@ -921,11 +817,6 @@ __global__ __launch_bounds__(256) void conv_x3_kernel(ConvP p) {
 #pragma unroll
       for (int it = 0; it < A_IT; ++it) {
         R.a_ok[it] = ca < p.Cin;             // rows beyond M: zeros from the range check
-        if (XG_ABL == 4) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) R.a_raw[it][j] = (float)(j + s);
-          continue;
-        }
         const bool second = p.in2 && c0 >= p.cin1;                      // wave-uniform
         u32x4 v0, v1;
         if (KEEP_LD_AUX_GEMM_A1 != 0 && BN >= 128 && p.Cout <= BN && !p.in2) {      // one column block: every A row is read exactly once
@@ -961,7 +852,6 @@ __global__ __launch_bounds__(256) void conv_x3_kernel(ConvP p) {
     const bool cb_ok = c0 + (b_pc >> 2) * 16 < p.Cin;
 #pragma unroll
     for (int it = 0; it < B_IT; ++it) {
-      if (XG_ABL == 5) { R.b_raw[it] = make_uint4(s, it, s, it); continue; }
       const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, cb_ok ? b_voff[it] : (int)0x80000000, (tap * p.Cin + c0) * 4, 0);
       R.b_raw[it] = make_uint4(v.x, v.y, v.z, v.w);
     }
@@ -990,10 +880,6 @@ __global__ __launch_bounds__(256) void conv_x3_kernel(ConvP p) {
             for (int j = 0; j < 8; ++j) v[j] = p.fast ? pro_apply_x3(v[j], p.pro_act) : pro_apply(v[j], p.pro_act);
           }
         }
-        if (XG_ABL == 1 && PLAIN && ONE) {
-          *reinterpret_cast<float4*>(&hi) = make_float4(v[0], v[1], v[2], v[3]);
-          *reinterpret_cast<float4*>(&lo) = make_float4(v[4], v[5], v[6], v[7]);
-        } else
 #pragma unroll
         for (int j = 0; j < 8; j += 2) {      // two values per instruction: v_pk_mul, v_cvt_pk_f16_f32, v_pk_add (VALU is paid in full: coissue_probe)
           const f32x2 vs = f32x2{v[j], v[j + 1]} * a_s[it];
@@ -1029,7 +915,6 @@ __global__ __launch_bounds__(256) void conv_x3_kernel(ConvP p) {
   const int b_f0 = (wn * TN * 32 + l31) * XP + lhi * 8;
 
   auto mma_step = [&](int buf, bool zc = false) {
-    if (XG_ABL == 3) return;
     const _Float16* Ab = As[buf];
     const _Float16* Bb = Bs[buf];
 #pragma unroll
@@ -1133,8 +1018,6 @@ __global__ __launch_bounds__(256) void conv_x3_kernel(ConvP p) {
         for (int j = 0; j < TN; ++j) acc[i][j] = tot[KSL ? i : 0][KSL ? j : 0];
     }
   }
-  if (XG_ABL == 2 && acc[0][0][0] != 1234.5f) return;
-  if (XG_ABL == 3) acc[0][0][0] = (float)As[0][threadIdx.x];
   const float asc = p.acc_scale;
   if (p.in_amax) {          // undo the per-image range scale: accumulator register r of tile i holds output row ...
 #pragma unroll
@@ -1463,7 +1346,7 @@ int keep_conv2d_x3_halo(const keep_conv2d_args* a, ConvP& p, hipStream_t st) {
     p.upsample = 0;                                    // the kernel addresses the source like a plain 3x3 convolution
     p.split_k = 1;
     dim3 grid(n_items < 2 * n_cu ? n_items : 2 * n_cu), block(256);
-    hipLaunchKernelGGL((conv3x3_halo_x3_kernel<32, KEEP_PRO_NONE, true, 0, true, true, true>), grid, block, 0, st, p, tx, ty, ncbv, n_items);
+    hipLaunchKernelGGL((conv3x3_halo_x3_kernel<32, KEEP_PRO_NONE, true, true, true, true>), grid, block, 0, st, p, tx, ty, ncbv, n_items);
     KEEP_LAUNCH_CHECK("keep_conv2d(halo x3, x2 phases)");
     return KEEP_OK;
   }
@@ -1478,96 +1361,20 @@ int keep_conv2d_x3_halo(const keep_conv2d_args* a, ConvP& p, hipStream_t st) {
   const int tiles_x = a->Wo / tw, tiles_y = a->Ho / th, ncb = (a->Cout + 63) / 64;
   const int n_items = a->N * tiles_x * tiles_y * ncb * p.split_k;
   const int n_cu = x3_num_cu();
-  const int per_cu = KEEP_DEV_ENV("KEEP_X3_BLOCKS_PER_CU") ? atoi(KEEP_DEV_ENV("KEEP_X3_BLOCKS_PER_CU")) : 2;      // dev: occupancy scaling probe
-  dim3 grid(n_items < per_cu * n_cu ? n_items : per_cu * n_cu), block(256);
+  dim3 grid(n_items < 2 * n_cu ? n_items : 2 * n_cu), block(256);      // 2 blocks per CU (one per CU measured: DESIGN 5.3, round 3)
   const bool simple = p.split_k == 1 && !a->aux && a->epi_act == KEEP_ACT_NONE;
-  // pipelined single-block-per-CU kernel: wide tiles, no split-K, at least two work items per CU
-#ifdef KEEP_X3_ABLATE
-  if (KEEP_DEV_ENV("KEEP_X3_EXP") && wide && simple && (a->pro_act == KEEP_PRO_SWISH || a->pro_act == KEEP_PRO_NONE)) {
-    const int ex = atoi(KEEP_DEV_ENV("KEEP_X3_EXP"));
-static unsigned long long* dbg = nullptr;
-    if (!dbg) (void)hipMalloc(&dbg, 128 + 1024 * 16);
-    const bool cyc = KEEP_DEV_ENV("KEEP_X3_CYC") != nullptr;
-    if (cyc) (void)hipMemsetAsync(dbg, 0, 128, st);
-    ConvP q = p;
-    q.ws = reinterpret_cast<float*>(dbg);
-    auto report = [&](int e) {      // shader cycles and 100 MHz ticks per block -> the effective shader clock of this variant
-      if (!cyc) return;
-      unsigned long long h[16];
-      (void)hipStreamSynchronize(st);
-      (void)hipMemcpy(h, dbg, 128, hipMemcpyDeviceToHost);
-      const double nb = (double)h[15];
-      fprintf(stderr, "[x3 cycles] exp %d  blocks %.0f  cycles/block %.0f  us/block %.1f  clock %.0f MHz\n", e, nb, h[13] / nb,
-              h[14] / nb / 100.0, (double)h[13] / ((double)h[14] / 100.0));
-      static unsigned long long se[2048];
-      const int nblk = (int)grid.x < 1024 ? (int)grid.x : 1024;
-      (void)hipMemcpy(se, dbg + 16, nblk * 16, hipMemcpyDeviceToHost);
-      unsigned long long t_min = ~0ull, t_max = 0;
-      for (int b = 0; b < nblk; ++b) {
-        if (se[2 * b] < t_min) t_min = se[2 * b];
-        if (se[2 * b + 1] > t_max) t_max = se[2 * b + 1];
-      }
-      double dur_x[8] = {0}, st_x[8] = {0}, en_x[8] = {0}, dmin = 1e30, dmax = 0;
-      int cnt_x[8] = {0};
-      for (int b = 0; b < nblk; ++b) {
-        const double d = (se[2 * b + 1] - se[2 * b]) / 100.0;
-        dur_x[b & 7] += d; st_x[b & 7] += (se[2 * b] - t_min) / 100.0; en_x[b & 7] += (se[2 * b + 1] - t_min) / 100.0; cnt_x[b & 7]++;
-        if (d < dmin) dmin = d;
-        if (d > dmax) dmax = d;
-      }
-      fprintf(stderr, "[x3 blocks] span %.1f us  block life min %.1f max %.1f us | per XCD (start, life, end):", (t_max - t_min) / 100.0, dmin, dmax);
-      for (int x = 0; x < 8; ++x) fprintf(stderr, "  %.0f/%.0f/%.0f", st_x[x] / cnt_x[x], dur_x[x] / cnt_x[x], en_x[x] / cnt_x[x]);
-      fprintf(stderr, "\n");
-    };
-#define KEEP_LAUNCH_ABL(E)                                                                                                         \
-  if (ex == E) {                                                                                                                   \
-    if (a->pro_act == KEEP_PRO_SWISH)                                                                                              \
-      hipLaunchKernelGGL((conv3x3_halo_x3_kernel<32, KEEP_PRO_SWISH, true, E, true, true>), grid, block, 0, st, q, tiles_x, tiles_y, ncb, n_items); \
-    else                                                                                                                           \
-      hipLaunchKernelGGL((conv3x3_halo_x3_kernel<32, KEEP_PRO_NONE, true, E, true, true>), grid, block, 0, st, q, tiles_x, tiles_y, ncb, n_items);  \
-    KEEP_LAUNCH_CHECK("keep_conv2d(halo x3 ablation)");                                                                            \
-    report(E);                                                                                                                     \
-    return KEEP_OK;                                                                                                                \
-  }
-    KEEP_LAUNCH_ABL(1) KEEP_LAUNCH_ABL(2) KEEP_LAUNCH_ABL(3) KEEP_LAUNCH_ABL(4) KEEP_LAUNCH_ABL(5) KEEP_LAUNCH_ABL(6) KEEP_LAUNCH_ABL(7)
-    KEEP_LAUNCH_ABL(8) KEEP_LAUNCH_ABL(10) KEEP_LAUNCH_ABL(11) KEEP_LAUNCH_ABL(12) KEEP_LAUNCH_ABL(13) KEEP_LAUNCH_ABL(14) KEEP_LAUNCH_ABL(15) KEEP_LAUNCH_ABL(16)
-    KEEP_LAUNCH_ABL(17)
-    if (ex == 9) {       // phase timeline: one instrumented launch, cycle sums printed to stderr
-      (void)hipMemsetAsync(dbg, 0, 128, st);
-      if (a->pro_act == KEEP_PRO_SWISH)
-        hipLaunchKernelGGL((conv3x3_halo_x3_kernel<32, KEEP_PRO_SWISH, true, 9, true, true>), grid, block, 0, st, q, tiles_x, tiles_y, ncb, n_items);
-      else
-        hipLaunchKernelGGL((conv3x3_halo_x3_kernel<32, KEEP_PRO_NONE, true, 9, true, true>), grid, block, 0, st, q, tiles_x, tiles_y, ncb, n_items);
-      unsigned long long h[16];
-      (void)hipStreamSynchronize(st);
-      (void)hipMemcpy(h, dbg, 128, hipMemcpyDeviceToHost);
-      const double nb = (double)h[12], tot = (double)(h[0] + h[1] + h[2] + h[3] + h[4] + h[5] + h[6] + h[7] + h[8] + h[9] + h[10] + h[11]);
-      fprintf(stderr, "[x3 timeline] stage split: DMA issue %.1f%%  wait halo regs %.1f%%  VALU+ds_write %.1f%%  wait DMA %.1f%%  | epilogue: park in LDS %.1f%%  rest %.1f%%\n",
-              100.0 * h[8] / tot, 100.0 * h[9] / tot, 100.0 * h[0] / tot, 100.0 * h[10] / tot, 100.0 * h[11] / tot, 100.0 * h[6] / tot);
-      fprintf(stderr, "[x3 timeline] blocks %.0f  cycles/block %.0f | stage %.1f%%  sync-after-stage %.1f%%  fetch-issue %.1f%%  mma %.1f%%  "
-              "sync-after-mma %.1f%%  item-setup %.1f%%  epilogue %.1f%%  wait-loads %.1f%%\n", nb, tot / nb, 100.0 * h[0] / tot, 100.0 * h[1] / tot,
-              100.0 * h[2] / tot, 100.0 * h[3] / tot, 100.0 * h[4] / tot, 100.0 * h[5] / tot, 100.0 * h[6] / tot, 100.0 * h[7] / tot);
-      return KEEP_OK;
-    }
-#undef KEEP_LAUNCH_ABL
-  }
-#endif
-  static const bool wdma = !KEEP_DEV_ENV("KEEP_X3_NO_WDMA");      // weights by LDS-DMA (default); the VGPR-staged form stays for A/B runs
+  // weights by LDS-DMA; the exact-activation form below keeps the VGPR-staged weights
 #define KEEP_LAUNCH_HX2(TWV, PROV)                                                                                          \
-  if (wdma && simple)                                                                                                      \
-    hipLaunchKernelGGL((conv3x3_halo_x3_kernel<TWV, PROV, true, 0, true, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);  \
-  else if (wdma)                                                                                                           \
-    hipLaunchKernelGGL((conv3x3_halo_x3_kernel<TWV, PROV, false, 0, true, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items); \
-  else if (simple)                                                                                                         \
-    hipLaunchKernelGGL((conv3x3_halo_x3_kernel<TWV, PROV, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);  \
+  if (simple)                                                                                                              \
+    hipLaunchKernelGGL((conv3x3_halo_x3_kernel<TWV, PROV, true, true, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);  \
   else                                                                                                                     \
-    hipLaunchKernelGGL((conv3x3_halo_x3_kernel<TWV, PROV, false>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
+    hipLaunchKernelGGL((conv3x3_halo_x3_kernel<TWV, PROV, false, true, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
 #define KEEP_LAUNCH_HX(TWV)                                       \
   if (a->pro_act == KEEP_PRO_SWISH && !p.fast) {                  \
     if (simple)                                                   \
-      hipLaunchKernelGGL((conv3x3_halo_x3_kernel<TWV, KEEP_PRO_SWISH, true, 0, false>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);  \
+      hipLaunchKernelGGL((conv3x3_halo_x3_kernel<TWV, KEEP_PRO_SWISH, true, false>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);  \
     else                                                          \
-      hipLaunchKernelGGL((conv3x3_halo_x3_kernel<TWV, KEEP_PRO_SWISH, false, 0, false>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items); \
+      hipLaunchKernelGGL((conv3x3_halo_x3_kernel<TWV, KEEP_PRO_SWISH, false, false>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items); \
   } else if (a->pro_act == KEEP_PRO_SWISH) {                      \
     KEEP_LAUNCH_HX2(TWV, KEEP_PRO_SWISH)                          \
   } else if (a->pro_act == KEEP_PRO_RELU) {                       \
@@ -1643,9 +1450,7 @@ __global__ __launch_bounds__(256) void conv_x3_gather_stats_replica_kernel(ConvP
   }
 }
 
-#ifndef KEEP_GATHER_SMALL_ROWS
-#define KEEP_GATHER_SMALL_ROWS 4096      // rows in flight up to which a launch planned for the 128 x 128 tile runs the 64 x 64 tile (dev A/B: -D)
-#endif
+static constexpr long KEEP_GATHER_SMALL_ROWS = 4096;      // rows in flight up to which a launch planned for the 128 x 128 tile runs the 64 x 64 tile
 // tile: plan_conv's choice (1: 64x64 block tiles, 2: 128x128, 3: 128x128 as four 32-row waves with the LayerNorm epilogue) --
 // the launch never re-derives it
 int keep_conv2d_x3_gather(const keep_conv2d_args* a, ConvP& p, int tile, hipStream_t st) {
@@ -1685,15 +1490,11 @@ int keep_conv2d_x3_gather(const keep_conv2d_args* a, ConvP& p, int tile, hipStre
     hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, false, true>), grid, block, 0, st, p);          \
   else                                                                                             \
     hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, false, false>), grid, block, 0, st, p);
-  // several column blocks and many row blocks: row-block-major order on a 1-D grid (KEEP_X3_GEMM_2D=1: the 2-D grid, for A/B runs)
+  // several column blocks and many row blocks: row-block-major order on a 1-D grid
   const int bt = big_tile ? 128 : 64;
   const long gx = cdiv(M, bt), gy = cdiv(a->Cout, bt);
-  const bool rowmajor = gy > 1 && gx >= 1024 && gx * gy < (1L << 30) && !KEEP_DEV_ENV("KEEP_X3_GEMM_2D");
+  const bool rowmajor = gy > 1 && gx >= 1024 && gx * gy < (1L << 30);
   p.tile_cols = rowmajor ? (int)gy : 0;
-  {
-    static const int rev = KEEP_DEV_ENV("KEEP_X3_GEMM_REVERSE") ? atoi(KEEP_DEV_ENV("KEEP_X3_GEMM_REVERSE")) : 0;      // dev A/B
-    p.reverse = rev;
-  }
   dim3 grid(rowmajor ? (unsigned)(gx * gy) : (unsigned)gx, rowmajor ? 1u : (unsigned)gy, p.split_k);
   if (tile == 3) {
     hipLaunchKernelGGL((conv_x3_kernel<4, 1, 1, 4, true, true>), grid, block, 0, st, p);

@@ -26,9 +26,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define XP_HBYTES (128 * XPP * 2)      // 10240: 128 rows per stage, rows 108 .. 127 parked but never read (every thread converts two pieces: one basic block)
 #define XP_WBYTES (9 * 64 * 64)        // 36864: 9 taps x 64 couts x 64 B
 
-#ifndef XQ_SCHED
-#define XQ_SCHED 1      // round 6: conversion of chunk c + 1 scheduled into the MFMA chain of chunk c (0: the compiler's own order)
-#endif
 #define XP_ST 3                        // operand stages in LDS: the loads of chunk c + 2 are issued before the MFMAs of chunk c
 // NCH > 0: the block's chunk count, known at compile time -- the ring is straight-line code and the compiler's wait counts are exact (inside
 // a loop it orders every LDS read of a stage behind vmcnt(0): the DMA that filled the stage came through the back edge); 0: any count.
@@ -316,15 +313,11 @@ __global__ __launch_bounds__(256) void conv3x3_x3p_kernel(ConvP p, int tiles_x, 
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {      // chunk ch_begin + c lives in stage c % XP_ST
         if (c + 2 < NCH) fetch(ch_begin + c + 2, (c + 2) % XP_ST);
-        if (XQ_SCHED && c + 1 < NCH) {
+        if (c + 1 < NCH) {      // round 6: the conversion of chunk c + 1 inside the MFMA chain of chunk c (-5 % per launch)
           fused(c % XP_ST, (c + 1) % XP_ST);
           XP_BARRIER()
         } else {
           mma(c % XP_ST);
-          if (c + 1 < NCH) {
-            stage((c + 1) % XP_ST);
-            XP_BARRIER()
-          }
         }
       }
     } else {
@@ -405,12 +398,7 @@ __global__ __launch_bounds__(256) void conv3x3_x3p_kernel(ConvP p, int tiles_x, 
   }
 }
 
-#ifndef XQ_DIST
-#define XQ_DIST 2      // chunks between a chunk's loads and its conversion (3: the register ring holds three chunks in flight)
-#endif
-#ifndef XQ_ABL
-#define XQ_ABL 0      // dev: 1 no staging after the first chunk, 2 no MFMAs, 3 no operand fetch after the prologue, 4 no fragment reads
-#endif
+static constexpr int XQ_DIST = 2;      // chunks between a chunk's loads and its conversion (3 chunks in flight: +2 ms per clip)
 // ------------------------------------------------------------------------------------------------ un-split plans: the whole convolution
 // The same blocks for plans WITHOUT split-K on wide maps (32 x 32 .. 128 x 128 of one clip: 16 .. 128 items of conv3x3_halo_x3s_kernel on
 // 256 CUs, each wave 108 MFMAs per chunk): this kernel reproduces THAT kernel's values -- its conversion arithmetic (fma(v, sc, sh);
@@ -561,13 +549,9 @@ __global__ __launch_bounds__(256) void conv3x3_x3q_kernel(ConvP p, int tiles_x, 
         const f16x8 ah = *reinterpret_cast<const f16x8*>(src), al = *reinterpret_cast<const f16x8*>(src + 16);
         const int o = b_base + ((kh * 3 + kw) * 64 + chf * 32) * 32;
         const f16x8 bh = *reinterpret_cast<const f16x8*>(&Ws[o]), bl = *reinterpret_cast<const f16x8*>(&Ws[o ^ 16]);
-        if (XQ_ABL == 2) {
-          acc[0] += (float)al[0] + (float)bh[0] + (float)ah[1] + (float)bl[1];
-        } else {
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);      // the streaming kernel's term order
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
         acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
-        }
       }
   };
   // Round 6: the 27 MFMAs of a chunk form ONE dependent chain (a wave owns one 32 x 32 accumulator): ~32 cycles each in which the wave can issue
@@ -673,22 +657,17 @@ __global__ __launch_bounds__(256) void conv3x3_x3q_kernel(ConvP p, int tiles_x, 
     const bool two = NCH > 0 ? NCH > 1 : nch > 1;
     fetch(0, 0);
     if (two) fetch(1, 1);
-    if (XQ_DIST == 3 && NCH > 2) fetch(2, 2);
     stage(0);
     XP_BARRIER()
     if (NCH > 0) {
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
-        if (c + XQ_DIST < NCH && XQ_ABL != 3) fetch(c + XQ_DIST, (c + XQ_DIST) % XP_ST);
-        if (XQ_SCHED && XQ_ABL == 0 && c + 1 < NCH) {
+        if (c + XQ_DIST < NCH) fetch(c + XQ_DIST, (c + XQ_DIST) % XP_ST);
+        if (c + 1 < NCH) {
           fused(c % XP_ST, (c + 1) % XP_ST);
           XP_BARRIER()
         } else {
           mma(c % XP_ST);
-          if (c + 1 < NCH) {
-            if (XQ_ABL != 1) stage((c + 1) % XP_ST);
-            XP_BARRIER()
-          }
         }
       }
     } else {
@@ -785,9 +764,7 @@ int keep_conv2d_x3_partials(const keep_conv2d_args* a, ConvP& p, hipStream_t st)
 }
 
 // Un-split plans on wide maps (what conv3x3_halo_x3s_kernel takes) with few items: the 64-pixel blocks, same values.
-#ifndef XQ_MAX_ITEMS
-#define XQ_MAX_ITEMS 64      // items of the 256-pixel streaming kernel up to which the 64-pixel blocks take the map
-#endif
+static constexpr long XQ_MAX_ITEMS = 64;      // items of the 256-pixel streaming kernel up to which the 64-pixel blocks take the map
 bool keep_conv_x3q_ok(const keep_conv2d_args* a, const ConvP& p, int split_k) {
   const long items_s = (long)a->N * (a->Ho / 8) * (a->Wo / 32) * ((a->Cout + 63) / 64);
   const bool aff = a->pro_scale != nullptr;

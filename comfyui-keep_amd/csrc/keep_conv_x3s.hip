@@ -42,9 +42,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define XS_WOFF (2 * XS_HBUF)                 // weight rows
 #define XS_LDS (XS_WOFF + 576 * 64)           // 81408 B: two blocks per CU
 #define XS_EP 68                              // floats per parked epilogue row
-#ifndef XS_ABL                                // dev builds: phase ablations (tools/dev/README.md); 0 = the product
-#define XS_ABL 0
-#endif
 
 __device__ __forceinline__ float xs_xor16_sum(float x) {
   const u32x2 r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
@@ -55,8 +52,8 @@ __device__ __forceinline__ float xs_xor32_sum(float x) {
   return __uint_as_float(r.x) + __uint_as_float(r.y);
 }
 
-// TL: dev builds (-DKEEP_X3_ABLATE, KEEP_X3_EXP=21): wave 0's s_memtime timeline summed into p.ws
-template <int PRO, bool AFF, bool TL = false>
+// Phase ablations of this kernel and the s_memtime timeline of wave 0: DESIGN 5.3 (a) / (b).
+template <int PRO, bool AFF>
 __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int tiles_x, int tiles_y, int ncb, int n_items) {
   static_assert(AFF || PRO == KEEP_PRO_NONE, "an activation prologue comes with its GroupNorm affine");
   __shared__ __attribute__((aligned(16))) unsigned char lds_raw[XS_LDS];
@@ -161,14 +158,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
   float padf = 0.f;                            // piece in flight: 1e30 for a zero-padding piece
   f32x16 acc[2][2];
 
-  unsigned long long tacc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t0 = 0;
-#define XS_T(IDX)                                                     \
-  if (TL) {                                                           \
-    const unsigned long long t1 = __builtin_amdgcn_s_memtime();       \
-    tacc[IDX] += t1 - t0;                                             \
-    t0 = t1;                                                          \
-  }
-
   // Conversion of piece k = q / 18 of the chunk in `hreg`, step q % 18 -- at most two plain VALU instructions or two transcendentals per
   // step, one step per MFMA gap (the budget per gap is five issue slots including the fragment read and its wait: coissue_probe2);
   // hb: byte offset of the halo buffer the packed rows go to.  The request of the same piece of the chunk after it (F) rides in step 1:
@@ -186,11 +175,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
     if (st == 1) {
       cv[2] = AFF ? __builtin_fmaf(hreg[k].z, csc[2], csh[2]) : hreg[k].z * rs;
       cv[3] = AFF ? __builtin_fmaf(hreg[k].w, csc[3], csh[3]) : hreg[k].w * rs;
-      if (XS_ABL != 11) {
-        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(okF ? in_rsrc : null_rsrc, h_voff[k], chF * 64, KEEP_LD_AUX_XS);
-        hreg[k] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-      }
-      if (AFF && k == HALO_IT - 1 && XS_ABL != 11) {           // the affine of this chunk has been read for the last time: the next chunk's
+      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(okF ? in_rsrc : null_rsrc, h_voff[k], chF * 64, KEEP_LD_AUX_XS);
+      hreg[k] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+      if (AFF && k == HALO_IT - 1) {           // the affine of this chunk has been read for the last time: the next chunk's
         const u32x4 a = __builtin_amdgcn_raw_buffer_load_b128(okF ? sc_rsrc : null_rsrc, sc_voff, chF * 64, 0);
         const u32x4 b = __builtin_amdgcn_raw_buffer_load_b128(okF ? sh_rsrc : null_rsrc, sc_voff, chF * 64, 0);
         sc4 = make_float4(__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z), __uint_as_float(a.w));
@@ -198,7 +185,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
       }
     }
     if (st == 2 && AFF) padf = (padmask & (1u << k)) ? 1e30f : 0.f;
-    if (XS_ABL == 10 && st >= 3 && st <= 12) return;
     if (SW) {
       if (st == 3) { cw[0] = __builtin_fmaf(cv[0], -1.4426950408889634f, padf); cw[1] = __builtin_fmaf(cv[1], -1.4426950408889634f, padf); }
       if (st == 4) { cw[2] = __builtin_fmaf(cv[2], -1.4426950408889634f, padf); cw[3] = __builtin_fmaf(cv[3], -1.4426950408889634f, padf); }
@@ -229,9 +215,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
     if (st == 16) {
       clo[0] = __builtin_convertvector(f32x2{cw[0], cw[1]}, f16x2);
       clo[1] = __builtin_convertvector(f32x2{cw[2], cw[3]}, f16x2);
-      if (XS_ABL != 12 || cw[0] == 1.2345e-30f) *reinterpret_cast<uint2*>(lds_raw + wr_addr[k] + hb) = make_uint2(__builtin_bit_cast(unsigned, chi[0]), __builtin_bit_cast(unsigned, chi[1]));
+      *reinterpret_cast<uint2*>(lds_raw + wr_addr[k] + hb) = make_uint2(__builtin_bit_cast(unsigned, chi[0]), __builtin_bit_cast(unsigned, chi[1]));
     }
-    if (st == 17 && (XS_ABL != 12 || cw[1] == 1.2345e-30f))
+    if (st == 17)
       *reinterpret_cast<uint2*>(lds_raw + (wr_addr[k] ^ 32) + hb) = make_uint2(__builtin_bit_cast(unsigned, clo[0]), __builtin_bit_cast(unsigned, clo[1]));
   };
   // weights of chunk C, taps 3 gq .. 3 gq + 2: L2 -> LDS, 12 pieces of 1 KB (piece q = 16 weight rows: tap q / 4, couts 16 (q % 4) + lane / 4),
@@ -270,12 +256,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
         const int term = m >> 2, i = (m >> 1) & 1, j = m & 1;
         const int ia = term == 0 ? i : 4 + i;
         const int ib = term == 2 ? 6 + j : 2 + j;
-        if (XS_ABL == 1) {
-          asm volatile("" ::"v"(fr[ia]), "v"(fr[ib]));
-        } else {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[ia], fr[ib], acc[i][j], 0, 0, 0);
-        }
-        if (t < 8 && XS_ABL != 5) {            // re-read behind the last use: a_lo0 m=1, a_lo1 3, b_hi0 6, b_hi1 7, a_hi0 9, b_lo0 10, a_hi1 / b_lo1 11
+        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[ia], fr[ib], acc[i][j], 0, 0, 0);
+        if (t < 8) {            // re-read behind the last use: a_lo0 m=1, a_lo1 3, b_hi0 6, b_hi1 7, a_hi0 9, b_lo0 10, a_hi1 / b_lo1 11
           if (m == 1) fr[0] = frag_of(t + 1, 0, hbM);
           if (m == 3) fr[1] = frag_of(t + 1, 1, hbM);
           if (m == 6) fr[2] = frag_of(t + 1, 2, hbM);
@@ -287,7 +269,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
             fr[7] = frag_of(t + 1, 7, hbM);
           }
         }
-        if (t * 12 + m < NCONV && XS_ABL != 2) conv_step(t * 12 + m, hbC);
+        if (t * 12 + m < NCONV) conv_step(t * 12 + m, hbC);
         __builtin_amdgcn_sched_barrier(0);
       }
       // The weight stage is a ring of three tap groups: once every wave is past taps 0-2 (their fragment reads completed before the MFMAs
@@ -302,13 +284,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
         } else {
           asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
         }
-        if (XS_ABL != 6) asm volatile("s_barrier" ::: "memory");
-        if (okC && XS_ABL != 4) dma_group(0);
+        asm volatile("s_barrier" ::: "memory");
+        if (okC) dma_group(0);
         __builtin_amdgcn_sched_barrier(0);
       }
       if (t == 5) {
-        if (XS_ABL != 6) asm volatile("s_barrier" ::: "memory");
-        if (okC && XS_ABL != 4) dma_group(1);
+        asm volatile("s_barrier" ::: "memory");
+        if (okC) dma_group(1);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -350,7 +332,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
 #pragma unroll
         for (int r8 = 0; r8 < 8; ++r8) {
           const int r = (rd & 1) * 8 + r8;
-          if (XS_ABL != 8 || acc[rd >> 1][j][r] == 1.2345e-30f) et[((r & 3) + 8 * ((r >> 2) & 1) + 4 * lhi) * XS_EP + j * 32 + l31] = acc[rd >> 1][j][r];
+          et[((r & 3) + 8 * ((r >> 2) & 1) + 4 * lhi) * XS_EP + j * 32 + l31] = acc[rd >> 1][j][r];
         }
       __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0): wave-local hand-off
 #pragma unroll
@@ -369,7 +351,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
         }
         u32x4 o;
         o.x = __float_as_uint(e[0]); o.y = __float_as_uint(e[1]); o.z = __float_as_uint(e[2]); o.w = __float_as_uint(e[3]);
-        if (XS_ABL != 7 || e[0] == 1.2345e-30f) __builtin_amdgcn_raw_buffer_store_b128(o, out_rsrc, v_out, dpix_of(rd * 4 + u) * p.out_ld * 4, KEEP_ST_AUX_XS);
+        __builtin_amdgcn_raw_buffer_store_b128(o, out_rsrc, v_out, dpix_of(rd * 4 + u) * p.out_ld * 4, KEEP_ST_AUX_XS);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           s4[q] += e[q];
@@ -378,7 +360,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
         }
       }
     }
-    if (p.stats && XS_ABL != 9) {              // one partial per 256-pixel tile: the four waves' sums meet in LDS, added in wave order
+    if (p.stats) {              // one partial per 256-pixel tile: the four waves' sums meet in LDS, added in wave order
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         s4[q] = xs_xor32_sum(xs_xor16_sum(s4[q]));
@@ -452,9 +434,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
 
   int amax_n = -1;                             // image of the max |out| this wave has committed or seen
   float amax_run = 0.f;
-  const unsigned long long cyc0 = TL ? __builtin_amdgcn_s_memtime() : 0ull;
-  const unsigned long long rtc0 = TL ? __builtin_amdgcn_s_memrealtime() : 0ull;
-  if (TL) t0 = cyc0;
   // one pipeline step; HB: byte offset of the halo buffer holding chunk M (compile time: folded into the DS offsets).  true: done
   auto step = [&](auto hb_c) __attribute__((always_inline)) -> bool {
     constexpr int HB = decltype(hb_c)::value;
@@ -465,7 +444,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
       if (p.bias && co < p.Cout) biasM = *reinterpret_cast<const float4*>(p.bias + co);
     }
     mma_step(HB, XS_HBUF - HB);
-    XS_T(0)
     // this wave's weight pieces (taps 0-5 of the next chunk) and converted rows are in LDS.  Younger than the last of those pieces are
     // the raw-piece requests of gaps 73 and 91 (and the two affine loads of gap 91): they may stay in flight -- vmcnt(0) here exposed
     // most of an HBM round trip per step
@@ -475,11 +453,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
       asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
     }
     asm volatile("s_barrier" ::: "memory");              // every wave is done with halo buffer HB and weight taps 6-8; the other buffer and the next taps 0-5 are complete
-    XS_T(1)
-    if (okC && XS_ABL != 4) dma_group(2);
-    XS_T(2)
+    if (okC) dma_group(2);
     if (last) {
-      const float amx = XS_ABL == 3 ? acc[0][0][0] + acc[1][1][5] : (p.res ? epilogue_t(HB, std::true_type{}) : epilogue_t(HB, std::false_type{}));
+      const float amx = p.res ? epilogue_t(HB, std::true_type{}) : epilogue_t(HB, std::false_type{});
       if (p.out_amax) {     // max|out| of the image: a wave goes to memory only above everything it has committed or seen for this image
         if (itM.n != amax_n) {
           amax_n = itM.n;
@@ -505,7 +481,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
         for (int j = 0; j < 2; ++j)
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-      XS_T(3)
     }
     after_epi = last;
     if (!okC) return true;
@@ -525,31 +500,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
       chC = chF;
       advance_F();                             // F <- the chunk after it
     }
-    XS_T(4)
     if (last) {                                // the parked rows / statistics of the epilogue live in buffer HB: the next step converts into it
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       asm volatile("s_barrier" ::: "memory");
     }
-    XS_T(6)
     return false;
   };
   while (true) {
     if (step(std::integral_constant<int, 0>{})) break;
     if (step(std::integral_constant<int, XS_HBUF>{})) break;
   }
-  if (TL && tid == 0) {
-    unsigned long long* dst = reinterpret_cast<unsigned long long*>(p.ws);
-#pragma unroll
-    for (int q = 0; q < 12; ++q) atomicAdd(dst + q, tacc[q]);
-    atomicAdd(dst + 12, 1ull);
-    atomicAdd(dst + 13, __builtin_amdgcn_s_memtime() - cyc0);
-    atomicAdd(dst + 14, __builtin_amdgcn_s_memrealtime() - rtc0);
-    if (blockIdx.x < 1024) {                   // per-block start / end (100 MHz ticks) behind the 16 sums
-      dst[16 + blockIdx.x * 2] = rtc0;
-      dst[17 + blockIdx.x * 2] = __builtin_amdgcn_s_memrealtime();
-    }
-  }
-#undef XS_T
 }
 
 // ------------------------------------------------------------------------------------------------ statistics of a written tile
@@ -635,53 +595,6 @@ int keep_conv2d_x3_stream(const keep_conv2d_args* a, ConvP& p, int n_cu, hipStre
   const int n_items = a->N * tiles_x * tiles_y * ncb;
   dim3 grid(n_items < 2 * n_cu ? n_items : 2 * n_cu), block(256);
   const bool aff = a->pro_scale != nullptr;
-  if (KEEP_DEV_ENV("KEEP_X3_OCC")) {      // dev: resident blocks per CU as the runtime sees them
-    int nb = -1;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, conv3x3_halo_x3s_kernel<KEEP_PRO_SWISH, true>, 256, 0);
-    fprintf(stderr, "[x3s] occupancy: %d blocks per CU (LDS %d B per block)\n", nb, XS_LDS);
-  }
-#ifdef KEEP_X3_ABLATE
-  if (KEEP_DEV_ENV("KEEP_X3_EXP") && atoi(KEEP_DEV_ENV("KEEP_X3_EXP")) == 21 && a->pro_act == KEEP_PRO_SWISH) {      // timeline of wave 0
-    static unsigned long long* dbg = nullptr;
-    if (!dbg) (void)hipMalloc(&dbg, 128 + 1024 * 16);
-    (void)hipMemsetAsync(dbg, 0, 128, st);
-    ConvP q = p;
-    q.ws = reinterpret_cast<float*>(dbg);
-    hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_SWISH, true, true>), grid, block, 0, st, q, tiles_x, tiles_y, ncb, n_items);
-    unsigned long long h[16];
-    (void)hipStreamSynchronize(st);
-    (void)hipMemcpy(h, dbg, 128, hipMemcpyDeviceToHost);
-    double tot = 0;
-    for (int i = 0; i < 12; ++i) tot += (double)h[i];
-    fprintf(stderr, "[x3s timeline] abl %d clock %.0f MHz | blocks %.0f cycles/block %.0f (whole %.0f) | mma+conv %.1f%%  sync %.1f%% | dma issue %.1f%%  epilogue %.1f%%  advance %.1f%%  dma wait %.1f%%  sync %.1f%%\n",
-            XS_ABL, (double)h[13] / ((double)h[14] / 100.0), (double)h[12], tot / h[12], (double)h[13] / h[12], 100.0 * h[0] / tot, 100.0 * h[1] / tot, 100.0 * h[2] / tot, 100.0 * h[3] / tot, 100.0 * h[4] / tot,
-            100.0 * h[5] / tot, 100.0 * h[6] / tot);
-    {      // block lifetimes of the launch (100 MHz ticks): spread and histogram
-      static unsigned long long se[2048];
-      const int nblk = (int)grid.x < 1024 ? (int)grid.x : 1024;
-      (void)hipMemcpy(se, dbg + 16, nblk * 16, hipMemcpyDeviceToHost);
-      unsigned long long t_min = ~0ull, t_max = 0;
-      for (int b = 0; b < nblk; ++b) {
-        if (se[2 * b] < t_min) t_min = se[2 * b];
-        if (se[2 * b + 1] > t_max) t_max = se[2 * b + 1];
-      }
-      double lsum = 0, lmin = 1e30, lmax = 0;
-      for (int b = 0; b < nblk; ++b) {
-        const double l = (se[2 * b + 1] - se[2 * b]) / 100.0;
-        lsum += l;
-        if (l < lmin) lmin = l;
-        if (l > lmax) lmax = l;
-      }
-      int hist[10] = {0};
-      for (int b = 0; b < nblk; ++b) hist[(int)(9.999 * ((se[2 * b + 1] - se[2 * b]) / 100.0 - lmin) / (lmax - lmin + 1e-9))]++;
-      fprintf(stderr, "[x3s blocks] span %.1f us | block life min %.1f mean %.1f max %.1f us | histogram (min..max, 10 bins):", (t_max - t_min) / 100.0, lmin,
-              lsum / nblk, lmax);
-      for (int i = 0; i < 10; ++i) fprintf(stderr, " %d", hist[i]);
-      fprintf(stderr, "\n");
-    }
-    return KEEP_OK;
-  }
-#endif
   if (a->pro_act == KEEP_PRO_SWISH)
     hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_SWISH, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
   else if (a->pro_act == KEEP_PRO_RELU)

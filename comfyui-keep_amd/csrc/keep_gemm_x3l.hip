@@ -27,14 +27,12 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // A wave now loads its 32 rows x 64 channels of A (and the 32 rows x 4 chunks of pre-split B) with 16-byte pieces CONSECUTIVE across lanes
 // (16 lanes = one 256-byte row run: 8 lines per instruction), parks them in its private LDS rows at a 272-byte pitch (68 floats: the eight
 // rows a ds_read_b128 phase touches fall on disjoint banks) and reads the MFMA fragments back: same values in the same registers, same
-// MFMA order -- same bits.  KEEP_GL_DIRECT=1 (dev builds) keeps the direct fragment loads.
+// MFMA order -- same bits.
 #define GL_ROWB (GL_G * 64 + 16)    // bytes per staged row
 // rows per image the family takes: the 16 x 16 token maps (code transformer, AttnBlock).  The 32 x 32 maps (CFA: 135 launches per clip)
 // were measured too: -0.5 ms per clip with one clip in flight, +1.8 ms per 16-clip step (64 x 64 tiles with slice totals against the
 // 128 x 128 tile of the sequential sum) -- left on conv_x3_kernel.
-#ifndef GL_MAX_HW
-#define GL_MAX_HW 256
-#endif
+static constexpr int GL_MAX_HW = 256;
 #define GL_MAX_TILES 512            // launches of more 32 x 32 output tiles run on conv_x3_kernel with canonical slices (same bits)
 
 template <int NW, int TM, bool PLAIN>

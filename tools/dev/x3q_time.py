@@ -1,4 +1,5 @@
-"""dev: us per launch of the 64-pixel-block convolution kernels on the shapes of one clip (hipGraph replay); KEEP_HIP_LIB selects an ablation build."""
+"""dev: us per launch of the 64-pixel-block convolution kernels on the shapes of one clip (hipGraph replay), each against the
+256-pixel kernels (flags = KEEP_CONV_NO_SMALL_PARTIALS); KEEP_HIP_LIB selects which library build is timed."""
 import os
 import sys
 
