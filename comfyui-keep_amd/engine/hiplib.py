@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('KEEP_HIP_LIB') or os.path.join(os.path.dirname(_HERE), 'csrc', 'libkeep_hip.so')   # (KEEP_HIP_LIB: dev A/B builds)
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 F32, BF16 = 0, 1
 MMA_F32, MMA_BF16, MMA_X3 = 0, 1, 2
@@ -112,6 +112,8 @@ _SIGNATURES = {
     'keep_draw_box': [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp],
     'keep_erode_rect': [_vp, _vp, _vp, _i32, _i32, _i32, _vp],
     'keep_paste_face': [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
+    'keep_lanczos4_tables': [_i32, _i32, _vp, _vp],                        # (host-only: no stream argument)
+    'keep_resize_lanczos4_u8': [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
 }
 EXPORTED_SYMBOLS = ['keep_abi_version', 'keep_last_error', 'keep_device_ok', 'keep_attention_workspace_bytes',
                     'keep_sizeof_conv2d_args', 'keep_sizeof_attention_args'] + list(_SIGNATURES)

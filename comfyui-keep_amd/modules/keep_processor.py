@@ -98,6 +98,28 @@ def opencv_agrees_with_gpu_paste(device):
     return bool(np.array_equal(gp.crop_faces(frame, [fwd], device=device)[0].cpu().numpy(), crop))
 
 
+def opencv_agrees_with_gpu_resize(device):
+    """True iff the HIP Lanczos resize (engine/resize.py) reproduces ``cv2.resize(..., INTER_LANCZOS4)`` bit for bit on this
+    installation: up- and down-scales of random frames, odd sizes, a geometry whose source coordinates land on whole pixels (the
+    1e30 branch of interpolateLanczos4) and a one-pixel-wide output.  Raises ImportError without cv2."""
+    import cv2
+    from ..engine.resize import Lanczos4Resizer
+    rz = Lanczos4Resizer(device)
+    rng = np.random.default_rng(0)
+    for (h, w), (h2, w2) in (((90, 160), (180, 320)), ((37, 53), (48, 68)), ((120, 200), (84, 140)), ((300, 9), (100, 3)),
+                             ((64, 64), (256, 256)), ((31, 17), (15, 1))):
+        img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+        ref = cv2.resize(img, (w2, h2), interpolation=cv2.INTER_LANCZOS4)
+        if not np.array_equal(rz.resize_u8(img, w2, h2).cpu().numpy(), ref):
+            return False
+    return True
+
+
+def _host(img):
+    """A background / face that leaves the device path (the helper's own paste, a frame returned as it is): a host array."""
+    return img.cpu().numpy() if isinstance(img, torch.Tensor) else img
+
+
 class _ReplayDetector:
     """Stands in for ``face_detector`` while the helper post-processes ONE frame of a batched detection pass: returns the
     stored ``detect_faces`` result of that frame."""
@@ -279,6 +301,13 @@ class KEEPFaceProcessor:
         self.gpu_paste = {'1': True, '0': False}.get(env, None)
         self._gpu_paste_forced = env == '1'        # the erosion-mask branch (use_parse=False) is not part of the cv2 self-check
         self._paster = None
+        # final_upscale_factor != 1: the INTER_LANCZOS4 resize of the background (and of aligned outputs) on the device
+        # (engine/resize.py).  KEEP_AMD_GPU_RESIZE: '1' on, '0' off (cv2.resize on the host); unset = auto: with cv2 the first resize
+        # runs ``opencv_agrees_with_gpu_resize`` and the device path is used only if it is bit-equal to cv2; without cv2 the device
+        # path is the only one there is.
+        env = os.environ.get('KEEP_AMD_GPU_RESIZE')
+        self.gpu_resize = {'1': True, '0': False}.get(env, None)
+        self._resizer = None
 
     # ------------------------------------------------------------------ net invocation
     def _restore_clips(self, crops_tensor, max_clip_length):
@@ -337,10 +366,45 @@ class KEEPFaceProcessor:
                         upscale_amount=model.scale)
         return comfy_image_to_cv2(torch.clamp(s.movedim(-3, -1), min=0, max=1.0))
 
-    def _final_background(self, frame_bgr, factor):
+    def _final_background(self, frame_bgr, factor, on_device=False):
+        """The background at the output size (face_restoration_helper.py:354-356).  ``on_device``: the consumer is the HIP paste, so
+        a background the device resized stays there (a tensor); otherwise it is a host array."""
         up = self._run_upscaler(self.bg_upscale_model, frame_bgr)
         h, w, _ = frame_bgr.shape
-        return _resize(up, int(w * factor), int(h * factor), 'INTER_LANCZOS4')
+        return self._lanczos(up, int(w * factor), int(h * factor), on_device)
+
+    def _lanczos(self, img, w, h, on_device=False):
+        """``_resize(img, w, h, 'INTER_LANCZOS4')``: identity returns ``img``; uint8 3-channel images go to the device kernel when
+        ``_gpu_resize_path`` allows it, everything else (grey / 4-channel / other dtypes, an empty target) to cv2."""
+        if img.shape[0] == h and img.shape[1] == w:
+            return img
+        if (w > 0 and h > 0 and len(img.shape) == 3 and img.shape[2] == 3 and img.dtype in (np.uint8, torch.uint8)
+                and self._gpu_resize_path()):
+            if self._resizer is None:
+                from ..engine.resize import Lanczos4Resizer
+                self._resizer = Lanczos4Resizer(self.device)
+            out = self._resizer.resize_u8(img, w, h)
+            return out if on_device else out.cpu().numpy()
+        return _resize(_host(img), w, h, 'INTER_LANCZOS4')
+
+    def _gpu_resize_path(self):
+        """Whether the HIP Lanczos resize stands in for cv2.resize: forced by KEEP_AMD_GPU_RESIZE, else decided once per processor --
+        by comparing it with cv2 itself where cv2 imports, and on without cv2 (no other path can run there)."""
+        if self.gpu_resize is None:
+            import logging
+            log = logging.getLogger('ComfyUI-KEEP')
+            try:
+                import cv2  # noqa: F401
+            except ImportError:
+                log.info("cv2 is not installed: final_upscale_factor resizes run on the device (KEEP_AMD_GPU_RESIZE)")
+                self.gpu_resize = True
+                return True
+            try:
+                self.gpu_resize = bool(opencv_agrees_with_gpu_resize(self.device))
+            except Exception as e:                      # no GPU / no library / any surprise: cv2
+                log.info("device Lanczos resize self-check failed (%s): cv2.resize", e)
+                self.gpu_resize = False
+        return self.gpu_resize
 
     # ------------------------------------------------------------------ single image
     @torch.no_grad()
@@ -348,7 +412,7 @@ class KEEPFaceProcessor:
                       only_center_face: bool, draw_box: bool):
         helper = self.face_helper
         helper.upscale_factor = final_upscale_factor
-        bg_img_final = self._final_background(cv2_image_orig, final_upscale_factor)
+        bg_img_final = self._final_background(cv2_image_orig, final_upscale_factor, on_device=not has_aligned)
 
         if has_aligned:
             face = _resize(cv2_image_orig, 512, 512, 'INTER_LINEAR')
@@ -360,11 +424,11 @@ class KEEPFaceProcessor:
             helper.read_image(cv2_image_orig)
             if helper.get_face_landmarks_5(only_center_face=only_center_face, resize=640,
                                            eye_dist_threshold=5) == 0:
-                return bg_img_final
+                return _host(bg_img_final)
             self._align_warp(helper)
             crops = list(helper.cropped_faces)
             if not crops:
-                return bg_img_final
+                return _host(bg_img_final)
 
         # one face -> T=2 duplicate, keep frame 0; several faces -> one "clip" of T=#faces (KP:173-178)
         faces = self._restore_crops_u8(crops, max_clip_length=max(len(crops), 1))
@@ -381,8 +445,8 @@ class KEEPFaceProcessor:
             if self.face_upscale_model:
                 out = self._run_upscaler(self.face_upscale_model, out)
             side = int(512 * final_upscale_factor)
-            out = _resize(out, side, side, 'INTER_LANCZOS4')
-        return out if out is not None else bg_img_final
+            out = self._lanczos(out, side, side)
+        return out if out is not None else _host(bg_img_final)
 
     # ------------------------------------------------------------------ paste-back
     def _paste(self, helper, bg, draw_box):
@@ -393,7 +457,7 @@ class KEEPFaceProcessor:
         helper that is not the reference's -- goes to the helper's own method."""
         if self._gpu_cv_path() and self._gpu_paste_applies(helper, bg, draw_box):
             return self._paste_gpu(helper, bg, draw_box)
-        return helper.paste_faces_to_input_image(upsample_img=bg, draw_box=draw_box, face_upsampler=self.face_upscale_model)
+        return helper.paste_faces_to_input_image(upsample_img=_host(bg), draw_box=draw_box, face_upsampler=self.face_upscale_model)
 
     def _gpu_cv_path(self):
         """Whether the OpenCV-arithmetic kernels (paste-back, crop warp) may stand in for cv2: forced by KEEP_AMD_GPU_PASTE, else
@@ -437,11 +501,16 @@ class KEEPFaceProcessor:
             return False
         if (use_parse and getattr(helper, 'face_parse', None) is None) or not faces or mats is None:
             return False
-        if len(faces) != len(mats) or not isinstance(bg, np.ndarray) or bg.dtype != np.uint8 or bg.ndim != 3 or bg.shape[2] != 3:
+        if len(faces) != len(mats):
+            return False
+        if isinstance(bg, torch.Tensor):                   # the background resized on the device (final_upscale_factor != 1)
+            if bg.dtype != torch.uint8 or bg.dim() != 3 or bg.shape[2] != 3 or not bg.is_cuda:
+                return False
+        elif not isinstance(bg, np.ndarray) or bg.dtype != np.uint8 or bg.ndim != 3 or bg.shape[2] != 3:
             return False
         h, w = getattr(helper, 'input_img', bg).shape[:2]
         up = getattr(helper, 'upscale_factor', 1)
-        if (int(h * up), int(w * up)) != bg.shape[:2]:          # :355-356 would resize the background first
+        if (int(h * up), int(w * up)) != tuple(bg.shape[:2]):   # :355-356 would resize the background first
             return False
         fw, fh = getattr(helper, 'face_size', (512, 512))
         # grey sources (is_gray: add_restored_face stored bgr2gray + AdaIN faces, [512,512]): the reference replicates the channel
@@ -461,7 +530,7 @@ class KEEPFaceProcessor:
         if not getattr(helper, 'use_parse', False):       # :386-415 erosion mask instead of the parse mask
             out = self._paster.paste(bg, faces, list(helper.inverse_affine_matrices), None, getattr(helper, 'upscale_factor', 1), draw_box)
             if out is None:                                # a face larger than the blur kernel takes: the helper's own path
-                return helper.paste_faces_to_input_image(upsample_img=bg, draw_box=draw_box, face_upsampler=None)
+                return helper.paste_faces_to_input_image(upsample_img=_host(bg), draw_box=draw_box, face_upsampler=None)
             return out.cpu().numpy()
         # :418-424  BGR uint8 -> RGB float (x/255 - 0.5)/0.5, one face per ParseNet call like the reference
         x = torch.empty(faces.shape, dtype=torch.float32, device=self.device)
@@ -577,10 +646,10 @@ class KEEPFaceProcessor:
                     for k, i in enumerate(idx):
                         classes[i] = cl[k]
                 for t in range(f0, f1):
-                    bg = self._final_background(frames_bgr[t], factor)
+                    bg = self._final_background(frames_bgr[t], factor, on_device=True)   # (factor != 1: resized on this stream)
                     k = faces_per_frame[t]
                     if k == 0:
-                        emit(t, on_dev(np.ascontiguousarray(bg)))
+                        emit(t, bg if isinstance(bg, torch.Tensor) else on_dev(np.ascontiguousarray(bg)))
                         continue
                     helper.affine_matrices = affines[st['aff']:st['aff'] + k]
                     helper.upscale_factor = factor
@@ -797,8 +866,10 @@ class KEEPFaceProcessor:
         out_frames = []
         face_ptr = aff_ptr = 0
         for i in tqdm(range(n_frames), desc="Pasting faces and finalizing frames"):
-            bg = self._final_background(frames_bgr[i], final_upscale_factor)
             k = faces_per_frame[i]
+            # (a background for the HIP paste may stay on the device; _paste downloads it if the helper's own paste takes the frame)
+            bg = self._final_background(frames_bgr[i], final_upscale_factor,
+                                        on_device=k > 0 and not has_aligned_frames and self.gpu_paste is not False)
             if has_aligned_frames and self.return_restored_aligned and k:
                 # opt-in fix of reference quirk P2: an aligned sequence returns its restored faces, resized the way the
                 # single-image node does (keep_processor.py:190-197), instead of the upscaled input
@@ -807,7 +878,7 @@ class KEEPFaceProcessor:
                 if self.face_upscale_model:
                     face = self._run_upscaler(self.face_upscale_model, face)
                 side = int(512 * final_upscale_factor)
-                out_frames.append(_resize(face, side, side, 'INTER_LANCZOS4'))
+                out_frames.append(self._lanczos(face, side, side))
                 continue
             if k == 0 or has_aligned_frames:            # aligned: restored faces unused (reference quirk P2)
                 out_frames.append(bg)

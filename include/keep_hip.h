@@ -30,8 +30,8 @@ extern "C" {
  * the fields a shorter known layout lacks as zero), keep_sizeof_*_args(), keep_argmax_gather takes the non-finite status word,
  * keep_nonfinite_flag.  v13: keep_conv2d_args.upsample accepts KEEP_UPSAMPLE_X2_PHASES (same layout; a v12 library refuses the
  * value, so the binding asks for 13).  v18: the two reserved words of keep_conv2d_args become `flags` / `plan_ref_images`, the one of
- * keep_attention_args `flags` (same layout and sizes; zero keeps the v17 behaviour) -- the library no longer reads ANY environment variable.  v19: keep_yolo_letterbox_u8, keep_yolo_select, keep_layernorm_amax, keep_geglu_amax, keep_retina_nms_ordered (additions only). */
-#define KEEP_ABI_VERSION 20
+ * keep_attention_args `flags` (same layout and sizes; zero keeps the v17 behaviour) -- the library no longer reads ANY environment variable.  v19: keep_yolo_letterbox_u8, keep_yolo_select, keep_layernorm_amax, keep_geglu_amax, keep_retina_nms_ordered (additions only).  v21: keep_lanczos4_tables, keep_resize_lanczos4_u8 (additions only). */
+#define KEEP_ABI_VERSION 21
 #define KEEP_OK 0
 #define KEEP_EINVAL (-1)
 #define KEEP_EUNSUP (-2)
@@ -491,6 +491,16 @@ int32_t keep_erode_rect(const float* src, float* tmp, float* dst, int32_t H, int
  * mask_border < 0: `mask` is a soft mask already in FRAME space [H,W] (the use_parse=False path), read at the destination pixel. */
 int32_t keep_paste_face(float* frame, int32_t H, int32_t W, const uint8_t* face, const float* mask, int32_t fh, int32_t fw,
                         const double* dst_to_src, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t mask_border, void* stream);
+
+/* ---- final_upscale_factor (v21; face_restoration_helper.py:354-356): cv2.resize(frame, (W2, H2), interpolation=INTER_LANCZOS4)
+ * keep_lanczos4_tables: HOST-only C (no device, no stream): the table of one axis of OpenCV 4.x resizeGeneric_ / interpolateLanczos4 for
+ * source size S and destination size D -- ofs[D] = floor of the source coordinate, coef[D * 8] = the 8 int16 coefficients (scale 2048)
+ * of taps ofs[d] - 3 .. ofs[d] + 4 (clamped to [0, S - 1]).  Both arrays are HOST memory owned by the caller.
+ * keep_resize_lanczos4_u8: N contiguous uint8 BGR frames [N,H,W,3] -> [N,H2,W2,3] with the tables of x (W -> W2) and y (H -> H2), all
+ * DEVICE pointers; horizontal then vertical int32 sums, (v + 2^21) >> 22 clamped to [0, 255] (VResizeLanczos4 / FixedPtCast<int,uchar,22>). */
+int32_t keep_lanczos4_tables(int32_t S, int32_t D, int32_t* ofs, int16_t* coef);
+int32_t keep_resize_lanczos4_u8(const uint8_t* src, uint8_t* dst, int32_t N, int32_t H, int32_t W, int32_t H2, int32_t W2,
+                                const int32_t* xofs, const int16_t* xcoef, const int32_t* yofs, const int16_t* ycoef, void* stream);
 
 #ifdef __cplusplus
 }
