@@ -1,0 +1,812 @@
+"""Which bytes do the kernels touch?  Every case runs one C-ABI call through tests/footprint.py: each tensor embedded in
+guards, strided tensors with their real ``ld`` (gap columns are surroundings), workspace / statistics partials / amax slots at
+exactly the size the library reports.  Written surroundings must stay bit-identical; the outputs must be bit-identical under
+zero / NaN / 3e38 surroundings of everything that is read, finite, and equal to the plain call.  Values are judged elsewhere.
+
+The case tables are plain data, importable without a GPU: tests/test_host_logic.py asks ``keep_conv2d_plan`` (host C) for every
+convolution case and checks that the tables reach every kernel family and name every launcher of include/keep_hip.h.
+"""
+import ctypes
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import footprint as FP
+from conftest import op_input
+from comfyui_keep_amd.engine import hiplib as L
+from comfyui_keep_amd.engine import ops
+
+pytestmark = pytest.mark.gpu
+
+F32, BF16 = torch.float32, torch.bfloat16
+# Largest block of memory one step of a convolution / attention kernel can touch past a tensor edge: a 128-row tile of the
+# widest row used here (in_ld <= 2048 floats) = 1 MiB would be the gather tile of a GEMM whose rows run over; the 3x3 halo
+# tile is (8 + 2) x (32 + 2) pixels.  Every case below has rows of at most 1040 floats, so 128 rows x 1040 x 4 = 520 KiB.
+CONV_TILE_BYTES = 128 * 1040 * 4
+
+
+def rnd(name, shape, scale=1.0, dtype=F32):
+    return op_input('fp:' + name, shape, scale).to(dtype)
+
+
+# ------------------------------------------------------------------------------------------------ keep_conv2d
+# name -> (expected family string of keep_conv2d_plan, arguments).  Geometry keys: N H W Cin Cout k stride pad (or pad_t/pad_l) Ho Wo
+# (default: same-size for stride 1, the symmetric-padding size otherwise) in_ld in_off out_ld out_off res_ld aux pro pro_act act split_k
+# stats amax in_amax in2_cin1 reflect upsample in_bf16 out_bf16 bk256 ln flags launch (False: plan-only).
+def _c(expect, mma, **kw):
+    return expect, dict(mma=mma, **kw)
+
+
+F_, B_, X_ = L.MMA_F32, L.MMA_BF16, L.MMA_X3
+CONV_CASES = {
+    # ---- <= 4 output channels, every policy (exact-fp32 VALU kernel): N = 3, strided input slice, prologue
+    'cout4_f32': _c('conv3x3_cout4_kernel', F_, N=3, H=8, W=32, Cin=16, Cout=3, in_ld=24, in_off=4, out_ld=5, out_off=1, pro=True,
+                    pro_act=L.PRO_SWISH),
+    'cout4_x3': _c('conv3x3_cout4_kernel', X_, N=1, H=16, W=32, Cin=32, Cout=2, act=L.ACT_SIGMOID),
+    # ---- RGB first convolutions (rows of 3 floats inside rows of 4: the 4th float is a gap)
+    'c3_bf16': _c('conv3x3_c3_kernel', B_, N=3, H=8, W=32, Cin=3, Cout=32, in_ld=4, stats=True),
+    'c3_x3': _c('conv3x3_c3_x3_kernel', X_, N=1, H=16, W=32, Cin=3, Cout=48, out_ld=64, out_off=8, in_amax=True, amax=True),
+    'c3_x3_dense': _c('conv3x3_c3_x3_kernel', X_, N=3, H=8, W=32, Cin=2, Cout=32, in_amax=True, amax=True, stats=True),
+    # ---- x3 halo kernels
+    'up2_phases': _c('conv3x3_halo_x3_kernel<32, x2 phases>', X_, N=1, H=8, W=32, Cin=16, Cout=64, upsample=2, in_ld=20, in_off=4,
+                     res_ld=72, in_amax=True, amax=True),
+    'up2_phases_n3': _c('conv3x3_halo_x3_kernel<32, x2 phases>', X_, N=3, H=8, W=32, Cin=48, Cout=64, upsample=2, out_ld=80, out_off=12,
+                        in_amax=True),
+    'x3s_plain': _c('conv3x3_halo_x3s_kernel', X_, N=3, H=8, W=32, Cin=32, Cout=32, in_ld=40, in_off=8, out_ld=48, out_off=8, res_ld=36,
+                    in_amax=True, amax=True),
+    'x3s_pro': _c('conv3x3_halo_x3s_kernel', X_, N=1, H=16, W=32, Cin=48, Cout=96, pro=True, pro_act=L.PRO_SWISH, stats=True, amax=True),
+    'x3s_reflect': _c('conv3x3_halo_x3s_kernel', X_, N=1, H=8, W=32, Cin=32, Cout=32, reflect=True, act=L.ACT_LRELU02, in_amax=True),
+    'x3s_up': _c('conv3x3_halo_x3s_kernel', X_, N=1, H=8, W=16, Cin=32, Cout=32, upsample=1, in_amax=True),
+    'halo_x3_16': _c('conv3x3_halo_x3_kernel<16>', X_, N=3, H=16, W=16, Cin=48, Cout=96, pro=True, pro_act=L.PRO_RELU, stats=True,
+                     amax=True, in_ld=52, in_off=4),
+    'halo_x3_16_aux': _c('conv3x3_halo_x3_kernel<16>', X_, N=1, H=16, W=16, Cin=16, Cout=32, res_ld=40, aux=True, in_amax=True),
+    'halo_x3_32_split': _c('conv3x3_halo_x3_kernel<32>', X_, N=1, H=8, W=32, Cin=48, Cout=32, split_k=3, in_amax=True, res_ld=32),
+    'halo_x3_16_autosplit': _c('conv3x3_halo_x3_kernel<16>', X_, N=1, H=16, W=16, Cin=128, Cout=32, pro=True, pro_act=L.PRO_SWISH),
+    # ---- x3 GEMM / gather kernels
+    'gemm_x3l_4': _c('gemm_x3l_kernel<4>', X_, N=3, H=64, W=1, Cin=256, Cout=32, k=1, in_ld=260, in_off=4, out_ld=40, out_off=4,
+                     res_ld=36, in_amax=True, amax=True, act=L.ACT_GELU),
+    'gemm_x3l_8': _c('gemm_x3l_kernel<8>', X_, N=1, H=192, W=1, Cin=1024, Cout=96, k=1, in_amax=True, amax=True),
+    'x3_ln': _c('conv_x3_kernel<4, 1, 1, 4, true, true> + LayerNorm', X_, N=3, H=128, W=1, Cin=48, Cout=128, k=1, ln=True, res_ld=132,
+                in_ld=56, in_off=4, in_amax=True, amax=True),
+    'x3_gemm_small': _c('conv_x3_kernel<2, 2, 1, 1, true, true>', X_, N=1, H=300, W=1, Cin=80, Cout=48, k=1, in_ld=96, in_off=8, out_ld=56,
+                        out_off=4, res_ld=52, in_amax=True),
+    'x3_gemm_in2': _c('conv_x3_kernel<2, 2, 1, 1, true, true>', X_, N=1, H=200, W=1, Cin=80, Cout=48, k=1, in2_cin1=32, in_ld=36),
+    'x3_gemm_big': _c('conv_x3_kernel<2, 2, 2, 2, true, true>', X_, N=1, H=777, W=1, Cin=48, Cout=96, k=1, in_amax=True, act=L.ACT_GELU),
+    'x3_gemm_pro_amax': _c('conv_x3_kernel<2, 2, 1, 1, false, true>', X_, N=3, H=8, W=8, Cin=48, Cout=48, k=1, pro=True, stats=True, amax=True),
+    'x3_gemm_split': _c('conv_x3_kernel<2, 2, 1, 1, true, true>', X_, N=1, H=300, W=1, Cin=512, Cout=48, k=1, in_amax=True, flags=L.CONV_NO_GEMM_LAT),
+    'x3_gather_down': _c('conv_x3_kernel<2, 2, 1, 1, true, false>', X_, N=3, H=10, W=14, Cin=16, Cout=48, stride=2, pad_t=0, pad_l=0,
+                         Ho=5, Wo=7, in_amax=True),
+    'x3_gather_7x7': _c('conv_x3_kernel<2, 2, 1, 1, false, false>', X_, N=1, H=5, W=7, Cin=144, Cout=48, k=7, pad=3, pro=True,
+                        pro_act=L.PRO_RELU, split_k=5),
+    'x3_gather_reflect': _c('conv_x3_kernel<2, 2, 2, 2, true, false>', X_, N=1, H=18, W=18, Cin=16, Cout=96, reflect=True, in_amax=True),
+    # ---- exact-f32 halo kernel
+    'halo_f32_32': _c('conv3x3_halo_f32_kernel<32>', F_, N=3, H=8, W=32, Cin=16, Cout=32, in_ld=24, in_off=4, out_ld=48, out_off=8,
+                      res_ld=40, pro=True, pro_act=L.PRO_SWISH),
+    'halo_f32_16': _c('conv3x3_halo_f32_kernel<16>', F_, N=1, H=16, W=16, Cin=48, Cout=96, stats=True, act=L.ACT_LRELU02),
+    'halo_f32_16_split': _c('conv3x3_halo_f32_kernel<16>', F_, N=1, H=16, W=16, Cin=48, Cout=96, split_k=3, res_ld=100, aux=True),
+    'halo_f32_up_auto': _c('conv3x3_halo_f32_kernel<16>', F_, N=1, H=8, W=8, Cin=128, Cout=32, upsample=1),
+    # ---- bf16 halo kernels
+    'halo3_f32in_32': _c('conv3x3_halo3_kernel<false, 32>', B_, N=1, H=8, W=32, Cin=32, Cout=32, in_ld=40, in_off=8, out_ld=48, out_off=8,
+                         res_ld=36),
+    'halo3_bf16in_16': _c('conv3x3_halo3_kernel<true, 16>', B_, N=3, H=16, W=16, Cin=32, Cout=64, in_bf16=True, out_bf16=True),
+    'halo3_bf16in_split': _c('conv3x3_halo3_kernel<true, 32>', B_, N=1, H=8, W=32, Cin=96, Cout=96, in_bf16=True, split_k=3, act=L.ACT_GELU),
+    'halo_bf16_pro_fused': _c('conv3x3_halo3_kernel<false, 16>', B_, N=1, H=16, W=16, Cin=32, Cout=64, pro=True, pro_act=L.PRO_SWISH, stats=True),
+    'halo_bf16_needs_prenorm': _c('(keep_norm_act_bf16 first)', B_, N=1, H=16, W=16, Cin=32, Cout=64, in_bf16=True, pro=True, launch=False),
+    # ---- bf16 gather kernels
+    'bf16_t0': _c('conv_bf16_kernel<4, 1, 1, 1, 64, 1, false>', B_, N=3, H=5, W=7, Cin=24, Cout=20, stride=2, in_ld=28, in_off=4),
+    'bf16_t1_plain': _c('conv_bf16_kernel<2, 2, 1, 1, 64, 1, true>', B_, N=1, H=300, W=1, Cin=80, Cout=48, k=1, in_ld=96, in_off=8, out_ld=56,
+                        out_off=4, res_ld=52, out_bf16=False),
+    'bf16_t1_pro': _c('conv_bf16_kernel<2, 2, 1, 1, 64, 1, false>', B_, N=1, H=5, W=7, Cin=130, Cout=48, k=7, pad=3, pro=True, pro_act=L.PRO_RELU),
+    'bf16_t1_bf16out': _c('conv_bf16_kernel<2, 2, 1, 1, 64, 1, true>', B_, N=1, H=250, W=1, Cin=48, Cout=64, k=1, out_bf16=True),
+    'bf16_t1_bk256': _c('conv_bf16_kernel<2, 2, 1, 1, 256, 1, false>', B_, N=1, H=100, W=1, Cin=512, Cout=64, k=1, bk256=True),
+    'bf16_t2': _c('conv_bf16_kernel<2, 2, 2, 2, 64, 1, true>', B_, N=1, H=4133, W=1, Cin=16, Cout=96, k=1, stats=False),
+    'bf16_t2_up': _c('conv_bf16_kernel<2, 2, 2, 2, 64, 1, false>', B_, N=1, H=33, W=35, Cin=16, Cout=96, upsample=1),
+    'bf16_flatk': _c('conv_bf16_kernel<2, 2, 1, 1, 64, 1, false>', B_, N=1, H=5, W=7, Cin=3, Cout=48),
+    # ---- exact-f32 gather kernels
+    'f32_t0_7x7': _c('conv_f32_kernel<4, 1, 1, 1>', F_, N=1, H=5, W=7, Cin=130, Cout=32, k=7, pad=3, in_ld=132),
+    'f32_t0_down': _c('conv_f32_kernel<4, 1, 1, 1>', F_, N=3, H=10, W=14, Cin=24, Cout=20, stride=2, pad_t=0, pad_l=0, Ho=5, Wo=7,
+                      pro=True, pro_act=L.PRO_SWISH, out_ld=23, out_off=2),
+    'f32_t1': _c('conv_f32_kernel<2, 2, 1, 1>', F_, N=1, H=300, W=1, Cin=80, Cout=48, k=1, in_ld=96, in_off=8, out_ld=56, out_off=4,
+                 res_ld=52, act=L.ACT_GELU),
+    'f32_t1_split': _c('conv_f32_kernel<2, 2, 1, 1>', F_, N=1, H=5, W=7, Cin=48, Cout=48, split_k=4, res_ld=50, aux=True),
+    'f32_t1_autosplit': _c('conv_f32_kernel<2, 2, 1, 1>', F_, N=1, H=8, W=8, Cin=512, Cout=64, k=1),
+    'f32_t1_stats': _c('conv_f32_kernel<2, 2, 1, 1>', F_, N=3, H=8, W=8, Cin=24, Cout=48, k=1, stats=True),
+    'f32_t1_reflect_up': _c('conv_f32_kernel<2, 2, 1, 1>', F_, N=1, H=5, W=7, Cin=10, Cout=40, reflect=True, upsample=1),
+    'f32_t1_flatk': _c('conv_f32_kernel<2, 2, 1, 1>', F_, N=3, H=9, W=11, Cin=3, Cout=36, stride=2),
+    'f32_t2': _c('conv_f32_kernel<2, 2, 2, 2>', F_, N=1, H=777, W=1, Cin=48, Cout=96, k=1, res_ld=96),
+    'f32_t2_x3_fallback': _c('conv_f32_kernel<2, 2, 2, 2>', X_, N=1, H=777, W=1, Cin=40, Cout=130, k=1, in_amax=False),
+}
+
+
+class _Geom:
+    """The derived sizes and the optional-tensor list of one convolution case."""
+
+    def __init__(self, kw):
+        g = dict(k=3, stride=1, in_off=0, out_off=0, res_ld=0, aux=False, pro=False, pro_act=L.PRO_NONE, act=L.ACT_NONE, split_k=0,
+                 stats=False, amax=False, in_amax=False, in2_cin1=0, reflect=False, upsample=0, in_bf16=False, out_bf16=False,
+                 bk256=False, ln=False, flags=0, launch=True)
+        g.update(kw)
+        self.__dict__.update(g)
+        k = self.k
+        pad = g.get('pad', k // 2)
+        self.pad_t, self.pad_l = g.get('pad_t', pad), g.get('pad_l', pad)
+        Hv, Wv = (2 * self.H, 2 * self.W) if self.upsample else (self.H, self.W)
+        self.Ho = g.get('Ho', (Hv + 2 * self.pad_t - k) // self.stride + 1)
+        self.Wo = g.get('Wo', (Wv + 2 * self.pad_l - k) // self.stride + 1)
+        self.cin1 = self.in2_cin1 if self.in2_cin1 else self.Cin           # channels read from `in`
+        self.in_ld = g.get('in_ld', self.cin1)
+        self.out_ld = g.get('out_ld', self.Cout)
+        self.x3 = self.mma == L.MMA_X3 and self.Cin % 16 == 0
+
+
+def _conv_args(g, t):
+    """keep_conv2d_args of case geometry ``g`` on tensors ``t`` (name -> tensor, or name -> fake address for the host-only plan)."""
+    def p(name):
+        v = t.get(name)
+        return v.data_ptr() if isinstance(v, torch.Tensor) else v
+    a = L.conv_args(
+        inp=p('x'), weight=p('w'), bias=p('bias'), out=p('out'), pro_scale=p('pro_scale'), pro_shift=p('pro_shift'), residual=p('res'),
+        aux=p('aux'), workspace=p('ws'), N=g.N, H=g.H, W=g.W, Cin=g.Cin, Cout=g.Cout, KH=g.k, KW=g.k, stride=g.stride, pad_t=g.pad_t,
+        pad_l=g.pad_l, Ho=g.Ho, Wo=g.Wo, in_ld=g.in_ld, out_ld=g.out_ld, res_ld=g.res_ld, upsample=g.upsample, pro_act=g.pro_act,
+        epi_act=g.act, aux_w=0.5, split_k=g.split_k, dtype=L.BF16 if g.in_bf16 else L.F32, mma=g.mma, weight_bf16=p('wb'),
+        stats_out=p('stats'), stats_P=t.get('stats_P', 0), bk256=int(g.bk256), out_dtype=L.BF16 if g.out_bf16 else L.F32,
+        weight_x3=p('wx3'), x3_acc_scale=float(t.get('acc_scale', 1.0)), x3_in_amax=p('in_amax'), x3_out_amax=p('amax'),
+        x3_out_amax_zeroed=1 if g.amax else 0, in2=p('x2'), in2_cin1=g.in2_cin1, pad_mode=L.PAD_REFLECT if g.reflect else L.PAD_ZERO,
+        ln_gamma=p('ln_gamma'), ln_beta=p('ln_beta'), ln_eps=1e-5 if g.ln else 0.0, flags=g.flags, plan_ref_images=0)
+    return a
+
+
+def conv_case_plan(name):
+    """keep_conv2d_plan of a table case without a GPU: pointers only contribute their alignment, so every tensor gets the
+    address it will have modulo 16 (allocations are 16-byte aligned, slices start ``off`` elements in)."""
+    expect, kw = CONV_CASES[name]
+    g = _Geom(kw)
+    base = 0x10000
+    isz = 2 if g.in_bf16 else 4
+    t = {'x': base + g.in_off * isz, 'w': base, 'bias': base, 'out': base + g.out_off * (2 if g.out_bf16 else 4)}
+    if g.pro:
+        t['pro_scale'] = t['pro_shift'] = base
+    if g.res_ld:
+        t['res'] = base
+    if g.aux:
+        t['aux'] = base
+    if g.mma == L.MMA_BF16:
+        t['wb'] = base
+    if g.x3:
+        t['wx3'] = base
+    if g.in_amax:
+        t['in_amax'] = base
+    if g.in2_cin1:
+        t['x2'] = base
+    if g.ln:
+        t['ln_gamma'] = t['ln_beta'] = base
+    if g.split_k > 1:
+        t['ws'] = base
+    return expect, g, L.conv2d_plan(_conv_args(g, t))
+
+
+def _conv_regions(name):
+    expect, g, plan = conv_case_plan(name)
+    assert plan.kernel.decode() == expect, (name, plan.kernel.decode(), expect)
+    tb = CONV_TILE_BYTES
+    idt = BF16 if g.in_bf16 else F32
+    N, Cin, Cout = g.N, g.Cin, g.Cout
+    x = rnd(name + 'x', (N, g.H, g.W, g.cin1), 2.0) + 0.3
+    w = rnd(name + 'w', (Cout, g.k, g.k, Cin), 0.05)
+    R = [FP.single('x', x.to(idt), ld=g.in_ld, off=g.in_off, tile_bytes=tb), FP.single('w', w.reshape(Cout, -1), tile_bytes=tb),
+         FP.single('bias', rnd(name + 'b', (1, Cout)), tile_bytes=tb),
+         FP.output('out', (N * g.Ho * g.Wo, Cout), BF16 if g.out_bf16 else F32, ld=g.out_ld, off=g.out_off, tile_bytes=tb)]
+    extra = {}
+    if g.pro:
+        R.append(FP.single('pro_scale', rnd(name + 'ps', (N, Cin)) * 0.2 + 1, tile_bytes=tb))
+        R.append(FP.single('pro_shift', rnd(name + 'ph', (N, Cin)) * 0.2, tile_bytes=tb))
+    if g.res_ld:
+        R.append(FP.single('res', rnd(name + 'r', (N * g.Ho * g.Wo, Cout)), ld=g.res_ld, tile_bytes=tb))
+    if g.aux:
+        R.append(FP.single('aux', rnd(name + 'a', (N * g.Ho * g.Wo, Cout)), tile_bytes=tb))
+    if g.mma == L.MMA_BF16:
+        R.append(FP.single('wb', w.reshape(Cout, -1).to(BF16), tile_bytes=tb))
+    if g.x3:
+        wsrc = ops.up2_phase_weights(w) if g.upsample == L.UPSAMPLE_X2_PHASES else w
+        sc = ops.x3_scale_for(float(wsrc.abs().max()))
+        wx3 = ops.split_x3(wsrc.reshape(-1, Cin), sc)
+        R.append(FP.single('wx3', wx3.reshape(wx3.shape[0], -1), tile_bytes=tb))
+        extra['acc_scale'] = 1.0 / sc
+    if g.in_amax:      # (any upper bound of max |x| per image works: the true one, in [N] floats with nothing behind it)
+        R.append(FP.single('in_amax', x.reshape(N, -1).abs().amax(1).reshape(1, N), tile_bytes=tb))
+    if g.in2_cin1:
+        R.append(FP.single('x2', rnd(name + 'x2', (N * g.H * g.W, Cin - g.cin1)), tile_bytes=tb))
+    if g.ln:
+        R.append(FP.single('ln_gamma', rnd(name + 'lg', (1, Cout)) * 0.2 + 1, tile_bytes=tb))
+        R.append(FP.single('ln_beta', rnd(name + 'lb', (1, Cout)) * 0.2, tile_bytes=tb))
+    if plan.split_k > 1:      # exactly the bytes the plan reports; scratch, not an output
+        assert plan.workspace_bytes == plan.split_k * N * g.Ho * g.Wo * Cout * 4
+        R.append(FP.output('ws', (1, plan.workspace_bytes // 4), tile_bytes=tb, compare=False))
+    if g.stats:
+        assert plan.stats_P > 0, (name, 'the case asks for statistics the plan cannot emit')
+        R.append(FP.output('stats', (1, N * plan.stats_P * Cout * 2), tile_bytes=tb))
+        extra['stats_P'] = plan.stats_P
+    if g.amax:         # slots 3 .. 3 + N of an 11-slot arena the caller zeroed: the neighbours are other launches' maxima
+        assert plan.out_amax_ok, (name, 'the case asks for x3_out_amax the plan cannot fill')
+        R.append(FP.Region(1, 11, {'amax': (3, N, torch.zeros(1, N))}, F32, 'rw', tb))
+    return g, plan, R, extra
+
+
+@pytest.mark.parametrize('name', [n for n, (_, kw) in CONV_CASES.items() if kw.get('launch', True)])
+def test_conv2d_footprint(name):
+    g, plan, regions, extra = _conv_regions(name)
+
+    def launch(t):
+        a = _conv_args(g, {**t, **extra})
+        pl = L.conv2d_plan(a)
+        sig = (pl.kernel, pl.split_k, pl.workspace_bytes, pl.stats_P, pl.out_amax_ok)
+        assert sig == (plan.kernel, plan.split_k, plan.workspace_bytes, plan.stats_P, plan.out_amax_ok), (name, sig)
+        a.split_k = pl.split_k
+        L.conv2d_launch(a)
+        return sig
+
+    out = FP.run(launch, regions, 'cuda')
+    assert float(out['out'].float().abs().max()) > 0
+
+
+# ------------------------------------------------------------------------------------------------ keep_attention
+def _attn(name, *, mma, B, H, Lq, Lk, D, Dv=None, mode=0, packed=False, o_ld=None, o_off=0, amax=False, in_bf16=False, flags=0, ws=True,
+          T=0, seg_len=0, img_h=0, img_w=0, ksplit=0, shift=0, kv_rot=0, n_img=0, lk_rows=None):
+    return dict(name=name, mma=mma, B=B, H=H, Lq=Lq, Lk=Lk, D=D, Dv=D if Dv is None else Dv, mode=mode, packed=packed, o_ld=o_ld, o_off=o_off,
+                amax=amax, in_bf16=in_bf16, flags=flags, ws=ws, T=T, seg_len=seg_len, img_h=img_h, img_w=img_w, ksplit=ksplit, shift=shift,
+                kv_rot=kv_rot, n_img=n_img, lk_rows=lk_rows)
+
+
+ATTN_CASES = [
+    _attn('f32_ragged', mma=F_, B=2, H=2, Lq=250, Lk=200, D=32, o_ld=72, o_off=4),
+    _attn('f32_dv', mma=F_, B=1, H=1, Lq=250, Lk=200, D=64, Dv=2),
+    _attn('bf16_ragged', mma=B_, B=2, H=2, Lq=250, Lk=200, D=32),
+    _attn('bf16_in', mma=B_, B=1, H=2, Lq=250, Lk=200, D=64, in_bf16=True),
+    _attn('x3_ragged', mma=X_, B=2, H=2, Lq=250, Lk=200, D=32, amax=True, o_ld=72, o_off=4),
+    _attn('x3_dv', mma=X_, B=1, H=1, Lq=250, Lk=200, D=64, Dv=2),
+    _attn('x3_small_heads', mma=X_, B=3, H=8, Lq=200, Lk=250, D=64, amax=True),
+    _attn('x3_no_small', mma=X_, B=1, H=8, Lq=200, Lk=250, D=64, flags=L.ATTN_NO_SMALL),
+    _attn('x3_sfull_two_pass', mma=X_, B=1, H=1, Lq=256, Lk=256, D=512),
+    _attn('x3_sfull2_amax', mma=X_, B=1, H=1, Lq=256, Lk=256, D=512, amax=True),
+    _attn('x3_sfull2', mma=X_, B=1, H=1, Lq=256, Lk=256, D=512, flags=L.ATTN_NO_TWO_PASS),
+    _attn('x3_sfull', mma=X_, B=1, H=1, Lq=256, Lk=256, D=512, flags=L.ATTN_NO_TWO_PASS | L.ATTN_NO_SFULL2),
+    _attn('x3_packed_ws', mma=X_, B=1, H=1, Lq=777, Lk=300, D=128, Dv=64),
+    _attn('x3_no_pack', mma=X_, B=1, H=1, Lq=777, Lk=300, D=128, Dv=64, flags=L.ATTN_NO_PACK),
+    _attn('f32_mode1', mma=F_, B=3, H=2, Lq=200, Lk=400, D=32, mode=1, T=3, seg_len=200, packed=True, lk_rows=200),
+    _attn('x3_mode1', mma=X_, B=3, H=2, Lq=200, Lk=400, D=32, mode=1, T=3, seg_len=200, packed=True, lk_rows=200),
+    _attn('bf16_mode1', mma=B_, B=3, H=2, Lq=200, Lk=400, D=32, mode=1, T=3, seg_len=200, packed=True, lk_rows=200),
+    _attn('f32_mode2', mma=F_, B=8, H=1, Lq=24, Lk=24, D=32, mode=2, img_h=8, img_w=12, ksplit=2, shift=0, kv_rot=1, n_img=2),
+    _attn('x3_mode2_shift', mma=X_, B=8, H=1, Lq=24, Lk=24, D=32, mode=2, img_h=8, img_w=12, ksplit=2, shift=2, kv_rot=1, n_img=2),
+    _attn('f32_mode2_shift', mma=F_, B=8, H=1, Lq=24, Lk=24, D=32, mode=2, img_h=8, img_w=12, ksplit=2, shift=2, kv_rot=1, n_img=2),
+    _attn('x3_mode2', mma=X_, B=8, H=1, Lq=24, Lk=24, D=32, mode=2, img_h=8, img_w=12, ksplit=2, shift=0, kv_rot=0, n_img=2),
+]
+# one attention step touches at most a 128-query tile of q / o and a 32-key tile of k / v rows (<= 3 * 512 floats wide here)
+ATTN_TILE_BYTES = 128 * 3 * 512 * 4
+
+
+@pytest.mark.parametrize('case', ATTN_CASES, ids=[c['name'] for c in ATTN_CASES])
+def test_attention_footprint(case):
+    c = dict(case)
+    B, H, Lq, Lk, D, Dv = c['B'], c['H'], c['Lq'], c['Lk'], c['D'], c['Dv']
+    name, tb = 'at' + c['name'], ATTN_TILE_BYTES
+    idt = BF16 if c['in_bf16'] else F32
+    krows = c['lk_rows'] or Lk                                 # rows of k / v per batch in memory (mode 1: seg_len; keys come from two frames)
+    q, k, v = rnd(name + 'q', (B, Lq, H * D), dtype=idt), rnd(name + 'k', (B, krows, H * D), dtype=idt), rnd(name + 'v', (B, krows, H * Dv), dtype=idt)
+    if c['packed']:        # one [rows, q | k | v] buffer with 4 gap columns on either side: each operand is nobody's surroundings
+        assert krows == Lq
+        ld = 2 * H * D + H * Dv + 8
+        R = [FP.Region(B * Lq, ld, {'q': (4, H * D, q), 'k': (4 + H * D, H * D, k), 'v': (4 + 2 * H * D, H * Dv, v)}, idt, 'r', tb)]
+        qs = ks = vs = (Lq * ld, ld)
+    else:
+        R = [FP.single('q', q, tile_bytes=tb), FP.single('k', k, tile_bytes=tb), FP.single('v', v, tile_bytes=tb)]
+        qs, ks, vs = (Lq * H * D, H * D), (krows * H * D, H * D), (krows * H * Dv, H * Dv)
+    o_ld = c['o_ld'] or H * Dv
+    per_b = c['ksplit'] ** 2 if c['mode'] == 2 else 1          # mode 2: [n_img, img_h * img_w, C] tensors, batch stride = image stride
+    qs, ks, vs = ((s_[0] * per_b, s_[1]) for s_ in (qs, ks, vs))
+    R.append(FP.output('o', (B * Lq, H * Dv), ld=o_ld, off=c['o_off'], tile_bytes=tb))
+    if c['amax']:
+        for n_, t_ in (('q_amax', q), ('k_amax', k), ('v_amax', v)):
+            R.append(FP.single(n_, t_.float().reshape(B, -1).abs().amax(1).reshape(1, B), tile_bytes=tb))
+
+    def args(t):
+        a = L.AttnArgs()
+        a.struct_size = ctypes.sizeof(L.AttnArgs)
+        for f, val in dict(q=t['q'], k=t['k'], v=t['v'], o=t['o'], q_bs=qs[0], q_ts=qs[1], q_hs=D, k_bs=ks[0], k_ts=ks[1], k_hs=D, v_bs=vs[0],
+                           v_ts=vs[1], v_hs=Dv, o_bs=Lq * o_ld * per_b, o_ts=o_ld, o_hs=Dv, B=B, H=H, Lq=Lq, Lk=Lk, D=D, Dv=Dv, scale=1.0 / math.sqrt(D),
+                           mode=c['mode'], T=c['T'], seg_len=c['seg_len'], img_h=c['img_h'], img_w=c['img_w'], ksplit=c['ksplit'],
+                           shift=c['shift'], kv_rot=c['kv_rot'], n_img=c['n_img'], mma=c['mma'], in_dtype=L.BF16 if c['in_bf16'] else L.F32,
+                           q_amax=t.get('q_amax'), k_amax=t.get('k_amax'), v_amax=t.get('v_amax'), flags=c['flags']).items():
+            setattr(a, f, val.data_ptr() if isinstance(val, torch.Tensor) else val)
+        return a
+
+    # the scratch the library asks for with these shapes (pointers do not enter), embedded at exactly that size
+    fake = {n_: 0x10000 for n_ in ('q', 'k', 'v', 'o') + (('q_amax', 'k_amax', 'v_amax') if c['amax'] else ())}
+    need = L.attention_workspace_bytes(args(fake)) if c['ws'] else 0
+    if need:
+        R.append(FP.output('ws', (1, (need + 3) // 4), tile_bytes=tb, compare=False))
+
+    def launch(t):
+        a = args(t)
+        now = L.attention_workspace_bytes(a)
+        assert now == need or not c['ws'], (now, need)
+        if need:
+            a.workspace, a.workspace_bytes = t['ws'].data_ptr(), need
+        L._check(L.load().keep_attention(ctypes.byref(a), L._stream()), 'keep_attention')
+        return now
+
+    out = FP.run(launch, R, 'cuda')
+    assert float(out['o'].abs().max()) > 0
+
+
+def test_attention_cases_reach_the_workspace_forms():
+    """The table's packed-K/V case really gets a workspace from the library, and the NO_PACK twin does not (host-side query)."""
+    def need(c):
+        a = L.AttnArgs()
+        a.struct_size = ctypes.sizeof(L.AttnArgs)
+        for f in ('B', 'H', 'Lq', 'Lk', 'D', 'Dv', 'mode', 'mma', 'flags'):
+            setattr(a, f, c[f])
+        a.q_ts = a.k_ts = c['H'] * c['D']
+        a.v_ts = a.o_ts = c['H'] * c['Dv']
+        a.q_hs = a.k_hs = c['D']
+        a.v_hs = a.o_hs = c['Dv']
+        a.q_bs, a.k_bs, a.v_bs, a.o_bs = c['Lq'] * a.q_ts, c['Lk'] * a.k_ts, c['Lk'] * a.v_ts, c['Lq'] * a.o_ts
+        return L.attention_workspace_bytes(a)
+    by = {c['name']: c for c in ATTN_CASES}
+    assert need(by['x3_packed_ws']) > 0 and need(by['x3_no_pack']) == 0
+    assert need(by['x3_sfull_two_pass']) == 256 * 256 * 4 and need(by['x3_sfull2']) == 0
+
+
+# ------------------------------------------------------------------------------------------------ the flat entry points
+def u8(name, shape):
+    return (op_input('fp:' + name, shape) * 127.5 + 127.5).clamp(0, 255).to(torch.uint8)
+
+
+def _call(fn, *args):
+    L.call(fn, *args)
+
+
+def _in(name, data, **kw):
+    return FP.single(name, data, **kw)
+
+
+def _elementwise(fn, make):
+    """(regions, launch) of one flat case; ``make`` returns them."""
+    return fn, make
+
+
+def _affine_act(n, hw, c):
+    x = rnd('aa', (n, hw, c), 2.0)
+    R = [_in('x', x), _in('s', rnd('aas', (n, c)) + 1.5), _in('h', rnd('aah', (n, c))), FP.output('o', (n * hw, c))]
+    return R, lambda t: _call('keep_affine_act', t['x'], t['s'], t['h'], t['o'], n, hw, c, L.ACT_RELU)
+
+
+def _gm_join(n, hw, c, with_a):
+    R = [_in('a', rnd('ja', (n, hw, c))), _in('b', rnd('jb', (n, hw, c))), _in('sb', rnd('jsb', (n, c)) + 1.5), _in('hb', rnd('jhb', (n, c))),
+         FP.output('o', (n * hw, c))]
+    if with_a:
+        R += [_in('sa', rnd('jsa', (n, c)) + 1.5), _in('ha', rnd('jha', (n, c)))]
+    return R, lambda t: _call('keep_gm_join', t['a'], t.get('sa'), t.get('ha'), t['b'], t['sb'], t['hb'], t['o'], n, hw, c)
+
+
+def _chan_stats(n, hw, c, ld, P):
+    R = [_in('x', rnd('cs', (n * hw, c)), ld=ld), FP.output('part', (1, n * P * c * 2))]
+    return R, lambda t: _call('keep_chan_stats', t['x'], t['part'], n, hw, c, ld, P)
+
+
+def _norm_finalize(n, hw, c, G, P, affine):
+    part = rnd('nf', (n, P, c, 2)).abs() * 3 + 1
+    part[..., 1] = part[..., 1] + part[..., 0] ** 2          # sumsq >= sum^2 / count: a variance that is not negative
+    R = [_in('part', part.reshape(1, -1)), FP.output('scale', (n, c)), FP.output('shift', (n, c))]
+    if affine:
+        R += [_in('g', rnd('nfg', (1, c)) + 1.5), _in('b', rnd('nfb', (1, c)))]
+    return R, lambda t: _call('keep_norm_finalize', t['part'], t.get('g'), t.get('b'), t['scale'], t['shift'], n, hw, c, G, P, 1e-6)
+
+
+def _group_stats(n, hw, c, G):
+    R = [_in('x', rnd('gs', (n, hw, c), 2.0)), _in('g', rnd('gsg', (1, c)) + 1.5), _in('b', rnd('gsb', (1, c))), FP.output('scale', (n, c)),
+         FP.output('shift', (n, c))]
+    return R, lambda t: _call('keep_group_stats', t['x'], t['g'], t['b'], t['scale'], t['shift'], n, hw, c, G, 1e-6)
+
+
+def _norm_act_bf16(n, hw, c, in_bf16):
+    x = rnd('nab', (n, hw, c), 2.0, BF16 if in_bf16 else F32)
+    R = [_in('x', x), _in('s', rnd('nabs', (n, c)) + 1.5), _in('h', rnd('nabh', (n, c))), FP.output('o', (n * hw, c), BF16)]
+    return R, lambda t: _call('keep_norm_act_bf16', t['x'], t['s'], t['h'], t['o'], n, hw, c, L.PRO_SWISH, L.BF16 if in_bf16 else L.F32)
+
+
+def _absmax(n, r, c, ld):
+    R = [_in('x', rnd('am', (n * r, c), 3.0), ld=ld), FP.Region(1, 9, {'amax': (2, n, torch.zeros(1, n))}, F32, 'rw')]
+    return R, lambda t: _call('keep_absmax', t['x'], t['amax'], n, r, c, ld, r * ld, 1)
+
+
+def _layernorm(m, c, res, pos_rows):
+    R = [_in('x', rnd('ln', (m, c), 2.0)), _in('g', rnd('lng', (1, c)) + 1.5), _in('b', rnd('lnb', (1, c))), FP.output('o', (m, c))]
+    if res:
+        R.append(_in('res', rnd('lnr', (m, c))))
+    if pos_rows:
+        R += [_in('pos', rnd('lnp', (pos_rows, c))), FP.output('o2', (m, c))]
+    return R, lambda t: _call('keep_layernorm', t['x'], t['g'], t['b'], t.get('res'), t['o'], t.get('pos'), pos_rows, t.get('o2'), m, c, 1e-5)
+
+
+def _layernorm_amax(n, rows, c):
+    m = n * rows
+    R = [_in('x', rnd('lna', (m, c), 2.0)), _in('g', rnd('lnag', (1, c)) + 1.5), _in('b', rnd('lnab', (1, c))), _in('res', rnd('lnar', (m, c))),
+         FP.output('o', (m, c)), FP.Region(1, 9, {'amax': (2, n, torch.zeros(1, n))}, F32, 'rw')]
+    return R, lambda t: _call('keep_layernorm_amax', t['x'], t['g'], t['b'], t['res'], t['o'], m, c, 1e-5, rows, t['amax'], 1)
+
+
+def _geglu(m, f):
+    R = [_in('x', rnd('gg', (m, 2 * f), 2.0)), FP.output('o', (m, f))]
+    return R, lambda t: _call('keep_geglu', t['x'], t['o'], m, f)
+
+
+def _geglu_amax(n, rows, f):
+    R = [_in('x', rnd('gga', (n * rows, 2 * f), 2.0)), FP.output('o', (n * rows, f)), FP.Region(1, 9, {'amax': (2, n, torch.zeros(1, n))}, F32, 'rw')]
+    return R, lambda t: _call('keep_geglu_amax', t['x'], t['o'], n, rows, f, t['amax'], 1)
+
+
+def _argmax_gather(m, ncodes, dim):
+    R = [_in('logits', rnd('ag', (m, ncodes), 4.0)), _in('cb', rnd('agc', (ncodes, dim))), FP.output('idx', (1, m), torch.int32),
+         FP.output('margin', (1, m)), FP.output('o', (m, dim)),
+         FP.Region(1, 5, {'status': (1, 1, torch.zeros(1, 1, dtype=torch.int32))}, torch.int32, 'rw')]
+    return R, lambda t: _call('keep_argmax_gather', t['logits'], t['cb'], None, t['idx'], t['margin'], t['o'], m, ncodes, dim, t['status'])
+
+
+def _nonfinite_flag(n):
+    R = [_in('x', rnd('nff', (1, n))), FP.Region(1, 5, {'status': (1, 1, torch.zeros(1, 1, dtype=torch.int32))}, torch.int32, 'rw')]
+    return R, lambda t: _call('keep_nonfinite_flag', t['x'], n, t['status'])
+
+
+def _vq_nearest(m, ncodes, dim):
+    R = [_in('z', rnd('vq', (m, dim))), _in('cb', rnd('vqc', (ncodes, dim))), FP.output('idx', (1, m), torch.int32)]
+    return R, lambda t: _call('keep_vq_nearest', t['z'], t['cb'], t['idx'], m, ncodes, dim)
+
+
+def _kalman(n, hw, c):
+    R = [_in('a', rnd('ka', (n, hw, c))), _in('b', rnd('kb', (n, hw, c))), _in('g', rnd('kg', (n, hw)).abs()), FP.output('o', (n * hw, c))]
+    return R, lambda t: _call('keep_kalman_update', t['a'], t['b'], t['g'], t['o'], n, hw, c)
+
+
+def _flow_warp(n, h, w, c):
+    # flow up to +-1.5 image sizes: most samples straddle or leave the border, where the zero-padding clamps live
+    flow = rnd('fw', (n, h, w, 2)) * torch.tensor([1.5 * w, 1.5 * h])
+    flow[0, 0, 0] = torch.tensor([-0.5, -0.5])
+    flow[0, h - 1, w - 1] = torch.tensor([0.5, 0.5])
+    R = [_in('x', rnd('fwx', (n * h * w, c))), _in('flow', flow.reshape(-1, 2)), FP.output('o', (n * h * w, c))]
+    return R, lambda t: _call('keep_flow_warp', t['x'], t['flow'], t['o'], n, h, w, c)
+
+
+def _convex_upsample(n, h, w, k):
+    R = [_in('mask', rnd('cu', (n * h * w, 9 * k * k), 3.0)), _in('flow', rnd('cuf', (n * h * w, 2), 5.0)), FP.output('o', (n * k * h * k * w, 2))]
+    return R, lambda t: _call('keep_convex_upsample', t['mask'], t['flow'], t['o'], n, h, w, k)
+
+
+def _bilinear_upscale(planes, h, w, s):
+    R = [_in('x', rnd('bu', (planes * h, w))), FP.output('o', (planes * h * s, w * s))]
+    return R, lambda t: _call('keep_bilinear_upscale', t['x'], t['o'], planes, h, w, s)
+
+
+def _nchw_to_nhwc(n, c, hw, mode):
+    R = [_in('x', rnd('cl', (n * c, hw))), FP.output('o', (n * hw, c))]
+    return R, lambda t: _call('keep_nchw_to_nhwc', t['x'], t['o'], n, c, hw, mode)
+
+
+def _nhwc_to_nchw(n, c, hw):
+    R = [_in('x', rnd('cf', (n * hw, c))), FP.output('o', (n * c, hw))]
+    return R, lambda t: _call('keep_nhwc_to_nchw', t['x'], t['o'], n, c, hw)
+
+
+def _rgb_s2d(n, h, w):
+    R = [_in('x', rnd('s2d', (n * 3 * h, w))), FP.output('o', (n * (h // 2) * (w // 2), 16))]
+    return R, lambda t: _call('keep_rgb_s2d', t['x'], t['o'], n, h, w)
+
+
+def _add_bcast(total, tsize):
+    R = [_in('a', rnd('ab', (1, total))), _in('t', rnd('abt', (1, tsize))), FP.output('o', (1, total))]
+    return R, lambda t: _call('keep_add_bcast', t['a'], t['t'], t['o'], total, tsize, -0.5)
+
+
+def _concat2(m, c1, c2, ld):
+    R = [_in('a', rnd('c2a', (m, c1))), _in('b', rnd('c2b', (m, c2))), FP.output('o', (m, ld))]
+    return R, lambda t: _call('keep_concat2', t['a'], t['b'], t['o'], m, c1, c2, ld)
+
+
+def _tensor2img(npix):
+    R = [_in('x', rnd('t2i', (npix, 3), 1.2)), FP.output('o', (npix, 3), torch.uint8)]
+    return R, lambda t: _call('keep_tensor2img', t['x'], t['o'], npix)
+
+
+def _img2tensor(npix, fn='keep_img2tensor'):
+    R = [_in('x', u8('i2t', (npix, 3))), FP.output('o', (npix, 3))]
+    return R, lambda t: _call(fn, t['x'], t['o'], npix)
+
+
+def _comfy_to_bgr(npix):
+    R = [_in('x', rnd('c2b8', (npix, 3)).abs()), FP.output('o', (npix, 3), torch.uint8)]
+    return R, lambda t: _call('keep_comfy_to_bgr_u8', t['x'], t['o'], npix)
+
+
+def _channel_argmax(m, c, ld):
+    R = [_in('x', rnd('ca', (m, c)), ld=ld), FP.output('o', (1, m), torch.uint8)]
+    return R, lambda t: _call('keep_channel_argmax', t['x'], t['o'], m, c, ld)
+
+
+def _maxpool3s2(n, h, w, c):
+    R = [_in('x', rnd('mp', (n * h * w, c))), FP.output('o', (n * ((h - 1) // 2 + 1) * ((w - 1) // 2 + 1), c))]
+    return R, lambda t: _call('keep_maxpool3s2', t['x'], t['o'], n, h, w, c)
+
+
+def _dwconv(n, h, w, c, stride):
+    ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
+    R = [_in('x', rnd('dw', (n * h * w, c))), _in('w', rnd('dww', (9, c))), _in('b', rnd('dwb', (1, c))), FP.output('o', (n * ho * wo, c))]
+    return R, lambda t: _call('keep_dwconv3x3', t['x'], t['w'], t['b'], t['o'], n, h, w, c, stride, L.ACT_LRELU01)
+
+
+def _maxpool2d(n, h, w, c, in_ld, out_ld, k, stride, pad, ceil):
+    f = math.ceil if ceil else math.floor
+    ho, wo = f((h + 2 * pad - k) / stride) + 1, f((w + 2 * pad - k) / stride) + 1
+    R = [_in('x', rnd('m2', (n * h * w, c)), ld=in_ld, off=in_ld - c - 4 if in_ld > c + 4 else 0),
+         FP.output('o', (n * ho * wo, c), ld=out_ld, off=out_ld - c if out_ld > c else 0)]
+    return R, lambda t: _call('keep_maxpool2d', t['x'], t['o'], n, h, w, c, in_ld, out_ld, k, stride, pad, ho, wo)
+
+
+def _slice_copy(n, h, w, c, src_ld, dst_ld, up):
+    hs, ws_ = (h >> up, w >> up)
+    R = [_in('src', rnd('sc', (n * hs * ws_, c)), ld=src_ld, off=src_ld - c), FP.output('dst', (n * h * w, c), ld=dst_ld, off=4)]
+    return R, lambda t: _call('keep_slice_copy', t['src'], t['dst'], n, h, w, c, src_ld, dst_ld, up)
+
+
+def _channel_shuffle2(rows, half, a_ld, b_ld):
+    R = [_in('a', rnd('sha', (rows, half)), ld=a_ld), _in('b', rnd('shb', (rows, half)), ld=b_ld, off=b_ld - half), FP.output('o', (rows, 2 * half))]
+    return R, lambda t: _call('keep_channel_shuffle2', t['a'], t['b'], t['o'], rows, half, a_ld, b_ld)
+
+
+def _yolo_decode(n, ny, nx):
+    rows_total = 3 * ny * nx + 7
+    R = [_in('raw', rnd('yd', (n * ny * nx, 48), 3.0)), _in('anch', rnd('yda', (1, 6)).abs() * 30 + 4),
+         FP.output('pred', (n * rows_total, 16), init=torch.zeros(n * rows_total, 16))]
+    return R, lambda t: _call('keep_yolo_decode', t['raw'], t['pred'], n, ny, nx, 8.0, t['anch'], 5, rows_total)
+
+
+def _yolo_letterbox(n, h, w, rh, rw, top, left, h2, w2):
+    R = [_in('x', u8('lb', (n * h * w, 3))), FP.output('o', (n * h2 * w2, 3))]
+    return R, lambda t: _call('keep_yolo_letterbox_u8', t['x'], t['o'], n, h, w, rh, rw, top, left, h2, w2, 1)
+
+
+def _canon_dets(n, cap):
+    """keep_yolo_select / keep_retina_decode append their survivors in ARRIVAL order (one atomic counter per frame; the ABI says so and
+    keep_retina_nms orders them afterwards): the rows of a frame are a set.  Compared: the counts, and -- for frames whose survivors
+    all fit -- the rows sorted by their last column (the unique row / anchor index).  Which rows an overflowing frame drops is
+    open, so only its count is compared."""
+    def canon(outs):
+        cnt = outs['counts'].reshape(-1).tolist()
+        d = outs['dets'].reshape(n, cap, 16)
+        rows = [d[i, :c][torch.argsort(d[i, :c, 15])] if c <= cap else d[i, :0] for i, c in enumerate(cnt)]
+        return {'counts': outs['counts'], 'dets': torch.cat(rows)}
+    return canon
+
+
+def _yolo_select(n, p, cap):
+    pred = rnd('ys', (n, p, 16)).abs()
+    R = [_in('pred', pred.reshape(n * p, 16)), FP.output('dets', (n * cap, 16), init=torch.zeros(n * cap, 16)),
+         FP.Region(1, n + 4, {'counts': (2, n, torch.zeros(1, n, dtype=torch.int32))}, torch.int32, 'rw')]
+    return R, lambda t: _call('keep_yolo_select', t['pred'], t['dets'], t['counts'], n, p, cap, 0.3), _canon_dets(n, cap)
+
+
+def _upsample_add(n, h, w, hb, wb, c):
+    R = [_in('a', rnd('ua', (n * h * w, c))), _in('b', rnd('ub', (n * hb * wb, c))), FP.output('o', (n * h * w, c))]
+    return R, lambda t: _call('keep_upsample_add', t['a'], t['b'], t['o'], n, h, w, hb, wb, c)
+
+
+def _act_inplace(n, act):
+    R = [FP.single('x', rnd('ai', (1, n), 3.0), role='rw')]
+    return R, lambda t: _call('keep_act_inplace', t['x'], n, act)
+
+
+def _sorted_dets(n, cap, cnt):
+    """Distinct, descending-free scores and plausible boxes: dets [n, cap, 16] with cnt[i] valid rows."""
+    d = rnd('nms', (n, cap, 16)).abs() * 40
+    d[..., 2:4] = d[..., 0:2] + 10 + rnd('nmsw', (n, cap, 2)).abs() * 30
+    d[..., 4] = torch.linspace(0.05, 0.95, n * cap)[torch.from_numpy(np.random.RandomState(0).permutation(n * cap))].reshape(n, cap)
+    d[..., 15] = torch.arange(cap, dtype=torch.float32)
+    return d
+
+
+def _retina_nms(n, cap, cnt, ordered):
+    d = _sorted_dets(n, cap, cnt)
+    counts = torch.tensor([cnt], dtype=torch.int32).repeat(1, n)
+    counts[0, -1] = max(cnt - 3, 0)
+    R = [_in('dets', d.reshape(n * cap, 16)), _in('counts', counts), FP.output('o', (n * cap, 16), init=torch.zeros(n * cap, 16)),
+         FP.output('oc', (1, n), torch.int32)]
+    if ordered:
+        order = torch.stack([torch.argsort(d[i, :, 4], descending=True).to(torch.int32) for i in range(n)])
+        # ranks 0 .. counts[n] must name valid rows: order the valid rows only
+        order = torch.stack([torch.argsort(torch.where(torch.arange(cap) < int(counts[0, i]), d[i, :, 4], torch.tensor(-1.0)),
+                                           descending=True).to(torch.int32) for i in range(n)])
+        R.append(_in('order', order.reshape(n, cap)))
+        return R, lambda t: _call('keep_retina_nms_ordered', t['dets'], t['counts'], t['order'], t['o'], t['oc'], n, cap, 0.4)
+    return R, lambda t: _call('keep_retina_nms', t['dets'], t['counts'], t['o'], t['oc'], n, cap, 0.4)
+
+
+def _retina_decode(n, p, cap):
+    R = [_in('heads', rnd('rd', (n * p, 32), 2.0)), _in('priors', rnd('rdp', (2 * p, 4)).abs() * 0.5 + 0.05),
+         FP.output('dets', (n * cap, 16), init=torch.zeros(n * cap, 16)),
+         FP.Region(1, n + 4, {'counts': (2, n, torch.zeros(1, n, dtype=torch.int32))}, torch.int32, 'rw')]
+    return R, lambda t: _call('keep_retina_decode', t['heads'], t['priors'], t['dets'], t['counts'], n, p, cap, 0.1, 0.2, 640.0, 480.0, 0.5), _canon_dets(n, cap)
+
+
+def _gauss(ntap):
+    x = torch.arange(ntap, dtype=torch.float32) - ntap // 2
+    k = torch.exp(-x * x / (2 * (0.3 * ((ntap - 1) * 0.5 - 1) + 0.8) ** 2))
+    return (k / k.sum()).reshape(1, ntap)
+
+
+def _sep_filter(n, h, w, ntap, classes):
+    R = [_in('kern', _gauss(ntap)), FP.output('tmp', (n * h, w), compare=False), FP.output('dst', (n * h, w))]
+    if classes:
+        R += [_in('cls', (u8('sfc', (n * h, w)) % 19)), _in('lut', rnd('sfl', (1, 19)).abs() * 255)]
+        return R, lambda t: _call('keep_sep_filter', None, t['cls'], t['lut'], t['tmp'], t['dst'], n, h, w, t['kern'], ntap)
+    R.append(_in('src', rnd('sfs', (n * h, w)).abs() * 255))
+    return R, lambda t: _call('keep_sep_filter', t['src'], None, None, t['tmp'], t['dst'], n, h, w, t['kern'], ntap)
+
+
+def _u8_to_f32(n):
+    R = [_in('x', u8('u2f', (1, n))), FP.output('o', (1, n))]
+    return R, lambda t: _call('keep_u8_to_f32', t['x'], t['o'], n)
+
+
+def _f32_round_u8(n):
+    R = [_in('x', rnd('f2u', (1, n), 300.0)), FP.output('o', (1, n), torch.uint8)]
+    return R, lambda t: _call('keep_f32_round_u8', t['x'], t['o'], n)
+
+
+def _d2s(m):
+    return (ctypes.c_double * 6)(*m)
+
+
+# destination -> source maps: a rotation + scale whose source window hangs over the frame edge on two sides
+_HANG = (0.93, -0.37, -6.3, 0.37, 0.93, -4.8)
+
+
+def _warp_affine(h, w, dh, dw, m):
+    R = [_in('src', u8('wa', (h * w, 3))), FP.output('dst', (dh * dw, 3), torch.uint8)]
+    return R, lambda t: _call('keep_warp_affine_u8', t['src'], h, w, t['dst'], dh, dw, _d2s(m), 135, 133, 132)
+
+
+def _warp_ones(h, w, fh, fw, m):
+    R = [FP.output('dst', (h, w))]
+    return R, lambda t: _call('keep_warp_ones', t['dst'], h, w, fh, fw, _d2s(m))
+
+
+def _erode(h, w, k):
+    R = [_in('src', (rnd('er', (h, w)) > -0.6).float()), FP.output('tmp', (h, w), compare=False), FP.output('dst', (h, w))]
+    return R, lambda t: _call('keep_erode_rect', t['src'], t['tmp'], t['dst'], h, w, k)
+
+
+def _draw_box(h, w, fh, fw, m, box):
+    R = [FP.single('frame', u8('db', (h * w, 3)), role='rw')]
+    return R, lambda t: _call('keep_draw_box', t['frame'], h, w, fh, fw, 2, _d2s(m), *box)
+
+
+def _paste_face(h, w, fh, fw, m, box, frame_mask):
+    R = [FP.single('frame', rnd('pf', (h * w, 3)).abs() * 255, role='rw'), _in('face', u8('pff', (fh * fw, 3)))]
+    if frame_mask:      # a soft mask already in frame space [H, W]
+        R.append(_in('mask', rnd('pfm', (h, w)).abs()))
+    else:
+        R.append(_in('mask', rnd('pfm', (fh, fw)).abs() * 255))
+    return R, lambda t: _call('keep_paste_face', t['frame'], h, w, t['face'], t['mask'], fh, fw, _d2s(m), *box, -1 if frame_mask else 3)
+
+
+def _lanczos(n, h, w, h2, w2):
+    lib = L.load(check_device=False)
+
+    def table(S, D):
+        ofs, coef = np.zeros(D, np.int32), np.zeros(D * 8, np.int16)
+        assert lib.keep_lanczos4_tables(S, D, ofs.ctypes.data, coef.ctypes.data) == 0
+        return torch.from_numpy(ofs).reshape(1, D), torch.from_numpy(coef).reshape(D, 8)
+    (xo, xc), (yo, yc) = table(w, w2), table(h, h2)
+    R = [_in('src', u8('lz', (n * h * w, 3))), _in('xo', xo), _in('xc', xc), _in('yo', yo), _in('yc', yc), FP.output('dst', (n * h2 * w2, 3), torch.uint8)]
+    return R, lambda t: _call('keep_resize_lanczos4_u8', t['src'], t['dst'], n, h, w, h2, w2, t['xo'], t['xc'], t['yo'], t['yc'])
+
+
+def _token_linear(m, n_out, out_bf16):
+    R = [_in('x', rnd('tl', (m, 128))), _in('w', rnd('tlw', (n_out, 128), 0.1, BF16)), _in('b', rnd('tlb', (1, n_out))),
+         FP.output('o', (m, n_out), BF16 if out_bf16 else F32)]
+    return R, lambda t: _call('keep_token_linear', t['x'], t['w'], t['b'], t['o'], m, 128, n_out, L.BF16 if out_bf16 else L.F32)
+
+
+def _gm_mlp(m):
+    C = 128
+    R = [_in('a', rnd('ma', (m, C))), _in('b', rnd('mb', (m, C))), _in('w0', rnd('mw0', (8 * C, 2 * C), 0.05, BF16)),
+         _in('w2', rnd('mw2', (C, 8 * C), 0.05, BF16)), FP.output('o', (m, C))]
+    return R, lambda t: _call('keep_gm_mlp', t['a'], t['b'], t['w0'], t['w2'], t['o'], m, C)
+
+
+def _gm_ffn_x3(m, hidden):
+    C = 128
+    w0, w2 = rnd('fw0', (hidden, 2 * C), 0.05), ops.ffn_w2_perm(rnd('fw2', (C, hidden), 0.05))
+    s0, s2 = ops.x3_scale_for(float(w0.abs().max())), ops.x3_scale_for(float(w2.abs().max()))
+    w0x, w2x = ops.split_x3(w0, s0), ops.split_x3(w2, s2)
+    R = [_in('src', rnd('fs', (m, C))), _in('msg', rnd('fm', (m, C))), _in('w0', w0x.reshape(hidden, -1)), _in('w2', w2x.reshape(C, -1)),
+         _in('g', rnd('fg', (1, C)) * 0.2 + 1), _in('b', rnd('fb', (1, C)) * 0.2), FP.output('o', (m, C))]
+    return R, lambda t: _call('keep_gm_ffn_x3', t['src'], t['msg'], t['w0'], 1.0 / s0, t['w2'], 1.0 / s2, t['g'], t['b'], 1e-5, t['o'], m, C, hidden, 0)
+
+
+# entry point -> [(case id, builder)]: one aligned and one ragged size each (element counts that are no multiple of 4, odd H / W,
+# C off the vector width where the ABI allows it, M off the block), border-crossing geometry for the samplers
+FLAT_CASES = {
+    'keep_chan_stats': [('aligned', lambda: _chan_stats(2, 256, 64, 64, 4)), ('ragged', lambda: _chan_stats(3, 35, 6, 9, 2))],
+    'keep_norm_finalize': [('gn32', lambda: _norm_finalize(2, 256, 64, 32, 4, True)), ('in', lambda: _norm_finalize(3, 35, 6, 6, 2, False))],
+    'keep_group_stats': [('aligned', lambda: _group_stats(2, 64, 64, 32)), ('ragged', lambda: _group_stats(3, 35, 12, 3))],
+    'keep_affine_act': [('aligned', lambda: _affine_act(2, 64, 32)), ('ragged', lambda: _affine_act(3, 35, 6))],
+    'keep_norm_act_bf16': [('aligned', lambda: _norm_act_bf16(2, 64, 32, False)), ('ragged_bf16in', lambda: _norm_act_bf16(3, 35, 8, True))],
+    'keep_gm_mlp': [('aligned', lambda: _gm_mlp(256)), ('ragged', lambda: _gm_mlp(300))],
+    'keep_gm_ffn_x3': [('aligned', lambda: _gm_ffn_x3(256, 256)), ('ragged', lambda: _gm_ffn_x3(777, 96))],
+    'keep_token_linear': [('aligned', lambda: _token_linear(256, 128, False)), ('ragged_bf16out', lambda: _token_linear(777, 384, True))],
+    'keep_gm_join': [('aligned', lambda: _gm_join(2, 64, 32, True)), ('ragged_identity', lambda: _gm_join(3, 35, 6, False))],
+    'keep_absmax': [('aligned', lambda: _absmax(2, 64, 32, 32)), ('ragged', lambda: _absmax(3, 35, 6, 9))],
+    'keep_layernorm': [('aligned', lambda: _layernorm(64, 128, True, 16)), ('ragged', lambda: _layernorm(35, 36, False, 0))],
+    'keep_geglu': [('aligned', lambda: _geglu(64, 128)), ('ragged', lambda: _geglu(35, 20))],
+    'keep_layernorm_amax': [('aligned', lambda: _layernorm_amax(2, 64, 128)), ('ragged', lambda: _layernorm_amax(3, 35, 36))],
+    'keep_geglu_amax': [('aligned', lambda: _geglu_amax(2, 64, 128)), ('ragged', lambda: _geglu_amax(3, 35, 20))],
+    'keep_argmax_gather': [('aligned', lambda: _argmax_gather(64, 1024, 256)), ('ragged', lambda: _argmax_gather(35, 1024, 256))],
+    'keep_nonfinite_flag': [('aligned', lambda: _nonfinite_flag(4096)), ('ragged', lambda: _nonfinite_flag(777))],
+    'keep_vq_nearest': [('aligned', lambda: _vq_nearest(64, 1024, 256)), ('ragged', lambda: _vq_nearest(35, 1024, 256))],
+    'keep_kalman_update': [('aligned', lambda: _kalman(2, 64, 32)), ('ragged', lambda: _kalman(3, 35, 6))],
+    'keep_flow_warp': [('aligned', lambda: _flow_warp(2, 8, 16, 4)), ('ragged_3ch', lambda: _flow_warp(3, 5, 7, 3)),
+                       ('one_pixel', lambda: _flow_warp(1, 1, 1, 3))],
+    'keep_convex_upsample': [('aligned', lambda: _convex_upsample(2, 8, 8, 4)), ('ragged', lambda: _convex_upsample(3, 5, 7, 8))],
+    'keep_bilinear_upscale': [('aligned', lambda: _bilinear_upscale(3, 8, 8, 4)), ('ragged', lambda: _bilinear_upscale(9, 5, 7, 4))],
+    'keep_nchw_to_nhwc': [('aligned', lambda: _nchw_to_nhwc(2, 16, 64, 0)), ('ragged_gm', lambda: _nchw_to_nhwc(3, 3, 35, 1))],
+    'keep_rgb_s2d': [('aligned', lambda: _rgb_s2d(2, 16, 16)), ('ragged', lambda: _rgb_s2d(3, 10, 14))],
+    'keep_nhwc_to_nchw': [('aligned', lambda: _nhwc_to_nchw(2, 32, 64)), ('ragged', lambda: _nhwc_to_nchw(3, 3, 35))],
+    'keep_add_bcast': [('aligned', lambda: _add_bcast(4096, 256)), ('ragged', lambda: _add_bcast(777, 37))],
+    'keep_concat2': [('aligned', lambda: _concat2(64, 128, 2, 144)), ('ragged', lambda: _concat2(35, 5, 2, 9))],
+    'keep_tensor2img': [('aligned', lambda: _tensor2img(256)), ('ragged', lambda: _tensor2img(35))],
+    'keep_img2tensor': [('aligned', lambda: _img2tensor(256)), ('ragged', lambda: _img2tensor(35))],
+    'keep_bgr_u8_to_comfy': [('aligned', lambda: _img2tensor(256, 'keep_bgr_u8_to_comfy')), ('ragged', lambda: _img2tensor(35, 'keep_bgr_u8_to_comfy'))],
+    'keep_comfy_to_bgr_u8': [('aligned', lambda: _comfy_to_bgr(256)), ('ragged', lambda: _comfy_to_bgr(35))],
+    'keep_channel_argmax': [('aligned', lambda: _channel_argmax(256, 19, 32)), ('ragged', lambda: _channel_argmax(35, 19, 19))],
+    'keep_maxpool3s2': [('aligned', lambda: _maxpool3s2(2, 8, 8, 64)), ('ragged', lambda: _maxpool3s2(3, 5, 7, 12))],
+    'keep_dwconv3x3': [('aligned', lambda: _dwconv(2, 8, 8, 32, 1)), ('ragged_s2', lambda: _dwconv(3, 5, 7, 12, 2))],
+    'keep_retina_nms': [('aligned', lambda: _retina_nms(2, 64, 64, False)), ('ragged', lambda: _retina_nms(3, 50, 37, False))],
+    'keep_retina_nms_ordered': [('aligned', lambda: _retina_nms(2, 64, 64, True)), ('ragged', lambda: _retina_nms(3, 50, 37, True))],
+    'keep_maxpool2d': [('stem_ceil', lambda: _maxpool2d(3, 5, 7, 8, 8, 16, 2, 2, 0, True)), ('spp', lambda: _maxpool2d(1, 5, 7, 4, 16, 16, 5, 1, 2, False))],
+    'keep_slice_copy': [('aligned', lambda: _slice_copy(2, 8, 8, 32, 32, 64, 0)), ('ragged_up', lambda: _slice_copy(3, 10, 14, 4, 12, 24, 1))],
+    'keep_channel_shuffle2': [('aligned', lambda: _channel_shuffle2(64, 32, 64, 32)), ('ragged', lambda: _channel_shuffle2(35, 4, 12, 12))],
+    'keep_yolo_decode': [('aligned', lambda: _yolo_decode(2, 8, 8)), ('ragged', lambda: _yolo_decode(3, 5, 7))],
+    'keep_yolo_letterbox_u8': [('resize', lambda: _yolo_letterbox(2, 20, 30, 16, 24, 4, 4, 24, 32)), ('copy_ragged', lambda: _yolo_letterbox(3, 5, 7, 5, 7, 1, 0, 7, 7)),
+                               ('one_pixel', lambda: _yolo_letterbox(1, 9, 11, 1, 1, 0, 0, 1, 1))],
+    'keep_yolo_select': [('aligned', lambda: _yolo_select(2, 256, 64)), ('ragged_overflow', lambda: _yolo_select(3, 35, 5))],
+    'keep_upsample_add': [('aligned', lambda: _upsample_add(2, 10, 14, 5, 7, 64)), ('ragged', lambda: _upsample_add(3, 9, 13, 5, 7, 12))],
+    'keep_act_inplace': [('aligned', lambda: _act_inplace(4096, L.ACT_RELU)), ('ragged', lambda: _act_inplace(780, L.ACT_SILU))],
+    'keep_retina_decode': [('aligned', lambda: _retina_decode(2, 256, 64)), ('ragged_overflow', lambda: _retina_decode(3, 35, 5))],
+    'keep_sep_filter': [('float', lambda: _sep_filter(2, 16, 16, 5, False)), ('classes_ragged', lambda: _sep_filter(3, 5, 7, 9, True))],
+    'keep_u8_to_f32': [('aligned', lambda: _u8_to_f32(4096)), ('ragged', lambda: _u8_to_f32(777))],
+    'keep_f32_round_u8': [('aligned', lambda: _f32_round_u8(4096)), ('ragged', lambda: _f32_round_u8(777))],
+    'keep_warp_affine_u8': [('inside', lambda: _warp_affine(16, 16, 8, 8, (1, 0, 2.5, 0, 1, 3.25))), ('hangs_over', lambda: _warp_affine(13, 17, 11, 9, _HANG)),
+                            ('one_pixel', lambda: _warp_affine(5, 7, 1, 1, (1, 0, 6.5, 0, 1, 4.5)))],
+    'keep_warp_ones': [('inside', lambda: _warp_ones(16, 16, 8, 8, (1, 0, -2.5, 0, 1, -3.25))), ('off_frame', lambda: _warp_ones(13, 17, 11, 9, _HANG))],
+    'keep_draw_box': [('inside', lambda: _draw_box(16, 16, 8, 8, (1, 0, -2.5, 0, 1, -3.25), (2, 3, 12, 13))),
+                      ('edge', lambda: _draw_box(13, 17, 11, 9, _HANG, (0, 0, 17, 13)))],
+    'keep_erode_rect': [('aligned', lambda: _erode(16, 16, 3)), ('k_larger_than_image', lambda: _erode(5, 7, 9))],
+    'keep_paste_face': [('inside', lambda: _paste_face(16, 16, 8, 8, (1, 0, -2.5, 0, 1, -3.25), (2, 3, 12, 13), False)),
+                        ('over_the_edge', lambda: _paste_face(13, 17, 11, 9, _HANG, (0, 0, 17, 13), False)),
+                        ('frame_mask', lambda: _paste_face(13, 17, 11, 9, _HANG, (5, 0, 17, 9), True))],
+    'keep_resize_lanczos4_u8': [('up', lambda: _lanczos(2, 8, 8, 16, 16)), ('ragged', lambda: _lanczos(3, 5, 7, 3, 100)), ('one_pixel', lambda: _lanczos(1, 5, 7, 1, 1))],
+}
+# launchers the convolution / attention tables above cover
+STRUCT_LAUNCHERS = {'keep_conv2d': CONV_CASES, 'keep_attention': ATTN_CASES}
+# entry points of include/keep_hip.h that launch nothing (host-only C)
+HOST_ONLY = {'keep_abi_version', 'keep_last_error', 'keep_device_ok', 'keep_sizeof_conv2d_args', 'keep_sizeof_attention_args',
+             'keep_conv2d_plan', 'keep_attention_workspace_bytes', 'keep_lanczos4_tables'}
+
+
+@pytest.mark.parametrize('fn,case', [(fn, cid) for fn, cases in FLAT_CASES.items() for cid, _ in cases])
+def test_flat_op_footprint(fn, case):
+    regions, launch, *canon = dict(FLAT_CASES[fn])[case]()
+    # outputs the kernel legitimately leaves partly unwritten (rows beyond a count) were given an initial value; everything else
+    # must come out finite
+    FP.run(launch, regions, 'cuda', canon=canon[0] if canon else None)

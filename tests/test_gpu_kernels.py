@@ -1838,3 +1838,144 @@ def test_winograd_x3_microkernel_vs_fp64(hw, cin, cout, swish):
     ref = F.conv2d(a.permute(0, 3, 1, 2), w.double().permute(0, 3, 1, 2), bias.double(), padding=1).permute(0, 2, 3, 1)
     err = (y.double() - ref).abs().max().item()
     assert torch.isfinite(y).all() and err <= 4e-6 * max(1.0, ref.abs().max().item()), err
+
+
+# ------------------------------------------------------------------------------------------------ kernels that were only ever judged inside a network
+def call_out(fn, out, *args):
+    L.call(fn, *args)
+    torch.cuda.synchronize()
+    return out.cpu()
+
+
+@pytest.mark.parametrize("n,h,w,c,groups", [(2, 16, 16, 64, 32), (3, 13, 11, 96, 32), (2, 16, 16, 24, 0), (1, 13, 11, 6, 0)])
+def test_chan_stats_and_norm_finalize_on_their_own_output(n, h, w, c, groups):
+    """keep_chan_stats + keep_norm_finalize as ops.norm_affine launches them (P = max(1, min(HW // 64, 1024)) chunks; 13 x 11 = 143
+    pixels in 2 chunks: P does not divide HW), judged on their own scale / shift against fp64 two-pass statistics -- GroupNorm(32,
+    eps 1e-6) with affine parameters and InstanceNorm2d(eps 1e-5) (groups = 0 here: one group per channel, no affine)."""
+    inorm = groups == 0
+    G, eps = (c, 1e-5) if inorm else (groups, 1e-6)
+    x = rnd('csx', (n, h, w, c), 2.0) + 0.3
+    gamma, beta = (None, None) if inorm else (rnd('csg', (c,)) * 0.2 + 1, rnd('csb', (c,)) * 0.2)
+    HW = h * w
+    P = max(1, min(HW // 64, 1024))
+    assert (HW % P != 0) == (HW == 143)
+    xd = dev(x)
+    part = torch.empty((n, P, c, 2), device='cuda')
+    scale, shift = torch.empty((n, c), device='cuda'), torch.empty((n, c), device='cuda')
+    L.call('keep_chan_stats', xd, part, n, HW, c, c, P)
+    L.call('keep_norm_finalize', part, None if inorm else dev(gamma), None if inorm else dev(beta), scale, shift, n, HW, c, G, P, eps)
+    # the partials themselves: every pixel is counted once, whatever the chunking
+    x64 = x.double().reshape(n, HW, c)
+    p64 = part.double().cpu().sum(1)
+    check(p64[..., 0], x64.sum(1), what='chan_stats sum'); check(p64[..., 1], (x64 * x64).sum(1), what='chan_stats sumsq')
+    g64 = x64.reshape(n, HW, G, c // G)
+    mean = g64.mean(dim=(1, 3), keepdim=True)
+    var = ((g64 - mean) ** 2).mean(dim=(1, 3), keepdim=True)
+    rstd = (1.0 / torch.sqrt(var + eps)).expand(n, 1, G, c // G).reshape(n, c)
+    mean = mean.expand(n, 1, G, c // G).reshape(n, c)
+    sc_ref = rstd if inorm else gamma.double() * rstd
+    sh_ref = -mean * sc_ref if inorm else beta.double() - mean * sc_ref
+    check(scale, sc_ref, what='norm_finalize scale'); check(shift, sh_ref, what='norm_finalize shift')
+    # and through ops.norm_affine's own dispatch rule the same numbers come back (it picks keep_group_stats for small maps)
+    sc2, sh2 = ops.norm_affine(xd, None if inorm else dev(gamma), None if inorm else dev(beta), G, eps)
+    check(sc2, sc_ref, what='norm_affine scale'); check(sh2, sh_ref, what='norm_affine shift')
+
+
+@pytest.mark.parametrize("n,hw,c", [(2, 64, 32), (3, 35, 6)])
+def test_affine_act_and_gm_join(n, hw, c):
+    """keep_affine_act (GM stem: relu(x * s + h)) and keep_gm_join (GM/backbone.py:36, with and without the shortcut's own
+    scale / shift, as engine/net.py calls it) against fp64."""
+    x, b = rnd('afx', (n, hw, c), 2.0), rnd('afb', (n, hw, c), 2.0)
+    s, h_, s2, h2 = rnd('afs', (n, c)) + 1.5, rnd('afh', (n, c)), rnd('afs2', (n, c)) + 1.5, rnd('afh2', (n, c))
+    bc = lambda t: t.double()[:, None, :]
+    out = torch.empty((n, hw, c), device='cuda')
+    got = call_out('keep_affine_act', out, dev(x), dev(s), dev(h_), out, n, hw, c, L.ACT_RELU)
+    check(got, torch.relu(x.double() * bc(s) + bc(h_)), what='affine_act')
+    yb = torch.relu(b.double() * bc(s2) + bc(h2))
+    got = call_out('keep_gm_join', out, dev(x), dev(s), dev(h_), dev(b), dev(s2), dev(h2), out, n, hw, c)
+    check(got, torch.relu(x.double() * bc(s) + bc(h_) + yb), what='gm_join (projected shortcut)')
+    got = call_out('keep_gm_join', out, dev(x), None, None, dev(b), dev(s2), dev(h2), out, n, hw, c)
+    check(got, torch.relu(x.double() + yb), what='gm_join (identity shortcut)')
+
+
+@pytest.mark.parametrize("n,c,h,w", [(2, 32, 16, 16), (3, 3, 5, 7), (1, 19, 15, 20)])
+def test_nhwc_to_nchw_is_a_permutation(n, c, h, w):
+    x = rnd('pmx', (n, h, w, c))
+    assert torch.equal(ops.nhwc_to_nchw(dev(x)).cpu(), x.permute(0, 3, 1, 2).contiguous())       # data movement: bit-exact
+
+
+@pytest.mark.parametrize("n,h,w,c", [(2, 8, 8, 64), (3, 5, 7, 12), (1, 1, 1, 4)])
+def test_maxpool3s2_is_max_pool2d_3_2_1(n, h, w, c):
+    x = rnd('mpx', (n, h, w, c), 3.0)
+    ref = nhwc(F.max_pool2d(nchw(x), 3, 2, 1))
+    out = torch.empty(ref.shape, device='cuda')
+    assert torch.equal(call_out('keep_maxpool3s2', out, dev(x), out, n, h, w, c), ref)            # a selection: bit-exact
+
+
+@pytest.mark.parametrize("H,W", [(10, 14), (9, 13), (5, 7)])
+def test_upsample_add_is_nearest_interpolate_plus_add(H, W):
+    """FPN top-down step: a + F.interpolate(b, size=(H, W), mode='nearest'), 5 x 7 onto an integer multiple, onto the non-integer
+    9 x 13, and onto itself; one fp32 addition per element, so the fp32 torch result is matched bit for bit."""
+    n, hb, wb, c = 3, 5, 7, 12
+    a, b = rnd('uaa', (n, H, W, c)), rnd('uab', (n, hb, wb, c))
+    up = F.interpolate(nchw(b), size=(H, W), mode='nearest')
+    out = torch.empty((n, H, W, c), device='cuda')
+    got = call_out('keep_upsample_add', out, dev(a), dev(b), out, n, H, W, hb, wb, c)
+    check(got, a.double() + nhwc(up).double(), what='upsample_add')
+    assert torch.equal(got, a + nhwc(up))
+
+
+@pytest.mark.parametrize("act", [L.ACT_NONE, L.ACT_RELU, L.ACT_LRELU02, L.ACT_GELU, L.ACT_SIGMOID, L.ACT_LRELU01, L.ACT_SILU])
+@pytest.mark.parametrize("n", [4096, 780])
+def test_act_inplace_every_activation(act, n):
+    x = rnd('aix', (n,), 6.0)
+    x64 = x.double()
+    ref = {L.ACT_NONE: x64, L.ACT_RELU: torch.relu(x64), L.ACT_LRELU02: F.leaky_relu(x64, 0.2), L.ACT_LRELU01: F.leaky_relu(x64, 0.1),
+           L.ACT_GELU: F.gelu(x64), L.ACT_SIGMOID: torch.sigmoid(x64), L.ACT_SILU: F.silu(x64)}[act]
+    xd = dev(x)
+    check(call_out('keep_act_inplace', xd, xd, n, act), ref, what=f'act_inplace {act}')
+
+
+def test_u8_to_f32_and_f32_round_u8_every_value():
+    """keep_u8_to_f32 on every byte value (bit-exact), keep_f32_round_u8 on every integer and every half in [-3, 259] (round half to
+    even), negatives, values beyond 255, +-inf and a ragged tail, bit-exact against the paste oracle's host expression
+    np.round(np.clip(x, 0, 255)).astype(np.uint8) (oracle/paste_oracle.py:paste_faces).  NaN: numpy's NaN -> uint8 cast is not defined;
+    the kernel clips first with fmaxf / fminf, which drop a NaN operand: 0."""
+    b = torch.arange(256, dtype=torch.uint8).repeat(4)[:777]
+    out = torch.empty(777, device='cuda')
+    assert torch.equal(call_out('keep_u8_to_f32', out, dev(b), out, 777), b.float())
+    grid = np.arange(-3 * 4, 259 * 4 + 1, dtype=np.float32) / 4                      # quarters: every integer, every half, both neighbours
+    near = np.concatenate([np.nextafter(grid, np.float32(np.inf)), np.nextafter(grid, np.float32(-np.inf))])
+    x = np.concatenate([grid, near, np.float32([-1e30, 1e30, np.inf, -np.inf, -0.0, 254.5, 255.4999, 255.5]),
+                        op_input('f2u', (1002,), 300.0).numpy()]).astype(np.float32)
+    ref = np.round(np.clip(x, 0, 255)).astype(np.uint8)
+    out8 = torch.empty(x.size, dtype=torch.uint8, device='cuda')
+    got = call_out('keep_f32_round_u8', out8, dev(torch.from_numpy(x)), out8, x.size).numpy()
+    assert x.size % 4 != 0 and np.array_equal(got, ref), np.flatnonzero(got != ref)[:8]
+    nan = torch.full((5,), float('nan'))
+    out8 = torch.empty(5, dtype=torch.uint8, device='cuda')
+    assert call_out('keep_f32_round_u8', out8, dev(nan), out8, 5).tolist() == [0] * 5
+
+
+@pytest.mark.parametrize("H,W,fh,fw,M", [(48, 64, 32, 32, [[1.1, 0.2, 9.3], [-0.2, 1.1, 6.7]]),         # inside the frame
+                                         (37, 53, 32, 24, [[0.9, -0.4, 38.6], [0.4, 0.9, -11.2]]),      # the crop hangs over two frame edges
+                                         (5, 7, 16, 16, [[0.3, 0.0, -1.0], [0.0, 0.3, 0.5]])])        # a frame smaller than the face
+def test_warp_ones_and_erode_rect_on_their_own(H, W, fh, fw, M):
+    """keep_warp_ones = cv2.warpAffine(ones(fh, fw), M, (W, H)) and keep_erode_rect = cv2.erode(., ones(k, k)) bit-exact against
+    oracle/paste_oracle.py, each on its own (GpuPaster.erosion_mask only ever showed their composition): a crop that maps partly
+    off-frame, k = 1, even and odd k, and k larger than the image."""
+    import ctypes as C
+    import paste_oracle as P
+    M = np.array(M, np.float64)
+    d2s = (C.c_double * 6)(*P.invert_affine(M).reshape(-1).tolist())
+    a = torch.empty((H, W), device='cuda')
+    got = call_out('keep_warp_ones', a, a, H, W, fh, fw, d2s).numpy()
+    ref = P.warp_affine_f32(np.ones((fh, fw), np.float32), M, W, H)
+    assert 0 < ref.sum() and np.array_equal(got, ref)
+    if H > 30:
+        assert ref.min() == 0 and ref.max() == 1 and ((ref > 0) & (ref < 1)).any()              # edges in the picture
+    tmp, dst = torch.empty_like(a), torch.empty_like(a)
+    src = op_input('erx', (H, W)).abs().numpy().astype(np.float32) * ref
+    for k in (1, 2, 3, 6, 9, max(H, W) + 4):
+        got = call_out('keep_erode_rect', dst, dev(torch.from_numpy(src)), tmp, dst, H, W, k).numpy()
+        assert np.array_equal(got, P.erode_rect(src, k)), k

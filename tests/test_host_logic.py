@@ -823,3 +823,133 @@ def test_loader_swaps_the_helpers_networks_for_engine_objects(monkeypatch):
     h3.face_parse = FakeModule(PN.synth_parsenet_state_dict(seed=0, in_size=128, out_size=128))
     engine_facelib(h3)
     assert isinstance(h3.face_parse, FakeModule)
+
+
+# ------------------------------------------------------------------------------------------------ footprint harness and tables
+def _footprint_toy(kind):
+    """Deliberately wrong torch "kernels" on the views the harness hands out: one writes one element past its payload, one lets
+    a neighbour of its input reach the result through a multiplication by zero, one leaves an output element unwritten."""
+    import footprint as FP
+    n = 37
+    x = torch.arange(n, dtype=torch.float32).reshape(1, n) + 1
+    regions = [FP.single('x', x), FP.output('o', (1, n))]
+
+    def reach(t, extra):      # the view widened by `extra` elements behind its end, as far as the allocation goes (none in a plain call)
+        room = t.untyped_storage().nbytes() // t.element_size() - t.storage_offset() - t.numel()
+        return t.as_strided((t.numel() + min(extra, room),), (1,), t.storage_offset())
+
+    def launch(t):
+        if kind == 'ok':
+            t['o'].copy_(t['x'] * 2)
+        elif kind == 'write':
+            wide = reach(t['o'], 1)
+            wide[:n] = t['x'].reshape(-1) * 2
+            wide[n:] = 1.0
+        elif kind == 'read':
+            t['o'].copy_(reach(t['x'], 2).sum() * 0 + t['x'] * 2)
+        elif kind == 'unwritten':
+            t['o'][:, :n - 1] = t['x'][:, :n - 1]
+    return FP, regions, launch
+
+
+def test_footprint_harness_bites():
+    """tests/footprint.py on the CPU: a correct toy kernel passes; a write one element past the payload raises WriteOutside (and says
+    where); `sum over a view reaching into the guard * 0 + x` raises ReadOutside (0 * NaN and 0 * Inf are NaN); an output element
+    left unwritten is reported as non-finite."""
+    FP, regions, launch = _footprint_toy('ok')
+    out = FP.run(launch, regions, 'cpu')
+    assert torch.equal(out['o'], (torch.arange(37, dtype=torch.float32).reshape(1, 37) + 1) * 2)
+    FP, regions, launch = _footprint_toy('write')
+    with pytest.raises(FP.WriteOutside, match=r'element \+37 relative to the payload start'):
+        FP.run(launch, regions, 'cpu')
+    FP, regions, launch = _footprint_toy('read')
+    with pytest.raises(FP.ReadOutside, match='depends on memory outside'):
+        FP.run(launch, regions, 'cpu')
+    FP, regions, launch = _footprint_toy('unwritten')
+    with pytest.raises(FP.ReadOutside, match='unwritten'):
+        FP.run(launch, regions, 'cpu')
+
+
+def test_footprint_harness_strided_gaps_and_shared_windows():
+    """Gap columns of a strided payload are surroundings: a kernel that reads a whole padded row, or writes one column behind its
+    slice, is caught; windows of one packed buffer are not each other's surroundings."""
+    import footprint as FP
+    a, b = torch.ones(5, 3), torch.full((5, 2), 2.0)
+
+    def regions():
+        return [FP.Region(5, 8, {'a': (1, 3, a), 'b': (4, 2, b)}, torch.float32, 'r'), FP.output('o', (5, 3), ld=6, off=2)]
+
+    FP.run(lambda t: t['o'].copy_(t['a'] + t['b'].sum(1, keepdim=True)), regions(), 'cpu')      # reads both windows: fine
+
+    def row_of(t, width):      # the rows of the window widened to `width` columns
+        return t.as_strided((t.shape[0], width), (t.stride(0), 1), t.storage_offset())
+
+    def wide_read(t):
+        t['o'].copy_(row_of(t['a'], 6)[:, 5:6] * 0 + t['a'] * 3)            # column 6 of the packed rows: a gap
+    with pytest.raises(FP.ReadOutside):
+        FP.run(wide_read, regions(), 'cpu')
+
+    def wide_write(t):
+        t['o'].copy_(t['a'] * 3)
+        row_of(t['o'], 4)[:, 3] = 0.0                                        # one column behind the slice
+    with pytest.raises(FP.WriteOutside, match=r'element \+3 relative'):
+        FP.run(wide_write, regions(), 'cpu')
+
+
+def _family(s):
+    """Kernel family of a plan string or of its format string: template arguments (numbers, booleans, %d / %s) dropped."""
+    def args(m):
+        rest = re.sub(r'%[ds]|\b\d+\b|\btrue\b|\bfalse\b|[,\s]', '', m.group(1))
+        return f'<{rest}>' if rest else ''
+    return re.sub(r'<([^>]*)>', args, s).strip()
+
+
+# families of csrc/keep_conv.hip:plan_conv that no argument struct can reach (must stay empty unless a family truly is unreachable)
+UNREACHABLE_CONV_FAMILIES = set()
+
+
+def test_footprint_conv_table_reaches_every_kernel_family():
+    """tests/test_gpu_footprint.py's convolution table against keep_conv2d_plan (host C): every case lands on the kernel it names,
+    and the families reached are exactly the family strings plan_conv can print -- a new family fails here until it has a case."""
+    import test_gpu_footprint as T
+    src = open(os.path.join(ROOT, 'comfyui-keep_amd', 'csrc', 'keep_conv.hip')).read()
+    declared = {_family(f) for f in re.findall(r'snprintf\(pl\.kernel, sizeof\(pl\.kernel\), "([^"]+)"', src)}
+    assert len(declared) >= 14, declared
+    reached, variants, auto_split = set(), set(), []
+    for name, (expect, kw) in T.CONV_CASES.items():
+        _, g, plan = T.conv_case_plan(name)
+        got = plan.kernel.decode()
+        assert got == expect, (name, got, expect)
+        assert (plan.split_k > 1) == (plan.workspace_bytes > 0)
+        if g.split_k > 1:
+            assert plan.split_k == g.split_k, (name, plan.split_k)
+        elif plan.split_k > 1:
+            auto_split.append(name)
+        if g.stats:
+            assert plan.stats_P > 0, name
+        if g.amax:
+            assert plan.out_amax_ok, name
+        reached.add(_family(got))
+        variants.add(got)
+    assert reached == declared - UNREACHABLE_CONV_FAMILIES, (sorted(declared - reached), sorted(reached - declared))
+    for v in ('conv3x3_halo_x3_kernel<16>', 'conv3x3_halo_x3_kernel<32>', 'conv3x3_halo_f32_kernel<16>', 'conv3x3_halo_f32_kernel<32>',
+              'gemm_x3l_kernel<4>', 'gemm_x3l_kernel<8>', 'conv_f32_kernel<4, 1, 1, 1>', 'conv_f32_kernel<2, 2, 1, 1>',
+              'conv_f32_kernel<2, 2, 2, 2>', 'conv3x3_halo3_kernel<false, 32>', 'conv3x3_halo3_kernel<true, 16>',
+              'conv_x3_kernel<2, 2, 1, 1, true, true>', 'conv_x3_kernel<2, 2, 2, 2, true, false>', 'conv_x3_kernel<2, 2, 1, 1, false, false>',
+              'conv_bf16_kernel<2, 2, 1, 1, 256, 1, false>', 'conv_bf16_kernel<4, 1, 1, 1, 64, 1, false>',
+              'conv_bf16_kernel<2, 2, 2, 2, 64, 1, true>'):
+        assert v in variants, v
+    assert auto_split, 'no case where the library itself chooses split-K'
+
+
+def test_footprint_tables_name_every_launcher():
+    """Every keep_* entry point include/keep_hip.h declares is either host-only or has footprint cases (>= 2 each for the flat ops)."""
+    import test_gpu_footprint as T
+    header = open(os.path.join(ROOT, 'include', 'keep_hip.h')).read()
+    declared = set(re.findall(r'\b(keep_[a-z0-9_]+)\s*\(', header))
+    covered = set(T.FLAT_CASES) | set(T.STRUCT_LAUNCHERS)
+    assert T.HOST_ONLY <= declared
+    assert covered | T.HOST_ONLY == declared, (sorted(declared - covered - T.HOST_ONLY), sorted(covered - declared))
+    assert not (covered & T.HOST_ONLY)
+    for fn, cases in T.FLAT_CASES.items():
+        assert len(cases) >= 2 and len({cid for cid, _ in cases}) == len(cases), fn
