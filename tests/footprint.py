@@ -167,6 +167,14 @@ def _one_run(launch, regions, device, embedded, poison):
     return outs, sig
 
 
+def plain(launch, regions, device):
+    """One plain call -- exactly sized buffers, no guards, gap columns zero: (outputs name -> tensor, the launch's signature).  For
+    the tests that judge values (tests/test_gpu_case_values.py); nothing about the footprint is checked."""
+    names = [n for r in regions for n in r.windows]
+    assert len(names) == len(set(names)), names
+    return _one_run(launch, regions, device, False, 'zero')
+
+
 def run(launch, regions, device, finite=True, canon=None):
     """``launch(tensors) -> signature``: the kernel call on the views in ``tensors`` (name -> [rows, C] view with row stride ld);
     the optional signature (e.g. the library's plan) must be the same for the plain and every embedded run.  Raises a

@@ -20,6 +20,7 @@ import pytest
 import torch
 
 import keep_oracle as O
+from abi_ref import sparse_causal_ref, win_ref, win_regions, win_shift, win_split, yardstick      # the one fp64 restatement of the modes
 from comfyui_keep_amd.engine import hiplib as L
 from comfyui_keep_amd.engine import ops
 
@@ -60,16 +61,6 @@ def workspace_bytes(q, k, v, mma, flags=0, *, q_str, k_str, v_str, o_str, **kw):
     return L.attention_workspace_bytes(a)
 
 
-def yardstick(what, e3, e32, sc, e3np=None):
-    """The suite's x3 bound; prints the ratios the PR description quotes (run with -s)."""
-    extra = '' if e3np is None else f' err_x3_nopack {e3np:.3e}'
-    print(f'[x3-yardstick] {what}: err_x3 {e3:.3e} err_f32 {e32:.3e} ratio {e3 / max(e32, 1e-300):.2f}{extra} scale {sc:.3g}')
-    assert e32 <= TOL * sc, f'{what}: f32 kernel err {e32:.3e} (scale {sc:.3g})'
-    assert e3 <= max(3.0 * e32, 2e-6 * sc), f'{what}: x3 err {e3:.3e} vs f32-kernel err {e32:.3e} (scale {sc:.3g})'
-    if e3np is not None:
-        assert e3np <= max(3.0 * e32, 2e-6 * sc), f'{what}: un-packed x3 err {e3np:.3e} vs f32-kernel err {e32:.3e} (scale {sc:.3g})'
-
-
 def sample_rows(L_, n=256):
     """~n query rows spread over [0, L_) with the last one included (ragged tail tiles)."""
     step = max(1, L_ // n)
@@ -78,45 +69,6 @@ def sample_rows(L_, n=256):
 
 
 # ------------------------------------------------------------------------------------------------ mode 2: shifted windows
-def win_shift(h, w, ks, shift):
-    wh, ww = h // ks, w // ks
-    return (wh // 2, ww // 2) if shift else (0, 0)
-
-
-def win_split(x, h, w, ks, sy, sx):
-    """[n, h*w, C] image frame -> [n*ks*ks, wh*ww, C]: rolled by (-sy, -sx), cut into windows (GM/transformer.py:75-85)."""
-    n, _, c = x.shape
-    x = torch.roll(x.reshape(n, h, w, c), shifts=(-sy, -sx), dims=(1, 2))
-    return O._split_cl(x.contiguous(), ks).reshape(n * ks * ks, -1, c)
-
-
-def win_regions(h, w, ks):
-    """[ks*ks, wh*ww] region id of every window token in the rolled frame (the slices of GM/transformer.py:24-35)."""
-    wh, ww = h // ks, w // ks
-    img = torch.zeros((1, h, w, 1))
-    cnt = 0
-    for hs in (slice(0, -wh), slice(-wh, -(wh // 2)), slice(-(wh // 2), None)):
-        for ws in (slice(0, -ww), slice(-ww, -(ww // 2)), slice(-(ww // 2), None)):
-            img[:, hs, ws, :] = cnt
-            cnt += 1
-    return O._split_cl(img, ks).reshape(ks * ks, -1)
-
-
-def win_ref(q, k, v, h, w, ks, shift, kv_rot, rows, mask_value=-100.0):
-    """fp64 window attention at window-local query rows `rows`: [n*ks*ks, len(rows), C].  Image i reads keys / values of image
-    (i + kv_rot) % n; shift adds `mask_value` to cross-region scores (the reference: -100)."""
-    n, _, c = q.shape
-    sy, sx = win_shift(h, w, ks, shift)
-    qw = win_split(q.double(), h, w, ks, sy, sx)[:, rows]
-    kw = win_split(torch.roll(k.double(), -kv_rot, 0), h, w, ks, sy, sx)
-    vw = win_split(torch.roll(v.double(), -kv_rot, 0), h, w, ks, sy, sx)
-    s = torch.matmul(qw, kw.transpose(1, 2)) / math.sqrt(c)
-    if shift:
-        reg = win_regions(h, w, ks).repeat(n, 1)
-        s = torch.where(reg[:, rows, None] != reg[:, None, :], s + mask_value, s)
-    return torch.matmul(torch.softmax(s, dim=-1), vw)
-
-
 def gm_call(h, w, P, shift, cross, C=128, ks=2, amp=1.5, seed=0):
     """GMFlow window attention as net.py:_gm_layer launches it: self-attention reads q | k | v from one packed [Ltok, 3C]
     buffer (kv_rot = 0), cross-attention a separate q and a [Ltok, 2C] k | v buffer (kv_rot = P: [f0;f1] vs [f1;f0])."""
@@ -297,22 +249,6 @@ def test_mode0_softargmax_and_flow_propagation_x3(h, w, fs, vkind):
 
 
 # ------------------------------------------------------------------------------------------------ mode 1: Kalman sparse-causal
-def sparse_causal_ref(qkv, Bc, T, Lt, H, D, rows):
-    """KA:704-716 in fp64: keys / values of frame f = [frame 0 ; frame max(f-1, 0)] of the same clip; [Bc*T, rows, H*D]."""
-    inner = H * D
-    q, k, v = (t.double() for t in qkv.reshape(Bc * T, Lt, 3 * inner).split(inner, dim=-1))
-    former = torch.clamp(torch.arange(T) - 1, min=0)
-
-    def gather(t):
-        t = t.reshape(Bc, T, Lt, inner)
-        return torch.cat([t[:, [0] * T], t[:, former]], dim=2).reshape(Bc * T, 2 * Lt, H, D).permute(0, 2, 1, 3)
-
-    qh = q[:, rows].reshape(Bc * T, len(rows), H, D).permute(0, 2, 1, 3)
-    s = torch.matmul(qh, gather(k).transpose(2, 3)) / math.sqrt(D)
-    o = torch.matmul(torch.softmax(s, dim=-1), gather(v))
-    return o.permute(0, 2, 1, 3).reshape(Bc * T, len(rows), inner)
-
-
 def sparse_causal_call(Bc, T, Lt, H, D, seed, amp=1.5):
     inner = H * D
     qkv = randn(seed, (Bc * T, Lt, 3 * inner))

@@ -1,7 +1,8 @@
 """Which bytes do the kernels touch?  Every case runs one C-ABI call through tests/footprint.py: each tensor embedded in
 guards, strided tensors with their real ``ld`` (gap columns are surroundings), workspace / statistics partials / amax slots at
 exactly the size the library reports.  Written surroundings must stay bit-identical; the outputs must be bit-identical under
-zero / NaN / 3e38 surroundings of everything that is read, finite, and equal to the plain call.  Values are judged elsewhere.
+zero / NaN / 3e38 surroundings of everything that is read, finite, and equal to the plain call.  The values of the same launches are
+judged by tests/test_gpu_case_values.py against the float64 restatement of the two ABIs in tests/abi_ref.py.
 
 The case tables are plain data, importable without a GPU: tests/test_host_logic.py asks ``keep_conv2d_plan`` (host C) for every
 convolution case and checks that the tables reach every kernel family and name every launcher of include/keep_hip.h.
@@ -14,6 +15,7 @@ import pytest
 import torch
 
 import footprint as FP
+from abi_ref import AUX_W, LN_EPS, attn_scale
 from conftest import op_input
 from comfyui_keep_amd.engine import hiplib as L
 from comfyui_keep_amd.engine import ops
@@ -34,7 +36,9 @@ def rnd(name, shape, scale=1.0, dtype=F32):
 # ------------------------------------------------------------------------------------------------ keep_conv2d
 # name -> (expected family string of keep_conv2d_plan, arguments).  Geometry keys: N H W Cin Cout k stride pad (or pad_t/pad_l) Ho Wo
 # (default: same-size for stride 1, the symmetric-padding size otherwise) in_ld in_off out_ld out_off res_ld aux pro pro_act act split_k
-# stats amax in_amax in2_cin1 reflect upsample in_bf16 out_bf16 bk256 ln flags launch (False: plan-only).
+# stats amax in_amax in2_cin1 reflect upsample in_bf16 out_bf16 bk256 ln flags launch (False: plan-only); data keys: pro_amp (prologue rows are
+# 1 +- pro_amp / +- pro_amp, default 0.2) and bias_amp (default 1): raised where a coarse tolerance class would otherwise let a
+# kernel that ignores the input pass (tests/test_host_logic.py: every optional input moves the reference by >= 100 x the tolerance).
 def _c(expect, mma, **kw):
     return expect, dict(mma=mma, **kw)
 
@@ -64,6 +68,14 @@ CONV_CASES = {
     'halo_x3_16_aux': _c('conv3x3_halo_x3_kernel<16>', X_, N=1, H=16, W=16, Cin=16, Cout=32, res_ld=40, aux=True, in_amax=True),
     'halo_x3_32_split': _c('conv3x3_halo_x3_kernel<32>', X_, N=1, H=8, W=32, Cin=48, Cout=32, split_k=3, in_amax=True, res_ld=32),
     'halo_x3_16_autosplit': _c('conv3x3_halo_x3_kernel<16>', X_, N=1, H=16, W=16, Cin=128, Cout=32, pro=True, pro_act=L.PRO_SWISH),
+    # ---- the 64-pixel-block x3 kernels of keep_conv_x3p.hip.  keep_conv2d_plan prints them under the halo names (it names the family whose
+    # values they reproduce); the dispatch takes them for few-item launches with Cout % 64 == 0 (keep_conv_x3p_ok / _full_ok / x3q_ok):
+    # conv3x3_x3p_kernel<.., 4> as split-K producer, conv3x3_x3p_kernel with the full epilogue (16-wide map, aux), conv3x3_x3q_kernel
+    'x3p_partials': _c('conv3x3_halo_x3_kernel<16>', X_, N=3, H=16, W=16, Cin=128, Cout=64, split_k=2, pro=True, in_ld=132, in_off=4, res_ld=72),
+    'x3p_full_aux': _c('conv3x3_halo_x3_kernel<16>', X_, N=1, H=16, W=16, Cin=64, Cout=64, split_k=1, res_ld=68, aux=True, act=L.ACT_LRELU02,
+                       in_amax=True, amax=True, out_ld=72, out_off=4),
+    'x3q_small': _c('conv3x3_halo_x3s_kernel', X_, N=3, H=8, W=32, Cin=32, Cout=64, split_k=1, in_ld=40, in_off=8, res_ld=68, act=L.ACT_LRELU02,
+                    stats=True, in_amax=True, amax=True),
     # ---- x3 GEMM / gather kernels
     'gemm_x3l_4': _c('gemm_x3l_kernel<4>', X_, N=3, H=64, W=1, Cin=256, Cout=32, k=1, in_ld=260, in_off=4, out_ld=40, out_off=4,
                      res_ld=36, in_amax=True, amax=True, act=L.ACT_GELU),
@@ -90,15 +102,16 @@ CONV_CASES = {
     # ---- bf16 halo kernels
     'halo3_f32in_32': _c('conv3x3_halo3_kernel<false, 32>', B_, N=1, H=8, W=32, Cin=32, Cout=32, in_ld=40, in_off=8, out_ld=48, out_off=8,
                          res_ld=36),
-    'halo3_bf16in_16': _c('conv3x3_halo3_kernel<true, 16>', B_, N=3, H=16, W=16, Cin=32, Cout=64, in_bf16=True, out_bf16=True),
+    'halo3_bf16in_16': _c('conv3x3_halo3_kernel<true, 16>', B_, N=3, H=16, W=16, Cin=32, Cout=64, in_bf16=True, out_bf16=True, bias_amp=2.0),
     'halo3_bf16in_split': _c('conv3x3_halo3_kernel<true, 32>', B_, N=1, H=8, W=32, Cin=96, Cout=96, in_bf16=True, split_k=3, act=L.ACT_GELU),
-    'halo_bf16_pro_fused': _c('conv3x3_halo3_kernel<false, 16>', B_, N=1, H=16, W=16, Cin=32, Cout=64, pro=True, pro_act=L.PRO_SWISH, stats=True),
+    'halo_bf16_pro_fused': _c('conv3x3_halo3_kernel<false, 16>', B_, N=1, H=16, W=16, Cin=32, Cout=64, pro=True, pro_act=L.PRO_SWISH, stats=True, pro_amp=0.8),
     'halo_bf16_needs_prenorm': _c('(keep_norm_act_bf16 first)', B_, N=1, H=16, W=16, Cin=32, Cout=64, in_bf16=True, pro=True, launch=False),
     # ---- bf16 gather kernels
     'bf16_t0': _c('conv_bf16_kernel<4, 1, 1, 1, 64, 1, false>', B_, N=3, H=5, W=7, Cin=24, Cout=20, stride=2, in_ld=28, in_off=4),
     'bf16_t1_plain': _c('conv_bf16_kernel<2, 2, 1, 1, 64, 1, true>', B_, N=1, H=300, W=1, Cin=80, Cout=48, k=1, in_ld=96, in_off=8, out_ld=56,
                         out_off=4, res_ld=52, out_bf16=False),
-    'bf16_t1_pro': _c('conv_bf16_kernel<2, 2, 1, 1, 64, 1, false>', B_, N=1, H=5, W=7, Cin=130, Cout=48, k=7, pad=3, pro=True, pro_act=L.PRO_RELU),
+    'bf16_t1_pro': _c('conv_bf16_kernel<2, 2, 1, 1, 64, 1, false>', B_, N=1, H=5, W=7, Cin=130, Cout=48, k=7, pad=3, pro=True, pro_act=L.PRO_RELU, pro_amp=1.5,
+                      bias_amp=3.0),
     'bf16_t1_bf16out': _c('conv_bf16_kernel<2, 2, 1, 1, 64, 1, true>', B_, N=1, H=250, W=1, Cin=48, Cout=64, k=1, out_bf16=True),
     'bf16_t1_bk256': _c('conv_bf16_kernel<2, 2, 1, 1, 256, 1, false>', B_, N=1, H=100, W=1, Cin=512, Cout=64, k=1, bk256=True),
     'bf16_t2': _c('conv_bf16_kernel<2, 2, 2, 2, 64, 1, true>', B_, N=1, H=4133, W=1, Cin=16, Cout=96, k=1, stats=False),
@@ -126,7 +139,7 @@ class _Geom:
     def __init__(self, kw):
         g = dict(k=3, stride=1, in_off=0, out_off=0, res_ld=0, aux=False, pro=False, pro_act=L.PRO_NONE, act=L.ACT_NONE, split_k=0,
                  stats=False, amax=False, in_amax=False, in2_cin1=0, reflect=False, upsample=0, in_bf16=False, out_bf16=False,
-                 bk256=False, ln=False, flags=0, launch=True)
+                 bk256=False, ln=False, flags=0, launch=True, pro_amp=0.2, bias_amp=1.0)
         g.update(kw)
         self.__dict__.update(g)
         k = self.k
@@ -150,19 +163,20 @@ def _conv_args(g, t):
         inp=p('x'), weight=p('w'), bias=p('bias'), out=p('out'), pro_scale=p('pro_scale'), pro_shift=p('pro_shift'), residual=p('res'),
         aux=p('aux'), workspace=p('ws'), N=g.N, H=g.H, W=g.W, Cin=g.Cin, Cout=g.Cout, KH=g.k, KW=g.k, stride=g.stride, pad_t=g.pad_t,
         pad_l=g.pad_l, Ho=g.Ho, Wo=g.Wo, in_ld=g.in_ld, out_ld=g.out_ld, res_ld=g.res_ld, upsample=g.upsample, pro_act=g.pro_act,
-        epi_act=g.act, aux_w=0.5, split_k=g.split_k, dtype=L.BF16 if g.in_bf16 else L.F32, mma=g.mma, weight_bf16=p('wb'),
+        epi_act=g.act, aux_w=AUX_W, split_k=g.split_k, dtype=L.BF16 if g.in_bf16 else L.F32, mma=g.mma, weight_bf16=p('wb'),
         stats_out=p('stats'), stats_P=t.get('stats_P', 0), bk256=int(g.bk256), out_dtype=L.BF16 if g.out_bf16 else L.F32,
         weight_x3=p('wx3'), x3_acc_scale=float(t.get('acc_scale', 1.0)), x3_in_amax=p('in_amax'), x3_out_amax=p('amax'),
         x3_out_amax_zeroed=1 if g.amax else 0, in2=p('x2'), in2_cin1=g.in2_cin1, pad_mode=L.PAD_REFLECT if g.reflect else L.PAD_ZERO,
-        ln_gamma=p('ln_gamma'), ln_beta=p('ln_beta'), ln_eps=1e-5 if g.ln else 0.0, flags=g.flags, plan_ref_images=0)
+        ln_gamma=p('ln_gamma'), ln_beta=p('ln_beta'), ln_eps=LN_EPS if g.ln else 0.0, flags=g.flags, plan_ref_images=0)
     return a
 
 
-def conv_case_plan(name):
+def conv_case_plan(name, kw=None):
     """keep_conv2d_plan of a table case without a GPU: pointers only contribute their alignment, so every tensor gets the
-    address it will have modulo 16 (allocations are 16-byte aligned, slices start ``off`` elements in)."""
-    expect, kw = CONV_CASES[name]
-    g = _Geom(kw)
+    address it will have modulo 16 (allocations are 16-byte aligned, slices start ``off`` elements in).  ``kw``: a variant of the
+    case's geometry (the exact-f32 twin of an x3 case, tests/test_gpu_case_values.py) instead of the table's own."""
+    expect, kw0 = CONV_CASES[name]
+    g = _Geom(kw0 if kw is None else kw)
     base = 0x10000
     isz = 2 if g.in_bf16 else 4
     t = {'x': base + g.in_off * isz, 'w': base, 'bias': base, 'out': base + g.out_off * (2 if g.out_bf16 else 4)}
@@ -187,21 +201,28 @@ def conv_case_plan(name):
     return expect, g, L.conv2d_plan(_conv_args(g, t))
 
 
-def _conv_regions(name):
-    expect, g, plan = conv_case_plan(name)
-    assert plan.kernel.decode() == expect, (name, plan.kernel.decode(), expect)
+def conv_case_x(name, g):
+    """The input payload of case ``name`` (channels [0, cin1) of `in`)."""
+    return rnd(name + 'x', (g.N, g.H, g.W, g.cin1), 2.0) + 0.3
+
+
+def _conv_regions(name, kw=None, x=None):
+    """(geometry, plan, regions, extra arguments) of a table case; the tensors depend on ``name`` alone, so a variant geometry
+    ``kw`` (see conv_case_plan) gets the same data, with ``x`` replacing the input payload where the variant reads another one."""
+    expect, g, plan = conv_case_plan(name, kw)
+    assert kw is not None or plan.kernel.decode() == expect, (name, plan.kernel.decode(), expect)
     tb = CONV_TILE_BYTES
     idt = BF16 if g.in_bf16 else F32
     N, Cin, Cout = g.N, g.Cin, g.Cout
-    x = rnd(name + 'x', (N, g.H, g.W, g.cin1), 2.0) + 0.3
+    x = conv_case_x(name, g) if x is None else x
     w = rnd(name + 'w', (Cout, g.k, g.k, Cin), 0.05)
     R = [FP.single('x', x.to(idt), ld=g.in_ld, off=g.in_off, tile_bytes=tb), FP.single('w', w.reshape(Cout, -1), tile_bytes=tb),
-         FP.single('bias', rnd(name + 'b', (1, Cout)), tile_bytes=tb),
+         FP.single('bias', rnd(name + 'b', (1, Cout)) * g.bias_amp, tile_bytes=tb),
          FP.output('out', (N * g.Ho * g.Wo, Cout), BF16 if g.out_bf16 else F32, ld=g.out_ld, off=g.out_off, tile_bytes=tb)]
     extra = {}
     if g.pro:
-        R.append(FP.single('pro_scale', rnd(name + 'ps', (N, Cin)) * 0.2 + 1, tile_bytes=tb))
-        R.append(FP.single('pro_shift', rnd(name + 'ph', (N, Cin)) * 0.2, tile_bytes=tb))
+        R.append(FP.single('pro_scale', rnd(name + 'ps', (N, Cin)) * g.pro_amp + 1, tile_bytes=tb))
+        R.append(FP.single('pro_shift', rnd(name + 'ph', (N, Cin)) * g.pro_amp, tile_bytes=tb))
     if g.res_ld:
         R.append(FP.single('res', rnd(name + 'r', (N * g.Ho * g.Wo, Cout)), ld=g.res_ld, tile_bytes=tb))
     if g.aux:
@@ -253,17 +274,18 @@ def test_conv2d_footprint(name):
 
 # ------------------------------------------------------------------------------------------------ keep_attention
 def _attn(name, *, mma, B, H, Lq, Lk, D, Dv=None, mode=0, packed=False, o_ld=None, o_off=0, amax=False, in_bf16=False, flags=0, ws=True,
-          T=0, seg_len=0, img_h=0, img_w=0, ksplit=0, shift=0, kv_rot=0, n_img=0, lk_rows=None):
+          T=0, seg_len=0, img_h=0, img_w=0, ksplit=0, shift=0, kv_rot=0, n_img=0, lk_rows=None, scale_mul=1.0, amp=1.0):
+    """``scale_mul``: keep_attention_args.scale = scale_mul / sqrt(D); ``amp``: amplitude of v (q, k: +-1 uniform)."""
     return dict(name=name, mma=mma, B=B, H=H, Lq=Lq, Lk=Lk, D=D, Dv=D if Dv is None else Dv, mode=mode, packed=packed, o_ld=o_ld, o_off=o_off,
                 amax=amax, in_bf16=in_bf16, flags=flags, ws=ws, T=T, seg_len=seg_len, img_h=img_h, img_w=img_w, ksplit=ksplit, shift=shift,
-                kv_rot=kv_rot, n_img=n_img, lk_rows=lk_rows)
+                kv_rot=kv_rot, n_img=n_img, lk_rows=lk_rows, scale_mul=scale_mul, amp=amp)
 
 
 ATTN_CASES = [
     _attn('f32_ragged', mma=F_, B=2, H=2, Lq=250, Lk=200, D=32, o_ld=72, o_off=4),
     _attn('f32_dv', mma=F_, B=1, H=1, Lq=250, Lk=200, D=64, Dv=2),
-    _attn('bf16_ragged', mma=B_, B=2, H=2, Lq=250, Lk=200, D=32),
-    _attn('bf16_in', mma=B_, B=1, H=2, Lq=250, Lk=200, D=64, in_bf16=True),
+    _attn('bf16_ragged', mma=B_, B=2, H=2, Lq=250, Lk=200, D=32, scale_mul=8.0, amp=4.0),
+    _attn('bf16_in', mma=B_, B=1, H=2, Lq=250, Lk=200, D=64, in_bf16=True, scale_mul=8.0, amp=4.0),
     _attn('x3_ragged', mma=X_, B=2, H=2, Lq=250, Lk=200, D=32, amax=True, o_ld=72, o_off=4),
     _attn('x3_dv', mma=X_, B=1, H=1, Lq=250, Lk=200, D=64, Dv=2),
     _attn('x3_small_heads', mma=X_, B=3, H=8, Lq=200, Lk=250, D=64, amax=True),
@@ -276,7 +298,7 @@ ATTN_CASES = [
     _attn('x3_no_pack', mma=X_, B=1, H=1, Lq=777, Lk=300, D=128, Dv=64, flags=L.ATTN_NO_PACK),
     _attn('f32_mode1', mma=F_, B=3, H=2, Lq=200, Lk=400, D=32, mode=1, T=3, seg_len=200, packed=True, lk_rows=200),
     _attn('x3_mode1', mma=X_, B=3, H=2, Lq=200, Lk=400, D=32, mode=1, T=3, seg_len=200, packed=True, lk_rows=200),
-    _attn('bf16_mode1', mma=B_, B=3, H=2, Lq=200, Lk=400, D=32, mode=1, T=3, seg_len=200, packed=True, lk_rows=200),
+    _attn('bf16_mode1', mma=B_, B=3, H=2, Lq=200, Lk=400, D=32, mode=1, T=3, seg_len=200, packed=True, lk_rows=200, scale_mul=8.0, amp=4.0),
     _attn('f32_mode2', mma=F_, B=8, H=1, Lq=24, Lk=24, D=32, mode=2, img_h=8, img_w=12, ksplit=2, shift=0, kv_rot=1, n_img=2),
     _attn('x3_mode2_shift', mma=X_, B=8, H=1, Lq=24, Lk=24, D=32, mode=2, img_h=8, img_w=12, ksplit=2, shift=2, kv_rot=1, n_img=2),
     _attn('f32_mode2_shift', mma=F_, B=8, H=1, Lq=24, Lk=24, D=32, mode=2, img_h=8, img_w=12, ksplit=2, shift=2, kv_rot=1, n_img=2),
@@ -286,14 +308,15 @@ ATTN_CASES = [
 ATTN_TILE_BYTES = 128 * 3 * 512 * 4
 
 
-@pytest.mark.parametrize('case', ATTN_CASES, ids=[c['name'] for c in ATTN_CASES])
-def test_attention_footprint(case):
+def attn_case_launch(case):
+    """(regions, launch) of one attention case: the operands with their real strides, the output slice, the range maxima and the
+    scratch the library asks for."""
     c = dict(case)
     B, H, Lq, Lk, D, Dv = c['B'], c['H'], c['Lq'], c['Lk'], c['D'], c['Dv']
     name, tb = 'at' + c['name'], ATTN_TILE_BYTES
     idt = BF16 if c['in_bf16'] else F32
     krows = c['lk_rows'] or Lk                                 # rows of k / v per batch in memory (mode 1: seg_len; keys come from two frames)
-    q, k, v = rnd(name + 'q', (B, Lq, H * D), dtype=idt), rnd(name + 'k', (B, krows, H * D), dtype=idt), rnd(name + 'v', (B, krows, H * Dv), dtype=idt)
+    q, k, v = rnd(name + 'q', (B, Lq, H * D), dtype=idt), rnd(name + 'k', (B, krows, H * D), dtype=idt), rnd(name + 'v', (B, krows, H * Dv), c['amp'], dtype=idt)
     if c['packed']:        # one [rows, q | k | v] buffer with 4 gap columns on either side: each operand is nobody's surroundings
         assert krows == Lq
         ld = 2 * H * D + H * Dv + 8
@@ -314,7 +337,7 @@ def test_attention_footprint(case):
         a = L.AttnArgs()
         a.struct_size = ctypes.sizeof(L.AttnArgs)
         for f, val in dict(q=t['q'], k=t['k'], v=t['v'], o=t['o'], q_bs=qs[0], q_ts=qs[1], q_hs=D, k_bs=ks[0], k_ts=ks[1], k_hs=D, v_bs=vs[0],
-                           v_ts=vs[1], v_hs=Dv, o_bs=Lq * o_ld * per_b, o_ts=o_ld, o_hs=Dv, B=B, H=H, Lq=Lq, Lk=Lk, D=D, Dv=Dv, scale=1.0 / math.sqrt(D),
+                           v_ts=vs[1], v_hs=Dv, o_bs=Lq * o_ld * per_b, o_ts=o_ld, o_hs=Dv, B=B, H=H, Lq=Lq, Lk=Lk, D=D, Dv=Dv, scale=attn_scale(c),
                            mode=c['mode'], T=c['T'], seg_len=c['seg_len'], img_h=c['img_h'], img_w=c['img_w'], ksplit=c['ksplit'],
                            shift=c['shift'], kv_rot=c['kv_rot'], n_img=c['n_img'], mma=c['mma'], in_dtype=L.BF16 if c['in_bf16'] else L.F32,
                            q_amax=t.get('q_amax'), k_amax=t.get('k_amax'), v_amax=t.get('v_amax'), flags=c['flags']).items():
@@ -336,6 +359,12 @@ def test_attention_footprint(case):
         L._check(L.load().keep_attention(ctypes.byref(a), L._stream()), 'keep_attention')
         return now
 
+    return R, launch
+
+
+@pytest.mark.parametrize('case', ATTN_CASES, ids=[c['name'] for c in ATTN_CASES])
+def test_attention_footprint(case):
+    R, launch = attn_case_launch(case)
     out = FP.run(launch, R, 'cuda')
     assert float(out['o'].abs().max()) > 0
 

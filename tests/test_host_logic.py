@@ -953,3 +953,151 @@ def test_footprint_tables_name_every_launcher():
     assert not (covered & T.HOST_ONLY)
     for fn, cases in T.FLAT_CASES.items():
         assert len(cases) >= 2 and len({cid for cid, _ in cases}) == len(cases), fn
+
+
+# ------------------------------------------------------------------------------------------------ the case-value judge (tests/abi_ref.py)
+def _payloads(regions):
+    return {n: d for r in regions for n, (_, _, d) in r.windows.items() if d is not None}
+
+
+def _conv_case_refs():
+    """(name, kernel, geometry, plan, payloads, reference) of every launched convolution case of the footprint table."""
+    import abi_ref as A
+    import test_gpu_footprint as T
+    for name, (_, kw) in T.CONV_CASES.items():
+        if kw.get('launch', True):
+            g, plan, regions, _ = T._conv_regions(name)
+            t = _payloads(regions)
+            yield name, plan.kernel.decode(), g, plan, t, A.conv2d_ref(g, t)
+
+
+def _attn_case_refs():
+    import abi_ref as A
+    import test_gpu_footprint as T
+    for c in T.ATTN_CASES:
+        t = _payloads(T.attn_case_launch(c)[0])
+        yield c, t, A.attention_ref(c, t['q'], t['k'], t['v'])
+
+
+def test_abi_ref_restates_the_bindings_constants():
+    import abi_ref as A
+    from comfyui_keep_amd.engine import hiplib as L
+    for n in ('MMA_F32', 'MMA_BF16', 'MMA_X3', 'PRO_NONE', 'PRO_SWISH', 'PRO_RELU', 'ACT_NONE', 'ACT_RELU', 'ACT_LRELU02', 'ACT_GELU',
+              'ACT_SIGMOID', 'ACT_LRELU01', 'ACT_SILU', 'ATTN_NO_X3'):
+        assert getattr(A, n) == getattr(L, n), n
+
+
+def test_case_value_references_refuse_unknown_keys_and_classify_every_case():
+    """conv2d_ref / attention_ref raise on a key they do not know (a key added to the table later cannot be silently ignored); every
+    table case maps to exactly one tolerance class through the kernel name its plan reports, a family nobody classified raises, and
+    the exact-f32 twin of every x3 case plans onto an exact-f32 kernel."""
+    import abi_ref as A
+    import test_gpu_footprint as T
+    g, _, regions, _ = T._conv_regions('halo_f32_32')
+    with pytest.raises(KeyError, match='dilation'):
+        A.conv2d_ref(A.dict_view(g, dilation=2), _payloads(regions))
+    c = T.ATTN_CASES[0]
+    t = _payloads(T.attn_case_launch(c)[0])
+    with pytest.raises(KeyError, match='causal'):
+        A.attention_ref(dict(c, causal=True), t['q'], t['k'], t['v'])
+    with pytest.raises(KeyError):
+        A.conv_class('conv_fp8_kernel<2, 2>')
+    classes = {}
+    for name, (expect, kw) in T.CONV_CASES.items():
+        _, g, plan = T.conv_case_plan(name)
+        klass = A.conv_class(plan.kernel.decode())
+        assert (klass == 'plan-only') == (not g.launch), name
+        classes.setdefault(klass, []).append(name)
+        if klass == 'x3':
+            _, _, twin = T.conv_case_plan(name, A.conv_twin_kw(kw))
+            assert A.conv_class(twin.kernel.decode()) == 'f32', (name, twin.kernel.decode())
+        elif klass != 'plan-only':
+            assert A.conv_tol(klass, g) in (2e-4, 2e-5, 2e-3, 2e-5 + 2.0 ** -8), name
+    assert {k_: len(v) for k_, v in classes.items()} == {'f32': 16, 'x3': 26, 'bf16': 13, 'plan-only': 1}, classes
+    # 'f32_t2_x3_fallback' asks for x3 and runs on an f32 kernel: the class follows the kernel, not the request
+    assert 'f32_t2_x3_fallback' in classes['f32'] and 'cout4_x3' in classes['f32']
+    assert sorted({A.attn_class(c) for c in T.ATTN_CASES}) == ['bf16', 'f32', 'x3']
+
+
+def test_case_value_references_feel_every_optional_input():
+    """For every case and every optional input it switches on, the reference without that input differs from the full reference by
+    at least 100 x the case's tolerance x scale: a kernel that ignores the input cannot pass tests/test_gpu_case_values.py.
+    Convolutions: bias, pro_scale, pro_shift, the per-image rows of both, prologue / epilogue activation, residual, aux, reflect, in2,
+    LayerNorm gamma / beta.  Attention: the mode-2 mask, roll and kv_rot, the mode-1 second key segment, the head stride."""
+    import abi_ref as A
+    seen = set()
+    for name, kernel, g, plan, t, ref in _conv_case_refs():
+        tol, sc = A.conv_tol(A.conv_class(kernel), g), max(1.0, float(ref['out'].abs().max()))
+        for what, g2, t2 in A.conv_removals(g, t):
+            d = float((A.conv2d_ref(g2, t2)['out'] - ref['out']).abs().max())
+            assert d >= A.SENSITIVITY * tol * sc, (name, what, d / sc, tol)
+            seen.add(what)
+    assert seen == {'bias', 'pro_scale', 'pro_shift', 'per-image prologue rows', 'prologue activation', 'epilogue activation', 'residual', 'aux',
+                    'reflect', 'in2', 'ln_gamma', 'ln_beta'}, seen
+    seen = set()
+    for c, t, ref in _attn_case_refs():
+        tol, sc = A.attn_tol(A.attn_class(c)), max(1.0, float(ref.abs().max()))
+        for what in A.attn_case_removals(c):
+            d = float((A.attention_ref(c, t['q'], t['k'], t['v'], remove=what) - ref).abs().max())
+            assert d >= A.SENSITIVITY * tol * sc, (c['name'], what, d / sc, tol)
+            seen.add(what)
+    assert seen == set(A.ATTN_REMOVALS), seen
+
+
+def _fake_device_conv(g, P, out64, stats_from=None):
+    """What a correct kernel would hand back for reference output ``out64``: `out` in the case's output dtype, P statistics partials per
+    image (of ``stats_from`` if given: an output and statistics that disagree), and the amax arena."""
+    out = out64.to(torch.bfloat16 if g.out_bf16 else torch.float32)
+    got = {'out': out}
+    if g.stats:
+        s = (out64 if stats_from is None else stats_from).reshape(g.N, P, -1, g.Cout)
+        got['stats'] = torch.stack([s.sum(2), (s * s).sum(2)], dim=-1).float().reshape(1, -1)
+    if g.amax:
+        got['amax'] = out.float().reshape(g.N, -1).abs().amax(1).reshape(1, g.N)
+        got['amax_lo'], got['amax_hi'] = torch.zeros(1, 3), torch.zeros(1, 8 - g.N)
+    return got
+
+
+def test_case_value_judge_bites(capsys):
+    """abi_ref.judge_conv / judge_attn on the CPU, for every table case: the reference itself (rounded to the output dtype) passes; the
+    same with ONE element moved by 10 x tol x scale fails; the reference of the case with any one optional input dropped fails; for
+    cases with fused outputs, statistics of another tensor than `out`, an amax slot one ulp off and a written neighbour slot fail."""
+    import abi_ref as A
+    n_bites = 0
+    for name, kernel, g, plan, t, ref in _conv_case_refs():
+        klass, P = A.conv_class(kernel), plan.stats_P
+        sc = max(1.0, float(ref['out'].abs().max()))
+        twin = ref['out'].float() if klass == 'x3' else None
+        A.judge_conv(name, kernel, g, _fake_device_conv(g, P, ref['out']), ref, twin, P)
+        moved = ref['out'].clone()
+        moved.view(-1)[moved.numel() // 2] += 10 * A.conv_tol(klass, g) * sc
+        wrong = [('one element', _fake_device_conv(g, P, moved))]
+        removed = {what: A.conv2d_ref(g2, t2)['out'] for what, g2, t2 in A.conv_removals(g, t)}
+        wrong += [(what, _fake_device_conv(g, P, o)) for what, o in removed.items()]
+        if g.stats:
+            wrong.append(('statistics of another tensor', _fake_device_conv(g, P, ref['out'], stats_from=removed['bias'])))
+        if g.amax:
+            ulp = _fake_device_conv(g, P, ref['out'])
+            ulp['amax'] = torch.nextafter(ulp['amax'], torch.full_like(ulp['amax'], 1e30))
+            nb = _fake_device_conv(g, P, ref['out'])
+            nb['amax_hi'][0, 0] = 1.0
+            wrong += [('amax one ulp off', ulp), ('neighbour slot written', nb)]
+        for what, got in wrong:
+            with pytest.raises(AssertionError):
+                A.judge_conv(name, kernel, g, got, ref, twin, P)
+                pytest.fail(f'{name}: the judge let "{what}" pass')
+            n_bites += 1
+    for c, t, ref in _attn_case_refs():
+        klass = A.attn_class(c)
+        twin = ref.float() if klass == 'x3' else None
+        A.judge_attn(c, ref.float(), ref, twin)
+        moved = ref.clone()
+        moved.view(-1)[moved.numel() // 2] += 10 * A.attn_tol(klass) * max(1.0, float(ref.abs().max()))
+        wrong = [('one element', moved)] + [(what, A.attention_ref(c, t['q'], t['k'], t['v'], remove=what)) for what in A.attn_case_removals(c)]
+        for what, got in wrong:
+            with pytest.raises(AssertionError):
+                A.judge_attn(c, got.float(), ref, twin)
+                pytest.fail(f"{c['name']}: the judge let \"{what}\" pass")
+            n_bites += 1
+    assert n_bites >= 200, n_bites
+    assert capsys.readouterr().out.count('[case-values]') >= n_bites
