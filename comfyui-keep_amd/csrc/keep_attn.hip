@@ -15,6 +15,8 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "keep_common.h"
 
 // cache policy of the x3 attention kernel's output rows: default (nt stores measured 3 ms slower per step: the merge GEMM that follows
@@ -41,6 +43,30 @@ struct AttnP {
   const float* q_amax;   // KEEP_MMA_X3 range probes ([B] each) or NULL
   const float* k_amax;
   const float* v_amax;
+};
+
+// What one keep_attention call launches.  plan_attention (in front of keep_attention) is the only place that fills it: the
+// scratch query and the launch both read its answer, and the launchers below take their LDS size from it.
+enum AttnForm {
+  ATTN_F32,          // attn_f32_kernel<waves, dvt>
+  ATTN_BF16,         // attn_bf16_kernel<waves, dvt>
+  ATTN_BF16IN,       // attn_bf16in_kernel<dvt, masked>
+  ATTN_X3_NQ8,       // attn_x3_kernel<waves, dvt, 8>: D <= 128, Q fragments in registers
+  ATTN_X3_NQ16,      // attn_x3_kernel<4, dvt, 16>: D <= 256
+  ATTN_X3_NQ0,       // attn_x3_kernel<4, dvt, 0>: Q and K re-staged per 128-wide chunk
+  ATTN_X3_PACKED,    // attn_pack_kv_x3_kernel into the scratch + attn_x3_kernel<4, dvt, D / 16, true>
+  ATTN_X3_SMALL,     // attn_x3_small_kernel
+  ATTN_X3_TWO_PASS,  // attn_scores_x3l_kernel into the scratch + attn_pv_x3l_kernel
+  ATTN_X3_SFULL,     // attn_x3_sfull_kernel<dvt>
+  ATTN_X3_SFULL2,    // attn_x3_sfull2_kernel
+};
+struct AttnPlan {
+  AttnForm form;
+  int waves;     // 32-query waves per block of the form's flash kernel: 1 or 4
+  int dvt;       // dv slice per block in 32-column tiles: 1 / 2 / 4 (AttnP.nslices slices per head)
+  bool masked;   // ATTN_BF16IN: the region-mask instantiation (shifted windows)
+  size_t lds;    // dynamic LDS bytes of the form's (last) launch
+  int64_t scratch;  // bytes of `workspace` the form writes; 0: none
 };
 
 // KEEP_MMA_X3 range scaling (same rule as keep_conv_common.h): power of two s with amax * s in [2^14, 2^15), and 1/s
@@ -387,21 +413,11 @@ __global__ __launch_bounds__(64 * WAVES, 2) void attn_f32_kernel(AttnP p) {
 }
 
 template <int WAVES, int DVT>
-static int launch_attn(const AttnP& p, hipStream_t st) {
-  const int DC = p.D < 128 ? p.D : 128;
-  const size_t lds = (size_t)((WAVES * 32 + 32) * (DC + 1) + 32 * DVT * 32) * sizeof(float);
-  static bool attr_set = false;  // per instantiation; idempotent, benign if raced
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_f32_kernel<WAVES, DVT>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      keep_set_error("keep_attention: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return KEEP_EHIP;
-    }
-    attr_set = true;
-  }
+static int launch_attn(const AttnP& p, const AttnPlan& pl, hipStream_t st) {
+  const int rc = keep_raise_lds_limit<attn_f32_kernel<WAVES, DVT>>("keep_attention");
+  if (rc != KEEP_OK) return rc;
   dim3 grid(cdiv(p.Lq, WAVES * 32), p.H * p.nslices, p.B);
-  hipLaunchKernelGGL((attn_f32_kernel<WAVES, DVT>), grid, dim3(64 * WAVES), lds, st, p);
+  hipLaunchKernelGGL((attn_f32_kernel<WAVES, DVT>), grid, dim3(64 * WAVES), pl.lds, st, p);
   KEEP_LAUNCH_CHECK("keep_attention");
   return KEEP_OK;
 }
@@ -575,21 +591,11 @@ __global__ __launch_bounds__(64 * WAVES) void attn_bf16_kernel(AttnP p) {
 }
 
 template <int WAVES, int DVT>
-static int launch_attn_bf16(const AttnP& p, hipStream_t st) {
-  const int DC = p.D < 128 ? p.D : 128;
-  const size_t lds = (size_t)((WAVES * 32 + 32) * (DC + 8) + DVT * 32 * 40) * 2;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_bf16_kernel<WAVES, DVT>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      keep_set_error("keep_attention: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return KEEP_EHIP;
-    }
-    attr_set = true;
-  }
+static int launch_attn_bf16(const AttnP& p, const AttnPlan& pl, hipStream_t st) {
+  const int rc = keep_raise_lds_limit<attn_bf16_kernel<WAVES, DVT>>("keep_attention");
+  if (rc != KEEP_OK) return rc;
   dim3 grid(cdiv(p.Lq, WAVES * 32), p.H * p.nslices, p.B);
-  hipLaunchKernelGGL((attn_bf16_kernel<WAVES, DVT>), grid, dim3(64 * WAVES), lds, st, p);
+  hipLaunchKernelGGL((attn_bf16_kernel<WAVES, DVT>), grid, dim3(64 * WAVES), pl.lds, st, p);
   KEEP_LAUNCH_CHECK("keep_attention(bf16)");
   return KEEP_OK;
 }
@@ -1112,60 +1118,26 @@ __global__ __launch_bounds__(256) void attn_pack_kv_x3_kernel(AttnP p, _Float16*
   for (int i = tid; i < PKV; i += 256) dst[PKK + slice * PKV + i] = reinterpret_cast<const uint4*>(img)[PKK + i];
 }
 
-// packed K / V^T path: worth it when several query blocks stream the same keys
-static long attn_pack_bytes(const AttnP& p, int mma) {
-  if (mma != KEEP_MMA_X3 || (p.D != 128 && p.D != 256) || p.Lq < 256 || (p.flags & KEEP_ATTN_NO_PACK)) return 0;
-  const int dvs = p.Dv <= 32 ? 32 : (p.Dv <= 64 ? 64 : 128);
-  const int nsl = (p.Dv + dvs - 1) / dvs;
-  return (long)p.B * p.H * ((p.Lk + 31) / 32) * ((32 * (2 * p.D + 8) + nsl * dvs * 72) * 2L);
-}
-
 template <int DVT, int NQ>
-static int launch_attn_x3_packed(const AttnP& p, hipStream_t st) {
-  constexpr int DC = 16 * NQ;
+static int launch_attn_x3_packed(const AttnP& p, const AttnPlan& pl, hipStream_t st) {
   const int ntl = (p.Lk + 31) / 32;
-  hipLaunchKernelGGL((attn_pack_kv_x3_kernel<DC, DVT * 32>), dim3(ntl, p.H * p.nslices, p.B), dim3(256), 0, st, p,
+  hipLaunchKernelGGL((attn_pack_kv_x3_kernel<16 * NQ, DVT * 32>), dim3(ntl, p.H * p.nslices, p.B), dim3(256), 0, st, p,
                      const_cast<_Float16*>(p.kv_pack));
   KEEP_LAUNCH_CHECK("keep_attention(x3 pack)");
-  size_t lds = (size_t)(32 * (2 * DC + 8) + DVT * 32 * 72) * 2;
-  if (p.mode == 2 && p.Lk <= 4096) lds += (size_t)ntl * (32 * 4 + 16 + 32);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_x3_kernel<4, DVT, NQ, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      keep_set_error("keep_attention: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return KEEP_EHIP;
-    }
-    attr_set = true;
-  }
+  const int rc = keep_raise_lds_limit<attn_x3_kernel<4, DVT, NQ, true>>("keep_attention");
+  if (rc != KEEP_OK) return rc;
   dim3 grid(cdiv(p.Lq, 128), p.H * p.nslices, p.B);
-  hipLaunchKernelGGL((attn_x3_kernel<4, DVT, NQ, true>), grid, dim3(256), lds, st, p);
+  hipLaunchKernelGGL((attn_x3_kernel<4, DVT, NQ, true>), grid, dim3(256), pl.lds, st, p);
   KEEP_LAUNCH_CHECK("keep_attention(x3 packed)");
   return KEEP_OK;
 }
 
 template <int WAVES, int DVT, int NQ>
-static int launch_attn_x3_t(const AttnP& p, hipStream_t st) {
-  constexpr bool QREG = NQ > 0;
-  const int DCMAX = QREG ? 16 * NQ : 128;
-  const int DC = p.D < DCMAX ? p.D : DCMAX;
-  size_t lds = (size_t)(((QREG ? 0 : WAVES * 32) + 32) * (2 * DC + 8) + DVT * 32 * 72) * 2;
-  if (WAVES == 4 && QREG && p.mode == 2 && p.Lk <= 4096) {      // window tables: pixel per key, packed + byte region ids
-    const size_t ntl = (size_t)(p.Lk + 31) / 32;
-    lds += ntl * 32 * 4 + ntl * 16 + ntl * 32;
-  }
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_x3_kernel<WAVES, DVT, NQ>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      keep_set_error("keep_attention: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return KEEP_EHIP;
-    }
-    attr_set = true;
-  }
+static int launch_attn_x3_t(const AttnP& p, const AttnPlan& pl, hipStream_t st) {
+  const int rc = keep_raise_lds_limit<attn_x3_kernel<WAVES, DVT, NQ>>("keep_attention");
+  if (rc != KEEP_OK) return rc;
   dim3 grid(cdiv(p.Lq, WAVES * 32), p.H * p.nslices, p.B);
-  hipLaunchKernelGGL((attn_x3_kernel<WAVES, DVT, NQ>), grid, dim3(64 * WAVES), lds, st, p);
+  hipLaunchKernelGGL((attn_x3_kernel<WAVES, DVT, NQ>), grid, dim3(64 * WAVES), pl.lds, st, p);
   KEEP_LAUNCH_CHECK("keep_attention(x3)");
   return KEEP_OK;
 }
@@ -1556,41 +1528,20 @@ __global__ __launch_bounds__(256, 1) void attn_x3_sfull2_kernel(AttnP p) {
   }
 }
 
-static bool attn_sfull2_ok(const AttnP& p) {
-  return p.mode == 0 && p.D == 512 && p.Lk <= 256 && p.Dv <= 512 && p.Dv % 4 == 0 && p.v_ts % 4 == 0 && p.v_bs % 4 == 0 &&
-         p.v_hs % 4 == 0 && (uintptr_t)p.v % 16 == 0 && !(p.flags & KEEP_ATTN_NO_SFULL2);
-}
-
-static int launch_attn_x3_sfull2(const AttnP& p, hipStream_t st) {
-  const size_t lds = (size_t)4 * (2 * 32 * (2 * 128 + 8)) * 2 + 4 * 1024 * 4;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_x3_sfull2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      keep_set_error("keep_attention: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return KEEP_EHIP;
-    }
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(attn_x3_sfull2_kernel, dim3(cdiv(p.Lq, 32), p.H, p.B), dim3(256), lds, st, p);
+static int launch_attn_x3_sfull2(const AttnP& p, const AttnPlan& pl, hipStream_t st) {
+  const int rc = keep_raise_lds_limit<attn_x3_sfull2_kernel>("keep_attention");
+  if (rc != KEEP_OK) return rc;
+  hipLaunchKernelGGL(attn_x3_sfull2_kernel, dim3(cdiv(p.Lq, 32), p.H, p.B), dim3(256), pl.lds, st, p);
   KEEP_LAUNCH_CHECK("keep_attention(x3, full score row, 32-query blocks)");
   return KEEP_OK;
 }
 
 template <int DVT>
-static int launch_attn_x3_sfull(const AttnP& p, hipStream_t st) {
-  const size_t lds = (size_t)((128 + 64) * (2 * 128 + 8) + DVT * 32 * 72) * 2;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_x3_sfull_kernel<DVT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      keep_set_error("keep_attention: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return KEEP_EHIP;
-    }
-    attr_set = true;
-  }
+static int launch_attn_x3_sfull(const AttnP& p, const AttnPlan& pl, hipStream_t st) {
+  const int rc = keep_raise_lds_limit<attn_x3_sfull_kernel<DVT>>("keep_attention");
+  if (rc != KEEP_OK) return rc;
   dim3 grid(cdiv(p.Lq, 128), p.H * p.nslices, p.B);
-  hipLaunchKernelGGL((attn_x3_sfull_kernel<DVT>), grid, dim3(256), lds, st, p);
+  hipLaunchKernelGGL((attn_x3_sfull_kernel<DVT>), grid, dim3(256), pl.lds, st, p);
   KEEP_LAUNCH_CHECK("keep_attention(x3, full score row)");
   return KEEP_OK;
 }
@@ -1734,12 +1685,6 @@ __global__ __launch_bounds__(256) void attn_pv_x3l_kernel(AttnP p, const float* 
   *reinterpret_cast<float4*>(p.o + (long)b * p.o_bs + (long)head * p.o_hs + (long)(q0 + row) * p.o_ts + dv0 + c4) =
       make_float4(v.x * il, v.y * il, v.z * il, v.w * il);
 }
-
-static bool attn_two_pass_ok(const AttnP& p) {
-  return p.mode == 0 && p.D == 512 && p.Dv == 512 && p.Lq == 256 && p.Lk == 256 && !p.q_amax && p.o_ts % 4 == 0 && p.o_bs % 4 == 0 &&
-         p.o_hs % 4 == 0 && (uintptr_t)p.o % 16 == 0 && !(p.flags & KEEP_ATTN_NO_TWO_PASS);
-}
-static long attn_two_pass_bytes(const AttnP& p) { return (long)p.B * p.H * p.Lq * p.Lk * 4; }
 
 static int launch_attn_x3_two_pass(const AttnP& p, float* scores, hipStream_t st) {
   hipLaunchKernelGGL(attn_scores_x3l_kernel, dim3(p.Lk / 32, p.Lq / 32, p.B * p.H), dim3(256), 0, st, p, scores);
@@ -1955,25 +1900,10 @@ __global__ __launch_bounds__(256) void attn_x3_small_kernel(AttnP p) {
   }
 }
 
-static bool attn_small_ok(const AttnP& p) {
-  return p.mode == 0 && p.D == 64 && p.Dv == 64 && p.Lk <= 256 && p.Lq >= 64 && p.v_ts % 4 == 0 && p.v_bs % 4 == 0 && p.v_hs % 4 == 0 &&
-         (uintptr_t)p.v % 16 == 0 && p.o_ts % 4 == 0 && p.o_bs % 4 == 0 && p.o_hs % 4 == 0 && (uintptr_t)p.o % 16 == 0 &&
-         !(p.flags & KEEP_ATTN_NO_SMALL);
-}
-
 static int launch_attn_x3_small(const AttnP& p, hipStream_t st) {
   hipLaunchKernelGGL(attn_x3_small_kernel, dim3(cdiv(p.Lq, 32), p.H, p.B), dim3(256), 0, st, p);
   KEEP_LAUNCH_CHECK("keep_attention(x3, small heads, latency form)");
   return KEEP_OK;
-}
-
-template <int WAVES, int DVT>
-static int launch_attn_x3(const AttnP& p, hipStream_t st) {
-  if (p.D <= 128) return launch_attn_x3_t<WAVES, DVT, 8>(p, st);
-  if (p.D <= 256) return launch_attn_x3_t<4, DVT, 16>(p, st);
-  if (attn_sfull2_ok(p)) return launch_attn_x3_sfull2(p, st);
-  if (p.mode == 0 && p.Lk <= 256 && p.D % 128 == 0) return launch_attn_x3_sfull<DVT>(p, st);
-  return launch_attn_x3_t<4, DVT, 0>(p, st);
 }
 
 // ------------------------------------------------------------------------------------------------ bf16-input variant
@@ -2312,29 +2242,15 @@ __global__ __launch_bounds__(256, 2) void attn_bf16in_kernel(AttnP p) {
 }
 
 template <int DVT>
-static int launch_attn_bf16in(const AttnP& p, hipStream_t st) {
-  const int DC = p.D < 128 ? p.D : 128;
-  const size_t operands = (size_t)((128 + 64) * (DC + 8) + DVT * 32 * 72) * 2;
-  const size_t staging = (size_t)4 * 32 * (DVT * 32 + 4) * 4;          // the output tiles reuse the operand area
-  const size_t lds = (128 + 3 * 64 + 3 * 64) * sizeof(long) + 3 * 16 * sizeof(unsigned long long) +
-                     (operands > staging ? operands : staging);
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)attn_bf16in_kernel<DVT, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       160 * 1024);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)attn_bf16in_kernel<DVT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      keep_set_error("keep_attention: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return KEEP_EHIP;
-    }
-    attr_set = true;
-  }
+static int launch_attn_bf16in(const AttnP& p, const AttnPlan& pl, hipStream_t st) {
+  int rc = keep_raise_lds_limit<attn_bf16in_kernel<DVT, false>>("keep_attention");   // both instantiations on first use of either
+  if (rc == KEEP_OK) rc = keep_raise_lds_limit<attn_bf16in_kernel<DVT, true>>("keep_attention");
+  if (rc != KEEP_OK) return rc;
   dim3 grid(cdiv(p.Lq, 128), p.H * p.nslices, p.B);
-  if (p.mode == 2 && p.shift > 0)
-    hipLaunchKernelGGL((attn_bf16in_kernel<DVT, true>), grid, dim3(256), lds, st, p);
+  if (pl.masked)
+    hipLaunchKernelGGL((attn_bf16in_kernel<DVT, true>), grid, dim3(256), pl.lds, st, p);
   else
-    hipLaunchKernelGGL((attn_bf16in_kernel<DVT, false>), grid, dim3(256), lds, st, p);
+    hipLaunchKernelGGL((attn_bf16in_kernel<DVT, false>), grid, dim3(256), pl.lds, st, p);
   KEEP_LAUNCH_CHECK("keep_attention(bf16 inputs)");
   return KEEP_OK;
 }
@@ -2353,132 +2269,204 @@ static int attn_args_in(const keep_attention_args* src, keep_attention_args& a) 
   return KEEP_OK;
 }
 
+// The one place where a call's kernel form is chosen: validates the shape, fills the complete kernel argument struct `p`
+// and the plan `pl`.  keep_attention_workspace_bytes asks with unlimited scratch and keep_attention with the caller's, so the
+// two cannot disagree; a form whose scratch need exceeds `scratch_avail` is skipped.  Pointers are only tested for
+// alignment, never dereferenced (the query is called without tensors).
+static int plan_attention(const keep_attention_args& a, int64_t scratch_avail, AttnP& p, AttnPlan& pl) {
+  KEEP_REQUIRE(a.B > 0 && a.H > 0 && a.Lq > 0 && a.Lk > 0 && a.D > 0 && a.Dv > 0, "keep_attention: bad dims");
+  KEEP_REQUIRE(a.D % 2 == 0 && (a.D <= 128 || a.D % 128 == 0), "keep_attention: D=%d must be even and (<= 128 or a multiple of 128)", a.D);
+  KEEP_REQUIRE(a.mode >= 0 && a.mode <= 2, "keep_attention: bad mode %d", a.mode);
+  KEEP_REQUIRE(a.mma == KEEP_MMA_F32 || a.mma == KEEP_MMA_BF16 || a.mma == KEEP_MMA_X3, "keep_attention: bad mma %d", a.mma);
+  if (a.mode == 1)
+    KEEP_REQUIRE(a.T > 0 && a.seg_len > 0 && a.Lk == 2 * a.seg_len && a.B % a.T == 0,
+                 "keep_attention: sparse-causal mode needs Lk == 2*seg_len and B %% T == 0");
+  if (a.mode == 2) {
+    KEEP_REQUIRE(a.ksplit > 0 && a.img_h % a.ksplit == 0 && a.img_w % a.ksplit == 0, "keep_attention: bad window split");
+    const int wh = a.img_h / a.ksplit, ww = a.img_w / a.ksplit;
+    KEEP_REQUIRE(a.Lq == wh * ww && a.Lk == wh * ww, "keep_attention: window mode needs Lq == Lk == window size");
+    KEEP_REQUIRE(a.n_img > 0 && a.B == a.n_img * a.ksplit * a.ksplit, "keep_attention: B != n_img*ksplit^2");
+    // the region mask (win_region / win_token) assumes a roll by half a window: shift is 0 or wh/2 (the kernels then roll the
+    // columns by ww/2, GM/transformer.py:75-80)
+    KEEP_REQUIRE(a.shift == 0 || a.shift == wh / 2, "keep_attention: shift=%d must be 0 or img_h/ksplit/2 = %d", a.shift, wh / 2);
+    KEEP_REQUIRE(a.kv_rot >= 0 && a.kv_rot < a.n_img, "keep_attention: bad kv_rot");
+    KEEP_REQUIRE((long)a.img_h * a.img_w <= 65536, "keep_attention: window mode supports maps of at most 65536 tokens");
+  }
+  KEEP_REQUIRE((!a.q_amax && !a.k_amax && !a.v_amax) || (a.q_amax && a.k_amax && a.v_amax && a.mode == 0 && a.mma == KEEP_MMA_X3),
+               "keep_attention: q/k/v_amax come together, with KEEP_MMA_X3 and mode 0 only");
+  p.flags = a.flags;
+  p.q = (const float*)a.q; p.k = (const float*)a.k; p.v = (const float*)a.v; p.o = a.o;
+  p.q16 = (const unsigned short*)a.q; p.k16 = (const unsigned short*)a.k; p.v16 = (const unsigned short*)a.v;
+  p.q_bs = a.q_bs; p.q_ts = a.q_ts; p.q_hs = a.q_hs;
+  p.k_bs = a.k_bs; p.k_ts = a.k_ts; p.k_hs = a.k_hs;
+  p.v_bs = a.v_bs; p.v_ts = a.v_ts; p.v_hs = a.v_hs;
+  p.o_bs = a.o_bs; p.o_ts = a.o_ts; p.o_hs = a.o_hs;
+  p.B = a.B; p.H = a.H; p.Lq = a.Lq; p.Lk = a.Lk; p.D = a.D; p.Dv = a.Dv;
+  p.scale = a.scale; p.mode = a.mode; p.T = a.T; p.seg_len = a.seg_len;
+  p.img_h = a.img_h; p.img_w = a.img_w; p.ksplit = a.ksplit; p.shift = a.shift; p.kv_rot = a.kv_rot;
+  p.n_img = a.n_img;
+  p.q_amax = a.q_amax; p.k_amax = a.k_amax; p.v_amax = a.v_amax;
+  p.kv_pack = nullptr;
+  // dv slice per block: 32 / 64 / 128 columns
+  const int dvt = a.Dv <= 32 ? 1 : (a.Dv <= 64 ? 2 : 4);
+  p.nslices = cdiv(a.Dv, dvt * 32);
+  // one wave per block for tiny query counts (temporal attention over T frames), else 4 (one per SIMD)
+  pl = AttnPlan{ATTN_F32, a.Lq <= 32 ? 1 : 4, dvt, false, 0, 0};
+
+  // rows of a tensor start on 16-byte boundaries: base pointer, and every stride a multiple of `n` elements
+  auto rows16 = [](const void* base, int64_t bs, int64_t ts, int64_t hs, int n) {
+    return bs % n == 0 && ts % n == 0 && hs % n == 0 && (uintptr_t)base % 16 == 0;
+  };
+  const int DC = a.D < 128 ? a.D : 128;                       // QK depth of one chunk of the staged kernels
+  const size_t ntl = (size_t)(a.Lk + 31) / 32;                // key tiles
+  const size_t win_tables = ntl * 32 * 4 + ntl * 16 + ntl * 32;    // window tables: pixel per key, packed + byte region ids
+
+  if (a.in_dtype == KEEP_BF16) {
+    const bool ok = a.mma == KEEP_MMA_BF16 && a.D % 16 == 0 && a.Dv % 8 == 0 && rows16(a.q, a.q_bs, a.q_ts, a.q_hs, 8) &&
+                    rows16(a.k, a.k_bs, a.k_ts, a.k_hs, 8) && rows16(a.v, a.v_bs, a.v_ts, a.v_hs, 8);
+    KEEP_REQUIRE(ok, "keep_attention: bf16 inputs need KEEP_MMA_BF16, D %% 16 == 0, Dv %% 8 == 0 and 16-byte aligned rows");
+    const size_t operands = (size_t)((128 + 64) * (DC + 8) + dvt * 32 * 72) * 2;
+    const size_t staging = (size_t)4 * 32 * (dvt * 32 + 4) * 4;          // the output tiles reuse the operand area
+    pl.form = ATTN_BF16IN;
+    pl.waves = 4;
+    pl.masked = a.mode == 2 && a.shift > 0;
+    pl.lds = (128 + 3 * 64 + 3 * 64) * sizeof(long) + 3 * 16 * sizeof(unsigned long long) + (operands > staging ? operands : staging);
+    return KEEP_OK;
+  }
+  // fp32 q / k with 16-byte aligned rows and D a multiple of 16: what the bf16-operand and the split-fp16 kernels both need
+  const bool qk16 = a.D % 16 == 0 && rows16(a.q, a.q_bs, a.q_ts, a.q_hs, 4) && rows16(a.k, a.k_bs, a.k_ts, a.k_hs, 4);
+  if (a.mma == KEEP_MMA_BF16) {
+    KEEP_REQUIRE(qk16, "keep_attention: KEEP_MMA_BF16 needs D %% 16 == 0 and 16-byte aligned q/k rows");
+    pl.form = ATTN_BF16;
+    pl.lds = (size_t)((pl.waves * 32 + 32) * (DC + 8) + dvt * 32 * 40) * 2;
+    return KEEP_OK;
+  }
+  // split fp16: everything else (and KEEP_ATTN_NO_X3) runs on the exact-f32 kernel
+  if (a.mma != KEEP_MMA_X3 || !qk16 || (a.flags & KEEP_ATTN_NO_X3)) {
+    pl.lds = (size_t)((pl.waves * 32 + 32) * (DC + 1) + 32 * dvt * 32) * sizeof(float);
+    return KEEP_OK;
+  }
+
+  const bool v16 = rows16(a.v, a.v_bs, a.v_ts, a.v_hs, 4), o16 = rows16(a.o, a.o_bs, a.o_ts, a.o_hs, 4);
+  // LDS of attn_x3_kernel<waves, dvt, nq, ·>: nq 16-wide Q steps in registers (nq = 0: Q staged next to K per 128-wide chunk)
+  auto x3_lds = [&](int waves, int nq) {
+    const int dc = nq == 0 ? 128 : (a.D < 16 * nq ? a.D : 16 * nq);
+    const size_t lds = (size_t)(((nq ? 0 : waves * 32) + 32) * (2 * dc + 8) + dvt * 32 * 72) * 2;
+    return lds + (waves == 4 && nq && a.mode == 2 && a.Lk <= 4096 ? win_tables : 0);
+  };
+  // small heads over at most 256 keys (the code transformer's MultiheadAttention): the latency form wins over everything
+  if (a.mode == 0 && a.D == 64 && a.Dv == 64 && a.Lk <= 256 && a.Lq >= 64 && v16 && o16 && !(a.flags & KEEP_ATTN_NO_SMALL)) {
+    pl.form = ATTN_X3_SMALL;
+    return KEEP_OK;
+  }
+  // the VQGAN AttnBlock at 16 x 16 as scores + softmax . V, the score matrix between the two launches in the scratch; its
+  // kernels take no range probes (!q_amax)
+  if (a.mode == 0 && a.D == 512 && a.Dv == 512 && a.Lq == 256 && a.Lk == 256 && !a.q_amax && o16 && !(a.flags & KEEP_ATTN_NO_TWO_PASS)) {
+    const int64_t need = (int64_t)a.B * a.H * a.Lq * a.Lk * 4;
+    if (scratch_avail >= need) {
+      pl.form = ATTN_X3_TWO_PASS;
+      pl.scratch = need;
+      return KEEP_OK;
+    }
+  }
+  // packed K / V^T path: worth it when several query blocks stream the same keys (Lq >= 256: never a one-wave call); the
+  // scratch holds one LDS tile image per key tile, K once and V^T per dv slice
+  if ((a.D == 128 || a.D == 256) && a.Lq >= 256 && !(a.flags & KEEP_ATTN_NO_PACK)) {
+    const int64_t need = (int64_t)a.B * a.H * (int64_t)ntl * ((32 * (2 * a.D + 8) + p.nslices * dvt * 32 * 72) * 2L);
+    if (scratch_avail >= need) {
+      pl.form = ATTN_X3_PACKED;
+      pl.lds = x3_lds(4, a.D / 16);
+      pl.scratch = need;
+      return KEEP_OK;
+    }
+  }
+  if (a.D <= 128) {
+    pl.form = ATTN_X3_NQ8;
+    pl.lds = x3_lds(pl.waves, 8);
+    return KEEP_OK;
+  }
+  pl.waves = 4;    // D > 128 has no one-wave kernel: Lq <= 32 runs the four-wave ones
+  if (a.D <= 256) {
+    pl.form = ATTN_X3_NQ16;
+    pl.lds = x3_lds(4, 16);
+  } else if (a.mode == 0 && a.D == 512 && a.Lk <= 256 && a.Dv <= 512 && a.Dv % 4 == 0 && v16 && !(a.flags & KEEP_ATTN_NO_SFULL2)) {
+    pl.form = ATTN_X3_SFULL2;
+    pl.lds = (size_t)4 * (2 * 32 * (2 * 128 + 8)) * 2 + 4 * 1024 * 4;
+  } else if (a.mode == 0 && a.Lk <= 256 && a.D % 128 == 0) {
+    pl.form = ATTN_X3_SFULL;
+    pl.lds = (size_t)((128 + 64) * (2 * 128 + 8) + dvt * 32 * 72) * 2;
+  } else {
+    pl.form = ATTN_X3_NQ0;
+    pl.lds = x3_lds(4, 0);
+  }
+  return KEEP_OK;
+}
+
+// the runtime dv slice width (AttnPlan.dvt: 1 / 2 / 4) as a compile-time constant: f(std::integral_constant<int, DVT>)
+template <class F>
+static int with_dvt(int dvt, F f) {
+  if (dvt == 1) return f(std::integral_constant<int, 1>{});
+  if (dvt == 2) return f(std::integral_constant<int, 2>{});
+  return f(std::integral_constant<int, 4>{});
+}
+
 extern "C" int32_t keep_sizeof_attention_args(void) { return (int32_t)sizeof(keep_attention_args); }
 
 extern "C" int64_t keep_attention_workspace_bytes(const keep_attention_args* a_in) {
-  keep_attention_args a_local;
-  if (attn_args_in(a_in, a_local) != KEEP_OK) return 0;
-  const keep_attention_args* a = &a_local;
-  if (a->mma != KEEP_MMA_X3 || a->in_dtype == KEEP_BF16 || a->B <= 0 || a->H <= 0 || a->Lk <= 0) return 0;
-  const bool x3_ok = (a->D % 16 == 0) && (a->q_ts % 4 == 0) && (a->q_bs % 4 == 0) && (a->q_hs % 4 == 0) && (a->k_ts % 4 == 0) &&
-                     (a->k_bs % 4 == 0) && (a->k_hs % 4 == 0) && ((uintptr_t)a->q % 16 == 0) && ((uintptr_t)a->k % 16 == 0) &&
-                     !(a->flags & KEEP_ATTN_NO_X3);
-  if (!x3_ok) return 0;
+  keep_attention_args a;
   AttnP p;
-  p.B = a->B; p.H = a->H; p.Lq = a->Lq; p.Lk = a->Lk; p.D = a->D; p.Dv = a->Dv; p.flags = a->flags;
-  p.mode = a->mode; p.q_amax = a->q_amax; p.o = a->o; p.o_ts = a->o_ts; p.o_bs = a->o_bs; p.o_hs = a->o_hs;
-  if (attn_two_pass_ok(p)) return attn_two_pass_bytes(p);      // the score matrix between the two launches
-  return attn_pack_bytes(p, a->mma);
+  AttnPlan pl;
+  if (attn_args_in(a_in, a) != KEEP_OK || plan_attention(a, INT64_MAX, p, pl) != KEEP_OK) return 0;
+  return pl.scratch;
 }
 
 extern "C" int32_t keep_attention(const keep_attention_args* a_in, void* stream) {
-  keep_attention_args a_local;
-  const int rc_in = attn_args_in(a_in, a_local);
+  keep_attention_args a;
+  const int rc_in = attn_args_in(a_in, a);
   if (rc_in != KEEP_OK) return rc_in;
-  const keep_attention_args* a = &a_local;
-  KEEP_REQUIRE(a->q && a->k && a->v && a->o, "keep_attention: null tensor pointer");
-  KEEP_REQUIRE(a->B > 0 && a->H > 0 && a->Lq > 0 && a->Lk > 0 && a->D > 0 && a->Dv > 0, "keep_attention: bad dims");
-  KEEP_REQUIRE(a->D % 2 == 0 && (a->D <= 128 || a->D % 128 == 0), "keep_attention: D=%d must be even and (<= 128 or a multiple of 128)", a->D);
-  KEEP_REQUIRE(a->mode >= 0 && a->mode <= 2, "keep_attention: bad mode %d", a->mode);
-  KEEP_REQUIRE(a->mma == KEEP_MMA_F32 || a->mma == KEEP_MMA_BF16 || a->mma == KEEP_MMA_X3, "keep_attention: bad mma %d", a->mma);
-  if (a->mode == 1)
-    KEEP_REQUIRE(a->T > 0 && a->seg_len > 0 && a->Lk == 2 * a->seg_len && a->B % a->T == 0,
-                 "keep_attention: sparse-causal mode needs Lk == 2*seg_len and B %% T == 0");
-  if (a->mode == 2) {
-    KEEP_REQUIRE(a->ksplit > 0 && a->img_h % a->ksplit == 0 && a->img_w % a->ksplit == 0, "keep_attention: bad window split");
-    const int wh = a->img_h / a->ksplit, ww = a->img_w / a->ksplit;
-    KEEP_REQUIRE(a->Lq == wh * ww && a->Lk == wh * ww, "keep_attention: window mode needs Lq == Lk == window size");
-    KEEP_REQUIRE(a->n_img > 0 && a->B == a->n_img * a->ksplit * a->ksplit, "keep_attention: B != n_img*ksplit^2");
-    // the region mask (win_region / win_token) assumes a roll by half a window: shift is 0 or wh/2 (the kernels then roll the
-    // columns by ww/2, GM/transformer.py:75-80)
-    KEEP_REQUIRE(a->shift == 0 || a->shift == wh / 2, "keep_attention: shift=%d must be 0 or img_h/ksplit/2 = %d", a->shift, wh / 2);
-    KEEP_REQUIRE(a->kv_rot >= 0 && a->kv_rot < a->n_img, "keep_attention: bad kv_rot");
-    KEEP_REQUIRE((long)a->img_h * a->img_w <= 65536, "keep_attention: window mode supports maps of at most 65536 tokens");
-  }
+  KEEP_REQUIRE(a.q && a.k && a.v && a.o, "keep_attention: null tensor pointer");
   AttnP p;
-  p.flags = a->flags;
-  p.q = (const float*)a->q; p.k = (const float*)a->k; p.v = (const float*)a->v; p.o = a->o;
-  p.q16 = (const unsigned short*)a->q; p.k16 = (const unsigned short*)a->k; p.v16 = (const unsigned short*)a->v;
-  p.q_bs = a->q_bs; p.q_ts = a->q_ts; p.q_hs = a->q_hs;
-  p.k_bs = a->k_bs; p.k_ts = a->k_ts; p.k_hs = a->k_hs;
-  p.v_bs = a->v_bs; p.v_ts = a->v_ts; p.v_hs = a->v_hs;
-  p.o_bs = a->o_bs; p.o_ts = a->o_ts; p.o_hs = a->o_hs;
-  p.B = a->B; p.H = a->H; p.Lq = a->Lq; p.Lk = a->Lk; p.D = a->D; p.Dv = a->Dv;
-  p.scale = a->scale; p.mode = a->mode; p.T = a->T; p.seg_len = a->seg_len;
-  p.img_h = a->img_h; p.img_w = a->img_w; p.ksplit = a->ksplit; p.shift = a->shift; p.kv_rot = a->kv_rot;
-  p.n_img = a->n_img;
-  p.q_amax = a->q_amax; p.k_amax = a->k_amax; p.v_amax = a->v_amax;
-  p.kv_pack = nullptr;
-  KEEP_REQUIRE((!a->q_amax && !a->k_amax && !a->v_amax) || (a->q_amax && a->k_amax && a->v_amax && a->mode == 0 && a->mma == KEEP_MMA_X3),
-               "keep_attention: q/k/v_amax come together, with KEEP_MMA_X3 and mode 0 only");
+  AttnPlan pl;
+  const bool ws_ok = a.workspace && (uintptr_t)a.workspace % 16 == 0;
+  const int rc = plan_attention(a, ws_ok ? a.workspace_bytes : 0, p, pl);
+  if (rc != KEEP_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  // dv slice per block: 32 / 64 / 128 columns
-  const int dvt = a->Dv <= 32 ? 1 : (a->Dv <= 64 ? 2 : 4);
-  p.nslices = cdiv(a->Dv, dvt * 32);
-  if (a->in_dtype == KEEP_BF16) {
-    const bool ok = a->mma == KEEP_MMA_BF16 && (a->D % 16 == 0) && (a->Dv % 8 == 0) && (a->q_ts % 8 == 0) &&
-                    (a->q_bs % 8 == 0) && (a->q_hs % 8 == 0) && (a->k_ts % 8 == 0) && (a->k_bs % 8 == 0) &&
-                    (a->k_hs % 8 == 0) && (a->v_ts % 8 == 0) && (a->v_bs % 8 == 0) && (a->v_hs % 8 == 0) &&
-                    ((uintptr_t)a->q % 16 == 0) && ((uintptr_t)a->k % 16 == 0) && ((uintptr_t)a->v % 16 == 0);
-    KEEP_REQUIRE(ok, "keep_attention: bf16 inputs need KEEP_MMA_BF16, D %% 16 == 0, Dv %% 8 == 0 and 16-byte aligned rows");
-    if (dvt == 1) return launch_attn_bf16in<1>(p, st);
-    if (dvt == 2) return launch_attn_bf16in<2>(p, st);
-    return launch_attn_bf16in<4>(p, st);
+  const bool one_wave = pl.waves == 1;
+  switch (pl.form) {
+    case ATTN_F32:
+      return with_dvt(pl.dvt, [&](auto dvt) {
+        return one_wave ? launch_attn<1, decltype(dvt)::value>(p, pl, st) : launch_attn<4, decltype(dvt)::value>(p, pl, st);
+      });
+    case ATTN_BF16:
+      return with_dvt(pl.dvt, [&](auto dvt) {
+        return one_wave ? launch_attn_bf16<1, decltype(dvt)::value>(p, pl, st) : launch_attn_bf16<4, decltype(dvt)::value>(p, pl, st);
+      });
+    case ATTN_BF16IN:
+      return with_dvt(pl.dvt, [&](auto dvt) { return launch_attn_bf16in<decltype(dvt)::value>(p, pl, st); });
+    case ATTN_X3_NQ8:
+      return with_dvt(pl.dvt, [&](auto dvt) {
+        return one_wave ? launch_attn_x3_t<1, decltype(dvt)::value, 8>(p, pl, st) : launch_attn_x3_t<4, decltype(dvt)::value, 8>(p, pl, st);
+      });
+    case ATTN_X3_NQ16:
+      return with_dvt(pl.dvt, [&](auto dvt) { return launch_attn_x3_t<4, decltype(dvt)::value, 16>(p, pl, st); });
+    case ATTN_X3_NQ0:
+      return with_dvt(pl.dvt, [&](auto dvt) { return launch_attn_x3_t<4, decltype(dvt)::value, 0>(p, pl, st); });
+    case ATTN_X3_PACKED:
+      p.kv_pack = (const _Float16*)a.workspace;
+      return with_dvt(pl.dvt, [&](auto dvt) {
+        return p.D == 128 ? launch_attn_x3_packed<decltype(dvt)::value, 8>(p, pl, st) : launch_attn_x3_packed<decltype(dvt)::value, 16>(p, pl, st);
+      });
+    case ATTN_X3_SMALL:
+      return launch_attn_x3_small(p, st);
+    case ATTN_X3_TWO_PASS:
+      return launch_attn_x3_two_pass(p, (float*)a.workspace, st);
+    case ATTN_X3_SFULL:
+      return with_dvt(pl.dvt, [&](auto dvt) { return launch_attn_x3_sfull<decltype(dvt)::value>(p, pl, st); });
+    case ATTN_X3_SFULL2:
+      return launch_attn_x3_sfull2(p, pl, st);
   }
-  if (a->mma == KEEP_MMA_BF16) {
-    // bf16 operands: needs 16-byte-aligned fp32 rows and D a multiple of 16
-    const bool ok = (a->D % 16 == 0) && (a->q_ts % 4 == 0) && (a->q_bs % 4 == 0) && (a->q_hs % 4 == 0) &&
-                    (a->k_ts % 4 == 0) && (a->k_bs % 4 == 0) && (a->k_hs % 4 == 0) && ((uintptr_t)a->q % 16 == 0) &&
-                    ((uintptr_t)a->k % 16 == 0);
-    KEEP_REQUIRE(ok, "keep_attention: KEEP_MMA_BF16 needs D %% 16 == 0 and 16-byte aligned q/k rows");
-    if (a->Lq <= 32) {
-      if (dvt == 1) return launch_attn_bf16<1, 1>(p, st);
-      if (dvt == 2) return launch_attn_bf16<1, 2>(p, st);
-      return launch_attn_bf16<1, 4>(p, st);
-    }
-    if (dvt == 1) return launch_attn_bf16<4, 1>(p, st);
-    if (dvt == 2) return launch_attn_bf16<4, 2>(p, st);
-    return launch_attn_bf16<4, 4>(p, st);
-  }
-  // split fp16: fp32 tensors with 16-byte aligned rows, D a multiple of 16; everything else runs on the exact-f32 kernel
-  if (a->mma == KEEP_MMA_X3 && (a->D % 16 == 0) && (a->q_ts % 4 == 0) && (a->q_bs % 4 == 0) && (a->q_hs % 4 == 0) &&
-      (a->k_ts % 4 == 0) && (a->k_bs % 4 == 0) && (a->k_hs % 4 == 0) && ((uintptr_t)a->q % 16 == 0) &&
-      ((uintptr_t)a->k % 16 == 0) && !(a->flags & KEEP_ATTN_NO_X3)) {
-    if (attn_small_ok(p)) return launch_attn_x3_small(p, st);
-    if (attn_two_pass_ok(p) && a->workspace && a->workspace_bytes >= attn_two_pass_bytes(p) && (uintptr_t)a->workspace % 16 == 0)
-      return launch_attn_x3_two_pass(p, (float*)a->workspace, st);
-    if (a->Lq <= 32) {
-      if (dvt == 1) return launch_attn_x3<1, 1>(p, st);
-      if (dvt == 2) return launch_attn_x3<1, 2>(p, st);
-      return launch_attn_x3<1, 4>(p, st);
-    }
-    {
-      const long need = attn_pack_bytes(p, a->mma);
-      if (need > 0 && a->workspace && a->workspace_bytes >= need && (uintptr_t)a->workspace % 16 == 0) {
-        p.kv_pack = (const _Float16*)a->workspace;
-        if (a->D == 128) {
-          if (dvt == 1) return launch_attn_x3_packed<1, 8>(p, st);
-          if (dvt == 2) return launch_attn_x3_packed<2, 8>(p, st);
-          return launch_attn_x3_packed<4, 8>(p, st);
-        }
-        if (dvt == 1) return launch_attn_x3_packed<1, 16>(p, st);
-        if (dvt == 2) return launch_attn_x3_packed<2, 16>(p, st);
-        return launch_attn_x3_packed<4, 16>(p, st);
-      }
-    }
-    if (dvt == 1) return launch_attn_x3<4, 1>(p, st);
-    if (dvt == 2) return launch_attn_x3<4, 2>(p, st);
-    return launch_attn_x3<4, 4>(p, st);
-  }
-  // one wave per block for tiny query counts (temporal attention over T frames), else 4 (one per SIMD)
-  if (a->Lq <= 32) {
-    if (dvt == 1) return launch_attn<1, 1>(p, st);
-    if (dvt == 2) return launch_attn<1, 2>(p, st);
-    return launch_attn<1, 4>(p, st);
-  }
-  if (dvt == 1) return launch_attn<4, 1>(p, st);
-  if (dvt == 2) return launch_attn<4, 2>(p, st);
-  return launch_attn<4, 4>(p, st);
+  keep_set_error("keep_attention: no kernel form planned");
+  return KEEP_EINVAL;
 }
 
 // ------------------------------------------------------------------------------------------------ fused GMFlow FFN
@@ -2750,15 +2738,8 @@ template <int NT>
 static int launch_token_linear(const float* x, const void* w, const float* bias, void* out, long M, int out_bf16,
                                hipStream_t st) {
   const size_t lds = (size_t)(NT * 128 + 128) * (TL_K + 8) * 2;     // W + X tile (the output staging aliases the X tile)
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)token_linear_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      keep_set_error("keep_token_linear: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return KEEP_EHIP;
-    }
-    attr_set = true;
-  }
+  const int rc = keep_raise_lds_limit<token_linear_kernel<NT>>("keep_token_linear");
+  if (rc != KEEP_OK) return rc;
   static int n_cu = 0;
   if (n_cu == 0) {
     int dev = 0;

@@ -34,6 +34,22 @@ void keep_set_error(const char* fmt, ...);
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// Raises Kernel's dynamic LDS limit to the 160 KB of a gfx950 CU before its first launch: once per kernel instantiation and
+// process (one flag per instantiation of this template; idempotent, benign if raced).  `who` opens the error text.
+template <auto Kernel>
+static int keep_raise_lds_limit(const char* who) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) {
+      keep_set_error("%s: hipFuncSetAttribute failed: %s", who, hipGetErrorString(e));
+      return KEEP_EHIP;
+    }
+    attr_set = true;
+  }
+  return KEEP_OK;
+}
+
 __device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.f ? 0.f : v; }
 
 __device__ __forceinline__ float act_apply(float v, int act) {
