@@ -2277,6 +2277,7 @@ static int plan_attention(const keep_attention_args& a, int64_t scratch_avail, A
   KEEP_REQUIRE(a.B > 0 && a.H > 0 && a.Lq > 0 && a.Lk > 0 && a.D > 0 && a.Dv > 0, "keep_attention: bad dims");
   KEEP_REQUIRE(a.D % 2 == 0 && (a.D <= 128 || a.D % 128 == 0), "keep_attention: D=%d must be even and (<= 128 or a multiple of 128)", a.D);
   KEEP_REQUIRE(a.mode >= 0 && a.mode <= 2, "keep_attention: bad mode %d", a.mode);
+  KEEP_REQUIRE(a.mma != KEEP_MMA_X1, "keep_attention: KEEP_MMA_X1 has no attention kernel (a keep_conv2d policy of the parsing network)");
   KEEP_REQUIRE(a.mma == KEEP_MMA_F32 || a.mma == KEEP_MMA_BF16 || a.mma == KEEP_MMA_X3, "keep_attention: bad mma %d", a.mma);
   if (a.mode == 1)
     KEEP_REQUIRE(a.T > 0 && a.seg_len > 0 && a.Lk == 2 * a.seg_len && a.B % a.T == 0,

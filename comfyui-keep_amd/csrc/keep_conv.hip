@@ -1700,6 +1700,8 @@ int keep_conv2d_x3_c3(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
 bool keep_conv_x3_halo_ok(const keep_conv2d_args* a);
 bool keep_conv_x3_stream_ok(const keep_conv2d_args* a, const ConvP& p, int split_k);
 bool keep_conv_x3_gather_ok(const keep_conv2d_args* a, const ConvP& p);
+bool keep_conv_x1_stream_ok(const keep_conv2d_args* a, const ConvP& p);
+bool keep_conv_x1_gather_ok(const keep_conv2d_args* a, const ConvP& p);
 bool keep_gemm_x3l_ok(const keep_conv2d_args* a);
 int keep_gemm_x3l_waves(const keep_conv2d_args* a);
 int keep_conv2d_x3_gemm_lat(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
@@ -1768,7 +1770,7 @@ static int validate_conv(const keep_conv2d_args* a) {
     KEEP_REQUIRE((long)(a->Ho - 1) * a->stride - a->pad_t < Hv && (long)(a->Wo - 1) * a->stride - a->pad_l < Wv,
                  "keep_conv2d: output extent %dx%d inconsistent with input %dx%d", a->Ho, a->Wo, Hv, Wv);
   }
-  KEEP_REQUIRE(a->mma == KEEP_MMA_F32 || a->mma == KEEP_MMA_BF16 || a->mma == KEEP_MMA_X3, "keep_conv2d: bad mma %d", a->mma);
+  KEEP_REQUIRE(a->mma == KEEP_MMA_F32 || a->mma == KEEP_MMA_BF16 || a->mma == KEEP_MMA_X3 || a->mma == KEEP_MMA_X1, "keep_conv2d: bad mma %d", a->mma);
   KEEP_REQUIRE(a->upsample == 0 || a->upsample == 1 || (a->upsample == KEEP_UPSAMPLE_X2_PHASES && a->mma == KEEP_MMA_X3),
                "keep_conv2d: upsample must be 0, 1 or KEEP_UPSAMPLE_X2_PHASES (KEEP_MMA_X3 only), got %d", a->upsample);
   KEEP_REQUIRE(a->pad_mode == KEEP_PAD_ZERO || a->pad_mode == KEEP_PAD_REFLECT, "keep_conv2d: bad pad_mode %d", a->pad_mode);
@@ -1795,7 +1797,7 @@ static int plan_conv(const keep_conv2d_args* a, ConvP& p, ConvPlan& pl) {
   const long M_real = (long)a->N * a->Ho * a->Wo;
   // rows the HEURISTICS below see (tile, split-K): per-image rows x the fixed reference batch under the parity policies,
   // the real row count under the bf16 speed policy; launches and buffer sizes always use the real M (p.M)
-  const long M = a->mma == KEEP_MMA_BF16 ? M_real : plan_ref_images(a) * (long)a->Ho * a->Wo;
+  const long M = a->mma == KEEP_MMA_BF16 ? M_real : plan_ref_images(a) * (long)a->Ho * a->Wo;      // (KEEP_MMA_X1 plans like x3: batch-invariant)
   p.in = (const float*)a->in;
   p.w = a->weight;
   p.wb = (const unsigned short*)a->weight_bf16;
@@ -1828,7 +1830,7 @@ static int plan_conv(const keep_conv2d_args* a, ConvP& p, ConvPlan& pl) {
   p.nsteps = a->KH * a->KW * p.cchunks;
   p.in_bf16 = (a->dtype == KEEP_BF16) ? 1 : 0;
   // fast-math activations: bf16 policy always; x3 policy unless KEEP_X3_EXACT_ACT is set (forms of x3 grade, keep_common.h)
-  p.fast = (a->mma == KEEP_MMA_BF16 || (a->mma == KEEP_MMA_X3 && !(a->flags & KEEP_CONV_X3_EXACT_ACT))) ? 1 : 0;
+  p.fast = (a->mma == KEEP_MMA_BF16 || ((a->mma == KEEP_MMA_X3 || a->mma == KEEP_MMA_X1) && !(a->flags & KEEP_CONV_X3_EXACT_ACT))) ? 1 : 0;
   p.out_bf16 = (a->out_dtype == KEEP_BF16) ? 1 : 0;
   p.vec_ok = (a->Cin % 4 == 0 && a->in_ld % 4 == 0 && ((uintptr_t)a->in % 16 == 0)) ? 1 : 0;
   p.vec_epi = (a->Cout % 4 == 0 && a->out_ld % 4 == 0 && (uintptr_t)a->out % 16 == 0 &&
@@ -1872,6 +1874,40 @@ static int plan_conv(const keep_conv2d_args* a, ConvP& p, ConvPlan& pl) {
     pl.stats_rows = 64;
     snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_c3_kernel");
     return KEEP_OK;
+  }
+  // ---- single fp16 (ParseNet's opt-in speed policy): the x1 instantiations of the streaming halo kernel and of the im2col gather kernel,
+  // planned by the x3 rules; every other shape is refused -- there is no kernel of this grade for it and no silent change of policy
+  if (mma == KEEP_MMA_X1) {
+    KEEP_REQUIRE(a->dtype == KEEP_F32 && a->out_dtype != KEEP_BF16, "keep_conv2d: KEEP_MMA_X1 takes and writes fp32 tensors");
+    const bool have_w = a->weight_x3 != nullptr && (uintptr_t)a->weight_x3 % 16 == 0 && a->x3_acc_scale > 0.f;
+    if (have_w && is33s1 && keep_conv_x3_halo_ok(a) && keep_conv_x1_stream_ok(a, p) && a->split_k <= 1 && !(a->flags & KEEP_CONV_NO_HALO_X3)) {
+      pl.path = PATH_HALO_X3;
+      pl.split_k = 1;
+      pl.stats_rows = 256;
+      pl.amax_ok = true;
+      snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_x3s_kernel<0, false, true>");      // (the x1 instantiation, as rocprofv3 prints it)
+      return KEEP_OK;
+    }
+    if (have_w && !is33s1 && keep_conv_x1_gather_ok(a, p) && !(a->flags & KEEP_CONV_NO_GATHER_X3)) {
+      pl.path = PATH_GATHER_X3;
+      pl.tile = (a->Cout <= 64 || M <= small_m_threshold(a)) ? 1 : 2;
+      pl.plain = true;
+      const int steps = a->KH * a->KW * (a->Cin / 32);
+      const long blocks = pl.tile == 1 ? (long)cdiv(M, 64) * cdiv(a->Cout, 64) : (long)cdiv(M, 128) * cdiv(a->Cout, 128);
+      const long waves = blocks * 4;
+      auto_split = (waves >= kTargetWaves || steps < 8) ? 1 : (int)max(1L, min(min(4L * kTargetWaves / waves, (long)steps / 2), 32L));
+      pl.split_k = a->split_k > 0 ? a->split_k : auto_split;
+      if (pl.split_k > steps) pl.split_k = steps;
+      pl.stats_rows = pl.tile == 1 ? 64 : 128;
+      pl.amax_ok = pl.split_k == 1 && ((long)a->Ho * a->Wo) % (pl.tile == 1 ? 32 : 64) == 0;
+      // (the x1 instantiation; its trailing template booleans as 0 / 1: the name has 63 characters)
+      snprintf(pl.kernel, sizeof(pl.kernel), "conv_x3_kernel<%s, true, 0, 0, 1, 0, 1>", pl.tile == 1 ? "2, 2, 1, 1" : "2, 2, 2, 2");
+      return KEEP_OK;
+    }
+    keep_set_error("keep_conv2d: KEEP_MMA_X1 has no kernel for this call: it needs weight_x3 (the hi-only fp16 twin) and x3_acc_scale, Cin %% 32 == 0, no "
+                   "prologue / aux / in2 / LayerNorm, and either a 3x3 stride-1 pad-1 convolution on a map of 8 x 32 tiles without split-K or an "
+                   "im2col shape (a strided or non-3x3 convolution that is not a 1x1 GEMM)");
+    return KEEP_EUNSUP;
   }
   // ---- split fp16: halo / gather kernels where the geometry fits, the exact-f32 kernels otherwise (same parity grade)
   if (mma == KEEP_MMA_X3) {

@@ -693,8 +693,12 @@ __device__ __forceinline__ void x3_gather_epilogue(const ConvP& p, f32x16 (&acc)
 // DEEP: the 64 x 64 tile's register prefetch ring (below); the im2col form at large row counts runs without it (bit-neutral).
 // KAL: KSL with slices of exactly PD = 4 K steps (K = 512, 1024: every token GEMM of the code transformer) -- slice boundaries are compile-time
 // positions of the unrolled ring: the first MFMA of a slice takes the inline constant 0 as C, the fold is 16 adds, nothing is zeroed.
-template <int WGM, int WGN, int TM, int TN, bool PLAIN, bool ONE = false, bool KSL = false, bool DEEP = true, bool KAL = false>
+// X1 (KEEP_MMA_X1): operands rounded once to fp16, one MFMA per product -- no `lo` halves are computed, staged or read.  p.wx3 is
+// the hi-only twin, plain [Cout][KH*KW][Cin] fp16: the 64 bytes a cout row needs per K step are pieces 0 .. 3 of a thread row (the threads
+// of pieces 4 .. 7 fetch and stage nothing).  The im2col form without prologue only (ParseNet's stride-2 convolutions).
+template <int WGM, int WGN, int TM, int TN, bool PLAIN, bool ONE = false, bool KSL = false, bool DEEP = true, bool KAL = false, bool X1 = false>
 __global__ __launch_bounds__(256) void conv_x3_kernel(ConvP p) {
+  static_assert(!X1 || (PLAIN && !ONE && !KSL && !KAL), "the single-fp16 form: im2col, no prologue, no K slices");
   constexpr int BM = WGM * TM * 32;
   constexpr int BN = WGN * TN * 32;
   constexpr int A_IT = BM / 64;             // (row, 8-channel group) pieces per thread: 4 groups per row
@@ -752,9 +756,9 @@ __global__ __launch_bounds__(256) void conv_x3_kernel(ConvP p) {
       }
     }
   }
-  const long wrow_stride = (long)p.KH * p.KW * p.Cin * 2;     // fp16 elements per cout row
+  const long wrow_stride = (long)p.KH * p.KW * p.Cin * (X1 ? 1 : 2);     // fp16 elements per cout row
   // b piece -> LDS column: 16-channel chunk c = b_pc >> 2, part = b_pc & 3 (0,1: hi ch 0-7 / 8-15; 2,3: lo)
-  const int b_col = ((b_pc & 3) >> 1) * XBK + (b_pc >> 2) * 16 + (b_pc & 1) * 8;
+  const int b_col = X1 ? (b_pc & 3) * 8 : ((b_pc & 3) >> 1) * XBK + (b_pc >> 2) * 16 + (b_pc & 1) * 8;
 
   // the in-flight operands of one K step (registers)
   struct StepRegs {
@@ -791,12 +795,12 @@ __global__ __launch_bounds__(256) void conv_x3_kernel(ConvP p) {
     for (int it = 0; it < A_IT; ++it) a2_voff[it] = ((a_row0 + it * 64) * ld2 + a_grp * 8) * 4;
   }
   const __amdgpu_buffer_rsrc_t w_rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.wx3, 0, p.Cout * p.KH * p.KW * p.Cin * 4, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc((void*)p.wx3, 0, p.Cout * p.KH * p.KW * p.Cin * (X1 ? 2 : 4), 0x00020000);
   int b_voff[B_IT];
 #pragma unroll
   for (int it = 0; it < B_IT; ++it) {
     const int co = n0 + b_row0 + it * 32;
-    b_voff[it] = co < p.Cout ? (int)((long)co * wrow_stride * 2) + b_pc * 16 : (int)0x80000000;
+    b_voff[it] = (co < p.Cout && !(X1 && b_pc >= 4)) ? (int)((long)co * wrow_stride * 2) + b_pc * 16 : (int)0x80000000;
   }
 
   auto fetch = [&](int s, StepRegs& R) {
@@ -849,10 +853,10 @@ __global__ __launch_bounds__(256) void conv_x3_kernel(ConvP p) {
         }
       }
     }
-    const bool cb_ok = c0 + (b_pc >> 2) * 16 < p.Cin;
+    const bool cb_ok = X1 ? c0 + (b_pc & 3) * 8 < p.Cin : c0 + (b_pc >> 2) * 16 < p.Cin;
 #pragma unroll
     for (int it = 0; it < B_IT; ++it) {
-      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, cb_ok ? b_voff[it] : (int)0x80000000, (tap * p.Cin + c0) * 4, 0);
+      const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, cb_ok ? b_voff[it] : (int)0x80000000, (tap * p.Cin + c0) * (X1 ? 2 : 4), 0);
       R.b_raw[it] = make_uint4(v.x, v.y, v.z, v.w);
     }
   };
@@ -884,9 +888,11 @@ __global__ __launch_bounds__(256) void conv_x3_kernel(ConvP p) {
         for (int j = 0; j < 8; j += 2) {      // two values per instruction: v_pk_mul, v_cvt_pk_f16_f32, v_pk_add (VALU is paid in full: coissue_probe)
           const f32x2 vs = f32x2{v[j], v[j + 1]} * a_s[it];
           const f16x2 h = __builtin_convertvector(vs, f16x2);
-          const f16x2 l = __builtin_convertvector(vs - __builtin_convertvector(h, f32x2), f16x2);
           hi[j] = h.x; hi[j + 1] = h.y;
-          lo[j] = l.x; lo[j + 1] = l.y;
+          if constexpr (!X1) {
+            const f16x2 l = __builtin_convertvector(vs - __builtin_convertvector(h, f32x2), f16x2);
+            lo[j] = l.x; lo[j + 1] = l.y;
+          }
         }
       } else {
 #pragma unroll
@@ -894,8 +900,9 @@ __global__ __launch_bounds__(256) void conv_x3_kernel(ConvP p) {
       }
       _Float16* dst = &As[buf][(a_row0 + it * 64) * XP + a_grp * 8];
       *reinterpret_cast<f16x8*>(dst) = hi;
-      *reinterpret_cast<f16x8*>(dst + XBK) = lo;
+      if constexpr (!X1) *reinterpret_cast<f16x8*>(dst + XBK) = lo;
     }
+    if (X1 && b_pc >= 4) return;
 #pragma unroll
     for (int it = 0; it < B_IT; ++it)
       *reinterpret_cast<uint4*>(&Bs[buf][(b_row0 + it * 32) * XP + b_col]) = R.b_raw[it];
@@ -923,18 +930,20 @@ __global__ __launch_bounds__(256) void conv_x3_kernel(ConvP p) {
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         ah[i] = *reinterpret_cast<const f16x8*>(Ab + a_f0 + i * 32 * XP + ks * 16);
-        al[i] = *reinterpret_cast<const f16x8*>(Ab + a_f0 + i * 32 * XP + ks * 16 + XBK);
+        if constexpr (!X1) al[i] = *reinterpret_cast<const f16x8*>(Ab + a_f0 + i * 32 * XP + ks * 16 + XBK);
       }
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         bh[j] = *reinterpret_cast<const f16x8*>(Bb + b_f0 + j * 32 * XP + ks * 16);
-        bl[j] = *reinterpret_cast<const f16x8*>(Bb + b_f0 + j * 32 * XP + ks * 16 + XBK);
+        if constexpr (!X1) bl[j] = *reinterpret_cast<const f16x8*>(Bb + b_f0 + j * 32 * XP + ks * 16 + XBK);
       }
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-          if (KAL && zc && ks == 0) {
+          if constexpr (X1) {
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+          } else if (KAL && zc && ks == 0) {
             const f32x16 z16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], z16, 0, 0, 0);
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
@@ -1330,6 +1339,12 @@ bool keep_conv_x3_gather_is_gemm(const keep_conv2d_args* a) {
          (long)a->in_ld * 4 * 128 < (1L << 30);
 }
 
+// KEEP_MMA_X1: the im2col form without prologue, whole 32-channel K steps (ParseNet's stride-2 convolutions)
+bool keep_conv_x1_gather_ok(const keep_conv2d_args* a, const ConvP& p) {
+  return keep_conv_x3_gather_ok(a, p) && !keep_conv_x3_gather_is_gemm(a) && !a->pro_scale && a->pro_act == KEEP_PRO_NONE && !a->in2 &&
+         !a->ln_gamma && a->Cin % 32 == 0;
+}
+
 bool keep_conv_x3p_ok(const keep_conv2d_args* a, const ConvP& p, int split_k);
 bool keep_conv_x3q_ok(const keep_conv2d_args* a, const ConvP& p, int split_k);
 bool keep_conv_x3p_full_ok(const keep_conv2d_args* a, const ConvP& p, int split_k);
@@ -1350,6 +1365,7 @@ int keep_conv2d_x3_halo(const keep_conv2d_args* a, ConvP& p, hipStream_t st) {
     KEEP_LAUNCH_CHECK("keep_conv2d(halo x3, x2 phases)");
     return KEEP_OK;
   }
+  if (a->mma == KEEP_MMA_X1) return keep_conv2d_x3_stream(a, p, x3_num_cu(), st);      // (plan_conv: keep_conv_x1_stream_ok, split_k == 1)
   const int nchunks = a->Cin / 16;
   if (p.split_k > nchunks) p.split_k = nchunks;
   if (keep_conv_x3p_ok(a, p, p.split_k)) return keep_conv2d_x3_partials(a, p, st);                        // keep_conv_x3p.hip (few images: 64-pixel tiles, same partials)
@@ -1474,7 +1490,9 @@ int keep_conv2d_x3_gather(const keep_conv2d_args* a, ConvP& p, int tile, hipStre
   // 1x1 stride-1 unpadded convolutions (token GEMMs): block-relative buffer-load fetch, no im2col index arithmetic
   const bool one = keep_conv_x3_gather_is_gemm(a);
 #define KEEP_LAUNCH_GX(A, B, C, D)                                                                 \
-  if (p.kslice_steps == 4 && plain && C * D == 1 && steps % 4 == 0)                                \
+  if (a->mma == KEEP_MMA_X1)      /* (keep_conv_x1_gather_ok: plain im2col form) */                \
+    hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, true, false, false, true, false, true>), grid, block, 0, st, p); \
+  else if (p.kslice_steps == 4 && plain && C * D == 1 && steps % 4 == 0)                                \
     hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, true, true, true, true, C * D == 1>), grid, block, 0, st, p); \
   else if (p.kslice_steps > 0 && plain)                                                            \
     hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, true, true, true>), grid, block, 0, st, p);     \

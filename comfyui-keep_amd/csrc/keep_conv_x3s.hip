@@ -53,9 +53,20 @@ __device__ __forceinline__ float xs_xor32_sum(float x) {
 }
 
 // Phase ablations of this kernel and the s_memtime timeline of wave 0: DESIGN 5.3 (a) / (b).
-template <int PRO, bool AFF>
+// X1 (KEEP_MMA_X1, DESIGN 4: ParseNet's opt-in single-fp16 policy): the same pipeline with the two low-term products removed at compile
+// time -- operands rounded ONCE to fp16, 36 MFMAs per chunk (a_hi*b_hi over the four accumulators), no `lo` conversion, no `lo` rows
+// written to or read from LDS.  Weights: p.wx3 is the hi-only twin, plain [Cout][9][Cin] fp16 (engine/ops.py:make_x1_blob), so the
+// 64 bytes of a weight row in LDS hold TWO chunks -- one LDS-DMA round (the x3 form's addresses and swizzle) serves chunks 2c and
+// 2c + 1, the B fragments of the odd chunk sit where the x3 form keeps `lo` (Cin % 32 == 0: host).  The conversion of a piece shrinks
+// to four gap steps (scale 2 + 2, convert, ds_write_b64) placed in the first four of the SIX gaps a piece owns (36 gaps / 6 pieces); the
+// fragments of tap t + 1 are read into a second register set during tap t (a single set would leave two gaps between a read and its use).
+// The requests of a step fall into gaps 1, 7, .., 31: two of them precede the first ring barrier (gap 11) and two follow the second
+// DMA group (gap 23), so the counted vmcnt waits of the x3 schedule hold unchanged.  Raw inputs without prologue only.
+template <int PRO, bool AFF, bool X1 = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int tiles_x, int tiles_y, int ncb, int n_items) {
   static_assert(AFF || PRO == KEEP_PRO_NONE, "an activation prologue comes with its GroupNorm affine");
+  static_assert(!X1 || (!AFF && PRO == KEEP_PRO_NONE), "the single-fp16 form takes raw inputs only");
+  constexpr int WB = X1 ? 2 : 4;               // bytes per weight of p.wx3
   __shared__ __attribute__((aligned(16))) unsigned char lds_raw[XS_LDS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lhi = lane >> 5, g = tid & 3;
   const int nch = p.Cin >> 4;                  // chunks per item (>= 2: host)
@@ -68,7 +79,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
     return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, bytes, 0x00020000);
   };
   const __amdgpu_buffer_rsrc_t null_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, 0, 0x00020000);   // every offset out of range: zeros, no traffic
-  const __amdgpu_buffer_rsrc_t w_rsrc = make_rsrc(p.wx3, p.Cout * 9 * p.Cin * 4);
+  const __amdgpu_buffer_rsrc_t w_rsrc = make_rsrc(p.wx3, p.Cout * 9 * p.Cin * WB);
   const __amdgpu_buffer_rsrc_t sc_rsrc = AFF ? make_rsrc(p.pro_scale, p.N * p.Cin * 4) : null_rsrc;
   const __amdgpu_buffer_rsrc_t sh_rsrc = AFF ? make_rsrc(p.pro_shift, p.N * p.Cin * 4) : null_rsrc;
 
@@ -132,7 +143,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int co = itF.n0 + ((j - wave) & 3) * 16 + (lane >> 2);
-      dma_voff[j] = co < p.Cout ? co * 9 * p.Cin * 4 + lp * 16 : -16;
+      dma_voff[j] = co < p.Cout ? co * 9 * p.Cin * WB + lp * 16 : -16;
     }
     in_sC = 1.f;
     in_invC = 1.f;
@@ -164,6 +175,23 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
   // the raw registers are dead from there on.  Zero padding applies to the normalised + activated tensor: under the swish the exp2
   // argument of a padding piece gets +1e30 (exp2 -> inf, rcp -> 0, y * 0 = 0) -- no select instructions.
   auto conv_step = [&](int q, int hb) __attribute__((always_inline)) {
+    if constexpr (X1) {                        // piece k = q / 6, steps 0 .. 3 of its six gaps
+      const int k = q / 6, st = q % 6;
+      const float rs = p.in_amax ? in_sC : 1.f;
+      if (st == 0) { cv[0] = hreg[k].x * rs; cv[1] = hreg[k].y * rs; }
+      if (st == 1) {
+        cv[2] = hreg[k].z * rs; cv[3] = hreg[k].w * rs;
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(okF ? in_rsrc : null_rsrc, h_voff[k], chF * 64, KEEP_LD_AUX_XS);
+        hreg[k] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+      }
+      if (st == 2) {
+        chi[0] = __builtin_convertvector(f32x2{cv[0], cv[1]}, f16x2);
+        chi[1] = __builtin_convertvector(f32x2{cv[2], cv[3]}, f16x2);
+      }
+      if (st == 3)
+        *reinterpret_cast<uint2*>(lds_raw + wr_addr[k] + hb) = make_uint2(__builtin_bit_cast(unsigned, chi[0]), __builtin_bit_cast(unsigned, chi[1]));
+      return;
+    }
     constexpr bool SW = PRO == KEEP_PRO_SWISH, RL = PRO == KEEP_PRO_RELU;
     const int k = q / 18, st = q % 18;
     const float rs = (PRO == KEEP_PRO_NONE && p.in_amax) ? in_sC : 1.f;
@@ -228,7 +256,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
     for (int u = 0; u < 3; ++u) {
       const int q = 12 * gq + w3 + u;
       __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (__attribute__((address_space(3))) void*)(lds_raw + XS_WOFF + q * 1024), 16, dma_voff[u],
-                                               ((q >> 2) * p.Cin + chC * 16) * 4, 0, 0);
+                                               X1 ? (q >> 2) * p.Cin * 2 + (chC >> 1) * 64 : ((q >> 2) * p.Cin + chC * 16) * 4, 0, 0);
     }
   };
   // fragments of one tap: 0 a_lo0, 1 a_lo1, 2 b_hi0, 3 b_hi1, 4 a_hi0, 5 a_hi1, 6 b_lo0, 7 b_lo1
@@ -245,6 +273,44 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
   };
   // MFMAs of the chunk in halo buffer hbM + everything that rides in their shadow (chunk C -> halo buffer hbC, request of chunk F)
   auto mma_step = [&](int hbM, int hbC) __attribute__((always_inline)) {
+    if constexpr (X1) {
+      const int rd_bM = rd_b ^ ((chM & 1) << 5);        // the chunk's half of the two-chunk weight rows
+      auto frag1 = [&](int t, int f) __attribute__((always_inline)) -> f16x8 {      // 0 a0, 1 a1, 2 b0, 3 b1 of tap t
+        const int kh = t / 3, kw = t - kh * 3;
+        if (f < 2) return *reinterpret_cast<const f16x8*>(lds_raw + rd_a[kw] + hbM + ((f + kh) * XS_HW) * 64);
+        return *reinterpret_cast<const f16x8*>(lds_raw + rd_bM + (t * 64 + (f - 2) * 32) * 64);
+      };
+      f16x8 fr[2][4];
+#pragma unroll
+      for (int f = 0; f < 4; ++f) fr[0][f] = frag1(0, f);
+#pragma unroll
+      for (int t = 0; t < 9; ++t) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+          const int i = m >> 1, j = m & 1;
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fr[t & 1][i], fr[t & 1][2 + j], acc[i][j], 0, 0, 0);
+          if (t < 8) fr[(t + 1) & 1][m] = frag1(t + 1, m);
+          conv_step(t * 4 + m, hbC);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if (t == 2) {          // the weight ring and its counted waits: see the x3 loop below (two requests, gaps 1 and 7, are younger than taps 6-8)
+          if (after_epi) {
+            asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
+          } else {
+            asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+          }
+          asm volatile("s_barrier" ::: "memory");
+          if (okC && !(chC & 1)) dma_group(0);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        if (t == 5) {
+          asm volatile("s_barrier" ::: "memory");
+          if (okC && !(chC & 1)) dma_group(1);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      return;
+    }
     constexpr int NCONV = 18 * HALO_IT;        // 108 conversion steps: one per MFMA gap
     f16x8 fr[8];
 #pragma unroll
@@ -416,7 +482,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
 #pragma unroll
   for (int k = 0; k < HALO_IT; ++k) {
 #pragma unroll
-    for (int st = 0; st < 18; ++st) conv_step(k * 18 + st, 0);
+    for (int st = 0; st < (X1 ? 6 : 18); ++st) conv_step(k * (X1 ? 6 : 18) + st, 0);
   }
   itM = itC;
   chM = 0;
@@ -453,7 +519,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
       asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
     }
     asm volatile("s_barrier" ::: "memory");              // every wave is done with halo buffer HB and weight taps 6-8; the other buffer and the next taps 0-5 are complete
-    if (okC) dma_group(2);
+    if (okC && (!X1 || !(chC & 1))) dma_group(2);
     if (last) {
       const float amx = p.res ? epilogue_t(HB, std::true_type{}) : epilogue_t(HB, std::false_type{});
       if (p.out_amax) {     // max|out| of the image: a wave goes to memory only above everything it has committed or seen for this image
@@ -590,12 +656,19 @@ bool keep_conv_x3_stream_ok(const keep_conv2d_args* a, const ConvP& p, int split
          (long)a->N * a->Cin * 4 < (1L << 31);
 }
 
+// KEEP_MMA_X1: what the single-fp16 form of the streaming kernel takes inside keep_conv_x3_stream_ok -- no prologue, whole two-chunk weight rows
+bool keep_conv_x1_stream_ok(const keep_conv2d_args* a, const ConvP& p) {
+  return keep_conv_x3_stream_ok(a, p, 1) && !a->pro_scale && a->pro_act == KEEP_PRO_NONE && a->Cin % 32 == 0 && a->upsample != KEEP_UPSAMPLE_X2_PHASES;
+}
+
 int keep_conv2d_x3_stream(const keep_conv2d_args* a, ConvP& p, int n_cu, hipStream_t st) {
   const int tiles_x = a->Wo / 32, tiles_y = a->Ho / 8, ncb = (a->Cout + 63) / 64;
   const int n_items = a->N * tiles_x * tiles_y * ncb;
   dim3 grid(n_items < 2 * n_cu ? n_items : 2 * n_cu), block(256);
   const bool aff = a->pro_scale != nullptr;
-  if (a->pro_act == KEEP_PRO_SWISH)
+  if (a->mma == KEEP_MMA_X1)      // (keep_conv_x1_stream_ok: raw inputs, Cin % 32 == 0)
+    hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_NONE, false, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
+  else if (a->pro_act == KEEP_PRO_SWISH)
     hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_SWISH, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
   else if (a->pro_act == KEEP_PRO_RELU)
     hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_RELU, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);

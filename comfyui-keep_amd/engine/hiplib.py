@@ -12,10 +12,10 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('KEEP_HIP_LIB') or os.path.join(os.path.dirname(_HERE), 'csrc', 'libkeep_hip.so')   # (KEEP_HIP_LIB: dev A/B builds)
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 F32, BF16 = 0, 1
-MMA_F32, MMA_BF16, MMA_X3 = 0, 1, 2
+MMA_F32, MMA_BF16, MMA_X3, MMA_X1 = 0, 1, 2, 3
 PRO_NONE, PRO_SWISH, PRO_RELU = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_LRELU02, ACT_GELU, ACT_SIGMOID, ACT_LRELU01, ACT_SILU = 0, 1, 2, 3, 4, 5, 6
 PAD_ZERO, PAD_REFLECT = 0, 1

@@ -77,7 +77,8 @@ def offset(t, off):
 class Ops:
     def __init__(self):
         # matrix-core operand precision of keep_conv2d / keep_attention launches:
-        #   L.MMA_F32 exact f32 (parity), L.MMA_X3 split fp16 x 3 (parity-grade fast policy), L.MMA_BF16 (speed policy)
+        #   L.MMA_F32 exact f32 (parity), L.MMA_X3 split fp16 x 3 (parity-grade fast policy), L.MMA_BF16 (speed policy),
+        #   L.MMA_X1 single fp16 (ParseNet's opt-in speed policy: keep_conv2d only, `blobx3` is then the hi-only twin of make_x1_blob)
         self.mma = L.MMA_F32
         self.attn_mma = L.MMA_F32
         self.blob32 = None      # packed fp32 weight blob the twins below are resolved against (same element offsets)
@@ -119,7 +120,10 @@ class Ops:
 
     def set_precision(self, mma, blob32=None, blob16=None, blobx3=None, x3_acc_scale=1.0, x3_scales=None):
         """x3_scales: per-tensor accumulator scales of the split-fp16 twin, [(first element, one past the last, 2^-e), ...] sorted
-        by offset (``make_x3_blob``); without it every tensor of the blob carries ``x3_acc_scale``."""
+        by offset (``make_x3_blob``); without it every tensor of the blob carries ``x3_acc_scale``.  ``mma = L.MMA_X1``: ``blobx3`` is
+        the hi-only twin of ``make_x1_blob`` (one fp16 per weight), same scale table."""
+        if mma not in (L.MMA_F32, L.MMA_BF16, L.MMA_X3, L.MMA_X1):
+            raise ValueError(f"set_precision: unknown matrix-core policy {mma!r}")
         self._x3_table = None
         if x3_scales:
             self._x3_table = ([a for a, _, _ in x3_scales], list(x3_scales))
@@ -193,9 +197,11 @@ class Ops:
     def x3_twin(self, w):
         """split-fp16 copy of an fp32 weight view (row slices of a [Cout, .., Cin] tensor keep their layout), or None
         when the policy has no x3 blob / the tensor's Cin is not a multiple of 16 (such layers run on the f32 kernels)."""
-        if self.blobx3 is None or w.shape[-1] % 16:
+        if self.blobx3 is None or w.shape[-1] % (32 if self.mma == L.MMA_X1 else 16):
             return None
         off = self._blob_off(w)
+        if self.mma == L.MMA_X1:      # hi-only twin: one fp16 per weight, the packed tensor's own element order
+            return self.blobx3[off:off + w.numel()]
         return self.blobx3[2 * off:2 * (off + w.numel())]
 
     def x3_scale_of(self, w):
@@ -256,8 +262,10 @@ class Ops:
             # nearest x2 + 3x3 as four 2x2-tap phase convolutions on the source grid: 4 of 9 taps are multiplied
             wx3, x3_acc_scale = self.up2_twin(w)
             up_mode = L.UPSAMPLE_X2_PHASES
-        if mma == L.MMA_X3 and wx3 is None:
-            wx3 = self.x3_twin(w)
+        if mma in (L.MMA_X3, L.MMA_X1) and wx3 is None:
+            wx3 = None if {mma, self.mma} == {L.MMA_X3, L.MMA_X1} else self.x3_twin(w)      # (the twin's layout is the Ops policy's)
+            if mma == L.MMA_X1 and wx3 is None:                     # no x1 kernel reads fp32 weights: such a layer (ParseNet's RGB convolution) runs exact f32
+                mma = L.MMA_F32
             if wx3 is not None and x3_acc_scale is None:
                 x3_acc_scale = self.x3_scale_of(w)
         if x3_acc_scale is None:
@@ -265,7 +273,7 @@ class Ops:
         want_bf16_out = bool(out_bf16) and mma == L.MMA_BF16 and residual is None
         xin = x if in_off == 0 else x.view(-1)[in_off:]
         in_amax = None
-        if mma == L.MMA_X3 and (wx3 is not None or (Cin <= 3 and KH == 3)) and pro is None and not bounded:   # (RGB convs split fp32 weights in-kernel)
+        if ((mma == L.MMA_X3 and (wx3 is not None or (Cin <= 3 and KH == 3))) or mma == L.MMA_X1) and pro is None and not bounded:   # (RGB convs split fp32 weights in-kernel)
             in_amax = x_amax if (x_amax is not None and x_amax.numel() == N) else absmax(xin, N, H * W, Cin, ld, H * W * ld, self)
         out_ld = (Cout if out is None else out.shape[-1]) if out_ld is None else out_ld
 
@@ -277,7 +285,7 @@ class Ops:
                 in_ld=ld, out_ld=out_ld, res_ld=0 if residual is None else residual.shape[-1],
                 upsample=up_mode, pro_act=pro_a, epi_act=act, aux_w=float(aux_w), split_k=sk, dtype=dtype,
                 mma=mma, weight_bf16=wb if mma == L.MMA_BF16 else None, stats_out=None, stats_P=0,
-                bk256=int(USE_BK256), out_dtype=odt, weight_x3=wx3 if mma == L.MMA_X3 else None,
+                bk256=int(USE_BK256), out_dtype=odt, weight_x3=wx3 if mma in (L.MMA_X3, L.MMA_X1) else None,
                 x3_acc_scale=float(x3_acc_scale), x3_in_amax=in_amax, x3_out_amax=None,
                 in2=x2, in2_cin1=0 if x2 is None else ld, pad_mode=L.PAD_REFLECT if reflect else L.PAD_ZERO,
                 ln_gamma=None if ln is None else ln[0], ln_beta=None if ln is None else ln[1],
@@ -613,6 +621,23 @@ def make_x3_blob(dev_blob, index, weights, names):
         t = weights[n]
         sc = x3_scale_for(float(t.abs().max()))
         bx[2 * off:2 * (off + t.numel())] = split_x3(t.reshape(-1, shape[-1]), sc).view(-1)
+        table.append((int(off), int(off + t.numel()), 1.0 / sc))
+    table.sort()
+    return bx, table
+
+
+def make_x1_blob(dev_blob, index, weights, names):
+    """Hi-only fp16 twin of the tensors ``names`` for ``L.MMA_X1``: element i of the int16 result is the fp16 bit pattern of
+    fp16(blob[i] * scale) -- ONE element per weight at the fp32 blob's own offsets, so a packed [Cout,KH,KW,Cin] tensor keeps its
+    element order (the `weight_x3` layout of KEEP_MMA_X1, include/keep_hip.h) -- with ``make_x3_blob``'s power-of-two scale per
+    tensor and the same (first element, one past the last, 2^-e) table."""
+    bx = torch.zeros(dev_blob.numel(), dtype=torch.int16, device=dev_blob.device)
+    table = []
+    for n in names:
+        off, shape = index[n]
+        t = weights[n]
+        sc = x3_scale_for(float(t.abs().max()))
+        bx[off:off + t.numel()] = (t.reshape(-1).float() * sc).to(torch.float16).view(torch.int16)
         table.append((int(off), int(off + t.numel()), 1.0 / sc))
     table.sort()
     return bx, table

@@ -28,6 +28,15 @@ from .weights import pack_blob, views
 
 BN_EPS = 1e-5          # nn.BatchNorm2d default (parsenet.py:22)
 PARSING_CH = 19
+# matrix-core policies of the engine: 'x3' split fp16 (fp32-grade, the default), 'fp32' exact f32, 'f16' operands rounded once to fp16
+# (KEEP_MMA_X1: an opt-in speed mode OUTSIDE bit-parity with the default, like the KEEP network's bf16 -- DESIGN 4)
+PRECISIONS = ('x3', 'fp32', 'f16')
+
+
+def check_precision(precision):
+    if precision not in PRECISIONS:
+        raise ValueError(f"ParseNet precision must be one of {PRECISIONS}, got {precision!r}")
+    return precision
 
 
 def parsenet_spec(in_size=512, out_size=512, min_feat_size=32, base_ch=64, parsing_ch=PARSING_CH, res_depth=10, ch_range=(32, 256)):
@@ -125,7 +134,7 @@ class ParseNetEngine:
             for c in ('conv1', 'conv2'):
                 put(f'{name}.{c}', *_fold_bn(sd[f'{name}.{c}.conv2d.weight'], sd, f'{name}.{c}'))
         self._blob, self._index = pack_blob(t)
-        self.precision = precision
+        self.precision = check_precision(precision)
         self.device = torch.device('cpu')
         self.w = None
         self.o = ops.Ops()
@@ -141,7 +150,7 @@ class ParseNetEngine:
         self.in_size, self.out_size = in_size, out_size
         self.blocks = parsenet_spec(in_size=in_size, out_size=out_size)
         self._blob, self._index = np.ascontiguousarray(blob), index
-        self.precision = precision
+        self.precision = check_precision(precision)
         self.device = torch.device('cpu')
         self.w = None
         self.o = ops.Ops()
@@ -164,7 +173,15 @@ class ParseNetEngine:
             names = [n for n, (_, sh) in self._index.items() if len(sh) == 4 and sh[-1] % 16 == 0]
             bx, table = ops.make_x3_blob(self._dev, self._index, self.w, names)       # one power-of-two scale per tensor
             self.o.set_precision(L.MMA_X3, self._dev, None, bx, 1.0, x3_scales=table)
+        elif self.precision == 'f16':
+            # hi-only twin of every layer the x1 kernels take (Cin % 32 == 0: all but the 3 -> 64 convolution, which stays exact f32 as
+            # under 'x3').  Range: every input carries its producer's max |x| (x3_in_amax), so no operand can leave the fp16 range --
+            # a non-finite INPUT propagates to the logits exactly as under 'x3' (no re-run: ParseNet has none on either policy)
+            names = [n for n, (_, sh) in self._index.items() if len(sh) == 4 and sh[-1] % 32 == 0]
+            bx, table = ops.make_x1_blob(self._dev, self._index, self.w, names)
+            self.o.set_precision(L.MMA_X1, self._dev, None, bx, 1.0, x3_scales=table)
         else:
+            check_precision(self.precision)
             self.o.set_precision(L.MMA_F32, self._dev, None)
         return self
 

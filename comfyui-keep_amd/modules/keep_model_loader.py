@@ -72,6 +72,16 @@ class KEEPModelPack:
         model_management.soft_empty_cache()
 
 
+def parse_precision_knob(environ=None):
+    """KEEP_AMD_PARSE_PRECISION=x3|fp32|f16 (default x3): the matrix-core policy of the face-parsing network, read ONCE when the
+    pack's helper is built.  'f16' is the opt-in single-fp16 speed mode, outside bit-parity with the default."""
+    from ..engine.parsenet import PRECISIONS
+    value = (os.environ if environ is None else environ).get('KEEP_AMD_PARSE_PRECISION', '') or 'x3'
+    if value not in PRECISIONS:
+        raise ValueError(f"KEEP_AMD_PARSE_PRECISION must be one of {', '.join(PRECISIONS)}; got {value!r}")
+    return value
+
+
 def engine_facelib(helper):
     """put the helper's face-analysis networks on the HIP engine where an engine counterpart exists -- the
     objects keep the reference's call signatures (``face_parse(x)[0]``, ``face_detector.detect_faces(img)``), so
@@ -81,8 +91,8 @@ def engine_facelib(helper):
     fp = getattr(helper, 'face_parse', None)
     if fp is not None and hasattr(fp, 'state_dict') and 'out_mask_conv.conv2d.weight' in fp.state_dict():
         from ..engine.parsenet import EngineFaceParse
-        helper.face_parse = EngineFaceParse.from_module(fp)
-        logger.debug("face_parse (ParseNet) runs on the HIP engine")
+        helper.face_parse = EngineFaceParse.from_module(fp, precision=parse_precision_knob())
+        logger.debug("face_parse (ParseNet) runs on the HIP engine, precision %s", helper.face_parse.engine.precision)
     det = getattr(helper, 'face_detector', None)
     if det is not None and hasattr(det, 'state_dict') and getattr(det, 'backbone', None) in ('Resnet50', 'mobilenet0.25'):
         from ..engine.retinaface import EngineRetinaFace

@@ -30,8 +30,8 @@ extern "C" {
  * the fields a shorter known layout lacks as zero), keep_sizeof_*_args(), keep_argmax_gather takes the non-finite status word,
  * keep_nonfinite_flag.  v13: keep_conv2d_args.upsample accepts KEEP_UPSAMPLE_X2_PHASES (same layout; a v12 library refuses the
  * value, so the binding asks for 13).  v18: the two reserved words of keep_conv2d_args become `flags` / `plan_ref_images`, the one of
- * keep_attention_args `flags` (same layout and sizes; zero keeps the v17 behaviour) -- the library no longer reads ANY environment variable.  v19: keep_yolo_letterbox_u8, keep_yolo_select, keep_layernorm_amax, keep_geglu_amax, keep_retina_nms_ordered (additions only).  v21: keep_lanczos4_tables, keep_resize_lanczos4_u8 (additions only). */
-#define KEEP_ABI_VERSION 21
+ * keep_attention_args `flags` (same layout and sizes; zero keeps the v17 behaviour) -- the library no longer reads ANY environment variable.  v19: keep_yolo_letterbox_u8, keep_yolo_select, keep_layernorm_amax, keep_geglu_amax, keep_retina_nms_ordered (additions only).  v21: keep_lanczos4_tables, keep_resize_lanczos4_u8 (additions only).  v22: KEEP_MMA_X1 accepted by keep_conv2d (a new value of `mma`; same layouts and sizes, every v21 call means what it meant). */
+#define KEEP_ABI_VERSION 22
 #define KEEP_OK 0
 #define KEEP_EINVAL (-1)
 #define KEEP_EUNSUP (-2)
@@ -54,6 +54,16 @@ extern "C" {
  *                 cover run on the exact-f32 kernels.  An activation beyond the fp16 range (65504) yields inf, never a
  *                 silently wrong value. */
 #define KEEP_MMA_X3 2
+/*   KEEP_MMA_X1   v_mfma_f32_32x32x16_f16 x 1 (v22): KEEP_MMA_X3 with the two low-term products dropped -- every operand is multiplied by the
+ *                 same power-of-two range scale and rounded ONCE to fp16 (<= 2^-11 relative each, ~2^-10 per product), fp32 accumulation,
+ *                 the x3 epilogues (bias, activation, residual, statistics, x3_out_amax) and x3_in_amax unchanged.  An opt-in SPEED policy
+ *                 outside the parity tolerance, built for the face-parsing network whose consumer is an arg-max (engine/parsenet.py,
+ *                 precision 'f16').  `weight_x3` is then the hi-only twin: fp16(weight * 2^e) as plain [Cout][KH*KW][Cin] fp16, 16-byte
+ *                 aligned, Cin %% 32 == 0; x3_acc_scale = 2^-e.  keep_conv2d only, and only where an x1 kernel exists: 3x3 stride-1
+ *                 pad-1 convolutions on maps of 8 x 32 tiles (zero or reflection padding, upsample 0 / 1, no split-K) and im2col shapes
+ *                 (strided / non-3x3, not the 1x1 GEMM form), all without prologue / aux / in2 / LayerNorm.  Everything else -- and
+ *                 keep_attention -- answers KEEP_EUNSUP / KEEP_EINVAL with keep_last_error text: there is no silent change of policy. */
+#define KEEP_MMA_X1 3
 
 /* prologue activation applied to the (affine-normalised) conv input */
 #define KEEP_PRO_NONE 0
@@ -143,7 +153,7 @@ typedef struct {
   float aux_w;
   int32_t split_k; /* 0: the library chooses (keep_conv2d_plan reports the choice and the workspace it needs) */
   int32_t dtype; /* KEEP_F32 */
-  int32_t mma;   /* KEEP_MMA_F32 | KEEP_MMA_BF16 | KEEP_MMA_X3 */
+  int32_t mma;   /* KEEP_MMA_F32 | KEEP_MMA_BF16 | KEEP_MMA_X3 | KEEP_MMA_X1 */
   const void* weight_bf16; /* [Cout][KH][KW][Cin] bf16, required when mma == KEEP_MMA_BF16 */
   /* optional: per-tile (sum, sumsq) of the epilogue OUTPUT per channel, [N][stats_P][Cout][2], for the next
    * GroupNorm / InstanceNorm (keep_norm_finalize with P = stats_P): saves one full read of the activation.
