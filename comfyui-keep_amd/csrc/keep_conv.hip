@@ -1875,7 +1875,7 @@ static int plan_conv(const keep_conv2d_args* a, ConvP& p, ConvPlan& pl) {
     snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_c3_kernel");
     return KEEP_OK;
   }
-  // ---- single fp16 (ParseNet's opt-in speed policy): the x1 instantiations of the streaming halo kernel and of the im2col gather kernel,
+  // ---- single fp16 (the opt-in speed policy of ParseNet and of the KEEP network's 'f16'): the x1 instantiations of the streaming halo kernel and of the im2col gather kernel,
   // planned by the x3 rules; every other shape is refused -- there is no kernel of this grade for it and no silent change of policy
   if (mma == KEEP_MMA_X1) {
     KEEP_REQUIRE(a->dtype == KEEP_F32 && a->out_dtype != KEEP_BF16, "keep_conv2d: KEEP_MMA_X1 takes and writes fp32 tensors");
@@ -1885,7 +1885,8 @@ static int plan_conv(const keep_conv2d_args* a, ConvP& p, ConvPlan& pl) {
       pl.split_k = 1;
       pl.stats_rows = 256;
       pl.amax_ok = true;
-      snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_x3s_kernel<0, false, true>");      // (the x1 instantiation, as rocprofv3 prints it)
+      // (the x1 instantiations, as rocprofv3 prints them: <prologue activation, GroupNorm affine, X1>)
+      snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_x3s_kernel<%d, %s, true>", a->pro_act, a->pro_scale ? "true" : "false");
       return KEEP_OK;
     }
     if (have_w && !is33s1 && keep_conv_x1_gather_ok(a, p) && !(a->flags & KEEP_CONV_NO_GATHER_X3)) {
@@ -1905,8 +1906,9 @@ static int plan_conv(const keep_conv2d_args* a, ConvP& p, ConvPlan& pl) {
       return KEEP_OK;
     }
     keep_set_error("keep_conv2d: KEEP_MMA_X1 has no kernel for this call: it needs weight_x3 (the hi-only fp16 twin) and x3_acc_scale, Cin %% 32 == 0, no "
-                   "prologue / aux / in2 / LayerNorm, and either a 3x3 stride-1 pad-1 convolution on a map of 8 x 32 tiles without split-K or an "
-                   "im2col shape (a strided or non-3x3 convolution that is not a 1x1 GEMM)");
+                   "aux / in2 / LayerNorm, and either a 3x3 stride-1 pad-1 convolution on a map of 8 x 32 tiles without split-K (raw inputs, or a "
+                   "GroupNorm affine prologue alone / with ReLU / with the fast swish under zero padding) or an im2col shape without prologue (a strided or non-3x3 "
+                   "convolution that is not a 1x1 GEMM)");
     return KEEP_EUNSUP;
   }
   // ---- split fp16: halo / gather kernels where the geometry fits, the exact-f32 kernels otherwise (same parity grade)

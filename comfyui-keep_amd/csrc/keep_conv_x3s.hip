@@ -61,11 +61,15 @@ __device__ __forceinline__ float xs_xor32_sum(float x) {
 // to four gap steps (scale 2 + 2, convert, ds_write_b64) placed in the first four of the SIX gaps a piece owns (36 gaps / 6 pieces); the
 // fragments of tap t + 1 are read into a second register set during tap t (a single set would leave two gaps between a read and its use).
 // The requests of a step fall into gaps 1, 7, .., 31: two of them precede the first ring barrier (gap 11) and two follow the second
-// DMA group (gap 23), so the counted vmcnt waits of the x3 schedule hold unchanged.  Raw inputs without prologue only.
+// DMA group (gap 23), so the counted vmcnt waits of the x3 schedule hold unchanged.
+// X1 with the prologue (AFF; KEEP network, precision 'f16'): affine -> activation -> range scale -> ONE rounding -> ds_write_b64, over all six
+// gaps of a piece (conv_step).  The request stays in the piece's gap 1 and the next chunk's affine rides with the last piece (gap 31), so the
+// waits are those of the x3 prologue forms: vmcnt(2) / (18) in front of the first ring barrier, vmcnt(4) at the end of a step.  Under the
+// swish a piece costs 28 VALU instructions (8 of them transcendental) + the request + the ds_write against ~4 free issue slots per gap
+// beside the fragment read: the VALU work exceeds the MFMA shadow by about one instruction per gap and is accepted.
 template <int PRO, bool AFF, bool X1 = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int tiles_x, int tiles_y, int ncb, int n_items) {
   static_assert(AFF || PRO == KEEP_PRO_NONE, "an activation prologue comes with its GroupNorm affine");
-  static_assert(!X1 || (!AFF && PRO == KEEP_PRO_NONE), "the single-fp16 form takes raw inputs only");
   constexpr int WB = X1 ? 2 : 4;               // bytes per weight of p.wx3
   __shared__ __attribute__((aligned(16))) unsigned char lds_raw[XS_LDS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, lhi = lane >> 5, g = tid & 3;
@@ -175,7 +179,65 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
   // the raw registers are dead from there on.  Zero padding applies to the normalised + activated tensor: under the swish the exp2
   // argument of a padding piece gets +1e30 (exp2 -> inf, rcp -> 0, y * 0 = 0) -- no select instructions.
   auto conv_step = [&](int q, int hb) __attribute__((always_inline)) {
-    if constexpr (X1) {                        // piece k = q / 6, steps 0 .. 3 of its six gaps
+    if constexpr (X1 && AFF) {                 // piece k = q / 6: affine, activation, range scale, ONE rounding, ds_write_b64 over its six gaps
+      constexpr bool SW = PRO == KEEP_PRO_SWISH, RL = PRO == KEEP_PRO_RELU;
+      const int k = q / 6, st = q % 6;
+      const float rs = p.in_amax ? in_sC : 1.f, rinv = p.in_amax ? in_invC : 1.f;
+      if (st == 0) {
+        cv[0] = __builtin_fmaf(hreg[k].x, sc4.x, sh4.x); cv[1] = __builtin_fmaf(hreg[k].y, sc4.y, sh4.y);
+        cv[2] = __builtin_fmaf(hreg[k].z, sc4.z, sh4.z); cv[3] = __builtin_fmaf(hreg[k].w, sc4.w, sh4.w);
+        padf = (padmask & (1u << k)) ? 1e30f : 0.f;
+      }
+      if (st == 1) {                           // the requests sit where the raw-input form has them (gaps 1, 7, .., 31: the counted waits)
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(okF ? in_rsrc : null_rsrc, h_voff[k], chF * 64, KEEP_LD_AUX_XS);
+        hreg[k] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
+        if (k == HALO_IT - 1) {                // the affine of this chunk has been read for the last time: the next chunk's
+          const u32x4 a = __builtin_amdgcn_raw_buffer_load_b128(okF ? sc_rsrc : null_rsrc, sc_voff, chF * 64, 0);
+          const u32x4 b = __builtin_amdgcn_raw_buffer_load_b128(okF ? sh_rsrc : null_rsrc, sc_voff, chF * 64, 0);
+          sc4 = make_float4(__uint_as_float(a.x), __uint_as_float(a.y), __uint_as_float(a.z), __uint_as_float(a.w));
+          sh4 = make_float4(__uint_as_float(b.x), __uint_as_float(b.y), __uint_as_float(b.z), __uint_as_float(b.w));
+        }
+      }
+      if (SW) {                                // the x3 form's sequence: v * rcp(1 + exp2(-v log2 e + padf)); the range scale rides in the `+ 1`:
+                                               // (e + 1) / s in one fma (a power of two: the same bits), so rcp() already carries s
+        if (st == 1) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) cw[e] = __builtin_fmaf(cv[e], -1.4426950408889634f, padf);
+        }
+        if (st == 2) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) cw[e] = __builtin_amdgcn_exp2f(cw[e]);
+        }
+        if (st == 3) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) cw[e] = __builtin_fmaf(cw[e], rinv, rinv);
+          cw[0] = __builtin_amdgcn_rcpf(cw[0]); cw[1] = __builtin_amdgcn_rcpf(cw[1]);
+        }
+        if (st == 4) {
+          cw[2] = __builtin_amdgcn_rcpf(cw[2]); cw[3] = __builtin_amdgcn_rcpf(cw[3]);
+          cv[0] *= cw[0]; cv[1] *= cw[1];
+        }
+        if (st == 5) { cv[2] *= cw[2]; cv[3] *= cw[3]; }
+      } else {                                 // ReLU / plain affine: padding by select (NaN stays NaN: relu_keep_nan)
+        if (st == 1 && RL) { cv[0] = relu_keep_nan(cv[0]); cv[1] = relu_keep_nan(cv[1]); }
+        if (st == 2 && RL) { cv[2] = relu_keep_nan(cv[2]); cv[3] = relu_keep_nan(cv[3]); }
+        if (st == 3) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) cv[e] *= rs;
+        }
+        if (st == 4) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) cv[e] = padf != 0.f ? 0.f : cv[e];
+        }
+      }
+      if (st == 5) {
+        chi[0] = __builtin_convertvector(f32x2{cv[0], cv[1]}, f16x2);
+        chi[1] = __builtin_convertvector(f32x2{cv[2], cv[3]}, f16x2);
+        *reinterpret_cast<uint2*>(lds_raw + wr_addr[k] + hb) = make_uint2(__builtin_bit_cast(unsigned, chi[0]), __builtin_bit_cast(unsigned, chi[1]));
+      }
+      return;
+    }
+    if constexpr (X1) {                        // raw inputs: piece k = q / 6, steps 0 .. 3 of its six gaps
       const int k = q / 6, st = q % 6;
       const float rs = p.in_amax ? in_sC : 1.f;
       if (st == 0) { cv[0] = hreg[k].x * rs; cv[1] = hreg[k].y * rs; }
@@ -656,9 +718,12 @@ bool keep_conv_x3_stream_ok(const keep_conv2d_args* a, const ConvP& p, int split
          (long)a->N * a->Cin * 4 < (1L << 31);
 }
 
-// KEEP_MMA_X1: what the single-fp16 form of the streaming kernel takes inside keep_conv_x3_stream_ok -- no prologue, whole two-chunk weight rows
+// KEEP_MMA_X1: what the single-fp16 form of the streaming kernel takes inside keep_conv_x3_stream_ok (its prologue rule included: raw inputs,
+// GroupNorm affine, affine + ReLU, affine + fast swish) -- un-split, no aux tensor, whole two-chunk weight rows.  The prologue forms are
+// the KEEP network's: zero padding only (a v22 caller's prologue call under reflection padding -- ParseNet's mode -- is refused as it was)
 bool keep_conv_x1_stream_ok(const keep_conv2d_args* a, const ConvP& p) {
-  return keep_conv_x3_stream_ok(a, p, 1) && !a->pro_scale && a->pro_act == KEEP_PRO_NONE && a->Cin % 32 == 0 && a->upsample != KEEP_UPSAMPLE_X2_PHASES;
+  return keep_conv_x3_stream_ok(a, p, 1) && a->Cin % 32 == 0 && a->upsample != KEEP_UPSAMPLE_X2_PHASES &&
+         (!a->pro_scale || a->pad_mode == KEEP_PAD_ZERO);
 }
 
 int keep_conv2d_x3_stream(const keep_conv2d_args* a, ConvP& p, int n_cu, hipStream_t st) {
@@ -666,9 +731,16 @@ int keep_conv2d_x3_stream(const keep_conv2d_args* a, ConvP& p, int n_cu, hipStre
   const int n_items = a->N * tiles_x * tiles_y * ncb;
   dim3 grid(n_items < 2 * n_cu ? n_items : 2 * n_cu), block(256);
   const bool aff = a->pro_scale != nullptr;
-  if (a->mma == KEEP_MMA_X1)      // (keep_conv_x1_stream_ok: raw inputs, Cin % 32 == 0)
-    hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_NONE, false, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
-  else if (a->pro_act == KEEP_PRO_SWISH)
+  if (a->mma == KEEP_MMA_X1) {    // (keep_conv_x1_stream_ok: Cin % 32 == 0, the prologue forms of the x3 instantiations below)
+    if (a->pro_act == KEEP_PRO_SWISH)
+      hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_SWISH, true, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
+    else if (a->pro_act == KEEP_PRO_RELU)
+      hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_RELU, true, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
+    else if (aff)
+      hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_NONE, true, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
+    else
+      hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_NONE, false, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
+  } else if (a->pro_act == KEEP_PRO_SWISH)
     hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_SWISH, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
   else if (a->pro_act == KEEP_PRO_RELU)
     hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_RELU, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);

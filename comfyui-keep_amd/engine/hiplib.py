@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('KEEP_HIP_LIB') or os.path.join(os.path.dirname(_HERE), 'csrc', 'libkeep_hip.so')   # (KEEP_HIP_LIB: dev A/B builds)
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 F32, BF16 = 0, 1
 MMA_F32, MMA_BF16, MMA_X3, MMA_X1 = 0, 1, 2, 3

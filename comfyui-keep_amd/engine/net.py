@@ -51,8 +51,9 @@ STREAM_OVERLAP_FIRST = int(os.environ.get('KEEP_AMD_OVERLAP_FIRST', '3'))
 STREAM_OVERLAP_CHUNK = int(os.environ.get('KEEP_AMD_OVERLAP_CHUNK', '4'))
 GRAPH_CACHE = 4
 RESIDENT = os.environ.get('KEEP_AMD_RESIDENT', '0') == '1'      # keep the packed weights on the device across offload()
-PRECISIONS = ('fp32', 'x3', 'bf16')
+PRECISIONS = ('fp32', 'x3', 'bf16', 'f16')
 DEFAULT_PRECISION = 'x3'
+X3_GRADE = ('x3', 'f16')      # policies whose operands are fp16 halves: the range check and its exact-f32 re-run apply
 
 
 ROCTX = os.environ.get('KEEP_AMD_ROCTX', '0') == '1'      # per-stage roctx ranges (rocprofv3 --marker-trace / --kernel-trace timelines)
@@ -112,6 +113,8 @@ class KeepNet:
         self._dev_blob16 = None    # bf16 twin of the packed blob (same offsets) for the bf16-MFMA policy
         self._dev_blobx3 = None    # split-fp16 twin (2 x int16 per weight) for the x3 policy
         self._x3_scales = None     # per-tensor accumulator scales of the x3 twin (ops.make_x3_blob)
+        self._dev_blobx1 = None    # 'f16': hi-only fp16 twin (1 x int16 per weight) of the 3x3 convolution weights outside GMFlow
+        self._x1_ranges = None
         self.o = ops.Ops()         # this net's precision policy + weight twins (never shared between nets)
         self.x3_fallbacks = 0      # batches the x3 policy handed back to the f32 kernels (non-finite output)
         # hipGraph replay of the whole forward for small batches (launch-bound: ~9 k kernels per clip): 'auto' = at most
@@ -169,7 +172,11 @@ class KeepNet:
     def set_precision(self, precision):
         """'fp32': exact f32 MFMA everywhere.  'x3': every matrix-core operand split into two fp16 halves, three MFMAs per
         product (<= 2^-22 relative per product, fp32 accumulate) -- parity-grade (<= 1e-3) at the 16-bit pipe's rate / 3.
-        'bf16': operands rounded to bf16 (speed policy, outside the parity tolerance)."""
+        'bf16': operands rounded to bf16 (speed policy, outside the parity tolerance).
+        'f16': the x3 policy with the streaming 3x3 convolutions (raw inputs and the GroupNorm-swish prologue) on SINGLE fp16
+        operands (KEEP_MMA_X1: one MFMA per product, 11 mantissa bits per operand) wherever keep_conv2d_plan admits it; attention,
+        the GEMM forms, the phase upsample, the split-K forms and GMFlow stay x3.  An opt-in speed policy outside the parity
+        tolerance like 'bf16' (DESIGN 4.2); batch invariance and the fp16-range fallback are those of 'x3'."""
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
         self.precision = precision
@@ -185,12 +192,28 @@ class KeepNet:
         # cost every other layer its `lo` bits (tests/test_gpu_net.py::test_x3_scale_is_per_tensor)
         self._dev_blobx3, self._x3_scales = ops.make_x3_blob(self._dev_blob, self._index, self.w, names)
 
+    def _make_x1(self):
+        """'f16': hi-only twin of every 3x3 convolution weight a streaming kernel could read (packed [Cout,3,3,Cin], Cin % 32 == 0),
+        GMFlow excluded (its flows feed a warp: it stays x3).  Same per-tensor scales as the x3 twin (one scale table serves both)."""
+        names = [n for n, (_, shape) in self._index.items() if len(shape) == 4 and shape[1] == 3 and shape[2] == 3 and shape[-1] % 32 == 0
+                 and not n.startswith('flownet.')]
+        self._dev_blobx1, self._x1_ranges = ops.make_x1_blob(self._dev_blob, self._index, self.w, names)
+        x3 = {(a, b): s for a, b, s in self._x3_scales}
+        assert all(x3.get((a, b)) == s for a, b, s in self._x1_ranges), 'x1 and x3 twins must share their per-tensor scales'
+
+    def twin_bytes(self, precision=None):
+        """Device bytes of the weight twins ``precision`` (default: the current one) holds beside the packed fp32 blob -- what
+        ``clips_per_call`` takes off the free memory while they are not built yet."""
+        precision = self.precision if precision is None else precision
+        n = int(self._dev_blob.numel()) if self._dev_blob is not None else (0 if self._blob is None else int(self._blob.size))
+        return {'bf16': 2 * n, 'x3': 4 * n, 'f16': 4 * n + 2 * n}.get(precision, 0)
+
     def _activate_precision(self):
         if self.precision == 'bf16':
             if self._dev_blob16 is None:
                 self._dev_blob16 = self._dev_blob.to(torch.bfloat16)
             self.o.set_precision(L.MMA_BF16, self._dev_blob, self._dev_blob16)
-        elif self.precision == 'x3':
+        elif self.precision in ('x3', 'f16'):
             if self._dev_blobx3 is None:
                 self._make_x3()
             self.o.set_precision(L.MMA_X3, self._dev_blob, None, self._dev_blobx3, 1.0, x3_scales=self._x3_scales)
@@ -202,6 +225,10 @@ class KeepNet:
                 for i, (kind, _, _) in enumerate(generator_blocks(self.cfg)):
                     if kind == 'up':
                         self.o.up2_twin(self.w[f'generator.blocks.{i}.conv.weight'])
+            if self.precision == 'f16':      # the x1 twin: built here, never inside a stream capture
+                if self._dev_blobx1 is None:
+                    self._make_x1()
+                self.o.set_x1_twin(self._dev_blobx1, self._x1_ranges)
         else:
             self.o.set_precision(L.MMA_F32, self._dev_blob, None)
 
@@ -212,7 +239,7 @@ class KeepNet:
                 self._pinned = torch.from_numpy(self._blob).pin_memory()
             from_blob = self._pinned
         self._dev_blob = from_blob.to(self.device, non_blocking=False)
-        self._dev_blob16 = self._dev_blobx3 = None
+        self._dev_blob16 = self._dev_blobx3 = self._dev_blobx1 = None
         self._graphs = {}
         self.w = views(self._dev_blob, self._index)
 
@@ -238,6 +265,7 @@ class KeepNet:
             # stale one; load_state_dict / adopt_packed close it) -- KEEPModelPack.offload() runs after every node call, and closing the
             # pool here cost every call a respawn of the workers (torch import, HIP init), a 633 MB broadcast and the x3 twins
             self._dev_blob, self._dev_blob16, self._dev_blobx3, self.w = None, None, None, None
+            self._dev_blobx1 = None
             self.o.set_precision(self.o.mma)        # drop this net's references to the device blobs
             self._const = {}
             self._graphs = {}
@@ -285,6 +313,7 @@ class KeepNet:
     def adopt_packed(self, index, dev_blob):
         """Install a packed blob received from another rank."""
         self._index, self._dev_blob, self._dev_blob16, self._dev_blobx3 = index, dev_blob, None, None
+        self._dev_blobx1 = None
         self._graphs = {}
         self.weights_generation += 1
         self.close_pool()
@@ -738,7 +767,7 @@ class KeepNet:
                 res = self._forward_graphed(x, B, T, H, Wd)
             else:
                 res = self._forward(x, B, T, H, Wd, force_indices, return_aux, force_flows)
-            if _defer_check or self.precision != 'x3' or not CHECK_X3_RANGE:
+            if _defer_check or self.precision not in X3_GRADE or not CHECK_X3_RANGE:
                 return res
             bits = self._status_bits()
             if bits == 0:
@@ -757,7 +786,7 @@ class KeepNet:
         generator would paint a finite, wrong frame), ReLU / flow_warp keep NaN, and the last kernel of the forward scans the
         output (KEEP_STATUS_NONFINITE_TENSOR).  Any bit set -> the batch is re-run on the exact-f32 kernels: never a quietly
         wrong frame.  The check is ONE int32 read (the forward's status word), not a host-side reduction over the output."""
-        if self.precision != 'x3' or not CHECK_X3_RANGE:
+        if self.precision not in X3_GRADE or not CHECK_X3_RANGE:
             return res
         if bits is None:
             bits = self._status_bits()
@@ -767,6 +796,7 @@ class KeepNet:
         logging.getLogger('ComfyUI-KEEP').warning(
             "x3 precision policy left the fp16 operand range on this batch (status %d); re-running it on the f32 kernels", bits)
         self.x3_fallbacks += 1
+        policy = self.precision                      # 'x3' or 'f16': restored after the re-run
         self.precision = 'fp32'
         try:
             self._activate_precision()
@@ -780,7 +810,7 @@ class KeepNet:
                                       for b0 in range(0, B, part)], 0)
             return self._forward(x, B, T, H, Wd, force_indices, return_aux, force_flows)
         finally:
-            self.precision = 'x3'
+            self.precision = policy
             self._activate_precision()
 
     def _forward_graphed(self, x, B, T, H, Wd):
@@ -940,7 +970,7 @@ class KeepNet:
             if return_aux:
                 flows = torch.cat([p[2] for p in flow_parts], dim=1)
         out = ops.nhwc_to_nchw(out_nhwc.view(B * T, H, Wd, 3)).view(B, T, 3, H, Wd)
-        if self.precision == 'x3' and CHECK_X3_RANGE:
+        if self.precision in X3_GRADE and CHECK_X3_RANGE:
             L.call('keep_nonfinite_flag', out, out.numel(), self.o.status)
         if return_aux:
             aux = {'indices': torch.stack(idx_all, 1), 'margins': torch.stack(margin_all, 1), 'gains': gains,
@@ -957,7 +987,8 @@ class KeepNet:
         caps it (default 48 = what 288 GB hold under x3: 16 / 32 / 48 clips per call run at 279.6 / 287.1 / 290.3 frames/s -- the
         16 x 16 ... 64 x 64 stages and the token GEMMs fill the chip better; results do not depend on the choice: per-image
         plans); the node's ``max_clip_length`` therefore still bounds memory: a longer clip means fewer clips per call, never a
-        bigger footprint."""
+        bigger footprint.  'f16' holds the x3 footprint per frame plus its hi-only weight twin (``twin_bytes``: 2 bytes per blob
+        element, 0.32 GB) -- a built twin shows in the free memory read here, one still to be built is taken off it."""
         cap = int(os.environ.get('KEEP_AMD_MAX_CLIPS', '48'))
         per_frame = {'bf16': 0.17e9, 'fp32': 0.36e9}.get(self.precision, 0.23e9) * (H * Wd) / (512.0 * 512.0)
         try:
@@ -965,6 +996,8 @@ class KeepNet:
             free += torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)   # cached blocks are reusable
         except Exception:
             free = 64e9
+        if self.precision == 'f16' and self._dev_blobx1 is None:      # the x1 twin is built at the first call: its bytes are not free
+            free -= self.twin_bytes('f16') - (0 if self._dev_blobx3 is None else self.twin_bytes('x3'))
         return max(1, min(cap, int(0.8 * free / (per_frame * max(T, 1)))))
 
     def run_clips(self, clips, need_upscale=False, max_b=None):
@@ -1153,6 +1186,6 @@ class KeepNet:
                 if pending is not None:
                     finish(pending)          # group g-1: its download ran under group g's launches
                 # x is kept only for the (rare) f32 re-run; precision 'x3' is the only policy that can ask for one
-                pending = (gi, x if (self.precision == 'x3' and CHECK_X3_RANGE) else None, r8_host, st_host, ev_done)
+                pending = (gi, x if (self.precision in X3_GRADE and CHECK_X3_RANGE) else None, r8_host, st_host, ev_done)
             finish(pending)
         return local

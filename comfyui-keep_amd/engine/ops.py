@@ -25,6 +25,7 @@ USE_BK256 = bool(int(os.environ.get('KEEP_BK256', '0')))   # measured slower tha
 HALO_PRENORM_MINPIX = int(os.environ.get('KEEP_HALO_PRENORM_MINPIX', '0'))
 
 DEBUG_SYNC = os.environ.get('KEEP_DEBUG_SYNC') is not None
+X3_STREAM_KERNEL = 'conv3x3_halo_x3s_kernel'      # keep_conv2d_plan's name of the x3 streaming 3x3 kernel: the one family 'f16' substitutes
 _PLAN_CACHE = {}
 # Deployment settings of the library, read ONCE here (the library itself reads no environment variable: they travel in the argument
 # structs).  KEEP_PLAN_REF_IMAGES: the fixed reference batch of the parity policies' plans (default 16; 2 = latency profile for single
@@ -98,6 +99,12 @@ class Ops:
         self.flags = DEFAULT_CONV_FLAGS
         self.attn_flags = 0
         self.plan_ref_images = PLAN_REF_IMAGES
+        # KeepNet's 'f16' policy: the x3 policy (mma, attn_mma and every twin above stay x3) plus a hi-only twin of the 3x3 weights
+        # (make_x1_blob) -- conv() substitutes L.MMA_X1 where the library's plan admits it (route_conv).  None: plain x3.
+        self.blobx1 = None
+        self._x1_table = None      # ([first element], [(first, one past the last)]) of the tensors blobx1 holds, sorted
+        self._x1_route = {}        # plan key -> L.MMA_X1 | L.MMA_X3: one keep_conv2d_plan query per shape
+        self.census = None         # when a dict: kernel name (plan string) -> launches, counted by conv() (tests, tools/bench_precision.py)
 
     def begin_forward(self, device):
         """Zero this forward's bookkeeping words with ONE fill launch: the status word (non-finite logits / tensors, see
@@ -128,12 +135,57 @@ class Ops:
         if x3_scales:
             self._x3_table = ([a for a, _, _ in x3_scales], list(x3_scales))
         self.mma = self.attn_mma = mma
+        self.blobx1, self._x1_table, self._x1_route = None, None, {}      # ('f16' re-attaches its twin after every policy change: set_x1_twin)
         if blobx3 is not None and (blob32 is not self._up2_src[0] or blobx3 is not self._up2_src[1]):
             # phase kernels of the Upsample convolutions (up2_twin): derived from THESE blob objects -- a new upload, even one that lands
             # on the same addresses, starts from an empty cache; a policy switch on the same blobs keeps it (captured x3 graphs hold
             # the addresses of its tensors)
             self._up2, self._up2_src = {}, (blob32, blobx3)
         self.blob32, self.blob16, self.blobx3, self.x3_acc_scale = blob32, blob16, blobx3, float(x3_acc_scale)
+
+    def set_x1_twin(self, blobx1=None, ranges=None):
+        """'f16' on top of an x3 policy set by ``set_precision``: ``blobx1`` is ``make_x1_blob``'s hi-only twin (same per-tensor
+        power-of-two scales as the x3 twin), ``ranges`` its (first element, one past the last, 2^-e) table.  None: back to plain x3."""
+        if blobx1 is not None and self.mma != L.MMA_X3:
+            raise ValueError("set_x1_twin: the single-fp16 substitution rides on the x3 policy (set_precision(L.MMA_X3, ...) first)")
+        self.blobx1 = blobx1
+        self._x1_table = None
+        if blobx1 is not None:
+            rows = sorted((int(a), int(b)) for a, b, _ in ranges)
+            self._x1_table = ([a for a, _ in rows], rows)
+        self._x1_route = {}
+
+    def x1_twin(self, w):
+        """Hi-only fp16 copy of an fp32 weight view for the 'f16' substitution, or None when the policy is off or the tensor has no
+        such twin (then the layer stays x3)."""
+        if self.blobx1 is None:
+            return None
+        import bisect
+        off = self._blob_off(w)
+        starts, rows = self._x1_table
+        i = bisect.bisect_right(starts, off) - 1
+        if i < 0 or not (rows[i][0] <= off and off + w.numel() <= rows[i][1]):
+            return None
+        return self.blobx1[off:off + w.numel()]
+
+    def route_conv(self, key, x3_plan, x1_plan):
+        """'f16': which matrix-core policy a convolution call runs under.  L.MMA_X1 exactly where the x3 plan of the call is the un-split
+        streaming 3x3 kernel AND the library's plan admits the call under KEEP_MMA_X1 (``x1_plan()``: keep_conv2d_plan, KEEP_EUNSUP ->
+        refused); L.MMA_X3 everywhere else -- the GEMM forms, the split-K / 64-pixel partial forms, the phase upsample, im2col shapes.
+        Both plans follow the per-image geometry and the fixed reference batch, so the answer (cached per ``key``) never depends on a
+        clip's batch-mates.  Attention never comes here: ``attn_mma`` stays x3."""
+        r = self._x1_route.get(key)
+        if r is None:
+            r = L.MMA_X3
+            if x3_plan.kernel == X3_STREAM_KERNEL and x3_plan.split_k == 1:
+                try:
+                    x1_plan()
+                    r = L.MMA_X1
+                except L.KeepHipError as e:
+                    if '(code -2)' not in str(e):      # anything but KEEP_EUNSUP is an error, not an answer
+                        raise
+            self._x1_route[key] = r
+        return r
 
     # ------------------------------------------------------------------ weight twins
     def _blob_off(self, w):
@@ -262,8 +314,10 @@ class Ops:
             # nearest x2 + 3x3 as four 2x2-tap phase convolutions on the source grid: 4 of 9 taps are multiplied
             wx3, x3_acc_scale = self.up2_twin(w)
             up_mode = L.UPSAMPLE_X2_PHASES
+        wx3_own = False              # wx3 is this Ops' x3 twin of w (not a caller's tensor): what 'f16' may replace by the x1 twin
         if mma in (L.MMA_X3, L.MMA_X1) and wx3 is None:
             wx3 = None if {mma, self.mma} == {L.MMA_X3, L.MMA_X1} else self.x3_twin(w)      # (the twin's layout is the Ops policy's)
+            wx3_own = wx3 is not None
             if mma == L.MMA_X1 and wx3 is None:                     # no x1 kernel reads fp32 weights: such a layer (ParseNet's RGB convolution) runs exact f32
                 mma = L.MMA_F32
             if wx3 is not None and x3_acc_scale is None:
@@ -310,6 +364,17 @@ class Ops:
             pro, pro_act, in_dtype = None, L.PRO_NONE, L.BF16
             a = make_args(xin, in_dtype, None, pro_act, odt, sk_req)
             pl = _plan(a, key_of(in_dtype, None, pro_act, odt, sk_req))
+        if self.blobx1 is not None and mma == L.MMA_X3 and self.mma == L.MMA_X3 and KH == 3 and wx3_own and x2 is None:
+            wx1 = self.x1_twin(w)                      # (a caller's own wx3 -- the phase weights of an Upsample -- stays x3)
+            if wx1 is not None:
+                key3 = key_of(in_dtype, pro, pro_act, odt, sk_req)
+                keep = (mma, wx3)
+                mma, wx3 = L.MMA_X1, wx1               # (make_args / key_of read these)
+                if self.route_conv(key3, pl, lambda: L.conv2d_plan(make_args(xin, in_dtype, pro, pro_act, odt, sk_req))) == L.MMA_X1:
+                    a = make_args(xin, in_dtype, pro, pro_act, odt, sk_req)
+                    pl = _plan(a, key_of(in_dtype, pro, pro_act, odt, sk_req))
+                else:
+                    mma, wx3 = keep
         if want_bf16_out and not pl.out_bf16_ok:
             want_bf16_out, odt = False, L.F32
             a = make_args(xin, in_dtype, pro, pro_act, odt, sk_req)
@@ -348,6 +413,8 @@ class Ops:
             print(f'[keep] {pl.kernel} N={N} H={H} W={W} ld={ld} Cin={Cin} Cout={Cout} k={KH} s={stride} up={int(upsample)} '
                   f'split={pl.split_k} in_off={in_off} pro={pro is not None}/{pro_act} act={act} res={residual is not None} '
                   f'aux={aux is not None} statsP={pl.stats_P if stats else 0}', file=sys.stderr, flush=True)
+        if self.census is not None:
+            self.census[pl.kernel] = self.census.get(pl.kernel, 0) + 1
         L.conv2d_launch(a)
         if DEBUG_SYNC:
             torch.cuda.synchronize()

@@ -30,8 +30,8 @@ extern "C" {
  * the fields a shorter known layout lacks as zero), keep_sizeof_*_args(), keep_argmax_gather takes the non-finite status word,
  * keep_nonfinite_flag.  v13: keep_conv2d_args.upsample accepts KEEP_UPSAMPLE_X2_PHASES (same layout; a v12 library refuses the
  * value, so the binding asks for 13).  v18: the two reserved words of keep_conv2d_args become `flags` / `plan_ref_images`, the one of
- * keep_attention_args `flags` (same layout and sizes; zero keeps the v17 behaviour) -- the library no longer reads ANY environment variable.  v19: keep_yolo_letterbox_u8, keep_yolo_select, keep_layernorm_amax, keep_geglu_amax, keep_retina_nms_ordered (additions only).  v21: keep_lanczos4_tables, keep_resize_lanczos4_u8 (additions only).  v22: KEEP_MMA_X1 accepted by keep_conv2d (a new value of `mma`; same layouts and sizes, every v21 call means what it meant). */
-#define KEEP_ABI_VERSION 22
+ * keep_attention_args `flags` (same layout and sizes; zero keeps the v17 behaviour) -- the library no longer reads ANY environment variable.  v19: keep_yolo_letterbox_u8, keep_yolo_select, keep_layernorm_amax, keep_geglu_amax, keep_retina_nms_ordered (additions only).  v21: keep_lanczos4_tables, keep_resize_lanczos4_u8 (additions only).  v22: KEEP_MMA_X1 accepted by keep_conv2d (a new value of `mma`; same layouts and sizes, every v21 call means what it meant).  v23: KEEP_MMA_X1 also takes the prologue forms of the streaming 3x3 kernel (pro_scale / pro_shift alone, with KEEP_PRO_RELU, with KEEP_PRO_SWISH in its fast form); additions only, every v22 call means what it meant. */
+#define KEEP_ABI_VERSION 23
 #define KEEP_OK 0
 #define KEEP_EINVAL (-1)
 #define KEEP_EUNSUP (-2)
@@ -61,8 +61,14 @@ extern "C" {
  *                 precision 'f16').  `weight_x3` is then the hi-only twin: fp16(weight * 2^e) as plain [Cout][KH*KW][Cin] fp16, 16-byte
  *                 aligned, Cin %% 32 == 0; x3_acc_scale = 2^-e.  keep_conv2d only, and only where an x1 kernel exists: 3x3 stride-1
  *                 pad-1 convolutions on maps of 8 x 32 tiles (zero or reflection padding, upsample 0 / 1, no split-K) and im2col shapes
- *                 (strided / non-3x3, not the 1x1 GEMM form), all without prologue / aux / in2 / LayerNorm.  Everything else -- and
- *                 keep_attention -- answers KEEP_EUNSUP / KEEP_EINVAL with keep_last_error text: there is no silent change of policy. */
+ *                 (strided / non-3x3, not the 1x1 GEMM form), all without aux / in2 / LayerNorm.  Everything else -- and
+ *                 keep_attention -- answers KEEP_EUNSUP / KEEP_EINVAL with keep_last_error text: there is no silent change of policy.
+ *                 v23: the 3x3 stride-1 form also takes the GroupNorm prologue under the rule of the x3 streaming kernel -- pro_scale /
+ *                 pro_shift alone, with KEEP_PRO_RELU, or with KEEP_PRO_SWISH (fast form: not with KEEP_CONV_X3_EXACT_ACT), KEEP_PAD_ZERO only; the KEEP
+ *                 network's opt-in precision 'f16' (engine/net.py).  Per element: v = x * pro_scale + pro_shift in fp32, the activation,
+ *                 the power-of-two range scale of x3_in_amax[n] where given (applied to the prologue's RESULT in every prologue form, and
+ *                 undone on the accumulators), one rounding to fp16.  Zero padding is the zero of the activated tensor.  The im2col
+ *                 shapes stay without prologue. */
 #define KEEP_MMA_X1 3
 
 /* prologue activation applied to the (affine-normalised) conv input */
