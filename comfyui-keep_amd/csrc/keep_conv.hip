@@ -1702,6 +1702,7 @@ bool keep_conv_x3_stream_ok(const keep_conv2d_args* a, const ConvP& p, int split
 bool keep_conv_x3_gather_ok(const keep_conv2d_args* a, const ConvP& p);
 bool keep_conv_x1_stream_ok(const keep_conv2d_args* a, const ConvP& p);
 bool keep_conv_x1_gather_ok(const keep_conv2d_args* a, const ConvP& p);
+bool keep_conv_x1_gemm_ok(const keep_conv2d_args* a, const ConvP& p);
 bool keep_gemm_x3l_ok(const keep_conv2d_args* a);
 int keep_gemm_x3l_waves(const keep_conv2d_args* a);
 int keep_conv2d_x3_gemm_lat(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
@@ -1889,7 +1890,9 @@ static int plan_conv(const keep_conv2d_args* a, ConvP& p, ConvPlan& pl) {
       snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_x3s_kernel<%d, %s, true>", a->pro_act, a->pro_scale ? "true" : "false");
       return KEEP_OK;
     }
-    if (have_w && !is33s1 && keep_conv_x1_gather_ok(a, p) && !(a->flags & KEEP_CONV_NO_GATHER_X3)) {
+    // (under KEEP_CONV_X1_GEMM also a 3x3 stride-1 pad-1 convolution NO halo kernel takes -- a ragged map, where x3 itself runs this im2col kernel)
+    if (have_w && (!is33s1 || ((a->flags & KEEP_CONV_X1_GEMM) && !keep_conv_x3_halo_ok(a))) && keep_conv_x1_gather_ok(a, p) &&
+        !(a->flags & KEEP_CONV_NO_GATHER_X3)) {
       pl.path = PATH_GATHER_X3;
       pl.tile = (a->Cout <= 64 || M <= small_m_threshold(a)) ? 1 : 2;
       pl.plain = true;
@@ -1904,6 +1907,32 @@ static int plan_conv(const keep_conv2d_args* a, ConvP& p, ConvPlan& pl) {
       // (the x1 instantiation; its trailing template booleans as 0 / 1: the name has 63 characters)
       snprintf(pl.kernel, sizeof(pl.kernel), "conv_x3_kernel<%s, true, 0, 0, 1, 0, 1>", pl.tile == 1 ? "2, 2, 1, 1" : "2, 2, 2, 2");
       return KEEP_OK;
+    }
+    // KEEP_CONV_X1_GEMM (opt-in bit: without it the 1x1 GEMM form stays refused, as every v22 / v23 caller was promised): the x1 instantiation of
+    // the GEMM variant of conv_x3_kernel, planned by the x3 rules of the gather path above -- tile and split-K from the reference batch.  The
+    // latency form (gemm_x3l_kernel) has no x1 twin: a shape x3 would send there takes this tile kernel too.
+    if (a->flags & KEEP_CONV_X1_GEMM) {
+      if (have_w && !is33s1 && keep_conv_x1_gemm_ok(a, p) && !(a->flags & KEEP_CONV_NO_GATHER_X3)) {
+        pl.path = PATH_GATHER_X3;
+        pl.tile = (a->Cout <= 64 || M <= small_m_threshold(a)) ? 1 : 2;
+        pl.plain = true;
+        const int steps = a->Cin / 32;
+        const long blocks = pl.tile == 1 ? (long)cdiv(M, 64) * cdiv(a->Cout, 64) : (long)cdiv(M, 128) * cdiv(a->Cout, 128);
+        const long waves = blocks * 4;
+        auto_split = (waves >= kTargetWaves || steps < 8) ? 1 : (int)max(1L, min(min(4L * kTargetWaves / waves, (long)steps / 2), 32L));
+        pl.split_k = a->split_k > 0 ? a->split_k : auto_split;
+        if (pl.split_k > steps) pl.split_k = steps;
+        pl.stats_rows = pl.tile == 1 ? 64 : 128;
+        pl.amax_ok = pl.split_k == 1 && ((long)a->Ho * a->Wo) % (pl.tile == 1 ? 32 : 64) == 0;
+        // (<tile, PLAIN, ONE, KSL, DEEP, KAL, X1>, the trailing booleans as 0 / 1 like the im2col form's name)
+        snprintf(pl.kernel, sizeof(pl.kernel), "conv_x3_kernel<%s, true, 1, 0, 1, 0, 1>", pl.tile == 1 ? "2, 2, 1, 1" : "2, 2, 2, 2");
+        return KEEP_OK;
+      }
+      keep_set_error("keep_conv2d: KEEP_MMA_X1 (with KEEP_CONV_X1_GEMM) has no kernel for this call: it needs weight_x3 (the hi-only fp16 twin) and "
+                     "x3_acc_scale, Cin %% 32 == 0, no aux / in2 / LayerNorm, and one of: a 3x3 stride-1 pad-1 convolution on a map of 8 x 32 tiles "
+                     "without split-K (raw inputs or the streaming kernel's prologue forms), an im2col shape without prologue (a 3x3 stride-1 pad-1 "
+                     "convolution only on a map no halo kernel tiles), or a 1x1 stride-1 unpadded GEMM without prologue");
+      return KEEP_EUNSUP;
     }
     keep_set_error("keep_conv2d: KEEP_MMA_X1 has no kernel for this call: it needs weight_x3 (the hi-only fp16 twin) and x3_acc_scale, Cin %% 32 == 0, no "
                    "aux / in2 / LayerNorm, and either a 3x3 stride-1 pad-1 convolution on a map of 8 x 32 tiles without split-K (raw inputs, or a "

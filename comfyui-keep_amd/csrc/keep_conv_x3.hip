@@ -695,10 +695,11 @@ __device__ __forceinline__ void x3_gather_epilogue(const ConvP& p, f32x16 (&acc)
 // positions of the unrolled ring: the first MFMA of a slice takes the inline constant 0 as C, the fold is 16 adds, nothing is zeroed.
 // X1 (KEEP_MMA_X1): operands rounded once to fp16, one MFMA per product -- no `lo` halves are computed, staged or read.  p.wx3 is
 // the hi-only twin, plain [Cout][KH*KW][Cin] fp16: the 64 bytes a cout row needs per K step are pieces 0 .. 3 of a thread row (the threads
-// of pieces 4 .. 7 fetch and stage nothing).  The im2col form without prologue only (ParseNet's stride-2 convolutions).
+// of pieces 4 .. 7 fetch and stage nothing).  Without prologue only: the im2col form (ParseNet's stride-2 convolutions) and, with ONE, the GEMM
+// form (the detector's 1x1 convolutions, KEEP_CONV_X1_GEMM) -- the A fetch, the epilogue and split-K are the x3 GEMM form's, no in2.
 template <int WGM, int WGN, int TM, int TN, bool PLAIN, bool ONE = false, bool KSL = false, bool DEEP = true, bool KAL = false, bool X1 = false>
 __global__ __launch_bounds__(256) void conv_x3_kernel(ConvP p) {
-  static_assert(!X1 || (PLAIN && !ONE && !KSL && !KAL), "the single-fp16 form: im2col, no prologue, no K slices");
+  static_assert(!X1 || (PLAIN && !KSL && !KAL), "the single-fp16 forms: im2col or GEMM, no prologue, no K slices");
   constexpr int BM = WGM * TM * 32;
   constexpr int BN = WGN * TN * 32;
   constexpr int A_IT = BM / 64;             // (row, 8-channel group) pieces per thread: 4 groups per row
@@ -1345,6 +1346,12 @@ bool keep_conv_x1_gather_ok(const keep_conv2d_args* a, const ConvP& p) {
          !a->ln_gamma && a->Cin % 32 == 0;
 }
 
+// KEEP_MMA_X1 with KEEP_CONV_X1_GEMM: the GEMM form without prologue / second input / LayerNorm / aux, whole 32-channel K steps
+bool keep_conv_x1_gemm_ok(const keep_conv2d_args* a, const ConvP& p) {
+  return keep_conv_x3_gather_ok(a, p) && keep_conv_x3_gather_is_gemm(a) && !a->pro_scale && a->pro_act == KEEP_PRO_NONE && !a->in2 &&
+         !a->ln_gamma && !a->aux && a->Cin % 32 == 0;
+}
+
 bool keep_conv_x3p_ok(const keep_conv2d_args* a, const ConvP& p, int split_k);
 bool keep_conv_x3q_ok(const keep_conv2d_args* a, const ConvP& p, int split_k);
 bool keep_conv_x3p_full_ok(const keep_conv2d_args* a, const ConvP& p, int split_k);
@@ -1490,7 +1497,9 @@ int keep_conv2d_x3_gather(const keep_conv2d_args* a, ConvP& p, int tile, hipStre
   // 1x1 stride-1 unpadded convolutions (token GEMMs): block-relative buffer-load fetch, no im2col index arithmetic
   const bool one = keep_conv_x3_gather_is_gemm(a);
 #define KEEP_LAUNCH_GX(A, B, C, D)                                                                 \
-  if (a->mma == KEEP_MMA_X1)      /* (keep_conv_x1_gather_ok: plain im2col form) */                \
+  if (a->mma == KEEP_MMA_X1 && one)      /* (keep_conv_x1_gemm_ok: plain GEMM form) */             \
+    hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, true, true, false, true, false, true>), grid, block, 0, st, p); \
+  else if (a->mma == KEEP_MMA_X1) /* (keep_conv_x1_gather_ok: plain im2col form) */                \
     hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, true, false, false, true, false, true>), grid, block, 0, st, p); \
   else if (p.kslice_steps == 4 && plain && C * D == 1 && steps % 4 == 0)                                \
     hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, true, true, true, true, C * D == 1>), grid, block, 0, st, p); \

@@ -104,6 +104,9 @@ class Ops:
         self.blobx1 = None
         self._x1_table = None      # ([first element], [(first, one past the last)]) of the tensors blobx1 holds, sorted
         self._x1_route = {}        # plan key -> L.MMA_X1 | L.MMA_X3: one keep_conv2d_plan query per shape
+        # which calls the twin substitutes: 'stream' = KeepNet's rule (route_conv), 'admitted' = the detector's (route_conv_admitted:
+        # every call the library's plan admits under L.MMA_X1 with L.CONV_X1_GEMM -- 1x1 GEMMs, im2col shapes and the streaming 3x3 form)
+        self.x1_mode = 'stream'
         self.census = None         # when a dict: kernel name (plan string) -> launches, counted by conv() (tests, tools/bench_precision.py)
 
     def begin_forward(self, device):
@@ -135,7 +138,7 @@ class Ops:
         if x3_scales:
             self._x3_table = ([a for a, _, _ in x3_scales], list(x3_scales))
         self.mma = self.attn_mma = mma
-        self.blobx1, self._x1_table, self._x1_route = None, None, {}      # ('f16' re-attaches its twin after every policy change: set_x1_twin)
+        self.blobx1, self._x1_table, self._x1_route, self.x1_mode = None, None, {}, 'stream'      # ('f16' re-attaches its twin after every policy change: set_x1_twin)
         if blobx3 is not None and (blob32 is not self._up2_src[0] or blobx3 is not self._up2_src[1]):
             # phase kernels of the Upsample convolutions (up2_twin): derived from THESE blob objects -- a new upload, even one that lands
             # on the same addresses, starts from an empty cache; a policy switch on the same blobs keeps it (captured x3 graphs hold
@@ -143,12 +146,16 @@ class Ops:
             self._up2, self._up2_src = {}, (blob32, blobx3)
         self.blob32, self.blob16, self.blobx3, self.x3_acc_scale = blob32, blob16, blobx3, float(x3_acc_scale)
 
-    def set_x1_twin(self, blobx1=None, ranges=None):
+    def set_x1_twin(self, blobx1=None, ranges=None, mode='stream'):
         """'f16' on top of an x3 policy set by ``set_precision``: ``blobx1`` is ``make_x1_blob``'s hi-only twin (same per-tensor
-        power-of-two scales as the x3 twin), ``ranges`` its (first element, one past the last, 2^-e) table.  None: back to plain x3."""
+        power-of-two scales as the x3 twin), ``ranges`` its (first element, one past the last, 2^-e) table.  None: back to plain x3.
+        ``mode``: 'stream' (KeepNet: ``route_conv``) or 'admitted' (the detector: ``route_conv_admitted``)."""
         if blobx1 is not None and self.mma != L.MMA_X3:
             raise ValueError("set_x1_twin: the single-fp16 substitution rides on the x3 policy (set_precision(L.MMA_X3, ...) first)")
+        if mode not in ('stream', 'admitted'):
+            raise ValueError(f"set_x1_twin: unknown routing mode {mode!r}")
         self.blobx1 = blobx1
+        self.x1_mode = mode
         self._x1_table = None
         if blobx1 is not None:
             rows = sorted((int(a), int(b)) for a, b, _ in ranges)
@@ -184,6 +191,22 @@ class Ops:
                 except L.KeepHipError as e:
                     if '(code -2)' not in str(e):      # anything but KEEP_EUNSUP is an error, not an answer
                         raise
+            self._x1_route[key] = r
+        return r
+
+    def route_conv_admitted(self, key, x1_plan):
+        """The detector's 'f16' rule, sibling of ``route_conv``: L.MMA_X1 (with L.CONV_X1_GEMM) iff the library's plan admits the call
+        under it -- asked once per ``key`` -- and L.MMA_X3 otherwise (KEEP_EUNSUP is the library's answer, anything else an error).  The
+        plan follows the per-image geometry and the fixed reference batch: a frame's route never depends on its batch-mates."""
+        r = self._x1_route.get(key)
+        if r is None:
+            r = L.MMA_X3
+            try:
+                x1_plan()
+                r = L.MMA_X1
+            except L.KeepHipError as e:
+                if '(code -2)' not in str(e):
+                    raise
             self._x1_route[key] = r
         return r
 
@@ -330,6 +353,7 @@ class Ops:
         if ((mma == L.MMA_X3 and (wx3 is not None or (Cin <= 3 and KH == 3))) or mma == L.MMA_X1) and pro is None and not bounded:   # (RGB convs split fp32 weights in-kernel)
             in_amax = x_amax if (x_amax is not None and x_amax.numel() == N) else absmax(xin, N, H * W, Cin, ld, H * W * ld, self)
         out_ld = (Cout if out is None else out.shape[-1]) if out_ld is None else out_ld
+        flags = self.flags
 
         def make_args(inp, dtype, pro_t, pro_a, odt, sk):
             return L.conv_args(
@@ -343,13 +367,13 @@ class Ops:
                 x3_acc_scale=float(x3_acc_scale), x3_in_amax=in_amax, x3_out_amax=None,
                 in2=x2, in2_cin1=0 if x2 is None else ld, pad_mode=L.PAD_REFLECT if reflect else L.PAD_ZERO,
                 ln_gamma=None if ln is None else ln[0], ln_beta=None if ln is None else ln[1],
-                ln_eps=0.0 if ln is None else float(ln[2]), flags=self.flags, plan_ref_images=self.plan_ref_images)
+                ln_eps=0.0 if ln is None else float(ln[2]), flags=flags, plan_ref_images=self.plan_ref_images)
 
         def key_of(dtype, pro_t, pro_a, odt, sk):
             return (N, H, W, ld, Cin, Cout, KH, stride, pad_t, pad_l, Ho, Wo, out_ld, up_mode, pro_a, act, dtype, mma,
                     odt, sk, pro_t is not None, residual is not None, 0 if residual is None else residual.shape[-1],
                     aux is not None, bias is not None, in_off % 8, wx3 is not None, USE_BK256, x2 is not None, bool(reflect),
-                    ln is not None, self.flags, self.plan_ref_images)
+                    ln is not None, flags, self.plan_ref_images)
 
         sk_req = 0 if split_k is None else int(split_k)
         odt = L.BF16 if want_bf16_out else L.F32
@@ -364,17 +388,23 @@ class Ops:
             pro, pro_act, in_dtype = None, L.PRO_NONE, L.BF16
             a = make_args(xin, in_dtype, None, pro_act, odt, sk_req)
             pl = _plan(a, key_of(in_dtype, None, pro_act, odt, sk_req))
-        if self.blobx1 is not None and mma == L.MMA_X3 and self.mma == L.MMA_X3 and KH == 3 and wx3_own and x2 is None:
+        admitted = self.x1_mode == 'admitted'          # (the detector's rule: every kernel size; KeepNet's: the 3x3 streaming form)
+        if self.blobx1 is not None and mma == L.MMA_X3 and self.mma == L.MMA_X3 and (KH == 3 or admitted) and wx3_own and x2 is None:
             wx1 = self.x1_twin(w)                      # (a caller's own wx3 -- the phase weights of an Upsample -- stays x3)
             if wx1 is not None:
                 key3 = key_of(in_dtype, pro, pro_act, odt, sk_req)
-                keep = (mma, wx3)
+                keep = (mma, wx3, flags)
                 mma, wx3 = L.MMA_X1, wx1               # (make_args / key_of read these)
-                if self.route_conv(key3, pl, lambda: L.conv2d_plan(make_args(xin, in_dtype, pro, pro_act, odt, sk_req))) == L.MMA_X1:
+                if admitted:
+                    flags |= L.CONV_X1_GEMM
+
+                def x1_plan():
+                    return L.conv2d_plan(make_args(xin, in_dtype, pro, pro_act, odt, sk_req))
+                if (self.route_conv_admitted(key3, x1_plan) if admitted else self.route_conv(key3, pl, x1_plan)) == L.MMA_X1:
                     a = make_args(xin, in_dtype, pro, pro_act, odt, sk_req)
                     pl = _plan(a, key_of(in_dtype, pro, pro_act, odt, sk_req))
                 else:
-                    mma, wx3 = keep
+                    mma, wx3, flags = keep
         if want_bf16_out and not pl.out_bf16_ok:
             want_bf16_out, odt = False, L.F32
             a = make_args(xin, in_dtype, pro, pro_act, odt, sk_req)

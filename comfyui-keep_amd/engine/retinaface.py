@@ -47,6 +47,9 @@ MNET_STAGES = (('stage1', ((3, 8, 2), (8, 16, 1), (16, 32, 2), (32, 32, 1), (32,
                ('stage2', ((64, 128, 2),) + ((128, 128, 1),) * 5),
                ('stage3', ((128, 256, 2), (256, 256, 1))))
 BACKBONES = {'resnet50': CFG_RE50, 'mobile0.25': CFG_MNET}
+# matrix-core policies: 'x3' split fp16 (parity grade, the default), 'fp32' exact, 'f16' the opt-in single-fp16 speed mode (KEEP_MMA_X1,
+# outside bit-parity with the default like ParseNet's: DESIGN 4.3)
+PRECISIONS = ('x3', 'fp32', 'f16')
 
 
 def backbone_of(state_dict):
@@ -187,7 +190,11 @@ def nms(dets, thresh):
 
 
 class RetinaFaceEngine:
+    PRECISIONS = PRECISIONS
+
     def __init__(self, state_dict, precision='x3', backbone=None):
+        if precision not in PRECISIONS:
+            raise ValueError(f"RetinaFace precision must be one of {PRECISIONS}, got {precision!r}")
         self.backbone = backbone or backbone_of(state_dict)
         self.cfg = BACKBONES[self.backbone]
         # LeakyReLU(0.1) in the FPN / SSH when out_channel <= 64 (retinaface_net.py:41-43,74-76), ReLU (= LeakyReLU(0)) otherwise
@@ -263,12 +270,21 @@ class RetinaFaceEngine:
         self._dev = torch.from_numpy(self._blob).to(device)
         self.w = views(self._dev, self._index)
         self._mean = torch.tensor(MEAN_BGR, dtype=torch.float32, device=device)
-        if self.precision == 'x3':
+        if self.precision in ('x3', 'f16'):
             names = [n for n, (_, sh) in self._index.items() if len(sh) >= 2 and sh[-1] % 16 == 0 and not n.endswith('.dw.weight')]
             bx, table = ops.make_x3_blob(self._dev, self._index, self.w, names)       # one power-of-two scale per tensor
             self.o.set_precision(L.MMA_X3, self._dev, None, bx, 1.0, x3_scales=table)
-        else:
+            if self.precision == 'f16':
+                # an x3 Ops that also holds a hi-only twin of every matrix weight with whole 32-channel K steps: a call runs single-fp16
+                # wherever the library's plan admits it (1x1 GEMMs, stride-2 im2col shapes, 3x3 on 8 x 32-tileable maps), x3 otherwise;
+                # the Cin = 3 stems and mobile0.25's 8 / 16-channel layers have no twin, its depthwise convolutions are not matrix products
+                n1 = [n for n in names if self._index[n][1][-1] % 32 == 0]
+                b1, t1 = ops.make_x1_blob(self._dev, self._index, self.w, n1)
+                self.o.set_x1_twin(b1, t1, mode='admitted')
+        elif self.precision == 'fp32':
             self.o.set_precision(L.MMA_F32, self._dev, None)
+        else:
+            raise ValueError(f"RetinaFace precision must be one of {PRECISIONS}, got {self.precision!r}")
         return self
 
     # ------------------------------------------------------------------ network

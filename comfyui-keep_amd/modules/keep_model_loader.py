@@ -82,6 +82,20 @@ def parse_precision_knob(environ=None):
     return value
 
 
+def detect_precision_knob(environ=None):
+    """KEEP_AMD_DETECT_PRECISION=x3|fp32|f16 (default x3): the matrix-core policy of the engine-backed RetinaFace detectors (resnet50 and
+    mobile0.25), read ONCE when the pack's helper is built.  'f16' is the opt-in single-fp16 speed mode, outside bit-parity with the
+    default.  The YOLOv5-face engines have no such mode: they keep x3 and say so once (``engine_facelib``)."""
+    from ..engine.retinaface import PRECISIONS
+    value = (os.environ if environ is None else environ).get('KEEP_AMD_DETECT_PRECISION', '') or 'x3'
+    if value not in PRECISIONS:
+        raise ValueError(f"KEEP_AMD_DETECT_PRECISION must be one of {', '.join(PRECISIONS)}; got {value!r}")
+    return value
+
+
+_yolo_f16_warned = False
+
+
 def engine_facelib(helper):
     """put the helper's face-analysis networks on the HIP engine where an engine counterpart exists -- the
     objects keep the reference's call signatures (``face_parse(x)[0]``, ``face_detector.detect_faces(img)``), so
@@ -96,13 +110,17 @@ def engine_facelib(helper):
     det = getattr(helper, 'face_detector', None)
     if det is not None and hasattr(det, 'state_dict') and getattr(det, 'backbone', None) in ('Resnet50', 'mobilenet0.25'):
         from ..engine.retinaface import EngineRetinaFace
-        helper.face_detector = EngineRetinaFace.from_module(det)            # (the configuration is read off the state dict)
-        logger.debug("face_detector (RetinaFace %s) runs on the HIP engine", det.backbone)
+        helper.face_detector = EngineRetinaFace.from_module(det, precision=detect_precision_knob())      # (the configuration is read off the state dict)
+        logger.debug("face_detector (RetinaFace %s) runs on the HIP engine, precision %s", det.backbone, helper.face_detector.engine.precision)
     yolo = getattr(det, 'detector', None)                  # YoloDetector (YOLOv5l / YOLOv5n, detection/__init__.py:42-49): its network
     if yolo is not None and hasattr(yolo, 'state_dict') and 'model.0.stem_1.conv.weight' in yolo.state_dict():
         from ..engine.yoloface import EngineYoloModel
         from ..engine.yoloface import yolo_detect_batch
         det.detector = EngineYoloModel.from_module(yolo)    # pre / post-processing stay YoloDetector's own (face_detector.py)
+        global _yolo_f16_warned
+        if detect_precision_knob() == 'f16' and not _yolo_f16_warned:      # no silent policy change and no error: x3, said once
+            _yolo_f16_warned = True
+            logger.warning("KEEP_AMD_DETECT_PRECISION=f16 does not apply to the YOLOv5-face engines: they keep the x3 policy")
         if hasattr(det, '_preprocess') and hasattr(det, '_postprocess'):      # the processor's batched pre-pass (one network call per chunk)
             import functools
             det.detect_batch = functools.partial(yolo_detect_batch, det)

@@ -102,6 +102,16 @@ extern "C" {
 #define KEEP_CONV_GEMM_LAT_WAVES (1u << 11) /* canonical K slices: the one-wave-per-slice kernel (gemm_x3l_kernel) whatever the row count (same bits) */
 #define KEEP_CONV_NO_SMALL_PARTIALS (1u << 13) /* x3 3x3 split-K plans with few images: conv3x3_halo_x3_kernel's 256-pixel blocks instead of conv3x3_x3p_kernel (same partials) */
 #define KEEP_CONV_GEMM_LAT_TILES (1u << 12) /* canonical K slices: conv_x3_kernel with slice totals whatever the row count (same bits) */
+/* KEEP_CONV_X1_GEMM: the one bit that ADMITS a form instead of removing one (additive, same ABI version: without it every call means what it
+ * meant).  Read under KEEP_MMA_X1 only -- every other policy ignores it.  With it KEEP_MMA_X1 also takes the 1x1 stride-1 unpadded GEMM form
+ * (conv_x3_kernel's GEMM variant, one fp16 MFMA per product): Cin % 32 == 0, the hi-only twin and x3_acc_scale given, no prologue / in2 /
+ * ln_gamma / aux; bias, epilogue activations, residual (res_ld), out_ld slices, x3_in_amax, x3_out_amax, statistics and split-K as in the x3
+ * GEMM form, tile and split-K planned by the x3 rules from plan_ref_images (never from N).  The latency form (gemm_x3l_kernel) has no x1
+ * twin: a shape KEEP_MMA_X3 would send there runs on this tile kernel instead.  The bit also opens the im2col form to the 3x3 stride-1 pad-1
+ * convolutions that no halo kernel tiles (maps that are neither 8 x 32 nor 16 x 16 tileable, e.g. a 1080p frame's 135 x 240: KEEP_MMA_X3 runs
+ * the same im2col kernel there), without prologue.  Everything else stays refused (KEEP_EUNSUP, keep_last_error).
+ * The detector's opt-in precision 'f16' (engine/retinaface.py) sets it. */
+#define KEEP_CONV_X1_GEMM (1u << 14)
 /* keep_attention_args.flags (v18) */
 #define KEEP_ATTN_NO_PACK (1u << 0)   /* x3: never pre-pack K / V^T (keep_attention_workspace_bytes answers 0) */
 #define KEEP_ATTN_NO_SFULL2 (1u << 1) /* x3, D = 512: the 128-query kernel instead of the 32-query one */
