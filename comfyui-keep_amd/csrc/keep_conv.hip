@@ -1703,6 +1703,7 @@ bool keep_conv_x3_gather_ok(const keep_conv2d_args* a, const ConvP& p);
 bool keep_conv_x1_stream_ok(const keep_conv2d_args* a, const ConvP& p);
 bool keep_conv_x1_gather_ok(const keep_conv2d_args* a, const ConvP& p);
 bool keep_conv_x1_gemm_ok(const keep_conv2d_args* a, const ConvP& p);
+bool keep_conv_x1_halo16_ok(const keep_conv2d_args* a);
 bool keep_gemm_x3l_ok(const keep_conv2d_args* a);
 int keep_gemm_x3l_waves(const keep_conv2d_args* a);
 int keep_conv2d_x3_gemm_lat(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
@@ -1890,6 +1891,27 @@ static int plan_conv(const keep_conv2d_args* a, ConvP& p, ConvPlan& pl) {
       snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_x3s_kernel<%d, %s, true>", a->pro_act, a->pro_scale ? "true" : "false");
       return KEEP_OK;
     }
+    // KEEP_CONV_X1_HALO16 (opt-in bit, like KEEP_CONV_X1_GEMM below: without it nothing changes): the x1 instantiation of the 16 x 16-tile halo
+    // kernel for the maps the streaming form does not tile.  Only where the x3 plan of the same call -- the rule of the KEEP_MMA_X3 branch below,
+    // from the reference batch, never from N -- is un-split: the form has no split-K, and a call x3 splits keeps x3's partition.
+    if ((a->flags & KEEP_CONV_X1_HALO16) && have_w && is33s1 && keep_conv_x1_halo16_ok(a) && !(a->flags & KEEP_CONV_NO_HALO_X3)) {
+      const long items = (M / 256) * ncb;
+      auto_split = items >= 256 ? 1 : (int)max(1L, min(min(512L / items, (long)a->Cin / 32), 16L));
+      int x3_split = a->split_k > 0 ? a->split_k : auto_split;
+      if (x3_split > a->Cin / 16) x3_split = a->Cin / 16;
+      if (x3_split == 1) {
+        pl.path = PATH_HALO_X3;
+        pl.split_k = 1;
+        pl.stats_rows = 256;
+        pl.amax_ok = true;
+        // (<TW, PRO, SIMPLE_EPI, FASTACT, WDMA, UP2, X1> as rocprofv3 prints it)
+        snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_x3_kernel<16, 0, %s, true, true, false, true>", a->epi_act == KEEP_ACT_NONE ? "true" : "false");
+        return KEEP_OK;
+      }
+      keep_set_error("keep_conv2d: KEEP_MMA_X1 (with KEEP_CONV_X1_HALO16) has no kernel for this call: KEEP_MMA_X3 plans it with split-K = %d "
+                     "(plan_ref_images = %ld) and the 16 x 16-tile single-fp16 form is un-split", x3_split, plan_ref_images(a));
+      return KEEP_EUNSUP;
+    }
     // (under KEEP_CONV_X1_GEMM also a 3x3 stride-1 pad-1 convolution NO halo kernel takes -- a ragged map, where x3 itself runs this im2col kernel)
     if (have_w && (!is33s1 || ((a->flags & KEEP_CONV_X1_GEMM) && !keep_conv_x3_halo_ok(a))) && keep_conv_x1_gather_ok(a, p) &&
         !(a->flags & KEEP_CONV_NO_GATHER_X3)) {
@@ -1928,10 +1950,26 @@ static int plan_conv(const keep_conv2d_args* a, ConvP& p, ConvPlan& pl) {
         snprintf(pl.kernel, sizeof(pl.kernel), "conv_x3_kernel<%s, true, 1, 0, 1, 0, 1>", pl.tile == 1 ? "2, 2, 1, 1" : "2, 2, 2, 2");
         return KEEP_OK;
       }
+      if (a->flags & KEEP_CONV_X1_HALO16) {
+        keep_set_error("keep_conv2d: KEEP_MMA_X1 (with KEEP_CONV_X1_HALO16) has no kernel for this call: it needs weight_x3 (the hi-only fp16 twin) and "
+                       "x3_acc_scale, Cin %% 32 == 0, no aux / in2 / LayerNorm, and one of: a 3x3 stride-1 pad-1 convolution on a map of 8 x 32 tiles "
+                       "without split-K (raw inputs or the streaming kernel's prologue forms), the same on a map of 16 x 16 tiles that is not 8 x 32 "
+                       "tileable (raw inputs, zero padding, no upsample, un-split under KEEP_MMA_X3), an im2col shape without prologue, or -- with "
+                       "KEEP_CONV_X1_GEMM -- a 1x1 stride-1 unpadded GEMM without prologue");
+        return KEEP_EUNSUP;
+      }
       keep_set_error("keep_conv2d: KEEP_MMA_X1 (with KEEP_CONV_X1_GEMM) has no kernel for this call: it needs weight_x3 (the hi-only fp16 twin) and "
                      "x3_acc_scale, Cin %% 32 == 0, no aux / in2 / LayerNorm, and one of: a 3x3 stride-1 pad-1 convolution on a map of 8 x 32 tiles "
                      "without split-K (raw inputs or the streaming kernel's prologue forms), an im2col shape without prologue (a 3x3 stride-1 pad-1 "
                      "convolution only on a map no halo kernel tiles), or a 1x1 stride-1 unpadded GEMM without prologue");
+      return KEEP_EUNSUP;
+    }
+    if (a->flags & KEEP_CONV_X1_HALO16) {
+      keep_set_error("keep_conv2d: KEEP_MMA_X1 (with KEEP_CONV_X1_HALO16) has no kernel for this call: it needs weight_x3 (the hi-only fp16 twin) and "
+                     "x3_acc_scale, Cin %% 32 == 0, no aux / in2 / LayerNorm, and one of: a 3x3 stride-1 pad-1 convolution on a map of 8 x 32 tiles "
+                     "without split-K (raw inputs or the streaming kernel's prologue forms), the same on a map of 16 x 16 tiles that is not 8 x 32 "
+                     "tileable (raw inputs, zero padding, no upsample, un-split under KEEP_MMA_X3), an im2col shape without prologue, or -- with "
+                     "KEEP_CONV_X1_GEMM -- a 1x1 stride-1 unpadded GEMM without prologue");
       return KEEP_EUNSUP;
     }
     keep_set_error("keep_conv2d: KEEP_MMA_X1 has no kernel for this call: it needs weight_x3 (the hi-only fp16 twin) and x3_acc_scale, Cin %% 32 == 0, no "

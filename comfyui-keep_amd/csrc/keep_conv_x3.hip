@@ -82,11 +82,22 @@ __device__ __forceinline__ float xor32_sum(float x) {
 //   ([phase][Cout][9 taps][Cin/16][hi16|lo16], unused taps zero and never fetched); an item is (source tile, phase, cout block), its
 //   MFMA loop is compiled per phase (static tap list), its epilogue scatters to the stride-2 output pixels.  Tiles, halo and
 //   addressing are those of a plain 3x3 convolution on the source (p.upsample = 0, p.Ho / p.Wo = the OUTPUT extent).
-template <int TW, int PRO, bool SIMPLE_EPI, bool FASTACT = true, bool WDMA = false, bool UP2 = false>
+// X1 (KEEP_MMA_X1 behind KEEP_CONV_X1_HALO16): operands rounded once to fp16, one MFMA per product.  A chunk is 32 channels: a
+//   halo row holds [ch 0..15 | ch 16..31] where the x3 form holds [hi x16 | lo x16] and a weight row (p.wx3 = the hi-only twin, plain
+//   [Cout][9][Cin] fp16) its 64 bytes of 32 channels where the x3 row holds hi | lo of 16 -- the LDS image, the DMA instructions and the 8
+//   fragment reads of a tap are the x3 form's, and feed 8 MFMAs (two K steps) for 32 channels where x3 issues 12 for 16.  No `lo` half is
+//   converted, staged or read: the bytes it would take carry the second 16 channels (half the chunks, barriers and fragment reads per
+//   channel).  A thread stages 8-byte pieces (4 channels of a pixel, 8 threads per pixel).  16 x 16 tiles, raw input, zero padding, un-split.
+template <int TW, int PRO, bool SIMPLE_EPI, bool FASTACT = true, bool WDMA = false, bool UP2 = false, bool X1 = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int tiles_x, int tiles_y, int ncb, int n_items) {
   static_assert(!UP2 || (TW == 32 && WDMA && SIMPLE_EPI && PRO == KEEP_PRO_NONE), "UP2: wide tiles, DMA weights, simple epilogue, no prologue");
+  static_assert(!X1 || (TW == 16 && WDMA && !UP2 && FASTACT && PRO == KEEP_PRO_NONE), "X1: 16 x 16 tiles, DMA weights, raw input");
+  constexpr int PSH = X1 ? 3 : 2;                       // log2(staging pieces per halo pixel): 32 channels (X1) or 16 of 4 floats each
+  constexpr int CSH = X1 ? 5 : 4;                       // log2(channels per chunk)
+  constexpr int WB = X1 ? 2 : 4;                        // bytes per weight in p.wx3
   constexpr int HALO_TH = 256 / TW, HALO_W = TW + 2, HALO_PIX = (HALO_TH + 2) * HALO_W;
   constexpr int RPT = 32 / TW;
+  constexpr int HIT = X1 ? (HALO_PIX * 8 + 255) / 256 : HALO_IT;      // staging pieces per thread
   constexpr int MAIN_B = (HALO_MAXPIX + 9 * 64) * XPITCH * 2;
   constexpr int EPI_B = 4 * 64 * 68 * 4;
   __shared__ __attribute__((aligned(16))) unsigned char lds_raw[MAIN_B > EPI_B ? MAIN_B : EPI_B];
@@ -102,21 +113,21 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
   const int items_per_z = n_items / p.split_k;
   const int Hv = p.upsample ? 2 * p.H : p.H;
   const int Wv = p.upsample ? 2 * p.W : p.W;
-  const int g = tid & 3;
-  const bool has_pro = p.pro_scale != nullptr || PRO != KEEP_PRO_NONE;
+  const int g = tid & ((1 << PSH) - 1);
+  const bool has_pro = !X1 && (p.pro_scale != nullptr || PRO != KEEP_PRO_NONE);
 
   // Operand fetch through buffer descriptors: ONE buffer_load_dwordx4 per 16-byte piece, no 64-bit address arithmetic and no
   // EXEC branches -- a padding pixel / a cout row beyond Cout carries the out-of-range offset -16 and the hardware returns
   // zeros (bounds check on voffset; the channel / tap displacement rides in the scalar offset).  (The flat-load form spent
   // ~185 instructions per chunk here, 15 % of the wave's time by the s_memtime timeline.)
-  int h_voff[HALO_IT];                   // byte offset of this thread's piece inside the image; < 0: zero padding
+  int h_voff[HIT];                   // byte offset of this thread's piece inside the image; < 0: zero padding
   int w_voff = -16;                      // byte offset of this thread's piece of its cout row in the split weight tensor
   int dma_voff[4] = {-16, -16, -16, -16};   // WDMA: this lane's source offset for the four 16-cout row groups of a tap
   long sc_off = 0;
   float in_s = 1.f, in_inv = 1.f;        // range scale of the item being FETCHED / staged (image it.n)
   __amdgpu_buffer_rsrc_t in_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, 0, 0x00020000);
   const __amdgpu_buffer_rsrc_t w_rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.wx3, 0, (UP2 ? 4 : 1) * p.Cout * 9 * p.Cin * 4, 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc((void*)p.wx3, 0, (UP2 ? 4 : 1) * p.Cout * 9 * p.Cin * WB, 0x00020000);
   const int cout_rows = (UP2 ? 4 : 1) * p.Cout;      // weight rows (UP2: four phase kernels)
   const int ncb_real = p.Cout >> 6;                  // UP2: cout blocks per phase (Cout % 64 == 0)
   float4 bias_nx = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -124,8 +135,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
   auto setup = [&](const HaloItem& it) {
     if (p.in_amax) amax_raw = p.in_amax[it.n];      // turned into (in_s, in_inv) at the top of the item: the load has an epilogue to land
 #pragma unroll
-    for (int k = 0; k < HALO_IT; ++k) {
-      const int hp = (tid >> 2) + k * 64;
+    for (int k = 0; k < HIT; ++k) {
+      const int hp = (tid >> PSH) + k * (256 >> PSH);
       h_voff[k] = -16;
       if (hp < HALO_PIX) {
         const int hy = hp / HALO_W, hx = hp - hy * HALO_W;
@@ -143,7 +154,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
     sc_off = (long)it.n * p.Cin + g * 4;
     bias_nx = make_float4(0.f, 0.f, 0.f, 0.f);       // bias of the item's cout block for this lane's four epilogue channels: in flight
     const int n0r = UP2 ? ((it.n0 >> 6) % ncb_real) << 6 : it.n0;          // real cout of the block's first channel
-    if (p.bias && p.split_k == 1 && n0r + (lane & 15) * 4 < p.Cout)      // over a whole item (loaded in the epilogue it was waited for at once)
+    if (p.bias && (X1 || p.split_k == 1) && n0r + (lane & 15) * 4 < p.Cout)      // over a whole item (loaded in the epilogue it was waited for at once)
       bias_nx = *reinterpret_cast<const float4*>(p.bias + n0r + (lane & 15) * 4);
     w_voff = (it.n0 + (tid >> 2)) < cout_rows ? ((it.n0 + (tid >> 2)) * 9 * p.Cin * 2 + g * 8) * 2 : -16;
     if (WDMA) {
@@ -154,18 +165,18 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int co = it.n0 + ((wave + j) & 3) * 16 + (lane >> 2);
-        dma_voff[j] = co < cout_rows ? co * 9 * p.Cin * 4 + lp * 16 : -16;
+        dma_voff[j] = co < cout_rows ? co * 9 * p.Cin * WB + lp * 16 : -16;
       }
     }
   };
 
-  float4 hreg[HALO_IT];
+  float4 hreg[HIT];
   uint4 wr0, wr1, wr2, wr3, wr4, wr5, wr6, wr7, wr8;
   float4 sc4 = make_float4(1.f, 1.f, 1.f, 1.f), sh4 = make_float4(0.f, 0.f, 0.f, 0.f);
   auto fetch = [&](int ch) {
-    const int c0 = ch << 4;
+    const int c0 = ch << CSH;
 #pragma unroll
-    for (int k = 0; k < HALO_IT; ++k) {
+    for (int k = 0; k < HIT; ++k) {
       const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(in_rsrc, h_voff[k], c0 * 4, 0);
       hreg[k] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
     }
@@ -187,13 +198,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
   int up_par = 0, up_mask = 0x1ff;       // UP2: phase (py * 2 + px) and tap set of the CURRENT item
   auto stage = [&]() {
     if (WDMA) {      // weights of the chunk being staged: L2 -> LDS, in flight under the halo's VALU work below
-      const int c0 = fetched_ch << 4;
+      const int c0 = fetched_ch << CSH;
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
         const int q = __builtin_amdgcn_readfirstlane(wave) * 9 + t;            // wave-uniform (M0 / soffset operands)
         if (UP2 && !((up_mask >> (q >> 2)) & 1)) continue;                      // a tap this phase does not use: never fetched
         __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (__attribute__((address_space(3))) void*)(wdma_base + q * 1024), 16,
-                                                 dma_voff[t & 3], ((q >> 2) * p.Cin + c0) * 4, 0, 0);
+                                                 dma_voff[t & 3], ((q >> 2) * p.Cin + c0) * WB, 0, 0);
       }
     }
     // GroupNorm affine + activation + split of this thread's 16-byte pieces, two values per instruction where the ISA has a packed
@@ -205,11 +216,20 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
     const f32x2 nsc01 = sc01 * -1.4426950408889634f, nsc23 = sc23 * -1.4426950408889634f;
     const f32x2 nsh01 = sh01 * -1.4426950408889634f, nsh23 = sh23 * -1.4426950408889634f;
 #pragma unroll
-    for (int k = 0; k < HALO_IT; ++k) {
-      const int hp = (tid >> 2) + k * 64;
+    for (int k = 0; k < HIT; ++k) {
+      const int hp = (tid >> PSH) + k * (256 >> PSH);
       if (hp < HALO_PIX) {
         _Float16* dst = &Hs[hp * XPITCH + g * 4];
-        if (!has_pro || h_voff[k] >= 0) {
+        if (X1) {      // rounded once: channels g * 4 .. + 3 of the 32-channel row (a padding pixel was fetched as zeros)
+          f32x2 v01 = {hreg[k].x, hreg[k].y}, v23 = {hreg[k].z, hreg[k].w};
+          if (p.in_amax) {
+            v01 *= in_s;
+            v23 *= in_s;
+          }
+          const f16x2 h01 = __builtin_convertvector(v01, f16x2), h23 = __builtin_convertvector(v23, f16x2);
+          const f16x4 hi = {h01.x, h01.y, h23.x, h23.y};
+          *reinterpret_cast<f16x4*>(dst) = hi;
+        } else if (!has_pro || h_voff[k] >= 0) {
           f32x2 v01 = {hreg[k].x, hreg[k].y}, v23 = {hreg[k].z, hreg[k].w};
           if (has_pro) {
             const f32x2 y01 = v01 * sc01 + sh01, y23 = v23 * sc23 + sh23;
@@ -288,7 +308,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
         for (int i = 0; i < 2; ++i)
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
-            MMA_X3(acc[i][j], ah[i], al[i], bh[j], bl[j])
+            if (X1) {      // (ah | al) = channels 0 .. 15 | 16 .. 31 of the chunk, (bh | bl) alike: two K steps
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bl[j], acc[i][j], 0, 0, 0);
+            } else {
+              MMA_X3(acc[i][j], ah[i], al[i], bh[j], bl[j])
+            }
           }
       }
     }
@@ -344,7 +369,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
     if (HAS_RES) {
       res_rsrc = make_rsrc(p.res + (long)it.n * hw_o * p.res_ld, hw_o * p.res_ld * 4);
       v_res = cok ? (pix_b * p.res_ld + co) * 4 : -16;
-      if (!SIMPLE_EPI && p.aux) {
+      if (!X1 && !SIMPLE_EPI && p.aux) {
         aux_rsrc = make_rsrc(p.aux + (long)it.n * hw_o * p.Cout, hw_o * p.Cout * 4);
         v_aux = cok ? (pix_b * p.Cout + co) * 4 : -16;
       }
@@ -371,17 +396,17 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
     u32x4 rgrp[4], agrp[4];
 #pragma unroll UNR
     for (int q16 = 0; q16 < 16; ++q16) {
-      if (!SIMPLE_EPI && HAS_RES && (q16 & 3) == 0 && p.split_k == 1) {
+      if (!SIMPLE_EPI && HAS_RES && (q16 & 3) == 0 && (X1 || p.split_k == 1)) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
           rgrp[u] = __builtin_amdgcn_raw_buffer_load_b128(res_rsrc, v_res, dpix_of(q16 + u) * p.res_ld * 4, 0);
-          if (p.aux) agrp[u] = __builtin_amdgcn_raw_buffer_load_b128(aux_rsrc, v_aux, dpix_of(q16 + u) * p.Cout * 4, 0);
+          if (!X1 && p.aux) agrp[u] = __builtin_amdgcn_raw_buffer_load_b128(aux_rsrc, v_aux, dpix_of(q16 + u) * p.Cout * 4, 0);
         }
       }
       const int px = q16 * 4 + prow;
       const int dpix = dpix_of(q16);
       const float4 v = *reinterpret_cast<const float4*>(et + px * EP + c4);
-      if (!SIMPLE_EPI && p.split_k > 1) {
+      if (!X1 && !SIMPLE_EPI && p.split_k > 1) {
         if (cok) {
           const long m = (long)it.n * hw_o + pix_b + dpix;
           *reinterpret_cast<float4*>(p.ws + ((long)it.z * p.M + m) * p.Cout + co) = make_float4(v.x * asc, v.y * asc, v.z * asc, v.w * asc);
@@ -397,7 +422,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
       if (HAS_RES) {
         const u32x4 r4 = SIMPLE_EPI ? rpre[SIMPLE_EPI ? q16 : 0] : rgrp[q16 & 3];
         const float rr[4] = {__uint_as_float(r4.x), __uint_as_float(r4.y), __uint_as_float(r4.z), __uint_as_float(r4.w)};
-        if (!SIMPLE_EPI && p.aux) {
+        if (!X1 && !SIMPLE_EPI && p.aux) {
           const u32x4 a4 = agrp[q16 & 3];
           const float aa[4] = {__uint_as_float(a4.x), __uint_as_float(a4.y), __uint_as_float(a4.z), __uint_as_float(a4.w)};
 #pragma unroll
@@ -454,7 +479,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
   float amax_run = 0.f;
   int item = blockIdx.x;
   if (item >= n_items) return;
-  HaloItem cur = halo_decode<TW, 4>(p, item, items_per_z, tiles_x, tiles_y, ncb);
+  HaloItem cur = halo_decode<TW, CSH>(p, item, items_per_z, tiles_x, tiles_y, ncb);
   setup(cur);
   if (cur.ch_begin < cur.ch_end) fetch(cur.ch_begin);
   while (true) {
@@ -488,7 +513,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3_kernel(ConvP p, int ti
     const float4 cur_bias = bias_nx;
     HaloItem nxt = cur;
     if (has_next) {
-      nxt = halo_decode<TW, 4>(p, next_item, items_per_z, tiles_x, tiles_y, ncb);
+      nxt = halo_decode<TW, CSH>(p, next_item, items_per_z, tiles_x, tiles_y, ncb);
       setup(nxt);
       if (nxt.ch_begin < nxt.ch_end) fetch(nxt.ch_begin);     // in flight during the epilogue below
     }
@@ -1346,6 +1371,21 @@ bool keep_conv_x1_gather_ok(const keep_conv2d_args* a, const ConvP& p) {
          !a->ln_gamma && a->Cin % 32 == 0;
 }
 
+// KEEP_MMA_X1 with KEEP_CONV_X1_HALO16: the 16 x 16-tile halo kernel's X1 form -- a map the streaming form does not tile, raw input, zero
+// padding, whole 32-channel chunks, no aux / second input / upsample (plan_conv adds: the x3 plan of the call is un-split).  The addressing
+// limits of keep_conv_x3_halo_ok(); Cout in whole float4 groups (the epilogue's granularity -- cout rows past Cout are fetched as zeros and
+// never stored), not x3's 32.
+bool keep_conv_x1_halo16_ok(const keep_conv2d_args* a) {
+  return a->dtype == KEEP_F32 && a->out_dtype != KEEP_BF16 && a->KH == 3 && a->KW == 3 && a->stride == 1 && a->pad_t == 1 && a->pad_l == 1 &&
+         a->pad_mode == KEEP_PAD_ZERO && !a->upsample && a->Ho == a->H && a->Wo == a->W && a->Ho % 16 == 0 && a->Wo % 16 == 0 &&
+         !(a->Ho % 8 == 0 && a->Wo % 32 == 0) && a->Cin % 32 == 0 && a->Cout % 4 == 0 && !a->pro_scale && a->pro_act == KEEP_PRO_NONE &&
+         !a->aux && !a->in2 && !a->ln_gamma &&
+         (long)a->H * a->W * a->in_ld * 4 < (1L << 31) && (long)a->Cout * 9 * a->Cin * 2 < (1L << 31) &&   // buffer offsets
+         (long)a->Ho * a->Wo * a->out_ld * 4 < (1L << 31) && (long)a->Ho * a->Wo * (a->residual ? a->res_ld : 1) * 4 < (1L << 31) &&
+         (a->in_ld % 4 == 0) && ((uintptr_t)a->in % 16 == 0) && (a->out_ld % 4 == 0) && ((uintptr_t)a->out % 16 == 0) &&
+         (!a->residual || (a->res_ld % 4 == 0 && (uintptr_t)a->residual % 16 == 0)) && (!a->bias || (uintptr_t)a->bias % 16 == 0);
+}
+
 // KEEP_MMA_X1 with KEEP_CONV_X1_GEMM: the GEMM form without prologue / second input / LayerNorm / aux, whole 32-channel K steps
 bool keep_conv_x1_gemm_ok(const keep_conv2d_args* a, const ConvP& p) {
   return keep_conv_x3_gather_ok(a, p) && keep_conv_x3_gather_is_gemm(a) && !a->pro_scale && a->pro_act == KEEP_PRO_NONE && !a->in2 &&
@@ -1372,7 +1412,20 @@ int keep_conv2d_x3_halo(const keep_conv2d_args* a, ConvP& p, hipStream_t st) {
     KEEP_LAUNCH_CHECK("keep_conv2d(halo x3, x2 phases)");
     return KEEP_OK;
   }
-  if (a->mma == KEEP_MMA_X1) return keep_conv2d_x3_stream(a, p, x3_num_cu(), st);      // (plan_conv: keep_conv_x1_stream_ok, split_k == 1)
+  if (a->mma == KEEP_MMA_X1 && a->Ho % 8 == 0 && a->Wo % 32 == 0) return keep_conv2d_x3_stream(a, p, x3_num_cu(), st);      // (plan_conv: keep_conv_x1_stream_ok, split_k == 1)
+  if (a->mma == KEEP_MMA_X1) {      // (plan_conv: keep_conv_x1_halo16_ok -- 16 x 16 tiles, raw input, zero padding, un-split)
+    const int tiles_x = a->Wo / 16, tiles_y = a->Ho / 16, ncb = (a->Cout + 63) / 64;
+    const int n_items = a->N * tiles_x * tiles_y * ncb;
+    const int n_cu = x3_num_cu();
+    dim3 grid(n_items < 2 * n_cu ? n_items : 2 * n_cu), block(256);
+    p.split_k = 1;
+    if (a->epi_act == KEEP_ACT_NONE)
+      hipLaunchKernelGGL((conv3x3_halo_x3_kernel<16, KEEP_PRO_NONE, true, true, true, false, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
+    else
+      hipLaunchKernelGGL((conv3x3_halo_x3_kernel<16, KEEP_PRO_NONE, false, true, true, false, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
+    KEEP_LAUNCH_CHECK("keep_conv2d(halo x1, 16 x 16 tiles)");
+    return KEEP_OK;
+  }
   const int nchunks = a->Cin / 16;
   if (p.split_k > nchunks) p.split_k = nchunks;
   if (keep_conv_x3p_ok(a, p, p.split_k)) return keep_conv2d_x3_partials(a, p, st);                        // keep_conv_x3p.hip (few images: 64-pixel tiles, same partials)

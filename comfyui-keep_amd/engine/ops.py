@@ -107,6 +107,7 @@ class Ops:
         # which calls the twin substitutes: 'stream' = KeepNet's rule (route_conv), 'admitted' = the detector's (route_conv_admitted:
         # every call the library's plan admits under L.MMA_X1 with L.CONV_X1_GEMM -- 1x1 GEMMs, im2col shapes and the streaming 3x3 form)
         self.x1_mode = 'stream'
+        self.x1_flags = L.CONV_X1_GEMM      # 'admitted': the opt-in form bits the X1 plan is asked with (YOLOv5-face adds L.CONV_X1_HALO16)
         self.census = None         # when a dict: kernel name (plan string) -> launches, counted by conv() (tests, tools/bench_precision.py)
 
     def begin_forward(self, device):
@@ -138,7 +139,7 @@ class Ops:
         if x3_scales:
             self._x3_table = ([a for a, _, _ in x3_scales], list(x3_scales))
         self.mma = self.attn_mma = mma
-        self.blobx1, self._x1_table, self._x1_route, self.x1_mode = None, None, {}, 'stream'      # ('f16' re-attaches its twin after every policy change: set_x1_twin)
+        self.blobx1, self._x1_table, self._x1_route, self.x1_mode, self.x1_flags = None, None, {}, 'stream', L.CONV_X1_GEMM      # ('f16' re-attaches its twin after every policy change: set_x1_twin)
         if blobx3 is not None and (blob32 is not self._up2_src[0] or blobx3 is not self._up2_src[1]):
             # phase kernels of the Upsample convolutions (up2_twin): derived from THESE blob objects -- a new upload, even one that lands
             # on the same addresses, starts from an empty cache; a policy switch on the same blobs keeps it (captured x3 graphs hold
@@ -146,16 +147,18 @@ class Ops:
             self._up2, self._up2_src = {}, (blob32, blobx3)
         self.blob32, self.blob16, self.blobx3, self.x3_acc_scale = blob32, blob16, blobx3, float(x3_acc_scale)
 
-    def set_x1_twin(self, blobx1=None, ranges=None, mode='stream'):
+    def set_x1_twin(self, blobx1=None, ranges=None, mode='stream', flags=L.CONV_X1_GEMM):
         """'f16' on top of an x3 policy set by ``set_precision``: ``blobx1`` is ``make_x1_blob``'s hi-only twin (same per-tensor
         power-of-two scales as the x3 twin), ``ranges`` its (first element, one past the last, 2^-e) table.  None: back to plain x3.
-        ``mode``: 'stream' (KeepNet: ``route_conv``) or 'admitted' (the detector: ``route_conv_admitted``)."""
+        ``mode``: 'stream' (KeepNet: ``route_conv``) or 'admitted' (the detectors: ``route_conv_admitted``); ``flags``: the opt-in form
+        bits an 'admitted' plan query carries (RetinaFace: L.CONV_X1_GEMM, the default; YOLOv5-face adds L.CONV_X1_HALO16)."""
         if blobx1 is not None and self.mma != L.MMA_X3:
             raise ValueError("set_x1_twin: the single-fp16 substitution rides on the x3 policy (set_precision(L.MMA_X3, ...) first)")
         if mode not in ('stream', 'admitted'):
             raise ValueError(f"set_x1_twin: unknown routing mode {mode!r}")
         self.blobx1 = blobx1
         self.x1_mode = mode
+        self.x1_flags = int(flags)
         self._x1_table = None
         if blobx1 is not None:
             rows = sorted((int(a), int(b)) for a, b, _ in ranges)
@@ -195,7 +198,7 @@ class Ops:
         return r
 
     def route_conv_admitted(self, key, x1_plan):
-        """The detector's 'f16' rule, sibling of ``route_conv``: L.MMA_X1 (with L.CONV_X1_GEMM) iff the library's plan admits the call
+        """The detector's 'f16' rule, sibling of ``route_conv``: L.MMA_X1 (with the form bits of ``set_x1_twin``) iff the library's plan admits the call
         under it -- asked once per ``key`` -- and L.MMA_X3 otherwise (KEEP_EUNSUP is the library's answer, anything else an error).  The
         plan follows the per-image geometry and the fixed reference batch: a frame's route never depends on its batch-mates."""
         r = self._x1_route.get(key)
@@ -396,7 +399,7 @@ class Ops:
                 keep = (mma, wx3, flags)
                 mma, wx3 = L.MMA_X1, wx1               # (make_args / key_of read these)
                 if admitted:
-                    flags |= L.CONV_X1_GEMM
+                    flags |= self.x1_flags
 
                 def x1_plan():
                     return L.conv2d_plan(make_args(xin, in_dtype, pro, pro_act, odt, sk_req))

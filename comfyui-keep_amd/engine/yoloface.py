@@ -137,11 +137,19 @@ def config_of(state_dict):
     return 'YOLOv5n' if 'model.1.branch1.0.weight' in keys else 'YOLOv5l'
 
 
+# matrix-core policies: 'x3' split fp16 (parity grade, the default), 'fp32' exact, 'f16' the opt-in single-fp16 speed mode (KEEP_MMA_X1,
+# outside bit-parity with the default like RetinaFace's: DESIGN 4.4)
+PRECISIONS = ('x3', 'fp32', 'f16')
+
+
 class YoloFaceEngine:
     """``bn_eps``: name of a BatchNorm -> its eps (the reference's Model keeps torch's 1e-5; checkpoints of the upstream trainer were
     made with 1e-3 -- ``EngineYoloModel.from_module`` reads the value off every module)."""
+    PRECISIONS = PRECISIONS
 
     def __init__(self, state_dict, precision='x3', bn_eps=None):
+        if precision not in PRECISIONS:
+            raise ValueError(f"YOLOv5-face precision must be one of {PRECISIONS}, got {precision!r}")
         self.name = config_of(state_dict)
         spec = yolo_state_dict_spec(self.name)
         missing = [k for k in spec if k not in state_dict]
@@ -216,13 +224,23 @@ class YoloFaceEngine:
         self.device = device
         self._dev = torch.from_numpy(self._blob).to(device)
         self.w = views(self._dev, self._index)
-        if self.precision == 'x3':
+        if self.precision in ('x3', 'f16'):
             names = [n for n, (_, sh) in self._index.items() if len(sh) >= 2 and sh[-1] % 16 == 0 and n.endswith('.weight')
                      and n[:-7] not in self._dw and n != 'anchor_grid']
             bx, table = ops.make_x3_blob(self._dev, self._index, self.w, names)
             self.o.set_precision(L.MMA_X3, self._dev, None, bx, 1.0, x3_scales=table)
-        else:
+            if self.precision == 'f16':
+                # an x3 Ops that also holds a hi-only twin of every matrix weight with whole 32-channel K steps: a call runs single-fp16
+                # wherever the library's plan admits it (1x1 GEMMs, stride-2 im2col shapes, 3x3 on 8 x 32 tiles, and -- KEEP_CONV_X1_HALO16
+                # -- on 16 x 16 tiles: the 48 x 80 stride-16 level of a 720p frame's 768 x 1280 letterbox), x3 otherwise; the Cin = 3 stem has no twin, the
+                # depthwise convolutions are not matrix products
+                n1 = [n for n in names if self._index[n][1][-1] % 32 == 0]
+                b1, t1 = ops.make_x1_blob(self._dev, self._index, self.w, n1)
+                self.o.set_x1_twin(b1, t1, mode='admitted', flags=L.CONV_X1_GEMM | L.CONV_X1_HALO16)
+        elif self.precision == 'fp32':
             self.o.set_precision(L.MMA_F32, self._dev, None)
+        else:
+            raise ValueError(f"YOLOv5-face precision must be one of {PRECISIONS}, got {self.precision!r}")
         return self
 
     # ------------------------------------------------------------------ building blocks

@@ -83,17 +83,15 @@ def parse_precision_knob(environ=None):
 
 
 def detect_precision_knob(environ=None):
-    """KEEP_AMD_DETECT_PRECISION=x3|fp32|f16 (default x3): the matrix-core policy of the engine-backed RetinaFace detectors (resnet50 and
-    mobile0.25), read ONCE when the pack's helper is built.  'f16' is the opt-in single-fp16 speed mode, outside bit-parity with the
-    default.  The YOLOv5-face engines have no such mode: they keep x3 and say so once (``engine_facelib``)."""
+    """KEEP_AMD_DETECT_PRECISION=x3|fp32|f16 (default x3): the matrix-core policy of every engine-backed detector -- RetinaFace (resnet50 and
+    mobile0.25) and YOLOv5-face (YOLOv5l and YOLOv5n) -- read ONCE when the pack's helper is built.  'f16' is the
+    opt-in single-fp16 speed mode, outside bit-parity with the default; unset, every detector runs x3, bit-equal to an engine built
+    without the knob."""
     from ..engine.retinaface import PRECISIONS
     value = (os.environ if environ is None else environ).get('KEEP_AMD_DETECT_PRECISION', '') or 'x3'
     if value not in PRECISIONS:
         raise ValueError(f"KEEP_AMD_DETECT_PRECISION must be one of {', '.join(PRECISIONS)}; got {value!r}")
     return value
-
-
-_yolo_f16_warned = False
 
 
 def engine_facelib(helper):
@@ -116,15 +114,11 @@ def engine_facelib(helper):
     if yolo is not None and hasattr(yolo, 'state_dict') and 'model.0.stem_1.conv.weight' in yolo.state_dict():
         from ..engine.yoloface import EngineYoloModel
         from ..engine.yoloface import yolo_detect_batch
-        det.detector = EngineYoloModel.from_module(yolo)    # pre / post-processing stay YoloDetector's own (face_detector.py)
-        global _yolo_f16_warned
-        if detect_precision_knob() == 'f16' and not _yolo_f16_warned:      # no silent policy change and no error: x3, said once
-            _yolo_f16_warned = True
-            logger.warning("KEEP_AMD_DETECT_PRECISION=f16 does not apply to the YOLOv5-face engines: they keep the x3 policy")
+        det.detector = EngineYoloModel.from_module(yolo, precision=detect_precision_knob())    # pre / post-processing stay YoloDetector's own (face_detector.py)
         if hasattr(det, '_preprocess') and hasattr(det, '_postprocess'):      # the processor's batched pre-pass (one network call per chunk)
             import functools
             det.detect_batch = functools.partial(yolo_detect_batch, det)
-        logger.debug("face_detector (%s) runs its network on the HIP engine", det.detector.engine.name)
+        logger.debug("face_detector (%s) runs its network on the HIP engine, precision %s", det.detector.engine.name, det.detector.engine.precision)
     return helper
 
 

@@ -112,6 +112,16 @@ extern "C" {
  * the same im2col kernel there), without prologue.  Everything else stays refused (KEEP_EUNSUP, keep_last_error).
  * The detector's opt-in precision 'f16' (engine/retinaface.py) sets it. */
 #define KEEP_CONV_X1_GEMM (1u << 14)
+/* KEEP_CONV_X1_HALO16: the second admitting bit (additive like KEEP_CONV_X1_GEMM: same ABI version, read under KEEP_MMA_X1 only, every other
+ * policy ignores it, and without it every call means what it meant).  With it KEEP_MMA_X1 also takes a 3x3 stride-1 pad-1 zero-padded
+ * convolution on a map of 16 x 16 tiles that is NOT 8 x 32 tileable (Ho % 16 == 0 && Wo % 16 == 0; the 8 x 32-tileable maps keep the streaming
+ * form): the single-fp16 instantiation of conv3x3_halo_x3_kernel<16>, 32-channel chunks, one fp16 MFMA per product.  Cin % 32 == 0, the
+ * hi-only twin and x3_acc_scale given, no prologue / aux / in2 / upsample / ln_gamma; bias, epilogue activations, residual (res_ld), out_ld
+ * slices, Cout % 64 != 0, x3_in_amax, x3_out_amax and the statistics partials as in the x3 form; no scratch.  Admitted only where the
+ * KEEP_MMA_X3 plan of the same call is un-split -- computed from plan_ref_images, never from N -- so a call x3 would split is refused
+ * (KEEP_EUNSUP, keep_last_error names the split) and the host keeps it on KEEP_MMA_X3.  The YOLOv5-face engines' opt-in precision 'f16'
+ * (engine/yoloface.py) sets it together with KEEP_CONV_X1_GEMM. */
+#define KEEP_CONV_X1_HALO16 (1u << 15)
 /* keep_attention_args.flags (v18) */
 #define KEEP_ATTN_NO_PACK (1u << 0)   /* x3: never pre-pack K / V^T (keep_attention_workspace_bytes answers 0) */
 #define KEEP_ATTN_NO_SFULL2 (1u << 1) /* x3, D = 512: the 128-query kernel instead of the 32-query one */
