@@ -228,7 +228,7 @@ class KeepNet:
             if self.precision == 'f16':      # the x1 twin: built here, never inside a stream capture
                 if self._dev_blobx1 is None:
                     self._make_x1()
-                self.o.set_x1_twin(self._dev_blobx1, self._x1_ranges)
+                self.o.set_x1_twin(self._dev_blobx1, self._x1_ranges, flags=0, base_kernel=ops.X3_STREAM_KERNEL)
         else:
             self.o.set_precision(L.MMA_F32, self._dev_blob, None)
 

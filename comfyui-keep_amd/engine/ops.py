@@ -10,6 +10,7 @@ policy and the weight blobs it needs live on an ``Ops`` INSTANCE owned by one ``
 nets (or two threads) with different policies never share state.  The module-level functions
 are the methods of a default fp32 instance (kernel tests call them with explicit ``mma=``).
 """
+import bisect
 import os
 
 import torch
@@ -25,8 +26,9 @@ USE_BK256 = bool(int(os.environ.get('KEEP_BK256', '0')))   # measured slower tha
 HALO_PRENORM_MINPIX = int(os.environ.get('KEEP_HALO_PRENORM_MINPIX', '0'))
 
 DEBUG_SYNC = os.environ.get('KEEP_DEBUG_SYNC') is not None
-X3_STREAM_KERNEL = 'conv3x3_halo_x3s_kernel'      # keep_conv2d_plan's name of the x3 streaming 3x3 kernel: the one family 'f16' substitutes
+X3_STREAM_KERNEL = 'conv3x3_halo_x3s_kernel'      # keep_conv2d_plan's name of the x3 streaming 3x3 kernel: the one family KeepNet's 'f16' substitutes
 _PLAN_CACHE = {}
+POLICY_NAMES = {L.MMA_F32: 'fp32', L.MMA_BF16: 'bf16', L.MMA_X3: 'x3'}      # the base policies of an Ops
 # Deployment settings of the library, read ONCE here (the library itself reads no environment variable: they travel in the argument
 # structs).  KEEP_PLAN_REF_IMAGES: the fixed reference batch of the parity policies' plans (default 16; 2 = latency profile for single
 # clips; results are batch-invariant within one value).  KEEP_X3_EXACT_ACT=1: library expf / erff inside the x3 kernels.
@@ -66,6 +68,14 @@ def _plan(a, key):
     return pl
 
 
+def _row_of(table, off, n):
+    """Row (first element, one past the last, 2^-e) of the tensor that holds elements off .. off + n of the packed blob, in a
+    ``([first element], rows)`` table sorted by offset (``make_x3_blob`` / ``make_x1_blob``); None when no tensor of the table does."""
+    starts, rows = table
+    i = bisect.bisect_right(starts, off) - 1
+    return rows[i] if i >= 0 and off + n <= rows[i][1] else None
+
+
 def empty(shape, like):
     return torch.empty(shape, dtype=torch.float32, device=like.device)
 
@@ -77,15 +87,16 @@ def offset(t, off):
 
 class Ops:
     def __init__(self):
-        # matrix-core operand precision of keep_conv2d / keep_attention launches:
-        #   L.MMA_F32 exact f32 (parity), L.MMA_X3 split fp16 x 3 (parity-grade fast policy), L.MMA_BF16 (speed policy),
-        #   L.MMA_X1 single fp16 (ParseNet's opt-in speed policy: keep_conv2d only, `blobx3` is then the hi-only twin of make_x1_blob)
+        # matrix-core operand precision of keep_conv2d / keep_attention launches, the BASE policy of this Ops:
+        #   L.MMA_F32 exact f32 (parity), L.MMA_X3 split fp16 x 3 (parity-grade fast policy), L.MMA_BF16 (speed policy).
+        #   Single fp16 (L.MMA_X1, 'f16') is never a base: it is a base policy plus an x1 twin (set_x1_twin)
         self.mma = L.MMA_F32
         self.attn_mma = L.MMA_F32
         self.blob32 = None      # packed fp32 weight blob the twins below are resolved against (same element offsets)
         self.blob16 = None      # bf16 twin
         self.blobx3 = None      # split-fp16 twin: int16 tensor, 2 elements per weight, per-tensor [.., Cin/16, hi16|lo16]
         self.x3_acc_scale = 1.0
+        self._x3_table = None
         self._up2, self._up2_src = {}, (None, None)
         # bench.py's roofline leg: when a list, every keep_conv2d launch is bracketed by HIP events on the launch stream
         # and appended as (kernel family, algorithmic_flops, split_k, start_event, end_event, algorithmic_bytes)
@@ -99,15 +110,14 @@ class Ops:
         self.flags = DEFAULT_CONV_FLAGS
         self.attn_flags = 0
         self.plan_ref_images = PLAN_REF_IMAGES
-        # KeepNet's 'f16' policy: the x3 policy (mma, attn_mma and every twin above stay x3) plus a hi-only twin of the 3x3 weights
-        # (make_x1_blob) -- conv() substitutes L.MMA_X1 where the library's plan admits it (route_conv).  None: plain x3.
+        # 'f16': a hi-only twin (make_x1_blob) attached to the base policy by set_x1_twin -- conv() substitutes L.MMA_X1 in every call of
+        # the base policy whose weight has such a twin and whose X1 plan the library admits (route_x1).  None: the plain base policy.
         self.blobx1 = None
-        self._x1_table = None      # ([first element], [(first, one past the last)]) of the tensors blobx1 holds, sorted
-        self._x1_route = {}        # plan key -> L.MMA_X1 | L.MMA_X3: one keep_conv2d_plan query per shape
-        # which calls the twin substitutes: 'stream' = KeepNet's rule (route_conv), 'admitted' = the detector's (route_conv_admitted:
-        # every call the library's plan admits under L.MMA_X1 with L.CONV_X1_GEMM -- 1x1 GEMMs, im2col shapes and the streaming 3x3 form)
-        self.x1_mode = 'stream'
-        self.x1_flags = L.CONV_X1_GEMM      # 'admitted': the opt-in form bits the X1 plan is asked with (YOLOv5-face adds L.CONV_X1_HALO16)
+        self._x1_table = None      # ([first element], [(first, one past the last, 2^-e)]) of the tensors blobx1 holds, sorted
+        self._x1_route = {}        # base plan key -> the call's X1 Plan | False: one keep_conv2d_plan query per shape
+        self.x1_flags = L.CONV_X1_GEMM      # opt-in form bits OR-ed into the X1 plan query and launch
+        self.x1_base = L.MMA_X3             # the policy a call without a twin, or one the library refuses, stays on
+        self.x1_base_kernel = None          # restriction: substitute only where the base plan is this kernel, un-split (None: everywhere)
         self.census = None         # when a dict: kernel name (plan string) -> launches, counted by conv() (tests, tools/bench_precision.py)
 
     def begin_forward(self, device):
@@ -131,15 +141,12 @@ class Ops:
 
     def set_precision(self, mma, blob32=None, blob16=None, blobx3=None, x3_acc_scale=1.0, x3_scales=None):
         """x3_scales: per-tensor accumulator scales of the split-fp16 twin, [(first element, one past the last, 2^-e), ...] sorted
-        by offset (``make_x3_blob``); without it every tensor of the blob carries ``x3_acc_scale``.  ``mma = L.MMA_X1``: ``blobx3`` is
-        the hi-only twin of ``make_x1_blob`` (one fp16 per weight), same scale table."""
-        if mma not in (L.MMA_F32, L.MMA_BF16, L.MMA_X3, L.MMA_X1):
-            raise ValueError(f"set_precision: unknown matrix-core policy {mma!r}")
-        self._x3_table = None
-        if x3_scales:
-            self._x3_table = ([a for a, _, _ in x3_scales], list(x3_scales))
+        by offset (``make_x3_blob``); without it every tensor of the blob carries ``x3_acc_scale``."""
+        if mma not in (L.MMA_F32, L.MMA_BF16, L.MMA_X3):
+            raise ValueError(f"set_precision: {mma!r} is no base policy (single fp16 is a base policy plus set_x1_twin)")
+        self._x3_table = ([a for a, _, _ in x3_scales], list(x3_scales)) if x3_scales else None
         self.mma = self.attn_mma = mma
-        self.blobx1, self._x1_table, self._x1_route, self.x1_mode, self.x1_flags = None, None, {}, 'stream', L.CONV_X1_GEMM      # ('f16' re-attaches its twin after every policy change: set_x1_twin)
+        self.set_x1_twin()      # ('f16' re-attaches its twin after every policy change)
         if blobx3 is not None and (blob32 is not self._up2_src[0] or blobx3 is not self._up2_src[1]):
             # phase kernels of the Upsample convolutions (up2_twin): derived from THESE blob objects -- a new upload, even one that lands
             # on the same addresses, starts from an empty cache; a policy switch on the same blobs keeps it (captured x3 graphs hold
@@ -147,71 +154,54 @@ class Ops:
             self._up2, self._up2_src = {}, (blob32, blobx3)
         self.blob32, self.blob16, self.blobx3, self.x3_acc_scale = blob32, blob16, blobx3, float(x3_acc_scale)
 
-    def set_x1_twin(self, blobx1=None, ranges=None, mode='stream', flags=L.CONV_X1_GEMM):
-        """'f16' on top of an x3 policy set by ``set_precision``: ``blobx1`` is ``make_x1_blob``'s hi-only twin (same per-tensor
-        power-of-two scales as the x3 twin), ``ranges`` its (first element, one past the last, 2^-e) table.  None: back to plain x3.
-        ``mode``: 'stream' (KeepNet: ``route_conv``) or 'admitted' (the detectors: ``route_conv_admitted``); ``flags``: the opt-in form
-        bits an 'admitted' plan query carries (RetinaFace: L.CONV_X1_GEMM, the default; YOLOv5-face adds L.CONV_X1_HALO16)."""
-        if blobx1 is not None and self.mma != L.MMA_X3:
-            raise ValueError("set_x1_twin: the single-fp16 substitution rides on the x3 policy (set_precision(L.MMA_X3, ...) first)")
-        if mode not in ('stream', 'admitted'):
-            raise ValueError(f"set_x1_twin: unknown routing mode {mode!r}")
-        self.blobx1 = blobx1
-        self.x1_mode = mode
-        self.x1_flags = int(flags)
+    def set_x1_twin(self, blobx1=None, ranges=None, flags=L.CONV_X1_GEMM, base=L.MMA_X3, base_kernel=None):
+        """'f16' on top of the base policy set by ``set_precision``: ``blobx1`` is ``make_x1_blob``'s hi-only twin, ``ranges`` its (first
+        element, one past the last, 2^-e) table -- the x1 launches take their ``x3_acc_scale`` from it.  None: back to the plain base.
+        ``flags``: opt-in form bits of the X1 plan query and launch (RetinaFace: L.CONV_X1_GEMM, the default; YOLOv5-face adds
+        L.CONV_X1_HALO16; ParseNet and KeepNet: 0).  ``base``: the policy the twin rides on, which must be this Ops' (a call without a
+        twin, or one the library refuses, stays there).  ``base_kernel``: substitute only calls whose base plan is this kernel, un-split
+        (KeepNet: X3_STREAM_KERNEL)."""
+        if blobx1 is not None and self.mma != base:
+            raise ValueError(f"set_x1_twin: this twin rides on the {POLICY_NAMES[base]} policy (set_precision(...) with it first)")
+        self.blobx1, self.x1_flags, self.x1_base, self.x1_base_kernel = blobx1, int(flags), base, base_kernel
         self._x1_table = None
         if blobx1 is not None:
-            rows = sorted((int(a), int(b)) for a, b, _ in ranges)
-            self._x1_table = ([a for a, _ in rows], rows)
+            rows = sorted((int(a), int(b), float(s)) for a, b, s in ranges)
+            self._x1_table = ([a for a, _, _ in rows], rows)
         self._x1_route = {}
 
-    def x1_twin(self, w):
-        """Hi-only fp16 copy of an fp32 weight view for the 'f16' substitution, or None when the policy is off or the tensor has no
-        such twin (then the layer stays x3)."""
-        if self.blobx1 is None:
+    def _x1_of(self, w):
+        """(hi-only fp16 copy, accumulator scale 2^-e) of an fp32 weight view, or None when no twin is attached or the tensor has none
+        (a view that does not lie inside the packed blob has none: the call runs as it would without 'f16')."""
+        if self.blobx1 is None or not w.is_contiguous():
             return None
-        import bisect
-        off = self._blob_off(w)
-        starts, rows = self._x1_table
-        i = bisect.bisect_right(starts, off) - 1
-        if i < 0 or not (rows[i][0] <= off and off + w.numel() <= rows[i][1]):
-            return None
-        return self.blobx1[off:off + w.numel()]
+        off = (w.data_ptr() - self.blob32.data_ptr()) // 4
+        row = _row_of(self._x1_table, off, w.numel())
+        return None if row is None else (self.blobx1[off:off + w.numel()], row[2])
 
-    def route_conv(self, key, x3_plan, x1_plan):
-        """'f16': which matrix-core policy a convolution call runs under.  L.MMA_X1 exactly where the x3 plan of the call is the un-split
-        streaming 3x3 kernel AND the library's plan admits the call under KEEP_MMA_X1 (``x1_plan()``: keep_conv2d_plan, KEEP_EUNSUP ->
-        refused); L.MMA_X3 everywhere else -- the GEMM forms, the split-K / 64-pixel partial forms, the phase upsample, im2col shapes.
-        Both plans follow the per-image geometry and the fixed reference batch, so the answer (cached per ``key``) never depends on a
-        clip's batch-mates.  Attention never comes here: ``attn_mma`` stays x3."""
+    def x1_twin(self, w):
+        """Hi-only fp16 copy of an fp32 weight view for the 'f16' substitution, or None (then the layer stays on the base policy)."""
+        tw = self._x1_of(w)
+        return None if tw is None else tw[0]
+
+    def route_x1(self, key, base_plan, x1_plan):
+        """'f16': the X1 Plan a convolution call of the base policy runs under, or None where it stays on the base.  The library decides:
+        ``x1_plan()`` is keep_conv2d_plan for the call under L.MMA_X1 with ``x1_flags`` -- KEEP_EUNSUP is its answer 'no kernel of this
+        grade' (anything else is an error) -- asked once per ``key`` and only where ``x1_base_kernel`` allows (KeepNet: the un-split x3
+        streaming 3x3 kernel, so the GEMM forms, the split-K forms, the phase upsample and im2col shapes stay x3 unasked).  Both plans
+        follow the per-image geometry and the fixed reference batch: a route never depends on a clip's or frame's batch-mates.
+        Attention never comes here: ``attn_mma`` is the base's."""
         r = self._x1_route.get(key)
         if r is None:
-            r = L.MMA_X3
-            if x3_plan.kernel == X3_STREAM_KERNEL and x3_plan.split_k == 1:
+            r = False
+            if self.x1_base_kernel is None or (base_plan.kernel == self.x1_base_kernel and base_plan.split_k == 1):
                 try:
-                    x1_plan()
-                    r = L.MMA_X1
+                    r = x1_plan()
                 except L.KeepHipError as e:
                     if '(code -2)' not in str(e):      # anything but KEEP_EUNSUP is an error, not an answer
                         raise
             self._x1_route[key] = r
-        return r
-
-    def route_conv_admitted(self, key, x1_plan):
-        """The detector's 'f16' rule, sibling of ``route_conv``: L.MMA_X1 (with the form bits of ``set_x1_twin``) iff the library's plan admits the call
-        under it -- asked once per ``key`` -- and L.MMA_X3 otherwise (KEEP_EUNSUP is the library's answer, anything else an error).  The
-        plan follows the per-image geometry and the fixed reference batch: a frame's route never depends on its batch-mates."""
-        r = self._x1_route.get(key)
-        if r is None:
-            r = L.MMA_X3
-            try:
-                x1_plan()
-                r = L.MMA_X1
-            except L.KeepHipError as e:
-                if '(code -2)' not in str(e):
-                    raise
-            self._x1_route[key] = r
-        return r
+        return r or None
 
     # ------------------------------------------------------------------ weight twins
     def _blob_off(self, w):
@@ -275,24 +265,19 @@ class Ops:
     def x3_twin(self, w):
         """split-fp16 copy of an fp32 weight view (row slices of a [Cout, .., Cin] tensor keep their layout), or None
         when the policy has no x3 blob / the tensor's Cin is not a multiple of 16 (such layers run on the f32 kernels)."""
-        if self.blobx3 is None or w.shape[-1] % (32 if self.mma == L.MMA_X1 else 16):
+        if self.blobx3 is None or w.shape[-1] % 16:
             return None
         off = self._blob_off(w)
-        if self.mma == L.MMA_X1:      # hi-only twin: one fp16 per weight, the packed tensor's own element order
-            return self.blobx3[off:off + w.numel()]
         return self.blobx3[2 * off:2 * (off + w.numel())]
 
     def x3_scale_of(self, w):
         """Accumulator scale (2^-e) of the twin of weight view ``w``: its own tensor's (a row slice shares its tensor's scale)."""
-        if getattr(self, '_x3_table', None) is None:
+        if self._x3_table is None:
             return self.x3_acc_scale
-        import bisect
-        off = self._blob_off(w)
-        starts, rows = self._x3_table
-        i = bisect.bisect_right(starts, off) - 1
-        if i < 0 or not (rows[i][0] <= off and off + w.numel() <= rows[i][1]):
+        row = _row_of(self._x3_table, self._blob_off(w), w.numel())
+        if row is None:
             raise RuntimeError("weight view does not lie inside one tensor of the x3 blob")
-        return rows[i][2]
+        return row[2]
 
     # ------------------------------------------------------------------ keep_conv2d
     def conv(self, x, w, bias=None, *, stride=1, pad=1, ksize=3, down=False, upsample=False, pro=None, pro_act=L.PRO_NONE,
@@ -306,6 +291,8 @@ class Ops:
         producer's ``Stats.amax`` of x (any upper bound of max |x| per image works), replacing the range probe.
         ``bounded=True``: the caller vouches that |x| stays far below the fp16 range (normalised / attention-averaged
         inputs); otherwise an x3 launch without a normalising prologue first probes the input range (keep_absmax).
+        ``x3_acc_scale`` belongs to the caller's ``wx3``: a call that leaves the weight operand to this Ops takes the scale of the twin it runs
+        on (the x1 twin's own table where 'f16' routes it to L.MMA_X1).
         ``ln=(gamma, beta, eps)``: LayerNorm over the output channels in the epilogue, BEFORE the residual is added (x3 GEMM form,
         Cout == 128, rows % 128 == 0: ``ln_fusable``); the library refuses anything else."""
         N, H, W, ld = x.shape
@@ -340,25 +327,27 @@ class Ops:
             # nearest x2 + 3x3 as four 2x2-tap phase convolutions on the source grid: 4 of 9 taps are multiplied
             wx3, x3_acc_scale = self.up2_twin(w)
             up_mode = L.UPSAMPLE_X2_PHASES
-        wx3_own = False              # wx3 is this Ops' x3 twin of w (not a caller's tensor): what 'f16' may replace by the x1 twin
-        if mma in (L.MMA_X3, L.MMA_X1) and wx3 is None:
-            wx3 = None if {mma, self.mma} == {L.MMA_X3, L.MMA_X1} else self.x3_twin(w)      # (the twin's layout is the Ops policy's)
-            wx3_own = wx3 is not None
-            if mma == L.MMA_X1 and wx3 is None:                     # no x1 kernel reads fp32 weights: such a layer (ParseNet's RGB convolution) runs exact f32
-                mma = L.MMA_F32
+        own_w = wx3 is None          # the weight operand is this Ops' to choose (not a caller's tensor -- the phase weights of an Upsample): what 'f16' may replace by the x1 twin
+        if mma == L.MMA_X3 and wx3 is None:
+            wx3 = self.x3_twin(w)
             if wx3 is not None and x3_acc_scale is None:
                 x3_acc_scale = self.x3_scale_of(w)
         if x3_acc_scale is None:
             x3_acc_scale = self.x3_acc_scale
         want_bf16_out = bool(out_bf16) and mma == L.MMA_BF16 and residual is None
         xin = x if in_off == 0 else x.view(-1)[in_off:]
-        in_amax = None
-        if ((mma == L.MMA_X3 and (wx3 is not None or (Cin <= 3 and KH == 3))) or mma == L.MMA_X1) and pro is None and not bounded:   # (RGB convs split fp32 weights in-kernel)
-            in_amax = x_amax if (x_amax is not None and x_amax.numel() == N) else absmax(xin, N, H * W, Cin, ld, H * W * ld, self)
-        out_ld = (Cout if out is None else out.shape[-1]) if out_ld is None else out_ld
-        flags = self.flags
 
-        def make_args(inp, dtype, pro_t, pro_a, odt, sk):
+        def in_range():      # per-image max |x|: the producer's, or one keep_absmax probe
+            return x_amax if (x_amax is not None and x_amax.numel() == N) else absmax(xin, N, H * W, Cin, ld, H * W * ld, self)
+        probes = pro is None and not bounded      # (a normalising prologue / a vouched-for input needs no range)
+        in_amax = None
+        if ((mma == L.MMA_X3 and (wx3 is not None or (Cin <= 3 and KH == 3))) or mma == L.MMA_X1) and probes:   # (RGB convs split fp32 weights in-kernel)
+            in_amax = in_range()
+        out_ld = (Cout if out is None else out.shape[-1]) if out_ld is None else out_ld
+        pol = (mma, wx3, float(x3_acc_scale), self.flags)      # what make_args / key_of launch under: (policy, weight_x3, x3_acc_scale, flags)
+
+        def make_args(inp, dtype, pro_t, pro_a, odt, sk, p=None):
+            mma, wx3, acc_scale, flags = p or pol
             return L.conv_args(
                 inp=inp, weight=w, bias=bias, out=out, pro_scale=None if pro_t is None else pro_t[0],
                 pro_shift=None if pro_t is None else pro_t[1], residual=residual, aux=aux, workspace=None,
@@ -367,12 +356,13 @@ class Ops:
                 upsample=up_mode, pro_act=pro_a, epi_act=act, aux_w=float(aux_w), split_k=sk, dtype=dtype,
                 mma=mma, weight_bf16=wb if mma == L.MMA_BF16 else None, stats_out=None, stats_P=0,
                 bk256=int(USE_BK256), out_dtype=odt, weight_x3=wx3 if mma in (L.MMA_X3, L.MMA_X1) else None,
-                x3_acc_scale=float(x3_acc_scale), x3_in_amax=in_amax, x3_out_amax=None,
+                x3_acc_scale=acc_scale, x3_in_amax=in_amax, x3_out_amax=None,
                 in2=x2, in2_cin1=0 if x2 is None else ld, pad_mode=L.PAD_REFLECT if reflect else L.PAD_ZERO,
                 ln_gamma=None if ln is None else ln[0], ln_beta=None if ln is None else ln[1],
                 ln_eps=0.0 if ln is None else float(ln[2]), flags=flags, plan_ref_images=self.plan_ref_images)
 
-        def key_of(dtype, pro_t, pro_a, odt, sk):
+        def key_of(dtype, pro_t, pro_a, odt, sk, p=None):
+            mma, wx3, _, flags = p or pol
             return (N, H, W, ld, Cin, Cout, KH, stride, pad_t, pad_l, Ho, Wo, out_ld, up_mode, pro_a, act, dtype, mma,
                     odt, sk, pro_t is not None, residual is not None, 0 if residual is None else residual.shape[-1],
                     aux is not None, bias is not None, in_off % 8, wx3 is not None, USE_BK256, x2 is not None, bool(reflect),
@@ -391,23 +381,16 @@ class Ops:
             pro, pro_act, in_dtype = None, L.PRO_NONE, L.BF16
             a = make_args(xin, in_dtype, None, pro_act, odt, sk_req)
             pl = _plan(a, key_of(in_dtype, None, pro_act, odt, sk_req))
-        admitted = self.x1_mode == 'admitted'          # (the detector's rule: every kernel size; KeepNet's: the 3x3 streaming form)
-        if self.blobx1 is not None and mma == L.MMA_X3 and self.mma == L.MMA_X3 and (KH == 3 or admitted) and wx3_own and x2 is None:
-            wx1 = self.x1_twin(w)                      # (a caller's own wx3 -- the phase weights of an Upsample -- stays x3)
-            if wx1 is not None:
-                key3 = key_of(in_dtype, pro, pro_act, odt, sk_req)
-                keep = (mma, wx3, flags)
-                mma, wx3 = L.MMA_X1, wx1               # (make_args / key_of read these)
-                if admitted:
-                    flags |= self.x1_flags
-
-                def x1_plan():
-                    return L.conv2d_plan(make_args(xin, in_dtype, pro, pro_act, odt, sk_req))
-                if (self.route_conv_admitted(key3, x1_plan) if admitted else self.route_conv(key3, pl, x1_plan)) == L.MMA_X1:
-                    a = make_args(xin, in_dtype, pro, pro_act, odt, sk_req)
-                    pl = _plan(a, key_of(in_dtype, pro, pro_act, odt, sk_req))
-                else:
-                    mma, wx3, flags = keep
+        tw1 = self._x1_of(w) if (self.blobx1 is not None and own_w and mma == self.mma == self.x1_base and x2 is None) else None
+        if tw1 is not None:      # 'f16': the call runs single-fp16 iff the library plans it so (route_x1)
+            x1 = (L.MMA_X1, tw1[0], tw1[1], self.flags | self.x1_flags)
+            pl1 = self.route_x1(key_of(in_dtype, pro, pro_act, odt, sk_req), pl, lambda: _plan(
+                make_args(xin, in_dtype, pro, pro_act, odt, sk_req, x1), key_of(in_dtype, pro, pro_act, odt, sk_req, x1)))
+            if pl1 is not None:
+                if in_amax is None and probes:      # (a base that reads no range -- exact f32 -- left the probe to this point)
+                    in_amax = in_range()
+                pol, pl = x1, pl1
+                a = make_args(xin, in_dtype, pro, pro_act, odt, sk_req)
         if want_bf16_out and not pl.out_bf16_ok:
             want_bf16_out, odt = False, L.F32
             a = make_args(xin, in_dtype, pro, pro_act, odt, sk_req)
@@ -426,12 +409,7 @@ class Ops:
                 st.part, st.P = empty((N, pl.stats_P, Cout, 2), x), pl.stats_P
                 a.stats_out, a.stats_P = st.part.data_ptr(), pl.stats_P
             if pl.out_amax_ok:
-                if self.amax_arena is not None and self.amax_pos + N <= self.amax_arena.numel():
-                    st.amax = self.amax_arena[self.amax_pos:self.amax_pos + N]       # zeroed once per forward (begin_forward)
-                    self.amax_pos += N
-                    a.x3_out_amax_zeroed = 1
-                else:
-                    st.amax = empty((N,), x)
+                st.amax, a.x3_out_amax_zeroed = self._amax_slots(N, x)
                 a.x3_out_amax = st.amax.data_ptr()
         if self.profile is not None:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -622,13 +600,8 @@ class Ops:
 def absmax(x, N, R, C, ld, img_stride, ops=None):
     """Range probe: max |x| per image over R rows x C columns (row stride ld, image stride img_stride) -> [N] floats.
     ``ops``: take the result slots from that Ops' per-forward arena (already zero: no zero-fill launch)."""
-    if ops is not None and ops.amax_arena is not None and ops.amax_pos + N <= ops.amax_arena.numel():
-        out = ops.amax_arena[ops.amax_pos:ops.amax_pos + N]
-        ops.amax_pos += N
-        L.call('keep_absmax', x, out, N, R, C, ld, img_stride, 1)
-        return out
-    out = torch.empty((N,), dtype=torch.float32, device=x.device)
-    L.call('keep_absmax', x, out, N, R, C, ld, img_stride, 0)
+    out, zeroed = (empty((N,), x), 0) if ops is None else ops._amax_slots(N, x)
+    L.call('keep_absmax', x, out, N, R, C, ld, img_stride, zeroed)
     return out
 
 

@@ -24,19 +24,11 @@ import torch
 
 from . import hiplib as L
 from . import ops
-from .weights import pack_blob, views
+from .packed import PRECISIONS, PackedEngine      # noqa: F401  (PRECISIONS: re-exported)
+from .weights import pack_blob
 
 BN_EPS = 1e-5          # nn.BatchNorm2d default (parsenet.py:22)
 PARSING_CH = 19
-# matrix-core policies of the engine: 'x3' split fp16 (fp32-grade, the default), 'fp32' exact f32, 'f16' operands rounded once to fp16
-# (KEEP_MMA_X1: an opt-in speed mode OUTSIDE bit-parity with the default, like the KEEP network's bf16 -- DESIGN 4)
-PRECISIONS = ('x3', 'fp32', 'f16')
-
-
-def check_precision(precision):
-    if precision not in PRECISIONS:
-        raise ValueError(f"ParseNet precision must be one of {PRECISIONS}, got {precision!r}")
-    return precision
 
 
 def parsenet_spec(in_size=512, out_size=512, min_feat_size=32, base_ch=64, parsing_ch=PARSING_CH, res_depth=10, ch_range=(32, 256)):
@@ -100,9 +92,15 @@ def _fold_bn(w, sd, p):
     return (w.double() * s.view(-1, 1, 1, 1)).float(), (b - m * s).float()
 
 
-class ParseNetEngine:
+class ParseNetEngine(PackedEngine):
     """``engine = ParseNetEngine(state_dict).to('cuda')``; ``engine.logits(x)`` / ``engine.classes(x)`` with x fp32 [N,3,S,S]
     in [-1, 1] (the helper's ``normalize(face/255, 0.5, 0.5)`` input, face_restoration_helper.py:420-421)."""
+    NET = 'ParseNet'
+    # 'f16' rides on exact f32, not on x3: the engine holds only the 2-bytes-per-weight twin, and the one layer without a twin (the 3 -> 64
+    # convolution) runs exact f32.  Range: every input carries its producer's max |x| (x3_in_amax) or is probed, so no operand can leave the
+    # fp16 range -- a non-finite INPUT propagates to the logits exactly as under 'x3' (no re-run: ParseNet has none on either policy)
+    X1_BASE = L.MMA_F32
+    X1_RULE = dict(flags=0)
 
     def __init__(self, state_dict, in_size=512, out_size=512, precision='x3'):
         self.in_size, self.out_size = in_size, out_size
@@ -133,11 +131,7 @@ class ParseNetEngine:
                 put(f'{name}.shortcut', sd[f'{name}.shortcut_func.conv2d.weight'], sd[f'{name}.shortcut_func.conv2d.bias'])
             for c in ('conv1', 'conv2'):
                 put(f'{name}.{c}', *_fold_bn(sd[f'{name}.{c}.conv2d.weight'], sd, f'{name}.{c}'))
-        self._blob, self._index = pack_blob(t)
-        self.precision = check_precision(precision)
-        self.device = torch.device('cpu')
-        self.w = None
-        self.o = ops.Ops()
+        self._init_packed(*pack_blob(t), precision)
 
     def packed(self):
         """(packed fp32 blob, index, in_size, out_size, precision): what ``from_packed`` rebuilds the engine from in another process
@@ -149,41 +143,11 @@ class ParseNetEngine:
         self = cls.__new__(cls)
         self.in_size, self.out_size = in_size, out_size
         self.blocks = parsenet_spec(in_size=in_size, out_size=out_size)
-        self._blob, self._index = np.ascontiguousarray(blob), index
-        self.precision = check_precision(precision)
-        self.device = torch.device('cpu')
-        self.w = None
-        self.o = ops.Ops()
+        self._init_packed(np.ascontiguousarray(blob), index, precision)
         return self
 
-    def to(self, device):
-        device = torch.device(device)
-        if device.type != 'cuda':
-            self.w, self._dev = None, None
-            self.o.set_precision(self.o.mma)
-            self.device = device
-            return self
-        if device.index is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        L.load(check_device=True)
-        self.device = device
-        self._dev = torch.from_numpy(self._blob).to(device)
-        self.w = views(self._dev, self._index)
-        if self.precision == 'x3':
-            names = [n for n, (_, sh) in self._index.items() if len(sh) == 4 and sh[-1] % 16 == 0]
-            bx, table = ops.make_x3_blob(self._dev, self._index, self.w, names)       # one power-of-two scale per tensor
-            self.o.set_precision(L.MMA_X3, self._dev, None, bx, 1.0, x3_scales=table)
-        elif self.precision == 'f16':
-            # hi-only twin of every layer the x1 kernels take (Cin % 32 == 0: all but the 3 -> 64 convolution, which stays exact f32 as
-            # under 'x3').  Range: every input carries its producer's max |x| (x3_in_amax), so no operand can leave the fp16 range --
-            # a non-finite INPUT propagates to the logits exactly as under 'x3' (no re-run: ParseNet has none on either policy)
-            names = [n for n, (_, sh) in self._index.items() if len(sh) == 4 and sh[-1] % 32 == 0]
-            bx, table = ops.make_x1_blob(self._dev, self._index, self.w, names)
-            self.o.set_precision(L.MMA_X1, self._dev, None, bx, 1.0, x3_scales=table)
-        else:
-            check_precision(self.precision)
-            self.o.set_precision(L.MMA_F32, self._dev, None)
-        return self
+    def x3_names(self):
+        return [n for n, (_, sh) in self._index.items() if len(sh) == 4 and sh[-1] % 16 == 0]
 
     def _conv(self, x, name, x_amax=None, **kw):
         """-> (y, per-image max |y| from the launch's epilogue or None): the x3 range scale of the convolutions that read y, so that none
@@ -240,6 +204,9 @@ class ParseNetEngine:
         with torch.cuda.device(self.device):
             L.call('keep_channel_argmax', y, out, N * H * W, PARSING_CH, ld)
         return out
+
+
+check_precision = ParseNetEngine.check_precision
 
 
 class EngineFaceParse:

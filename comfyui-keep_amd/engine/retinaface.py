@@ -33,7 +33,8 @@ import torch
 
 from . import hiplib as L
 from . import ops
-from .weights import pack_blob, views
+from .packed import PRECISIONS, PackedEngine      # noqa: F401  (PRECISIONS: re-exported)
+from .weights import pack_blob
 
 BN_EPS = 1e-5
 CFG_RE50 = {'min_sizes': [[16, 32], [64, 128], [256, 512]], 'steps': [8, 16, 32], 'variance': [0.1, 0.2], 'clip': False,
@@ -47,9 +48,6 @@ MNET_STAGES = (('stage1', ((3, 8, 2), (8, 16, 1), (16, 32, 2), (32, 32, 1), (32,
                ('stage2', ((64, 128, 2),) + ((128, 128, 1),) * 5),
                ('stage3', ((128, 256, 2), (256, 256, 1))))
 BACKBONES = {'resnet50': CFG_RE50, 'mobile0.25': CFG_MNET}
-# matrix-core policies: 'x3' split fp16 (parity grade, the default), 'fp32' exact, 'f16' the opt-in single-fp16 speed mode (KEEP_MMA_X1,
-# outside bit-parity with the default like ParseNet's: DESIGN 4.3)
-PRECISIONS = ('x3', 'fp32', 'f16')
 
 
 def backbone_of(state_dict):
@@ -189,12 +187,13 @@ def nms(dets, thresh):
     return keep
 
 
-class RetinaFaceEngine:
-    PRECISIONS = PRECISIONS
+class RetinaFaceEngine(PackedEngine):
+    NET = 'RetinaFace'
+    # 'f16' (outside bit-parity with the default: DESIGN 4.3): single fp16 on the 1x1 GEMMs, the stride-2 im2col shapes and the 3x3
+    # convolutions on 8 x 32-tileable maps; mobile0.25's 8 / 16-channel layers have no twin, its depthwise convolutions are not matrix products
+    X1_RULE = dict(flags=L.CONV_X1_GEMM)
 
     def __init__(self, state_dict, precision='x3', backbone=None):
-        if precision not in PRECISIONS:
-            raise ValueError(f"RetinaFace precision must be one of {PRECISIONS}, got {precision!r}")
         self.backbone = backbone or backbone_of(state_dict)
         self.cfg = BACKBONES[self.backbone]
         # LeakyReLU(0.1) in the FPN / SSH when out_channel <= 64 (retinaface_net.py:41-43,74-76), ReLU (= LeakyReLU(0)) otherwise
@@ -243,11 +242,7 @@ class RetinaFaceEngine:
             w = torch.cat([sd[f'{h}.{i}.conv1x1.weight'] for h in ('ClassHead', 'BboxHead', 'LandmarkHead')], 0)
             b = torch.cat([sd[f'{h}.{i}.conv1x1.bias'] for h in ('ClassHead', 'BboxHead', 'LandmarkHead')], 0)
             put(f'heads.{i}', w, b)
-        self._blob, self._index = pack_blob(t)
-        self.precision = precision
-        self.device = torch.device('cpu')
-        self.w = None
-        self.o = ops.Ops()
+        self._init_packed(*pack_blob(t), precision)
         self._priors = {}
         self._priors_dev = {}
         self.max_survivors = int(os.environ.get('KEEP_AMD_DETECT_SURVIVORS', '4096'))      # rows of the device-side compact list per frame
@@ -255,37 +250,13 @@ class RetinaFaceEngine:
         # score ordering + NMS of the survivors on the device (keep_retina_nms); 0: the numpy path of round 3 (the tests' reference)
         self.device_nms = os.environ.get('KEEP_AMD_DEVICE_NMS', '1') != '0' and self.max_survivors <= 4096
 
-    def to(self, device):
-        device = torch.device(device)
+    def x3_names(self):
+        return [n for n, (_, sh) in self._index.items() if len(sh) >= 2 and sh[-1] % 16 == 0 and not n.endswith('.dw.weight')]
+
+    def _uploaded(self):
         self._priors_dev = {}
-        if device.type != 'cuda':
-            self.w, self._dev = None, None
-            self.o.set_precision(self.o.mma)
-            self.device = device
-            return self
-        if device.index is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        L.load(check_device=True)
-        self.device = device
-        self._dev = torch.from_numpy(self._blob).to(device)
-        self.w = views(self._dev, self._index)
-        self._mean = torch.tensor(MEAN_BGR, dtype=torch.float32, device=device)
-        if self.precision in ('x3', 'f16'):
-            names = [n for n, (_, sh) in self._index.items() if len(sh) >= 2 and sh[-1] % 16 == 0 and not n.endswith('.dw.weight')]
-            bx, table = ops.make_x3_blob(self._dev, self._index, self.w, names)       # one power-of-two scale per tensor
-            self.o.set_precision(L.MMA_X3, self._dev, None, bx, 1.0, x3_scales=table)
-            if self.precision == 'f16':
-                # an x3 Ops that also holds a hi-only twin of every matrix weight with whole 32-channel K steps: a call runs single-fp16
-                # wherever the library's plan admits it (1x1 GEMMs, stride-2 im2col shapes, 3x3 on 8 x 32-tileable maps), x3 otherwise;
-                # the Cin = 3 stems and mobile0.25's 8 / 16-channel layers have no twin, its depthwise convolutions are not matrix products
-                n1 = [n for n in names if self._index[n][1][-1] % 32 == 0]
-                b1, t1 = ops.make_x1_blob(self._dev, self._index, self.w, n1)
-                self.o.set_x1_twin(b1, t1, mode='admitted')
-        elif self.precision == 'fp32':
-            self.o.set_precision(L.MMA_F32, self._dev, None)
-        else:
-            raise ValueError(f"RetinaFace precision must be one of {PRECISIONS}, got {self.precision!r}")
-        return self
+        if self.w is not None:
+            self._mean = torch.tensor(MEAN_BGR, dtype=torch.float32, device=self.device)
 
     # ------------------------------------------------------------------ network
     def _c(self, x, name, **kw):

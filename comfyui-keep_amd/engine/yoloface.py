@@ -28,7 +28,8 @@ import torch
 
 from . import hiplib as L
 from . import ops
-from .weights import pack_blob, views
+from .packed import PRECISIONS, PackedEngine      # noqa: F401  (PRECISIONS: re-exported)
+from .weights import pack_blob
 
 ANCHORS = ((4, 5, 8, 10, 13, 16), (23, 29, 43, 55, 73, 105), (146, 217, 231, 300, 335, 433))      # both yaml files
 STRIDES = (8.0, 16.0, 32.0)                                                                       # Model.__init__, yolo.py:103-105
@@ -137,19 +138,15 @@ def config_of(state_dict):
     return 'YOLOv5n' if 'model.1.branch1.0.weight' in keys else 'YOLOv5l'
 
 
-# matrix-core policies: 'x3' split fp16 (parity grade, the default), 'fp32' exact, 'f16' the opt-in single-fp16 speed mode (KEEP_MMA_X1,
-# outside bit-parity with the default like RetinaFace's: DESIGN 4.4)
-PRECISIONS = ('x3', 'fp32', 'f16')
-
-
-class YoloFaceEngine:
+class YoloFaceEngine(PackedEngine):
     """``bn_eps``: name of a BatchNorm -> its eps (the reference's Model keeps torch's 1e-5; checkpoints of the upstream trainer were
     made with 1e-3 -- ``EngineYoloModel.from_module`` reads the value off every module)."""
-    PRECISIONS = PRECISIONS
+    NET = 'YOLOv5-face'
+    # 'f16' (outside bit-parity with the default: DESIGN 4.4): RetinaFace's forms and -- KEEP_CONV_X1_HALO16 -- the 3x3 convolutions on
+    # 16 x 16 tiles (the 48 x 80 stride-16 level of a 720p frame's 768 x 1280 letterbox); the depthwise convolutions are not matrix products
+    X1_RULE = dict(flags=L.CONV_X1_GEMM | L.CONV_X1_HALO16)
 
     def __init__(self, state_dict, precision='x3', bn_eps=None):
-        if precision not in PRECISIONS:
-            raise ValueError(f"YOLOv5-face precision must be one of {PRECISIONS}, got {precision!r}")
         self.name = config_of(state_dict)
         spec = yolo_state_dict_spec(self.name)
         missing = [k for k in spec if k not in state_dict]
@@ -205,43 +202,11 @@ class YoloFaceEngine:
                     put(f'{p}.m.{k}', sd[f'{p}.m.{k}.weight'], sd[f'{p}.m.{k}.bias'])
                 # anchor_grid (pixels) is what the decode multiplies by (yolo.py:59-74); it travels with the weights
                 t['anchor_grid'] = sd[f'{p}.anchor_grid'].reshape(3, 6).contiguous()
-        self._blob, self._index = pack_blob(t)
-        self.precision = precision
-        self.device = torch.device('cpu')
-        self.w = None
-        self.o = ops.Ops()
+        self._init_packed(*pack_blob(t), precision)
 
-    def to(self, device):
-        device = torch.device(device)
-        if device.type != 'cuda':
-            self.w, self._dev = None, None
-            self.o.set_precision(self.o.mma)
-            self.device = device
-            return self
-        if device.index is None:
-            device = torch.device('cuda', torch.cuda.current_device())
-        L.load(check_device=True)
-        self.device = device
-        self._dev = torch.from_numpy(self._blob).to(device)
-        self.w = views(self._dev, self._index)
-        if self.precision in ('x3', 'f16'):
-            names = [n for n, (_, sh) in self._index.items() if len(sh) >= 2 and sh[-1] % 16 == 0 and n.endswith('.weight')
-                     and n[:-7] not in self._dw and n != 'anchor_grid']
-            bx, table = ops.make_x3_blob(self._dev, self._index, self.w, names)
-            self.o.set_precision(L.MMA_X3, self._dev, None, bx, 1.0, x3_scales=table)
-            if self.precision == 'f16':
-                # an x3 Ops that also holds a hi-only twin of every matrix weight with whole 32-channel K steps: a call runs single-fp16
-                # wherever the library's plan admits it (1x1 GEMMs, stride-2 im2col shapes, 3x3 on 8 x 32 tiles, and -- KEEP_CONV_X1_HALO16
-                # -- on 16 x 16 tiles: the 48 x 80 stride-16 level of a 720p frame's 768 x 1280 letterbox), x3 otherwise; the Cin = 3 stem has no twin, the
-                # depthwise convolutions are not matrix products
-                n1 = [n for n in names if self._index[n][1][-1] % 32 == 0]
-                b1, t1 = ops.make_x1_blob(self._dev, self._index, self.w, n1)
-                self.o.set_x1_twin(b1, t1, mode='admitted', flags=L.CONV_X1_GEMM | L.CONV_X1_HALO16)
-        elif self.precision == 'fp32':
-            self.o.set_precision(L.MMA_F32, self._dev, None)
-        else:
-            raise ValueError(f"YOLOv5-face precision must be one of {PRECISIONS}, got {self.precision!r}")
-        return self
+    def x3_names(self):
+        return [n for n, (_, sh) in self._index.items() if len(sh) >= 2 and sh[-1] % 16 == 0 and n.endswith('.weight')
+                and n[:-7] not in self._dw and n != 'anchor_grid']
 
     # ------------------------------------------------------------------ building blocks
     def _c(self, x, name, act=L.ACT_SILU, stride=1, **kw):

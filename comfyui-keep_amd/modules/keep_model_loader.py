@@ -72,14 +72,18 @@ class KEEPModelPack:
         model_management.soft_empty_cache()
 
 
+def _precision_knob(name, environ):
+    from ..engine.packed import PRECISIONS
+    value = (os.environ if environ is None else environ).get(name, '') or 'x3'
+    if value not in PRECISIONS:
+        raise ValueError(f"{name} must be one of {', '.join(PRECISIONS)}; got {value!r}")
+    return value
+
+
 def parse_precision_knob(environ=None):
     """KEEP_AMD_PARSE_PRECISION=x3|fp32|f16 (default x3): the matrix-core policy of the face-parsing network, read ONCE when the
     pack's helper is built.  'f16' is the opt-in single-fp16 speed mode, outside bit-parity with the default."""
-    from ..engine.parsenet import PRECISIONS
-    value = (os.environ if environ is None else environ).get('KEEP_AMD_PARSE_PRECISION', '') or 'x3'
-    if value not in PRECISIONS:
-        raise ValueError(f"KEEP_AMD_PARSE_PRECISION must be one of {', '.join(PRECISIONS)}; got {value!r}")
-    return value
+    return _precision_knob('KEEP_AMD_PARSE_PRECISION', environ)
 
 
 def detect_precision_knob(environ=None):
@@ -87,11 +91,7 @@ def detect_precision_knob(environ=None):
     mobile0.25) and YOLOv5-face (YOLOv5l and YOLOv5n) -- read ONCE when the pack's helper is built.  'f16' is the
     opt-in single-fp16 speed mode, outside bit-parity with the default; unset, every detector runs x3, bit-equal to an engine built
     without the knob."""
-    from ..engine.retinaface import PRECISIONS
-    value = (os.environ if environ is None else environ).get('KEEP_AMD_DETECT_PRECISION', '') or 'x3'
-    if value not in PRECISIONS:
-        raise ValueError(f"KEEP_AMD_DETECT_PRECISION must be one of {', '.join(PRECISIONS)}; got {value!r}")
-    return value
+    return _precision_knob('KEEP_AMD_DETECT_PRECISION', environ)
 
 
 def engine_facelib(helper):

@@ -91,7 +91,8 @@ def test_x1_kernel_numerics_against_fp64(kind):
     ref = F.conv2d(xp, w.double(), b.double(), stride=stride)
     sabs = F.conv2d(xp.abs(), w.double().abs(), None, stride=stride)
     wp = w.permute(0, 2, 3, 1).contiguous().cuda()
-    kw = dict(stride=stride, pad=1, ksize=3, upsample=up, reflect=True, mma=L.MMA_X1, stats='amax')
+    # (the 3 -> 64 layer has no x1 kernel: the engine runs it on its base policy, exact f32)
+    kw = dict(stride=stride, pad=1, ksize=3, upsample=up, reflect=True, mma=L.MMA_X1 if Cin % 32 == 0 else L.MMA_F32, stats='amax')
     floor = torch.zeros_like(ref)
     if Cin % 32 == 0:
         tw, sw = x1_twin(wp, Cin)
@@ -171,7 +172,7 @@ def test_parsenet_f16_against_the_reference_logits():
     for key, size, n, gy, gx, step in (('parsenet128', 128, 2, 1, 2, 4), ('parsenet512', 512, 1, 3, 5, 16)):
         W = PN.synth_parsenet_state_dict(seed=0, in_size=size, out_size=size)
         eng = PN.ParseNetEngine(W, in_size=size, out_size=size, precision='f16').to('cuda')
-        assert eng.o.mma == L.MMA_X1
+        assert eng.o.mma == L.MMA_F32 and eng.o.blobx1 is not None and eng.o.blobx3 is None      # the twin rides on exact f32
         x = op_input(key, (n, 3, size, size))
         logits = eng.logits(x.cuda()).cpu().numpy()
         assert np.isfinite(logits).all()
@@ -193,6 +194,35 @@ def test_parsenet_f16_against_the_reference_logits():
         assert errs[key + '_worst_margin'] <= 2 * E16_BOUND, (key, errs[key + '_worst_margin'])
         # condition on the fixture (also checkable on the CPU from the golden alone): the pixels the statement above protects
         assert _golden_fixture_share(key, 2 * E16_BOUND) >= 0.90, (key, _golden_fixture_share(key, 2 * E16_BOUND))
+
+
+# the kernel of the one layer without an x1 twin (the Cin = 3 convolution) under 'f16', as keep_conv2d_plan names it: read off the 'f16' launch
+# list of ParseNetEngine(128, 128) at commit bc12ff0 (where 'f16' was an Ops policy of its own) -- exact f32, then as now
+RGB_KERNEL_F16 = 'conv_f32_kernel<2, 2, 1, 1>'
+
+
+def test_parsenet_f16_launch_census():
+    """One ParseNet(128, 128) forward of 2 images per policy: under 'f16' EVERY convolution with whole 32-channel K steps is an x1 launch
+    -- a layer the library refused would run on the base policy (exact f32) without a word -- the rest (the 3 -> 64 layer) runs the
+    kernel it always ran, and the number of launches is the x3 policy's."""
+    W = PN.synth_parsenet_state_dict(seed=0, in_size=128, out_size=128)
+    x = nhwc(op_input('parsenet128', (2, 3, 128, 128)))
+    census = {}
+    for prec in ('f16', 'x3'):
+        eng = PN.ParseNetEngine(W, in_size=128, out_size=128, precision=prec).to('cuda')
+        eng.o.census = census[prec] = {}
+        assert torch.isfinite(eng.logits_nhwc(x)).all()
+    cins = []                                     # Cin of every convolution of engine.blocks
+    for name, kind, cin, cout in eng.blocks:
+        cins += [cin] if kind == 'conv' else [cin] * (2 if f'{name}.shortcut.weight' in eng.w else 1) + [cout]
+    c16, c3 = census['f16'], census['x3']
+    print('[f16-census] parsenet f16:', sorted(c16.items()), '\n[f16-census] parsenet x3 :', sorted(c3.items()))
+    n_x1 = sum(1 for c in cins if c % 32 == 0)
+    assert 0 < n_x1 == len(cins) - 1 and cins.count(3) == 1
+    assert sum(n for k, n in c16.items() if k in X1_KERNELS) == n_x1
+    assert sum(c16.values()) == sum(c3.values()) == len(cins)
+    assert {k: n for k, n in c16.items() if k not in X1_KERNELS} == {RGB_KERNEL_F16: 1}
+    assert not any(k in X1_KERNELS for k in c3)
 
 
 def test_parsenet_f16_batch_of_16_equals_one_by_one():

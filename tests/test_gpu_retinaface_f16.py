@@ -62,7 +62,7 @@ def test_f16_against_the_reference_goldens(backbone):
     img, *keys = GOLD[backbone]
     x = nhwc(op_input(img, (2, 3, 160, 224), 100.0))
     eng = engine(backbone, 'f16')
-    assert eng.o.mma == L.MMA_X3 and eng.o.blobx1 is not None and eng.o.x1_mode == 'admitted'
+    assert eng.o.mma == L.MMA_X3 and eng.o.blobx1 is not None and eng.o.x1_flags == L.CONV_X1_GEMM and eng.o.x1_base_kernel is None
     got16, got3 = heads(eng, x), heads(engine(backbone, 'x3'), x)
     errs = {}
     for g16, g3, key in zip(got16, got3, keys):

@@ -119,14 +119,33 @@ def test_hi_only_blob_is_fp16_of_scaled_weights_in_the_packed_order():
         covered[off:off + t[n].numel()] = True
     assert not bx[~covered].any()                                # tensors outside `names` have no twin
 
+    # ParseNet's rule: the twin rides on exact f32 (the engine holds no x3 twin), and carries its own scale table
+    assert PN.ParseNetEngine.X1_RULE == dict(flags=0) and PN.ParseNetEngine.X1_BASE == L.MMA_F32
+    rule = dict(PN.ParseNetEngine.X1_RULE, base=PN.ParseNetEngine.X1_BASE)
     o = ops.Ops()
-    o.set_precision(L.MMA_X1, dev, None, bx, 1.0, x3_scales=table)
+    o.set_precision(L.MMA_F32, dev, None)
+    o.set_x1_twin(bx, table, **rule)
+    assert o.mma == L.MMA_F32 and o.blobx3 is None and o.x1_flags == 0
     off, _ = index['b.weight']
-    assert o.x3_twin(w['b.weight']).data_ptr() == bx[off:].data_ptr() and o.x3_twin(w['b.weight']).numel() == w['b.weight'].numel()
+    assert o.x1_twin(w['b.weight']).data_ptr() == bx[off:].data_ptr() and o.x1_twin(w['b.weight']).numel() == w['b.weight'].numel()
+    assert o.x1_twin(w['rgb.weight']) is None and o.x3_twin(w['b.weight']) is None      # a tensor without a twin stays on the base
+    assert o.x1_twin(torch.zeros(64, 3, 3, 32)) is None                                      # ... and so does a view outside the packed blob
+    assert o._x1_of(w['a.weight'])[1] == 1.0 / ops.x3_scale_for(float(t['a.weight'].abs().max()))
+    assert o._x1_of(w['b.weight'][8:24])[1] == 1.0 / ops.x3_scale_for(float(t['b.weight'].abs().max()))      # a row slice: its tensor's scale
+    o.set_precision(L.MMA_F32, dev, None)
+    assert o.blobx1 is None and o.x1_twin(w['b.weight']) is None                            # a policy change drops the twin
+    o.set_precision(L.MMA_X3, dev, None, x3, 1.0, x3_scales=table3)
+    with pytest.raises(ValueError, match='fp32 policy'):                                    # the twin's stated base is not this Ops'
+        o.set_x1_twin(bx, table, **rule)
+    # x3_twin / x3_scale_of on an x3 Ops: two int16 per weight at twice the offset, the tensor's own scale
+    assert o.x3_twin(w['b.weight']).data_ptr() == x3[2 * off:].data_ptr() and o.x3_twin(w['b.weight']).numel() == 2 * w['b.weight'].numel()
     assert o.x3_twin(w['rgb.weight']) is None
     assert o.x3_scale_of(w['a.weight']) == 1.0 / ops.x3_scale_for(float(t['a.weight'].abs().max()))
-    with pytest.raises(ValueError):
-        o.set_precision(7)
+    with pytest.raises(RuntimeError, match='x3 blob'):
+        o.x3_scale_of(w['a.bias'])
+    for bad in (7, L.MMA_X1):
+        with pytest.raises(ValueError):
+            o.set_precision(bad)
 
 
 def test_library_refuses_x1_where_no_kernel_exists():

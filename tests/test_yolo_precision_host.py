@@ -66,14 +66,16 @@ def test_loader_hands_the_knob_to_the_yolo_engine(monkeypatch):
 
 
 def test_twin_flags_default_leaves_the_gemm_bit_alone():
+    from comfyui_keep_amd.engine import retinaface as RF
     o = ops.Ops()
     assert o.x1_flags == L.CONV_X1_GEMM
-    o.set_x1_twin(None, None, mode='admitted')
+    o.set_x1_twin(None, None)
     assert o.x1_flags == L.CONV_X1_GEMM                  # RetinaFace's call: unchanged
-    o.set_x1_twin(None, None, mode='admitted', flags=BOTH)
+    o.set_x1_twin(None, None, flags=BOTH)
     assert o.x1_flags == BOTH
     o.set_precision(L.MMA_F32)
-    assert o.x1_flags == L.CONV_X1_GEMM and o.x1_mode == 'stream'
+    assert o.x1_flags == L.CONV_X1_GEMM and o.x1_base_kernel is None and o.x1_base == L.MMA_X3
+    assert RF.RetinaFaceEngine.X1_RULE == dict(flags=L.CONV_X1_GEMM) and YF.YoloFaceEngine.X1_RULE == dict(flags=BOTH)
 
 
 def _planner():
