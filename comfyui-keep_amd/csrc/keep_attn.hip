@@ -2741,13 +2741,7 @@ static int launch_token_linear(const float* x, const void* w, const float* bias,
   const size_t lds = (size_t)(NT * 128 + 128) * (TL_K + 8) * 2;     // W + X tile (the output staging aliases the X tile)
   const int rc = keep_raise_lds_limit<token_linear_kernel<NT>>("keep_token_linear");
   if (rc != KEEP_OK) return rc;
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-    if (n_cu <= 0) n_cu = 256;
-  }
+  const int n_cu = keep_num_cu();
   const int n_tiles = cdiv(M, 128);
   const int per_cu = (NT == 1) ? 2 : 1;
   const int blocks = n_tiles < per_cu * n_cu ? n_tiles : per_cu * n_cu;

@@ -34,6 +34,18 @@ void keep_set_error(const char* fmt, ...);
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// compute units of the current device (asked once per translation unit; 256 where the runtime cannot say)
+static inline int keep_num_cu() {
+  static int n_cu = 0;
+  if (n_cu == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
+    if (n_cu <= 0) n_cu = 256;
+  }
+  return n_cu;
+}
+
 // Raises Kernel's dynamic LDS limit to the 160 KB of a gfx950 CU before its first launch: once per kernel instantiation and
 // process (one flag per instantiation of this template; idempotent, benign if raced).  `who` opens the error text.
 template <auto Kernel>

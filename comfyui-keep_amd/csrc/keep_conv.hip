@@ -1689,53 +1689,16 @@ __global__ void conv_splitk_reduce4_kernel(ConvP p) {
 }
 
 // ------------------------------------------------------------------------------------------------ plan + dispatch
-// ONE place decides which kernel a keep_conv2d call runs on, its tile, the split-K factor and the layout of the epilogue
-// statistics: plan_conv().  keep_conv2d_plan() exposes that decision to the host, which sizes the workspace / statistics
-// buffers from it and never re-derives kernel internals (a retune here cannot silently corrupt a caller).
-int keep_conv2d_x3_halo(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
-bool keep_conv_x3_up2_ok(const keep_conv2d_args* a);
-int keep_conv2d_x3_gather(const keep_conv2d_args* a, ConvP& p, int tile, hipStream_t st);
-bool keep_conv_x3_gather_is_gemm(const keep_conv2d_args* a);
-int keep_conv2d_x3_c3(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
-bool keep_conv_x3_halo_ok(const keep_conv2d_args* a);
-bool keep_conv_x3_stream_ok(const keep_conv2d_args* a, const ConvP& p, int split_k);
-bool keep_conv_x3_gather_ok(const keep_conv2d_args* a, const ConvP& p);
-bool keep_conv_x1_stream_ok(const keep_conv2d_args* a, const ConvP& p);
-bool keep_conv_x1_gather_ok(const keep_conv2d_args* a, const ConvP& p);
-bool keep_conv_x1_gemm_ok(const keep_conv2d_args* a, const ConvP& p);
-bool keep_conv_x1_halo16_ok(const keep_conv2d_args* a);
-bool keep_gemm_x3l_ok(const keep_conv2d_args* a);
-int keep_gemm_x3l_waves(const keep_conv2d_args* a);
-int keep_conv2d_x3_gemm_lat(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
-
-enum ConvPath {
-  PATH_COUT4 = 0, PATH_C3, PATH_HALO_F32, PATH_HALO_BF16, PATH_HALO_BF16_V1, PATH_GATHER_BF16, PATH_GATHER_F32, PATH_HALO_X3,
-  PATH_GATHER_X3, PATH_NEEDS_PRENORM, PATH_C3_X3
-};
-
-struct ConvPlan {
-  ConvPath path;
-  int tile;            // gather kernels: 0 = 128x32 (4,1,1,1), 1 = 64x64 (2,2,1,1), 2 = 128x128 (2,2,2,2)
-  bool plain, wide, bk256;
-  int split_k;
-  int stats_rows;      // output pixels per statistics partial; 0 = this call cannot emit statistics
-  int wants_bf16_input, out_bf16_ok;
-  bool amax_ok;          // this path can fill x3_out_amax (x3 kernels, single pass)
-  char kernel[64];
-};
-
-static int n_cu_cached() {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-    if (n_cu <= 0) n_cu = 256;
-  }
-  return n_cu;
-}
-
-static const int kTargetWaves = 1024;
+// plan_conv() decides, once per keep_conv2d call, everything a caller can observe or must size buffers for: the kernel family and its form
+// (ConvPlan::path / form, keep_conv_common.h), the block tile, the split-K factor, the statistics partition and whether max |out| rides
+// along.  Under the parity policies (f32, x3, x1) it reads the per-image geometry and the fixed reference batch, never the real N, so a
+// clip's bits do not depend on its batch-mates.  keep_conv2d_plan() reports the decision; the host sizes workspace / statistics buffers
+// from it and never mirrors a rule of this file.
+// A launcher receives the plan and switches on the form.  From the real N it may still choose among kernels that evaluate the SAME sums
+// in the SAME order into the SAME partition -- 64-pixel blocks for a map with few items, the 64 x 64 tile for few rows (statistics then
+// from a replica kernel), the shallow pipeline beyond 262144 rows, which kernel walks canonical K slices -- because only occupancy
+// depends on N.  Nothing a launcher chooses changes a value, a buffer size or the reported plan.
+static const int kTargetWaves = 1024;      // below this many matrix-core waves a launch cannot fill 256 CUs x 4 SIMDs -> split K
 // Parity policies (exact f32, x3): every choice that changes the ORDER of a floating-point sum -- the split-K factor, and with
 // it the statistics partition -- is made from the per-image geometry and this fixed reference batch, never from the actual N.
 // A clip's result is then bit-identical whatever its batch-mates are (KeepNet.clips_per_call follows free HBM; round 2's plans
@@ -1747,7 +1710,7 @@ static const int kTargetWaves = 1024;
 static long plan_ref_images(const keep_conv2d_args* a) { return a->plan_ref_images > 0 ? a->plan_ref_images : 16; }
 // gather kernels: launches of at most this many output rows use 64x64 tiles (more blocks), larger ones 128x128.  A tuning
 // rule the HOST never mirrors (keep_conv2d_plan reports what follows from it): KEEP_CONV_SMALL_TILES forces the small tile (tests).
-static long small_m_threshold(const keep_conv2d_args* a) { return (a->flags & KEEP_CONV_SMALL_TILES) ? (1L << 62) : 4096; }   // below this many matrix-core waves a launch cannot fill 256 CUs x 4 SIMDs -> split K
+static long small_m_threshold(const keep_conv2d_args* a) { return (a->flags & KEEP_CONV_SMALL_TILES) ? (1L << 62) : 4096; }
 
 static int validate_conv(const keep_conv2d_args* a) {
   KEEP_REQUIRE(a != nullptr, "keep_conv2d: null args");
@@ -1767,17 +1730,14 @@ static int validate_conv(const keep_conv2d_args* a) {
   KEEP_REQUIRE(!a->aux || a->residual, "keep_conv2d: aux epilogue requires residual");
   KEEP_REQUIRE(!a->residual || a->res_ld >= a->Cout, "keep_conv2d: res_ld smaller than Cout");
   KEEP_REQUIRE(a->split_k >= 0, "keep_conv2d: split_k must be >= 0 (0 = let the library choose)");
-  {
-    const int Hv = a->upsample ? 2 * a->H : a->H, Wv = a->upsample ? 2 * a->W : a->W;
-    KEEP_REQUIRE((long)(a->Ho - 1) * a->stride - a->pad_t < Hv && (long)(a->Wo - 1) * a->stride - a->pad_l < Wv,
-                 "keep_conv2d: output extent %dx%d inconsistent with input %dx%d", a->Ho, a->Wo, Hv, Wv);
-  }
+  const int Hv = a->upsample ? 2 * a->H : a->H, Wv = a->upsample ? 2 * a->W : a->W;
+  KEEP_REQUIRE((long)(a->Ho - 1) * a->stride - a->pad_t < Hv && (long)(a->Wo - 1) * a->stride - a->pad_l < Wv,
+               "keep_conv2d: output extent %dx%d inconsistent with input %dx%d", a->Ho, a->Wo, Hv, Wv);
   KEEP_REQUIRE(a->mma == KEEP_MMA_F32 || a->mma == KEEP_MMA_BF16 || a->mma == KEEP_MMA_X3 || a->mma == KEEP_MMA_X1, "keep_conv2d: bad mma %d", a->mma);
   KEEP_REQUIRE(a->upsample == 0 || a->upsample == 1 || (a->upsample == KEEP_UPSAMPLE_X2_PHASES && a->mma == KEEP_MMA_X3),
                "keep_conv2d: upsample must be 0, 1 or KEEP_UPSAMPLE_X2_PHASES (KEEP_MMA_X3 only), got %d", a->upsample);
   KEEP_REQUIRE(a->pad_mode == KEEP_PAD_ZERO || a->pad_mode == KEEP_PAD_REFLECT, "keep_conv2d: bad pad_mode %d", a->pad_mode);
   if (a->pad_mode == KEEP_PAD_REFLECT) {
-    const int Hv = a->upsample ? 2 * a->H : a->H, Wv = a->upsample ? 2 * a->W : a->W;
     if (a->mma == KEEP_MMA_BF16 || a->dtype != KEEP_F32 || a->pad_t != a->pad_l || a->pad_t >= Hv || a->pad_t >= Wv ||
         a->pad_t != a->KH / 2 || a->KH != a->KW) {
       keep_set_error("keep_conv2d: KEEP_PAD_REFLECT needs fp32 tensors, KEEP_MMA_F32 / KEEP_MMA_X3, a square odd kernel and pad_t == pad_l == KH/2 < min(H, W)");
@@ -1792,14 +1752,10 @@ static int validate_conv(const keep_conv2d_args* a) {
   return KEEP_OK;
 }
 
-// Pointer-independent geometry checks use the pointers only for their alignment; the plan query passes the same struct
+// The launch parameters that follow from the argument struct alone (the gather planners add flatk / flatk_f32 / nsteps, the launch split_k
+// and out_amax).  Pointer-independent geometry checks use the pointers only for their alignment; the plan query passes the same struct
 // the launch will see (NULL optional tensors stay NULL), so plan and launch always agree.
-static int plan_conv(const keep_conv2d_args* a, ConvP& p, ConvPlan& pl) {
-  memset(&pl, 0, sizeof(pl));
-  const long M_real = (long)a->N * a->Ho * a->Wo;
-  // rows the HEURISTICS below see (tile, split-K): per-image rows x the fixed reference batch under the parity policies,
-  // the real row count under the bf16 speed policy; launches and buffer sizes always use the real M (p.M)
-  const long M = a->mma == KEEP_MMA_BF16 ? M_real : plan_ref_images(a) * (long)a->Ho * a->Wo;      // (KEEP_MMA_X1 plans like x3: batch-invariant)
+static void fill_conv_params(const keep_conv2d_args* a, ConvP& p) {
   p.in = (const float*)a->in;
   p.w = a->weight;
   p.wb = (const unsigned short*)a->weight_bf16;
@@ -1827,7 +1783,7 @@ static int plan_conv(const keep_conv2d_args* a, ConvP& p, ConvPlan& pl) {
   p.stride = a->stride; p.pad_t = a->pad_t; p.pad_l = a->pad_l; p.Ho = a->Ho; p.Wo = a->Wo;
   p.in_ld = a->in_ld; p.out_ld = a->out_ld; p.res_ld = a->res_ld;
   p.upsample = a->upsample; p.pro_act = a->pro_act; p.epi_act = a->epi_act; p.aux_w = a->aux_w;
-  p.M = (int)M_real;
+  p.M = (int)((long)a->N * a->Ho * a->Wo);
   p.cchunks = (a->Cin + BK - 1) / BK;
   p.nsteps = a->KH * a->KW * p.cchunks;
   p.in_bf16 = (a->dtype == KEEP_BF16) ? 1 : 0;
@@ -1843,286 +1799,280 @@ static int plan_conv(const keep_conv2d_args* a, ConvP& p, ConvPlan& pl) {
   p.flatk_f32 = 0;
   p.stats = a->stats_out;
   p.stats_P = a->stats_P;
-  const bool no_pro = !a->pro_scale && a->pro_act == KEEP_PRO_NONE;
-  const bool is33s1 = a->KH == 3 && a->KW == 3 && a->stride == 1 && a->pad_t == 1 && a->pad_l == 1;
-  const bool same_size = a->Ho == (a->upsample ? 2 * a->H : a->H) && a->Wo == (a->upsample ? 2 * a->W : a->W);
-  const bool tileable = (a->Ho % 8 == 0 && a->Wo % 32 == 0) || (a->Ho % 16 == 0 && a->Wo % 16 == 0);
-  const bool pro_al = !a->pro_scale || ((uintptr_t)a->pro_scale % 16 == 0 && (uintptr_t)a->pro_shift % 16 == 0);
-  const bool epi_al = (a->out_ld % 4 == 0) && ((uintptr_t)a->out % 16 == 0) &&
-                      (!a->residual || (a->res_ld % 4 == 0 && (uintptr_t)a->residual % 16 == 0)) &&
-                      (!a->aux || (uintptr_t)a->aux % 16 == 0) && (!a->bias || (uintptr_t)a->bias % 16 == 0);
-  pl.wide = (a->Ho % 8 == 0 && a->Wo % 32 == 0);
-  const int ncb = (a->Cout + 63) / 64;
-  int mma = a->mma;
-  int auto_split = 1;
+}
 
-  // ---- <= 4 output channels: exact-fp32 VALU kernel in every precision policy
-  const bool reflect = a->pad_mode == KEEP_PAD_REFLECT;
-  if (a->Cout <= 4 && is33s1 && !reflect && !a->upsample && a->dtype == KEEP_F32 && a->out_dtype != KEEP_BF16 && a->Cin % SC_CH == 0 &&
-      a->in_ld % 4 == 0 && (uintptr_t)a->in % 16 == 0 && a->Ho == a->H && a->Wo == a->W && a->Ho % SC_TH == 0 &&
-      a->Wo % SC_TW == 0 && !a->residual && !a->aux && a->split_k <= 1 && pro_al && !(a->flags & KEEP_CONV_NO_COUT4)) {
-    pl.path = PATH_COUT4;
-    pl.split_k = 1;
-    snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_cout4_kernel");
-    return KEEP_OK;
-  }
-  // ---- RGB first convolutions, bf16 policy: persistent im2col-in-LDS kernel
-  if (mma == KEEP_MMA_BF16 && is33s1 && !a->upsample && a->Cin <= 3 && a->Cout % 4 == 0 && a->Cout >= 32 && a->dtype == KEEP_F32 &&
-      a->out_dtype != KEEP_BF16 && a->Ho == a->H && a->Wo == a->W && a->Ho % 8 == 0 && a->Wo % 32 == 0 && no_pro && !a->residual &&
-      !a->aux && a->split_k <= 1 && a->out_ld % 4 == 0 && (uintptr_t)a->out % 16 == 0 && (!a->bias || (uintptr_t)a->bias % 16 == 0) &&
-      !(a->flags & KEEP_CONV_NO_C3)) {
-    pl.path = PATH_C3;
-    pl.split_k = 1;
-    pl.stats_rows = 64;
-    snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_c3_kernel");
-    return KEEP_OK;
-  }
-  // ---- single fp16 (the opt-in speed policy of ParseNet and of the KEEP network's 'f16'): the x1 instantiations of the streaming halo kernel and of the im2col gather kernel,
-  // planned by the x3 rules; every other shape is refused -- there is no kernel of this grade for it and no silent change of policy
-  if (mma == KEEP_MMA_X1) {
-    KEEP_REQUIRE(a->dtype == KEEP_F32 && a->out_dtype != KEEP_BF16, "keep_conv2d: KEEP_MMA_X1 takes and writes fp32 tensors");
-    const bool have_w = a->weight_x3 != nullptr && (uintptr_t)a->weight_x3 % 16 == 0 && a->x3_acc_scale > 0.f;
-    if (have_w && is33s1 && keep_conv_x3_halo_ok(a) && keep_conv_x1_stream_ok(a, p) && a->split_k <= 1 && !(a->flags & KEEP_CONV_NO_HALO_X3)) {
-      pl.path = PATH_HALO_X3;
-      pl.split_k = 1;
-      pl.stats_rows = 256;
-      pl.amax_ok = true;
-      // (the x1 instantiations, as rocprofv3 prints them: <prologue activation, GroupNorm affine, X1>)
-      snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_x3s_kernel<%d, %s, true>", a->pro_act, a->pro_scale ? "true" : "false");
-      return KEEP_OK;
-    }
-    // KEEP_CONV_X1_HALO16 (opt-in bit, like KEEP_CONV_X1_GEMM below: without it nothing changes): the x1 instantiation of the 16 x 16-tile halo
-    // kernel for the maps the streaming form does not tile.  Only where the x3 plan of the same call -- the rule of the KEEP_MMA_X3 branch below,
-    // from the reference batch, never from N -- is un-split: the form has no split-K, and a call x3 splits keeps x3's partition.
-    if ((a->flags & KEEP_CONV_X1_HALO16) && have_w && is33s1 && keep_conv_x1_halo16_ok(a) && !(a->flags & KEEP_CONV_NO_HALO_X3)) {
-      const long items = (M / 256) * ncb;
-      auto_split = items >= 256 ? 1 : (int)max(1L, min(min(512L / items, (long)a->Cin / 32), 16L));
-      int x3_split = a->split_k > 0 ? a->split_k : auto_split;
-      if (x3_split > a->Cin / 16) x3_split = a->Cin / 16;
-      if (x3_split == 1) {
-        pl.path = PATH_HALO_X3;
-        pl.split_k = 1;
-        pl.stats_rows = 256;
-        pl.amax_ok = true;
-        // (<TW, PRO, SIMPLE_EPI, FASTACT, WDMA, UP2, X1> as rocprofv3 prints it)
-        snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_x3_kernel<16, 0, %s, true, true, false, true>", a->epi_act == KEEP_ACT_NONE ? "true" : "false");
-        return KEEP_OK;
-      }
-      keep_set_error("keep_conv2d: KEEP_MMA_X1 (with KEEP_CONV_X1_HALO16) has no kernel for this call: KEEP_MMA_X3 plans it with split-K = %d "
-                     "(plan_ref_images = %ld) and the 16 x 16-tile single-fp16 form is un-split", x3_split, plan_ref_images(a));
-      return KEEP_EUNSUP;
-    }
-    // (under KEEP_CONV_X1_GEMM also a 3x3 stride-1 pad-1 convolution NO halo kernel takes -- a ragged map, where x3 itself runs this im2col kernel)
-    if (have_w && (!is33s1 || ((a->flags & KEEP_CONV_X1_GEMM) && !keep_conv_x3_halo_ok(a))) && keep_conv_x1_gather_ok(a, p) &&
-        !(a->flags & KEEP_CONV_NO_GATHER_X3)) {
-      pl.path = PATH_GATHER_X3;
-      pl.tile = (a->Cout <= 64 || M <= small_m_threshold(a)) ? 1 : 2;
-      pl.plain = true;
-      const int steps = a->KH * a->KW * (a->Cin / 32);
-      const long blocks = pl.tile == 1 ? (long)cdiv(M, 64) * cdiv(a->Cout, 64) : (long)cdiv(M, 128) * cdiv(a->Cout, 128);
-      const long waves = blocks * 4;
-      auto_split = (waves >= kTargetWaves || steps < 8) ? 1 : (int)max(1L, min(min(4L * kTargetWaves / waves, (long)steps / 2), 32L));
-      pl.split_k = a->split_k > 0 ? a->split_k : auto_split;
-      if (pl.split_k > steps) pl.split_k = steps;
-      pl.stats_rows = pl.tile == 1 ? 64 : 128;
-      pl.amax_ok = pl.split_k == 1 && ((long)a->Ho * a->Wo) % (pl.tile == 1 ? 32 : 64) == 0;
-      // (the x1 instantiation; its trailing template booleans as 0 / 1: the name has 63 characters)
-      snprintf(pl.kernel, sizeof(pl.kernel), "conv_x3_kernel<%s, true, 0, 0, 1, 0, 1>", pl.tile == 1 ? "2, 2, 1, 1" : "2, 2, 2, 2");
-      return KEEP_OK;
-    }
-    // KEEP_CONV_X1_GEMM (opt-in bit: without it the 1x1 GEMM form stays refused, as every v22 / v23 caller was promised): the x1 instantiation of
-    // the GEMM variant of conv_x3_kernel, planned by the x3 rules of the gather path above -- tile and split-K from the reference batch.  The
-    // latency form (gemm_x3l_kernel) has no x1 twin: a shape x3 would send there takes this tile kernel too.
-    if (a->flags & KEEP_CONV_X1_GEMM) {
-      if (have_w && !is33s1 && keep_conv_x1_gemm_ok(a, p) && !(a->flags & KEEP_CONV_NO_GATHER_X3)) {
-        pl.path = PATH_GATHER_X3;
-        pl.tile = (a->Cout <= 64 || M <= small_m_threshold(a)) ? 1 : 2;
-        pl.plain = true;
-        const int steps = a->Cin / 32;
-        const long blocks = pl.tile == 1 ? (long)cdiv(M, 64) * cdiv(a->Cout, 64) : (long)cdiv(M, 128) * cdiv(a->Cout, 128);
-        const long waves = blocks * 4;
-        auto_split = (waves >= kTargetWaves || steps < 8) ? 1 : (int)max(1L, min(min(4L * kTargetWaves / waves, (long)steps / 2), 32L));
-        pl.split_k = a->split_k > 0 ? a->split_k : auto_split;
-        if (pl.split_k > steps) pl.split_k = steps;
-        pl.stats_rows = pl.tile == 1 ? 64 : 128;
-        pl.amax_ok = pl.split_k == 1 && ((long)a->Ho * a->Wo) % (pl.tile == 1 ? 32 : 64) == 0;
-        // (<tile, PLAIN, ONE, KSL, DEEP, KAL, X1>, the trailing booleans as 0 / 1 like the im2col form's name)
-        snprintf(pl.kernel, sizeof(pl.kernel), "conv_x3_kernel<%s, true, 1, 0, 1, 0, 1>", pl.tile == 1 ? "2, 2, 1, 1" : "2, 2, 2, 2");
-        return KEEP_OK;
-      }
-      if (a->flags & KEEP_CONV_X1_HALO16) {
-        keep_set_error("keep_conv2d: KEEP_MMA_X1 (with KEEP_CONV_X1_HALO16) has no kernel for this call: it needs weight_x3 (the hi-only fp16 twin) and "
-                       "x3_acc_scale, Cin %% 32 == 0, no aux / in2 / LayerNorm, and one of: a 3x3 stride-1 pad-1 convolution on a map of 8 x 32 tiles "
-                       "without split-K (raw inputs or the streaming kernel's prologue forms), the same on a map of 16 x 16 tiles that is not 8 x 32 "
-                       "tileable (raw inputs, zero padding, no upsample, un-split under KEEP_MMA_X3), an im2col shape without prologue, or -- with "
-                       "KEEP_CONV_X1_GEMM -- a 1x1 stride-1 unpadded GEMM without prologue");
-        return KEEP_EUNSUP;
-      }
-      keep_set_error("keep_conv2d: KEEP_MMA_X1 (with KEEP_CONV_X1_GEMM) has no kernel for this call: it needs weight_x3 (the hi-only fp16 twin) and "
-                     "x3_acc_scale, Cin %% 32 == 0, no aux / in2 / LayerNorm, and one of: a 3x3 stride-1 pad-1 convolution on a map of 8 x 32 tiles "
-                     "without split-K (raw inputs or the streaming kernel's prologue forms), an im2col shape without prologue (a 3x3 stride-1 pad-1 "
-                     "convolution only on a map no halo kernel tiles), or a 1x1 stride-1 unpadded GEMM without prologue");
-      return KEEP_EUNSUP;
-    }
-    if (a->flags & KEEP_CONV_X1_HALO16) {
-      keep_set_error("keep_conv2d: KEEP_MMA_X1 (with KEEP_CONV_X1_HALO16) has no kernel for this call: it needs weight_x3 (the hi-only fp16 twin) and "
-                     "x3_acc_scale, Cin %% 32 == 0, no aux / in2 / LayerNorm, and one of: a 3x3 stride-1 pad-1 convolution on a map of 8 x 32 tiles "
-                     "without split-K (raw inputs or the streaming kernel's prologue forms), the same on a map of 16 x 16 tiles that is not 8 x 32 "
-                     "tileable (raw inputs, zero padding, no upsample, un-split under KEEP_MMA_X3), an im2col shape without prologue, or -- with "
-                     "KEEP_CONV_X1_GEMM -- a 1x1 stride-1 unpadded GEMM without prologue");
-      return KEEP_EUNSUP;
-    }
+// What the planners below ask of a call more than once.
+struct ConvGeom {
+  long M;            // rows the HEURISTICS see (tile, split-K): per-image rows x the fixed reference batch under the parity policies (x1 plans
+                     // like x3), the real row count under the bf16 speed policy; launches and buffer sizes always use the real M (p.M)
+  int ncb;           // 64-channel output blocks
+  bool no_pro, is33s1, same_size, tileable, pro_al, epi_al, reflect;
+};
+
+static ConvGeom conv_geom(const keep_conv2d_args* a) {
+  ConvGeom g;
+  g.M = a->mma == KEEP_MMA_BF16 ? (long)a->N * a->Ho * a->Wo : plan_ref_images(a) * (long)a->Ho * a->Wo;
+  g.ncb = (a->Cout + 63) / 64;
+  g.no_pro = !a->pro_scale && a->pro_act == KEEP_PRO_NONE;
+  g.is33s1 = a->KH == 3 && a->KW == 3 && a->stride == 1 && a->pad_t == 1 && a->pad_l == 1;
+  g.same_size = a->Ho == (a->upsample ? 2 * a->H : a->H) && a->Wo == (a->upsample ? 2 * a->W : a->W);
+  g.tileable = (a->Ho % 8 == 0 && a->Wo % 32 == 0) || (a->Ho % 16 == 0 && a->Wo % 16 == 0);
+  g.pro_al = !a->pro_scale || ((uintptr_t)a->pro_scale % 16 == 0 && (uintptr_t)a->pro_shift % 16 == 0);
+  g.epi_al = (a->out_ld % 4 == 0) && ((uintptr_t)a->out % 16 == 0) &&
+             (!a->residual || (a->res_ld % 4 == 0 && (uintptr_t)a->residual % 16 == 0)) &&
+             (!a->aux || (uintptr_t)a->aux % 16 == 0) && (!a->bias || (uintptr_t)a->bias % 16 == 0);
+  g.reflect = a->pad_mode == KEEP_PAD_REFLECT;
+  return g;
+}
+
+// the caller's split_k, else the library's; never more K ranges than `cap` units of K
+static int pick_split_k(const keep_conv2d_args* a, int auto_split, int cap) {
+  const int s = a->split_k > 0 ? a->split_k : auto_split;
+  return s > cap ? cap : s;
+}
+
+// Split-K of the halo kernels of the parity policies (x3, f32; the un-split x1 16 x 16 form asks what x3 would do): items of 256 pixels x
+// 64 output channels; fewer than 256 of them split K toward 512, a range no shorter than 32 channels, at most 16 ways; a range holds at
+// least one 16-channel chunk.
+static int halo_split_k(const keep_conv2d_args* a, const ConvGeom& g) {
+  const long items = (g.M / 256) * g.ncb;
+  const int auto_split = items >= 256 ? 1 : (int)max(1L, min(min(512L / items, (long)a->Cin / 32), 16L));
+  return pick_split_k(a, auto_split, a->Cin / 16);
+}
+
+// Gather kernels: tile -> blocks -> waves -> split-K.
+static int gather_tile(const keep_conv2d_args* a, const ConvGeom& g) { return (a->Cout <= 64 || g.M <= small_m_threshold(a)) ? 1 : 2; }
+
+static long gather_waves(int tile, long M, int Cout) {
+  const long blocks = tile == 0 ? (long)cdiv(M, 128) * cdiv(Cout, 32)
+                      : (tile == 1 ? (long)cdiv(M, 64) * cdiv(Cout, 64) : (long)cdiv(M, 128) * cdiv(Cout, 128));
+  return blocks * 4;
+}
+
+enum SplitKind { SPLIT_HALF, SPLIT_F32, SPLIT_BK256 };      // 16-bit operands (bf16, x3, x1) / f32 operands / bf16 with 256-channel K steps
+
+static int gather_auto_split(long waves, int steps, SplitKind kind) {
+  if (kind == SPLIT_BK256) return (int)max(1L, min(min(512L / max(waves / 4, 1L), (long)steps / 2), 16L));
+  if (waves >= kTargetWaves || steps < 8) return 1;
+  if (kind == SPLIT_F32) return (int)max(1L, min(min((long)kTargetWaves / waves, (long)steps / 4), 32L));
+  return (int)max(1L, min(min(4L * kTargetWaves / waves, (long)steps / 2), 32L));
+}
+
+// x3 / x1 gather forms: tile and split-K from the reference batch, K steps of 32 channels
+static void plan_x3_gather(const keep_conv2d_args* a, const ConvGeom& g, ConvForm form, bool plain, ConvPlan& pl) {
+  pl.path = PATH_GATHER_X3;
+  pl.form = form;
+  pl.plain = plain;
+  pl.gemm = keep_conv_x3_gather_is_gemm(a);
+  pl.tile = gather_tile(a, g);
+  const int steps = a->KH * a->KW * ((a->Cin + 31) / 32);
+  pl.split_k = pick_split_k(a, gather_auto_split(gather_waves(pl.tile, g.M, a->Cout), steps, SPLIT_HALF), steps);
+  pl.stats_rows = pl.tile == 1 ? 64 : 128;
+  // a wave's rows must lie in one image: Ho*Wo a multiple of the wave tile (32 or 64 rows)
+  pl.amax_ok = pl.split_k == 1 && ((long)a->Ho * a->Wo) % (pl.tile == 1 ? 32 : 64) == 0;
+}
+
+// un-split forms of the x3 / x1 halo path: one statistics partial per 256-pixel tile, max |out| available
+static void plan_halo_x3_unsplit(ConvForm form, ConvPlan& pl) {
+  pl.path = PATH_HALO_X3;
+  pl.form = form;
+  pl.split_k = 1;
+  pl.stats_rows = 256;
+  pl.amax_ok = true;
+}
+
+static bool x3_weights_ok(const keep_conv2d_args* a) {
+  return a->weight_x3 != nullptr && (uintptr_t)a->weight_x3 % 16 == 0 && a->x3_acc_scale > 0.f;
+}
+
+// KEEP_MMA_X1 found no kernel: what the policy covers under the opt-in bits the caller set
+static int refuse_x1(const keep_conv2d_args* a) {
+  if (a->flags & KEEP_CONV_X1_HALO16)
+    keep_set_error("keep_conv2d: KEEP_MMA_X1 (with KEEP_CONV_X1_HALO16) has no kernel for this call: it needs weight_x3 (the hi-only fp16 twin) and "
+                   "x3_acc_scale, Cin %% 32 == 0, no aux / in2 / LayerNorm, and one of: a 3x3 stride-1 pad-1 convolution on a map of 8 x 32 tiles "
+                   "without split-K (raw inputs or the streaming kernel's prologue forms), the same on a map of 16 x 16 tiles that is not 8 x 32 "
+                   "tileable (raw inputs, zero padding, no upsample, un-split under KEEP_MMA_X3), an im2col shape without prologue, or -- with "
+                   "KEEP_CONV_X1_GEMM -- a 1x1 stride-1 unpadded GEMM without prologue");
+  else if (a->flags & KEEP_CONV_X1_GEMM)
+    keep_set_error("keep_conv2d: KEEP_MMA_X1 (with KEEP_CONV_X1_GEMM) has no kernel for this call: it needs weight_x3 (the hi-only fp16 twin) and "
+                   "x3_acc_scale, Cin %% 32 == 0, no aux / in2 / LayerNorm, and one of: a 3x3 stride-1 pad-1 convolution on a map of 8 x 32 tiles "
+                   "without split-K (raw inputs or the streaming kernel's prologue forms), an im2col shape without prologue (a 3x3 stride-1 pad-1 "
+                   "convolution only on a map no halo kernel tiles), or a 1x1 stride-1 unpadded GEMM without prologue");
+  else
     keep_set_error("keep_conv2d: KEEP_MMA_X1 has no kernel for this call: it needs weight_x3 (the hi-only fp16 twin) and x3_acc_scale, Cin %% 32 == 0, no "
                    "aux / in2 / LayerNorm, and either a 3x3 stride-1 pad-1 convolution on a map of 8 x 32 tiles without split-K (raw inputs, or a "
                    "GroupNorm affine prologue alone / with ReLU / with the fast swish under zero padding) or an im2col shape without prologue (a strided or non-3x3 "
                    "convolution that is not a 1x1 GEMM)");
-    return KEEP_EUNSUP;
-  }
-  // ---- split fp16: halo / gather kernels where the geometry fits, the exact-f32 kernels otherwise (same parity grade)
-  if (mma == KEEP_MMA_X3) {
-    KEEP_REQUIRE(a->dtype == KEEP_F32 && a->out_dtype != KEEP_BF16, "keep_conv2d: KEEP_MMA_X3 takes and writes fp32 tensors");
-    const bool have_w = a->weight_x3 != nullptr && (uintptr_t)a->weight_x3 % 16 == 0 && a->x3_acc_scale > 0.f;
-    // RGB first convolutions: persistent im2col-in-LDS kernel, weights split on the fly from the fp32 tensor
-    if (is33s1 && !reflect && !a->upsample && a->Cin <= 3 && a->Cout % 4 == 0 && a->Cout >= 32 && a->Ho == a->H && a->Wo == a->W &&
-        a->Ho % 8 == 0 && a->Wo % 32 == 0 && no_pro && !a->residual && !a->aux && a->split_k <= 1 && a->out_ld % 4 == 0 &&
-        (uintptr_t)a->out % 16 == 0 && (!a->bias || (uintptr_t)a->bias % 16 == 0) && a->weight && !(a->flags & KEEP_CONV_NO_C3)) {
-      pl.path = PATH_C3_X3;
-      pl.split_k = 1;
-      pl.stats_rows = 64;
-      pl.amax_ok = true;
-      snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_c3_x3_kernel");
-      return KEEP_OK;
-    }
-    if (a->upsample == KEEP_UPSAMPLE_X2_PHASES) {      // weight_x3 holds the four phase kernels: only the phase form of the halo kernel can run it
-      if (!(have_w && is33s1 && keep_conv_x3_up2_ok(a))) {
-        keep_set_error("keep_conv2d: upsample = KEEP_UPSAMPLE_X2_PHASES needs KEEP_MMA_X3 phase weights, a 3x3 stride-1 pad-1 convolution without "
-                       "prologue / activation / aux / split-K, H %% 8 == 0, W %% 32 == 0, Cin %% 16 == 0 and Cout %% 64 == 0");
-        return KEEP_EUNSUP;
-      }
-      pl.path = PATH_HALO_X3;
-      pl.split_k = 1;
-      pl.stats_rows = 256;
-      pl.amax_ok = true;
-      snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_x3_kernel<32, x2 phases>");
-      return KEEP_OK;
-    }
-    if (have_w && is33s1 && keep_conv_x3_halo_ok(a) && !(a->flags & KEEP_CONV_NO_HALO_X3)) {
-      pl.path = PATH_HALO_X3;
-      const long items = (M / 256) * ncb;
-      auto_split = items >= 256 ? 1 : (int)max(1L, min(min(512L / items, (long)a->Cin / 32), 16L));
-      pl.split_k = a->split_k > 0 ? a->split_k : auto_split;
-      if (pl.split_k > a->Cin / 16) pl.split_k = a->Cin / 16;
-      pl.stats_rows = 256;      // one statistics partial per 256-pixel tile (the block adds its four waves' sums in LDS)
-      pl.amax_ok = pl.split_k == 1;
-      if (keep_conv_x3_stream_ok(a, p, pl.split_k))      // the streaming form (keep_conv_x3s.hip): what rocprofv3 prints
-        snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_x3s_kernel");
-      else
-        snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_x3_kernel<%d>", pl.wide ? 32 : 16);
-      return KEEP_OK;
-    }
-    if (a->in2) {      // K-concatenated input: GEMM form of the x3 gather kernel only
-      const bool ok2 = have_w && keep_conv_x3_gather_ok(a, p) && keep_conv_x3_gather_is_gemm(a) && no_pro && !a->x3_in_amax &&
-                       a->in2_cin1 > 0 && a->in2_cin1 < a->Cin && a->in2_cin1 % 32 == 0 && (a->Cin - a->in2_cin1) % 4 == 0 &&
-                       a->in_ld >= a->in2_cin1 && (uintptr_t)a->in2 % 16 == 0 && !is33s1 && !(a->flags & KEEP_CONV_NO_GATHER_X3);
-      if (!ok2) {
-        keep_set_error("keep_conv2d: in2 (K-concatenated input) needs KEEP_MMA_X3, a 1x1 stride-1 convolution without prologue / range probe and in2_cin1 %% 32 == 0");
-        return KEEP_EUNSUP;
-      }
-    }
-    // GEMM form with few rows per image (token GEMMs of the frame recurrence): the latency form, K cut into canonical slices
-    // (keep_gemm_x3l.hip).  A per-image rule -- the sums it defines are the same at every batch size.
-    if (have_w && keep_gemm_x3l_ok(a) && keep_conv_x3_gather_ok(a, p) && keep_conv_x3_gather_is_gemm(a) &&
-        !(a->flags & (KEEP_CONV_NO_GATHER_X3 | KEEP_CONV_NO_GEMM_LAT))) {
-      pl.path = PATH_GATHER_X3;
-      pl.tile = 4;
-      pl.plain = no_pro;
-      pl.split_k = 1;
-      pl.stats_rows = 0;
-      pl.amax_ok = true;
-      snprintf(pl.kernel, sizeof(pl.kernel), "gemm_x3l_kernel<%d>", keep_gemm_x3l_waves(a));
-      return KEEP_OK;
-    }
-    if (have_w && keep_conv_x3_gather_ok(a, p) && !(a->flags & KEEP_CONV_NO_GATHER_X3)) {
-      pl.path = PATH_GATHER_X3;
-      pl.tile = (a->Cout <= 64 || M <= small_m_threshold(a)) ? 1 : 2;
-      pl.plain = no_pro;
-      const int steps = a->KH * a->KW * ((a->Cin + 31) / 32);
-      const long blocks = pl.tile == 1 ? (long)cdiv(M, 64) * cdiv(a->Cout, 64) : (long)cdiv(M, 128) * cdiv(a->Cout, 128);
-      const long waves = blocks * 4;
-      auto_split = (waves >= kTargetWaves || steps < 8) ? 1 : (int)max(1L, min(min(4L * kTargetWaves / waves, (long)steps / 2), 32L));
-      pl.split_k = a->split_k > 0 ? a->split_k : auto_split;
-      if (pl.split_k > steps) pl.split_k = steps;
-      pl.stats_rows = pl.tile == 1 ? 64 : 128;
-      // a wave's rows must lie in one image: Ho*Wo a multiple of the wave tile (32 or 64 rows)
-      pl.amax_ok = pl.split_k == 1 && ((long)a->Ho * a->Wo) % (pl.tile == 1 ? 32 : 64) == 0;
-      if (a->ln_gamma) {      // LayerNorm in the epilogue: one wave holds whole 128-channel rows (tile <4,1,1,4>), full row tiles only
-        if (!(a->ln_beta && keep_conv_x3_gather_is_gemm(a) && no_pro && a->Cout == 128 && a->out_ld == 128 && M_real % 128 == 0 &&
-              a->split_k <= 1 && a->epi_act == KEEP_ACT_NONE && !a->aux && !a->stats_out && a->out_dtype == KEEP_F32 &&
-              (uintptr_t)a->ln_gamma % 16 == 0 && (uintptr_t)a->ln_beta % 16 == 0 && (!a->residual || a->res_ld % 4 == 0))) {
-          keep_set_error("keep_conv2d: ln_gamma (LayerNorm epilogue) needs the KEEP_MMA_X3 GEMM form (1x1, stride 1, no prologue / activation / "
-                         "aux / split-K / statistics), Cout == out_ld == 128, fp32 output and N*Ho*Wo %% 128 == 0");
-          return KEEP_EUNSUP;
-        }
-        pl.tile = 3;
-        pl.split_k = 1;
-        pl.stats_rows = 0;
-        pl.amax_ok = ((long)a->Ho * a->Wo) % 32 == 0;
-        snprintf(pl.kernel, sizeof(pl.kernel), "conv_x3_kernel<4, 1, 1, 4, true, true> + LayerNorm");
-        return KEEP_OK;
-      }
-      snprintf(pl.kernel, sizeof(pl.kernel), "conv_x3_kernel<%s, %s, %s>", pl.tile == 1 ? "2, 2, 1, 1" : "2, 2, 2, 2",
-               pl.plain ? "true" : "false", keep_conv_x3_gather_is_gemm(a) ? "true" : "false");
-      return KEEP_OK;
-    }
-    if (a->ln_gamma) {
-      keep_set_error("keep_conv2d: ln_gamma (LayerNorm epilogue) is a feature of the KEEP_MMA_X3 GEMM form");
-      return KEEP_EUNSUP;
-    }
-    mma = KEEP_MMA_F32;
-  }
-  KEEP_REQUIRE(mma == KEEP_MMA_F32 || (a->weight_bf16 && (uintptr_t)a->weight_bf16 % 16 == 0) || a->weight == nullptr,
-               "keep_conv2d: KEEP_MMA_BF16 needs a 16-byte aligned weight_bf16");
-  // ---- fp32 policy: persistent LDS-halo kernel on f32 MFMA
-  if (mma == KEEP_MMA_F32 && a->dtype == KEEP_F32 && a->out_dtype != KEEP_BF16 && is33s1 && (a->Cin % 16 == 0) &&
-      (a->Cout % 32 == 0) && tileable && same_size && pro_al && (a->in_ld % 4 == 0) && ((uintptr_t)a->in % 16 == 0) &&
-      ((uintptr_t)a->weight % 16 == 0) && epi_al && (!a->workspace || (uintptr_t)a->workspace % 16 == 0) &&
-      !(a->flags & KEEP_CONV_NO_HALO_F32)) {
-    pl.path = PATH_HALO_F32;
-    const long items = (M / 256) * ncb;
-    auto_split = items >= 256 ? 1 : (int)max(1L, min(min(512L / items, (long)a->Cin / 32), 16L));
-    pl.split_k = a->split_k > 0 ? a->split_k : auto_split;
-    if (pl.split_k > a->Cin / 16) pl.split_k = a->Cin / 16;
-    pl.stats_rows = 64;
-    snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_f32_kernel<%d>", pl.wide ? 32 : 16);
+  return KEEP_EUNSUP;
+}
+
+// ---- single fp16 (the opt-in speed policy 'f16' of the engines): the x1 instantiations of the x3 kernels, planned by the x3 rules; every
+// other shape is refused -- there is no kernel of this grade for it and no silent change of policy
+static int plan_x1(const keep_conv2d_args* a, const ConvP& p, const ConvGeom& g, ConvPlan& pl) {
+  KEEP_REQUIRE(a->dtype == KEEP_F32 && a->out_dtype != KEEP_BF16, "keep_conv2d: KEEP_MMA_X1 takes and writes fp32 tensors");
+  const bool have_w = x3_weights_ok(a);
+  if (have_w && g.is33s1 && keep_conv_x3_halo_ok(a) && keep_conv_x1_stream_ok(a, p) && a->split_k <= 1 && !(a->flags & KEEP_CONV_NO_HALO_X3)) {
+    plan_halo_x3_unsplit(FORM_X1_STREAM, pl);
     return KEEP_OK;
   }
-  // ---- bf16 policy: LDS-halo kernel (persistent v3; v1 when the prologue is fused into its staging step)
-  constexpr int halo_ver = 3;
-  const bool halo_geom = mma == KEEP_MMA_BF16 && is33s1 && (a->Cin % 32 == 0) && (a->Cout % 32 == 0) && tileable && same_size &&
-                         (a->in_ld % 8 == 0) && ((uintptr_t)a->in % 16 == 0) && epi_al;
-  if (halo_geom) {
-    const bool v3 = halo_ver == 3 && no_pro;
-    const bool out16_ok = no_pro && !a->residual && a->split_k <= 1 && a->Cout % 64 == 0 && halo_ver == 3;
+  // KEEP_CONV_X1_HALO16 (opt-in bit, like KEEP_CONV_X1_GEMM below: without it nothing changes): the 16 x 16-tile halo kernel for the maps the
+  // streaming form does not tile.  Only where the x3 plan of the same call is un-split: the form has no split-K, and a call x3 splits keeps
+  // x3's partition.
+  if ((a->flags & KEEP_CONV_X1_HALO16) && have_w && g.is33s1 && keep_conv_x1_halo16_ok(a) && !(a->flags & KEEP_CONV_NO_HALO_X3)) {
+    const int x3_split = halo_split_k(a, g);
+    if (x3_split != 1) {
+      keep_set_error("keep_conv2d: KEEP_MMA_X1 (with KEEP_CONV_X1_HALO16) has no kernel for this call: KEEP_MMA_X3 plans it with split-K = %d "
+                     "(plan_ref_images = %ld) and the 16 x 16-tile single-fp16 form is un-split", x3_split, plan_ref_images(a));
+      return KEEP_EUNSUP;
+    }
+    plan_halo_x3_unsplit(FORM_X1_HALO16, pl);
+    pl.simple_epi = a->epi_act == KEEP_ACT_NONE;
+    return KEEP_OK;
+  }
+  // im2col (under KEEP_CONV_X1_GEMM also a 3x3 stride-1 pad-1 convolution NO halo kernel takes -- a ragged map, where x3 itself runs this kernel)
+  if (have_w && (!g.is33s1 || ((a->flags & KEEP_CONV_X1_GEMM) && !keep_conv_x3_halo_ok(a))) && keep_conv_x1_gather_ok(a, p) &&
+      !(a->flags & KEEP_CONV_NO_GATHER_X3)) {
+    plan_x3_gather(a, g, FORM_X1_IM2COL, true, pl);
+    return KEEP_OK;
+  }
+  // KEEP_CONV_X1_GEMM (opt-in bit: without it the 1x1 GEMM form stays refused).  The latency form (gemm_x3l_kernel) has no x1 twin: a shape
+  // x3 would send there takes this tile kernel too.
+  if ((a->flags & KEEP_CONV_X1_GEMM) && have_w && !g.is33s1 && keep_conv_x1_gemm_ok(a, p) && !(a->flags & KEEP_CONV_NO_GATHER_X3)) {
+    plan_x3_gather(a, g, FORM_X1_GEMM, true, pl);
+    return KEEP_OK;
+  }
+  return refuse_x1(a);
+}
+
+// LayerNorm in the epilogue of the x3 GEMM form: one wave holds whole 128-channel rows (tile <4,1,1,4>), full row tiles only
+static int plan_x3_layernorm(const keep_conv2d_args* a, const ConvGeom& g, ConvPlan& pl) {
+  if (!(a->ln_beta && pl.gemm && g.no_pro && a->Cout == 128 && a->out_ld == 128 && ((long)a->N * a->Ho * a->Wo) % 128 == 0 &&
+        a->split_k <= 1 && a->epi_act == KEEP_ACT_NONE && !a->aux && !a->stats_out && a->out_dtype == KEEP_F32 &&
+        (uintptr_t)a->ln_gamma % 16 == 0 && (uintptr_t)a->ln_beta % 16 == 0 && (!a->residual || a->res_ld % 4 == 0))) {
+    keep_set_error("keep_conv2d: ln_gamma (LayerNorm epilogue) needs the KEEP_MMA_X3 GEMM form (1x1, stride 1, no prologue / activation / "
+                   "aux / split-K / statistics), Cout == out_ld == 128, fp32 output and N*Ho*Wo %% 128 == 0");
+    return KEEP_EUNSUP;
+  }
+  pl.form = FORM_GEMM_LN;
+  pl.tile = 2;
+  pl.split_k = 1;
+  pl.stats_rows = 0;
+  pl.amax_ok = ((long)a->Ho * a->Wo) % 32 == 0;
+  return KEEP_OK;
+}
+
+// ---- split fp16: halo / gather kernels where the geometry fits; `to_f32` = no x3 kernel takes the call and the exact-f32 kernels do
+// (same parity grade)
+static int plan_x3(const keep_conv2d_args* a, const ConvP& p, const ConvGeom& g, ConvPlan& pl, bool& to_f32) {
+  to_f32 = false;
+  KEEP_REQUIRE(a->dtype == KEEP_F32 && a->out_dtype != KEEP_BF16, "keep_conv2d: KEEP_MMA_X3 takes and writes fp32 tensors");
+  const bool have_w = x3_weights_ok(a);
+  // RGB first convolutions: persistent im2col-in-LDS kernel, weights split on the fly from the fp32 tensor
+  if (g.is33s1 && !g.reflect && !a->upsample && a->Cin <= 3 && a->Cout % 4 == 0 && a->Cout >= 32 && a->Ho == a->H && a->Wo == a->W &&
+      a->Ho % 8 == 0 && a->Wo % 32 == 0 && g.no_pro && !a->residual && !a->aux && a->split_k <= 1 && a->out_ld % 4 == 0 &&
+      (uintptr_t)a->out % 16 == 0 && (!a->bias || (uintptr_t)a->bias % 16 == 0) && a->weight && !(a->flags & KEEP_CONV_NO_C3)) {
+    pl.path = PATH_C3_X3;
+    pl.split_k = 1;
+    pl.stats_rows = 64;
+    pl.amax_ok = true;
+    return KEEP_OK;
+  }
+  if (a->upsample == KEEP_UPSAMPLE_X2_PHASES) {      // weight_x3 holds the four phase kernels: only the phase form of the halo kernel can run it
+    if (!(have_w && g.is33s1 && keep_conv_x3_up2_ok(a))) {
+      keep_set_error("keep_conv2d: upsample = KEEP_UPSAMPLE_X2_PHASES needs KEEP_MMA_X3 phase weights, a 3x3 stride-1 pad-1 convolution without "
+                     "prologue / activation / aux / split-K, H %% 8 == 0, W %% 32 == 0, Cin %% 16 == 0 and Cout %% 64 == 0");
+      return KEEP_EUNSUP;
+    }
+    plan_halo_x3_unsplit(FORM_HALO_UP2, pl);
+    return KEEP_OK;
+  }
+  if (have_w && g.is33s1 && keep_conv_x3_halo_ok(a) && !(a->flags & KEEP_CONV_NO_HALO_X3)) {
+    pl.path = PATH_HALO_X3;
+    pl.form = FORM_X3_HALO;
+    pl.split_k = halo_split_k(a, g);
+    pl.stats_rows = 256;      // one statistics partial per 256-pixel tile (the block adds its four waves' sums in LDS)
+    pl.amax_ok = pl.split_k == 1;
+    pl.stream = keep_conv_x3_stream_ok(a, p, pl.split_k);      // the streaming form (keep_conv_x3s.hip)
+    return KEEP_OK;
+  }
+  const bool gather_ok = have_w && keep_conv_x3_gather_ok(a, p);
+  const bool is_gemm = keep_conv_x3_gather_is_gemm(a);
+  if (a->in2) {      // K-concatenated input: GEMM form of the x3 gather kernel only
+    const bool ok2 = gather_ok && is_gemm && g.no_pro && !a->x3_in_amax &&
+                     a->in2_cin1 > 0 && a->in2_cin1 < a->Cin && a->in2_cin1 % 32 == 0 && (a->Cin - a->in2_cin1) % 4 == 0 &&
+                     a->in_ld >= a->in2_cin1 && (uintptr_t)a->in2 % 16 == 0 && !g.is33s1 && !(a->flags & KEEP_CONV_NO_GATHER_X3);
+    if (!ok2) {
+      keep_set_error("keep_conv2d: in2 (K-concatenated input) needs KEEP_MMA_X3, a 1x1 stride-1 convolution without prologue / range probe and in2_cin1 %% 32 == 0");
+      return KEEP_EUNSUP;
+    }
+  }
+  // GEMM form with few rows per image (token GEMMs of the frame recurrence): the latency form, K cut into canonical slices
+  // (keep_gemm_x3l.hip).  A per-image rule -- the sums it defines are the same at every batch size.
+  if (gather_ok && is_gemm && keep_gemm_x3l_ok(a) && !(a->flags & (KEEP_CONV_NO_GATHER_X3 | KEEP_CONV_NO_GEMM_LAT))) {
+    pl.path = PATH_GATHER_X3;
+    pl.form = FORM_GEMM_LAT;
+    pl.plain = g.no_pro;
+    pl.gemm = true;
+    pl.split_k = 1;
+    pl.stats_rows = 0;
+    pl.amax_ok = true;
+    return KEEP_OK;
+  }
+  if (gather_ok && !(a->flags & KEEP_CONV_NO_GATHER_X3)) {
+    plan_x3_gather(a, g, FORM_X3_GATHER, g.no_pro, pl);
+    return a->ln_gamma ? plan_x3_layernorm(a, g, pl) : KEEP_OK;
+  }
+  if (a->ln_gamma) {
+    keep_set_error("keep_conv2d: ln_gamma (LayerNorm epilogue) is a feature of the KEEP_MMA_X3 GEMM form");
+    return KEEP_EUNSUP;
+  }
+  to_f32 = true;
+  return KEEP_OK;
+}
+
+// ---- fp32 policy (and what no x3 kernel takes): persistent LDS-halo kernel on f32 MFMA, else the f32 gather kernel
+static int plan_f32(const keep_conv2d_args* a, ConvP& p, const ConvGeom& g, ConvPlan& pl) {
+  if (a->dtype == KEEP_F32 && a->out_dtype != KEEP_BF16 && g.is33s1 && (a->Cin % 16 == 0) &&
+      (a->Cout % 32 == 0) && g.tileable && g.same_size && g.pro_al && (a->in_ld % 4 == 0) && ((uintptr_t)a->in % 16 == 0) &&
+      ((uintptr_t)a->weight % 16 == 0) && g.epi_al && (!a->workspace || (uintptr_t)a->workspace % 16 == 0) &&
+      !(a->flags & KEEP_CONV_NO_HALO_F32)) {
+    pl.path = PATH_HALO_F32;
+    pl.split_k = halo_split_k(a, g);
+    pl.stats_rows = 64;
+    return KEEP_OK;
+  }
+  pl.path = PATH_GATHER_F32;
+  pl.tile = a->Cout <= 32 ? 0 : gather_tile(a, g);
+  pl.stats_rows = pl.tile == 1 ? 64 : 128;
+  p.flatk_f32 = (a->Cin < 8 && a->dtype == KEEP_F32 && g.no_pro && !(a->flags & KEEP_CONV_NO_FLATK_F32)) ? 1 : 0;
+  if (p.flatk_f32) p.nsteps = (a->KH * a->KW * a->Cin + BK - 1) / BK;
+  pl.plain = p.vec_ok && a->Cin % 16 == 0 && g.no_pro && !a->upsample && pl.tile != 0 && !(a->flags & KEEP_CONV_NO_PLAIN);
+  pl.split_k = pick_split_k(a, gather_auto_split(gather_waves(pl.tile, g.M, a->Cout), p.nsteps, SPLIT_F32), p.nsteps);
+  return KEEP_OK;
+}
+
+// ---- bf16 policy: LDS-halo kernel (persistent; the first version when the prologue is fused into its staging step), else the bf16 gather kernel
+static int plan_bf16(const keep_conv2d_args* a, ConvP& p, const ConvGeom& g, ConvPlan& pl) {
+  KEEP_REQUIRE((a->weight_bf16 && (uintptr_t)a->weight_bf16 % 16 == 0) || a->weight == nullptr,
+               "keep_conv2d: KEEP_MMA_BF16 needs a 16-byte aligned weight_bf16");
+  if (g.is33s1 && (a->Cin % 32 == 0) && (a->Cout % 32 == 0) && g.tileable && g.same_size && (a->in_ld % 8 == 0) &&
+      ((uintptr_t)a->in % 16 == 0) && g.epi_al) {
+    const bool out16_ok = g.no_pro && !a->residual && a->split_k <= 1 && a->Cout % 64 == 0;
     pl.out_bf16_ok = out16_ok ? 1 : 0;
     // an fp32 input with a prologue: the host should run keep_norm_act_bf16 first and come back with a bf16 tensor
-    pl.wants_bf16_input = (!no_pro && halo_ver == 3) ? 1 : 0;
-    if (p.in_bf16 && !no_pro) {      // a bf16 tensor that still carries a prologue: only the two-pass form exists
+    pl.wants_bf16_input = g.no_pro ? 0 : 1;
+    if (p.in_bf16 && !g.no_pro) {      // a bf16 tensor that still carries a prologue: only the two-pass form exists
       pl.path = PATH_NEEDS_PRENORM;
       pl.split_k = 1;
-      snprintf(pl.kernel, sizeof(pl.kernel), "(keep_norm_act_bf16 first)");
       return KEEP_OK;
     }
-    const bool ok = (a->dtype == KEEP_F32 || no_pro) && pro_al && (a->out_dtype != KEEP_BF16 || out16_ok) &&
-                    (a->Cout % 64 == 0 || v3);
-    if (ok) {
-      pl.path = v3 ? PATH_HALO_BF16 : PATH_HALO_BF16_V1;
-      const long waves = (M / 256) * ncb * 4;
-      auto_split = (a->out_dtype == KEEP_BF16 || waves >= kTargetWaves) ? 1
-                   : (int)max(1L, min(min((long)kTargetWaves / waves, (long)a->Cin / 64), 16L));
-      pl.split_k = a->split_k > 0 ? a->split_k : auto_split;
-      if (pl.split_k > a->Cin / 32) pl.split_k = a->Cin / 32;
-      pl.stats_rows = v3 ? 64 : 256;
-      snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo3_kernel<%s, %d>", p.in_bf16 ? "true" : "false", pl.wide ? 32 : 16);
+    if ((a->dtype == KEEP_F32 || g.no_pro) && g.pro_al && (a->out_dtype != KEEP_BF16 || out16_ok) && (a->Cout % 64 == 0 || g.no_pro)) {
+      pl.path = g.no_pro ? PATH_HALO_BF16 : PATH_HALO_BF16_V1;
+      const long waves = (g.M / 256) * g.ncb * 4;
+      const int auto_split = (a->out_dtype == KEEP_BF16 || waves >= kTargetWaves) ? 1
+                             : (int)max(1L, min(min((long)kTargetWaves / waves, (long)a->Cin / 64), 16L));
+      pl.split_k = pick_split_k(a, auto_split, a->Cin / 32);
+      pl.stats_rows = g.no_pro ? 64 : 256;
       return KEEP_OK;
     }
   }
@@ -2131,42 +2081,58 @@ static int plan_conv(const keep_conv2d_args* a, ConvP& p, ConvPlan& pl) {
                    "(Cin%%32, Cout%%32, tileable map, no prologue)");
     return KEEP_EUNSUP;
   }
-  // ---- gather kernels
-  pl.tile = a->Cout <= 32 ? 0 : ((a->Cout <= 64 || M <= small_m_threshold(a)) ? 1 : 2);
-  const long blocks = pl.tile == 0 ? (long)cdiv(M, 128) * cdiv(a->Cout, 32)
-                      : (pl.tile == 1 ? (long)cdiv(M, 64) * cdiv(a->Cout, 64) : (long)cdiv(M, 128) * cdiv(a->Cout, 128));
-  const long waves = blocks * 4;
+  pl.path = PATH_GATHER_BF16;
+  pl.tile = a->Cout <= 32 ? 0 : gather_tile(a, g);
   pl.stats_rows = pl.tile == 1 ? 64 : 128;
-  if (mma == KEEP_MMA_BF16) {
-    pl.path = PATH_GATHER_BF16;
-    p.flatk = (a->Cin < 8 && no_pro) ? 1 : 0;
-    pl.plain = !p.flatk && p.vec_ok && no_pro && !a->upsample && (a->Cin % 8 == 0) && !(a->flags & KEEP_CONV_NO_PLAIN);
-    int steps = p.flatk ? (a->KH * a->KW * a->Cin + BK16 - 1) / BK16 : a->KH * a->KW * ((a->Cin + BK16 - 1) / BK16);
-    pl.bk256 = a->bk256 && !p.flatk && pl.tile == 1;
-    if (pl.bk256) {
-      steps = a->KH * a->KW * ((a->Cin + 255) / 256);
-      auto_split = (int)max(1L, min(min(512L / max(blocks, 1L), (long)steps / 2), 16L));
-    } else {
-      auto_split = (waves >= kTargetWaves || steps < 8) ? 1 : (int)max(1L, min(min(4L * kTargetWaves / waves, (long)steps / 2), 32L));
-    }
-    if (a->out_dtype == KEEP_BF16) auto_split = 1;
-    pl.out_bf16_ok = (p.vec_epi && !a->residual) ? 1 : 0;
-    pl.split_k = a->split_k > 0 ? a->split_k : auto_split;
-    if (pl.split_k > steps) pl.split_k = steps;
-    const char* t = pl.tile == 0 ? "4, 1, 1, 1" : (pl.tile == 1 ? "2, 2, 1, 1" : "2, 2, 2, 2");
-    snprintf(pl.kernel, sizeof(pl.kernel), "conv_bf16_kernel<%s, %s, %s>", t, pl.bk256 ? "256, 1" : "64, 1",
-             (pl.plain && !pl.bk256 && pl.tile != 0) ? "true" : "false");
+  p.flatk = (a->Cin < 8 && g.no_pro) ? 1 : 0;
+  pl.plain = !p.flatk && p.vec_ok && g.no_pro && !a->upsample && (a->Cin % 8 == 0) && !(a->flags & KEEP_CONV_NO_PLAIN);
+  pl.bk256 = a->bk256 && !p.flatk && pl.tile == 1;
+  const int steps = pl.bk256 ? a->KH * a->KW * ((a->Cin + 255) / 256)
+                    : (p.flatk ? (a->KH * a->KW * a->Cin + BK16 - 1) / BK16 : a->KH * a->KW * ((a->Cin + BK16 - 1) / BK16));
+  const int auto_split = a->out_dtype == KEEP_BF16 ? 1 : gather_auto_split(gather_waves(pl.tile, g.M, a->Cout), steps, pl.bk256 ? SPLIT_BK256 : SPLIT_HALF);
+  pl.out_bf16_ok = (p.vec_epi && !a->residual) ? 1 : 0;
+  pl.split_k = pick_split_k(a, auto_split, steps);
+  return KEEP_OK;
+}
+
+// The two policy-independent forms first, then one planner per precision policy.  Where two forms could both take a call the order of the
+// tests decides, here and inside the planners.
+static int plan_form(const keep_conv2d_args* a, ConvP& p, const ConvGeom& g, ConvPlan& pl) {
+  // ---- <= 4 output channels: exact-fp32 VALU kernel in every precision policy
+  if (a->Cout <= 4 && g.is33s1 && !g.reflect && !a->upsample && a->dtype == KEEP_F32 && a->out_dtype != KEEP_BF16 && a->Cin % SC_CH == 0 &&
+      a->in_ld % 4 == 0 && (uintptr_t)a->in % 16 == 0 && a->Ho == a->H && a->Wo == a->W && a->Ho % SC_TH == 0 &&
+      a->Wo % SC_TW == 0 && !a->residual && !a->aux && a->split_k <= 1 && g.pro_al && !(a->flags & KEEP_CONV_NO_COUT4)) {
+    pl.path = PATH_COUT4;
+    pl.split_k = 1;
     return KEEP_OK;
   }
-  pl.path = PATH_GATHER_F32;
-  p.flatk_f32 = (a->Cin < 8 && a->dtype == KEEP_F32 && no_pro && !(a->flags & KEEP_CONV_NO_FLATK_F32)) ? 1 : 0;
-  if (p.flatk_f32) p.nsteps = (a->KH * a->KW * a->Cin + BK - 1) / BK;
-  pl.plain = p.vec_ok && a->Cin % 16 == 0 && no_pro && !a->upsample && pl.tile != 0 && !(a->flags & KEEP_CONV_NO_PLAIN);
-  auto_split = (waves >= kTargetWaves || p.nsteps < 8) ? 1 : (int)max(1L, min(min((long)kTargetWaves / waves, (long)p.nsteps / 4), 32L));
-  pl.split_k = a->split_k > 0 ? a->split_k : auto_split;
-  if (pl.split_k > p.nsteps) pl.split_k = p.nsteps;
-  snprintf(pl.kernel, sizeof(pl.kernel), "conv_f32_kernel<%s>", pl.tile == 0 ? "4, 1, 1, 1" : (pl.tile == 1 ? "2, 2, 1, 1" : "2, 2, 2, 2"));
-  return KEEP_OK;
+  // ---- RGB first convolutions, bf16 policy: persistent im2col-in-LDS kernel
+  if (a->mma == KEEP_MMA_BF16 && g.is33s1 && !a->upsample && a->Cin <= 3 && a->Cout % 4 == 0 && a->Cout >= 32 && a->dtype == KEEP_F32 &&
+      a->out_dtype != KEEP_BF16 && a->Ho == a->H && a->Wo == a->W && a->Ho % 8 == 0 && a->Wo % 32 == 0 && g.no_pro && !a->residual &&
+      !a->aux && a->split_k <= 1 && a->out_ld % 4 == 0 && (uintptr_t)a->out % 16 == 0 && (!a->bias || (uintptr_t)a->bias % 16 == 0) &&
+      !(a->flags & KEEP_CONV_NO_C3)) {
+    pl.path = PATH_C3;
+    pl.split_k = 1;
+    pl.stats_rows = 64;
+    return KEEP_OK;
+  }
+  if (a->mma == KEEP_MMA_X1) return plan_x1(a, p, g, pl);
+  if (a->mma == KEEP_MMA_BF16) return plan_bf16(a, p, g, pl);
+  if (a->mma == KEEP_MMA_X3) {
+    bool to_f32;
+    const int rc = plan_x3(a, p, g, pl, to_f32);
+    if (!to_f32) return rc;
+  }
+  return plan_f32(a, p, g, pl);
+}
+
+static int plan_conv(const keep_conv2d_args* a, ConvP& p, ConvPlan& pl) {
+  memset(&pl, 0, sizeof(pl));
+  fill_conv_params(a, p);
+  pl.wide = (a->Ho % 8 == 0 && a->Wo % 32 == 0);
+  const int rc = plan_form(a, p, conv_geom(a), pl);
+  if (rc == KEEP_OK) plan_kernel_name(a, pl);
+  return rc;
 }
 
 // The struct the caller was compiled against may be an older (shorter) layout of this ABI version: `struct_size` says which.
@@ -2186,18 +2152,30 @@ static int conv_args_in(const keep_conv2d_args* src, keep_conv2d_args& a) {
 
 extern "C" int32_t keep_sizeof_conv2d_args(void) { return (int32_t)sizeof(keep_conv2d_args); }
 
+// What keep_conv2d_plan and keep_conv2d share: the caller's struct in this library's layout, validated and planned (`launch`: with the
+// tensors a launch reads)
+static int conv_prelude(const keep_conv2d_args* a_in, bool launch, keep_conv2d_args& a, ConvP& p, ConvPlan& pl) {
+  int rc = conv_args_in(a_in, a);
+  if (rc != KEEP_OK) return rc;
+  rc = validate_conv(&a);
+  if (rc != KEEP_OK) return rc;
+  if (launch) {
+    KEEP_REQUIRE(a.in && a.weight && a.out, "keep_conv2d: null tensor pointer");
+    KEEP_REQUIRE((uintptr_t)a.weight % 16 == 0, "keep_conv2d: weight pointer must be 16-byte aligned");
+    KEEP_REQUIRE(!a.pro_scale || ((uintptr_t)a.pro_scale % 16 == 0 && (uintptr_t)a.pro_shift % 16 == 0),
+                 "keep_conv2d: pro_scale/pro_shift must be 16-byte aligned");
+  }
+  return plan_conv(&a, p, pl);
+}
+
 extern "C" int32_t keep_conv2d_plan(const keep_conv2d_args* a_in, keep_conv2d_plan_out* out) {
   KEEP_REQUIRE(out != nullptr, "keep_conv2d_plan: null output");
   keep_conv2d_args a_local;
-  int rc = conv_args_in(a_in, a_local);
-  if (rc != KEEP_OK) return rc;
-  const keep_conv2d_args* a = &a_local;
-  rc = validate_conv(a);
-  if (rc != KEEP_OK) return rc;
   ConvP p;
   ConvPlan pl;
-  rc = plan_conv(a, p, pl);
+  const int rc = conv_prelude(a_in, false, a_local, p, pl);
   if (rc != KEEP_OK) return rc;
+  const keep_conv2d_args* a = &a_local;
   memset(out, 0, sizeof(*out));
   const long hw_o = (long)a->Ho * a->Wo;
   out->split_k = pl.split_k;
@@ -2215,19 +2193,11 @@ extern "C" int32_t keep_conv2d_plan(const keep_conv2d_args* a_in, keep_conv2d_pl
 
 extern "C" int32_t keep_conv2d(const keep_conv2d_args* a_in, void* stream) {
   keep_conv2d_args a_local;
-  int rc = conv_args_in(a_in, a_local);
-  if (rc != KEEP_OK) return rc;
-  const keep_conv2d_args* a = &a_local;
-  rc = validate_conv(a);
-  if (rc != KEEP_OK) return rc;
-  KEEP_REQUIRE(a->in && a->weight && a->out, "keep_conv2d: null tensor pointer");
-  KEEP_REQUIRE((uintptr_t)a->weight % 16 == 0, "keep_conv2d: weight pointer must be 16-byte aligned");
-  KEEP_REQUIRE(!a->pro_scale || ((uintptr_t)a->pro_scale % 16 == 0 && (uintptr_t)a->pro_shift % 16 == 0),
-               "keep_conv2d: pro_scale/pro_shift must be 16-byte aligned");
   ConvP p;
   ConvPlan pl;
-  rc = plan_conv(a, p, pl);
+  int rc = conv_prelude(a_in, true, a_local, p, pl);
   if (rc != KEEP_OK) return rc;
+  const keep_conv2d_args* a = &a_local;
   if (pl.path == PATH_NEEDS_PRENORM) {
     keep_set_error("keep_conv2d: a bf16 input with a prologue must go through keep_norm_act_bf16 first (keep_conv2d_plan: wants_bf16_input)");
     return KEEP_EUNSUP;
@@ -2256,7 +2226,7 @@ extern "C" int32_t keep_conv2d(const keep_conv2d_args* a_in, void* stream) {
   dim3 block(256);
   const int tw = pl.wide ? 32 : 16, th = 256 / tw;
   const int tiles_x = a->Wo / tw, tiles_y = a->Ho / th, ncb = (a->Cout + 63) / 64;
-  const int n_cu = n_cu_cached();
+  const int n_cu = keep_num_cu();
   switch (pl.path) {
     case PATH_COUT4: {
       dim3 grid((a->Ho / SC_TH) * (a->Wo / SC_TW), a->N);
@@ -2267,7 +2237,7 @@ extern "C" int32_t keep_conv2d(const keep_conv2d_args* a_in, void* stream) {
     case PATH_C3: {
       const int tx = a->Wo / 32, ty = a->Ho / 8;
       const int n_items = a->N * tx * ty * ncb;
-      hipLaunchKernelGGL(conv3x3_c3_kernel, dim3(n_items < 2 * n_cu ? n_items : 2 * n_cu), block, 0, st, p, tx, ty, ncb, n_items);
+      hipLaunchKernelGGL(conv3x3_c3_kernel, dim3(persistent_grid(n_items, n_cu)), block, 0, st, p, tx, ty, ncb, n_items);
       KEEP_LAUNCH_CHECK("keep_conv2d(Cin<=3)");
       return KEEP_OK;
     }
@@ -2276,16 +2246,16 @@ extern "C" int32_t keep_conv2d(const keep_conv2d_args* a_in, void* stream) {
       if (rc != KEEP_OK) return rc;
       break;
     case PATH_HALO_X3:
-      rc = keep_conv2d_x3_halo(a, p, st);
+      rc = keep_conv2d_x3_halo(a, p, pl, st);
       if (rc != KEEP_OK) return rc;
       break;
     case PATH_GATHER_X3:
-      rc = pl.tile == 4 ? keep_conv2d_x3_gemm_lat(a, p, st) : keep_conv2d_x3_gather(a, p, pl.tile, st);
+      rc = pl.form == FORM_GEMM_LAT ? keep_conv2d_x3_gemm_lat(a, p, pl, st) : keep_conv2d_x3_gather(a, p, pl, st);
       if (rc != KEEP_OK) return rc;
       break;
     case PATH_HALO_F32: {
       const int n_items = a->N * tiles_x * tiles_y * ncb * p.split_k;
-      dim3 gridf(n_items < 2 * n_cu ? n_items : 2 * n_cu);
+      dim3 gridf(persistent_grid(n_items, n_cu));
 #define KEEP_LAUNCH_HF(TWV)                                                                                                  \
   if (a->pro_act == KEEP_PRO_SWISH)                                                                                          \
     hipLaunchKernelGGL((conv3x3_halo_f32_kernel<TWV, KEEP_PRO_SWISH>), gridf, block, 0, st, p, tiles_x, tiles_y, ncb, n_items); \
@@ -2304,7 +2274,7 @@ extern "C" int32_t keep_conv2d(const keep_conv2d_args* a_in, void* stream) {
     }
     case PATH_HALO_BF16: {
       const int n_items = a->N * tiles_x * tiles_y * ncb * p.split_k;
-      dim3 grid3(n_items < 2 * n_cu ? n_items : 2 * n_cu);
+      dim3 grid3(persistent_grid(n_items, n_cu));
       const bool simple = p.split_k == 1 && !a->aux && a->epi_act == KEEP_ACT_NONE;
 #define KEEP_LAUNCH_H3(INB, TWV)                                                                                          \
   if (simple)                                                                                                             \
@@ -2379,8 +2349,7 @@ extern "C" int32_t keep_conv2d(const keep_conv2d_args* a_in, void* stream) {
       KEEP_LAUNCH_CHECK("keep_conv2d(gather f32)");
       break;
     }
-    case PATH_NEEDS_PRENORM:
-      break;
+    case PATH_NEEDS_PRENORM: break;      // (refused above, before anything was launched; no default: a new path must get an arm)
   }
   if (p.split_k > 1) {
     const long total = M * a->Cout;

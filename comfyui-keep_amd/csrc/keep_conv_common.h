@@ -331,3 +331,119 @@ __device__ __forceinline__ HaloItem halo_decode(const ConvP& p, int item, int it
 }
 
 #define KEEP_TAPS(X) X(0, wr0) X(1, wr1) X(2, wr2) X(3, wr3) X(4, wr4) X(5, wr5) X(6, wr6) X(7, wr7) X(8, wr8)
+
+// ------------------------------------------------------------------------------------------------ the plan (host)
+// What plan_conv() (keep_conv.hip) decides for one keep_conv2d call and every launcher receives: the kernel family (path), the form of
+// that family (form), the block tile, split-K and the statistics partition.  The plan names the form; a launcher switches on it and asks
+// again only what follows from the real N (see "plan + dispatch" in keep_conv.hip).
+enum ConvPath {
+  PATH_COUT4 = 0, PATH_C3, PATH_HALO_F32, PATH_HALO_BF16, PATH_HALO_BF16_V1, PATH_GATHER_BF16, PATH_GATHER_F32, PATH_HALO_X3,
+  PATH_GATHER_X3, PATH_NEEDS_PRENORM, PATH_C3_X3
+};
+
+enum ConvForm {
+  FORM_PATH = 0,        // every path but the two below: the path alone names the kernel
+  // PATH_HALO_X3
+  FORM_HALO_UP2,        // x3, KEEP_UPSAMPLE_X2_PHASES: four 2x2-tap phase convolutions on the source grid
+  FORM_X1_STREAM,       // single fp16, 8 x 32 tiles: the streaming kernel's X1 instantiations
+  FORM_X1_HALO16,       // single fp16, 16 x 16 tiles (KEEP_CONV_X1_HALO16); ConvPlan::simple_epi picks the epilogue
+  FORM_X3_HALO,         // x3: the streaming kernel or the stage-barrier one (ConvPlan::stream), the 64-pixel blocks at launch
+  // PATH_GATHER_X3
+  FORM_X1_IM2COL,       // single fp16 im2col
+  FORM_X1_GEMM,         // single fp16 1x1 GEMM (KEEP_CONV_X1_GEMM)
+  FORM_GEMM_LAT,        // x3 GEMM with few rows per image: canonical K slices (keep_gemm_x3l.hip)
+  FORM_GEMM_LN,         // x3 GEMM, four 32-row waves over whole 128-channel rows, LayerNorm in the epilogue
+  FORM_X3_GATHER        // x3 im2col / GEMM
+};
+
+struct ConvPlan {
+  ConvPath path;
+  ConvForm form;
+  int tile;            // gather kernels' block tile: 0 = 128x32 (4,1,1,1), 1 = 64x64 (2,2,1,1), 2 = 128x128 (2,2,2,2 -- FORM_GEMM_LN: 4,1,1,4)
+  bool plain, wide, bk256;
+  bool gemm;           // PATH_GATHER_X3: 1x1 stride-1 unpadded (keep_conv_x3_gather_is_gemm)
+  bool stream;         // FORM_X3_HALO: keep_conv_x3_stream_ok at the planned split-K
+  bool simple_epi;     // FORM_X1_HALO16: no epilogue activation
+  int split_k;
+  int stats_rows;      // output pixels per statistics partial; 0 = this call cannot emit statistics
+  int wants_bf16_input, out_bf16_ok;
+  bool amax_ok;          // this path can fill x3_out_amax (x3 kernels, single pass)
+  char kernel[64];
+};
+
+// geometry the x3 / x1 kernels accept (keep_conv_x3.hip, keep_conv_x3s.hip, keep_gemm_x3l.hip)
+bool keep_conv_x3_halo_ok(const keep_conv2d_args* a);
+bool keep_conv_x3_up2_ok(const keep_conv2d_args* a);
+bool keep_conv_x3_stream_ok(const keep_conv2d_args* a, const ConvP& p, int split_k);
+bool keep_conv_x3_gather_ok(const keep_conv2d_args* a, const ConvP& p);
+bool keep_conv_x3_gather_is_gemm(const keep_conv2d_args* a);
+bool keep_conv_x1_stream_ok(const keep_conv2d_args* a, const ConvP& p);
+bool keep_conv_x1_halo16_ok(const keep_conv2d_args* a);
+bool keep_conv_x1_gather_ok(const keep_conv2d_args* a, const ConvP& p);
+bool keep_conv_x1_gemm_ok(const keep_conv2d_args* a, const ConvP& p);
+bool keep_gemm_x3l_ok(const keep_conv2d_args* a);
+int keep_gemm_x3l_waves(const keep_conv2d_args* a);
+// launch-time shapes of FORM_X3_HALO (keep_conv_x3p.hip: 64-pixel blocks while the real N leaves CUs idle; same values)
+bool keep_conv_x3p_ok(const keep_conv2d_args* a, const ConvP& p, int split_k);
+bool keep_conv_x3q_ok(const keep_conv2d_args* a, const ConvP& p, int split_k);
+bool keep_conv_x3p_full_ok(const keep_conv2d_args* a, const ConvP& p, int split_k);
+// launchers
+int keep_conv2d_x3_c3(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
+int keep_conv2d_x3_halo(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st);
+int keep_conv2d_x3_stream(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st);
+int keep_conv2d_x3_partials(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
+int keep_conv2d_x3_small_full(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
+int keep_conv2d_x3_gather(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st);
+int keep_conv2d_x3_gemm_lat(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st);
+void keep_conv_stats_replica(const ConvP& p, int n_img, hipStream_t st);
+
+// persistent kernels: two blocks per CU walk the items with a grid stride
+static inline int persistent_grid(int n_items, int n_cu) { return n_items < 2 * n_cu ? n_items : 2 * n_cu; }
+
+// The kernel a plan reports (keep_conv2d_plan_out.kernel, as rocprofv3 prints the instantiation), keyed by path and form.  FORM_X3_HALO
+// reports the 256-pixel kernel of the plan also where the launch takes the 64-pixel blocks for the real N.
+static inline void plan_kernel_name(const keep_conv2d_args* a, ConvPlan& pl) {
+  const char* tile = pl.tile == 0 ? "4, 1, 1, 1" : (pl.tile == 1 ? "2, 2, 1, 1" : "2, 2, 2, 2");
+  const char* in_bf16 = a->dtype == KEEP_BF16 ? "true" : "false";
+  const int tw = pl.wide ? 32 : 16;
+  switch (pl.path) {
+    case PATH_COUT4: snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_cout4_kernel"); return;
+    case PATH_C3: snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_c3_kernel"); return;
+    case PATH_C3_X3: snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_c3_x3_kernel"); return;
+    case PATH_HALO_F32: snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_f32_kernel<%d>", tw); return;
+    case PATH_NEEDS_PRENORM: snprintf(pl.kernel, sizeof(pl.kernel), "(keep_norm_act_bf16 first)"); return;
+    case PATH_HALO_BF16:
+    case PATH_HALO_BF16_V1: snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo3_kernel<%s, %d>", in_bf16, tw); return;
+    case PATH_GATHER_BF16:
+      snprintf(pl.kernel, sizeof(pl.kernel), "conv_bf16_kernel<%s, %s, %s>", tile, pl.bk256 ? "256, 1" : "64, 1",
+               (pl.plain && !pl.bk256 && pl.tile != 0) ? "true" : "false");
+      return;
+    case PATH_GATHER_F32: snprintf(pl.kernel, sizeof(pl.kernel), "conv_f32_kernel<%s>", tile); return;
+    case PATH_HALO_X3:
+    case PATH_GATHER_X3: break;
+  }
+  switch (pl.form) {
+    case FORM_HALO_UP2: snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_x3_kernel<32, x2 phases>"); return;
+    case FORM_X1_STREAM:      // <prologue activation, GroupNorm affine, X1>
+      snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_x3s_kernel<%d, %s, true>", a->pro_act, a->pro_scale ? "true" : "false");
+      return;
+    case FORM_X1_HALO16:      // <TW, PRO, SIMPLE_EPI, FASTACT, WDMA, UP2, X1>
+      snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_x3_kernel<16, 0, %s, true, true, false, true>", pl.simple_epi ? "true" : "false");
+      return;
+    case FORM_X3_HALO:
+      if (pl.stream)
+        snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_x3s_kernel");
+      else
+        snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_x3_kernel<%d>", tw);
+      return;
+    // <tile, PLAIN, ONE, KSL, DEEP, KAL, X1>: the trailing template booleans of the x1 instantiations as 0 / 1 (the names have 63 characters)
+    case FORM_X1_IM2COL: snprintf(pl.kernel, sizeof(pl.kernel), "conv_x3_kernel<%s, true, 0, 0, 1, 0, 1>", tile); return;
+    case FORM_X1_GEMM: snprintf(pl.kernel, sizeof(pl.kernel), "conv_x3_kernel<%s, true, 1, 0, 1, 0, 1>", tile); return;
+    case FORM_GEMM_LAT: snprintf(pl.kernel, sizeof(pl.kernel), "gemm_x3l_kernel<%d>", keep_gemm_x3l_waves(a)); return;
+    case FORM_GEMM_LN: snprintf(pl.kernel, sizeof(pl.kernel), "conv_x3_kernel<4, 1, 1, 4, true, true> + LayerNorm"); return;
+    case FORM_X3_GATHER:
+      snprintf(pl.kernel, sizeof(pl.kernel), "conv_x3_kernel<%s, %s, %s>", tile, pl.plain ? "true" : "false", pl.gemm ? "true" : "false");
+      return;
+    case FORM_PATH: break;
+  }
+}

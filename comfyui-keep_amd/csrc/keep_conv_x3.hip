@@ -1083,18 +1083,6 @@ __global__ __launch_bounds__(256) void conv_x3_kernel(ConvP p) {
   staged_epilogue<WGM, WGN, TM, TN>(p, acc, reinterpret_cast<float*>(smem_b), m0, n0, wm, wn, lane, wave, z);
 }
 
-// ------------------------------------------------------------------------------------------------ dispatch
-static int x3_num_cu() {
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-    if (n_cu <= 0) n_cu = 256;
-  }
-  return n_cu;
-}
-
 // ------------------------------------------------------------------------------------------------ 3x3, Cin <= 3, split fp16
 // The RGB first convolutions (3 -> 64 at 512x512: VQ conv_in of the LQ encoder over all B*T frames, of the HQ encoder every
 // frame) under KEEP_MMA_X3 -- the x3 form of conv3x3_c3_kernel (keep_conv.hip): persistent blocks (2 per CU), per 8x32-pixel
@@ -1326,8 +1314,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c3_x3_kernel(ConvP p, int tile
 int keep_conv2d_x3_c3(const keep_conv2d_args* a, ConvP& p, hipStream_t st) {
   const int tx = a->Wo / 32, ty = a->Ho / 8, ncb = (a->Cout + 63) / 64;
   const int n_items = a->N * tx * ty * ncb;
-  const int n_cu = x3_num_cu();
-  hipLaunchKernelGGL(conv3x3_c3_x3_kernel, dim3(n_items < 2 * n_cu ? n_items : 2 * n_cu), dim3(256), 0, st, p, tx, ty, ncb, n_items);
+  hipLaunchKernelGGL(conv3x3_c3_x3_kernel, dim3(persistent_grid(n_items, keep_num_cu())), dim3(256), 0, st, p, tx, ty, ncb, n_items);
   KEEP_LAUNCH_CHECK("keep_conv2d(Cin<=3, x3)");
   return KEEP_OK;
 }
@@ -1392,52 +1379,52 @@ bool keep_conv_x1_gemm_ok(const keep_conv2d_args* a, const ConvP& p) {
          !a->ln_gamma && !a->aux && a->Cin % 32 == 0;
 }
 
-bool keep_conv_x3p_ok(const keep_conv2d_args* a, const ConvP& p, int split_k);
-bool keep_conv_x3q_ok(const keep_conv2d_args* a, const ConvP& p, int split_k);
-bool keep_conv_x3p_full_ok(const keep_conv2d_args* a, const ConvP& p, int split_k);
-int keep_conv2d_x3_small_full(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
-int keep_conv2d_x3_partials(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
-bool keep_conv_x3_stream_ok(const keep_conv2d_args* a, const ConvP& p, int split_k);
-int keep_conv2d_x3_stream(const keep_conv2d_args* a, ConvP& p, int n_cu, hipStream_t st);
+// What runs a FORM_X3_HALO plan: it may shrink to 64-pixel blocks while the real N leaves the 256-pixel kernels too few items
+// (keep_conv_x3p.hip: same values, same partials).  The other forms of PATH_HALO_X3 are fixed by the plan.
+enum HaloRun { RUN_SMALL_PARTIALS, RUN_SMALL_FULL, RUN_STREAM, RUN_HALO };
 
-int keep_conv2d_x3_halo(const keep_conv2d_args* a, ConvP& p, hipStream_t st) {
-  if (a->upsample == KEEP_UPSAMPLE_X2_PHASES) {      // four 2x2-tap phase convolutions on the source grid (kernel comment: UP2)
+static HaloRun x3_halo_run(const keep_conv2d_args* a, const ConvP& p, const ConvPlan& pl) {
+  if (keep_conv_x3p_ok(a, p, p.split_k)) return RUN_SMALL_PARTIALS;                       // split-K, few images: 64-pixel tiles, same partials
+  if (pl.stream) return keep_conv_x3q_ok(a, p, p.split_k) ? RUN_SMALL_FULL : RUN_STREAM;      // few items: 64-pixel blocks, the streaming kernel's values
+  if (keep_conv_x3p_full_ok(a, p, p.split_k)) return RUN_SMALL_PARTIALS;                  // few items, the stage-barrier kernel's epilogue (aux tensor / 16-wide maps)
+  return RUN_HALO;
+}
+
+int keep_conv2d_x3_halo(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st) {
+  const int n_cu = keep_num_cu();
+  dim3 block(256);
+  if (pl.form == FORM_X1_STREAM) return keep_conv2d_x3_stream(a, p, pl, st);      // keep_conv_x3s.hip
+  if (pl.form == FORM_HALO_UP2) {      // four 2x2-tap phase convolutions on the source grid (kernel comment: UP2)
     const int tx = a->W / 32, ty = a->H / 8, ncbv = 4 * (a->Cout / 64);
     const int n_items = a->N * tx * ty * ncbv;
-    const int n_cu = x3_num_cu();
     p.upsample = 0;                                    // the kernel addresses the source like a plain 3x3 convolution
-    p.split_k = 1;
-    dim3 grid(n_items < 2 * n_cu ? n_items : 2 * n_cu), block(256);
+    dim3 grid(persistent_grid(n_items, n_cu));
     hipLaunchKernelGGL((conv3x3_halo_x3_kernel<32, KEEP_PRO_NONE, true, true, true, true>), grid, block, 0, st, p, tx, ty, ncbv, n_items);
     KEEP_LAUNCH_CHECK("keep_conv2d(halo x3, x2 phases)");
     return KEEP_OK;
   }
-  if (a->mma == KEEP_MMA_X1 && a->Ho % 8 == 0 && a->Wo % 32 == 0) return keep_conv2d_x3_stream(a, p, x3_num_cu(), st);      // (plan_conv: keep_conv_x1_stream_ok, split_k == 1)
-  if (a->mma == KEEP_MMA_X1) {      // (plan_conv: keep_conv_x1_halo16_ok -- 16 x 16 tiles, raw input, zero padding, un-split)
+  if (pl.form == FORM_X1_HALO16) {      // 16 x 16 tiles, raw input, zero padding, un-split
     const int tiles_x = a->Wo / 16, tiles_y = a->Ho / 16, ncb = (a->Cout + 63) / 64;
     const int n_items = a->N * tiles_x * tiles_y * ncb;
-    const int n_cu = x3_num_cu();
-    dim3 grid(n_items < 2 * n_cu ? n_items : 2 * n_cu), block(256);
-    p.split_k = 1;
-    if (a->epi_act == KEEP_ACT_NONE)
+    dim3 grid(persistent_grid(n_items, n_cu));
+    if (pl.simple_epi)
       hipLaunchKernelGGL((conv3x3_halo_x3_kernel<16, KEEP_PRO_NONE, true, true, true, false, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
     else
       hipLaunchKernelGGL((conv3x3_halo_x3_kernel<16, KEEP_PRO_NONE, false, true, true, false, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
     KEEP_LAUNCH_CHECK("keep_conv2d(halo x1, 16 x 16 tiles)");
     return KEEP_OK;
   }
-  const int nchunks = a->Cin / 16;
-  if (p.split_k > nchunks) p.split_k = nchunks;
-  if (keep_conv_x3p_ok(a, p, p.split_k)) return keep_conv2d_x3_partials(a, p, st);                        // keep_conv_x3p.hip (few images: 64-pixel tiles, same partials)
-  if (keep_conv_x3_stream_ok(a, p, p.split_k) && keep_conv_x3q_ok(a, p, p.split_k)) return keep_conv2d_x3_small_full(a, p, st);      // few items: 64-pixel blocks, the streaming kernel's values
-  if (keep_conv_x3_stream_ok(a, p, p.split_k)) return keep_conv2d_x3_stream(a, p, x3_num_cu(), st);      // keep_conv_x3s.hip
-  if (keep_conv_x3p_full_ok(a, p, p.split_k)) return keep_conv2d_x3_partials(a, p, st);                  // few items, this kernel's epilogue (aux tensor / 16-wide maps): 64-pixel blocks, same values
-  const bool wide = (a->Ho % 8 == 0 && a->Wo % 32 == 0);
+  switch (x3_halo_run(a, p, pl)) {      // FORM_X3_HALO
+    case RUN_SMALL_PARTIALS: return keep_conv2d_x3_partials(a, p, st);      // keep_conv_x3p.hip
+    case RUN_SMALL_FULL: return keep_conv2d_x3_small_full(a, p, st);
+    case RUN_STREAM: return keep_conv2d_x3_stream(a, p, pl, st);      // keep_conv_x3s.hip
+    case RUN_HALO: break;
+  }
+  const bool wide = pl.wide;
   const int tw = wide ? 32 : 16, th = 256 / tw;
   const int tiles_x = a->Wo / tw, tiles_y = a->Ho / th, ncb = (a->Cout + 63) / 64;
   const int n_items = a->N * tiles_x * tiles_y * ncb * p.split_k;
-  const int n_cu = x3_num_cu();
-  dim3 grid(n_items < 2 * n_cu ? n_items : 2 * n_cu), block(256);      // 2 blocks per CU (one per CU measured: DESIGN 5.3, round 3)
+  dim3 grid(persistent_grid(n_items, n_cu));      // 2 blocks per CU (one per CU measured: DESIGN 5.3, round 3)
   const bool simple = p.split_k == 1 && !a->aux && a->epi_act == KEEP_ACT_NONE;
   // weights by LDS-DMA; the exact-activation form below keeps the VGPR-staged weights
 #define KEEP_LAUNCH_HX2(TWV, PROV)                                                                                          \
@@ -1527,32 +1514,31 @@ __global__ __launch_bounds__(256) void conv_x3_gather_stats_replica_kernel(ConvP
 }
 
 static constexpr long KEEP_GATHER_SMALL_ROWS = 4096;      // rows in flight up to which a launch planned for the 128 x 128 tile runs the 64 x 64 tile
-// tile: plan_conv's choice (1: 64x64 block tiles, 2: 128x128, 3: 128x128 as four 32-row waves with the LayerNorm epilogue) --
-// the launch never re-derives it
-int keep_conv2d_x3_gather(const keep_conv2d_args* a, ConvP& p, int tile, hipStream_t st) {
+// The plan's form picks the kernel variant; its tile follows the reference batch because the statistics partition does.
+int keep_conv2d_x3_gather(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st) {
   const long M = p.M;
-  // the plan's tile follows the reference batch because the statistics partition does; a launch WITHOUT statistics may take the small
-  // tile when the real row count is small (one clip in flight: 4 x the blocks) -- the K order of a row's sum does not depend on the tile.
-  // WITH statistics (the encoder's stride-2 convolutions): the small tile too, the 128-row partials then come from the replica kernel above.
+  const bool ln = pl.form == FORM_GEMM_LN, x1 = pl.form == FORM_X1_IM2COL || pl.form == FORM_X1_GEMM;
+  // a launch WITHOUT statistics may take the small tile when the real row count is small (one clip in flight: 4 x the blocks) -- the K
+  // order of a row's sum does not depend on the tile.  WITH statistics (the encoder's stride-2 convolutions): the small tile too, the
+  // 128-row partials then come from the replica kernel above.
+  bool big_tile = pl.tile == 2;
   float* replica_stats = nullptr;
-  if (tile == 2 && p.stats && M <= KEEP_GATHER_SMALL_ROWS && M % 128 == 0 && ((long)p.Ho * p.Wo) % 128 == 0 && p.split_k == 1 && p.vec_epi &&
+  if (big_tile && p.stats && M <= KEEP_GATHER_SMALL_ROWS && M % 128 == 0 && ((long)p.Ho * p.Wo) % 128 == 0 && p.split_k == 1 && p.vec_epi &&
       p.Cout % 4 == 0 && !p.out_bf16 && !(a->flags & KEEP_CONV_NO_SMALL_PARTIALS)) {
     replica_stats = p.stats;
     p.stats = nullptr;
-    tile = 1;
+    big_tile = false;
   }
-  if (tile == 2 && !p.stats && M <= KEEP_GATHER_SMALL_ROWS) tile = 1;
-  const int big_tile = tile >= 2;
+  if (big_tile && !ln && !p.stats && M <= KEEP_GATHER_SMALL_ROWS) big_tile = false;
   const int steps = a->KH * a->KW * ((a->Cin + XBK - 1) / XBK);
-  if (p.split_k > steps) p.split_k = steps;
-  const bool plain = !a->pro_scale && a->pro_act == KEEP_PRO_NONE;
+  const bool plain = pl.plain;
   dim3 block(256);
   // 1x1 stride-1 unpadded convolutions (token GEMMs): block-relative buffer-load fetch, no im2col index arithmetic
-  const bool one = keep_conv_x3_gather_is_gemm(a);
+  const bool one = pl.gemm;
 #define KEEP_LAUNCH_GX(A, B, C, D)                                                                 \
-  if (a->mma == KEEP_MMA_X1 && one)      /* (keep_conv_x1_gemm_ok: plain GEMM form) */             \
+  if (x1 && one)                                                                                   \
     hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, true, true, false, true, false, true>), grid, block, 0, st, p); \
-  else if (a->mma == KEEP_MMA_X1) /* (keep_conv_x1_gather_ok: plain im2col form) */                \
+  else if (x1)                                                                                     \
     hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, true, false, false, true, false, true>), grid, block, 0, st, p); \
   else if (p.kslice_steps == 4 && plain && C * D == 1 && steps % 4 == 0)                                \
     hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, true, true, true, true, C * D == 1>), grid, block, 0, st, p); \
@@ -1576,7 +1562,7 @@ int keep_conv2d_x3_gather(const keep_conv2d_args* a, ConvP& p, int tile, hipStre
   const bool rowmajor = gy > 1 && gx >= 1024 && gx * gy < (1L << 30);
   p.tile_cols = rowmajor ? (int)gy : 0;
   dim3 grid(rowmajor ? (unsigned)(gx * gy) : (unsigned)gx, rowmajor ? 1u : (unsigned)gy, p.split_k);
-  if (tile == 3) {
+  if (ln) {
     hipLaunchKernelGGL((conv_x3_kernel<4, 1, 1, 4, true, true>), grid, block, 0, st, p);
   } else if (!big_tile) {
     KEEP_LAUNCH_GX(2, 2, 1, 1)

@@ -728,8 +728,6 @@ bool keep_conv_x3p_ok(const keep_conv2d_args* a, const ConvP& p, int split_k) {
          (a->pro_act == KEEP_PRO_NONE || (a->pro_act == KEEP_PRO_SWISH && p.fast)) && !(a->flags & KEEP_CONV_NO_SMALL_PARTIALS);
 }
 
-void keep_conv_stats_replica(const ConvP& p, int n_img, hipStream_t st);      // keep_conv_x3s.hip
-
 // Un-split plans conv3x3_halo_x3_kernel would run (keep_conv2d_x3_halo has already offered them to the streaming kernel's family) with few
 // items: the same 64-pixel blocks with the full epilogue.  Statistics only on 8 x 32-tile maps (the replica kernel's partition).
 bool keep_conv_x3p_full_ok(const keep_conv2d_args* a, const ConvP& p, int split_k) {

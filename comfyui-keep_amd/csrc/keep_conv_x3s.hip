@@ -726,12 +726,12 @@ bool keep_conv_x1_stream_ok(const keep_conv2d_args* a, const ConvP& p) {
          (!a->pro_scale || a->pad_mode == KEEP_PAD_ZERO);
 }
 
-int keep_conv2d_x3_stream(const keep_conv2d_args* a, ConvP& p, int n_cu, hipStream_t st) {
+int keep_conv2d_x3_stream(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st) {
   const int tiles_x = a->Wo / 32, tiles_y = a->Ho / 8, ncb = (a->Cout + 63) / 64;
   const int n_items = a->N * tiles_x * tiles_y * ncb;
-  dim3 grid(n_items < 2 * n_cu ? n_items : 2 * n_cu), block(256);
+  dim3 grid(persistent_grid(n_items, keep_num_cu())), block(256);
   const bool aff = a->pro_scale != nullptr;
-  if (a->mma == KEEP_MMA_X1) {    // (keep_conv_x1_stream_ok: Cin % 32 == 0, the prologue forms of the x3 instantiations below)
+  if (pl.form == FORM_X1_STREAM) {    // (keep_conv_x1_stream_ok: Cin % 32 == 0, the prologue forms of the x3 instantiations below)
     if (a->pro_act == KEEP_PRO_SWISH)
       hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_SWISH, true, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
     else if (a->pro_act == KEEP_PRO_RELU)

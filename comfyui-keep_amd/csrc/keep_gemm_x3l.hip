@@ -231,21 +231,21 @@ bool keep_gemm_x3l_ok(const keep_conv2d_args* a) {
 // every 4 K steps at least where the launches are many (conv_x3_kernel KSL: 16 adds per 24 MFMAs and wave)
 int keep_gemm_x3l_waves(const keep_conv2d_args* a) { return a->Cin >= 1024 ? 8 : 4; }
 
-int keep_conv2d_x3_gather(const keep_conv2d_args* a, ConvP& p, int tile, hipStream_t st);
-
 // The sums are defined by the K slicing; WHICH kernel evaluates them follows the real row count (bit-neutral): the latency form while
 // its 32 x 32 tiles leave CUs idle, conv_x3_kernel with canonical slices (p.kslice_steps: 64 x 64 or 128 x 128 block tiles, operands
 // staged through LDS -- 4 x less L2 -> CU traffic per FLOP) beyond.
-int keep_conv2d_x3_gemm_lat(const keep_conv2d_args* a, ConvP& p, hipStream_t st) {
+int keep_conv2d_x3_gemm_lat(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st) {
   const long M = p.M;
-  const bool plain = !a->pro_scale && a->pro_act == KEEP_PRO_NONE;
+  const bool plain = pl.plain;
   const int nw = keep_gemm_x3l_waves(a);
   const long tiles32 = (M / 32) * (a->Cout / 32);
   const bool by_tiles = (a->flags & KEEP_CONV_GEMM_LAT_TILES) || (tiles32 > GL_MAX_TILES && !(a->flags & KEEP_CONV_GEMM_LAT_WAVES));
   if (by_tiles) {
     p.kslice_steps = a->Cin / nw / 32;
-    p.split_k = 1;
-    return keep_conv2d_x3_gather(a, p, 1, st);      // 64 x 64 tiles at every row count: the slice totals of a 128 x 128 tile leave one block per CU
+    ConvPlan tiles = pl;      // 64 x 64 tiles at every row count: the slice totals of a 128 x 128 tile leave one block per CU
+    tiles.form = FORM_X3_GATHER;
+    tiles.tile = 1;
+    return keep_conv2d_x3_gather(a, p, tiles, st);
   }
   const int gm = cdiv(M, 32), gn = a->Cout / 32;
   const int m_fast = (long)M > (long)a->Cout ? 1 : 0;       // the faster index walks the LARGER operand: each XCD sees 1/8 of it

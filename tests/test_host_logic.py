@@ -904,15 +904,15 @@ def _family(s):
     return re.sub(r'<([^>]*)>', args, s).strip()
 
 
-# families of csrc/keep_conv.hip:plan_conv that no argument struct can reach (must stay empty unless a family truly is unreachable)
+# families of csrc/keep_conv_common.h:plan_kernel_name that no argument struct can reach (must stay empty unless a family truly is unreachable)
 UNREACHABLE_CONV_FAMILIES = set()
 
 
 def test_footprint_conv_table_reaches_every_kernel_family():
     """tests/test_gpu_footprint.py's convolution table against keep_conv2d_plan (host C): every case lands on the kernel it names,
-    and the families reached are exactly the family strings plan_conv can print -- a new family fails here until it has a case."""
+    and the families reached are exactly the family strings plan_kernel_name can print -- a new family fails here until it has a case."""
     import test_gpu_footprint as T
-    src = open(os.path.join(ROOT, 'comfyui-keep_amd', 'csrc', 'keep_conv.hip')).read()
+    src = open(os.path.join(ROOT, 'comfyui-keep_amd', 'csrc', 'keep_conv_common.h')).read()
     declared = {_family(f) for f in re.findall(r'snprintf\(pl\.kernel, sizeof\(pl\.kernel\), "([^"]+)"', src)}
     assert len(declared) >= 14, declared
     reached, variants, auto_split = set(), set(), []
