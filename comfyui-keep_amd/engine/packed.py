@@ -1,5 +1,6 @@
 """Lifecycle shared by the packed facelib engines (ParseNet, RetinaFace, YOLOv5-face): one packed fp32 blob on the host, ``to()`` uploads
 it and activates the matrix-core policy, ``to('cpu')`` drops the device copies."""
+import numpy as np
 import torch
 
 from . import hiplib as L
@@ -32,6 +33,16 @@ class PackedEngine:
         self.device = torch.device('cpu')
         self.w = self._dev = None
         self.o = ops.Ops()
+
+    @classmethod
+    def _rebuild(cls, blob, index, precision, **attrs):
+        """The shared half of an engine's ``from_packed``: an instance around a packed blob that another process (or this one) made, with the
+        attributes its constructor would have derived (``attrs``) -- no state dict, no folding, nothing uploaded yet."""
+        self = cls.__new__(cls)
+        for k, v in attrs.items():
+            setattr(self, k, v)
+        self._init_packed(np.ascontiguousarray(blob), index, precision)
+        return self
 
     def x3_names(self):
         raise NotImplementedError

@@ -140,11 +140,8 @@ class ParseNetEngine(PackedEngine):
 
     @classmethod
     def from_packed(cls, blob, index, in_size=512, out_size=512, precision='x3'):
-        self = cls.__new__(cls)
-        self.in_size, self.out_size = in_size, out_size
-        self.blocks = parsenet_spec(in_size=in_size, out_size=out_size)
-        self._init_packed(np.ascontiguousarray(blob), index, precision)
-        return self
+        return cls._rebuild(blob, index, precision, in_size=in_size, out_size=out_size,
+                            blocks=parsenet_spec(in_size=in_size, out_size=out_size))
 
     def x3_names(self):
         return [n for n, (_, sh) in self._index.items() if len(sh) == 4 and sh[-1] % 16 == 0]

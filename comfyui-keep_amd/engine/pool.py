@@ -22,6 +22,9 @@ Round 5:
   * ``set_parser``: the workers also run ParseNet on the crops they restored (face_restoration_helper.py:418-424) and hand the class
     maps back with them, so that of a single video's ``detect -> restore -> parse -> paste`` chain only the paste-back itself stays
     on the root GPU;
+  * ``set_detector`` / ``detect``: the workers also hold the RetinaFace detector (``RetinaFaceEngine.packed()``) and run their share of
+    a video's detection pre-pass -- chunk k of detector inputs on rank k % world, inputs through the same input arena, the few rows
+    per frame back over the control connection (modules/keep_processor.py:_detect_all);
   * no strong reference from the interpreter's exit handlers to the net: ``weakref.finalize`` owns the clean-up, the pool holds no
     reference to the net at all (``run(net, ...)``).
 
@@ -47,6 +50,7 @@ from . import dist as kdist
 
 _WORKER = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'pool_worker.py')
 JOIN_TIMEOUT_S = float(os.environ.get('KEEP_POOL_JOIN_TIMEOUT', '120'))
+DETECTOR_KINDS = ('retinaface',)         # ``pool_kind`` of the detector engines a worker can rebuild (pool_worker.py: 'detector')
 
 
 def wanted_gpus():
@@ -131,6 +135,10 @@ class GpuPool:
         self._procs, self._conns, self._arenas, self._listener_box = [], {}, {}, [None]
         self._seq = 0
         self._parser_sent = None
+        self._detector_sent = None
+        self._names_unsent = set()                       # ranks whose arenas were (re)allocated and who have not been told the names yet
+        self.detector_calls, self.detect_ms = {}, {}     # per rank, of the last ``detect``: detector calls so far / time inside the detector
+        self.detect_ms_total = {}                        # per rank, summed over every ``detect`` so far (a caller may clear it)
         self.weights_generation = getattr(net, 'weights_generation', 0)
         self._finalizer = weakref.finalize(self, _cleanup, self._procs, self._conns, self._listener_box, self._arenas)
         try:
@@ -287,8 +295,34 @@ class GpuPool:
         self._broadcast_request(lambda r, seq: ('parsenet', seq, packed))
         self._parser_sent = engine
 
+    @property
+    def closed(self):
+        return not self._conns
+
+    @staticmethod
+    def takes_detector(engine):
+        """Whether ``engine`` is a detector the workers can rebuild: it names a kind they know (``pool_kind``) and has ``packed()``."""
+        return getattr(engine, 'pool_kind', None) in DETECTOR_KINDS and hasattr(engine, 'packed')
+
+    def set_detector(self, engine):
+        """Give every worker the detector -- ``engine``: the root's ``engine/retinaface.py:RetinaFaceEngine`` (its kind, its packed blob
+        and the settings its constructor resolved are what travels) -- so that ``detect`` spreads a video's detection pre-pass over the
+        pool.  Sent once per engine object; the root runs its own share on ``engine`` itself."""
+        if self._detector_sent is engine:
+            return
+        if self.closed:
+            raise PoolError("GPU pool: set_detector on a closed pool")
+        if not self.takes_detector(engine):
+            raise PoolError(f"GPU pool: set_detector takes an engine of kind {DETECTOR_KINDS} with packed(), got {type(engine).__name__} "
+                            f"(pool_kind {getattr(engine, 'pool_kind', None)!r})")
+        kind, packed = engine.pool_kind, tuple(engine.packed())
+        self._detector_sent = None
+        self._broadcast_request(lambda r, seq: ('detector', seq, kind, packed))
+        self._detector_sent = engine
+
     def _arena(self, r, need_in, need_out):
-        """The worker's pair of shared-memory arenas, grown (never shrunk) to the sizes this call needs."""
+        """The worker's pair of shared-memory arenas, grown (never shrunk) to the sizes this call needs.  A rank whose arenas changed stays
+        in ``_names_unsent`` until a request has carried the new names to it (``_arena_names``), whatever happens in between."""
         cur = self._arenas.get(r, (None, None))
         sizes = (need_in, need_out)
         new = list(cur)
@@ -301,7 +335,13 @@ class GpuPool:
                 new[k] = shared_memory.SharedMemory(create=True, size=max(int(sizes[k] * 1.25), 1 << 20))
                 changed = True
         self._arenas[r] = tuple(new)
+        if changed:
+            self._names_unsent.add(r)
         return self._arenas[r], changed
+
+    def _arena_names(self, r):
+        """What a request tells worker ``r`` about its arenas: their names while it has not heard of them, None afterwards."""
+        return tuple(m.name for m in self._arenas[r]) if r in self._names_unsent else None
 
     # ------------------------------------------------------------------ one sharded call
     def run(self, net, clips_u8, max_b=None, sink=None, parse=False):
@@ -322,7 +362,7 @@ class GpuPool:
             shapes = [tuple(int(v) for v in clips_u8[i].shape) for i in ids]
             total = int(sum(int(np.prod(s)) for s in shapes))
             n_cls = int(sum(int(np.prod(s[:3])) for s in shapes)) if parse else 0
-            (shm_in, shm_out), changed = self._arena(r, total, total + n_cls)
+            (shm_in, shm_out), _ = self._arena(r, total, total + n_cls)
             off = 0
             for i, s in zip(ids, shapes):
                 k = int(np.prod(s))
@@ -334,9 +374,10 @@ class GpuPool:
                 else:
                     torch.from_numpy(dst).copy_(c)           # (host or device tensor)
                 off += k
-            jobs[r] = (ids, shapes, shm_in, shm_out, changed)
+            jobs[r] = (ids, shapes, shm_in, shm_out)
         seq, sent, err = self._request(
-            sorted(jobs), lambda r, s: ('run', s, (jobs[r][2].name, jobs[r][3].name) if jobs[r][4] else None, jobs[r][0], jobs[r][1], max_b, bool(parse)))
+            sorted(jobs), lambda r, s: ('run', s, self._arena_names(r), jobs[r][0], jobs[r][1], max_b, bool(parse)))
+        self._names_unsent.difference_update(sent)
         mine = {i: clips_u8[i] for i in range(0, n, self.world)}
         out = [None] * n
         if err is None:
@@ -347,7 +388,7 @@ class GpuPool:
             except BaseException as e:                       # still drain the workers that were dispatched: their replies must
                 err = e                                      # not be read by the NEXT call
         for r in sent:
-            ids, shapes, shm_in, shm_out, _ = jobs[r]
+            ids, shapes, shm_in, shm_out = jobs[r]
             try:
                 self._collect(r, seq)
                 if err is not None:
@@ -375,6 +416,71 @@ class GpuPool:
                 self.close()                                 # protocol / worker failure: nothing of this pool can be trusted
             raise err
         return None if sink is not None else out
+
+    # ------------------------------------------------------------------ one sharded detection call
+    def detect(self, chunks, conf_threshold=0.8):
+        """list of uint8 [n_k,H,W,3] detector inputs (host numpy or tensors; n_k may differ) -> one ``detect_batch`` result per frame, in
+        frame order, as the root's ``detect_batch`` over the concatenated frames returns them.  Chunk k runs on rank k % world: a worker's
+        chunks travel through its input arena, its (few) rows per frame come back over the control connection; the root runs its own
+        chunks on its GPU while the workers run theirs."""
+        engine = self._detector_sent
+        if engine is None:
+            raise PoolError("GPU pool: detect() before the detector was sent (GpuPool.set_detector)")
+        if self.closed:
+            raise PoolError("GPU pool: detect() on a closed pool")
+        n = len(chunks)
+        for i, c in enumerate(chunks):                       # every chunk is judged before any arena is touched
+            if c.dtype not in (np.uint8, torch.uint8):
+                raise TypeError(f"GpuPool.detect: chunk {i} is {c.dtype}, not uint8")
+            if len(c.shape) != 4 or int(c.shape[3]) != 3:
+                raise ValueError(f"GpuPool.detect: chunk {i} has shape {tuple(c.shape)}, not [n, H, W, 3]")
+        self.detect_ms = {}
+        jobs = {}
+        for r in range(1, self.world):
+            ids = list(range(r, n, self.world))
+            if not ids:
+                continue
+            shapes = [tuple(int(v) for v in chunks[i].shape) for i in ids]
+            total = int(sum(int(np.prod(s)) for s in shapes))
+            (shm_in, _), _ = self._arena(r, total, 0)
+            off = 0
+            for i, s in zip(ids, shapes):
+                dst = np.ndarray(s, dtype=np.uint8, buffer=shm_in.buf, offset=off)
+                torch.from_numpy(dst).copy_(torch.as_tensor(chunks[i]))   # (host array, host or device tensor)
+                off += int(np.prod(s))
+            jobs[r] = (ids, shapes)
+        seq, sent, err = self._request(
+            sorted(jobs), lambda r, s: ('detect', s, self._arena_names(r), jobs[r][1], float(conf_threshold)))
+        self._names_unsent.difference_update(sent)
+        out = [None] * n
+        if err is None:
+            try:
+                t0 = time.perf_counter()
+                for i in range(0, n, self.world):
+                    out[i] = engine.detect_batch(chunks[i], conf_threshold)
+                self.detect_ms[0] = (time.perf_counter() - t0) * 1e3
+            except BaseException as e:                       # still drain the workers that were dispatched
+                err = e
+        for r in sent:
+            ids, shapes = jobs[r]
+            try:
+                msg = self._collect(r, seq)
+                if err is not None:
+                    continue
+                _, _, results, self.detector_calls[r], self.detect_ms[r] = msg
+                if len(results) != len(ids) or any(len(res) != s[0] for res, s in zip(results, shapes)):
+                    raise PoolError(f"pool worker {r}: detect returned {[len(x) for x in results]} frames for chunks of {[s[0] for s in shapes]}")
+                for i, res in zip(ids, results):
+                    out[i] = res
+            except BaseException as e:
+                err = err or e
+        if err is not None:
+            if isinstance(err, PoolError):
+                self.close()                                 # protocol / worker failure: nothing of this pool can be trusted
+            raise err
+        for r, v in self.detect_ms.items():
+            self.detect_ms_total[r] = self.detect_ms_total.get(r, 0.0) + v
+        return [f for res in out for f in res]
 
     def close(self):
         self._finalizer()                                    # idempotent: runs _cleanup once, also at garbage collection / exit

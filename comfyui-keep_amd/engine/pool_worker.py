@@ -9,17 +9,25 @@ the group and then serves numbered requests:
         this GPU -> restored uint8 crops (and, with ``parse``, the ParseNet class maps of those crops) into the output arena
   ('configure', seq, cfg)      ``KeepNet.apply_pool_config``: precision policy, plan reference batch, kernel overrides, graph mode
   ('parsenet', seq, packed)    rebuild ``engine/parsenet.py:ParseNetEngine`` from the root engine's packed blob (``ParseNetEngine.packed()``)
+  ('detector', seq, kind, packed)   kind 'retinaface': rebuild ``engine/retinaface.py:RetinaFaceEngine`` from the root engine's
+        ``packed()`` on this GPU; any other kind is refused
+  ('detect', seq, arena names | None, shapes, conf_threshold)   uint8 detector inputs [n_k,H,W,3], chunk after chunk in the input
+        arena -> ``detect_batch`` per chunk on this GPU -> ('done', seq, one list of per-frame [n,15] arrays per chunk, detector calls
+        so far, milliseconds inside the detector) over the control connection (a few rows per frame: no arena)
 
 The engine is imported by path, without the ComfyUI node surface (``comfyui-keep_amd/__init__.py`` is never executed here): a
 worker needs neither ComfyUI nor the face helper.  ``KEEP_POOL_FAKE_NET=1``: a stand-in engine (restored = 255 - crop, class map =
-blue channel mod 19) so that the protocol runs on a machine without a GPU (tests/test_dist_gloo.py).
+blue channel mod 19; detector = ``fake_detect_batch``) so that the protocol runs on a machine without a GPU (tests/test_dist_gloo.py,
+tests/test_pool_detect.py).
 """
 import argparse
 import ast
+import contextlib
 import datetime
 import importlib
 import os
 import sys
+import time
 import traceback
 import types
 from multiprocessing import resource_tracker, shared_memory
@@ -53,6 +61,26 @@ class _FakeNet:
         import numpy as np
         top = 255 if self.config['precision'] == 'x3' else 254
         return {i: (top - c.numpy().astype(np.int16)).clip(0, 255).astype(np.uint8) for i, c in mine.items()}
+
+
+def fake_detect_batch(frames, conf_threshold=0.8):
+    """The stand-in detector of KEEP_POOL_FAKE_NET=1: one [1,15] float32 row per frame, a deterministic function of the frame's bytes
+    (and of the threshold), so that order and content of a pooled detection can be checked against a local run of this function."""
+    import numpy as np
+    out = []
+    for f in np.asarray(frames):
+        b = np.ascontiguousarray(f).reshape(-1).astype(np.int64)
+        s = int(b.sum())
+        w = int((b * (np.arange(b.size, dtype=np.int64) % 251 + 1)).sum())
+        row = [s % 97, w % 89, s % 97 + 20 + f.shape[1], w % 89 + 20 + f.shape[0], float(conf_threshold)]
+        row += [float((w // (k + 1) + 7 * k) % 509) / 4.0 for k in range(10)]
+        out.append(np.asarray([row], dtype=np.float32))
+    return out
+
+
+class _FakeDetector:
+    def detect_batch(self, frames, conf_threshold=0.8):
+        return fake_detect_batch(frames, conf_threshold)
 
 
 def _attach(name):
@@ -118,7 +146,8 @@ def main():
         except Exception:
             pass
         raise
-    parser = None
+    parser = detector = None
+    detector_calls = 0
     arenas = [None, None]
     while True:
         try:
@@ -141,13 +170,47 @@ def main():
                     parser = PN.ParseNetEngine.from_packed(*msg[2]).to(device)
                 conn.send(('ok', seq))
                 continue
-            _, _, names, ids, shapes, max_b, parse = msg
+            if msg[0] == 'detector':
+                _, _, kind, packed = msg
+                if kind != 'retinaface':                     # (the kinds of engine/pool.py:DETECTOR_KINDS, one branch each)
+                    raise RuntimeError(f"detector of kind {kind!r}: this worker rebuilds 'retinaface' only")
+                if fake:
+                    detector = _FakeDetector()
+                else:
+                    (RF,) = _engine('retinaface')
+                    with torch.cuda.device(device):
+                        detector = RF.RetinaFaceEngine.from_packed(*packed).to(device)
+                conn.send(('ok', seq))
+                continue
+            names = msg[2]
             if names is not None:                        # the root (re)allocated this worker's arenas
                 for m in arenas:
                     if m is not None:
                         m.close()
                 arenas = [_attach(names[0]), _attach(names[1])]
             shm_in, shm_out = arenas
+            if msg[0] == 'detect':
+                _, _, _, shapes, conf = msg
+                if detector is None:
+                    raise RuntimeError("detect before the detector was sent (GpuPool.set_detector)")
+                if fail_at == f'{a.rank}:detect':
+                    raise RuntimeError('injected failure inside detect')
+                results, off = [], 0
+                t0 = time.perf_counter()
+                # a request is served on this process's main thread, but grad mode and the current device are thread-local state nobody
+                # else sets here: say both where the detector runs
+                with torch.no_grad(), (contextlib.nullcontext() if fake else torch.cuda.device(device)):
+                    for s in shapes:
+                        frames = np.ndarray(s, dtype=np.uint8, buffer=shm_in.buf, offset=off)
+                        off += int(np.prod(s))
+                        try:
+                            results.append(detector.detect_batch(frames, conf))
+                        finally:
+                            del frames                   # (a view of the arena must not outlive the request: the arena could not be closed)
+                        detector_calls += 1
+                conn.send(('done', seq, results, detector_calls, (time.perf_counter() - t0) * 1e3))
+                continue
+            _, _, _, ids, shapes, max_b, parse = msg
             mine, off = {}, 0
             for i, s in zip(ids, shapes):
                 k = int(np.prod(s))

@@ -250,6 +250,32 @@ class RetinaFaceEngine(PackedEngine):
         # score ordering + NMS of the survivors on the device (keep_retina_nms); 0: the numpy path of round 3 (the tests' reference)
         self.device_nms = os.environ.get('KEEP_AMD_DEVICE_NMS', '1') != '0' and self.max_survivors <= 4096
 
+    pool_kind = 'retinaface'     # what engine/pool.py:GpuPool.set_detector tells the workers to rebuild from ``packed()``
+
+    def settings(self):
+        """What the constructor resolved from the ``KEEP_AMD_DETECT_*`` / ``KEEP_AMD_DEVICE_NMS`` environment: travels with ``packed()`` so
+        that a rebuilt engine does not resolve them again in the process that rebuilds it.  (``KEEP_AMD_DEVICE_TIED_NMS`` is not among
+        them: ``_tied_frames`` reads it per call, and both of its paths return the same rows.)"""
+        return {'max_survivors': self.max_survivors, 'max_frames': self.max_frames, 'device_nms': self.device_nms}
+
+    def packed(self):
+        """(packed fp32 blob, index, backbone, precision, settings): what ``from_packed`` rebuilds the engine from in another process
+        (engine/pool.py: the workers of the GPU pool run their share of a video's detection pre-pass)."""
+        return self._blob, self._index, self.backbone, self.precision, self.settings()
+
+    @classmethod
+    def from_packed(cls, blob, index, backbone, precision='x3', settings=None):
+        if backbone not in BACKBONES:
+            raise ValueError(f"RetinaFaceEngine: backbone must be one of {tuple(BACKBONES)}, got {backbone!r}")
+        cfg = BACKBONES[backbone]
+        self = cls._rebuild(blob, index, precision, backbone=backbone, cfg=cfg,
+                            _act=L.ACT_LRELU01 if cfg['out_channel'] <= 64 else L.ACT_RELU, _priors={}, _priors_dev={})
+        s = settings or {}
+        self.max_survivors = int(s.get('max_survivors', 4096))
+        self.max_frames = int(s.get('max_frames', 32))
+        self.device_nms = bool(s.get('device_nms', True)) and self.max_survivors <= 4096
+        return self
+
     def x3_names(self):
         return [n for n, (_, sh) in self._index.items() if len(sh) >= 2 and sh[-1] % 16 == 0 and not n.endswith('.dw.weight')]
 

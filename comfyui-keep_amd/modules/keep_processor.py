@@ -702,7 +702,9 @@ class KEEPFaceProcessor:
         """Landmarks of every frame (keep_processor.py:207-213: one ``get_face_landmarks_5`` call -- one detector forward and
         one host round trip -- per frame).  With the engine's detector (engine/retinaface.py, ``detect_batch``) the network
         runs over the video in chunks of the detector's batch axis (``KEEP_AMD_DETECT_BATCH`` frames: the host never holds more
-        than one chunk of detector inputs -- a 3000-frame 1080p video would otherwise stack ~13 GB of resized frames); the
+        than two chunks of detector inputs, the one in the detector and the one being prepared -- a 3000-frame 1080p video would
+        otherwise stack ~13 GB of resized frames; with a worker pool the chunks go out in windows of ``world`` chunks,
+        ``_detect_all_pooled``, and the bound is two windows = 2 x world chunks); the
         helper's own per-frame host logic (resize rule, eye-distance filter, centre-face selection:
         face_restoration_helper.py:206-252) then runs unchanged on the stored detections of the chunk, on the SAME
         ``read_image`` result the detector input was built from, so the landmarks are what the per-frame loop produces."""
@@ -713,6 +715,11 @@ class KEEPFaceProcessor:
         chunk = max(1, int(getattr(getattr(det, 'engine', None), 'max_frames', 32))) if use_batch else 1
         bar = tqdm(total=len(frames_bgr), desc="Detecting face landmarks")
         starts = list(range(0, len(frames_bgr), chunk))
+        gpus = self._detection_pool(det, len(starts)) if use_batch else None
+        if gpus is not None:
+            self._detect_all_pooled(gpus, det, frames_bgr, only_center_face, chunk, starts, raw, bar)
+            bar.close()
+            return raw
         # Round 6: the detector's forward of chunk k (GPU, one worker thread: the launches and the D2H waits release the GIL) runs under the
         # HOST preparation of chunk k + 1 (read_image + the INTER_AREA resize of every frame: a third of the pre-pass) -- the same calls
         # on the same data in the same order per frame, only interleaved; KEEP_AMD_DETECT_OVERLAP=0: one after the other
@@ -736,27 +743,86 @@ class KEEPFaceProcessor:
                         prepared = self._prep_detect_chunk(frames_bgr[starts[k + 1]:starts[k + 1] + chunk], 640)
                     if fut is not None:
                         batched = fut.result()
-                for j, frame in enumerate(part):
-                    helper.clean_all()
-                    if states is not None:
-                        helper.input_img, helper.is_gray = states[j]       # what read_image(frame) left behind (:172-184)
-                    else:
-                        helper.read_image(frame)
-                    if batched is None:
-                        helper.get_face_landmarks_5(only_center_face=only_center_face, resize=640, eye_dist_threshold=5)
-                    else:
-                        helper.face_detector = _ReplayDetector(batched[j])
-                        try:
-                            helper.get_face_landmarks_5(only_center_face=only_center_face, resize=640, eye_dist_threshold=5)
-                        finally:
-                            helper.face_detector = det
-                    raw.append(list(helper.all_landmarks_5))
-                    bar.update(1)
+                self._replay_chunk(det, part, states, batched, only_center_face, raw, bar)
         finally:
             if pool is not None:
                 pool.shutdown(wait=True)
         bar.close()
         return raw
+
+    def _replay_chunk(self, det, part, states, batched, only_center_face, raw, bar):
+        """The helper's per-frame host logic over one chunk of frames, in frame order: on the stored ``read_image`` state and the stored
+        detections of the batched forward where there are any (``states`` / ``batched``), through the helper's own calls otherwise."""
+        helper = self.face_helper
+        for j, frame in enumerate(part):
+            helper.clean_all()
+            if states is not None:
+                helper.input_img, helper.is_gray = states[j]       # what read_image(frame) left behind (:172-184)
+            else:
+                helper.read_image(frame)
+            if batched is None:
+                helper.get_face_landmarks_5(only_center_face=only_center_face, resize=640, eye_dist_threshold=5)
+            else:
+                helper.face_detector = _ReplayDetector(batched[j])
+                try:
+                    helper.get_face_landmarks_5(only_center_face=only_center_face, resize=640, eye_dist_threshold=5)
+                finally:
+                    helper.face_detector = det
+            raw.append(list(helper.all_landmarks_5))
+            bar.update(1)
+
+    def _detection_pool(self, det, n_chunks):
+        """The net's worker pool when the detection pre-pass can be spread over it: a live pool (``KEEP_AMD_GPUS``), a detector whose engine
+        is of a kind the workers rebuild (``GpuPool.takes_detector``: RetinaFace; YOLOv5-face and dlib stay on the root) and more than one chunk.  KEEP_AMD_POOL_DETECT=0:
+        never."""
+        if n_chunks < 2 or os.environ.get('KEEP_AMD_POOL_DETECT', '1') == '0':
+            return None
+        gpus = getattr(self.keep_net, 'pool', None)
+        if gpus is None or not hasattr(gpus, 'takes_detector') or getattr(gpus, 'closed', False):
+            return None
+        return gpus if gpus.takes_detector(getattr(det, 'engine', None)) else None
+
+    def _detect_all_pooled(self, gpus, det, frames_bgr, only_center_face, chunk, starts, raw, bar):
+        """``_detect_all`` over the worker pool (engine/pool.py:GpuPool.detect): the chunks are dispatched in windows of ``world`` chunks,
+        chunk k of a window on rank k (the root's own on its GPU, under the workers' runs), and the host preparation of the next window
+        runs under the current window's detection (KEEP_AMD_DETECT_OVERLAP=0: one after the other), so the root holds at most TWO windows
+        of detector inputs.  A chunk without a batch (mixed sizes, non-uint8 frames) takes the per-frame path on the root.  The helper's
+        per-frame host logic then replays on the root, in frame order, exactly as without a pool."""
+        world = int(gpus.world)
+        gpus.set_detector(det.engine)
+        windows = [starts[i:i + world] for i in range(0, len(starts), world)]
+
+        def prep(win):
+            return [self._prep_detect_chunk(frames_bgr[s:s + chunk], 640) for s in win]
+
+        def forward(prepared):
+            live = [batch for _, batch in prepared if batch is not None]
+            flat = gpus.detect(live, 0.97) if live else []
+            out, off = [], 0
+            for _, batch in prepared:
+                out.append(None if batch is None else flat[off:off + len(batch)])
+                off += 0 if batch is None else len(batch)
+            return out
+        thread = None
+        if len(windows) > 1 and os.environ.get('KEEP_AMD_DETECT_OVERLAP', '1') != '0':
+            from concurrent.futures import ThreadPoolExecutor
+            thread = ThreadPoolExecutor(max_workers=1, thread_name_prefix='keep-detect')
+        try:
+            prepared = prep(windows[0])
+            for k, win in enumerate(windows):
+                current = prepared
+                fut = thread.submit(forward, current) if thread is not None else None
+                batched = forward(current) if fut is None else None
+                if k + 1 < len(windows):                                   # host work of the next window, under this window's detection
+                    prepared = prep(windows[k + 1])
+                if fut is not None:
+                    batched = fut.result()
+                for s, (states, _), res in zip(win, current, batched):
+                    self._replay_chunk(det, frames_bgr[s:s + chunk], states, res, only_center_face, raw, bar)
+                del current, batched
+        finally:
+            if thread is not None:
+                thread.shutdown(wait=True)
 
     def _prep_detect_chunk(self, frames_bgr, resize):
         """One chunk of frames, host side only: the helper state ``read_image`` leaves behind per frame (input image, grey flag) and the
