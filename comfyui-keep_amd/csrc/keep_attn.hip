@@ -55,6 +55,7 @@ enum AttnForm {
   ATTN_X3_NQ16,      // attn_x3_kernel<4, dvt, 16>: D <= 256
   ATTN_X3_NQ0,       // attn_x3_kernel<4, dvt, 0>: Q and K re-staged per 128-wide chunk
   ATTN_X3_PACKED,    // attn_pack_kv_x3_kernel into the scratch + attn_x3_kernel<4, dvt, D / 16, true>
+  ATTN_X1_PACKED,    // KEEP_MMA_X1 + KEEP_ATTN_X1: the single-fp16 instantiation of the same two kernels (<.., true> as their last argument)
   ATTN_X3_SMALL,     // attn_x3_small_kernel
   ATTN_X3_TWO_PASS,  // attn_scores_x3l_kernel into the scratch + attn_pv_x3l_kernel
   ATTN_X3_SFULL,     // attn_x3_sfull_kernel<dvt>
@@ -620,21 +621,26 @@ typedef _Float16 af16x2 __attribute__((ext_vector_type(2)));
 // [32 x (hi128|lo128|pad8) | 128 x (32 hi permuted | 32 lo | pad8)] -- 2208 16-byte pieces per key tile copied global -> register
 // -> LDS: 9 wide loads and 9 ds_write_b128 per thread and tile instead of 20 loads (16 of them 4-byte), 128 split
 // operations and 20 narrow LDS writes (the phase ablation: loads 55 %, commit 25 % of the unpacked kernel's time).
-template <int WAVES, int DVT, int NQ, bool PACKED = false>
+// X1 (KEEP_MMA_X1 with KEEP_ATTN_X1; PACKED, D = 128 only): the same kernel on the hi halves alone -- Q (in registers), the K and V^T images
+// and P are each rounded ONCE to fp16 and every product is one MFMA.  The rows lose their lo half: K pitch DC + 8 (17 16-byte slots) and
+// V^T pitch 40 (5 slots) are odd slot counts like 2 DC + 8 (33) and 72 (9), so the 16 rows one ds_read_b128 phase touches still fall on 16
+// different slots of the 64 banks.  1184 16-byte pieces per key tile instead of 2208; scores, softmax and accumulators unchanged.
+template <int WAVES, int DVT, int NQ, bool PACKED = false, bool X1 = false>
 __global__ __launch_bounds__(64 * WAVES, ((WAVES == 4 && NQ != 16) ? 2 : 1)) void attn_x3_kernel(AttnP p) {
+  static_assert(!X1 || (PACKED && WAVES == 4 && NQ == 8), "the single-fp16 form exists for the packed D = 128 kernel only");
   constexpr bool QREG = NQ > 0;             // NQ 16-wide d steps of Q live in registers (NQ = 16: D <= 256, one block per CU)
   constexpr int NQA = QREG ? NQ : 1;
   extern __shared__ __attribute__((aligned(16))) _Float16 smemx[];
   constexpr int DVS = DVT * 32;
   constexpr int NT = 64 * WAVES;
-  constexpr int VP = 72;
+  constexpr int VP = X1 ? 40 : 72;
   constexpr bool PF = (WAVES == 4) && QREG;
   constexpr int KPF = PF ? (32 * 4 * NQA + NT - 1) / NT : 1;   // float4 pieces of a 32 x (16*NQ) K tile per thread
   constexpr int VPF = PF ? (16 * DVS + NT - 1) / NT : 1;       // (key pair, dv) items of a 32 x DVS V tile per thread
   const int DCMAX = QREG ? 16 * NQA : 128;
   const int DC = p.D < DCMAX ? p.D : DCMAX;
   const int nch = p.D / DC;
-  const int QP = 2 * DC + 8;
+  const int QP = (X1 ? DC : 2 * DC) + 8;
   _Float16* Ks = smemx;                               // [32][QP]
   _Float16* Vt = Ks + 32 * QP;                        // [DVS][VP]
   _Float16* Qs = Vt + DVS * VP;                       // [WAVES*32][QP], chunked path only
@@ -829,8 +835,8 @@ __global__ __launch_bounds__(64 * WAVES, ((WAVES == 4 && NQ != 16) ? 2 : 1)) voi
 
   // packed tile of (batch, head, key tile): [K image 32 x (2 D + 8)] [V^T slice 0: DVS x 72] [slice 1] ...; a block copies the K
   // image and ITS dv slice -- contiguous in LDS (Ks, then Vt)
-  constexpr int PKK = PACKED ? 32 * (2 * 16 * NQA + 8) / 8 : 1;       // 16-byte pieces of the K image (D == 16 NQ)
-  constexpr int PKV = PACKED ? DVS * 72 / 8 : 1;                      // ... of one V^T slice
+  constexpr int PKK = PACKED ? 32 * ((X1 ? 1 : 2) * 16 * NQA + 8) / 8 : 1;   // 16-byte pieces of the K image (D == 16 NQ)
+  constexpr int PKV = PACKED ? DVS * VP / 8 : 1;                      // ... of one V^T slice
   constexpr int PK16 = PKK + PKV;
   constexpr int PKN = PACKED ? (PK16 + NT - 1) / NT : 1;
   uint4 preg[PKN];
@@ -920,9 +926,11 @@ __global__ __launch_bounds__(64 * WAVES, ((WAVES == 4 && NQ != 16) ? 2 : 1)) voi
       for (int d8 = 0; d8 < NQA; ++d8) {
         if (d8 * 16 < DC) {
           const af16x8 kh8 = *reinterpret_cast<const af16x8*>(kp + d8 * 16);
-          const af16x8 kl8 = *reinterpret_cast<const af16x8*>(kp + DC + d8 * 16);
-          s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl8, qfh[QREG ? d8 : 0], s, 0, 0, 0);
-          s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, qfl[QREG ? d8 : 0], s, 0, 0, 0);
+          if (!X1) {
+            const af16x8 kl8 = *reinterpret_cast<const af16x8*>(kp + DC + d8 * 16);
+            s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kl8, qfh[QREG ? d8 : 0], s, 0, 0, 0);
+            s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, qfl[QREG ? d8 : 0], s, 0, 0, 0);
+          }
           s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kh8, qfh[QREG ? d8 : 0], s, 0, 0, 0);
         }
       }
@@ -1014,9 +1022,12 @@ __global__ __launch_bounds__(64 * WAVES, ((WAVES == 4 && NQ != 16) ? 2 : 1)) voi
 #pragma unroll
       for (int j = 0; j < DVT; ++j) {
         const _Float16* vrow = Vt + (j * 32 + l31) * VP + (st * 2 + lhi) * 8;
-        const af16x8 vh8 = *reinterpret_cast<const af16x8*>(vrow), vl8 = *reinterpret_cast<const af16x8*>(vrow + 32);
-        o[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pl, vh8, o[j], 0, 0, 0);
-        o[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph, vl8, o[j], 0, 0, 0);
+        const af16x8 vh8 = *reinterpret_cast<const af16x8*>(vrow);
+        if (!X1) {
+          const af16x8 vl8 = *reinterpret_cast<const af16x8*>(vrow + 32);
+          o[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pl, vh8, o[j], 0, 0, 0);
+          o[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph, vl8, o[j], 0, 0, 0);
+        }
         o[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph, vh8, o[j], 0, 0, 0);
       }
     }
@@ -1055,9 +1066,10 @@ __global__ __launch_bounds__(64 * WAVES, ((WAVES == 4 && NQ != 16) ? 2 : 1)) voi
 // K / V^T tile images for the PACKED variant above: one block per (key tile, head, batch) gathers the tile's 32 key rows
 // (window / sparse-causal index math once per element instead of once per query block), applies the range scales, splits,
 // assembles the LDS image in LDS and writes it out with 16-byte stores.
-template <int DC, int DVS>
+// X1: the images of the single-fp16 kernel -- hi halves only, rows of DC + 8 (K) and 40 (V^T) halves.
+template <int DC, int DVS, bool X1 = false>
 __global__ __launch_bounds__(256) void attn_pack_kv_x3_kernel(AttnP p, _Float16* out) {
-  constexpr int QP = 2 * DC + 8, VP = 72, PKK = 32 * QP / 8, PKV = DVS * VP / 8;
+  constexpr int QP = (X1 ? DC : 2 * DC) + 8, VP = X1 ? 40 : 72, PKK = 32 * QP / 8, PKV = DVS * VP / 8;
   __shared__ __attribute__((aligned(16))) _Float16 img[32 * QP + DVS * VP];
   _Float16* Ks = img;
   _Float16* Vt = img + 32 * QP;
@@ -1086,7 +1098,7 @@ __global__ __launch_bounds__(256) void attn_pack_kv_x3_kernel(AttnP p, _Float16*
           lo[j] = (_Float16)(f[j] - (float)h);
         }
         *reinterpret_cast<af16x4*>(Ks + row * QP + c) = hi;
-        *reinterpret_cast<af16x4*>(Ks + row * QP + DC + c) = lo;
+        if (!X1) *reinterpret_cast<af16x4*>(Ks + row * QP + DC + c) = lo;
       }
     }
   }
@@ -1109,7 +1121,7 @@ __global__ __launch_bounds__(256) void attn_pack_kv_x3_kernel(AttnP p, _Float16*
     }
     _Float16* d = Vt + dv * VP + vt_pos(pair * 2);
     *reinterpret_cast<af16x2*>(d) = hi;
-    *reinterpret_cast<af16x2*>(d + 32) = lo;
+    if (!X1) *reinterpret_cast<af16x2*>(d + 32) = lo;
   }
   __syncthreads();
   uint4* dst = reinterpret_cast<uint4*>(out) + (((long)b * p.H + head) * gridDim.x + kt) * (PKK + p.nslices * PKV);
@@ -1118,16 +1130,16 @@ __global__ __launch_bounds__(256) void attn_pack_kv_x3_kernel(AttnP p, _Float16*
   for (int i = tid; i < PKV; i += 256) dst[PKK + slice * PKV + i] = reinterpret_cast<const uint4*>(img)[PKK + i];
 }
 
-template <int DVT, int NQ>
+template <int DVT, int NQ, bool X1 = false>
 static int launch_attn_x3_packed(const AttnP& p, const AttnPlan& pl, hipStream_t st) {
   const int ntl = (p.Lk + 31) / 32;
-  hipLaunchKernelGGL((attn_pack_kv_x3_kernel<16 * NQ, DVT * 32>), dim3(ntl, p.H * p.nslices, p.B), dim3(256), 0, st, p,
+  hipLaunchKernelGGL((attn_pack_kv_x3_kernel<16 * NQ, DVT * 32, X1>), dim3(ntl, p.H * p.nslices, p.B), dim3(256), 0, st, p,
                      const_cast<_Float16*>(p.kv_pack));
   KEEP_LAUNCH_CHECK("keep_attention(x3 pack)");
-  const int rc = keep_raise_lds_limit<attn_x3_kernel<4, DVT, NQ, true>>("keep_attention");
+  const int rc = keep_raise_lds_limit<attn_x3_kernel<4, DVT, NQ, true, X1>>("keep_attention");
   if (rc != KEEP_OK) return rc;
   dim3 grid(cdiv(p.Lq, 128), p.H * p.nslices, p.B);
-  hipLaunchKernelGGL((attn_x3_kernel<4, DVT, NQ, true>), grid, dim3(256), pl.lds, st, p);
+  hipLaunchKernelGGL((attn_x3_kernel<4, DVT, NQ, true, X1>), grid, dim3(256), pl.lds, st, p);
   KEEP_LAUNCH_CHECK("keep_attention(x3 packed)");
   return KEEP_OK;
 }
@@ -2277,8 +2289,9 @@ static int plan_attention(const keep_attention_args& a, int64_t scratch_avail, A
   KEEP_REQUIRE(a.B > 0 && a.H > 0 && a.Lq > 0 && a.Lk > 0 && a.D > 0 && a.Dv > 0, "keep_attention: bad dims");
   KEEP_REQUIRE(a.D % 2 == 0 && (a.D <= 128 || a.D % 128 == 0), "keep_attention: D=%d must be even and (<= 128 or a multiple of 128)", a.D);
   KEEP_REQUIRE(a.mode >= 0 && a.mode <= 2, "keep_attention: bad mode %d", a.mode);
-  KEEP_REQUIRE(a.mma != KEEP_MMA_X1, "keep_attention: KEEP_MMA_X1 has no attention kernel (a keep_conv2d policy of the parsing network)");
-  KEEP_REQUIRE(a.mma == KEEP_MMA_F32 || a.mma == KEEP_MMA_BF16 || a.mma == KEEP_MMA_X3, "keep_attention: bad mma %d", a.mma);
+  const bool x1 = a.mma == KEEP_MMA_X1 && (a.flags & KEEP_ATTN_X1);      // (the bit is read under KEEP_MMA_X1 only)
+  KEEP_REQUIRE(a.mma != KEEP_MMA_X1 || x1, "keep_attention: KEEP_MMA_X1 has no attention kernel without KEEP_ATTN_X1 (flags), which admits the packed D = Dv = 128 form only");
+  KEEP_REQUIRE(a.mma == KEEP_MMA_F32 || a.mma == KEEP_MMA_BF16 || a.mma == KEEP_MMA_X3 || x1, "keep_attention: bad mma %d", a.mma);
   if (a.mode == 1)
     KEEP_REQUIRE(a.T > 0 && a.seg_len > 0 && a.Lk == 2 * a.seg_len && a.B % a.T == 0,
                  "keep_attention: sparse-causal mode needs Lk == 2*seg_len and B %% T == 0");
@@ -2293,6 +2306,15 @@ static int plan_attention(const keep_attention_args& a, int64_t scratch_avail, A
     KEEP_REQUIRE(a.kv_rot >= 0 && a.kv_rot < a.n_img, "keep_attention: bad kv_rot");
     KEEP_REQUIRE((long)a.img_h * a.img_w <= 65536, "keep_attention: window mode supports maps of at most 65536 tokens");
   }
+  // KEEP_MMA_X1 | KEEP_ATTN_X1 admits ONE form; whatever else it is asked for is refused (KEEP_EUNSUP), never run on another policy
+#define ATTN_X1_ADMITS(cond, ...)    \
+  do {                               \
+    if (!(cond)) {                   \
+      keep_set_error(__VA_ARGS__);   \
+      return KEEP_EUNSUP;            \
+    }                                \
+  } while (0)
+  if (x1) ATTN_X1_ADMITS(!a.q_amax && !a.k_amax && !a.v_amax, "keep_attention: KEEP_MMA_X1 takes no q/k/v_amax range probes (normalised operands only)");
   KEEP_REQUIRE((!a.q_amax && !a.k_amax && !a.v_amax) || (a.q_amax && a.k_amax && a.v_amax && a.mode == 0 && a.mma == KEEP_MMA_X3),
                "keep_attention: q/k/v_amax come together, with KEEP_MMA_X3 and mode 0 only");
   p.flags = a.flags;
@@ -2322,6 +2344,25 @@ static int plan_attention(const keep_attention_args& a, int64_t scratch_avail, A
   const size_t ntl = (size_t)(a.Lk + 31) / 32;                // key tiles
   const size_t win_tables = ntl * 32 * 4 + ntl * 16 + ntl * 32;    // window tables: pixel per key, packed + byte region ids
 
+  if (x1) {
+    // the packed form of KEEP_MMA_X3 on hi halves alone: attn_pack_kv_x3_kernel<128, 128, true> + attn_x3_kernel<4, 4, 8, true, true>
+    ATTN_X1_ADMITS(a.in_dtype == KEEP_F32, "keep_attention: KEEP_MMA_X1 needs fp32 q / k / v (in_dtype KEEP_F32)");
+    ATTN_X1_ADMITS(a.mode == 0 || a.mode == 2, "keep_attention: KEEP_MMA_X1 covers mode 0 and mode 2, not mode %d", a.mode);
+    ATTN_X1_ADMITS(a.D == 128 && a.Dv == 128, "keep_attention: KEEP_MMA_X1 covers D = Dv = 128 only (D=%d Dv=%d)", a.D, a.Dv);
+    ATTN_X1_ADMITS(a.Lq >= 256, "keep_attention: KEEP_MMA_X1 covers Lq >= 256 only (Lq=%d): the packed form", a.Lq);
+    ATTN_X1_ADMITS(rows16(a.q, a.q_bs, a.q_ts, a.q_hs, 4) && rows16(a.k, a.k_bs, a.k_ts, a.k_hs, 4) && rows16(a.v, a.v_bs, a.v_ts, a.v_hs, 4),
+                   "keep_attention: KEEP_MMA_X1 needs 16-byte aligned q / k / v rows");
+    ATTN_X1_ADMITS(!(a.flags & KEEP_ATTN_NO_PACK), "keep_attention: KEEP_MMA_X1 has the packed form only (KEEP_ATTN_NO_PACK is set)");
+    const int64_t need = (int64_t)a.B * a.H * (int64_t)ntl * ((32 * (a.D + 8) + p.nslices * dvt * 32 * 40) * 2L);
+    ATTN_X1_ADMITS(scratch_avail >= need, "keep_attention: KEEP_MMA_X1 needs a 16-byte aligned workspace of %lld bytes (keep_attention_workspace_bytes), got %lld",
+                   (long long)need, (long long)scratch_avail);
+    pl.form = ATTN_X1_PACKED;
+    pl.waves = 4;
+    pl.lds = (size_t)(32 * (a.D + 8) + dvt * 32 * 40) * 2 + (a.mode == 2 && a.Lk <= 4096 ? win_tables : 0);
+    pl.scratch = need;
+    return KEEP_OK;
+  }
+#undef ATTN_X1_ADMITS
   if (a.in_dtype == KEEP_BF16) {
     const bool ok = a.mma == KEEP_MMA_BF16 && a.D % 16 == 0 && a.Dv % 8 == 0 && rows16(a.q, a.q_bs, a.q_ts, a.q_hs, 8) &&
                     rows16(a.k, a.k_bs, a.k_ts, a.k_hs, 8) && rows16(a.v, a.v_bs, a.v_ts, a.v_hs, 8);
@@ -2417,7 +2458,9 @@ extern "C" int64_t keep_attention_workspace_bytes(const keep_attention_args* a_i
   keep_attention_args a;
   AttnP p;
   AttnPlan pl;
-  if (attn_args_in(a_in, a) != KEEP_OK || plan_attention(a, INT64_MAX, p, pl) != KEEP_OK) return 0;
+  if (attn_args_in(a_in, a) != KEEP_OK) return 0;
+  const int rc = plan_attention(a, INT64_MAX, p, pl);
+  if (rc != KEEP_OK) return (rc == KEEP_EUNSUP && a.mma == KEEP_MMA_X1) ? -1 : 0;      // -1: the refusal of KEEP_MMA_X1 | KEEP_ATTN_X1
   return pl.scratch;
 }
 
@@ -2457,6 +2500,9 @@ extern "C" int32_t keep_attention(const keep_attention_args* a_in, void* stream)
       return with_dvt(pl.dvt, [&](auto dvt) {
         return p.D == 128 ? launch_attn_x3_packed<decltype(dvt)::value, 8>(p, pl, st) : launch_attn_x3_packed<decltype(dvt)::value, 16>(p, pl, st);
       });
+    case ATTN_X1_PACKED:
+      p.kv_pack = (const _Float16*)a.workspace;
+      return launch_attn_x3_packed<4, 8, true>(p, pl, st);
     case ATTN_X3_SMALL:
       return launch_attn_x3_small(p, st);
     case ATTN_X3_TWO_PASS:

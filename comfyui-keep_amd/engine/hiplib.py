@@ -26,6 +26,7 @@ UPSAMPLE_X2_PHASES = 2
 CONV_X1_HALO16 = 1 << 15    # opt-in: MMA_X1 also takes 3x3 stride-1 convolutions on 16 x 16-tile maps that are not 8 x 32 tileable (KEEP_CONV_X1_HALO16)
 CONV_X1_GEMM = 1 << 14      # opt-in: MMA_X1 also takes the 1x1 stride-1 GEMM form (KEEP_CONV_X1_GEMM); ignored by every other policy
 ATTN_NO_PACK, ATTN_NO_SFULL2, ATTN_NO_X3, ATTN_NO_SMALL, ATTN_NO_TWO_PASS = 1, 2, 4, 8, 16
+ATTN_X1 = 1 << 5            # opt-in: MMA_X1 takes the packed D = Dv = 128 attention form on single fp16 operands (KEEP_ATTN_X1); ignored by every other policy
 
 _vp, _i32, _i64, _f32, _u32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_uint32
 STATUS_NONFINITE_LOGITS, STATUS_NONFINITE_TENSOR = 1, 2
@@ -206,8 +207,27 @@ def conv2d_plan(a):
 
 
 def attention_workspace_bytes(a):
-    """keep_attention_workspace_bytes: scratch the library can use for this call (0 = none)."""
+    """keep_attention_workspace_bytes: scratch the library can use for this call (0 = none; -1 = MMA_X1 | ATTN_X1 refuses the call)."""
     return int(load(check_device=False).keep_attention_workspace_bytes(C.byref(a)))
+
+
+def attn_args(**kw):
+    a = AttnArgs()
+    a.struct_size = C.sizeof(AttnArgs)
+    for k, v in kw.items():
+        setattr(a, k, _ptr(v) if (isinstance(v, torch.Tensor) or v is None) else v)
+    return a
+
+
+def attention_x1_plan(**kw):
+    """The library's answer to `this call under MMA_X1 | ATTN_X1`: the scratch bytes the single-fp16 form needs.  A refusal
+    (keep_attention_workspace_bytes = -1, what keep_attention answers KEEP_EUNSUP to) raises KeepHipError with `(code -2)` and the
+    library's reason, like keep_conv2d_plan does; needs no device."""
+    a = attn_args(**dict(kw, mma=MMA_X1, flags=int(kw.get('flags', 0)) | ATTN_X1))
+    need = attention_workspace_bytes(a)
+    if need < 0:
+        raise KeepHipError(f"keep_attention plan failed (code -2): {_lib.keep_last_error().decode()}")
+    return need
 
 
 def conv2d_launch(a):
@@ -220,12 +240,9 @@ def conv2d(**kw):
 
 def attention(**kw):
     lib = load()
-    a = AttnArgs()
-    a.struct_size = C.sizeof(AttnArgs)
-    for k, v in kw.items():
-        setattr(a, k, _ptr(v) if (isinstance(v, torch.Tensor) or v is None) else v)
+    a = attn_args(**kw)
     need = int(lib.keep_attention_workspace_bytes(C.byref(a)))       # the library asks; the host only allocates
-    if need:
+    if need > 0:                                                     # (-1: a refused MMA_X1 call -- keep_attention below says why)
         ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=kw['q'].device)   # stream-ordered free after the call
         a.workspace, a.workspace_bytes = ws.data_ptr(), need
     _check(lib.keep_attention(C.byref(a), _stream()), 'keep_attention')

@@ -54,6 +54,10 @@ RESIDENT = os.environ.get('KEEP_AMD_RESIDENT', '0') == '1'      # keep the packe
 PRECISIONS = ('fp32', 'x3', 'bf16', 'f16')
 DEFAULT_PRECISION = 'x3'
 X3_GRADE = ('x3', 'f16')      # policies whose operands are fp16 halves: the range check and its exact-f32 re-run apply
+# KEEP_AMD_FLOW_PRECISION: GMFlow's own knob, independent of KEEP_AMD_PRECISION.  'x3' (default): GMFlow runs on the net's policy.  'f16': its
+# CNN backbone, swin blocks and q / k projections take single-fp16 operands where the library admits them; needs an x3-grade base
+FLOW_PRECISIONS = ('x3', 'f16')
+FLOW_PRECISION_ENV = 'KEEP_AMD_FLOW_PRECISION'
 
 
 ROCTX = os.environ.get('KEEP_AMD_ROCTX', '0') == '1'      # per-stage roctx ranges (rocprofv3 --marker-trace / --kernel-trace timelines)
@@ -115,7 +119,13 @@ class KeepNet:
         self._x3_scales = None     # per-tensor accumulator scales of the x3 twin (ops.make_x3_blob)
         self._dev_blobx1 = None    # 'f16': hi-only fp16 twin (1 x int16 per weight) of the 3x3 convolution weights outside GMFlow
         self._x1_ranges = None
+        self._dev_blobx1f = None   # flow 'f16': hi-only twin of the flownet weights (3x3, 1x1, linear; Cin % 32 == 0)
+        self._x1f_ranges = None
         self.o = ops.Ops()         # this net's precision policy + weight twins (never shared between nets)
+        # the Ops of the `flownet.*` layers that may run single-fp16: self.o itself while the flow knob is off (no second object, no other
+        # plan query, the same launches); with flow 'f16' a second Ops on x3 that carries the flownet x1 twin (_activate_precision)
+        self.of = self.o
+        self._of = None
         self.x3_fallbacks = 0      # batches the x3 policy handed back to the f32 kernels (non-finite output)
         # hipGraph replay of the whole forward for small batches (launch-bound: ~9 k kernels per clip): 'auto' = at most
         # GRAPH_MAX_CLIPS clips per call, '1' = always, '0' = never.  One captured graph per (B, T, H, W, policy).
@@ -133,6 +143,8 @@ class KeepNet:
                                       # received an older blob is stale and is closed (engine/pool.py)
         self.precision = 'fp32'
         self.set_precision(os.environ.get('KEEP_AMD_PRECISION', DEFAULT_PRECISION))
+        self.flow_precision = 'x3'
+        self.set_flow_precision(os.environ.get(FLOW_PRECISION_ENV) or 'x3')
 
     # ------------------------------------------------------------------ nn.Module-like surface
     def load_state_dict(self, state_dict, strict=True):
@@ -182,6 +194,33 @@ class KeepNet:
         self.precision = precision
         return self
 
+    def set_flow_precision(self, precision):
+        """GMFlow's knob (``KEEP_AMD_FLOW_PRECISION``).  'x3' (default): GMFlow runs on the net's policy, as if the knob did not exist.
+        'f16': on an 'x3' or 'f16' base (anything else raises when the policy is activated), the CNN backbone, the six swin blocks and the
+        flow-propagation q / k projections go through a second ``Ops`` that substitutes single-fp16 operands wherever the library's plan
+        admits them: un-split 3x3 / im2col / 1x1 GEMM convolutions with Cin % 32 == 0 and the 128-wide window attention.  The global
+        correlation and flow-propagation attentions (probabilities times pixel coordinates), the convex upsampler, the fused FFN
+        (``keep_gm_ffn_x3`` has no single-fp16 form), the LayerNorm-epilogue GEMMs, the 16-channel stem and split plans stay x3.  An
+        opt-in speed mode outside the 1e-3 parity tolerance, never a default."""
+        if precision not in FLOW_PRECISIONS:
+            raise ValueError(f"{FLOW_PRECISION_ENV} (set_flow_precision) must be one of {FLOW_PRECISIONS}, got {precision!r}")
+        self.flow_precision = precision
+        return self
+
+    @staticmethod
+    def flow_x1_names(index):
+        """Names of the flow twin's tensors: `flownet.*` matrix weights with Cin % 32 == 0 -- packed 3x3 [Cout,3,3,Cin], and 1x1 / linear
+        [Cout,Cin] -- disjoint from ``_make_x1``'s list by construction (that one excludes `flownet.`).  The two stride-2 1x1 shortcut
+        convolutions of the backbone (`downsample.0`) have no twin and stay x3: their launch shapes measured 0.99 x and 1.01 x under
+        single fp16 (bound by the strided gather, not by the products), and a shape that is not faster is not routed."""
+        return [n for n, (_, shape) in index.items() if n.startswith('flownet.') and shape[-1] % 32 == 0 and '.downsample.' not in n
+                and ((len(shape) == 4 and shape[1] == 3 and shape[2] == 3) or len(shape) == 2)]
+
+    def _make_x1_flow(self):
+        self._dev_blobx1f, self._x1f_ranges = ops.make_x1_blob(self._dev_blob, self._index, self.w, self.flow_x1_names(self._index))
+        x3 = {(a, b): s for a, b, s in self._x3_scales}
+        assert all(x3.get((a, b)) == s for a, b, s in self._x1f_ranges), 'x1 and x3 twins must share their per-tensor scales'
+
     def _make_x3(self):
         """Split-fp16 twin of every matrix weight in the blob (2-D+ tensors whose reduction axis is a multiple of 16)."""
         # only tensors a keep_conv2d call consumes as its x3 operand: the position table and the codebook are read by
@@ -192,12 +231,16 @@ class KeepNet:
         # cost every other layer its `lo` bits (tests/test_gpu_net.py::test_x3_scale_is_per_tensor)
         self._dev_blobx3, self._x3_scales = ops.make_x3_blob(self._dev_blob, self._index, self.w, names)
 
+    @staticmethod
+    def x1_names(index):
+        """Names of the 'f16' twin's tensors (``_make_x1``)."""
+        return [n for n, (_, shape) in index.items() if len(shape) == 4 and shape[1] == 3 and shape[2] == 3 and shape[-1] % 32 == 0
+                and not n.startswith('flownet.')]
+
     def _make_x1(self):
         """'f16': hi-only twin of every 3x3 convolution weight a streaming kernel could read (packed [Cout,3,3,Cin], Cin % 32 == 0),
-        GMFlow excluded (its flows feed a warp: it stays x3).  Same per-tensor scales as the x3 twin (one scale table serves both)."""
-        names = [n for n, (_, shape) in self._index.items() if len(shape) == 4 and shape[1] == 3 and shape[2] == 3 and shape[-1] % 32 == 0
-                 and not n.startswith('flownet.')]
-        self._dev_blobx1, self._x1_ranges = ops.make_x1_blob(self._dev_blob, self._index, self.w, names)
+        GMFlow excluded (its flows feed a warp: it stays x3 unless KEEP_AMD_FLOW_PRECISION=f16 opts its feature layers in, ``set_flow_precision``).  Same per-tensor scales as the x3 twin (one scale table serves both)."""
+        self._dev_blobx1, self._x1_ranges = ops.make_x1_blob(self._dev_blob, self._index, self.w, self.x1_names(self._index))
         x3 = {(a, b): s for a, b, s in self._x3_scales}
         assert all(x3.get((a, b)) == s for a, b, s in self._x1_ranges), 'x1 and x3 twins must share their per-tensor scales'
 
@@ -206,9 +249,32 @@ class KeepNet:
         ``clips_per_call`` takes off the free memory while they are not built yet."""
         precision = self.precision if precision is None else precision
         n = int(self._dev_blob.numel()) if self._dev_blob is not None else (0 if self._blob is None else int(self._blob.size))
-        return {'bf16': 2 * n, 'x3': 4 * n, 'f16': 4 * n + 2 * n}.get(precision, 0)
+        flow = 2 * n if (self.flow_precision == 'f16' and precision in X3_GRADE) else 0      # the flow twin: 2 bytes per blob element
+        return {'bf16': 2 * n, 'x3': 4 * n, 'f16': 4 * n + 2 * n}.get(precision, 0) + flow
+
+    def _activate_flow_precision(self):
+        """``self.of``: self.o, or (flow 'f16') the second Ops on x3 with the flownet x1 twin -- built here, never inside a stream capture."""
+        if self.flow_precision != 'f16':
+            self.of = self.o
+            return
+        if self.precision not in X3_GRADE:
+            raise ValueError(f"{FLOW_PRECISION_ENV}=f16 needs the base precision 'x3' or 'f16', not {self.precision!r}")
+        if self._dev_blobx1f is None:
+            self._make_x1_flow()
+        of = self._of = self._of or ops.Ops()
+        if not (of.mma == L.MMA_X3 and of.blob32 is self._dev_blob and of.blobx3 is self._dev_blobx3 and of.blobx1 is self._dev_blobx1f):
+            of.set_precision(L.MMA_X3, self._dev_blob, None, self._dev_blobx3, 1.0, x3_scales=self._x3_scales)
+            of.set_x1_twin(self._dev_blobx1f, self._x1f_ranges, flags=L.CONV_X1_GEMM, base_kernel=None)
+        of.attn_x1 = True
+        # per-net settings and instruments live on self.o (tests, bench.py, the pool): the flow Ops follows them
+        of.flags, of.attn_flags, of.plan_ref_images, of.profile, of.census = self.o.flags, self.o.attn_flags, self.o.plan_ref_images, self.o.profile, self.o.census
+        self.of = of
 
     def _activate_precision(self):
+        self._activate_base_precision()
+        self._activate_flow_precision()
+
+    def _activate_base_precision(self):
         if self.precision == 'bf16':
             if self._dev_blob16 is None:
                 self._dev_blob16 = self._dev_blob.to(torch.bfloat16)
@@ -239,7 +305,7 @@ class KeepNet:
                 self._pinned = torch.from_numpy(self._blob).pin_memory()
             from_blob = self._pinned
         self._dev_blob = from_blob.to(self.device, non_blocking=False)
-        self._dev_blob16 = self._dev_blobx3 = self._dev_blobx1 = None
+        self._dev_blob16 = self._dev_blobx3 = self._dev_blobx1 = self._dev_blobx1f = None
         self._graphs = {}
         self.w = views(self._dev_blob, self._index)
 
@@ -265,8 +331,9 @@ class KeepNet:
             # stale one; load_state_dict / adopt_packed close it) -- KEEPModelPack.offload() runs after every node call, and closing the
             # pool here cost every call a respawn of the workers (torch import, HIP init), a 633 MB broadcast and the x3 twins
             self._dev_blob, self._dev_blob16, self._dev_blobx3, self.w = None, None, None, None
-            self._dev_blobx1 = None
+            self._dev_blobx1 = self._dev_blobx1f = None
             self.o.set_precision(self.o.mma)        # drop this net's references to the device blobs
+            self.of, self._of = self.o, None
             self._const = {}
             self._graphs = {}
         return self
@@ -298,11 +365,12 @@ class KeepNet:
         policy, the plans' reference batch, the kernel-selection overrides and the hipGraph mode.  ``GpuPool.run`` compares it with
         what the workers were last told and re-configures them when it moved (``set_precision`` after the pool came up)."""
         return {'precision': self.precision, 'plan_ref_images': int(self.o.plan_ref_images), 'flags': int(self.o.flags),
-                'attn_flags': int(self.o.attn_flags), 'graph_mode': str(self.graph_mode)}
+                'attn_flags': int(self.o.attn_flags), 'graph_mode': str(self.graph_mode), 'flow_precision': self.flow_precision}
 
     def apply_pool_config(self, cfg):
         """Worker side of ``pool_config``."""
         self.set_precision(cfg['precision'])
+        self.set_flow_precision(cfg.get('flow_precision', 'x3'))
         self.o.plan_ref_images, self.o.flags, self.o.attn_flags = int(cfg['plan_ref_images']), int(cfg['flags']), int(cfg['attn_flags'])
         self.graph_mode = str(cfg['graph_mode'])
 
@@ -313,7 +381,7 @@ class KeepNet:
     def adopt_packed(self, index, dev_blob):
         """Install a packed blob received from another rank."""
         self._index, self._dev_blob, self._dev_blob16, self._dev_blobx3 = index, dev_blob, None, None
-        self._dev_blobx1 = None
+        self._dev_blobx1 = self._dev_blobx1f = None
         self._graphs = {}
         self.weights_generation += 1
         self.close_pool()
@@ -582,13 +650,13 @@ class KeepNet:
     def _gm_resblock(self, x, p, stride):
         """GM/backbone.py:25-36."""
         w = self.w
-        c1, st1 = self.o.conv(x, w[f'{p}.conv1.weight'], None, stride=stride, pad=1, stats=True, bounded=True)
-        c2, st2 = self.o.conv(c1, w[f'{p}.conv2.weight'], None, pro=self._inorm(c1, st1), pro_act=L.PRO_RELU, stats=True)
+        c1, st1 = self.of.conv(x, w[f'{p}.conv1.weight'], None, stride=stride, pad=1, stats=True, bounded=True)
+        c2, st2 = self.of.conv(c1, w[f'{p}.conv2.weight'], None, pro=self._inorm(c1, st1), pro_act=L.PRO_RELU, stats=True)
         s2, h2 = self._inorm(c2, st2)
         N, H, Wd, C = c2.shape
         out = torch.empty_like(c2)
         if f'{p}.downsample.0.weight' in w:
-            d, std = self.o.conv(x, w[f'{p}.downsample.0.weight'].view(C, 1, 1, -1), w[f'{p}.downsample.0.bias'],
+            d, std = self.of.conv(x, w[f'{p}.downsample.0.weight'].view(C, 1, 1, -1), w[f'{p}.downsample.0.bias'],
                                  stride=stride, pad=0, ksize=1, stats=True, bounded=True)
             sd, hd = self._inorm(d, std)
             L.call('keep_gm_join', d, sd, hd, c2, s2, h2, out, N, H * Wd, C)
@@ -605,28 +673,28 @@ class KeepNet:
         wqkv = w[f'{p}.qkv.weight']
         o = torch.empty_like(src)
         if tgt is src:
-            qkv = self.o.linear(src, wqkv, out_bf16=True, bounded=True, n_img=n_img)
+            qkv = self.of.linear(src, wqkv, out_bf16=True, bounded=True, n_img=n_img)
             q, k, v = qkv, ops.offset(qkv, C), ops.offset(qkv, 2 * C)
             sq = skv = (Ltok * 3 * C, 3 * C, 0)
         else:
-            q = self.o.linear(src, wqkv[:C], out_bf16=True, bounded=True, n_img=n_img)
-            kv = self.o.linear(tgt, wqkv[C:], out_bf16=True, bounded=True, n_img=n_img)
+            q = self.of.linear(src, wqkv[:C], out_bf16=True, bounded=True, n_img=n_img)
+            kv = self.of.linear(tgt, wqkv[C:], out_bf16=True, bounded=True, n_img=n_img)
             k, v = kv, ops.offset(kv, C)
             sq, skv = (Ltok * C, C, 0), (Ltok * 2 * C, 2 * C, 0)
-        self.o.attention(q, k, v, o, B=n_img * 4, H=1, Lq=Ltok // 4, Lk=Ltok // 4, D=C, Dv=C, scale=1.0 / (C ** 0.5),
+        self.of.attention(q, k, v, o, B=n_img * 4, H=1, Lq=Ltok // 4, Lk=Ltok // 4, D=C, Dv=C, scale=1.0 / (C ** 0.5),
                       q_str=sq, k_str=skv, v_str=skv, o_str=(Ltok * C, C, 0), mode=2, img_h=h8, img_w=w8, ksplit=2,
                       shift=shift, kv_rot=kv_rot, n_img=n_img)
         n1 = (w[f'{p}.norm1.weight'], w[f'{p}.norm1.bias'], 1e-5)
-        fuse = self.o.ln_fusable(w[f'{p}.merge.weight'], Ltok)      # LayerNorm in the GEMM's epilogue (keep_conv2d ln_gamma, ABI v16)
+        fuse = self.of.ln_fusable(w[f'{p}.merge.weight'], Ltok)      # LayerNorm in the GEMM's epilogue (keep_conv2d ln_gamma, ABI v16)
         if not ffn:
             if fuse:
-                return self.o.linear(o, w[f'{p}.merge.weight'], bounded=True, n_img=n_img, ln=n1, residual=src)
-            m = self.o.linear(o, w[f'{p}.merge.weight'], bounded=True, n_img=n_img)
+                return self.of.linear(o, w[f'{p}.merge.weight'], bounded=True, n_img=n_img, ln=n1, residual=src)
+            m = self.of.linear(o, w[f'{p}.merge.weight'], bounded=True, n_img=n_img)
             return ops.layernorm(m, n1[0], n1[1], res=src)
         if fuse:
-            m = self.o.linear(o, w[f'{p}.merge.weight'], bounded=True, n_img=n_img, ln=n1)
+            m = self.of.linear(o, w[f'{p}.merge.weight'], bounded=True, n_img=n_img, ln=n1)
         else:
-            m = ops.layernorm(self.o.linear(o, w[f'{p}.merge.weight'], bounded=True, n_img=n_img), n1[0], n1[1])
+            m = ops.layernorm(self.of.linear(o, w[f'{p}.merge.weight'], bounded=True, n_img=n_img), n1[0], n1[1])
         if (self.o.mma == L.MMA_X3 and C == 128 and FUSED_GM_FFN_X3 and self.o.x3_twin(w[f'{p}.mlp.0.weight']) is not None):
             # mlp.0 -> GELU -> mlp.2 -> norm2 -> + src as ONE launch: the [M, 8C] intermediate (10 GB at 16 clips) stays in registers
             return self.o.gm_ffn_x3(src, m, w[f'{p}.mlp.0.weight'], w[f'{p}.mlp.2.weight'], w[f'{p}.norm2.weight'], w[f'{p}.norm2.bias'], 1e-5)
@@ -634,13 +702,13 @@ class KeepNet:
             m2 = self.o.gm_mlp(src, m, w[f'{p}.mlp.0.weight'], w[f'{p}.mlp.2.weight'])      # [M,8C] never leaves the CU
         else:
             if self.o.mma == L.MMA_X3:      # cat[src | m] folded into the GEMM: two K-concatenated inputs (keep_conv2d in2)
-                hmid = self.o.linear(src, w[f'{p}.mlp.0.weight'], act=L.ACT_GELU, bounded=True, x2=m, n_img=n_img)
+                hmid = self.of.linear(src, w[f'{p}.mlp.0.weight'], act=L.ACT_GELU, bounded=True, x2=m, n_img=n_img)
             else:
-                hmid = self.o.linear(ops.concat2(src, m), w[f'{p}.mlp.0.weight'], act=L.ACT_GELU, bounded=True, n_img=n_img)
-            if self.o.ln_fusable(w[f'{p}.mlp.2.weight'], Ltok):
-                return self.o.linear(hmid, w[f'{p}.mlp.2.weight'], bounded=True, n_img=n_img, residual=src,
+                hmid = self.of.linear(ops.concat2(src, m), w[f'{p}.mlp.0.weight'], act=L.ACT_GELU, bounded=True, n_img=n_img)
+            if self.of.ln_fusable(w[f'{p}.mlp.2.weight'], Ltok):
+                return self.of.linear(hmid, w[f'{p}.mlp.2.weight'], bounded=True, n_img=n_img, residual=src,
                                      ln=(w[f'{p}.norm2.weight'], w[f'{p}.norm2.bias'], 1e-5))
-            m2 = self.o.linear(hmid, w[f'{p}.mlp.2.weight'], bounded=True, n_img=n_img)
+            m2 = self.of.linear(hmid, w[f'{p}.mlp.2.weight'], bounded=True, n_img=n_img)
         return ops.layernorm(m2, w[f'{p}.norm2.weight'], w[f'{p}.norm2.bias'], res=src)
 
     def _gm_backbone(self, img_nchw):
@@ -653,17 +721,17 @@ class KeepNet:
             # the 7x7 stride-2 convolution as a 4x4 stride-1 convolution on the 2x2 space-to-depth image (16-channel rows: the MFMA
             # kernels take it; the 147-deep element-wise gather of the 3-channel form ran at 0.5 TB/s)
             img = ops.rgb_s2d(img_nchw.contiguous())                                       # [N,H/2,W/2,16] normalised
-            f, fst = self.o.conv(img, ws2d, None, stride=1, pad=2, ksize=4, stats=True, bounded=True, out_hw=img.shape[1:3])
+            f, fst = self.of.conv(img, ws2d, None, stride=1, pad=2, ksize=4, stats=True, bounded=True, out_hw=img.shape[1:3])
         else:
             img = ops.nchw_to_nhwc(img_nchw, mode=1)                                       # [N,H,W,3] normalised
-            f, fst = self.o.conv(img, w[f'{pfx}.backbone.conv1.weight'], None, stride=2, pad=3, ksize=7, stats=True)
+            f, fst = self.of.conv(img, w[f'{pfx}.backbone.conv1.weight'], None, stride=2, pad=3, ksize=7, stats=True)
         s, hh = self._inorm(f, fst)
         x = torch.empty_like(f)
         L.call('keep_affine_act', f, s, hh, x, f.shape[0], f.shape[1] * f.shape[2], f.shape[3], L.ACT_RELU)
         for li, stride in ((1, 1), (2, 2), (3, 2)):
             x = self._gm_resblock(x, f'{pfx}.backbone.layer{li}.0', stride)
             x = self._gm_resblock(x, f'{pfx}.backbone.layer{li}.1', 1)
-        return self.o.linear(x, w[f'{pfx}.backbone.conv2.weight'], w[f'{pfx}.backbone.conv2.bias'], bounded=True)
+        return self.of.linear(x, w[f'{pfx}.backbone.conv2.weight'], w[f'{pfx}.backbone.conv2.bias'], bounded=True)
 
     def _gmflow(self, im1, im2):
         """im1, im2 [P,3,H,W] NCHW in [-1,1] -> backward flow [P,H,W,2] (channels-last: (dx, dy))."""
@@ -718,15 +786,17 @@ class KeepNet:
         f0 = c0[:P * Ltok]
         f1 = c0[P * Ltok:]
         sF = (Ltok * C, C, 0)
-        # global correlation soft-argmax (GM/matching.py:15-34): V = pixel grid, shared by all pairs
+        # global correlation soft-argmax (GM/matching.py:15-34): V = pixel grid, shared by all pairs.  This attention, the flow propagation
+        # below (probabilities times coordinates up to w8 - 1, the grid subtracted afterwards) and the convex upsampler run on self.o: x3
+        # whatever the flow knob says
         corr = ops.empty((P * Ltok, 2), f0)
         self.o.attention(f0, f1, grid, corr, B=P, H=1, Lq=Ltok, Lk=Ltok, D=C, Dv=2, scale=1.0 / (C ** 0.5),
                       q_str=sF, k_str=sF, v_str=(0, 2, 0), o_str=(Ltok * 2, 2, 0))
         flow = ops.add_bcast(corr, grid, alpha=-1.0)
         # flow propagation (GM/transformer.py:363-372): k projected from the projected q
         fp = f'{pfx}.feature_flow_attn'
-        q = self.o.linear(f0, w[f'{fp}.q_proj.weight'], w[f'{fp}.q_proj.bias'], bounded=True, n_img=P)
-        k = self.o.linear(q, w[f'{fp}.k_proj.weight'], w[f'{fp}.k_proj.bias'], bounded=True, n_img=P)
+        q = self.of.linear(f0, w[f'{fp}.q_proj.weight'], w[f'{fp}.q_proj.bias'], bounded=True, n_img=P)
+        k = self.of.linear(q, w[f'{fp}.k_proj.weight'], w[f'{fp}.k_proj.bias'], bounded=True, n_img=P)
         flow2 = ops.empty((P * Ltok, 2), f0)
         self.o.attention(q, k, flow, flow2, B=P, H=1, Lq=Ltok, Lk=Ltok, D=C, Dv=2, scale=1.0 / (C ** 0.5),
                       q_str=sF, k_str=sF, v_str=(Ltok * 2, 2, 0), o_str=(Ltok * 2, 2, 0))
@@ -796,8 +866,8 @@ class KeepNet:
         logging.getLogger('ComfyUI-KEEP').warning(
             "x3 precision policy left the fp16 operand range on this batch (status %d); re-running it on the f32 kernels", bits)
         self.x3_fallbacks += 1
-        policy = self.precision                      # 'x3' or 'f16': restored after the re-run
-        self.precision = 'fp32'
+        policy, flow_policy = self.precision, self.flow_precision      # 'x3' or 'f16' (and the flow knob): restored after the re-run
+        self.precision, self.flow_precision = 'fp32', 'x3'
         try:
             self._activate_precision()
             res = None                               # (callers drop their reference to the x3 result before calling: the re-run needs the room)
@@ -810,7 +880,7 @@ class KeepNet:
                                       for b0 in range(0, B, part)], 0)
             return self._forward(x, B, T, H, Wd, force_indices, return_aux, force_flows)
         finally:
-            self.precision = policy
+            self.precision, self.flow_precision = policy, flow_policy
             self._activate_precision()
 
     def _forward_graphed(self, x, B, T, H, Wd):
@@ -821,6 +891,9 @@ class KeepNet:
         self.o.ensure_arena(self.device)
         key = (B, T, H, Wd, self.precision, self._dev_blob.data_ptr(), self.o.arena_generation, self.o.flags, self.o.attn_flags,
                self.o.plan_ref_images)
+        if self.of is not self.o:
+            self.of.ensure_arena(self.device)
+            key += (self.flow_precision, self.of.arena_generation)
         ent = self._graphs.get(key)
         if ent is None:
             # First occurrence of a key: run eagerly (it is also the warm-up: weight twins, constants, plans, allocator).
@@ -853,6 +926,8 @@ class KeepNet:
     def _forward(self, x, B, T, H, Wd, force_indices, return_aux, force_flows=None):
         cfg = self.cfg
         self.o.begin_forward(self.device)
+        if self.of is not self.o:      # the flow Ops hands out its own max|out| slots
+            self.of.begin_forward(self.device)
         self._aux_top1 = []
         # K1: flows for all T-1 pairs (KA:976-986): flownet(x[:,1:], x[:,:-1])
         flows = None
@@ -996,8 +1071,12 @@ class KeepNet:
             free += torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)   # cached blocks are reusable
         except Exception:
             free = 64e9
+        n2 = 2 * (int(self._dev_blob.numel()) if self._dev_blob is not None else (0 if self._blob is None else int(self._blob.size)))
+        flow = n2 if (self.flow_precision == 'f16' and self.precision in X3_GRADE) else 0
         if self.precision == 'f16' and self._dev_blobx1 is None:      # the x1 twin is built at the first call: its bytes are not free
-            free -= self.twin_bytes('f16') - (0 if self._dev_blobx3 is None else self.twin_bytes('x3'))
+            free -= (self.twin_bytes('f16') - flow) - (0 if self._dev_blobx3 is None else self.twin_bytes('x3') - flow)
+        if flow and self._dev_blobx1f is None:      # likewise the flow twin
+            free -= flow
         return max(1, min(cap, int(0.8 * free / (per_frame * max(T, 1)))))
 
     def run_clips(self, clips, need_upscale=False, max_b=None):

@@ -119,6 +119,10 @@ class Ops:
         self.x1_base = L.MMA_X3             # the policy a call without a twin, or one the library refuses, stays on
         self.x1_base_kernel = None          # restriction: substitute only where the base plan is this kernel, un-split (None: everywhere)
         self.census = None         # when a dict: kernel name (plan string) -> launches, counted by conv() (tests, tools/bench_precision.py)
+        # single-fp16 attention (L.MMA_X1 | L.ATTN_X1): off by default.  True: attention() asks the library about every call of the x3
+        # base once per shape (route_attn_x1) and runs it single-fp16 where admitted -- KeepNet's flow Ops (KEEP_AMD_FLOW_PRECISION=f16)
+        self.attn_x1 = False
+        self._attn_x1_route = {}   # shape key -> True | False
 
     def begin_forward(self, device):
         """Zero this forward's bookkeeping words with ONE fill launch: the status word (non-finite logits / tensors, see
@@ -147,6 +151,7 @@ class Ops:
         self._x3_table = ([a for a, _, _ in x3_scales], list(x3_scales)) if x3_scales else None
         self.mma = self.attn_mma = mma
         self.set_x1_twin()      # ('f16' re-attaches its twin after every policy change)
+        self._attn_x1_route = {}
         if blobx3 is not None and (blob32 is not self._up2_src[0] or blobx3 is not self._up2_src[1]):
             # phase kernels of the Upsample convolutions (up2_twin): derived from THESE blob objects -- a new upload, even one that lands
             # on the same addresses, starts from an empty cache; a policy switch on the same blobs keeps it (captured x3 graphs hold
@@ -202,6 +207,22 @@ class Ops:
                         raise
             self._x1_route[key] = r
         return r or None
+
+    def route_attn_x1(self, key, x1_plan):
+        """``attn_x1``: does this attention call of the x3 base run under L.MMA_X1 | L.ATTN_X1?  The library decides: ``x1_plan()`` is
+        ``hiplib.attention_x1_plan`` for the call -- KEEP_EUNSUP is its answer 'stay on x3' (anything else is an error) -- asked once
+        per ``key``.  The key holds the per-image shape, the alignment classes and the flags, never the batch."""
+        r = self._attn_x1_route.get(key)
+        if r is None:
+            try:
+                x1_plan()
+                r = True
+            except L.KeepHipError as e:
+                if '(code -2)' not in str(e):      # anything but KEEP_EUNSUP is an error, not an answer
+                    raise
+                r = False
+            self._attn_x1_route[key] = r
+        return r
 
     # ------------------------------------------------------------------ weight twins
     def _blob_off(self, w):
@@ -564,12 +585,18 @@ class Ops:
             import sys
             print(f'[keep] attention mma={mma} in_dtype={in_dtype} B={B} H={H} Lq={Lq} Lk={Lk} D={D} Dv={Dv} mode={mode}',
                   file=sys.stderr, flush=True)
-        L.attention(q=q, k=k, v=v, o=o,
-                    q_bs=q_str[0], q_ts=q_str[1], q_hs=q_str[2], k_bs=k_str[0], k_ts=k_str[1], k_hs=k_str[2],
-                    v_bs=v_str[0], v_ts=v_str[1], v_hs=v_str[2], o_bs=o_str[0], o_ts=o_str[1], o_hs=o_str[2],
-                    B=B, H=H, Lq=Lq, Lk=Lk, D=D, Dv=Dv, scale=float(scale), mode=mode, T=T, seg_len=seg_len,
-                    img_h=img_h, img_w=img_w, ksplit=ksplit, shift=shift, kv_rot=kv_rot, n_img=n_img, mma=mma,
-                    in_dtype=in_dtype, q_amax=amax[0], k_amax=amax[1], v_amax=amax[2], flags=self.attn_flags)
+        kw = dict(q=q, k=k, v=v, o=o,
+                  q_bs=q_str[0], q_ts=q_str[1], q_hs=q_str[2], k_bs=k_str[0], k_ts=k_str[1], k_hs=k_str[2],
+                  v_bs=v_str[0], v_ts=v_str[1], v_hs=v_str[2], o_bs=o_str[0], o_ts=o_str[1], o_hs=o_str[2],
+                  B=B, H=H, Lq=Lq, Lk=Lk, D=D, Dv=Dv, scale=float(scale), mode=mode, T=T, seg_len=seg_len,
+                  img_h=img_h, img_w=img_w, ksplit=ksplit, shift=shift, kv_rot=kv_rot, n_img=n_img, mma=mma,
+                  in_dtype=in_dtype, q_amax=amax[0], k_amax=amax[1], v_amax=amax[2], flags=self.attn_flags)
+        if self.attn_x1 and mma == self.attn_mma == L.MMA_X3 and in_dtype == L.F32:
+            key = (H, Lq, Lk, D, Dv, mode, ksplit, img_h, img_w, shift, tuple(s % 4 for s in (*q_str, *k_str, *v_str)),
+                   tuple(t.data_ptr() % 16 for t in (q, k, v)), amax[0] is not None, self.attn_flags)
+            if self.route_attn_x1(key, lambda: L.attention_x1_plan(**kw)):      # single fp16 where the library admits it, x3 otherwise
+                kw.update(mma=L.MMA_X1, flags=self.attn_flags | L.ATTN_X1)
+        L.attention(**kw)
         if DEBUG_SYNC:
             torch.cuda.synchronize()
             if not bool(torch.isfinite(o).all()):

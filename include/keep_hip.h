@@ -62,7 +62,8 @@ extern "C" {
  *                 aligned, Cin %% 32 == 0; x3_acc_scale = 2^-e.  keep_conv2d only, and only where an x1 kernel exists: 3x3 stride-1
  *                 pad-1 convolutions on maps of 8 x 32 tiles (zero or reflection padding, upsample 0 / 1, no split-K) and im2col shapes
  *                 (strided / non-3x3, not the 1x1 GEMM form), all without aux / in2 / LayerNorm.  Everything else -- and
- *                 keep_attention -- answers KEEP_EUNSUP / KEEP_EINVAL with keep_last_error text: there is no silent change of policy.
+ *                 keep_attention without its own admitting bit (KEEP_ATTN_X1 below) -- answers KEEP_EUNSUP / KEEP_EINVAL with keep_last_error
+ *                 text: there is no silent change of policy.
  *                 v23: the 3x3 stride-1 form also takes the GroupNorm prologue under the rule of the x3 streaming kernel -- pro_scale /
  *                 pro_shift alone, with KEEP_PRO_RELU, or with KEEP_PRO_SWISH (fast form: not with KEEP_CONV_X3_EXACT_ACT), KEEP_PAD_ZERO only; the KEEP
  *                 network's opt-in precision 'f16' (engine/net.py).  Per element: v = x * pro_scale + pro_shift in fp32, the activation,
@@ -128,6 +129,23 @@ extern "C" {
 #define KEEP_ATTN_NO_X3 (1u << 2)     /* KEEP_MMA_X3 calls run on the exact-f32 kernel */
 #define KEEP_ATTN_NO_TWO_PASS (1u << 4) /* x3, D = Dv = 512, 256 tokens: attn_x3_sfull2_kernel instead of scores + softmax.V in the latency form */
 #define KEEP_ATTN_NO_SMALL (1u << 3)  /* x3, D = Dv = 64, <= 256 keys: attn_x3_kernel instead of the latency form (attn_x3_small_kernel) */
+/* KEEP_ATTN_X1: the admitting bit of keep_attention (additive like KEEP_CONV_X1_GEMM: same ABI version, read under mma == KEEP_MMA_X1 only,
+ * every other policy ignores it, and KEEP_MMA_X1 without it is refused as before).  With it KEEP_MMA_X1 takes exactly ONE form, the packed
+ * form of KEEP_MMA_X3 on single fp16 operands (attn_pack_kv_x3_kernel + attn_x3_kernel, both in their single-fp16 instantiation): mode 0 or
+ * mode 2, D == 128 and Dv == 128, Lq >= 256, in_dtype KEEP_F32 with 16-byte aligned q / k / v rows, no q/k/v_amax, and a 16-byte aligned
+ * `workspace` of at least keep_attention_workspace_bytes(a) bytes for the flagged call:
+ *     B * H * ceil(Lk / 32) * (32 * (D + 8) + ceil(Dv / 128) * 128 * 40) * 2      (x3: 32 * (2 D + 8) and 128 * 72)
+ * -- one image per key tile holding the hi halves only, K as 32 rows of D + 8 halves, V^T as 128 rows of 32 + 8 halves.  Anything else
+ * (another shape, KEEP_ATTN_NO_PACK, a missing or smaller workspace) answers KEEP_EUNSUP with keep_last_error naming what failed, and
+ * keep_attention_workspace_bytes answers -1: the library never runs such a call on another policy.
+ * What is rounded, in order: q, k and v are each converted from fp32 to fp16 (round to nearest even) AS GIVEN -- `scale` is not folded
+ * into Q; like KEEP_MMA_X3 the kernel multiplies the fp32 score accumulators S = sum_d fp16(q_d) * fp16(k_d) by scale * log2(e) afterwards,
+ * adds the -100 window mask and runs the online softmax in fp32 (exp2 domain).  Each probability p = exp2(s - running max) in (0, 1] is
+ * then rounded once to fp16 for P.V^T, while the softmax denominator sums the UNROUNDED fp32 p; the output accumulates in fp32 and is
+ * divided by that denominator.  So the result is fp32 attention on fp16(q), fp16(k), fp16(v) up to one 2^-11 relative rounding per
+ * probability term.  A value beyond the fp16 range (65504) becomes inf and the output non-finite, as under KEEP_MMA_X3.
+ * GMFlow's swin window attention under KEEP_AMD_FLOW_PRECISION=f16 (engine/net.py) sets it. */
+#define KEEP_ATTN_X1 (1u << 5)
 
 /* padding mode of keep_conv2d */
 #define KEEP_UPSAMPLE_X2_PHASES 2
@@ -282,7 +300,8 @@ typedef struct {
   int32_t T, seg_len;                           /* mode 1 */
   int32_t img_h, img_w, ksplit, shift, kv_rot, n_img; /* mode 2 */
   int32_t mma; /* KEEP_MMA_F32 | KEEP_MMA_BF16 (Q,K,V,P rounded to bf16; fp32 softmax + accumulate) | KEEP_MMA_X3 (Q,K,V,P
-                  split into fp16 hi + lo, three MFMAs per product: fp32-grade; exact-fp32 softmax) */
+                  split into fp16 hi + lo, three MFMAs per product: fp32-grade; exact-fp32 softmax) | KEEP_MMA_X1 with
+                  flags & KEEP_ATTN_X1 (Q,K,V,P rounded once to fp16, one MFMA per product; the packed D = Dv = 128 form only) */
   int32_t in_dtype; /* KEEP_F32, or KEEP_BF16 (with KEEP_MMA_BF16): q, k, v are bf16 tensors, strides in elements */
   /* KEEP_MMA_X3, mode 0 only: per-batch max |q|, |k|, |v| ([B] floats each, keep_absmax) for operands that are not
    * bounded by a normalisation (CFA reads the raw residual stream); all three or none */
@@ -297,7 +316,8 @@ typedef struct {
 } keep_attention_args;
 #define KEEP_ATTENTION_ARGS_V12_SIZE 248
 int32_t keep_attention(const keep_attention_args* a, void* stream);
-/* bytes of `workspace` this call can use (0: none); a smaller or NULL workspace selects the unpacked path */
+/* bytes of `workspace` this call can use (0: none); a smaller or NULL workspace selects the unpacked path.  KEEP_MMA_X1 with KEEP_ATTN_X1:
+ * the bytes the call NEEDS, or -1 where keep_attention would answer KEEP_EUNSUP (keep_last_error says why) */
 int64_t keep_attention_workspace_bytes(const keep_attention_args* a);
 
 /* ------------------------------------------------------------------------------------------------
