@@ -1984,6 +1984,7 @@ static int plan_x3(const keep_conv2d_args* a, const ConvP& p, const ConvGeom& g,
       return KEEP_EUNSUP;
     }
     plan_halo_x3_unsplit(FORM_HALO_UP2, pl);
+    pl.stream = keep_conv_x3_up2_stream_ok(a);      // two phases per staged halo (keep_conv_x3s.hip); the plan reports one kernel name for the form
     return KEEP_OK;
   }
   if (have_w && g.is33s1 && keep_conv_x3_halo_ok(a) && !(a->flags & KEEP_CONV_NO_HALO_X3)) {

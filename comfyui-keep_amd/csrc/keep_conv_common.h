@@ -362,7 +362,7 @@ struct ConvPlan {
   int tile;            // gather kernels' block tile: 0 = 128x32 (4,1,1,1), 1 = 64x64 (2,2,1,1), 2 = 128x128 (2,2,2,2 -- FORM_GEMM_LN: 4,1,1,4)
   bool plain, wide, bk256;
   bool gemm;           // PATH_GATHER_X3: 1x1 stride-1 unpadded (keep_conv_x3_gather_is_gemm)
-  bool stream;         // FORM_X3_HALO: keep_conv_x3_stream_ok at the planned split-K
+  bool stream;         // FORM_X3_HALO: keep_conv_x3_stream_ok at the planned split-K; FORM_HALO_UP2: keep_conv_x3_up2_stream_ok
   bool simple_epi;     // FORM_X1_HALO16: no epilogue activation
   int split_k;
   int stats_rows;      // output pixels per statistics partial; 0 = this call cannot emit statistics
@@ -375,6 +375,7 @@ struct ConvPlan {
 bool keep_conv_x3_halo_ok(const keep_conv2d_args* a);
 bool keep_conv_x3_up2_ok(const keep_conv2d_args* a);
 bool keep_conv_x3_stream_ok(const keep_conv2d_args* a, const ConvP& p, int split_k);
+bool keep_conv_x3_up2_stream_ok(const keep_conv2d_args* a);
 bool keep_conv_x3_gather_ok(const keep_conv2d_args* a, const ConvP& p);
 bool keep_conv_x3_gather_is_gemm(const keep_conv2d_args* a);
 bool keep_conv_x1_stream_ok(const keep_conv2d_args* a, const ConvP& p);
@@ -391,6 +392,7 @@ bool keep_conv_x3p_full_ok(const keep_conv2d_args* a, const ConvP& p, int split_
 int keep_conv2d_x3_c3(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
 int keep_conv2d_x3_halo(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st);
 int keep_conv2d_x3_stream(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st);
+int keep_conv2d_x3_up2_stream(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
 int keep_conv2d_x3_partials(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
 int keep_conv2d_x3_small_full(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
 int keep_conv2d_x3_gather(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st);

@@ -82,6 +82,8 @@ __device__ __forceinline__ float xor32_sum(float x) {
 //   ([phase][Cout][9 taps][Cin/16][hi16|lo16], unused taps zero and never fetched); an item is (source tile, phase, cout block), its
 //   MFMA loop is compiled per phase (static tap list), its epilogue scatters to the stride-2 output pixels.  Tiles, halo and
 //   addressing are those of a plain 3x3 convolution on the source (p.upsample = 0, p.Ho / p.Wo = the OUTPUT extent).
+//   Calls with Cin >= 32 run on conv3x3_up2_x3s_kernel (keep_conv_x3s.hip: two phases per staged halo, the same values bit for bit); this
+//   form keeps Cin = 16 and KEEP_CONV_NO_STREAM.
 // X1 (KEEP_MMA_X1 behind KEEP_CONV_X1_HALO16): operands rounded once to fp16, one MFMA per product.  A chunk is 32 channels: a
 //   halo row holds [ch 0..15 | ch 16..31] where the x3 form holds [hi x16 | lo x16] and a weight row (p.wx3 = the hi-only twin, plain
 //   [Cout][9][Cin] fp16) its 64 bytes of 32 channels where the x3 row holds hi | lo of 16 -- the LDS image, the DMA instructions and the 8
@@ -1395,6 +1397,7 @@ int keep_conv2d_x3_halo(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl,
   dim3 block(256);
   if (pl.form == FORM_X1_STREAM) return keep_conv2d_x3_stream(a, p, pl, st);      // keep_conv_x3s.hip
   if (pl.form == FORM_HALO_UP2) {      // four 2x2-tap phase convolutions on the source grid (kernel comment: UP2)
+    if (pl.stream) return keep_conv2d_x3_up2_stream(a, p, st);      // keep_conv_x3s.hip: the same values, two phases per staged halo
     const int tx = a->W / 32, ty = a->H / 8, ncbv = 4 * (a->Cout / 64);
     const int n_items = a->N * tx * ty * ncbv;
     p.upsample = 0;                                    // the kernel addresses the source like a plain 3x3 convolution

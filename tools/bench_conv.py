@@ -29,6 +29,11 @@ LAYERS = {  # name: (N, H, W, Cin, Cout, ksize, upsample)
     'c128_256_n1': (1, 256, 256, 128, 128, 3, False),
     'c256_64_n1': (1, 64, 64, 256, 256, 3, False),          # one clip in flight: the 64-pixel-block kernels (conv3x3_x3q_kernel)
     'c256_32_n1': (1, 32, 32, 256, 256, 3, False),
+    'up128_512_n48': (48, 256, 256, 128, 128, 3, True),     # the generator's four Upsample convolutions at 48 clips (UP2=1 X3=1: the phase form;
+    'up128_256_n48': (48, 128, 128, 128, 128, 3, True),     # CONV_FLAGS=512 puts them on the stage-barrier kernel)
+    'up256_128_n48': (48, 64, 64, 256, 256, 3, True),
+    'up256_64_n48': (48, 32, 32, 256, 256, 3, True),
+    'up128_512_n1': (1, 256, 256, 128, 128, 3, True),
     'lin128': (1, 622592, 1, 128, 128, 1, False),
     'lin256_1024': (1, 622592, 1, 256, 1024, 1, False),
     't512_1024': (1, 4096, 1, 512, 1024, 1, False),

@@ -35,19 +35,32 @@ EXTRA = {
     'gather_stats_replica': dict(mma=X3, N=1, H=64, W=64, Cin=16, Cout=128, stride=2, split_k=1, stats=True),
     'gather_small_tile': dict(mma=X3, N=1, H=64, W=64, Cin=16, Cout=128, stride=2, split_k=1),
     'gather_shallow': dict(mma=X3, N=1, H=1040, W=1040, Cin=16, Cout=32, stride=2),
+    # the x2-phase Upsample (phase weights, output 2H x 2W): three cout blocks with inner tile edges, 640 items on <= 512 blocks (item seams,
+    # image boundaries), and the stage-barrier form of the first under KEEP_CONV_NO_STREAM on the same data (`data`) -- the same hashes as its twin
+    'up2_three_blocks': dict(mma=X3, N=1, H=16, W=64, Cin=32, Cout=192, up2=True, split_k=1, stats=True),
+    'up2_item_seams': dict(mma=X3, N=5, H=64, W=64, Cin=32, Cout=256, up2=True, split_k=1, stats=True),
+    'up2_three_blocks_no_stream': dict(mma=X3, N=1, H=16, W=64, Cin=32, Cout=192, up2=True, split_k=1, stats=True, flags=L.CONV_NO_STREAM,
+                                       data='up2_three_blocks'),
 }
 
 
 def extra_case(name):
-    c = dict(k=3, stride=1, pro=False, pro_act=L.PRO_NONE, act=L.ACT_NONE, flags=0, stats=False, split_k=0)      # (split_k = 1: the caller asks for a single pass, as it does when it wants statistics)
+    c = dict(k=3, stride=1, pro=False, pro_act=L.PRO_NONE, act=L.ACT_NONE, flags=0, stats=False, split_k=0, up2=False)      # (split_k = 1: the caller asks for a single pass, as it does when it wants statistics)
     c.update(EXTRA[name])
+    name = c.get('data', name)      # (the inputs are generated from the case's name)
     k, s, N, H, W, Cin, Cout = c['k'], c['stride'], c['N'], c['H'], c['W'], c['Cin'], c['Cout']
     pad = k // 2
     Ho, Wo = (H + 2 * pad - k) // s + 1, (W + 2 * pad - k) // s + 1
     x = op_input('cch:' + name + 'x', (N * H * W, Cin), 2.0) + 0.3
     w = op_input('cch:' + name + 'w', (Cout, k, k, Cin), 0.05)
     sc = ops.x3_scale_for(float(w.abs().max()))
-    twin = (w * sc).to(torch.float16).reshape(Cout, -1) if c['mma'] == X1 else ops.split_x3(w.reshape(-1, Cin), sc).reshape(Cout, -1)
+    if c['up2']:
+        Ho, Wo = 2 * H, 2 * W
+        w4 = ops.up2_phase_weights(w)
+        sc = ops.x3_scale_for(float(w4.abs().max()))
+        twin = ops.split_x3(w4.reshape(-1, Cin), sc).reshape(4 * Cout, -1)
+    else:
+        twin = (w * sc).to(torch.float16).reshape(Cout, -1) if c['mma'] == X1 else ops.split_x3(w.reshape(-1, Cin), sc).reshape(Cout, -1)
     amax = x.reshape(N, -1).abs().amax(1) * (1.2 if c['pro'] else 1.0) + (0.2 if c['pro'] else 0.0)      # (an upper bound of what the prologue gives)
     R = [FP.single('x', x), FP.single('w', w.reshape(Cout, -1)), FP.single('bias', op_input('cch:' + name + 'b', (1, Cout))),
          FP.single('wx3', twin.contiguous()), FP.single('in_amax', amax.reshape(1, N)), FP.output('out', (N * Ho * Wo, Cout))]
@@ -59,7 +72,8 @@ def extra_case(name):
         return L.conv_args(inp=p['x'], weight=p['w'], bias=p['bias'], out=p['out'], pro_scale=p.get('pro_scale'), pro_shift=p.get('pro_shift'),
                            workspace=p.get('ws'), stats_out=p.get('stats'), stats_P=t.get('stats_P', 0), N=N, H=H, W=W, Cin=Cin, Cout=Cout, KH=k, KW=k,
                            stride=s, pad_t=pad, pad_l=pad, Ho=Ho, Wo=Wo, in_ld=Cin, out_ld=Cout, pro_act=c['pro_act'], epi_act=c['act'], mma=c['mma'],
-                           weight_x3=p['wx3'], x3_acc_scale=1.0 / sc, x3_in_amax=p['in_amax'], flags=c['flags'], split_k=c['split_k'])
+                           weight_x3=p['wx3'], x3_acc_scale=1.0 / sc, x3_in_amax=p['in_amax'], flags=c['flags'], split_k=c['split_k'],
+                           upsample=L.UPSAMPLE_X2_PHASES if c['up2'] else 0)
     plan = L.conv2d_plan(args({n: 0x10000 for r in R for n in r.windows}))
     extra = {}
     if plan.split_k > 1:
