@@ -1734,8 +1734,10 @@ static int validate_conv(const keep_conv2d_args* a) {
   KEEP_REQUIRE((long)(a->Ho - 1) * a->stride - a->pad_t < Hv && (long)(a->Wo - 1) * a->stride - a->pad_l < Wv,
                "keep_conv2d: output extent %dx%d inconsistent with input %dx%d", a->Ho, a->Wo, Hv, Wv);
   KEEP_REQUIRE(a->mma == KEEP_MMA_F32 || a->mma == KEEP_MMA_BF16 || a->mma == KEEP_MMA_X3 || a->mma == KEEP_MMA_X1, "keep_conv2d: bad mma %d", a->mma);
-  KEEP_REQUIRE(a->upsample == 0 || a->upsample == 1 || (a->upsample == KEEP_UPSAMPLE_X2_PHASES && a->mma == KEEP_MMA_X3),
-               "keep_conv2d: upsample must be 0, 1 or KEEP_UPSAMPLE_X2_PHASES (KEEP_MMA_X3 only), got %d", a->upsample);
+  KEEP_REQUIRE(a->upsample == 0 || a->upsample == 1 ||
+                   (a->upsample == KEEP_UPSAMPLE_X2_PHASES &&
+                    (a->mma == KEEP_MMA_X3 || (a->mma == KEEP_MMA_X1 && (a->flags & KEEP_CONV_X1_UP2)))),
+               "keep_conv2d: upsample must be 0, 1 or KEEP_UPSAMPLE_X2_PHASES (KEEP_MMA_X3, or KEEP_MMA_X1 with KEEP_CONV_X1_UP2), got %d", a->upsample);
   KEEP_REQUIRE(a->pad_mode == KEEP_PAD_ZERO || a->pad_mode == KEEP_PAD_REFLECT, "keep_conv2d: bad pad_mode %d", a->pad_mode);
   if (a->pad_mode == KEEP_PAD_REFLECT) {
     if (a->mma == KEEP_MMA_BF16 || a->dtype != KEEP_F32 || a->pad_t != a->pad_l || a->pad_t >= Hv || a->pad_t >= Wv ||
@@ -1911,6 +1913,29 @@ static int refuse_x1(const keep_conv2d_args* a) {
 static int plan_x1(const keep_conv2d_args* a, const ConvP& p, const ConvGeom& g, ConvPlan& pl) {
   KEEP_REQUIRE(a->dtype == KEEP_F32 && a->out_dtype != KEEP_BF16, "keep_conv2d: KEEP_MMA_X1 takes and writes fp32 tensors");
   const bool have_w = x3_weights_ok(a);
+  // KEEP_CONV_X1_UP2 (the third opt-in bit; validate_conv() lets the phase mode through under KEEP_MMA_X1 only with it): weight_x3 holds the
+  // hi-only PHASE twin, so nothing but the phase kernel's single-fp16 instantiation can run the call
+  if (a->upsample == KEEP_UPSAMPLE_X2_PHASES) {
+    const char* why = !have_w ? "weight_x3 (the hi-only phase twin [4][Cout][3*3][Cin] fp16, 16-byte aligned) and x3_acc_scale are missing"
+                      : a->pro_scale || a->pro_act != KEEP_PRO_NONE ? "it takes raw inputs: no prologue (pro_scale / pro_shift / pro_act)"
+                      : a->epi_act != KEEP_ACT_NONE ? "it has no epilogue activation"
+                      : a->aux ? "it has no aux epilogue"
+                      : a->in2 ? "it has no second input (in2)"
+                      : a->ln_gamma ? "it has no LayerNorm epilogue"
+                      : a->split_k > 1 ? "it is un-split (split_k <= 1)"
+                      : g.reflect ? "it pads with zeros (no KEEP_PAD_REFLECT)"
+                      : a->Cin % 32 != 0 ? "it needs Cin % 32 == 0 (whole two-chunk weight rows)"
+                      : !(g.is33s1 && keep_conv_x1_up2_ok(a)) ? "KEEP_MMA_X3 does not plan the streaming phase form for it (a 3x3 stride-1 pad-1 "
+                                                                "convolution, H % 8 == 0, W % 32 == 0, Cout % 64 == 0, Cin >= 32, no KEEP_CONV_NO_STREAM)"
+                      : (a->flags & KEEP_CONV_NO_HALO_X3) ? "KEEP_CONV_NO_HALO_X3 removes the halo kernels"
+                                                          : nullptr;
+    if (why) {
+      keep_set_error("keep_conv2d: KEEP_MMA_X1 (with KEEP_CONV_X1_UP2) has no kernel for this upsample = KEEP_UPSAMPLE_X2_PHASES call: %s", why);
+      return KEEP_EUNSUP;
+    }
+    plan_halo_x3_unsplit(FORM_X1_UP2, pl);
+    return KEEP_OK;
+  }
   if (have_w && g.is33s1 && keep_conv_x3_halo_ok(a) && keep_conv_x1_stream_ok(a, p) && a->split_k <= 1 && !(a->flags & KEEP_CONV_NO_HALO_X3)) {
     plan_halo_x3_unsplit(FORM_X1_STREAM, pl);
     return KEEP_OK;

@@ -347,6 +347,7 @@ enum ConvForm {
   FORM_HALO_UP2,        // x3, KEEP_UPSAMPLE_X2_PHASES: four 2x2-tap phase convolutions on the source grid
   FORM_X1_STREAM,       // single fp16, 8 x 32 tiles: the streaming kernel's X1 instantiations
   FORM_X1_HALO16,       // single fp16, 16 x 16 tiles (KEEP_CONV_X1_HALO16); ConvPlan::simple_epi picks the epilogue
+  FORM_X1_UP2,          // single fp16, KEEP_UPSAMPLE_X2_PHASES (KEEP_CONV_X1_UP2): the streaming phase kernel's X1 instantiation
   FORM_X3_HALO,         // x3: the streaming kernel or the stage-barrier one (ConvPlan::stream), the 64-pixel blocks at launch
   // PATH_GATHER_X3
   FORM_X1_IM2COL,       // single fp16 im2col
@@ -380,6 +381,7 @@ bool keep_conv_x3_gather_ok(const keep_conv2d_args* a, const ConvP& p);
 bool keep_conv_x3_gather_is_gemm(const keep_conv2d_args* a);
 bool keep_conv_x1_stream_ok(const keep_conv2d_args* a, const ConvP& p);
 bool keep_conv_x1_halo16_ok(const keep_conv2d_args* a);
+bool keep_conv_x1_up2_ok(const keep_conv2d_args* a);
 bool keep_conv_x1_gather_ok(const keep_conv2d_args* a, const ConvP& p);
 bool keep_conv_x1_gemm_ok(const keep_conv2d_args* a, const ConvP& p);
 bool keep_gemm_x3l_ok(const keep_conv2d_args* a);
@@ -392,7 +394,7 @@ bool keep_conv_x3p_full_ok(const keep_conv2d_args* a, const ConvP& p, int split_
 int keep_conv2d_x3_c3(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
 int keep_conv2d_x3_halo(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st);
 int keep_conv2d_x3_stream(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st);
-int keep_conv2d_x3_up2_stream(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
+int keep_conv2d_x3_up2_stream(const keep_conv2d_args* a, ConvP& p, bool x1, hipStream_t st);
 int keep_conv2d_x3_partials(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
 int keep_conv2d_x3_small_full(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
 int keep_conv2d_x3_gather(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st);
@@ -432,6 +434,7 @@ static inline void plan_kernel_name(const keep_conv2d_args* a, ConvPlan& pl) {
     case FORM_X1_HALO16:      // <TW, PRO, SIMPLE_EPI, FASTACT, WDMA, UP2, X1>
       snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_x3_kernel<16, 0, %s, true, true, false, true>", pl.simple_epi ? "true" : "false");
       return;
+    case FORM_X1_UP2: snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_x3_kernel<32, x2 phases, true>"); return;      // the form's name + X1
     case FORM_X3_HALO:
       if (pl.stream)
         snprintf(pl.kernel, sizeof(pl.kernel), "conv3x3_halo_x3s_kernel");

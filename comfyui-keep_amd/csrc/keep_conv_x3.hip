@@ -1397,7 +1397,7 @@ int keep_conv2d_x3_halo(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl,
   dim3 block(256);
   if (pl.form == FORM_X1_STREAM) return keep_conv2d_x3_stream(a, p, pl, st);      // keep_conv_x3s.hip
   if (pl.form == FORM_HALO_UP2) {      // four 2x2-tap phase convolutions on the source grid (kernel comment: UP2)
-    if (pl.stream) return keep_conv2d_x3_up2_stream(a, p, st);      // keep_conv_x3s.hip: the same values, two phases per staged halo
+    if (pl.stream) return keep_conv2d_x3_up2_stream(a, p, false, st);      // keep_conv_x3s.hip: the same values, two phases per staged halo
     const int tx = a->W / 32, ty = a->H / 8, ncbv = 4 * (a->Cout / 64);
     const int n_items = a->N * tx * ty * ncbv;
     p.upsample = 0;                                    // the kernel addresses the source like a plain 3x3 convolution
@@ -1406,6 +1406,7 @@ int keep_conv2d_x3_halo(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl,
     KEEP_LAUNCH_CHECK("keep_conv2d(halo x3, x2 phases)");
     return KEEP_OK;
   }
+  if (pl.form == FORM_X1_UP2) return keep_conv2d_x3_up2_stream(a, p, true, st);      // the hi-only phase twin on the same pipeline
   if (pl.form == FORM_X1_HALO16) {      // 16 x 16 tiles, raw input, zero padding, un-split
     const int tiles_x = a->Wo / 16, tiles_y = a->Ho / 16, ncb = (a->Cout + 63) / 64;
     const int n_items = a->N * tiles_x * tiles_y * ncb;

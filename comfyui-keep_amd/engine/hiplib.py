@@ -24,6 +24,7 @@ UPSAMPLE_X2_PHASES = 2
 (CONV_NO_COUT4, CONV_NO_C3, CONV_NO_HALO_F32, CONV_NO_HALO_X3, CONV_NO_GATHER_X3, CONV_NO_PLAIN, CONV_NO_FLATK_F32,
  CONV_SMALL_TILES, CONV_X3_EXACT_ACT, CONV_NO_STREAM, CONV_NO_GEMM_LAT, CONV_GEMM_LAT_WAVES, CONV_GEMM_LAT_TILES, CONV_NO_SMALL_PARTIALS) = (1 << i for i in range(14))
 CONV_X1_HALO16 = 1 << 15    # opt-in: MMA_X1 also takes 3x3 stride-1 convolutions on 16 x 16-tile maps that are not 8 x 32 tileable (KEEP_CONV_X1_HALO16)
+CONV_X1_UP2 = 1 << 16       # opt-in: MMA_X1 also takes upsample = UPSAMPLE_X2_PHASES where x3 plans the streaming phase form, Cin % 32 == 0 (KEEP_CONV_X1_UP2)
 CONV_X1_GEMM = 1 << 14      # opt-in: MMA_X1 also takes the 1x1 stride-1 GEMM form (KEEP_CONV_X1_GEMM); ignored by every other policy
 ATTN_NO_PACK, ATTN_NO_SFULL2, ATTN_NO_X3, ATTN_NO_SMALL, ATTN_NO_TWO_PASS = 1, 2, 4, 8, 16
 ATTN_X1 = 1 << 5            # opt-in: MMA_X1 takes the packed D = Dv = 128 attention form on single fp16 operands (KEEP_ATTN_X1); ignored by every other policy

@@ -58,6 +58,11 @@ X3_GRADE = ('x3', 'f16')      # policies whose operands are fp16 halves: the ran
 # CNN backbone, swin blocks and q / k projections take single-fp16 operands where the library admits them; needs an x3-grade base
 FLOW_PRECISIONS = ('x3', 'f16')
 FLOW_PRECISION_ENV = 'KEEP_AMD_FLOW_PRECISION'
+# KEEP_AMD_UPSAMPLE_PRECISION: the generator's x2-phase Upsample convolutions' own knob, independent of KEEP_AMD_PRECISION (whose 'f16' leaves
+# them on x3).  'x3' (default): as if the knob did not exist.  'f16': the Upsample convolutions the phase form takes run on single-fp16 operands
+# where the library admits them (KEEP_CONV_X1_UP2); needs an x3-grade base
+UPSAMPLE_PRECISIONS = ('x3', 'f16')
+UPSAMPLE_PRECISION_ENV = 'KEEP_AMD_UPSAMPLE_PRECISION'
 
 
 ROCTX = os.environ.get('KEEP_AMD_ROCTX', '0') == '1'      # per-stage roctx ranges (rocprofv3 --marker-trace / --kernel-trace timelines)
@@ -145,6 +150,8 @@ class KeepNet:
         self.set_precision(os.environ.get('KEEP_AMD_PRECISION', DEFAULT_PRECISION))
         self.flow_precision = 'x3'
         self.set_flow_precision(os.environ.get(FLOW_PRECISION_ENV) or 'x3')
+        self.upsample_precision = 'x3'
+        self.set_upsample_precision(os.environ.get(UPSAMPLE_PRECISION_ENV) or 'x3')
 
     # ------------------------------------------------------------------ nn.Module-like surface
     def load_state_dict(self, state_dict, strict=True):
@@ -187,8 +194,9 @@ class KeepNet:
         'bf16': operands rounded to bf16 (speed policy, outside the parity tolerance).
         'f16': the x3 policy with the streaming 3x3 convolutions (raw inputs and the GroupNorm-swish prologue) on SINGLE fp16
         operands (KEEP_MMA_X1: one MFMA per product, 11 mantissa bits per operand) wherever keep_conv2d_plan admits it; attention,
-        the GEMM forms, the phase upsample, the split-K forms and GMFlow stay x3.  An opt-in speed policy outside the parity
-        tolerance like 'bf16' (DESIGN 4.2); batch invariance and the fp16-range fallback are those of 'x3'."""
+        the GEMM forms, the phase upsample, the split-K forms and GMFlow stay x3 (GMFlow and the phase upsample have knobs of their
+        own on top of an 'x3' or 'f16' base: ``set_flow_precision``, ``set_upsample_precision``).  An opt-in speed policy outside the
+        parity tolerance like 'bf16' (DESIGN 4.2); batch invariance and the fp16-range fallback are those of 'x3'."""
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
         self.precision = precision
@@ -206,6 +214,47 @@ class KeepNet:
             raise ValueError(f"{FLOW_PRECISION_ENV} (set_flow_precision) must be one of {FLOW_PRECISIONS}, got {precision!r}")
         self.flow_precision = precision
         return self
+
+    def set_upsample_precision(self, precision):
+        """The generator's Upsample knob (``KEEP_AMD_UPSAMPLE_PRECISION``).  'x3' (default): as if the knob did not exist -- no extra
+        plan query, the same launches.  'f16': on an 'x3' or 'f16' base (anything else raises when the policy is activated), the
+        x2-phase Upsample convolutions (32^2, 64^2, 128^2 and 256^2 sources; the 16^2 one is not 8 x 32 tileable and stays as it is)
+        run on single-fp16 operands -- the hi-only phase twin, KEEP_MMA_X1 with KEEP_CONV_X1_UP2 -- wherever keep_conv2d_plan admits
+        it.  An opt-in speed mode outside the 1e-3 parity tolerance, never a default; batch invariance and the fp16-range
+        fallback are x3's."""
+        if precision not in UPSAMPLE_PRECISIONS:
+            raise ValueError(f"{UPSAMPLE_PRECISION_ENV} (set_upsample_precision) must be one of {UPSAMPLE_PRECISIONS}, got {precision!r}")
+        self.upsample_precision = precision
+        return self
+
+    def up2_x1_names(self):
+        """Names of the Upsample convolution weights that get a hi-only phase twin: those whose source map (square, ``img_size`` / 2^levels
+        doubling with every Upsample) the phase form tiles -- a multiple of 32 -- with Cin % 32 == 0.  The 16^2 -> 32^2 one has none."""
+        names, res = [], self.cfg['img_size'] // 2 ** (len(self.cfg['ch_mult']) - 1)
+        for i, (kind, cin, _) in enumerate(generator_blocks(self.cfg)):
+            if kind == 'up':
+                if res % 32 == 0 and cin % 32 == 0:
+                    names.append(f'generator.blocks.{i}.conv.weight')
+                res *= 2
+        return names
+
+    def _up2_x1_bytes(self):
+        """Device bytes of the hi-only phase twins: four phase kernels of 2 bytes per weight for every name of ``up2_x1_names``."""
+        if self._index is None:
+            return 0
+        return sum(8 * int(np.prod(self._index[n][1])) for n in self.up2_x1_names())
+
+    def _activate_upsample_precision(self):
+        """``self.o.up2_x1`` follows the knob; the hi-only phase twins are built here, never inside a stream capture."""
+        if self.upsample_precision != 'f16':
+            self.o.up2_x1 = False
+            return
+        if self.precision not in X3_GRADE:
+            raise ValueError(f"{UPSAMPLE_PRECISION_ENV}=f16 needs the base precision 'x3' or 'f16', not {self.precision!r}")
+        if ops.UP2_PHASES and self.w is not None:
+            for n_ in self.up2_x1_names():
+                self.o.up2_x1_twin(self.w[n_])
+        self.o.up2_x1 = True
 
     @staticmethod
     def flow_x1_names(index):
@@ -250,7 +299,8 @@ class KeepNet:
         precision = self.precision if precision is None else precision
         n = int(self._dev_blob.numel()) if self._dev_blob is not None else (0 if self._blob is None else int(self._blob.size))
         flow = 2 * n if (self.flow_precision == 'f16' and precision in X3_GRADE) else 0      # the flow twin: 2 bytes per blob element
-        return {'bf16': 2 * n, 'x3': 4 * n, 'f16': 4 * n + 2 * n}.get(precision, 0) + flow
+        up = self._up2_x1_bytes() if (self.upsample_precision == 'f16' and precision in X3_GRADE) else 0      # the hi-only phase twins
+        return {'bf16': 2 * n, 'x3': 4 * n, 'f16': 4 * n + 2 * n}.get(precision, 0) + flow + up
 
     def _activate_flow_precision(self):
         """``self.of``: self.o, or (flow 'f16') the second Ops on x3 with the flownet x1 twin -- built here, never inside a stream capture."""
@@ -273,6 +323,7 @@ class KeepNet:
     def _activate_precision(self):
         self._activate_base_precision()
         self._activate_flow_precision()
+        self._activate_upsample_precision()
 
     def _activate_base_precision(self):
         if self.precision == 'bf16':
@@ -365,12 +416,14 @@ class KeepNet:
         policy, the plans' reference batch, the kernel-selection overrides and the hipGraph mode.  ``GpuPool.run`` compares it with
         what the workers were last told and re-configures them when it moved (``set_precision`` after the pool came up)."""
         return {'precision': self.precision, 'plan_ref_images': int(self.o.plan_ref_images), 'flags': int(self.o.flags),
-                'attn_flags': int(self.o.attn_flags), 'graph_mode': str(self.graph_mode), 'flow_precision': self.flow_precision}
+                'attn_flags': int(self.o.attn_flags), 'graph_mode': str(self.graph_mode), 'flow_precision': self.flow_precision,
+                'upsample_precision': self.upsample_precision}
 
     def apply_pool_config(self, cfg):
         """Worker side of ``pool_config``."""
         self.set_precision(cfg['precision'])
         self.set_flow_precision(cfg.get('flow_precision', 'x3'))
+        self.set_upsample_precision(cfg.get('upsample_precision', 'x3'))
         self.o.plan_ref_images, self.o.flags, self.o.attn_flags = int(cfg['plan_ref_images']), int(cfg['flags']), int(cfg['attn_flags'])
         self.graph_mode = str(cfg['graph_mode'])
 
@@ -866,8 +919,8 @@ class KeepNet:
         logging.getLogger('ComfyUI-KEEP').warning(
             "x3 precision policy left the fp16 operand range on this batch (status %d); re-running it on the f32 kernels", bits)
         self.x3_fallbacks += 1
-        policy, flow_policy = self.precision, self.flow_precision      # 'x3' or 'f16' (and the flow knob): restored after the re-run
-        self.precision, self.flow_precision = 'fp32', 'x3'
+        policy, flow_policy, up_policy = self.precision, self.flow_precision, self.upsample_precision      # 'x3' or 'f16' (and the two knobs): restored after the re-run
+        self.precision, self.flow_precision, self.upsample_precision = 'fp32', 'x3', 'x3'
         try:
             self._activate_precision()
             res = None                               # (callers drop their reference to the x3 result before calling: the re-run needs the room)
@@ -880,7 +933,7 @@ class KeepNet:
                                       for b0 in range(0, B, part)], 0)
             return self._forward(x, B, T, H, Wd, force_indices, return_aux, force_flows)
         finally:
-            self.precision, self.flow_precision = policy, flow_policy
+            self.precision, self.flow_precision, self.upsample_precision = policy, flow_policy, up_policy
             self._activate_precision()
 
     def _forward_graphed(self, x, B, T, H, Wd):
@@ -890,7 +943,7 @@ class KeepNet:
         the host code between launches only computes shapes, so the replay is bit-identical to the eager run."""
         self.o.ensure_arena(self.device)
         key = (B, T, H, Wd, self.precision, self._dev_blob.data_ptr(), self.o.arena_generation, self.o.flags, self.o.attn_flags,
-               self.o.plan_ref_images)
+               self.o.plan_ref_images, self.upsample_precision)
         if self.of is not self.o:
             self.of.ensure_arena(self.device)
             key += (self.flow_precision, self.of.arena_generation)
@@ -1077,6 +1130,8 @@ class KeepNet:
             free -= (self.twin_bytes('f16') - flow) - (0 if self._dev_blobx3 is None else self.twin_bytes('x3') - flow)
         if flow and self._dev_blobx1f is None:      # likewise the flow twin
             free -= flow
+        if self.upsample_precision == 'f16' and self.precision in X3_GRADE and not self.o.up2_x1:      # likewise the hi-only phase twins
+            free -= self._up2_x1_bytes()
         return max(1, min(cap, int(0.8 * free / (per_frame * max(T, 1)))))
 
     def run_clips(self, clips, need_upscale=False, max_b=None):

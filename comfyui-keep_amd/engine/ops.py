@@ -27,6 +27,7 @@ HALO_PRENORM_MINPIX = int(os.environ.get('KEEP_HALO_PRENORM_MINPIX', '0'))
 
 DEBUG_SYNC = os.environ.get('KEEP_DEBUG_SYNC') is not None
 X3_STREAM_KERNEL = 'conv3x3_halo_x3s_kernel'      # keep_conv2d_plan's name of the x3 streaming 3x3 kernel: the one family KeepNet's 'f16' substitutes
+X1_UP2_KERNEL = 'conv3x3_halo_x3_kernel<32, x2 phases, true>'    # keep_conv2d_plan's name of the single-fp16 x2-phase Upsample kernel (L.CONV_X1_UP2): what ``Ops.up2_x1`` routes to
 _PLAN_CACHE = {}
 POLICY_NAMES = {L.MMA_F32: 'fp32', L.MMA_BF16: 'bf16', L.MMA_X3: 'x3'}      # the base policies of an Ops
 # Deployment settings of the library, read ONCE here (the library itself reads no environment variable: they travel in the argument
@@ -123,6 +124,11 @@ class Ops:
         # base once per shape (route_attn_x1) and runs it single-fp16 where admitted -- KeepNet's flow Ops (KEEP_AMD_FLOW_PRECISION=f16)
         self.attn_x1 = False
         self._attn_x1_route = {}   # shape key -> True | False
+        # single-fp16 x2-phase Upsample convolutions (L.MMA_X1 | L.CONV_X1_UP2): off by default -- conv() then issues no plan query beyond the
+        # base's.  True: the up2 branch of conv() asks the library once per plan key (route_up2_x1) and runs the call on the hi-only phase twin
+        # (up2_x1_twin) where admitted -- KeepNet's KEEP_AMD_UPSAMPLE_PRECISION=f16
+        self.up2_x1 = False
+        self._up2_x1_route = {}    # base plan key -> the call's X1 Plan | False
 
     def begin_forward(self, device):
         """Zero this forward's bookkeeping words with ONE fill launch: the status word (non-finite logits / tensors, see
@@ -152,6 +158,7 @@ class Ops:
         self.mma = self.attn_mma = mma
         self.set_x1_twin()      # ('f16' re-attaches its twin after every policy change)
         self._attn_x1_route = {}
+        self._up2_x1_route = {}
         if blobx3 is not None and (blob32 is not self._up2_src[0] or blobx3 is not self._up2_src[1]):
             # phase kernels of the Upsample convolutions (up2_twin): derived from THESE blob objects -- a new upload, even one that lands
             # on the same addresses, starts from an empty cache; a policy switch on the same blobs keeps it (captured x3 graphs hold
@@ -252,6 +259,33 @@ class Ops:
             tw = self._up2[key] = (split_x3(w4.reshape(-1, w.shape[-1]), sc).view(-1), 1.0 / sc)
         return tw
 
+    def up2_x1_twin(self, w):
+        """(weight_x3, acc_scale) of the HI-ONLY phase twin of ``w`` for ``upsample = UPSAMPLE_X2_PHASES`` under L.MMA_X1 with
+        L.CONV_X1_UP2: fp16(up2_phase_weights(w) * 2^e) as plain [4, Cout, 3*3, Cin] fp16 bit patterns and 2^-e (``up2_twin``'s scale).
+        Built once per weight tensor (outside any stream capture: ``KeepNet._activate_precision``) and kept with the up2 twins."""
+        key = ('up2_x1', w.data_ptr(), tuple(w.shape))
+        tw = self._up2.get(key)
+        if tw is None:
+            w4 = up2_phase_weights(w)
+            sc = x3_scale_for(float(w4.abs().max()))
+            tw = self._up2[key] = ((w4 * sc).to(torch.float16).view(torch.int16).view(-1), 1.0 / sc)
+        return tw
+
+    def route_up2_x1(self, key, x1_plan):
+        """``up2_x1``: the X1 Plan an x2-phase Upsample call of the x3 base runs under, or None where it stays x3.  The library decides:
+        ``x1_plan()`` is keep_conv2d_plan for the call under L.MMA_X1 with L.CONV_X1_UP2 and the phase x1 twin -- KEEP_EUNSUP is its answer
+        'stay on x3' (anything else is an error) -- asked once per ``key`` (per-image geometry and the reference batch, never N)."""
+        r = self._up2_x1_route.get(key)
+        if r is None:
+            r = False
+            try:
+                r = x1_plan()
+            except L.KeepHipError as e:
+                if '(code -2)' not in str(e):      # anything but KEEP_EUNSUP is an error, not an answer
+                    raise
+            self._up2_x1_route[key] = r
+        return r or None
+
     def ffn_w2_twin(self, w2):
         """(weight_x3, acc_scale) of ``w2`` [C, hidden] for ``keep_gm_ffn_x3``: every group of 16 hidden units in the order
         [0-3, 8-11, 4-7, 12-15] (``ffn_w2_perm``), split with the tensor's own power-of-two scale.  Built once per weight tensor
@@ -341,6 +375,7 @@ class Ops:
         if mma == L.MMA_BF16 and wb is None and self.blob16 is not None:
             wb = self.bf16_twin(w)      # (without a twin the library still accepts the exact-fp32 Cout <= 4 kernel)
         up_mode = L.UPSAMPLE_X2_PHASES if upsample == L.UPSAMPLE_X2_PHASES and upsample is not True else int(bool(upsample))   # (explicit 2: the caller brings phase weights)
+        own_up2 = False              # the phase weights are this Ops' own (up2_twin of ``w``): what ``up2_x1`` may replace by the phase x1 twin
         if (upsample and mma == L.MMA_X3 and wx3 is None and UP2_PHASES and KH == 3 and stride == 1 and pad == 1 and not down
                 and pro is None and pro_act == L.PRO_NONE and act == L.ACT_NONE and aux is None and x2 is None and not reflect
                 and split_k in (None, 1) and H % 8 == 0 and W % 32 == 0 and Cin % 16 == 0 and Cout % 64 == 0 and in_dtype == L.F32
@@ -348,6 +383,7 @@ class Ops:
             # nearest x2 + 3x3 as four 2x2-tap phase convolutions on the source grid: 4 of 9 taps are multiplied
             wx3, x3_acc_scale = self.up2_twin(w)
             up_mode = L.UPSAMPLE_X2_PHASES
+            own_up2 = True
         own_w = wx3 is None          # the weight operand is this Ops' to choose (not a caller's tensor -- the phase weights of an Upsample): what 'f16' may replace by the x1 twin
         if mma == L.MMA_X3 and wx3 is None:
             wx3 = self.x3_twin(w)
@@ -402,6 +438,16 @@ class Ops:
             pro, pro_act, in_dtype = None, L.PRO_NONE, L.BF16
             a = make_args(xin, in_dtype, None, pro_act, odt, sk_req)
             pl = _plan(a, key_of(in_dtype, None, pro_act, odt, sk_req))
+        # ``up2_x1``: the call runs single-fp16 iff the library plans it so under L.CONV_X1_UP2 (route_up2_x1).  The hi-only phase twin has whole
+        # 32-channel weight rows: a depth that is no multiple of 32 has no twin (none is built here, possibly inside a capture, to be refused)
+        if own_up2 and self.up2_x1 and Cin % 32 == 0:
+            twu = self.up2_x1_twin(w)
+            x1 = (L.MMA_X1, twu[0], twu[1], self.flags | L.CONV_X1_UP2)
+            pl1 = self.route_up2_x1(key_of(in_dtype, pro, pro_act, odt, sk_req), lambda: _plan(
+                make_args(xin, in_dtype, pro, pro_act, odt, sk_req, x1), key_of(in_dtype, pro, pro_act, odt, sk_req, x1)))
+            if pl1 is not None:
+                pol, pl = x1, pl1
+                a = make_args(xin, in_dtype, pro, pro_act, odt, sk_req)
         tw1 = self._x1_of(w) if (self.blobx1 is not None and own_w and mma == self.mma == self.x1_base and x2 is None) else None
         if tw1 is not None:      # 'f16': the call runs single-fp16 iff the library plans it so (route_x1)
             x1 = (L.MMA_X1, tw1[0], tw1[1], self.flags | self.x1_flags)

@@ -123,6 +123,17 @@ extern "C" {
  * (KEEP_EUNSUP, keep_last_error names the split) and the host keeps it on KEEP_MMA_X3.  The YOLOv5-face engines' opt-in precision 'f16'
  * (engine/yoloface.py) sets it together with KEEP_CONV_X1_GEMM. */
 #define KEEP_CONV_X1_HALO16 (1u << 15)
+/* KEEP_CONV_X1_UP2: the third admitting bit (additive like the two above: same ABI version, read under KEEP_MMA_X1 only, every other policy
+ * ignores it, and without it every call means what it meant -- KEEP_MMA_X1 with upsample = KEEP_UPSAMPLE_X2_PHASES stays refused).  With it
+ * KEEP_MMA_X1 takes upsample = KEEP_UPSAMPLE_X2_PHASES where the KEEP_MMA_X3 plan of the call takes the streaming phase form (3x3 stride-1
+ * pad-1, H % 8 == 0, W % 32 == 0, Cout % 64 == 0, Cin >= 32, no KEEP_CONV_NO_STREAM) and Cin % 32 == 0: the single-fp16 instantiation of
+ * conv3x3_up2_x3s_kernel, one fp16 MFMA per product, operands rounded once after the range scale.  `weight_x3` is the hi-only phase twin
+ * fp16(up2_phase_weights(w) * 2^e) as plain [4][Cout][3*3][Cin] fp16, 16-byte aligned, x3_acc_scale = 2^-e.  x3_in_amax and the per-image
+ * range scale, bias, residual (in place included), in_ld / out_ld slices, the statistics partials (one per source tile and phase) and
+ * x3_out_amax as in the x3 form; un-split, no scratch.  Anything else -- a prologue, an activation, aux, in2, ln_gamma, split-K, reflection
+ * padding, Cin % 32 != 0, a map or Cout the phase form refuses, a missing twin -- answers KEEP_EUNSUP with keep_last_error naming the reason,
+ * and the host keeps the call on KEEP_MMA_X3.  KeepNet's opt-in KEEP_AMD_UPSAMPLE_PRECISION=f16 (engine/net.py) sets it. */
+#define KEEP_CONV_X1_UP2 (1u << 16)
 /* keep_attention_args.flags (v18) */
 #define KEEP_ATTN_NO_PACK (1u << 0)   /* x3: never pre-pack K / V^T (keep_attention_workspace_bytes answers 0) */
 #define KEEP_ATTN_NO_SFULL2 (1u << 1) /* x3, D = 512: the 128-query kernel instead of the 32-query one */

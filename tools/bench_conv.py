@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """Micro-benchmark of keep_conv2d on the hot layer shapes (through the C-ABI), for rocprofv3 / PMC runs.
-   python tools/bench_conv.py [layer ...]   layers: c64_512 c128_256 up128_512 c256_64 c512_16 lin128"""
+   python tools/bench_conv.py [layer ...]   layers: c64_512 c128_256 up128_512 c256_64 c512_16 lin128
+   X3=1 / X1=1 / F32=1 select the policy (default bf16); UP2=1 runs the up* layers as four phase convolutions (x3 and x1)."""
 import os
 import sys
 import time
@@ -71,6 +72,14 @@ def run(name, mma, in_bf16, iters=int(os.environ.get('ITERS', '20'))):
         kw['residual'] = torch.randn(N, Ho, Wo, Cout, device='cuda')
     if os.environ.get('ACT') == 'gelu':
         kw['act'] = L.ACT_GELU
+    if mma == L.MMA_X1:              # single fp16 (X1=1): the hi-only twin on the streaming form, upsample = 1 for the up* layers ...
+        sc = ops.x3_scale_for(float(w.abs().max()))
+        kw.update(wx3=(w.reshape(-1) * sc).to(torch.float16).view(torch.int16), x3_acc_scale=1.0 / sc)
+    if os.environ.get('UP2') and up and mma == L.MMA_X1:      # ... or (UP2=1) their four phase convolutions on the hi-only phase twin
+        w4 = ops.up2_phase_weights(w)
+        sc4 = ops.x3_scale_for(float(w4.abs().max()))
+        ops.DEFAULT.flags |= L.CONV_X1_UP2
+        kw.update(upsample=L.UPSAMPLE_X2_PHASES, wx3=(w4.reshape(-1) * sc4).to(torch.float16).view(torch.int16), x3_acc_scale=1.0 / sc4)
     if os.environ.get('UP2') and up and mma == L.MMA_X3:      # nearest x2 + 3x3 as four 2x2-tap phase convolutions
         w4 = ops.up2_phase_weights(w)
         sc4 = ops.x3_scale_for(float(w4.abs().max()))
@@ -93,7 +102,7 @@ def run(name, mma, in_bf16, iters=int(os.environ.get('ITERS', '20'))):
     rec, ops.DEFAULT.profile = ops.DEFAULT.profile, None
     ms = sum(r[3].elapsed_time(r[4]) for r in rec) / len(rec)
     fl = rec[0][1]
-    print(f"{name:10s} mma={('f32 ', 'bf16', 'x3  ')[mma]} pre-activated-bf16-input={in_bf16!s:5s} kernel={rec[0][0]:22s} "
+    print(f"{name:10s} mma={('f32 ', 'bf16', 'x3  ', 'x1  ')[mma]} pre-activated-bf16-input={in_bf16!s:5s} kernel={rec[0][0]:22s} "
           f"{ms * 1e3:8.1f} us  {fl / ms / 1e9:7.1f} TFLOP/s (incl. the norm_act pass when present)")
     return y
 
@@ -103,6 +112,10 @@ if __name__ == '__main__':
     if os.environ.get('F32'):
         for n in names:
             run(n, L.MMA_F32, False)
+        sys.exit(0)
+    if os.environ.get('X1'):      # single fp16, raw inputs (the 3x3 layers with Cin % 32 == 0; UP2=1: the up* layers' phase form)
+        for n in names:
+            run(n, L.MMA_X1, False)
         sys.exit(0)
     if os.environ.get('X3'):      # split fp16: plain input, and with the fused GroupNorm affine + swish prologue
         for n in names:

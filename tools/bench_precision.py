@@ -1,4 +1,6 @@
-"""The KEEP network's precision policies side by side: frames/s of 'x3', 'f16' and 'bf16' for 1 and 16 clips per call at T = 20, the
+"""The KEEP network's precision policies side by side: frames/s of 'x3', 'f16' and 'bf16' (and, as extra rows, 'x3+up' / 'f16+up': the same
+base with KEEP_AMD_UPSAMPLE_PRECISION=f16, the single-fp16 Upsample convolutions) for 1 and 16 clips per call at T = 20 -- rounds alternated
+between the policies --, the
 code-index agreement of 'f16' and 'bf16' with 'x3' over all frames, the share of the convolution FLOPs 'f16' runs on single-fp16
 operands (counted from the plans of one forward), and a per-layer A/B of the X1 GroupNorm-swish kernel against the x3 kernel.
 
@@ -26,35 +28,39 @@ from comfyui_keep_amd.engine.net import KeepNet  # noqa: E402
 
 GFLOP_PER_FRAME = 1038.5      # algorithmic FLOPs of one 512 x 512 frame
 X1_FORMS = ('conv3x3_halo_x3s_kernel<0, false, true>', 'conv3x3_halo_x3s_kernel<0, true, true>', 'conv3x3_halo_x3s_kernel<1, true, true>',
-            'conv3x3_halo_x3s_kernel<2, true, true>')
+            'conv3x3_halo_x3s_kernel<2, true, true>', ops.X1_UP2_KERNEL)
 
 
 def network(a):
     W = synth.synth_state_dict(seed=0)
     T = a.frames
     clips = {b: synth.synth_clip(T=T, B=b, seed=1234).cuda() for b in a.clips}
-    idx = {}
-    for prec in a.precisions:
-        net = KeepNet(**DEFAULT_ARCH)
+    idx, nets = {}, {}
+    for prec in a.precisions:      # 'x3+up': base 'x3' with the Upsample knob on
+        net = nets[prec] = KeepNet(**DEFAULT_ARCH)
         net.load_state_dict(W, strict=True)
-        net.to('cuda').eval().set_precision(prec)
-        for b in a.clips:
-            x = clips[b]
+        net.to('cuda').eval().set_precision(prec.split('+')[0]).set_upsample_precision('f16' if prec.endswith('+up') else 'x3')
+    for b in a.clips:              # every round visits every policy once: drift of the box hits all of them alike
+        x = clips[b]
+        for net in nets.values():
             for _ in range(a.warmup):
                 net(x)
-            torch.cuda.synchronize()
-            s = []
-            for _ in range(a.reps):
+        torch.cuda.synchronize()
+        s = {prec: [] for prec in nets}
+        for _ in range(a.reps):
+            for prec, net in nets.items():
                 t0 = time.perf_counter()
                 net(x)
                 torch.cuda.synchronize()
-                s.append(time.perf_counter() - t0)
-            med = statistics.median(s)
-            print(json.dumps({'bench': 'keep_forward', 'precision': prec, 'clips': b, 'T': T, 'median_s': round(med, 4), 'min_s': round(min(s), 4),
-                              'frames_per_s': round(b * T / med, 1), 'reps': a.reps, 'fallbacks': net.x3_fallbacks}), flush=True)
+                s[prec].append(time.perf_counter() - t0)
+        for prec, net in nets.items():
+            med = statistics.median(s[prec])
+            print(json.dumps({'bench': 'keep_forward', 'precision': prec, 'clips': b, 'T': T, 'median_s': round(med, 4), 'min_s': round(min(s[prec]), 4),
+                              'max_s': round(max(s[prec]), 4), 'frames_per_s': round(b * T / med, 1), 'reps': a.reps, 'fallbacks': net.x3_fallbacks}), flush=True)
+    for prec, net in nets.items():
         _, aux = net(clips[max(a.clips)], return_aux=True)
         idx[prec] = aux['indices'].cpu()
-        if prec == 'f16':      # what runs on single fp16: one profiled forward of one clip, FLOPs by the plan's kernel name
+        if prec.split('+')[0] == 'f16':      # what runs on single fp16: one profiled forward of one clip, FLOPs by the plan's kernel name
             net.o.profile = []
             net(clips[min(a.clips)][:1], return_aux=True)
             torch.cuda.synchronize()
@@ -63,13 +69,11 @@ def network(a):
                 by[rec[0]] = by.get(rec[0], 0.0) + rec[1]
             net.o.profile = None
             x1 = sum(v for k, v in by.items() if k in X1_FORMS)
-            print(json.dumps({'bench': 'f16_flop_share', 'x1_gflop_per_frame': round(x1 / T / 1e9, 1),
+            print(json.dumps({'bench': 'f16_flop_share', 'precision': prec, 'x1_gflop_per_frame': round(x1 / T / 1e9, 1),
                               'x3_streaming_gflop_per_frame_left': round(by.get(ops.X3_STREAM_KERNEL, 0.0) / T / 1e9, 1),
                               'conv_gflop_per_frame': round(sum(by.values()) / T / 1e9, 1), 'share_of_conv_flops': round(x1 / sum(by.values()), 4),
                               'share_of_1038.5_gflop': round(x1 / T / 1e9 / GFLOP_PER_FRAME, 4),
                               'by_kernel_gflop_per_frame': {k: round(v / T / 1e9, 2) for k, v in sorted(by.items(), key=lambda kv: -kv[1])}}), flush=True)
-        del net
-        torch.cuda.empty_cache()
     for prec in a.precisions:
         if prec != 'x3' and 'x3' in idx:
             agree = (idx[prec] == idx['x3']).float()
@@ -116,7 +120,7 @@ def per_layer(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--precisions', nargs='+', default=['x3', 'f16', 'bf16'])
+    ap.add_argument('--precisions', nargs='+', default=['x3', 'f16', 'bf16'], help="base policies; 'x3+up' / 'f16+up' add the Upsample knob")
     ap.add_argument('--clips', type=int, nargs='+', default=[1, 16])
     ap.add_argument('--frames', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=2)
