@@ -126,8 +126,15 @@ _lib = None
 _device_checked = set()
 
 
+EINVAL, EUNSUP = -1, -2      # KEEP_EINVAL / KEEP_EUNSUP of include/keep_hip.h
+
+
 class KeepHipError(RuntimeError):
-    pass
+    """``code``: the library's return code (EINVAL, EUNSUP, ...), None where no call returned one (library not found, ABI mismatch)."""
+
+    def __init__(self, msg, code=None):
+        super().__init__(msg)
+        self.code = code
 
 
 def load(check_device=True):
@@ -166,7 +173,7 @@ def load(check_device=True):
         if dev not in _device_checked:
             rc = _lib.keep_device_ok(dev)
             if rc != 0:
-                raise KeepHipError(_lib.keep_last_error().decode())
+                raise KeepHipError(_lib.keep_last_error().decode(), code=rc)
             _device_checked.add(dev)
     return _lib
 
@@ -181,7 +188,7 @@ def _stream():
 
 def _check(rc, what):
     if rc != 0:
-        raise KeepHipError(f"{what} failed (code {rc}): {_lib.keep_last_error().decode()}")
+        raise KeepHipError(f"{what} failed (code {rc}): {_lib.keep_last_error().decode()}", code=rc)
 
 
 def call(name, *args):
@@ -222,12 +229,12 @@ def attn_args(**kw):
 
 def attention_x1_plan(**kw):
     """The library's answer to `this call under MMA_X1 | ATTN_X1`: the scratch bytes the single-fp16 form needs.  A refusal
-    (keep_attention_workspace_bytes = -1, what keep_attention answers KEEP_EUNSUP to) raises KeepHipError with `(code -2)` and the
+    (keep_attention_workspace_bytes = -1, what keep_attention answers KEEP_EUNSUP to) raises KeepHipError with ``code == EUNSUP`` and the
     library's reason, like keep_conv2d_plan does; needs no device."""
     a = attn_args(**dict(kw, mma=MMA_X1, flags=int(kw.get('flags', 0)) | ATTN_X1))
     need = attention_workspace_bytes(a)
     if need < 0:
-        raise KeepHipError(f"keep_attention plan failed (code -2): {_lib.keep_last_error().decode()}")
+        raise KeepHipError(f"keep_attention plan failed (code -2): {_lib.keep_last_error().decode()}", code=EUNSUP)
     return need
 
 

@@ -63,6 +63,7 @@ FLOW_PRECISION_ENV = 'KEEP_AMD_FLOW_PRECISION'
 # where the library admits them (KEEP_CONV_X1_UP2); needs an x3-grade base
 UPSAMPLE_PRECISIONS = ('x3', 'f16')
 UPSAMPLE_PRECISION_ENV = 'KEEP_AMD_UPSAMPLE_PRECISION'
+KNOB_OFF = {'flow_precision': 'x3', 'upsample_precision': 'x3'}      # the opt-in knobs beside `precision`, each with its `as if it did not exist`
 
 
 ROCTX = os.environ.get('KEEP_AMD_ROCTX', '0') == '1'      # per-stage roctx ranges (rocprofv3 --marker-trace / --kernel-trace timelines)
@@ -238,12 +239,6 @@ class KeepNet:
                 res *= 2
         return names
 
-    def _up2_x1_bytes(self):
-        """Device bytes of the hi-only phase twins: four phase kernels of 2 bytes per weight for every name of ``up2_x1_names``."""
-        if self._index is None:
-            return 0
-        return sum(8 * int(np.prod(self._index[n][1])) for n in self.up2_x1_names())
-
     def _activate_upsample_precision(self):
         """``self.o.up2_x1`` follows the knob; the hi-only phase twins are built here, never inside a stream capture."""
         if self.upsample_precision != 'f16':
@@ -259,16 +254,11 @@ class KeepNet:
     @staticmethod
     def flow_x1_names(index):
         """Names of the flow twin's tensors: `flownet.*` matrix weights with Cin % 32 == 0 -- packed 3x3 [Cout,3,3,Cin], and 1x1 / linear
-        [Cout,Cin] -- disjoint from ``_make_x1``'s list by construction (that one excludes `flownet.`).  The two stride-2 1x1 shortcut
+        [Cout,Cin] -- disjoint from ``x1_names`` by construction (that one excludes `flownet.`).  The two stride-2 1x1 shortcut
         convolutions of the backbone (`downsample.0`) have no twin and stay x3: their launch shapes measured 0.99 x and 1.01 x under
         single fp16 (bound by the strided gather, not by the products), and a shape that is not faster is not routed."""
         return [n for n, (_, shape) in index.items() if n.startswith('flownet.') and shape[-1] % 32 == 0 and '.downsample.' not in n
                 and ((len(shape) == 4 and shape[1] == 3 and shape[2] == 3) or len(shape) == 2)]
-
-    def _make_x1_flow(self):
-        self._dev_blobx1f, self._x1f_ranges = ops.make_x1_blob(self._dev_blob, self._index, self.w, self.flow_x1_names(self._index))
-        x3 = {(a, b): s for a, b, s in self._x3_scales}
-        assert all(x3.get((a, b)) == s for a, b, s in self._x1f_ranges), 'x1 and x3 twins must share their per-tensor scales'
 
     def _make_x3(self):
         """Split-fp16 twin of every matrix weight in the blob (2-D+ tensors whose reduction axis is a multiple of 16)."""
@@ -282,25 +272,36 @@ class KeepNet:
 
     @staticmethod
     def x1_names(index):
-        """Names of the 'f16' twin's tensors (``_make_x1``)."""
+        """Names of the 'f16' twin's tensors: every 3x3 convolution weight a streaming kernel could read (packed [Cout,3,3,Cin], Cin % 32 == 0),
+        GMFlow excluded (its flows feed a warp: it stays x3 unless KEEP_AMD_FLOW_PRECISION=f16 opts its feature layers in, ``set_flow_precision``)."""
         return [n for n, (_, shape) in index.items() if len(shape) == 4 and shape[1] == 3 and shape[2] == 3 and shape[-1] % 32 == 0
                 and not n.startswith('flownet.')]
 
-    def _make_x1(self):
-        """'f16': hi-only twin of every 3x3 convolution weight a streaming kernel could read (packed [Cout,3,3,Cin], Cin % 32 == 0),
-        GMFlow excluded (its flows feed a warp: it stays x3 unless KEEP_AMD_FLOW_PRECISION=f16 opts its feature layers in, ``set_flow_precision``).  Same per-tensor scales as the x3 twin (one scale table serves both)."""
-        self._dev_blobx1, self._x1_ranges = ops.make_x1_blob(self._dev_blob, self._index, self.w, self.x1_names(self._index))
+    def _make_x1(self, names):
+        """(hi-only fp16 twin, its ranges) of the tensors ``names`` (``x1_names``: 'f16'; ``flow_x1_names``: the flow knob) -- with the
+        per-tensor scales of the x3 twin (one scale table serves both)."""
+        blob, ranges = ops.make_x1_blob(self._dev_blob, self._index, self.w, names)
         x3 = {(a, b): s for a, b, s in self._x3_scales}
-        assert all(x3.get((a, b)) == s for a, b, s in self._x1_ranges), 'x1 and x3 twins must share their per-tensor scales'
+        assert all(x3.get((a, b)) == s for a, b, s in ranges), 'x1 and x3 twins must share their per-tensor scales'
+        return blob, ranges
+
+    def _twins(self, precision):
+        """twin -> (device bytes, already built?) of every weight twin ``precision`` holds beside the packed fp32 blob under the current
+        knobs: the one table ``twin_bytes`` and ``clips_per_call`` read."""
+        n = int(self._dev_blob.numel()) if self._dev_blob is not None else (0 if self._blob is None else int(self._blob.size))
+        on = precision in X3_GRADE
+        up = 0 if self._index is None else sum(8 * int(np.prod(self._index[m][1])) for m in self.up2_x1_names())      # four phase kernels, 2 bytes per weight
+        rows = (('bf16', precision == 'bf16', 2 * n, self._dev_blob16 is not None),
+                ('x3', on, 4 * n, self._dev_blobx3 is not None),
+                ('x1', precision == 'f16', 2 * n, self._dev_blobx1 is not None),      # hi-only: 2 bytes per blob element
+                ('flow', on and self.flow_precision == 'f16', 2 * n, self._dev_blobx1f is not None),      # likewise the flownet twin
+                ('up2', on and self.upsample_precision == 'f16', up, bool(self.o.up2_x1)))      # the hi-only phase twins of ``up2_x1_names``
+        return {k: (b, built) for k, held, b, built in rows if held}
 
     def twin_bytes(self, precision=None):
         """Device bytes of the weight twins ``precision`` (default: the current one) holds beside the packed fp32 blob -- what
         ``clips_per_call`` takes off the free memory while they are not built yet."""
-        precision = self.precision if precision is None else precision
-        n = int(self._dev_blob.numel()) if self._dev_blob is not None else (0 if self._blob is None else int(self._blob.size))
-        flow = 2 * n if (self.flow_precision == 'f16' and precision in X3_GRADE) else 0      # the flow twin: 2 bytes per blob element
-        up = self._up2_x1_bytes() if (self.upsample_precision == 'f16' and precision in X3_GRADE) else 0      # the hi-only phase twins
-        return {'bf16': 2 * n, 'x3': 4 * n, 'f16': 4 * n + 2 * n}.get(precision, 0) + flow + up
+        return sum(b for b, _ in self._twins(self.precision if precision is None else precision).values())
 
     def _activate_flow_precision(self):
         """``self.of``: self.o, or (flow 'f16') the second Ops on x3 with the flownet x1 twin -- built here, never inside a stream capture."""
@@ -310,7 +311,7 @@ class KeepNet:
         if self.precision not in X3_GRADE:
             raise ValueError(f"{FLOW_PRECISION_ENV}=f16 needs the base precision 'x3' or 'f16', not {self.precision!r}")
         if self._dev_blobx1f is None:
-            self._make_x1_flow()
+            self._dev_blobx1f, self._x1f_ranges = self._make_x1(self.flow_x1_names(self._index))
         of = self._of = self._of or ops.Ops()
         if not (of.mma == L.MMA_X3 and of.blob32 is self._dev_blob and of.blobx3 is self._dev_blobx3 and of.blobx1 is self._dev_blobx1f):
             of.set_precision(L.MMA_X3, self._dev_blob, None, self._dev_blobx3, 1.0, x3_scales=self._x3_scales)
@@ -344,7 +345,7 @@ class KeepNet:
                         self.o.up2_twin(self.w[f'generator.blocks.{i}.conv.weight'])
             if self.precision == 'f16':      # the x1 twin: built here, never inside a stream capture
                 if self._dev_blobx1 is None:
-                    self._make_x1()
+                    self._dev_blobx1, self._x1_ranges = self._make_x1(self.x1_names(self._index))
                 self.o.set_x1_twin(self._dev_blobx1, self._x1_ranges, flags=0, base_kernel=ops.X3_STREAM_KERNEL)
         else:
             self.o.set_precision(L.MMA_F32, self._dev_blob, None)
@@ -416,14 +417,13 @@ class KeepNet:
         policy, the plans' reference batch, the kernel-selection overrides and the hipGraph mode.  ``GpuPool.run`` compares it with
         what the workers were last told and re-configures them when it moved (``set_precision`` after the pool came up)."""
         return {'precision': self.precision, 'plan_ref_images': int(self.o.plan_ref_images), 'flags': int(self.o.flags),
-                'attn_flags': int(self.o.attn_flags), 'graph_mode': str(self.graph_mode), 'flow_precision': self.flow_precision,
-                'upsample_precision': self.upsample_precision}
+                'attn_flags': int(self.o.attn_flags), 'graph_mode': str(self.graph_mode), **{k: getattr(self, k) for k in KNOB_OFF}}
 
     def apply_pool_config(self, cfg):
         """Worker side of ``pool_config``."""
         self.set_precision(cfg['precision'])
-        self.set_flow_precision(cfg.get('flow_precision', 'x3'))
-        self.set_upsample_precision(cfg.get('upsample_precision', 'x3'))
+        for k, off in KNOB_OFF.items():      # (a root without the knob: as if it did not exist)
+            getattr(self, 'set_' + k)(cfg.get(k, off))
         self.o.plan_ref_images, self.o.flags, self.o.attn_flags = int(cfg['plan_ref_images']), int(cfg['flags']), int(cfg['attn_flags'])
         self.graph_mode = str(cfg['graph_mode'])
 
@@ -919,8 +919,8 @@ class KeepNet:
         logging.getLogger('ComfyUI-KEEP').warning(
             "x3 precision policy left the fp16 operand range on this batch (status %d); re-running it on the f32 kernels", bits)
         self.x3_fallbacks += 1
-        policy, flow_policy, up_policy = self.precision, self.flow_precision, self.upsample_precision      # 'x3' or 'f16' (and the two knobs): restored after the re-run
-        self.precision, self.flow_precision, self.upsample_precision = 'fp32', 'x3', 'x3'
+        knobs = {k: getattr(self, k) for k in ('precision', *KNOB_OFF)}      # 'x3' or 'f16', and the opt-in knobs: restored after the re-run
+        self.__dict__.update(KNOB_OFF, precision='fp32')
         try:
             self._activate_precision()
             res = None                               # (callers drop their reference to the x3 result before calling: the re-run needs the room)
@@ -933,7 +933,7 @@ class KeepNet:
                                       for b0 in range(0, B, part)], 0)
             return self._forward(x, B, T, H, Wd, force_indices, return_aux, force_flows)
         finally:
-            self.precision, self.flow_precision, self.upsample_precision = policy, flow_policy, up_policy
+            self.__dict__.update(knobs)
             self._activate_precision()
 
     def _forward_graphed(self, x, B, T, H, Wd):
@@ -1124,14 +1124,11 @@ class KeepNet:
             free += torch.cuda.memory_reserved(self.device) - torch.cuda.memory_allocated(self.device)   # cached blocks are reusable
         except Exception:
             free = 64e9
-        n2 = 2 * (int(self._dev_blob.numel()) if self._dev_blob is not None else (0 if self._blob is None else int(self._blob.size)))
-        flow = n2 if (self.flow_precision == 'f16' and self.precision in X3_GRADE) else 0
-        if self.precision == 'f16' and self._dev_blobx1 is None:      # the x1 twin is built at the first call: its bytes are not free
-            free -= (self.twin_bytes('f16') - flow) - (0 if self._dev_blobx3 is None else self.twin_bytes('x3') - flow)
-        if flow and self._dev_blobx1f is None:      # likewise the flow twin
-            free -= flow
-        if self.upsample_precision == 'f16' and self.precision in X3_GRADE and not self.o.up2_x1:      # likewise the hi-only phase twins
-            free -= self._up2_x1_bytes()
+        twins = self._twins(self.precision)
+        todo = {k: b for k, (b, built) in twins.items() if not built}      # twins built at the first call: their bytes are not free
+        free -= sum(todo.get(k, 0) for k in ('x1', 'flow', 'up2'))
+        if 'x1' in todo and 'x3' in todo:      # 'f16' before anything is built: the x3 twin it rides on as well -- and, as ever, the phase twins with it
+            free -= todo['x3'] + twins.get('up2', (0,))[0]
         return max(1, min(cap, int(0.8 * free / (per_frame * max(T, 1)))))
 
     def run_clips(self, clips, need_upscale=False, max_b=None):

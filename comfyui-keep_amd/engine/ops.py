@@ -112,23 +112,23 @@ class Ops:
         self.attn_flags = 0
         self.plan_ref_images = PLAN_REF_IMAGES
         # 'f16': a hi-only twin (make_x1_blob) attached to the base policy by set_x1_twin -- conv() substitutes L.MMA_X1 in every call of
-        # the base policy whose weight has such a twin and whose X1 plan the library admits (route_x1).  None: the plain base policy.
+        # the base policy whose weight has such a twin and whose X1 plan the library admits (_route).  None: the plain base policy.
         self.blobx1 = None
         self._x1_table = None      # ([first element], [(first, one past the last, 2^-e)]) of the tensors blobx1 holds, sorted
-        self._x1_route = {}        # base plan key -> the call's X1 Plan | False: one keep_conv2d_plan query per shape
+        # what the library answered to `this call under L.MMA_X1?` (_route), per rule: the blob twin and the phase twin (``up2_x1``): base
+        # plan key -> the call's X1 Plan | False; ``attn_x1``: shape key -> True | False
+        self._x1_route, self._up2_x1_route, self._attn_x1_route = {}, {}, {}
         self.x1_flags = L.CONV_X1_GEMM      # opt-in form bits OR-ed into the X1 plan query and launch
         self.x1_base = L.MMA_X3             # the policy a call without a twin, or one the library refuses, stays on
         self.x1_base_kernel = None          # restriction: substitute only where the base plan is this kernel, un-split (None: everywhere)
         self.census = None         # when a dict: kernel name (plan string) -> launches, counted by conv() (tests, tools/bench_precision.py)
         # single-fp16 attention (L.MMA_X1 | L.ATTN_X1): off by default.  True: attention() asks the library about every call of the x3
-        # base once per shape (route_attn_x1) and runs it single-fp16 where admitted -- KeepNet's flow Ops (KEEP_AMD_FLOW_PRECISION=f16)
+        # base once per shape (_route) and runs it single-fp16 where admitted -- KeepNet's flow Ops (KEEP_AMD_FLOW_PRECISION=f16)
         self.attn_x1 = False
-        self._attn_x1_route = {}   # shape key -> True | False
         # single-fp16 x2-phase Upsample convolutions (L.MMA_X1 | L.CONV_X1_UP2): off by default -- conv() then issues no plan query beyond the
-        # base's.  True: the up2 branch of conv() asks the library once per plan key (route_up2_x1) and runs the call on the hi-only phase twin
+        # base's.  True: the up2 branch of conv() asks the library once per plan key (_route) and runs the call on the hi-only phase twin
         # (up2_x1_twin) where admitted -- KeepNet's KEEP_AMD_UPSAMPLE_PRECISION=f16
         self.up2_x1 = False
-        self._up2_x1_route = {}    # base plan key -> the call's X1 Plan | False
 
     def begin_forward(self, device):
         """Zero this forward's bookkeeping words with ONE fill launch: the status word (non-finite logits / tensors, see
@@ -157,8 +157,7 @@ class Ops:
         self._x3_table = ([a for a, _, _ in x3_scales], list(x3_scales)) if x3_scales else None
         self.mma = self.attn_mma = mma
         self.set_x1_twin()      # ('f16' re-attaches its twin after every policy change)
-        self._attn_x1_route = {}
-        self._up2_x1_route = {}
+        self._forget_routes(self._x1_route, self._up2_x1_route, self._attn_x1_route)
         if blobx3 is not None and (blob32 is not self._up2_src[0] or blobx3 is not self._up2_src[1]):
             # phase kernels of the Upsample convolutions (up2_twin): derived from THESE blob objects -- a new upload, even one that lands
             # on the same addresses, starts from an empty cache; a policy switch on the same blobs keeps it (captured x3 graphs hold
@@ -180,7 +179,7 @@ class Ops:
         if blobx1 is not None:
             rows = sorted((int(a), int(b), float(s)) for a, b, s in ranges)
             self._x1_table = ([a for a, _, _ in rows], rows)
-        self._x1_route = {}
+        self._forget_routes(self._x1_route)
 
     def _x1_of(self, w):
         """(hi-only fp16 copy, accumulator scale 2^-e) of an fp32 weight view, or None when no twin is attached or the tensor has none
@@ -196,40 +195,29 @@ class Ops:
         tw = self._x1_of(w)
         return None if tw is None else tw[0]
 
-    def route_x1(self, key, base_plan, x1_plan):
-        """'f16': the X1 Plan a convolution call of the base policy runs under, or None where it stays on the base.  The library decides:
-        ``x1_plan()`` is keep_conv2d_plan for the call under L.MMA_X1 with ``x1_flags`` -- KEEP_EUNSUP is its answer 'no kernel of this
-        grade' (anything else is an error) -- asked once per ``key`` and only where ``x1_base_kernel`` allows (KeepNet: the un-split x3
-        streaming 3x3 kernel, so the GEMM forms, the split-K forms, the phase upsample and im2col shapes stay x3 unasked).  Both plans
-        follow the per-image geometry and the fixed reference batch: a route never depends on a clip's or frame's batch-mates.
-        Attention never comes here: ``attn_mma`` is the base's."""
-        r = self._x1_route.get(key)
-        if r is None:
-            r = False
-            if self.x1_base_kernel is None or (base_plan.kernel == self.x1_base_kernel and base_plan.split_k == 1):
-                try:
-                    r = x1_plan()
-                except L.KeepHipError as e:
-                    if '(code -2)' not in str(e):      # anything but KEEP_EUNSUP is an error, not an answer
-                        raise
-            self._x1_route[key] = r
-        return r or None
-
-    def route_attn_x1(self, key, x1_plan):
-        """``attn_x1``: does this attention call of the x3 base run under L.MMA_X1 | L.ATTN_X1?  The library decides: ``x1_plan()`` is
-        ``hiplib.attention_x1_plan`` for the call -- KEEP_EUNSUP is its answer 'stay on x3' (anything else is an error) -- asked once
-        per ``key``.  The key holds the per-image shape, the alignment classes and the flags, never the batch."""
-        r = self._attn_x1_route.get(key)
+    @staticmethod
+    def _route(routes, key, query):
+        """The single-fp16 substitution rule of every call site: what the library answered to `this call under L.MMA_X1?`, asked once
+        per ``key`` of ``routes`` (``_x1_route``, ``_up2_x1_route``: ``query()`` is keep_conv2d_plan under L.MMA_X1 with the rule's twin and flags,
+        the answer the call's X1 Plan; ``_attn_x1_route``: ``hiplib.attention_x1_plan``, the answer True).  KEEP_EUNSUP is the library's answer 'no kernel of
+        this grade, stay on the base': False, cached like any other.  Every other failure is an error: it propagates and nothing is cached.
+        The keys hold the per-image geometry, the alignment classes, the flags and the reference batch, never N: a route never depends on
+        a clip's or frame's batch-mates."""
+        r = routes.get(key)
         if r is None:
             try:
-                x1_plan()
-                r = True
+                r = query()
             except L.KeepHipError as e:
-                if '(code -2)' not in str(e):      # anything but KEEP_EUNSUP is an error, not an answer
+                if e.code != L.EUNSUP:
                     raise
                 r = False
-            self._attn_x1_route[key] = r
+            routes[key] = r
         return r
+
+    @staticmethod
+    def _forget_routes(*routes):
+        for r in routes:
+            r.clear()
 
     # ------------------------------------------------------------------ weight twins
     def _blob_off(self, w):
@@ -270,21 +258,6 @@ class Ops:
             sc = x3_scale_for(float(w4.abs().max()))
             tw = self._up2[key] = ((w4 * sc).to(torch.float16).view(torch.int16).view(-1), 1.0 / sc)
         return tw
-
-    def route_up2_x1(self, key, x1_plan):
-        """``up2_x1``: the X1 Plan an x2-phase Upsample call of the x3 base runs under, or None where it stays x3.  The library decides:
-        ``x1_plan()`` is keep_conv2d_plan for the call under L.MMA_X1 with L.CONV_X1_UP2 and the phase x1 twin -- KEEP_EUNSUP is its answer
-        'stay on x3' (anything else is an error) -- asked once per ``key`` (per-image geometry and the reference batch, never N)."""
-        r = self._up2_x1_route.get(key)
-        if r is None:
-            r = False
-            try:
-                r = x1_plan()
-            except L.KeepHipError as e:
-                if '(code -2)' not in str(e):      # anything but KEEP_EUNSUP is an error, not an answer
-                    raise
-            self._up2_x1_route[key] = r
-        return r or None
 
     def ffn_w2_twin(self, w2):
         """(weight_x3, acc_scale) of ``w2`` [C, hidden] for ``keep_gm_ffn_x3``: every group of 16 hidden units in the order
@@ -350,6 +323,7 @@ class Ops:
         on (the x1 twin's own table where 'f16' routes it to L.MMA_X1).
         ``ln=(gamma, beta, eps)``: LayerNorm over the output channels in the epilogue, BEFORE the residual is added (x3 GEMM form,
         Cout == 128, rows % 128 == 0: ``ln_fusable``); the library refuses anything else."""
+        # -- geometry
         N, H, W, ld = x.shape
         Cout = w.shape[0]
         Cin = ld if cin is None else cin
@@ -370,6 +344,7 @@ class Ops:
             assert out_hw[0] <= Ho and out_hw[1] <= Wo
             Ho, Wo = out_hw
         M = N * Ho * Wo
+        # -- operands and policy
         mma = self.mma if mma is None else mma
         in_dtype = L.BF16 if x.dtype == torch.bfloat16 else L.F32
         if mma == L.MMA_BF16 and wb is None and self.blob16 is not None:
@@ -401,34 +376,33 @@ class Ops:
         if ((mma == L.MMA_X3 and (wx3 is not None or (Cin <= 3 and KH == 3))) or mma == L.MMA_X1) and probes:   # (RGB convs split fp32 weights in-kernel)
             in_amax = in_range()
         out_ld = (Cout if out is None else out.shape[-1]) if out_ld is None else out_ld
-        pol = (mma, wx3, float(x3_acc_scale), self.flags)      # what make_args / key_of launch under: (policy, weight_x3, x3_acc_scale, flags)
+        # -- plan: re-derived (``planned``) after the bf16 pre-normalisation, the single-fp16 swap and a refused bf16 output
+        sk_req = 0 if split_k is None else int(split_k)
+        odt = L.BF16 if want_bf16_out else L.F32
+        pol = (mma, wx3, float(x3_acc_scale), self.flags)      # what the call launches under: (policy, weight_x3, x3_acc_scale, flags)
 
-        def make_args(inp, dtype, pro_t, pro_a, odt, sk, p=None):
+        def planned(p=None):
+            """(arguments, Plan, plan key) of the call as these locals stand NOW, under ``p`` (default: ``pol``)."""
             mma, wx3, acc_scale, flags = p or pol
-            return L.conv_args(
-                inp=inp, weight=w, bias=bias, out=out, pro_scale=None if pro_t is None else pro_t[0],
-                pro_shift=None if pro_t is None else pro_t[1], residual=residual, aux=aux, workspace=None,
+            a = L.conv_args(
+                inp=xin, weight=w, bias=bias, out=out, pro_scale=None if pro is None else pro[0],
+                pro_shift=None if pro is None else pro[1], residual=residual, aux=aux, workspace=None,
                 N=N, H=H, W=W, Cin=Cin, Cout=Cout, KH=KH, KW=KW, stride=stride, pad_t=pad_t, pad_l=pad_l, Ho=Ho, Wo=Wo,
                 in_ld=ld, out_ld=out_ld, res_ld=0 if residual is None else residual.shape[-1],
-                upsample=up_mode, pro_act=pro_a, epi_act=act, aux_w=float(aux_w), split_k=sk, dtype=dtype,
+                upsample=up_mode, pro_act=pro_act, epi_act=act, aux_w=float(aux_w), split_k=sk_req, dtype=in_dtype,
                 mma=mma, weight_bf16=wb if mma == L.MMA_BF16 else None, stats_out=None, stats_P=0,
                 bk256=int(USE_BK256), out_dtype=odt, weight_x3=wx3 if mma in (L.MMA_X3, L.MMA_X1) else None,
                 x3_acc_scale=acc_scale, x3_in_amax=in_amax, x3_out_amax=None,
                 in2=x2, in2_cin1=0 if x2 is None else ld, pad_mode=L.PAD_REFLECT if reflect else L.PAD_ZERO,
                 ln_gamma=None if ln is None else ln[0], ln_beta=None if ln is None else ln[1],
                 ln_eps=0.0 if ln is None else float(ln[2]), flags=flags, plan_ref_images=self.plan_ref_images)
+            key = (N, H, W, ld, Cin, Cout, KH, stride, pad_t, pad_l, Ho, Wo, out_ld, up_mode, pro_act, act, in_dtype, mma,
+                   odt, sk_req, pro is not None, residual is not None, 0 if residual is None else residual.shape[-1],
+                   aux is not None, bias is not None, in_off % 8, wx3 is not None, USE_BK256, x2 is not None, bool(reflect),
+                   ln is not None, flags, self.plan_ref_images)
+            return a, _plan(a, key), key
 
-        def key_of(dtype, pro_t, pro_a, odt, sk, p=None):
-            mma, wx3, _, flags = p or pol
-            return (N, H, W, ld, Cin, Cout, KH, stride, pad_t, pad_l, Ho, Wo, out_ld, up_mode, pro_a, act, dtype, mma,
-                    odt, sk, pro_t is not None, residual is not None, 0 if residual is None else residual.shape[-1],
-                    aux is not None, bias is not None, in_off % 8, wx3 is not None, USE_BK256, x2 is not None, bool(reflect),
-                    ln is not None, flags, self.plan_ref_images)
-
-        sk_req = 0 if split_k is None else int(split_k)
-        odt = L.BF16 if want_bf16_out else L.F32
-        a = make_args(xin, in_dtype, pro, pro_act, odt, sk_req)
-        pl = _plan(a, key_of(in_dtype, pro, pro_act, odt, sk_req))
+        a, pl, key = planned()
         if (pl.wants_bf16_input and in_off == 0 and Cin == ld and N * H * W >= HALO_PRENORM_MINPIX):
             # bf16 policy, 3x3 halo geometry with a prologue: normalise + activate once per element into a bf16 tensor
             x16 = torch.empty((N, H, W, ld), dtype=torch.bfloat16, device=x.device)
@@ -436,32 +410,33 @@ class Ops:
                    N, H * W, ld, pro_act, in_dtype)
             x = xin = x16
             pro, pro_act, in_dtype = None, L.PRO_NONE, L.BF16
-            a = make_args(xin, in_dtype, None, pro_act, odt, sk_req)
-            pl = _plan(a, key_of(in_dtype, None, pro_act, odt, sk_req))
-        # ``up2_x1``: the call runs single-fp16 iff the library plans it so under L.CONV_X1_UP2 (route_up2_x1).  The hi-only phase twin has whole
-        # 32-channel weight rows: a depth that is no multiple of 32 has no twin (none is built here, possibly inside a capture, to be refused)
-        if own_up2 and self.up2_x1 and Cin % 32 == 0:
-            twu = self.up2_x1_twin(w)
-            x1 = (L.MMA_X1, twu[0], twu[1], self.flags | L.CONV_X1_UP2)
-            pl1 = self.route_up2_x1(key_of(in_dtype, pro, pro_act, odt, sk_req), lambda: _plan(
-                make_args(xin, in_dtype, pro, pro_act, odt, sk_req, x1), key_of(in_dtype, pro, pro_act, odt, sk_req, x1)))
-            if pl1 is not None:
-                pol, pl = x1, pl1
-                a = make_args(xin, in_dtype, pro, pro_act, odt, sk_req)
-        tw1 = self._x1_of(w) if (self.blobx1 is not None and own_w and mma == self.mma == self.x1_base and x2 is None) else None
-        if tw1 is not None:      # 'f16': the call runs single-fp16 iff the library plans it so (route_x1)
-            x1 = (L.MMA_X1, tw1[0], tw1[1], self.flags | self.x1_flags)
-            pl1 = self.route_x1(key_of(in_dtype, pro, pro_act, odt, sk_req), pl, lambda: _plan(
-                make_args(xin, in_dtype, pro, pro_act, odt, sk_req, x1), key_of(in_dtype, pro, pro_act, odt, sk_req, x1)))
-            if pl1 is not None:
+            a, pl, key = planned()
+        # The call's ONE single-fp16 candidate (its routes, weight_x3, x3_acc_scale, flags to OR in); it runs single-fp16 iff the library plans it so
+        # (_route).  ``up2_x1``: the hi-only phase twin, when the phase weights are this Ops' own -- it has whole 32-channel weight rows: a
+        # depth that is no multiple of 32 has no twin (none is built here, possibly inside a capture, to be refused).  Otherwise 'f16': the
+        # blob twin of ``w``, only where ``x1_base_kernel`` allows (KeepNet: the un-split x3 streaming 3x3 kernel, so the GEMM forms, the
+        # split-K forms and im2col shapes stay x3 unasked).  The two exclude each other: an Ops-owned phase twin has set ``wx3``.
+        cand = None
+        if own_up2:
+            if self.up2_x1 and Cin % 32 == 0:
+                cand = (self._up2_x1_route, *self.up2_x1_twin(w), L.CONV_X1_UP2)
+        elif (self.blobx1 is not None and own_w and mma == self.mma == self.x1_base and x2 is None
+              and (self.x1_base_kernel is None or (pl.kernel == self.x1_base_kernel and pl.split_k == 1))):
+            tw1 = self._x1_of(w)
+            if tw1 is not None:
+                cand = (self._x1_route, *tw1, self.x1_flags)
+        if cand is not None:
+            x1 = (L.MMA_X1, cand[1], cand[2], self.flags | cand[3])
+            pl1 = self._route(cand[0], key, lambda: planned(x1)[1])
+            if pl1:
                 if in_amax is None and probes:      # (a base that reads no range -- exact f32 -- left the probe to this point)
                     in_amax = in_range()
-                pol, pl = x1, pl1
-                a = make_args(xin, in_dtype, pro, pro_act, odt, sk_req)
+                pol = x1
+                a, pl = planned()[0], pl1
         if want_bf16_out and not pl.out_bf16_ok:
             want_bf16_out, odt = False, L.F32
-            a = make_args(xin, in_dtype, pro, pro_act, odt, sk_req)
-            pl = _plan(a, key_of(in_dtype, pro, pro_act, odt, sk_req))
+            a, pl, key = planned()
+        # -- launch
         if out is None:
             out = torch.empty((N, Ho, Wo, Cout), dtype=torch.bfloat16 if want_bf16_out else torch.float32, device=x.device)
             a.out = out.data_ptr()
@@ -640,7 +615,7 @@ class Ops:
         if self.attn_x1 and mma == self.attn_mma == L.MMA_X3 and in_dtype == L.F32:
             key = (H, Lq, Lk, D, Dv, mode, ksplit, img_h, img_w, shift, tuple(s % 4 for s in (*q_str, *k_str, *v_str)),
                    tuple(t.data_ptr() % 16 for t in (q, k, v)), amax[0] is not None, self.attn_flags)
-            if self.route_attn_x1(key, lambda: L.attention_x1_plan(**kw)):      # single fp16 where the library admits it, x3 otherwise
+            if self._route(self._attn_x1_route, key, lambda: L.attention_x1_plan(**kw) is not None):      # single fp16 where the library admits it, x3 otherwise
                 kw.update(mma=L.MMA_X1, flags=self.attn_flags | L.ATTN_X1)
         L.attention(**kw)
         if DEBUG_SYNC:

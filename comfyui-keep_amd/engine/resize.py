@@ -22,7 +22,7 @@ def lanczos4_tables(S, D):
     coef = np.empty((D, 8), np.int16)
     rc = lib.keep_lanczos4_tables(int(S), int(D), ofs.ctypes.data_as(C.c_void_p), coef.ctypes.data_as(C.c_void_p))
     if rc != 0:
-        raise L.KeepHipError(f"keep_lanczos4_tables failed (code {rc}): {lib.keep_last_error().decode()}")
+        raise L.KeepHipError(f"keep_lanczos4_tables failed (code {rc}): {lib.keep_last_error().decode()}", code=rc)
     return ofs, coef
 
 

@@ -95,32 +95,6 @@ def test_unknown_precision_string_raises(backbone):
     assert RF.EngineRetinaFace(RF.RetinaFaceEngine(sd, precision='f16')).engine.precision == 'f16'
 
 
-def test_unrestricted_rule_asks_the_library_once_per_shape():
-    """The detectors' rule (no base-plan restriction): whatever the base plan is, the library's X1 plan decides."""
-    o = ops.Ops()
-    assert o.x1_base_kernel is None and o.x1_base == L.MMA_X3
-    calls = []
-    base, x1 = object(), object()
-
-    def admit():
-        calls.append(1)
-        return x1
-
-    def refuse():
-        calls.append(1)
-        raise L.KeepHipError("keep_conv2d_plan failed (code -2): KEEP_MMA_X1 has no kernel for this call")
-
-    def broken():
-        raise L.KeepHipError("keep_conv2d_plan failed (code -1): bad argument")
-    assert o.route_x1('a', base, admit) is x1 and o.route_x1('a', base, admit) is x1
-    assert o.route_x1('b', base, refuse) is None and o.route_x1('b', base, refuse) is None
-    assert len(calls) == 2                              # the library is asked once per shape
-    with pytest.raises(L.KeepHipError):
-        o.route_x1('c', base, broken)
-    o.set_x1_twin()                                     # detaching (what set_precision does) forgets the routes
-    assert o.route_x1('b', base, admit) is x1
-
-
 def _planner():
     L.load(check_device=False)
     buf = torch.zeros(64, dtype=torch.float32)

@@ -80,29 +80,6 @@ def test_flow_twin_names(synth_weights):
                                                                      'flownet.model.backbone.layer3.0.downsample.0.weight']
 
 
-def test_route_attn_x1_asks_once_per_key_and_only_eunsup_means_x3():
-    o = ops.Ops()
-    asked = []
-
-    def admits():
-        asked.append('yes')
-        return 1234
-
-    def refuses():
-        asked.append('no')
-        raise L.KeepHipError('keep_attention plan failed (code -2): keep_attention: KEEP_MMA_X1 covers D = Dv = 128 only (D=128 Dv=2)')
-
-    def broken():
-        raise L.KeepHipError('keep_attention failed (code -1): keep_attention: bad dims')
-    assert o.route_attn_x1('a', admits) is True and o.route_attn_x1('b', refuses) is False
-    assert o.route_attn_x1('a', refuses) is True and o.route_attn_x1('b', admits) is False and asked == ['yes', 'no']
-    with pytest.raises(L.KeepHipError, match='bad dims'):      # an error is not an answer
-        o.route_attn_x1('c', broken)
-    assert 'c' not in o._attn_x1_route
-    o.set_precision(L.MMA_X3, torch.zeros(64), None, torch.zeros(128, dtype=torch.int16))      # a policy change forgets the routes
-    assert o._attn_x1_route == {} and o.attn_x1 is False
-
-
 def _attention_through_a_stub(monkeypatch, o, Dv=128, **over):
     """Ops.attention on CPU tensors with the binding's two entry points replaced: returns (plan queries, launches as (mma, flags))."""
     plans, launches = [], []
@@ -110,7 +87,7 @@ def _attention_through_a_stub(monkeypatch, o, Dv=128, **over):
     def plan(**kw):
         plans.append((kw['Lq'], kw['Dv']))
         if kw['Dv'] != 128:
-            raise L.KeepHipError('keep_attention plan failed (code -2): keep_attention: KEEP_MMA_X1 covers D = Dv = 128 only')
+            raise L.KeepHipError('keep_attention plan failed (code -2): keep_attention: KEEP_MMA_X1 covers D = Dv = 128 only', code=L.EUNSUP)
         return 4096
 
     monkeypatch.setattr(L, 'attention_x1_plan', plan)
@@ -137,6 +114,7 @@ def test_ops_attention_rule_with_a_stub_library(monkeypatch):
     assert plans == [(256, 128)] and launches == [(L.MMA_X1, L.ATTN_NO_SMALL | L.ATTN_X1)] * 3      # one query per shape key, x1 where admitted
     plans, launches = _attention_through_a_stub(monkeypatch, o, Dv=2)
     assert plans == [(256, 2)] and launches == [(L.MMA_X3, L.ATTN_NO_SMALL)] * 3                     # KEEP_EUNSUP: the call stays on x3
+    assert list(o._attn_x1_route.values()) == [True, False]
     plans, launches = _attention_through_a_stub(monkeypatch, o, B=7)                                  # the batch is no part of the key
     assert plans == [] and launches == [(L.MMA_X1, L.ATTN_NO_SMALL | L.ATTN_X1)] * 3
     # an explicit policy of another kind, or another base, is never asked about
@@ -149,7 +127,7 @@ def test_ops_attention_rule_with_a_stub_library(monkeypatch):
     o.attn_mma = L.MMA_X3
 
     def broken(**kw):
-        raise L.KeepHipError('keep_attention plan failed (code -3): hip error')
+        raise L.KeepHipError('keep_attention plan failed (code -3): hip error', code=-3)
     monkeypatch.setattr(L, 'attention_x1_plan', broken)
     q = torch.zeros(512, 128)
     with pytest.raises(L.KeepHipError, match='code -3'):

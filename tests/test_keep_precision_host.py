@@ -1,5 +1,5 @@
 """CPU: the host side of the KEEP network's opt-in single-fp16 precision ('f16': the x3 policy with KEEP_MMA_X1 substituted where the
-library's plan admits it) -- the precision knob, the per-call routing of Ops, and the ABI version of header and binding."""
+library's plan admits it) -- the precision knob and the ABI version of header and binding."""
 import os
 import re
 
@@ -30,44 +30,6 @@ def test_environment_selects_f16_and_unknown_values_raise(monkeypatch):
         N.KeepNet(**DEFAULT_ARCH)
     with pytest.raises(ValueError, match='precision must be one of'):
         net.set_precision('half')
-
-
-class _Plan:
-    def __init__(self, kernel, split_k=1):
-        self.kernel, self.split_k = kernel, split_k
-
-
-def test_routing_picks_x1_where_the_plan_admits_it_and_x3_otherwise():
-    """KeepNet's rule (Ops.set_x1_twin(..., base_kernel=X3_STREAM_KERNEL)): route_x1 hands back the call's X1 plan, or None = the base."""
-    import torch
-    o = ops.Ops()
-    o.set_precision(L.MMA_X3, torch.zeros(64), None, torch.zeros(128, dtype=torch.int16))
-    o.set_x1_twin(torch.zeros(64, dtype=torch.int16), [(0, 64, 1.0)], flags=0, base_kernel=ops.X3_STREAM_KERNEL)
-    asked = []
-    x1 = _Plan('conv3x3_halo_x3s_kernel<1, true, true>')
-
-    def admits():
-        asked.append('yes')
-        return x1
-
-    def refuses():
-        asked.append('no')
-        raise L.KeepHipError('keep_conv2d_plan failed (code -2): keep_conv2d: KEEP_MMA_X1 has no kernel for this call')
-
-    def broken():
-        raise L.KeepHipError('keep_conv2d_plan failed (code -1): keep_conv2d: bad mma 7')
-    stream = _Plan(ops.X3_STREAM_KERNEL)
-    assert o.route_x1('a', stream, admits) is x1
-    assert o.route_x1('b', stream, refuses) is None      # KEEP_EUNSUP: the call stays on the base
-    # one plan query per shape: the answers are cached by key
-    assert o.route_x1('a', stream, refuses) is x1 and o.route_x1('b', stream, admits) is None and asked == ['yes', 'no']
-    # only the un-split streaming 3x3 kernel is substituted: the library is not even asked about anything else
-    for k, pl in enumerate((_Plan('gemm_x3l_kernel<4>'), _Plan('conv_x3_kernel<2, 2, 2, 2, true, true>'), _Plan('conv3x3_halo_x3_kernel<32, x2 phases>'),
-                            _Plan('conv3x3_halo_x3_kernel<16>'), _Plan(ops.X3_STREAM_KERNEL, split_k=4))):
-        assert o.route_x1(('other', k), pl, admits) is None
-    assert asked == ['yes', 'no']
-    with pytest.raises(L.KeepHipError, match='bad mma'):      # an error is not an answer
-        o.route_x1('c', stream, broken)
 
 
 def test_x1_is_no_base_policy():

@@ -153,9 +153,9 @@ def _conv_through_a_stub(monkeypatch, o, w, refuse=False, broken=False, N_=2):
     def plan(a):
         plans.append((a.mma, a.flags, a.weight_x3, a.x3_acc_scale))
         if a.mma == L.MMA_X1 and refuse:
-            raise L.KeepHipError('keep_conv2d_plan failed (code -2): keep_conv2d: KEEP_MMA_X1 (with KEEP_CONV_X1_UP2) has no kernel for this call')
+            raise L.KeepHipError('keep_conv2d_plan failed (code -2): keep_conv2d: KEEP_MMA_X1 (with KEEP_CONV_X1_UP2) has no kernel for this call', code=L.EUNSUP)
         if a.mma == L.MMA_X1 and broken:
-            raise L.KeepHipError('keep_conv2d_plan failed (code -1): keep_conv2d: non-positive dimension')
+            raise L.KeepHipError('keep_conv2d_plan failed (code -1): keep_conv2d: non-positive dimension', code=L.EINVAL)
         return _REAL_PLAN(a)
 
     monkeypatch.setattr(ops, '_PLAN_CACHE', {})

@@ -1,7 +1,9 @@
 """Host-side launch record of one source tree, WITHOUT a device: every library entry point is replaced by a recorder and 'cuda' devices
 map to the CPU, so what the host decides -- plans (keep_conv2d_plan is host code and runs for real), policies, flags, scales, call order --
 is written down exactly as it would be handed to the GPU.  Per engine and precision: the ordered calls, for every keep_conv2d its plan's
-kernel name and every non-pointer field of keep_conv2d_args plus which pointers are set, for every other call its name and numeric arguments.
+kernel name and every non-pointer field of keep_conv2d_args plus which pointers are set, for keep_attention its policy, flags and shape, for
+every other call its name and numeric arguments.  KeepNet is recorded per (precision, flow knob, upsample knob), two forwards each (the second
+is served from the route and plan caches), with ``twin_bytes`` and ``clips_per_call`` before and after the twins are built.
 
     python tools/dev/host_launch_record.py TREE OUT.json          # TREE: this checkout or an exported copy of another commit (with its built library)
 
@@ -66,7 +68,10 @@ def launch(a):
 def call(name, *args):
     LOG.append([name] + [x for x in args if isinstance(x, (int, float))])
 L.conv2d_launch, L.call = launch, call
-L.attention = lambda **kw: LOG.append(['keep_attention'])
+def attention(**kw):      # the policy of the call (the single-fp16 route shows in mma / flags), its shape, and which range pointers are set
+    LOG.append(['keep_attention'] + [int(kw[f]) for f in ('mma', 'flags', 'in_dtype', 'B', 'H', 'Lq', 'Lk', 'D', 'Dv', 'mode', 'ksplit', 'shift')]
+               + [kw[f] is not None for f in ('q_amax', 'k_amax', 'v_amax')])
+L.attention = attention
 def nhwc(t): return t.permute(0, 2, 3, 1).contiguous()
 rows = []
 from comfyui_keep_amd.engine import synth
@@ -74,16 +79,36 @@ from comfyui_keep_amd.engine.arch import DEFAULT_ARCH
 from comfyui_keep_amd.engine.net import KeepNet
 W = synth.synth_state_dict(seed=0)
 clip = synth.synth_clip(T=2, B=1, seed=1234)
-for prec in ('fp32', 'x3', 'bf16', 'f16'):
+def free_hbm(free):      # clips_per_call reads the free memory of the device: a fixed figure, nothing reserved
+    torch.cuda.mem_get_info = lambda *a: (int(free), int(288e9))
+    torch.cuda.memory_reserved = torch.cuda.memory_allocated = lambda *a: 0
+def clips(net):
+    """clips_per_call(20) at 200 GB free, and a reading fine enough to see every twin's bytes: 64 x 64 frames, T = 1, 2.5 GB free, no cap."""
+    free_hbm(200e9); coarse = net.clips_per_call(20)
+    free_hbm(2.5e9); os.environ['KEEP_AMD_MAX_CLIPS'] = str(10 ** 6)
+    fine = net.clips_per_call(1, 64, 64)
+    del os.environ['KEEP_AMD_MAX_CLIPS']
+    return [coarse, fine]
+# (precision, flow, upsample): the four base policies, then the two knobs alone, together on 'f16'
+for prec, flow, up in (('fp32', 'x3', 'x3'), ('x3', 'x3', 'x3'), ('bf16', 'x3', 'x3'), ('f16', 'x3', 'x3'),
+                       ('x3', 'f16', 'x3'), ('x3', 'x3', 'f16'), ('f16', 'f16', 'f16')):
     net = KeepNet(**DEFAULT_ARCH); net.load_state_dict(W, strict=True); net.to('cuda').eval().set_precision(prec)
-    del LOG[:]
-    try:
-        net(clip)
-    except Exception as e:
-        import traceback; traceback.print_exc(limit=3)
-        LOG.append(['EXC', type(e).__name__, str(e)[:80]])
-    rows.append({'name': 'KeepNet/' + prec, 'calls': list(LOG), 'mma': int(net.o.mma), 'twin_elems': [net.twin_bytes(p) for p in ('fp32', 'x3', 'bf16', 'f16')] + [net.twin_bytes()]})
-    print(prec, len(LOG), sum(1 for c in LOG if c[0] == 'keep_conv2d'), sum(1 for c in LOG if c[0] == 'keep_absmax'), [c for c in LOG if c[0] == 'EXC'], flush=True)
+    net.set_flow_precision(flow); net.set_upsample_precision(up)
+    name = 'KeepNet/' + prec + ('' if (flow, up) == ('x3', 'x3') else f'/flow={flow}/up={up}')
+    row = {'name': name, 'clips_unbuilt': clips(net)}
+    for leg in ('calls', 'calls_again'):      # the second forward: routes and plans served from the caches
+        del LOG[:]
+        try:
+            net(clip)
+        except Exception as e:
+            import traceback; traceback.print_exc(limit=3)
+            LOG.append(['EXC', type(e).__name__, str(e)[:80]])
+        row[leg] = list(LOG)
+        print(name, leg, len(LOG), sum(1 for c in LOG if c[0] == 'keep_conv2d'), sum(1 for c in LOG if c[0] == 'keep_conv2d' and c[2] == L.MMA_X1),
+              sum(1 for c in LOG if c[0] == 'keep_attention'), sum(1 for c in LOG if c[0] == 'keep_attention' and c[1] == L.MMA_X1),
+              sum(1 for c in LOG if c[0] == 'keep_absmax'), [c for c in LOG if c[0] == 'EXC'], flush=True)
+    row.update(mma=int(net.o.mma), twin_elems=[net.twin_bytes(p) for p in ('fp32', 'x3', 'bf16', 'f16')] + [net.twin_bytes()], clips_built=clips(net))
+    rows.append(row)
 def record(name, make, run):
     eng = make(); del LOG[:]
     try:
