@@ -122,6 +122,14 @@ _SIGNATURES = {
 EXPORTED_SYMBOLS = ['keep_abi_version', 'keep_last_error', 'keep_device_ok', 'keep_attention_workspace_bytes',
                     'keep_sizeof_conv2d_args', 'keep_sizeof_attention_args'] + list(_SIGNATURES)
 
+# the extension header include/keep_cv_hip.h of the same library: its own version, its own table (the core C-ABI above is frozen)
+CV_ABI_VERSION = 1
+_CV_SIGNATURES = {
+    'keep_area_tables': [_i32, _i32, _i32, _vp, _vp, _vp],                 # (host-only: no stream argument)
+    'keep_resize_area_u8': [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+}
+CV_EXPORTED_SYMBOLS = ['keep_cv_abi_version'] + list(_CV_SIGNATURES)
+
 _lib = None
 _device_checked = set()
 
@@ -161,7 +169,13 @@ def load(check_device=True):
             if want != C.sizeof(struct):        # a layout drift between this binding and the library is a load-time error
                 raise KeepHipError(f"{name}() = {want} but the ctypes {struct.__name__} is {C.sizeof(struct)} bytes; "
                                    f"engine/hiplib.py and include/keep_hip.h disagree")
-        for name, argtypes in _SIGNATURES.items():
+        if not hasattr(lib, 'keep_cv_abi_version'):
+            raise KeepHipError("libkeep_hip.so lacks the include/keep_cv_hip.h entry points (keep_cv_abi_version); rebuild")
+        lib.keep_cv_abi_version.restype = _i32
+        ver = lib.keep_cv_abi_version()
+        if ver != CV_ABI_VERSION:
+            raise KeepHipError(f"libkeep_hip.so keep_cv_hip.h version {ver} != expected {CV_ABI_VERSION}; rebuild")
+        for name, argtypes in list(_SIGNATURES.items()) + list(_CV_SIGNATURES.items()):
             fn = getattr(lib, name)            # AttributeError if the symbol is missing
             fn.restype = _i32
             fn.argtypes = argtypes

@@ -6,8 +6,15 @@ library's host C (``keep_lanczos4_tables``), are uploaded once per geometry and 
 of a call is one launch of ``keep_resize_lanczos4_u8`` (csrc/keep_resize.hip).  Whether this equals cv2 itself on an installation is
 decided at run time by the processor (``opencv_agrees_with_gpu_resize``); tests/cv_lanczos_ref.py is the independent restatement the
 kernel is checked against bit for bit.
+
+``cv2.resize(img, (W2, H2), interpolation=cv2.INTER_AREA)`` for frames that shrink on both axes -- the detector input of
+face_restoration_helper.py:206-216 -- is the second resize here: ``area_tables`` (``keep_area_tables``, host C: OpenCV 4.x
+``computeResizeAreaTab`` in CSR form) and ``AreaResizer`` (``keep_resize_area_u8``, csrc/keep_resize_area.hip, declared in the
+extension header include/keep_cv_hip.h).  Its float32 sums are order-bound, so the kernel is built without FMA contraction;
+tests/cv_area_ref.py is its restatement, and the processor's ``opencv_agrees_with_gpu_detect_resize`` decides on an installation.
 """
 import ctypes as C
+import sys
 
 import numpy as np
 import torch
@@ -70,4 +77,79 @@ class Lanczos4Resizer:
         xo, xc, yo, yc = self._device_tables(H, W, H2, W2)
         with torch.cuda.device(self.device):
             L.call('keep_resize_lanczos4_u8', x, out, N, H, W, H2, W2, xo, xc, yo, yc)
+        return out if batched else out[0]
+
+
+def area_tables(S, D):
+    """(start int32 [D + 1], si int32 [n], alpha float32 [n]) of one axis of INTER_AREA, S source -> D < S destination pixels: the entries
+    of destination d are ``start[d] .. start[d + 1]`` (host memory; no device needed)."""
+    lib = L.load(check_device=False)
+    S, D = int(S), int(D)
+    cap = max(1, S + 2 * max(D, 0))                      # a head and a tail per destination, every source pixel once
+    start = np.empty(max(D, 0) + 1, np.int32)
+    si = np.empty(cap, np.int32)
+    alpha = np.empty(cap, np.float32)
+    rc = lib.keep_area_tables(S, D, cap, start.ctypes.data_as(C.c_void_p), si.ctypes.data_as(C.c_void_p), alpha.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise L.KeepHipError(f"keep_area_tables failed (code {rc}): {lib.keep_last_error().decode()}", code=rc)
+    n = int(start[D])
+    return start, si[:n].copy(), alpha[:n].copy()
+
+
+def _whole_scale(S, D):
+    scale = 1.0 / (float(D) / float(S))
+    return abs(scale - int(scale)) < sys.float_info.epsilon
+
+
+def area_geometry_refused(H, W, H2, W2):
+    """Whether ``keep_resize_area_u8`` refuses [H,W] -> [H2,W2]: not a shrink on both axes, or a whole-number scale on both (OpenCV's
+    integer INTER_AREA path, which the library does not restate)."""
+    if H2 <= 0 or W2 <= 0 or H2 >= H or W2 >= W:
+        return True
+    return _whole_scale(H, H2) and _whole_scale(W, W2)
+
+
+class AreaResizer:
+    """Device tables cached per (H, W, H2, W2), like ``Lanczos4Resizer``.  One instance per processor."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        if self.device.type == 'cuda' and self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        self._tables = {}
+
+    def _device_tables(self, H, W, H2, W2):
+        key = (H, W, H2, W2)
+        t = self._tables.get(key)
+        if t is None:
+            t = tuple(torch.from_numpy(a).to(self.device) for a in area_tables(W, W2) + area_tables(H, H2))
+            torch.cuda.current_stream(self.device).synchronize()     # (read later from whichever stream resizes)
+            self._tables[key] = t
+        return t
+
+    def resize_u8(self, frames, W2, H2):
+        """uint8 frames [H,W,3] or [N,H,W,3] (numpy or tensor) -> uint8 [H2,W2,3] / [N,H2,W2,3] on the device, one launch on the current
+        stream.  A refused geometry (``area_geometry_refused``) raises KeepHipError: there is no other path here."""
+        W2, H2 = int(W2), int(H2)
+        shape = tuple(frames.shape)
+        if len(shape) not in (3, 4) or shape[-1] != 3:
+            raise ValueError(f"resize_u8: expected [H,W,3] or [N,H,W,3] uint8 frames, got shape {shape}")
+        H, W = shape[-3], shape[-2]
+        x = torch.as_tensor(frames)
+        if x.dtype != torch.uint8:
+            raise ValueError(f"resize_u8: expected uint8 frames, got {x.dtype}")
+        if area_geometry_refused(H, W, H2, W2):
+            raise L.KeepHipError(f"keep_resize_area_u8 refuses {W}x{H} -> {W2}x{H2}: INTER_AREA on the device is for shrinking on both "
+                                 f"axes with a scale that is not a whole number on both", code=L.EINVAL)
+        x = x.to(self.device, non_blocking=True).contiguous()
+        batched = x.dim() == 4
+        if not batched:
+            x = x[None]
+        N = x.shape[0]
+        out = torch.empty((N, H2, W2, 3), dtype=torch.uint8, device=self.device)
+        if N == 0:
+            return out if batched else out[0]
+        tables = self._device_tables(H, W, H2, W2)
+        with torch.cuda.device(self.device):
+            L.call('keep_resize_area_u8', x, out, N, H, W, H2, W2, *tables)
         return out if batched else out[0]

@@ -115,6 +115,23 @@ def opencv_agrees_with_gpu_resize(device):
     return True
 
 
+def opencv_agrees_with_gpu_detect_resize(device):
+    """True iff the HIP area resize (engine/resize.py:AreaResizer) reproduces ``cv2.resize(..., INTER_AREA)`` bit for bit on this
+    installation: the detector-input geometries of 1080p and 720p video (short side to 640) and small frames with 2-3 taps, a scale
+    below 1.2 and a whole-number scale on one axis only.  Raises ImportError without cv2."""
+    import cv2
+    from ..engine.resize import AreaResizer
+    rz = AreaResizer(device)
+    rng = np.random.default_rng(0)
+    for (h, w), (h2, w2) in (((1080, 1920), (640, 1137)), ((720, 1280), (640, 1137)), ((54, 96), (32, 56)), ((45, 80), (40, 71)),
+                             ((48, 64), (16, 21)), ((270, 480), (160, 284))):
+        img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+        ref = cv2.resize(img, (w2, h2), interpolation=cv2.INTER_AREA)
+        if not np.array_equal(rz.resize_u8(img, w2, h2).cpu().numpy(), ref):
+            return False
+    return True
+
+
 def _host(img):
     """A background / face that leaves the device path (the helper's own paste, a frame returned as it is): a host array."""
     return img.cpu().numpy() if isinstance(img, torch.Tensor) else img
@@ -308,6 +325,13 @@ class KEEPFaceProcessor:
         env = os.environ.get('KEEP_AMD_GPU_RESIZE')
         self.gpu_resize = {'1': True, '0': False}.get(env, None)
         self._resizer = None
+        # the INTER_AREA resize of the detector inputs (face_restoration_helper.py:206-216) on the device (engine/resize.py:AreaResizer;
+        # ``_prep_detect_chunk``).  KEEP_AMD_GPU_DETECT_RESIZE: '1' on, '0' off; unset = auto, decided like KEEP_AMD_GPU_RESIZE: with cv2
+        # by ``opencv_agrees_with_gpu_detect_resize`` once per processor, without cv2 the device path.
+        env = os.environ.get('KEEP_AMD_GPU_DETECT_RESIZE')
+        self.gpu_detect_resize = {'1': True, '0': False}.get(env, None)
+        self._area_resizer = None
+        self.detect_resize = 640        # the sequence pre-pass's ``resize`` of get_face_landmarks_5 (keep_processor.py:207-213 of the reference)
 
     # ------------------------------------------------------------------ net invocation
     def _restore_clips(self, crops_tensor, max_clip_length):
@@ -405,6 +429,60 @@ class KEEPFaceProcessor:
                 log.info("device Lanczos resize self-check failed (%s): cv2.resize", e)
                 self.gpu_resize = False
         return self.gpu_resize
+
+    def _gpu_detect_resize_path(self):
+        """Whether the HIP area resize stands in for the INTER_AREA cv2.resize of the detector inputs: forced by
+        KEEP_AMD_GPU_DETECT_RESIZE, else decided once per processor -- by comparing it with cv2 itself where cv2 imports, and on without
+        cv2 (a frame above the detector size has no other resize there)."""
+        if self.gpu_detect_resize is None:
+            import logging
+            log = logging.getLogger('ComfyUI-KEEP')
+            try:
+                _cv2()
+            except ImportError:
+                log.info("cv2 is not installed: detector inputs are resized on the device (KEEP_AMD_GPU_DETECT_RESIZE)")
+                self.gpu_detect_resize = True
+                return True
+            try:
+                self.gpu_detect_resize = bool(opencv_agrees_with_gpu_detect_resize(self.device))
+            except Exception as e:                      # no GPU / no library / any surprise: cv2
+                log.info("device area resize self-check failed (%s): cv2.resize", e)
+                self.gpu_detect_resize = False
+        return self.gpu_detect_resize
+
+    def _detect_resize_device(self, imgs, w2, h2):
+        """uint8 [H,W,3] frames of one size -> the uint8 [n,h2,w2,3] detector batch on the device: every frame is copied straight into one
+        [n,H,W,3] device tensor (no host stack; frames of the pinned conversion buffer copy asynchronously) and all of them are resized
+        by one ``keep_resize_area_u8`` launch on the device's current stream.  The resized frames never exist on the host."""
+        if self._area_resizer is None:
+            from ..engine.resize import AreaResizer
+            self._area_resizer = AreaResizer(self.device)
+        dev = self._area_resizer.device
+        h, w = imgs[0].shape[:2]
+        with torch.cuda.device(dev):
+            buf = torch.empty((len(imgs), h, w, 3), dtype=torch.uint8, device=dev)
+            for i, im in enumerate(imgs):
+                buf[i].copy_(im if isinstance(im, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(im)), non_blocking=True)
+            return self._area_resizer.resize_u8(buf, w2, h2)
+
+    def _detect_resize_applies(self, imgs, resize):
+        """(w2, h2) when the device resize takes this chunk's detector inputs -- every frame uint8 [H,W,3] of one size whose short side
+        exceeds ``resize``, a geometry the kernel takes (a whole-number scale on both axes is OpenCV's integer path: cv2), the path
+        enabled -- else None."""
+        if resize is None or not imgs or self.gpu_detect_resize is False:
+            return None
+        first = tuple(imgs[0].shape)
+        if len(first) != 3 or first[2] != 3 or min(first[:2]) <= resize:
+            return None
+        if any(tuple(im.shape) != first or im.dtype not in (np.uint8, torch.uint8) for im in imgs):
+            return None
+        from ..engine.resize import area_geometry_refused
+        h, w = first[:2]
+        scale = resize / min(h, w)
+        w2, h2 = int(w * scale), int(h * scale)
+        if area_geometry_refused(h, w, h2, w2) or not self._gpu_detect_resize_path():
+            return None
+        return w2, h2
 
     # ------------------------------------------------------------------ single image
     @torch.no_grad()
@@ -722,13 +800,15 @@ class KEEPFaceProcessor:
             return raw
         # Round 6: the detector's forward of chunk k (GPU, one worker thread: the launches and the D2H waits release the GIL) runs under the
         # HOST preparation of chunk k + 1 (read_image + the INTER_AREA resize of every frame: a third of the pre-pass) -- the same calls
-        # on the same data in the same order per frame, only interleaved; KEEP_AMD_DETECT_OVERLAP=0: one after the other
+        # on the same data in the same order per frame, only interleaved; KEEP_AMD_DETECT_OVERLAP=0: one after the other.  Where the device
+        # resize applies (KEEP_AMD_GPU_DETECT_RESIZE, ``_prep_detect_chunk``) that host resize is gone: the chunk's frames are copied to the
+        # device and resized there by one launch, stream-ordered behind the forward of chunk k
         pool = None
         if use_batch and len(starts) > 1 and os.environ.get('KEEP_AMD_DETECT_OVERLAP', '1') != '0':
             from concurrent.futures import ThreadPoolExecutor
             pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix='keep-detect')
         try:
-            prepared = self._prep_detect_chunk(frames_bgr[starts[0]:starts[0] + chunk], 640) if use_batch else None
+            prepared = self._prep_detect_chunk(frames_bgr[starts[0]:starts[0] + chunk], self.detect_resize) if use_batch else None
             for k, s in enumerate(starts):
                 part = frames_bgr[s:s + chunk]
                 states, batched = None, None
@@ -740,7 +820,7 @@ class KEEPFaceProcessor:
                         if fut is None:
                             batched = det.detect_batch(batch, 0.97)
                     if k + 1 < len(starts):                                # host work of the next chunk, under this chunk's forward
-                        prepared = self._prep_detect_chunk(frames_bgr[starts[k + 1]:starts[k + 1] + chunk], 640)
+                        prepared = self._prep_detect_chunk(frames_bgr[starts[k + 1]:starts[k + 1] + chunk], self.detect_resize)
                     if fut is not None:
                         batched = fut.result()
                 self._replay_chunk(det, part, states, batched, only_center_face, raw, bar)
@@ -761,11 +841,11 @@ class KEEPFaceProcessor:
             else:
                 helper.read_image(frame)
             if batched is None:
-                helper.get_face_landmarks_5(only_center_face=only_center_face, resize=640, eye_dist_threshold=5)
+                helper.get_face_landmarks_5(only_center_face=only_center_face, resize=self.detect_resize, eye_dist_threshold=5)
             else:
                 helper.face_detector = _ReplayDetector(batched[j])
                 try:
-                    helper.get_face_landmarks_5(only_center_face=only_center_face, resize=640, eye_dist_threshold=5)
+                    helper.get_face_landmarks_5(only_center_face=only_center_face, resize=self.detect_resize, eye_dist_threshold=5)
                 finally:
                     helper.face_detector = det
             raw.append(list(helper.all_landmarks_5))
@@ -793,7 +873,8 @@ class KEEPFaceProcessor:
         windows = [starts[i:i + world] for i in range(0, len(starts), world)]
 
         def prep(win):
-            return [self._prep_detect_chunk(frames_bgr[s:s + chunk], 640) for s in win]
+            # (host batches: they cross to the workers through shared memory, so the device resize is not used here)
+            return [self._prep_detect_chunk(frames_bgr[s:s + chunk], self.detect_resize, device_resize=False) for s in win]
 
         def forward(prepared):
             live = [batch for _, batch in prepared if batch is not None]
@@ -824,25 +905,36 @@ class KEEPFaceProcessor:
             if thread is not None:
                 thread.shutdown(wait=True)
 
-    def _prep_detect_chunk(self, frames_bgr, resize):
-        """One chunk of frames, host side only: the helper state ``read_image`` leaves behind per frame (input image, grey flag) and the
-        detector inputs ``get_face_landmarks_5`` would build from it (face_restoration_helper.py:206-216: frames whose short side exceeds
-        ``resize`` are scaled down with INTER_AREA), stacked -> (states, batch).  ``batch`` is None when the frames differ in size or are
-        not uint8 (16-bit sources become float64 in ``read_image``: the per-frame path converts them the way the reference does)."""
+    def _prep_detect_chunk(self, frames_bgr, resize, device_resize=True):
+        """One chunk of frames: the helper state ``read_image`` leaves behind per frame (input image, grey flag) and the detector inputs
+        ``get_face_landmarks_5`` would build from it (face_restoration_helper.py:206-216: frames whose short side exceeds ``resize`` are
+        scaled down with INTER_AREA), stacked -> (states, batch).  ``batch`` is None when the frames differ in size or are not uint8
+        (16-bit sources become float64 in ``read_image``: the per-frame path converts them the way the reference does).  Who resizes: a
+        helper's own ``resize_for_detector`` first; else, with ``device_resize``, the HIP area resize over the whole chunk
+        (``_detect_resize_applies``: the batch is then a device tensor); else ``_resize`` (cv2, on the host) frame by frame."""
         helper = self.face_helper
-        states, imgs = [], []
+        own = getattr(helper, 'resize_for_detector', None)          # (a helper may bring its own resize: bench.py's cv2-free stand-in)
+        states = []
         for frame in frames_bgr:
             helper.clean_all()
             helper.read_image(frame)
-            img = helper.input_img
-            states.append((img, getattr(helper, 'is_gray', False)))
+            states.append((helper.input_img, getattr(helper, 'is_gray', False)))
+        imgs = [img for img, _ in states]
+        target = self._detect_resize_applies(imgs, resize) if own is None and device_resize else None
+        if target is not None:
+            try:
+                return states, self._detect_resize_device(imgs, *target)
+            except Exception as e:                      # logged, and the present path takes the chunk (and every later one)
+                import logging
+                logging.getLogger('ComfyUI-KEEP').warning("device resize of the detector inputs failed (%s): cv2.resize", e)
+                self.gpu_detect_resize = False
+        for i, img in enumerate(imgs):
             h, w = img.shape[:2]
             if resize is not None and min(h, w) > resize:
                 scale = resize / min(h, w)
-                own = getattr(helper, 'resize_for_detector', None)      # (a helper may bring its own resize: bench.py's cv2-free stand-in)
                 img = (own(img, int(w * scale), int(h * scale)) if own is not None
                        else _resize(img, int(w * scale), int(h * scale), 'INTER_AREA' if scale < 1 else 'INTER_LINEAR'))
-            imgs.append(img if isinstance(img, torch.Tensor) else np.ascontiguousarray(img))
+            imgs[i] = img if isinstance(img, torch.Tensor) else np.ascontiguousarray(img)
         if any(tuple(im.shape) != tuple(imgs[0].shape) or im.dtype not in (np.uint8, torch.uint8) for im in imgs):
             return states, None
         return states, (torch.stack(imgs) if isinstance(imgs[0], torch.Tensor) else np.stack(imgs))

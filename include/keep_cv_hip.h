@@ -1,0 +1,48 @@
+/* keep_cv_hip.h -- extension header of libkeep_hip.so: OpenCV-arithmetic image kernels that are not part of the core C-ABI.
+ *
+ * The core header (keep_hip.h) and its KEEP_ABI_VERSION are frozen; entry points added beside it live here under a version of their
+ * own, in the same shared library.  The boundary rules are the core header's:
+ *   - every pointer the caller passes is CALLER-OWNED; device pointers are plain device memory (torch tensor.data_ptr() works);
+ *   - launchers are stream-ordered on the hipStream_t passed as `void* stream` (NULL = default stream), allocate nothing and
+ *     synchronise nothing;
+ *   - returns KEEP_OK (0), KEEP_EINVAL (-1) bad argument / refused geometry, KEEP_EHIP (-3) HIP runtime error, with a thread-local
+ *     message behind keep_hip.h's keep_last_error that opens with the function's name;
+ *   - the library reads no environment variable.
+ */
+#ifndef KEEP_CV_HIP_H
+#define KEEP_CV_HIP_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define KEEP_CV_ABI_VERSION 1
+
+int32_t keep_cv_abi_version(void);
+
+/* ---- detector input (face_restoration_helper.py:206-216): cv2.resize(frame, (W2, H2), interpolation=INTER_AREA), uint8, 3 channels,
+ * shrinking on BOTH axes: OpenCV 4.x resize.cpp computeResizeAreaTab + ResizeArea_Invoker<uchar, float>.
+ *
+ * Refused geometries (KEEP_EINVAL): D >= S on an axis, and -- by the launcher -- a geometry whose scale 1.0 / ((double)D / S) is a
+ * whole number on BOTH axes (OpenCV's is_area_fast: an integer path with other arithmetic, which this library does not restate).
+ *
+ * keep_area_tables: HOST-only C (no device, no stream): the table of one axis, S source -> D destination pixels, in CSR form: the
+ * entries of destination index d are start[d] .. start[d + 1] - 1, entry e adds source pixel si[e] with weight alpha[e], source indices
+ * ascending.  start has D + 1 elements, si / alpha have `cap` elements; KEEP_EINVAL when the table needs more than `cap` entries (an axis
+ * never needs more than S + 2 * D).
+ *
+ * keep_resize_area_u8: N contiguous uint8 frames [N,H,W,3] -> [N,H2,W2,3] in one launch with the tables of x (W -> W2) and y
+ * (H -> H2) as keep_area_tables wrote them, all DEVICE pointers.  Per output value, in float32 with separately rounded multiplies and
+ * adds: for every y entry in order, buf = sum over the x entries in order of src * alpha; sum = beta * buf for the first y entry,
+ * sum + beta * buf for the later ones; dst = saturate_u8(round-half-to-even(sum)). */
+int32_t keep_area_tables(int32_t S, int32_t D, int32_t cap, int32_t* start /*[D+1]*/, int32_t* si /*[cap]*/, float* alpha /*[cap]*/);
+int32_t keep_resize_area_u8(const uint8_t* src, uint8_t* dst, int32_t N, int32_t H, int32_t W, int32_t H2, int32_t W2,
+                            const int32_t* xstart, const int32_t* xsi, const float* xalpha, const int32_t* ystart, const int32_t* ysi,
+                            const float* yalpha, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* KEEP_CV_HIP_H */
