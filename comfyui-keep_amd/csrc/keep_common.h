@@ -116,3 +116,20 @@ __device__ __forceinline__ float pro_apply(float v, int act) {
   if (act == KEEP_PRO_RELU) return relu_keep_nan(v);
   return v;
 }
+
+// One axis of OpenCV's 8-bit bilinear resize (modules/imgproc/src/resize.cpp, resizeGeneric_, INTER_LINEAR; the arithmetic is spelt out
+// in keep_yolo.hip): destination index d -> source index s and the 11-bit weights of s and s + 1.  `scale` is the double OpenCV forms,
+// 1. / ((double)dsize / ssize).  clamp_pos (columns): an outside position is clamped and its weight reset; rows keep s and the weights, and
+// the caller clamps the row it reads.  Shared by the letterbox (keep_yolo.hip) and keep_resize_linear.hip.
+__device__ __forceinline__ void cv_lin_coef(int d, double scale, int size, bool clamp_pos, int& s, int& a0, int& a1) {
+  float f = (float)__dadd_rn(__dmul_rn((double)d + 0.5, scale), -0.5);      // (two roundings, as the host code compiles: no fma)
+  int i = (int)floorf(f);
+  f -= (float)i;
+  if (clamp_pos) {
+    if (i < 0) { i = 0; f = 0.f; }
+    if (i >= size - 1) { i = size - 1; f = 0.f; }
+  }
+  s = i;
+  a0 = max(-32768, min(32767, __float2int_rn((1.f - f) * 2048.f)));
+  a1 = max(-32768, min(32767, __float2int_rn(f * 2048.f)));
+}

@@ -13,20 +13,7 @@
 //   fx = (float)((dx + 0.5) * scale_x - 0.5), sx = floor(fx), fx -= sx; sx < 0: (0, fx = 0); sx >= W - 1: (W - 1, fx = 0);
 //   alpha = { sat_short(rint((1.f - fx) * 2048)), sat_short(rint(fx * 2048)) }; rows likewise except that out-of-range ROWS are clamped
 //   and keep their weights; horizontal pass in int: S * a0 + S' * a1; vertical: (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2.
-// scale_x / scale_y arrive as the doubles OpenCV forms: 1. / ((double)rw / W).
-__device__ __forceinline__ void cv_lin_coef(int d, double scale, int size, bool clamp_pos, int& s, int& a0, int& a1) {
-  float f = (float)__dadd_rn(__dmul_rn((double)d + 0.5, scale), -0.5);      // (two roundings, as the host code compiles: no fma)
-  int i = (int)floorf(f);
-  f -= (float)i;
-  if (clamp_pos) {
-    if (i < 0) { i = 0; f = 0.f; }
-    if (i >= size - 1) { i = size - 1; f = 0.f; }
-  }
-  s = i;
-  a0 = max(-32768, min(32767, __float2int_rn((1.f - f) * 2048.f)));
-  a1 = max(-32768, min(32767, __float2int_rn(f * 2048.f)));
-}
-
+// scale_x / scale_y arrive as the doubles OpenCV forms: 1. / ((double)rw / W).  The per-axis coefficients: keep_common.h:cv_lin_coef.
 __global__ __launch_bounds__(256) void yolo_letterbox_kernel(const uint8_t* __restrict__ frames, float* __restrict__ out, int N, int H, int W,
                                                              int rh, int rw, int top, int left, int H2, int W2, double scale_x,
                                                              double scale_y, int swap_rb) {

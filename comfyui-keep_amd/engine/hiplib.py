@@ -127,6 +127,7 @@ CV_ABI_VERSION = 1
 _CV_SIGNATURES = {
     'keep_area_tables': [_i32, _i32, _i32, _vp, _vp, _vp],                 # (host-only: no stream argument)
     'keep_resize_area_u8': [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    'keep_resize_linear_u8': [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
 }
 CV_EXPORTED_SYMBOLS = ['keep_cv_abi_version'] + list(_CV_SIGNATURES)
 

@@ -12,6 +12,11 @@ face_restoration_helper.py:206-216 -- is the second resize here: ``area_tables``
 ``computeResizeAreaTab`` in CSR form) and ``AreaResizer`` (``keep_resize_area_u8``, csrc/keep_resize_area.hip, declared in the
 extension header include/keep_cv_hip.h).  Its float32 sums are order-bound, so the kernel is built without FMA contraction;
 tests/cv_area_ref.py is its restatement, and the processor's ``opencv_agrees_with_gpu_detect_resize`` decides on an installation.
+
+``cv2.resize(img, (W2, H2), interpolation=cv2.INTER_LINEAR)`` -- the aligned-face input (keep_processor.py:158,250 of the reference) --
+is the third: ``LinearResizer`` (``keep_resize_linear_u8``, csrc/keep_resize_linear.hip), any geometry, no tables: OpenCV's 11-bit fixed
+point, and the 2 x 2 integer average cv2.resize substitutes at an exact 2x shrink.  tests/cv_linear_ref.py is its restatement, and
+``opencv_agrees_with_gpu_aligned_resize`` decides on an installation.
 """
 import ctypes as C
 import sys
@@ -153,3 +158,42 @@ class AreaResizer:
         with torch.cuda.device(self.device):
             L.call('keep_resize_area_u8', x, out, N, H, W, H2, W2, *tables)
         return out if batched else out[0]
+
+
+class LinearResizer:
+    """``cv2.resize(..., INTER_LINEAR)`` for uint8 3-channel frames; the kernel needs no tables, so there is nothing to cache.  One
+    instance per processor."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        if self.device.type == 'cuda' and self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+
+    def resize_u8(self, frames, W2, H2, out=None):
+        """uint8 frames [H,W,3] or [N,H,W,3] (numpy or tensor) -> uint8 [H2,W2,3] / [N,H2,W2,3] on the device, one launch on the current
+        stream.  At identity the input comes back as it is and nothing is launched, like ``Lanczos4Resizer.resize_u8``.  ``out``: a
+        contiguous uint8 tensor of the result's shape on this device to write into (a slice of a larger batch) instead of a new one; at
+        identity the frames are copied into it."""
+        W2, H2 = int(W2), int(H2)
+        shape = tuple(frames.shape)
+        if len(shape) not in (3, 4) or shape[-1] != 3:
+            raise ValueError(f"resize_u8: expected [H,W,3] or [N,H,W,3] uint8 frames, got shape {shape}")
+        H, W = shape[-3], shape[-2]
+        want = shape[:-3] + (H2, W2, 3)
+        if out is not None and (tuple(out.shape) != want or out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous()):
+            raise ValueError(f"resize_u8: out must be a contiguous uint8 {want} tensor on {self.device}")
+        if (H, W) == (H2, W2):
+            return frames if out is None else out.copy_(torch.as_tensor(frames), non_blocking=True)
+        x = torch.as_tensor(frames)
+        if x.dtype != torch.uint8:
+            raise ValueError(f"resize_u8: expected uint8 frames, got {x.dtype}")
+        x = x.to(self.device, non_blocking=True).contiguous()
+        batched = x.dim() == 4
+        if not batched:
+            x = x[None]
+        N = x.shape[0]
+        y = torch.empty((N, H2, W2, 3), dtype=torch.uint8, device=self.device) if out is None else out.view(N, H2, W2, 3)
+        if N > 0:
+            with torch.cuda.device(self.device):
+                L.call('keep_resize_linear_u8', x, y, N, H, W, H2, W2)
+        return y if batched else y[0]

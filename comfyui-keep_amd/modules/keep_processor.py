@@ -26,6 +26,10 @@ device (``run_clips_u8(sink=...)``), ParseNet runs on batches of up to 32 faces 
 face_restoration_helper.py:418-424), and the frames whose faces are all restored are composited and downloaded on a second HIP
 stream while the next group is being restored.  Same arithmetic, same order per frame: the output equals the per-frame path bit
 for bit (tests/test_gpu_paste.py::test_streamed_sequence_equals_the_per_frame_path); every other configuration keeps that path.
+
+Aligned inputs (``has_aligned``): a frame that is not 512 x 512 is brought there by the INTER_LINEAR resize on the device
+(``_aligned_face``, KEEP_AMD_GPU_ALIGNED_RESIZE), and an aligned sequence stays on the device from upload to output
+(``_aligned_streamed``), equal to the per-frame path bit for bit (tests/test_gpu_aligned.py).
 """
 import os
 
@@ -128,6 +132,22 @@ def opencv_agrees_with_gpu_detect_resize(device):
         img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
         ref = cv2.resize(img, (w2, h2), interpolation=cv2.INTER_AREA)
         if not np.array_equal(rz.resize_u8(img, w2, h2).cpu().numpy(), ref):
+            return False
+    return True
+
+
+def opencv_agrees_with_gpu_aligned_resize(device):
+    """True iff the HIP bilinear resize (engine/resize.py:LinearResizer) reproduces ``cv2.resize(..., INTER_LINEAR)`` bit for bit on this
+    installation, at the aligned-face target of 512 x 512: an enlargement, a fractional shrink, the exact 2x shrink (INTER_AREA's 2 x 2
+    path inside cv2.resize), a non-square source and a one-pixel-wide source.  Raises ImportError without cv2."""
+    import cv2
+    from ..engine.resize import LinearResizer
+    rz = LinearResizer(device)
+    rng = np.random.default_rng(0)
+    for h, w in ((256, 256), (720, 720), (1024, 1024), (300, 400), (64, 1)):
+        img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+        ref = cv2.resize(img, (512, 512), interpolation=cv2.INTER_LINEAR)
+        if not np.array_equal(rz.resize_u8(img, 512, 512).cpu().numpy(), ref):
             return False
     return True
 
@@ -331,6 +351,13 @@ class KEEPFaceProcessor:
         env = os.environ.get('KEEP_AMD_GPU_DETECT_RESIZE')
         self.gpu_detect_resize = {'1': True, '0': False}.get(env, None)
         self._area_resizer = None
+        # has_aligned: the INTER_LINEAR resize of a frame that is not 512 x 512 already (keep_processor.py:158,250 of the reference) on the
+        # device (engine/resize.py:LinearResizer; ``_aligned_face``, ``_aligned_streamed``).  KEEP_AMD_GPU_ALIGNED_RESIZE: '1' on, '0' off;
+        # unset = auto, decided like the two above: with cv2 by ``opencv_agrees_with_gpu_aligned_resize`` once per processor, without cv2
+        # the device path.
+        env = os.environ.get('KEEP_AMD_GPU_ALIGNED_RESIZE')
+        self.gpu_aligned_resize = {'1': True, '0': False}.get(env, None)
+        self._linear_resizer = None
         self.detect_resize = 640        # the sequence pre-pass's ``resize`` of get_face_landmarks_5 (keep_processor.py:207-213 of the reference)
 
     # ------------------------------------------------------------------ net invocation
@@ -411,6 +438,16 @@ class KEEPFaceProcessor:
             return out if on_device else out.cpu().numpy()
         return _resize(_host(img), w, h, 'INTER_LANCZOS4')
 
+    def _lanczos_batch(self, frames, w, h):
+        """``_lanczos`` over a uint8 [m,H,W,3] device batch that stays on the device: one launch on the current stream, identity returns
+        ``frames``.  For callers that have settled ``_gpu_resize_path`` already (``_aligned_stream_applies``)."""
+        if frames.shape[1] == h and frames.shape[2] == w:
+            return frames
+        if self._resizer is None:
+            from ..engine.resize import Lanczos4Resizer
+            self._resizer = Lanczos4Resizer(self.device)
+        return self._resizer.resize_u8(frames, w, h)
+
     def _gpu_resize_path(self):
         """Whether the HIP Lanczos resize stands in for cv2.resize: forced by KEEP_AMD_GPU_RESIZE, else decided once per processor --
         by comparing it with cv2 itself where cv2 imports, and on without cv2 (no other path can run there)."""
@@ -484,6 +521,50 @@ class KEEPFaceProcessor:
             return None
         return w2, h2
 
+    def _gpu_aligned_resize_path(self):
+        """Whether the HIP bilinear resize stands in for the INTER_LINEAR cv2.resize of aligned inputs: forced by
+        KEEP_AMD_GPU_ALIGNED_RESIZE, else decided once per processor -- by comparing it with cv2 itself where cv2 imports, and on without
+        cv2 (an aligned frame that is not 512 x 512 has no other resize there)."""
+        if self.gpu_aligned_resize is None:
+            import logging
+            log = logging.getLogger('ComfyUI-KEEP')
+            try:
+                _cv2()
+            except ImportError:
+                log.info("cv2 is not installed: aligned inputs are resized on the device (KEEP_AMD_GPU_ALIGNED_RESIZE)")
+                self.gpu_aligned_resize = True
+                return True
+            try:
+                self.gpu_aligned_resize = bool(opencv_agrees_with_gpu_aligned_resize(self.device))
+            except Exception as e:                      # no GPU / no library / any surprise: cv2
+                log.info("device bilinear resize self-check failed (%s): cv2.resize", e)
+                self.gpu_aligned_resize = False
+        return self.gpu_aligned_resize
+
+    def _aligned_resize_device(self, frames, out=None):
+        """uint8 [H,W,3] / [n,H,W,3] (host or device) -> the 512 x 512 crops on the device: one ``keep_resize_linear_u8`` launch on the
+        current stream (into ``out`` where given)."""
+        if self._linear_resizer is None:
+            from ..engine.resize import LinearResizer
+            self._linear_resizer = LinearResizer(self.device)
+        return self._linear_resizer.resize_u8(frames, 512, 512, out=out)
+
+    def _aligned_face(self, img):
+        """``_resize(img, 512, 512, 'INTER_LINEAR')`` of an aligned input: identity returns ``img``; a uint8 [H,W,3] image goes to the
+        device kernel when ``_gpu_aligned_resize_path`` allows it and comes back as a host array; everything else (grey / 4-channel /
+        other dtypes, an empty image, the path off) goes to cv2.  A device failure is logged and turns the path off."""
+        if img.shape[0] == 512 and img.shape[1] == 512:
+            return img
+        if (len(img.shape) == 3 and img.shape[2] == 3 and img.dtype == np.uint8 and img.shape[0] > 0 and img.shape[1] > 0
+                and self._gpu_aligned_resize_path()):
+            try:
+                return self._aligned_resize_device(img).cpu().numpy()
+            except Exception as e:
+                import logging
+                logging.getLogger('ComfyUI-KEEP').warning("device resize of the aligned input failed (%s): cv2.resize", e)
+                self.gpu_aligned_resize = False
+        return _resize(img, 512, 512, 'INTER_LINEAR')
+
     # ------------------------------------------------------------------ single image
     @torch.no_grad()
     def process_image(self, cv2_image_orig: np.ndarray, final_upscale_factor: float, has_aligned: bool,
@@ -493,7 +574,7 @@ class KEEPFaceProcessor:
         bg_img_final = self._final_background(cv2_image_orig, final_upscale_factor, on_device=not has_aligned)
 
         if has_aligned:
-            face = _resize(cv2_image_orig, 512, 512, 'INTER_LINEAR')
+            face = self._aligned_face(cv2_image_orig)
             helper.is_gray = _is_gray(face, threshold=10)
             helper.cropped_faces = [face]
             crops = [face]
@@ -775,6 +856,133 @@ class KEEPFaceProcessor:
         self.last_restored_faces = _DeviceFaces(ready) if keep_restored else []
         return st['out']
 
+    # ------------------------------------------------------------------ streamed aligned sequence
+    def _aligned_stream_applies(self, frames_bgr, factor):
+        """The device-resident form of an aligned sequence (``_aligned_streamed``) needs: the engine's net (``run_clips_u8`` with
+        ``sink``) in one process without a worker pool (a pool worker's share arrives in host memory: the per-frame path keeps that
+        case), not inside a torch.distributed job, no face / background upscale model, uint8 colour frames of one size, and the device
+        path of every resize the call makes: ``_gpu_resize_path`` when the output size differs from its source's,
+        ``_gpu_aligned_resize_path`` when the frames are not 512 x 512.  ``KEEP_AMD_STREAM_PASTE=0`` keeps the per-frame path."""
+        net = self.keep_net
+        if os.environ.get('KEEP_AMD_STREAM_PASTE', '1') == '0' or not getattr(net, 'supports_sink', False):
+            return False
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            return False
+        if getattr(net, 'pool', None) is not None or self.face_upscale_model is not None or self.bg_upscale_model is not None:
+            return False
+        f0 = frames_bgr[0]
+        if any(not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape != f0.shape or f.shape[2] != 3
+               for f in frames_bgr):
+            return False
+        h, w = f0.shape[:2]
+        if h <= 0 or w <= 0:
+            return False
+        src = (512, 512) if self.return_restored_aligned else (w, h)
+        dst = (int(src[0] * factor), int(src[1] * factor))
+        if dst[0] <= 0 or dst[1] <= 0 or (dst != src and not self._gpu_resize_path()):
+            return False
+        return (h, w) == (512, 512) or bool(self._gpu_aligned_resize_path())
+
+    def _aligned_streamed(self, frames_bgr, max_clip_length, factor, pbar, as_u8):
+        """Steps 2 - 4 of an aligned sequence (keep_processor.py:250-291 of the reference) with the frames resident on the GPU.
+
+        The frames are uploaded in chunks of at most ``KEEP_AMD_DETECT_BATCH``, each frame copied straight into the chunk's [n,H,W,3]
+        device tensor, and one ``keep_resize_linear_u8`` launch per chunk writes the chunk's 512 x 512 crops into the crop tensor of the
+        sequence (frames that are 512 x 512 are copied into it and nothing is launched).  The clips are views of that tensor, so
+        ``run_clips_u8(sink=...)`` neither stages nor uploads them.  The sink builds the output of every finished run of frames on the
+        device: by default (reference quirk P2: the restored faces are not used) the input frames at the output size, one batched
+        Lanczos launch per chunk; with ``return_restored_aligned`` the restored crops at ``int(512 * factor)``, one launch per run.
+        All of it is queued on the stream the forward runs on -- the restored crops are consumed on their producing stream -- and
+        only the finished output crosses PCIe (float RGB via ``keep_bgr_u8_to_comfy`` unless ``as_u8``).  Returns None, before anything
+        was restored, when the device resize fails."""
+        from ..engine import hiplib as L
+        net, dev = self.keep_net, torch.device(self.device)
+        if dev.index is None:
+            dev = torch.device('cuda', torch.cuda.current_device())
+        n = len(frames_bgr)
+        h, w = frames_bgr[0].shape[:2]
+        restored_out = bool(self.return_restored_aligned)
+        src_w, src_h = (512, 512) if restored_out else (w, h)
+        out_w, out_h = int(src_w * factor), int(src_h * factor)
+        chunk = max(1, int(os.environ.get('KEEP_AMD_DETECT_BATCH', '32') or 32))
+        starts = list(range(0, n, chunk))
+        keep_frames = not restored_out            # P2: the output is made of the input frames
+        with torch.cuda.device(dev):
+            crops = torch.empty((n, 512, 512, 3), dtype=torch.uint8, device=dev)
+            frames_dev = []                       # per chunk: its [m,H,W,3] input frames on the device (None once emitted / unused)
+            for a in starts:
+                part = frames_bgr[a:a + chunk]
+                buf = crops[a:a + len(part)] if (h, w) == (512, 512) else torch.empty((len(part), h, w, 3), dtype=torch.uint8, device=dev)
+                for i, fr in enumerate(part):
+                    buf[i].copy_(torch.from_numpy(np.ascontiguousarray(fr)), non_blocking=True)
+                if (h, w) != (512, 512):
+                    try:
+                        self._aligned_resize_device(buf, out=crops[a:a + len(part)])
+                    except Exception as e:              # logged, and the per-frame path (cv2) takes the sequence and every later one
+                        import logging
+                        logging.getLogger('ComfyUI-KEEP').warning("device resize of the aligned frames failed (%s): cv2.resize", e)
+                        self.gpu_aligned_resize = False
+                        return None
+                frames_dev.append(buf if keep_frames else None)
+        spans = split_clips(n, max_clip_length)
+        t1_ok = getattr(net, 'supports_single_frame', False)
+        clips = [crops[s:e] if (e - s > 1 or t1_ok) else torch.cat([crops[s:e], crops[s:e]]) for s, e in spans]   # (T >= 2: KP:173-178)
+        restored = [None] * n
+        keep_restored = self.keep_restored_faces
+        st = {'next': 0, 'out': None}
+
+        def emit(f0, frames_dev_out):
+            """finished frames f0 .. (uint8 BGR [m,H',W',3] on the device) -> the output tensor in host memory"""
+            m = frames_dev_out.shape[0]
+            if st['out'] is None:
+                shape = (n, out_h, out_w, 3)
+                try:
+                    st['out'] = torch.empty(shape, dtype=torch.uint8 if as_u8 else torch.float32, pin_memory=True)
+                except RuntimeError:                                  # more than the host will pin: pageable memory, slower copies
+                    st['out'] = torch.empty(shape, dtype=torch.uint8 if as_u8 else torch.float32)
+            if as_u8:
+                st['out'][f0:f0 + m].copy_(frames_dev_out, non_blocking=True)
+            else:                                                      # cv2_to_comfy_image on the device (keep_bgr_u8_to_comfy)
+                ff = torch.empty(frames_dev_out.shape, dtype=torch.float32, device=dev)
+                L.call('keep_bgr_u8_to_comfy', frames_dev_out.contiguous(), ff, frames_dev_out.numel() // 3)
+                st['out'][f0:f0 + m].copy_(ff, non_blocking=True)
+
+        def advance():
+            f0 = f1 = st['next']
+            while f1 < n and restored[f1] is not None:
+                f1 += 1
+            if f1 == f0:
+                return
+            with torch.cuda.device(dev):           # (the current stream: the one the forward that produced the crops was queued on)
+                if restored_out:
+                    faces = torch.stack([restored[i] for i in range(f0, f1)])
+                    emit(f0, self._lanczos_batch(faces, out_w, out_h))
+                else:
+                    for c in range(f0 // chunk, (f1 - 1) // chunk + 1):
+                        a, b = max(f0, c * chunk), min(f1, (c + 1) * chunk)
+                        emit(a, self._lanczos_batch(frames_dev[c][a - c * chunk:b - c * chunk], out_w, out_h))
+                        if b == min(n, (c + 1) * chunk):
+                            frames_dev[c] = None                       # the chunk's frames are released once all of them are out
+            if not keep_restored:
+                for i in range(f0, f1):
+                    restored[i] = _EMITTED
+            st['next'] = f1
+
+        def sink(ids, crops_list, classes_list):
+            for j, cid in enumerate(ids):
+                s, e = spans[cid]
+                for k in range(e - s):
+                    restored[s + k] = crops_list[j][k]
+            advance()
+
+        net.run_clips_u8(clips, sink=sink)
+        torch.cuda.current_stream(dev).synchronize()
+        if st['next'] != n:
+            raise RuntimeError(f"streamed aligned sequence: {n - st['next']} frame(s) never became ready")
+        pbar.update(n)
+        self.last_restored_faces = _DeviceFaces(restored) if keep_restored else []
+        return st['out']
+
     # ------------------------------------------------------------------ sequence
     def _detect_all(self, frames_bgr, only_center_face):
         """Landmarks of every frame (keep_processor.py:207-213: one ``get_face_landmarks_5`` call -- one detector forward and
@@ -964,7 +1172,8 @@ class KEEPFaceProcessor:
     def process_frames_u8(self, frames_bgr, final_upscale_factor: float = 1.0, has_aligned_frames: bool = False,
                           only_center_face: bool = True, draw_box: bool = False, max_clip_length: int = 20):
         """``process_image_sequence`` between its two ComfyUI converters: list of uint8 BGR frames -> uint8 BGR frames
-        (a [N,H',W',3] tensor from the streamed path, a list of arrays otherwise).  What a video tool that already holds
+        (a [N,H',W',3] tensor from the streamed paths -- ``_restore_and_paste_streamed``, ``_aligned_streamed`` --, a list of arrays
+        otherwise).  What a video tool that already holds
         uint8 frames calls, and what bench.py times next to the float entry point."""
         return self._process_frames(list(frames_bgr), final_upscale_factor, has_aligned_frames, only_center_face, draw_box,
                                     max_clip_length, as_u8=True)
@@ -985,12 +1194,18 @@ class KEEPFaceProcessor:
         else:
             pbar.update(n_frames * 2)
 
+        # -- 2 - 4 of an aligned sequence with its frames resident on the device
+        if has_aligned_frames and n_frames and self._aligned_stream_applies(frames_bgr, final_upscale_factor):
+            out = self._aligned_streamed(frames_bgr, max_clip_length, final_upscale_factor, pbar, as_u8)
+            if out is not None:                         # (None: the device resize failed and turned itself off)
+                return out
+
         # -- 2. crops, flat and frame-major
         crops, affines, faces_per_frame = [], [], []
         stream_ok = (not has_aligned_frames) and self._stream_applies(helper, frames_bgr, None, draw_box)
         for i in tqdm(range(n_frames), desc="Cropping and aligning faces"):
             if has_aligned_frames:
-                frame_crops, frame_aff = [_resize(frames_bgr[i], 512, 512, 'INTER_LINEAR')], []
+                frame_crops, frame_aff = [self._aligned_face(frames_bgr[i])], []
             else:
                 frame_crops, frame_aff = [], []
                 active = [seq[i] for seq in tracks.values() if not np.isnan(seq[i]).any()]

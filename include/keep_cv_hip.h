@@ -42,6 +42,17 @@ int32_t keep_resize_area_u8(const uint8_t* src, uint8_t* dst, int32_t N, int32_t
                             const int32_t* xstart, const int32_t* xsi, const float* xalpha, const int32_t* ystart, const int32_t* ysi,
                             const float* yalpha, void* stream);
 
+/* ---- aligned-face input (keep_processor.py:158,250 of the reference): cv2.resize(frame, (W2, H2), interpolation=INTER_LINEAR), uint8,
+ * 3 channels, ANY geometry (enlarging, shrinking, mixed; identity is an exact copy): OpenCV 4.x resize.cpp.
+ *
+ * keep_resize_linear_u8: N contiguous uint8 frames [N,H,W,3] -> [N,H2,W2,3] in one launch, DEVICE pointers, no tables.  Per axis
+ * scale = 1.0 / ((double)D / S); f = (float)((d + 0.5) * scale - 0.5), product and sum rounded separately in double; s = floor(f),
+ * f -= s; columns: s < 0 -> (0, f = 0), s >= S - 1 -> (S - 1, f = 0); rows are clamped to [0, S - 1] and keep their weights; weights
+ * sat_short(rint((1.f - f) * 2048)), sat_short(rint(f * 2048)); horizontal S0 * a0 + S1 * a1 in int32; vertical
+ * (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2, saturated to 0..255.  H == 2 * H2 && W == 2 * W2 is the case
+ * cv2.resize hands to INTER_AREA's 2 x 2 integer path: (a + b + c + d + 2) >> 2 per channel. */
+int32_t keep_resize_linear_u8(const uint8_t* src, uint8_t* dst, int32_t N, int32_t H, int32_t W, int32_t H2, int32_t W2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
