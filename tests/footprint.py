@@ -12,7 +12,7 @@ then judged three ways:
   bit-identical, and finite: a stray value that reaches a result -- also one that is "masked" by a multiplication with zero --
   raises ``ReadOutside``.
 * **value check** -- the zero-poison output equals the plain call (exactly sized buffers, no guards) bit for bit.  Accuracy is
-  the business of the reference tests.
+  the business of the value judges of the same cases (tests/test_gpu_case_values.py, tests/test_gpu_flat_values.py) and of the reference tests.
 
 Guard size is a condition, not a measurement: at least ``GUARD_BYTES`` (64 KiB) and at least the ``tile_bytes`` a case states
 for its kernel family (the largest block of memory one step of the kernel can touch).  Buffers whose size the library reports

@@ -2,12 +2,14 @@
 guards, strided tensors with their real ``ld`` (gap columns are surroundings), workspace / statistics partials / amax slots at
 exactly the size the library reports.  Written surroundings must stay bit-identical; the outputs must be bit-identical under
 zero / NaN / 3e38 surroundings of everything that is read, finite, and equal to the plain call.  The values of the same launches are
-judged by tests/test_gpu_case_values.py against the float64 restatement of the two ABIs in tests/abi_ref.py.
+judged by tests/test_gpu_case_values.py against the float64 restatement of the two ABIs in tests/abi_ref.py, those of the flat entry
+points by tests/test_gpu_flat_values.py against the restatements in tests/flat_ref.py.
 
 The case tables are plain data, importable without a GPU: tests/test_host_logic.py asks ``keep_conv2d_plan`` (host C) for every
 convolution case and checks that the tables reach every kernel family and name every launcher of include/keep_hip.h.
 """
 import ctypes
+import inspect
 import math
 
 import numpy as np
@@ -388,6 +390,9 @@ def test_attention_cases_reach_the_workspace_forms():
 
 
 # ------------------------------------------------------------------------------------------------ the flat entry points
+# Every builder states the parameters of its case ONCE, as its own arguments (constants such as the activation, eps or a threshold are
+# keyword defaults): ``_k`` binds them and hands them on as the third element of the case, so the launch below and the float64
+# restatement in tests/flat_ref.py read the same numbers.
 def u8(name, shape):
     return (op_input('fp:' + name, shape) * 127.5 + 127.5).clamp(0, 255).to(torch.uint8)
 
@@ -400,15 +405,25 @@ def _in(name, data, **kw):
     return FP.single(name, data, **kw)
 
 
-def _elementwise(fn, make):
-    """(regions, launch) of one flat case; ``make`` returns them."""
-    return fn, make
+def _k(cid, builder, *a, **kw):
+    """One table case: (case id, builder thunk -> (regions, launch[, canon]), the builder's bound parameters by name)."""
+    b = inspect.signature(builder).bind(*a, **kw)
+    b.apply_defaults()
+    return cid, (lambda: builder(*a, **kw)), dict(b.arguments)
 
 
-def _affine_act(n, hw, c):
+AMAX_SLOTS, AMAX_OFF = 9, 2          # the amax arena of the flat cases: the case's N slots start at slot 2 of 9
+AMAX_STALE = 3e38                    # what the case's own slots hold before a `zeroed = 0` call (the library must reset them)
+
+
+def _amax_region(n, zeroed):
+    return FP.Region(1, AMAX_SLOTS, {'amax': (AMAX_OFF, n, torch.zeros(1, n) if zeroed else torch.full((1, n), AMAX_STALE))}, F32, 'rw')
+
+
+def _affine_act(n, hw, c, act=L.ACT_RELU):
     x = rnd('aa', (n, hw, c), 2.0)
     R = [_in('x', x), _in('s', rnd('aas', (n, c)) + 1.5), _in('h', rnd('aah', (n, c))), FP.output('o', (n * hw, c))]
-    return R, lambda t: _call('keep_affine_act', t['x'], t['s'], t['h'], t['o'], n, hw, c, L.ACT_RELU)
+    return R, lambda t: _call('keep_affine_act', t['x'], t['s'], t['h'], t['o'], n, hw, c, act)
 
 
 def _gm_join(n, hw, c, with_a):
@@ -424,46 +439,49 @@ def _chan_stats(n, hw, c, ld, P):
     return R, lambda t: _call('keep_chan_stats', t['x'], t['part'], n, hw, c, ld, P)
 
 
-def _norm_finalize(n, hw, c, G, P, affine):
+def _norm_finalize(n, hw, c, G, P, affine, eps=1e-6):
     part = rnd('nf', (n, P, c, 2)).abs() * 3 + 1
     part[..., 1] = part[..., 1] + part[..., 0] ** 2          # sumsq >= sum^2 / count: a variance that is not negative
     R = [_in('part', part.reshape(1, -1)), FP.output('scale', (n, c)), FP.output('shift', (n, c))]
     if affine:
         R += [_in('g', rnd('nfg', (1, c)) + 1.5), _in('b', rnd('nfb', (1, c)))]
-    return R, lambda t: _call('keep_norm_finalize', t['part'], t.get('g'), t.get('b'), t['scale'], t['shift'], n, hw, c, G, P, 1e-6)
+    return R, lambda t: _call('keep_norm_finalize', t['part'], t.get('g'), t.get('b'), t['scale'], t['shift'], n, hw, c, G, P, eps)
 
 
-def _group_stats(n, hw, c, G):
-    R = [_in('x', rnd('gs', (n, hw, c), 2.0)), _in('g', rnd('gsg', (1, c)) + 1.5), _in('b', rnd('gsb', (1, c))), FP.output('scale', (n, c)),
-         FP.output('shift', (n, c))]
-    return R, lambda t: _call('keep_group_stats', t['x'], t['g'], t['b'], t['scale'], t['shift'], n, hw, c, G, 1e-6)
+def _group_stats(n, hw, c, G, eps=1e-6, affine=True):
+    R = [_in('x', rnd('gs', (n, hw, c), 2.0)), FP.output('scale', (n, c)), FP.output('shift', (n, c))]
+    if affine:
+        R += [_in('g', rnd('gsg', (1, c)) + 1.5), _in('b', rnd('gsb', (1, c)))]
+    return R, lambda t: _call('keep_group_stats', t['x'], t.get('g'), t.get('b'), t['scale'], t['shift'], n, hw, c, G, eps)
 
 
-def _norm_act_bf16(n, hw, c, in_bf16):
+def _norm_act_bf16(n, hw, c, in_bf16, act=L.PRO_SWISH, affine=True):
     x = rnd('nab', (n, hw, c), 2.0, BF16 if in_bf16 else F32)
-    R = [_in('x', x), _in('s', rnd('nabs', (n, c)) + 1.5), _in('h', rnd('nabh', (n, c))), FP.output('o', (n * hw, c), BF16)]
-    return R, lambda t: _call('keep_norm_act_bf16', t['x'], t['s'], t['h'], t['o'], n, hw, c, L.PRO_SWISH, L.BF16 if in_bf16 else L.F32)
+    R = [_in('x', x), FP.output('o', (n * hw, c), BF16)]
+    if affine:
+        R += [_in('s', rnd('nabs', (n, c)) + 1.5), _in('h', rnd('nabh', (n, c)))]
+    return R, lambda t: _call('keep_norm_act_bf16', t['x'], t.get('s'), t.get('h'), t['o'], n, hw, c, act, L.BF16 if in_bf16 else L.F32)
 
 
-def _absmax(n, r, c, ld):
-    R = [_in('x', rnd('am', (n * r, c), 3.0), ld=ld), FP.Region(1, 9, {'amax': (2, n, torch.zeros(1, n))}, F32, 'rw')]
-    return R, lambda t: _call('keep_absmax', t['x'], t['amax'], n, r, c, ld, r * ld, 1)
+def _absmax(n, r, c, ld, zeroed=1):
+    R = [_in('x', rnd('am', (n * r, c), 3.0), ld=ld), _amax_region(n, zeroed)]
+    return R, lambda t: _call('keep_absmax', t['x'], t['amax'], n, r, c, ld, r * ld, zeroed)
 
 
-def _layernorm(m, c, res, pos_rows):
+def _layernorm(m, c, res, pos_rows, eps=1e-5):
     R = [_in('x', rnd('ln', (m, c), 2.0)), _in('g', rnd('lng', (1, c)) + 1.5), _in('b', rnd('lnb', (1, c))), FP.output('o', (m, c))]
     if res:
         R.append(_in('res', rnd('lnr', (m, c))))
     if pos_rows:
         R += [_in('pos', rnd('lnp', (pos_rows, c))), FP.output('o2', (m, c))]
-    return R, lambda t: _call('keep_layernorm', t['x'], t['g'], t['b'], t.get('res'), t['o'], t.get('pos'), pos_rows, t.get('o2'), m, c, 1e-5)
+    return R, lambda t: _call('keep_layernorm', t['x'], t['g'], t['b'], t.get('res'), t['o'], t.get('pos'), pos_rows, t.get('o2'), m, c, eps)
 
 
-def _layernorm_amax(n, rows, c):
+def _layernorm_amax(n, rows, c, eps=1e-5, zeroed=1):
     m = n * rows
     R = [_in('x', rnd('lna', (m, c), 2.0)), _in('g', rnd('lnag', (1, c)) + 1.5), _in('b', rnd('lnab', (1, c))), _in('res', rnd('lnar', (m, c))),
-         FP.output('o', (m, c)), FP.Region(1, 9, {'amax': (2, n, torch.zeros(1, n))}, F32, 'rw')]
-    return R, lambda t: _call('keep_layernorm_amax', t['x'], t['g'], t['b'], t['res'], t['o'], m, c, 1e-5, rows, t['amax'], 1)
+         FP.output('o', (m, c)), _amax_region(n, zeroed)]
+    return R, lambda t: _call('keep_layernorm_amax', t['x'], t['g'], t['b'], t['res'], t['o'], m, c, eps, rows, t['amax'], zeroed)
 
 
 def _geglu(m, f):
@@ -471,9 +489,9 @@ def _geglu(m, f):
     return R, lambda t: _call('keep_geglu', t['x'], t['o'], m, f)
 
 
-def _geglu_amax(n, rows, f):
-    R = [_in('x', rnd('gga', (n * rows, 2 * f), 2.0)), FP.output('o', (n * rows, f)), FP.Region(1, 9, {'amax': (2, n, torch.zeros(1, n))}, F32, 'rw')]
-    return R, lambda t: _call('keep_geglu_amax', t['x'], t['o'], n, rows, f, t['amax'], 1)
+def _geglu_amax(n, rows, f, zeroed=1):
+    R = [_in('x', rnd('gga', (n * rows, 2 * f), 2.0)), FP.output('o', (n * rows, f)), _amax_region(n, zeroed)]
+    return R, lambda t: _call('keep_geglu_amax', t['x'], t['o'], n, rows, f, t['amax'], zeroed)
 
 
 def _argmax_gather(m, ncodes, dim):
@@ -532,9 +550,9 @@ def _rgb_s2d(n, h, w):
     return R, lambda t: _call('keep_rgb_s2d', t['x'], t['o'], n, h, w)
 
 
-def _add_bcast(total, tsize):
+def _add_bcast(total, tsize, alpha=-0.5):
     R = [_in('a', rnd('ab', (1, total))), _in('t', rnd('abt', (1, tsize))), FP.output('o', (1, total))]
-    return R, lambda t: _call('keep_add_bcast', t['a'], t['t'], t['o'], total, tsize, -0.5)
+    return R, lambda t: _call('keep_add_bcast', t['a'], t['t'], t['o'], total, tsize, alpha)
 
 
 def _concat2(m, c1, c2, ld):
@@ -567,10 +585,12 @@ def _maxpool3s2(n, h, w, c):
     return R, lambda t: _call('keep_maxpool3s2', t['x'], t['o'], n, h, w, c)
 
 
-def _dwconv(n, h, w, c, stride):
+def _dwconv(n, h, w, c, stride, act=L.ACT_LRELU01, bias=True):
     ho, wo = (h - 1) // stride + 1, (w - 1) // stride + 1
-    R = [_in('x', rnd('dw', (n * h * w, c))), _in('w', rnd('dww', (9, c))), _in('b', rnd('dwb', (1, c))), FP.output('o', (n * ho * wo, c))]
-    return R, lambda t: _call('keep_dwconv3x3', t['x'], t['w'], t['b'], t['o'], n, h, w, c, stride, L.ACT_LRELU01)
+    R = [_in('x', rnd('dw', (n * h * w, c))), _in('w', rnd('dww', (9, c))), FP.output('o', (n * ho * wo, c))]
+    if bias:
+        R.append(_in('b', rnd('dwb', (1, c))))
+    return R, lambda t: _call('keep_dwconv3x3', t['x'], t['w'], t.get('b'), t['o'], n, h, w, c, stride, act)
 
 
 def _maxpool2d(n, h, w, c, in_ld, out_ld, k, stride, pad, ceil):
@@ -592,16 +612,16 @@ def _channel_shuffle2(rows, half, a_ld, b_ld):
     return R, lambda t: _call('keep_channel_shuffle2', t['a'], t['b'], t['o'], rows, half, a_ld, b_ld)
 
 
-def _yolo_decode(n, ny, nx):
-    rows_total = 3 * ny * nx + 7
+def _yolo_decode(n, ny, nx, stride=8.0, row0=5, rows_after=2):
+    rows_total = row0 + 3 * ny * nx + rows_after
     R = [_in('raw', rnd('yd', (n * ny * nx, 48), 3.0)), _in('anch', rnd('yda', (1, 6)).abs() * 30 + 4),
          FP.output('pred', (n * rows_total, 16), init=torch.zeros(n * rows_total, 16))]
-    return R, lambda t: _call('keep_yolo_decode', t['raw'], t['pred'], n, ny, nx, 8.0, t['anch'], 5, rows_total)
+    return R, lambda t: _call('keep_yolo_decode', t['raw'], t['pred'], n, ny, nx, stride, t['anch'], row0, rows_total)
 
 
-def _yolo_letterbox(n, h, w, rh, rw, top, left, h2, w2):
+def _yolo_letterbox(n, h, w, rh, rw, top, left, h2, w2, swap_rb=1):
     R = [_in('x', u8('lb', (n * h * w, 3))), FP.output('o', (n * h2 * w2, 3))]
-    return R, lambda t: _call('keep_yolo_letterbox_u8', t['x'], t['o'], n, h, w, rh, rw, top, left, h2, w2, 1)
+    return R, lambda t: _call('keep_yolo_letterbox_u8', t['x'], t['o'], n, h, w, rh, rw, top, left, h2, w2, swap_rb)
 
 
 def _canon_dets(n, cap):
@@ -617,11 +637,11 @@ def _canon_dets(n, cap):
     return canon
 
 
-def _yolo_select(n, p, cap):
+def _yolo_select(n, p, cap, thr=0.3):
     pred = rnd('ys', (n, p, 16)).abs()
     R = [_in('pred', pred.reshape(n * p, 16)), FP.output('dets', (n * cap, 16), init=torch.zeros(n * cap, 16)),
          FP.Region(1, n + 4, {'counts': (2, n, torch.zeros(1, n, dtype=torch.int32))}, torch.int32, 'rw')]
-    return R, lambda t: _call('keep_yolo_select', t['pred'], t['dets'], t['counts'], n, p, cap, 0.3), _canon_dets(n, cap)
+    return R, lambda t: _call('keep_yolo_select', t['pred'], t['dets'], t['counts'], n, p, cap, thr), _canon_dets(n, cap)
 
 
 def _upsample_add(n, h, w, hb, wb, c):
@@ -643,27 +663,26 @@ def _sorted_dets(n, cap, cnt):
     return d
 
 
-def _retina_nms(n, cap, cnt, ordered):
+def _retina_nms(n, cap, cnt, ordered, iou=0.4):
     d = _sorted_dets(n, cap, cnt)
     counts = torch.tensor([cnt], dtype=torch.int32).repeat(1, n)
     counts[0, -1] = max(cnt - 3, 0)
     R = [_in('dets', d.reshape(n * cap, 16)), _in('counts', counts), FP.output('o', (n * cap, 16), init=torch.zeros(n * cap, 16)),
          FP.output('oc', (1, n), torch.int32)]
     if ordered:
-        order = torch.stack([torch.argsort(d[i, :, 4], descending=True).to(torch.int32) for i in range(n)])
         # ranks 0 .. counts[n] must name valid rows: order the valid rows only
         order = torch.stack([torch.argsort(torch.where(torch.arange(cap) < int(counts[0, i]), d[i, :, 4], torch.tensor(-1.0)),
                                            descending=True).to(torch.int32) for i in range(n)])
         R.append(_in('order', order.reshape(n, cap)))
-        return R, lambda t: _call('keep_retina_nms_ordered', t['dets'], t['counts'], t['order'], t['o'], t['oc'], n, cap, 0.4)
-    return R, lambda t: _call('keep_retina_nms', t['dets'], t['counts'], t['o'], t['oc'], n, cap, 0.4)
+        return R, lambda t: _call('keep_retina_nms_ordered', t['dets'], t['counts'], t['order'], t['o'], t['oc'], n, cap, iou)
+    return R, lambda t: _call('keep_retina_nms', t['dets'], t['counts'], t['o'], t['oc'], n, cap, iou)
 
 
-def _retina_decode(n, p, cap):
+def _retina_decode(n, p, cap, var0=0.1, var1=0.2, sx=640.0, sy=480.0, thr=0.5):
     R = [_in('heads', rnd('rd', (n * p, 32), 2.0)), _in('priors', rnd('rdp', (2 * p, 4)).abs() * 0.5 + 0.05),
          FP.output('dets', (n * cap, 16), init=torch.zeros(n * cap, 16)),
          FP.Region(1, n + 4, {'counts': (2, n, torch.zeros(1, n, dtype=torch.int32))}, torch.int32, 'rw')]
-    return R, lambda t: _call('keep_retina_decode', t['heads'], t['priors'], t['dets'], t['counts'], n, p, cap, 0.1, 0.2, 640.0, 480.0, 0.5), _canon_dets(n, cap)
+    return R, lambda t: _call('keep_retina_decode', t['heads'], t['priors'], t['dets'], t['counts'], n, p, cap, var0, var1, sx, sy, thr), _canon_dets(n, cap)
 
 
 def _gauss(ntap):
@@ -699,9 +718,9 @@ def _d2s(m):
 _HANG = (0.93, -0.37, -6.3, 0.37, 0.93, -4.8)
 
 
-def _warp_affine(h, w, dh, dw, m):
+def _warp_affine(h, w, dh, dw, m, border=(135, 133, 132)):
     R = [_in('src', u8('wa', (h * w, 3))), FP.output('dst', (dh * dw, 3), torch.uint8)]
-    return R, lambda t: _call('keep_warp_affine_u8', t['src'], h, w, t['dst'], dh, dw, _d2s(m), 135, 133, 132)
+    return R, lambda t: _call('keep_warp_affine_u8', t['src'], h, w, t['dst'], dh, dw, _d2s(m), *border)
 
 
 def _warp_ones(h, w, fh, fw, m):
@@ -714,18 +733,18 @@ def _erode(h, w, k):
     return R, lambda t: _call('keep_erode_rect', t['src'], t['tmp'], t['dst'], h, w, k)
 
 
-def _draw_box(h, w, fh, fw, m, box):
+def _draw_box(h, w, fh, fw, m, box, thickness=2):
     R = [FP.single('frame', u8('db', (h * w, 3)), role='rw')]
-    return R, lambda t: _call('keep_draw_box', t['frame'], h, w, fh, fw, 2, _d2s(m), *box)
+    return R, lambda t: _call('keep_draw_box', t['frame'], h, w, fh, fw, thickness, _d2s(m), *box)
 
 
-def _paste_face(h, w, fh, fw, m, box, frame_mask):
+def _paste_face(h, w, fh, fw, m, box, frame_mask, mask_border=3):
     R = [FP.single('frame', rnd('pf', (h * w, 3)).abs() * 255, role='rw'), _in('face', u8('pff', (fh * fw, 3)))]
     if frame_mask:      # a soft mask already in frame space [H, W]
         R.append(_in('mask', rnd('pfm', (h, w)).abs()))
     else:
         R.append(_in('mask', rnd('pfm', (fh, fw)).abs() * 255))
-    return R, lambda t: _call('keep_paste_face', t['frame'], h, w, t['face'], t['mask'], fh, fw, _d2s(m), *box, -1 if frame_mask else 3)
+    return R, lambda t: _call('keep_paste_face', t['frame'], h, w, t['face'], t['mask'], fh, fw, _d2s(m), *box, -1 if frame_mask else mask_border)
 
 
 def _lanczos(n, h, w, h2, w2):
@@ -740,91 +759,136 @@ def _lanczos(n, h, w, h2, w2):
     return R, lambda t: _call('keep_resize_lanczos4_u8', t['src'], t['dst'], n, h, w, h2, w2, t['xo'], t['xc'], t['yo'], t['yc'])
 
 
-def _token_linear(m, n_out, out_bf16):
-    R = [_in('x', rnd('tl', (m, 128))), _in('w', rnd('tlw', (n_out, 128), 0.1, BF16)), _in('b', rnd('tlb', (1, n_out))),
-         FP.output('o', (m, n_out), BF16 if out_bf16 else F32)]
-    return R, lambda t: _call('keep_token_linear', t['x'], t['w'], t['b'], t['o'], m, 128, n_out, L.BF16 if out_bf16 else L.F32)
+def _token_linear(m, n_out, out_bf16, k=128, bias=True):
+    R = [_in('x', rnd('tl', (m, k))), _in('w', rnd('tlw', (n_out, k), 0.1, BF16)), FP.output('o', (m, n_out), BF16 if out_bf16 else F32)]
+    if bias:
+        R.append(_in('b', rnd('tlb', (1, n_out))))
+    return R, lambda t: _call('keep_token_linear', t['x'], t['w'], t.get('b'), t['o'], m, k, n_out, L.BF16 if out_bf16 else L.F32)
 
 
-def _gm_mlp(m):
-    C = 128
+def _gm_mlp(m, c=128):
+    C = c
     R = [_in('a', rnd('ma', (m, C))), _in('b', rnd('mb', (m, C))), _in('w0', rnd('mw0', (8 * C, 2 * C), 0.05, BF16)),
          _in('w2', rnd('mw2', (C, 8 * C), 0.05, BF16)), FP.output('o', (m, C))]
     return R, lambda t: _call('keep_gm_mlp', t['a'], t['b'], t['w0'], t['w2'], t['o'], m, C)
 
 
-def _gm_ffn_x3(m, hidden):
-    C = 128
-    w0, w2 = rnd('fw0', (hidden, 2 * C), 0.05), ops.ffn_w2_perm(rnd('fw2', (C, hidden), 0.05))
+def gm_ffn_weights(hidden, c=128):
+    """The plain fp32 weights W0 [hidden, 2C] / W2 [C, hidden] the keep_gm_ffn_x3 cases split into fp16 halves (the reference reads these)."""
+    return rnd('fw0', (hidden, 2 * c), 0.05), rnd('fw2', (c, hidden), 0.05)
+
+
+def _gm_ffn_x3(m, hidden, c=128, eps=1e-5, exact_act=0):
+    C = c
+    w0, w2 = gm_ffn_weights(hidden, C)
+    w2 = ops.ffn_w2_perm(w2)
     s0, s2 = ops.x3_scale_for(float(w0.abs().max())), ops.x3_scale_for(float(w2.abs().max()))
     w0x, w2x = ops.split_x3(w0, s0), ops.split_x3(w2, s2)
     R = [_in('src', rnd('fs', (m, C))), _in('msg', rnd('fm', (m, C))), _in('w0', w0x.reshape(hidden, -1)), _in('w2', w2x.reshape(C, -1)),
          _in('g', rnd('fg', (1, C)) * 0.2 + 1), _in('b', rnd('fb', (1, C)) * 0.2), FP.output('o', (m, C))]
-    return R, lambda t: _call('keep_gm_ffn_x3', t['src'], t['msg'], t['w0'], 1.0 / s0, t['w2'], 1.0 / s2, t['g'], t['b'], 1e-5, t['o'], m, C, hidden, 0)
+    return R, lambda t: _call('keep_gm_ffn_x3', t['src'], t['msg'], t['w0'], 1.0 / s0, t['w2'], 1.0 / s2, t['g'], t['b'], eps, t['o'], m, C, hidden, exact_act)
 
 
-# entry point -> [(case id, builder)]: one aligned and one ragged size each (element counts that are no multiple of 4, odd H / W,
-# C off the vector width where the ABI allows it, M off the block), border-crossing geometry for the samplers
+# entry point -> [(case id, builder thunk, parameters)]: one aligned and one ragged size each (element counts that are no multiple of 4,
+# odd H / W, C off the vector width where the ABI allows it, M off the block), border-crossing geometry for the samplers.  The values
+# of every case are judged by tests/test_gpu_flat_values.py against tests/flat_ref.py.
+#
+# Branches of the launchers (csrc/keep_ops.hip, csrc/keep_paste.hip) and the case that reaches each:
+#   keep_chan_stats    one `cbase` pass, several pixels per pass (C = 64: 4 rows)      -> aligned
+#                      C < 256 not dividing 256 (C = 6: 42 rows, idle lanes)           -> ragged
+#                      two `cbase` passes, the second 64 wide (C = 320)                -> c320
+#                      P not dividing HW (35 pixels in 4 chunks of 9, 9, 9, 8)         -> p_ragged
+#   keep_layernorm     layernorm_kernel, C % 4 == 0                                    -> aligned (M = 64 < 4096), ragged (C = 36)
+#                      layernorm128_kernel (C == 128, M >= 4096), ragged last block    -> c128_stream
+#   keep_absmax        dense rows (ld == C)                                            -> aligned
+#                      scalar channel slice (C % 4 != 0, ld > C)                       -> ragged
+#                      vectorised channel slice (C % 4 == 0, ld > C); 300 float4s per image,
+#                      so the (row, column) walk takes a second step that wraps the column  -> slice_vec4
+#                      absmax_zero_kernel (zeroed = 0)                                 -> unzeroed
+#   keep_layernorm_amax / keep_geglu_amax   the library's own zero-fill (zeroed = 0)   -> unzeroed
+#   keep_group_stats   scalar form (C / G = 2) -> aligned; float4 form (C / G = 4) -> ragged; NULL gamma / beta, one channel per group -> instance_no_affine
+#   keep_norm_act_bf16 float32 input, swish -> aligned; bf16 input -> ragged_bf16in; NULL scale / shift (plain cast), no activation -> cast_only;
+#                      ReLU -> relu_bf16in
+#   keep_layernorm_amax  one atomic per block (its four rows in one image) -> aligned; per wave (a block across two images, rows beyond M) -> ragged
+#   keep_comfy_to_bgr_u8  four-pixel body -> aligned; body + three-pixel tail -> ragged; tail without a body -> tail_only
+#   keep_token_linear  N = 128 -> aligned; N = 384, bf16 output -> ragged_bf16out; N = 256, NULL bias, M below one tile -> n256_no_bias
+#   keep_affine_act / keep_gm_join   float4 form (C % 4 == 0) -> aligned; scalar form (C = 6) -> ragged
+#   keep_act_inplace   float4 body -> aligned (ReLU); float4 body + scalar tail is not reachable (n % 4 == 0 is required): the ragged case
+#                      has 195 float4s, no multiple of the block; the exp-based SiLU -> ragged; erff GELU -> gelu; leaky 0.1 -> lrelu01
+#   keep_sep_filter    float source, 5 taps -> float; class map through the LUT, 9 taps wider than the 5 x 7 image -> classes_ragged
+#   keep_dwconv3x3     stride 1 -> aligned; stride 2 on an odd map -> ragged_s2; no bias, no activation -> no_bias
+#   keep_yolo_select / keep_retina_decode   every frame fits -> aligned; a fitting frame beside overflowing ones -> ragged_overflow
+# caps of the two compacting selectors: `aligned` holds every frame's survivors, `ragged_overflow` holds those of at least one frame and
+# overflows on another (tests/test_host_logic.py asserts both from the float64 reference)
+YS_CAP_ALIGNED, YS_CAP_RAGGED, RD_CAP_ALIGNED, RD_CAP_RAGGED = 128, 8, 512, 33
 FLAT_CASES = {
-    'keep_chan_stats': [('aligned', lambda: _chan_stats(2, 256, 64, 64, 4)), ('ragged', lambda: _chan_stats(3, 35, 6, 9, 2))],
-    'keep_norm_finalize': [('gn32', lambda: _norm_finalize(2, 256, 64, 32, 4, True)), ('in', lambda: _norm_finalize(3, 35, 6, 6, 2, False))],
-    'keep_group_stats': [('aligned', lambda: _group_stats(2, 64, 64, 32)), ('ragged', lambda: _group_stats(3, 35, 12, 3))],
-    'keep_affine_act': [('aligned', lambda: _affine_act(2, 64, 32)), ('ragged', lambda: _affine_act(3, 35, 6))],
-    'keep_norm_act_bf16': [('aligned', lambda: _norm_act_bf16(2, 64, 32, False)), ('ragged_bf16in', lambda: _norm_act_bf16(3, 35, 8, True))],
-    'keep_gm_mlp': [('aligned', lambda: _gm_mlp(256)), ('ragged', lambda: _gm_mlp(300))],
-    'keep_gm_ffn_x3': [('aligned', lambda: _gm_ffn_x3(256, 256)), ('ragged', lambda: _gm_ffn_x3(777, 96))],
-    'keep_token_linear': [('aligned', lambda: _token_linear(256, 128, False)), ('ragged_bf16out', lambda: _token_linear(777, 384, True))],
-    'keep_gm_join': [('aligned', lambda: _gm_join(2, 64, 32, True)), ('ragged_identity', lambda: _gm_join(3, 35, 6, False))],
-    'keep_absmax': [('aligned', lambda: _absmax(2, 64, 32, 32)), ('ragged', lambda: _absmax(3, 35, 6, 9))],
-    'keep_layernorm': [('aligned', lambda: _layernorm(64, 128, True, 16)), ('ragged', lambda: _layernorm(35, 36, False, 0))],
-    'keep_geglu': [('aligned', lambda: _geglu(64, 128)), ('ragged', lambda: _geglu(35, 20))],
-    'keep_layernorm_amax': [('aligned', lambda: _layernorm_amax(2, 64, 128)), ('ragged', lambda: _layernorm_amax(3, 35, 36))],
-    'keep_geglu_amax': [('aligned', lambda: _geglu_amax(2, 64, 128)), ('ragged', lambda: _geglu_amax(3, 35, 20))],
-    'keep_argmax_gather': [('aligned', lambda: _argmax_gather(64, 1024, 256)), ('ragged', lambda: _argmax_gather(35, 1024, 256))],
-    'keep_nonfinite_flag': [('aligned', lambda: _nonfinite_flag(4096)), ('ragged', lambda: _nonfinite_flag(777))],
-    'keep_vq_nearest': [('aligned', lambda: _vq_nearest(64, 1024, 256)), ('ragged', lambda: _vq_nearest(35, 1024, 256))],
-    'keep_kalman_update': [('aligned', lambda: _kalman(2, 64, 32)), ('ragged', lambda: _kalman(3, 35, 6))],
-    'keep_flow_warp': [('aligned', lambda: _flow_warp(2, 8, 16, 4)), ('ragged_3ch', lambda: _flow_warp(3, 5, 7, 3)),
-                       ('one_pixel', lambda: _flow_warp(1, 1, 1, 3))],
-    'keep_convex_upsample': [('aligned', lambda: _convex_upsample(2, 8, 8, 4)), ('ragged', lambda: _convex_upsample(3, 5, 7, 8))],
-    'keep_bilinear_upscale': [('aligned', lambda: _bilinear_upscale(3, 8, 8, 4)), ('ragged', lambda: _bilinear_upscale(9, 5, 7, 4))],
-    'keep_nchw_to_nhwc': [('aligned', lambda: _nchw_to_nhwc(2, 16, 64, 0)), ('ragged_gm', lambda: _nchw_to_nhwc(3, 3, 35, 1))],
-    'keep_rgb_s2d': [('aligned', lambda: _rgb_s2d(2, 16, 16)), ('ragged', lambda: _rgb_s2d(3, 10, 14))],
-    'keep_nhwc_to_nchw': [('aligned', lambda: _nhwc_to_nchw(2, 32, 64)), ('ragged', lambda: _nhwc_to_nchw(3, 3, 35))],
-    'keep_add_bcast': [('aligned', lambda: _add_bcast(4096, 256)), ('ragged', lambda: _add_bcast(777, 37))],
-    'keep_concat2': [('aligned', lambda: _concat2(64, 128, 2, 144)), ('ragged', lambda: _concat2(35, 5, 2, 9))],
-    'keep_tensor2img': [('aligned', lambda: _tensor2img(256)), ('ragged', lambda: _tensor2img(35))],
-    'keep_img2tensor': [('aligned', lambda: _img2tensor(256)), ('ragged', lambda: _img2tensor(35))],
-    'keep_bgr_u8_to_comfy': [('aligned', lambda: _img2tensor(256, 'keep_bgr_u8_to_comfy')), ('ragged', lambda: _img2tensor(35, 'keep_bgr_u8_to_comfy'))],
-    'keep_comfy_to_bgr_u8': [('aligned', lambda: _comfy_to_bgr(256)), ('ragged', lambda: _comfy_to_bgr(35))],
-    'keep_channel_argmax': [('aligned', lambda: _channel_argmax(256, 19, 32)), ('ragged', lambda: _channel_argmax(35, 19, 19))],
-    'keep_maxpool3s2': [('aligned', lambda: _maxpool3s2(2, 8, 8, 64)), ('ragged', lambda: _maxpool3s2(3, 5, 7, 12))],
-    'keep_dwconv3x3': [('aligned', lambda: _dwconv(2, 8, 8, 32, 1)), ('ragged_s2', lambda: _dwconv(3, 5, 7, 12, 2))],
-    'keep_retina_nms': [('aligned', lambda: _retina_nms(2, 64, 64, False)), ('ragged', lambda: _retina_nms(3, 50, 37, False))],
-    'keep_retina_nms_ordered': [('aligned', lambda: _retina_nms(2, 64, 64, True)), ('ragged', lambda: _retina_nms(3, 50, 37, True))],
-    'keep_maxpool2d': [('stem_ceil', lambda: _maxpool2d(3, 5, 7, 8, 8, 16, 2, 2, 0, True)), ('spp', lambda: _maxpool2d(1, 5, 7, 4, 16, 16, 5, 1, 2, False))],
-    'keep_slice_copy': [('aligned', lambda: _slice_copy(2, 8, 8, 32, 32, 64, 0)), ('ragged_up', lambda: _slice_copy(3, 10, 14, 4, 12, 24, 1))],
-    'keep_channel_shuffle2': [('aligned', lambda: _channel_shuffle2(64, 32, 64, 32)), ('ragged', lambda: _channel_shuffle2(35, 4, 12, 12))],
-    'keep_yolo_decode': [('aligned', lambda: _yolo_decode(2, 8, 8)), ('ragged', lambda: _yolo_decode(3, 5, 7))],
-    'keep_yolo_letterbox_u8': [('resize', lambda: _yolo_letterbox(2, 20, 30, 16, 24, 4, 4, 24, 32)), ('copy_ragged', lambda: _yolo_letterbox(3, 5, 7, 5, 7, 1, 0, 7, 7)),
-                               ('one_pixel', lambda: _yolo_letterbox(1, 9, 11, 1, 1, 0, 0, 1, 1))],
-    'keep_yolo_select': [('aligned', lambda: _yolo_select(2, 256, 64)), ('ragged_overflow', lambda: _yolo_select(3, 35, 5))],
-    'keep_upsample_add': [('aligned', lambda: _upsample_add(2, 10, 14, 5, 7, 64)), ('ragged', lambda: _upsample_add(3, 9, 13, 5, 7, 12))],
-    'keep_act_inplace': [('aligned', lambda: _act_inplace(4096, L.ACT_RELU)), ('ragged', lambda: _act_inplace(780, L.ACT_SILU))],
-    'keep_retina_decode': [('aligned', lambda: _retina_decode(2, 256, 64)), ('ragged_overflow', lambda: _retina_decode(3, 35, 5))],
-    'keep_sep_filter': [('float', lambda: _sep_filter(2, 16, 16, 5, False)), ('classes_ragged', lambda: _sep_filter(3, 5, 7, 9, True))],
-    'keep_u8_to_f32': [('aligned', lambda: _u8_to_f32(4096)), ('ragged', lambda: _u8_to_f32(777))],
-    'keep_f32_round_u8': [('aligned', lambda: _f32_round_u8(4096)), ('ragged', lambda: _f32_round_u8(777))],
-    'keep_warp_affine_u8': [('inside', lambda: _warp_affine(16, 16, 8, 8, (1, 0, 2.5, 0, 1, 3.25))), ('hangs_over', lambda: _warp_affine(13, 17, 11, 9, _HANG)),
-                            ('one_pixel', lambda: _warp_affine(5, 7, 1, 1, (1, 0, 6.5, 0, 1, 4.5)))],
-    'keep_warp_ones': [('inside', lambda: _warp_ones(16, 16, 8, 8, (1, 0, -2.5, 0, 1, -3.25))), ('off_frame', lambda: _warp_ones(13, 17, 11, 9, _HANG))],
-    'keep_draw_box': [('inside', lambda: _draw_box(16, 16, 8, 8, (1, 0, -2.5, 0, 1, -3.25), (2, 3, 12, 13))),
-                      ('edge', lambda: _draw_box(13, 17, 11, 9, _HANG, (0, 0, 17, 13)))],
-    'keep_erode_rect': [('aligned', lambda: _erode(16, 16, 3)), ('k_larger_than_image', lambda: _erode(5, 7, 9))],
-    'keep_paste_face': [('inside', lambda: _paste_face(16, 16, 8, 8, (1, 0, -2.5, 0, 1, -3.25), (2, 3, 12, 13), False)),
-                        ('over_the_edge', lambda: _paste_face(13, 17, 11, 9, _HANG, (0, 0, 17, 13), False)),
-                        ('frame_mask', lambda: _paste_face(13, 17, 11, 9, _HANG, (5, 0, 17, 9), True))],
-    'keep_resize_lanczos4_u8': [('up', lambda: _lanczos(2, 8, 8, 16, 16)), ('ragged', lambda: _lanczos(3, 5, 7, 3, 100)), ('one_pixel', lambda: _lanczos(1, 5, 7, 1, 1))],
+    'keep_chan_stats': [_k('aligned', _chan_stats, 2, 256, 64, 64, 4), _k('ragged', _chan_stats, 3, 35, 6, 9, 2), _k('c320', _chan_stats, 2, 40, 320, 320, 2),
+                        _k('p_ragged', _chan_stats, 3, 35, 6, 9, 4)],
+    'keep_norm_finalize': [_k('gn32', _norm_finalize, 2, 256, 64, 32, 4, True), _k('in', _norm_finalize, 3, 35, 6, 6, 2, False)],
+    'keep_group_stats': [_k('aligned', _group_stats, 2, 64, 64, 32), _k('ragged', _group_stats, 3, 35, 12, 3),
+                         _k('instance_no_affine', _group_stats, 3, 35, 12, 12, eps=1e-5, affine=False)],
+    'keep_affine_act': [_k('aligned', _affine_act, 2, 64, 32), _k('ragged', _affine_act, 3, 35, 6)],
+    'keep_norm_act_bf16': [_k('aligned', _norm_act_bf16, 2, 64, 32, False), _k('ragged_bf16in', _norm_act_bf16, 3, 35, 8, True),
+                           _k('cast_only', _norm_act_bf16, 3, 35, 8, False, act=L.PRO_NONE, affine=False), _k('relu_bf16in', _norm_act_bf16, 3, 35, 8, True, act=L.PRO_RELU)],
+    'keep_gm_mlp': [_k('aligned', _gm_mlp, 256), _k('ragged', _gm_mlp, 300)],
+    'keep_gm_ffn_x3': [_k('aligned', _gm_ffn_x3, 256, 256), _k('ragged', _gm_ffn_x3, 777, 96)],
+    'keep_token_linear': [_k('aligned', _token_linear, 256, 128, False), _k('ragged_bf16out', _token_linear, 777, 384, True),
+                          _k('n256_no_bias', _token_linear, 35, 256, False, bias=False)],
+    'keep_gm_join': [_k('aligned', _gm_join, 2, 64, 32, True), _k('ragged_identity', _gm_join, 3, 35, 6, False)],
+    'keep_absmax': [_k('aligned', _absmax, 2, 64, 32, 32), _k('ragged', _absmax, 3, 35, 6, 9), _k('slice_vec4', _absmax, 3, 100, 12, 20),
+                    _k('unzeroed', _absmax, 3, 35, 6, 9, zeroed=0)],
+    'keep_layernorm': [_k('aligned', _layernorm, 64, 128, True, 16), _k('ragged', _layernorm, 35, 36, False, 0),
+                       _k('c128_stream', _layernorm, 4099, 128, True, 0)],
+    'keep_geglu': [_k('aligned', _geglu, 64, 128), _k('ragged', _geglu, 35, 20)],
+    'keep_layernorm_amax': [_k('aligned', _layernorm_amax, 2, 64, 128), _k('ragged', _layernorm_amax, 3, 35, 36),
+                            _k('unzeroed', _layernorm_amax, 3, 35, 36, zeroed=0)],
+    'keep_geglu_amax': [_k('aligned', _geglu_amax, 2, 64, 128), _k('ragged', _geglu_amax, 3, 35, 20), _k('unzeroed', _geglu_amax, 3, 35, 20, zeroed=0)],
+    'keep_argmax_gather': [_k('aligned', _argmax_gather, 64, 1024, 256), _k('ragged', _argmax_gather, 35, 1024, 256)],
+    'keep_nonfinite_flag': [_k('aligned', _nonfinite_flag, 4096), _k('ragged', _nonfinite_flag, 777)],
+    'keep_vq_nearest': [_k('aligned', _vq_nearest, 64, 1024, 256), _k('ragged', _vq_nearest, 35, 1024, 256)],
+    'keep_kalman_update': [_k('aligned', _kalman, 2, 64, 32), _k('ragged', _kalman, 3, 35, 6)],
+    'keep_flow_warp': [_k('aligned', _flow_warp, 2, 8, 16, 4), _k('ragged_3ch', _flow_warp, 3, 5, 7, 3), _k('one_pixel', _flow_warp, 1, 1, 1, 3)],
+    'keep_convex_upsample': [_k('aligned', _convex_upsample, 2, 8, 8, 4), _k('ragged', _convex_upsample, 3, 5, 7, 8)],
+    'keep_bilinear_upscale': [_k('aligned', _bilinear_upscale, 3, 8, 8, 4), _k('ragged', _bilinear_upscale, 9, 5, 7, 4)],
+    'keep_nchw_to_nhwc': [_k('aligned', _nchw_to_nhwc, 2, 16, 64, 0), _k('ragged_gm', _nchw_to_nhwc, 3, 3, 35, 1)],
+    'keep_rgb_s2d': [_k('aligned', _rgb_s2d, 2, 16, 16), _k('ragged', _rgb_s2d, 3, 10, 14)],
+    'keep_nhwc_to_nchw': [_k('aligned', _nhwc_to_nchw, 2, 32, 64), _k('ragged', _nhwc_to_nchw, 3, 3, 35)],
+    'keep_add_bcast': [_k('aligned', _add_bcast, 4096, 256), _k('ragged', _add_bcast, 777, 37)],
+    'keep_concat2': [_k('aligned', _concat2, 64, 128, 2, 144), _k('ragged', _concat2, 35, 5, 2, 9)],
+    'keep_tensor2img': [_k('aligned', _tensor2img, 256), _k('ragged', _tensor2img, 35)],
+    'keep_img2tensor': [_k('aligned', _img2tensor, 256), _k('ragged', _img2tensor, 35)],
+    'keep_bgr_u8_to_comfy': [_k('aligned', _img2tensor, 256, 'keep_bgr_u8_to_comfy'), _k('ragged', _img2tensor, 35, 'keep_bgr_u8_to_comfy')],
+    'keep_comfy_to_bgr_u8': [_k('aligned', _comfy_to_bgr, 256), _k('ragged', _comfy_to_bgr, 35), _k('tail_only', _comfy_to_bgr, 3)],
+    'keep_channel_argmax': [_k('aligned', _channel_argmax, 256, 19, 32), _k('ragged', _channel_argmax, 35, 19, 19)],
+    'keep_maxpool3s2': [_k('aligned', _maxpool3s2, 2, 8, 8, 64), _k('ragged', _maxpool3s2, 3, 5, 7, 12)],
+    'keep_dwconv3x3': [_k('aligned', _dwconv, 2, 8, 8, 32, 1), _k('ragged_s2', _dwconv, 3, 5, 7, 12, 2),
+                       _k('no_bias', _dwconv, 1, 5, 7, 4, 1, act=L.ACT_NONE, bias=False)],
+    'keep_retina_nms': [_k('aligned', _retina_nms, 2, 64, 64, False), _k('ragged', _retina_nms, 3, 50, 37, False)],
+    'keep_retina_nms_ordered': [_k('aligned', _retina_nms, 2, 64, 64, True), _k('ragged', _retina_nms, 3, 50, 37, True)],
+    'keep_maxpool2d': [_k('stem_ceil', _maxpool2d, 3, 5, 7, 8, 8, 16, 2, 2, 0, True), _k('spp', _maxpool2d, 1, 5, 7, 4, 16, 16, 5, 1, 2, False)],
+    'keep_slice_copy': [_k('aligned', _slice_copy, 2, 8, 8, 32, 32, 64, 0), _k('ragged_up', _slice_copy, 3, 10, 14, 4, 12, 24, 1)],
+    'keep_channel_shuffle2': [_k('aligned', _channel_shuffle2, 64, 32, 64, 32), _k('ragged', _channel_shuffle2, 35, 4, 12, 12)],
+    'keep_yolo_decode': [_k('aligned', _yolo_decode, 2, 8, 8), _k('ragged', _yolo_decode, 3, 5, 7)],
+    'keep_yolo_letterbox_u8': [_k('resize', _yolo_letterbox, 2, 20, 30, 16, 24, 4, 4, 24, 32), _k('copy_ragged', _yolo_letterbox, 3, 5, 7, 5, 7, 1, 0, 7, 7),
+                               _k('one_pixel', _yolo_letterbox, 1, 9, 11, 1, 1, 0, 0, 1, 1)],
+    'keep_yolo_select': [_k('aligned', _yolo_select, 2, 256, YS_CAP_ALIGNED), _k('ragged_overflow', _yolo_select, 3, 35, YS_CAP_RAGGED)],
+    'keep_upsample_add': [_k('aligned', _upsample_add, 2, 10, 14, 5, 7, 64), _k('ragged', _upsample_add, 3, 9, 13, 5, 7, 12)],
+    'keep_act_inplace': [_k('aligned', _act_inplace, 4096, L.ACT_RELU), _k('ragged', _act_inplace, 780, L.ACT_SILU), _k('gelu', _act_inplace, 780, L.ACT_GELU),
+                         _k('lrelu01', _act_inplace, 780, L.ACT_LRELU01)],
+    'keep_retina_decode': [_k('aligned', _retina_decode, 2, 256, RD_CAP_ALIGNED), _k('ragged_overflow', _retina_decode, 3, 35, RD_CAP_RAGGED)],
+    'keep_sep_filter': [_k('float', _sep_filter, 2, 16, 16, 5, False), _k('classes_ragged', _sep_filter, 3, 5, 7, 9, True)],
+    'keep_u8_to_f32': [_k('aligned', _u8_to_f32, 4096), _k('ragged', _u8_to_f32, 777)],
+    'keep_f32_round_u8': [_k('aligned', _f32_round_u8, 4096), _k('ragged', _f32_round_u8, 777)],
+    'keep_warp_affine_u8': [_k('inside', _warp_affine, 16, 16, 8, 8, (1, 0, 2.5, 0, 1, 3.25)), _k('hangs_over', _warp_affine, 13, 17, 11, 9, _HANG),
+                            _k('one_pixel', _warp_affine, 5, 7, 1, 1, (1, 0, 6.5, 0, 1, 4.5))],
+    'keep_warp_ones': [_k('inside', _warp_ones, 16, 16, 8, 8, (1, 0, -2.5, 0, 1, -3.25)), _k('off_frame', _warp_ones, 13, 17, 11, 9, _HANG)],
+    'keep_draw_box': [_k('inside', _draw_box, 16, 16, 8, 8, (1, 0, -2.5, 0, 1, -3.25), (2, 3, 12, 13)),
+                      _k('edge', _draw_box, 13, 17, 11, 9, _HANG, (0, 0, 17, 13))],
+    'keep_erode_rect': [_k('aligned', _erode, 16, 16, 3), _k('k_larger_than_image', _erode, 5, 7, 9)],
+    'keep_paste_face': [_k('inside', _paste_face, 16, 16, 8, 8, (1, 0, -2.5, 0, 1, -3.25), (2, 3, 12, 13), False),
+                        _k('over_the_edge', _paste_face, 13, 17, 11, 9, _HANG, (0, 0, 17, 13), False),
+                        _k('frame_mask', _paste_face, 13, 17, 11, 9, _HANG, (5, 0, 17, 9), True)],
+    'keep_resize_lanczos4_u8': [_k('up', _lanczos, 2, 8, 8, 16, 16), _k('ragged', _lanczos, 3, 5, 7, 3, 100), _k('one_pixel', _lanczos, 1, 5, 7, 1, 1)],
 }
 # launchers the convolution / attention tables above cover
 STRUCT_LAUNCHERS = {'keep_conv2d': CONV_CASES, 'keep_attention': ATTN_CASES}
@@ -833,9 +897,16 @@ HOST_ONLY = {'keep_abi_version', 'keep_last_error', 'keep_device_ok', 'keep_size
              'keep_conv2d_plan', 'keep_attention_workspace_bytes', 'keep_lanczos4_tables'}
 
 
-@pytest.mark.parametrize('fn,case', [(fn, cid) for fn, cases in FLAT_CASES.items() for cid, _ in cases])
+def flat_case(fn, cid):
+    """(regions, launch, canon or None, parameters) of one flat case."""
+    builder, params = {c: (b, p) for c, b, p in FLAT_CASES[fn]}[cid]
+    regions, launch, *canon = builder()
+    return regions, launch, (canon[0] if canon else None), params
+
+
+@pytest.mark.parametrize('fn,case', [(fn, cid) for fn, cases in FLAT_CASES.items() for cid, _, _ in cases])
 def test_flat_op_footprint(fn, case):
-    regions, launch, *canon = dict(FLAT_CASES[fn])[case]()
+    regions, launch, canon, _ = flat_case(fn, case)
     # outputs the kernel legitimately leaves partly unwritten (rows beyond a count) were given an initial value; everything else
     # must come out finite
-    FP.run(launch, regions, 'cuda', canon=canon[0] if canon else None)
+    FP.run(launch, regions, 'cuda', canon=canon)

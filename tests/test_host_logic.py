@@ -952,7 +952,7 @@ def test_footprint_tables_name_every_launcher():
     assert covered | T.HOST_ONLY == declared, (sorted(declared - covered - T.HOST_ONLY), sorted(covered - declared))
     assert not (covered & T.HOST_ONLY)
     for fn, cases in T.FLAT_CASES.items():
-        assert len(cases) >= 2 and len({cid for cid, _ in cases}) == len(cases), fn
+        assert len(cases) >= 2 and len({cid for cid, _, _ in cases}) == len(cases), fn
 
 
 # ------------------------------------------------------------------------------------------------ the case-value judge (tests/abi_ref.py)
@@ -1101,3 +1101,112 @@ def test_case_value_judge_bites(capsys):
             n_bites += 1
     assert n_bites >= 200, n_bites
     assert capsys.readouterr().out.count('[case-values]') >= n_bites
+
+
+# ------------------------------------------------------------------------------------------------ the flat-op value judge (tests/flat_ref.py)
+FLAT_CLASSES = {'exact', 'f32-arith', 'bf16', 'reduction', 'reduction+amax', 'f32-arith+amax', 'amax', 'index', 'dets', 'matrix'}
+
+
+def _flat_case_refs():
+    """(entry point, case id, parameters, payloads, regions, specs) of every flat case of the footprint table."""
+    import flat_ref as R
+    import test_gpu_footprint as T
+    for fn, cases in T.FLAT_CASES.items():
+        for cid, _, _ in cases:
+            regions, _, _, params = T.flat_case(fn, cid)
+            t = R.payloads(regions, fn, params)
+            yield fn, cid, params, t, regions, R.reference(fn, params, t)
+
+
+def test_flat_refs_cover_every_case_with_exactly_one_class():
+    """Every (entry point, case) of FLAT_CASES has a reference in tests/flat_ref.py that judges every output the case declares (regions
+    that are written and compared) and falls into exactly one class; an entry point without a reference and a parameter the reference
+    does not know both raise, so a case added later cannot slip past the judge."""
+    import flat_ref as R
+    import test_gpu_footprint as T
+    from comfyui_keep_amd.engine import hiplib as L
+    assert (R.KEEP_F32, R.KEEP_BF16) == (L.F32, L.BF16)
+    assert (R.AMAX_SLOTS, R.AMAX_OFF) == (T.AMAX_SLOTS, T.AMAX_OFF)
+    assert set(R.REFS) == set(T.FLAT_CASES)
+    seen = {}
+    for fn, cid, params, t, regions, specs in _flat_case_refs():
+        outs = {n for r in regions if r.role != 'r' and r.compare for n in r.windows}
+        judged = set(specs) | ({'counts'} if any(s['kind'] == 'dets' for s in specs.values()) else set())
+        assert judged == outs, (fn, cid, sorted(judged), sorted(outs))
+        klass = R.case_class(fn, specs)
+        assert klass in FLAT_CLASSES, (fn, cid, klass)
+        seen.setdefault(klass, set()).add(fn)
+        with pytest.raises(KeyError, match='dilation'):
+            R.reference(fn, dict(params, dilation=2), t)
+    assert set(seen) == FLAT_CLASSES, sorted(FLAT_CLASSES - set(seen))
+    with pytest.raises(KeyError):
+        R.reference('keep_fft', {}, {})
+    # the two entry points whose class depends on a parameter have a case of either class
+    assert seen['exact'] >= {'keep_nchw_to_nhwc', 'keep_act_inplace'} and seen['f32-arith'] >= {'keep_nchw_to_nhwc', 'keep_act_inplace'}
+
+
+def test_flat_judge_bites(capsys):
+    """flat_ref.judge on the CPU, for every flat case: the reference itself (cast to the output dtype) passes; it fails with the LAST element
+    of any output (the ragged tail) or a middle one moved by 10 x tol x scale -- one bit or one index for exact and index outputs --, with
+    an amax slot one ulp off, a written neighbour slot, a miscounted or foreign survivor."""
+    import flat_ref as R
+    n_bites = n_cases = 0
+    for fn, cid, params, t, regions, specs in _flat_case_refs():
+        got = R.fake_outputs(specs)
+        R.judge(fn, cid, specs, got)
+        n_cases += 1
+        for what, wrong in R.doctored(specs, got):
+            with pytest.raises(AssertionError):
+                R.judge(fn, cid, specs, wrong)
+                pytest.fail(f'{fn}[{cid}]: the judge let "{what}" pass')
+            n_bites += 1
+    assert n_cases >= 111 and n_bites >= 2 * n_cases, (n_cases, n_bites)
+    assert capsys.readouterr().out.count('[flat-values]') >= n_bites
+
+
+def test_flat_refs_feel_every_optional_input():
+    """For every flat case and every optional input or switch it uses, the reference without it differs from the full one by at least
+    SENSITIVITY x tol x scale (bits of an exact output differ): a kernel that ignores the input cannot pass."""
+    import flat_ref as R
+    seen = set()
+    for fn, cid, params, t, regions, specs in _flat_case_refs():
+        for what, name, other in R.removals(fn, params, t):
+            s = specs[name]
+            if s['kind'] == 'exact':
+                assert not torch.equal(other['ref'], s['ref']), (fn, cid, what)
+                got = dict(R.fake_outputs(specs), **{name: other['ref']})
+            else:
+                tol, sc, _ = R.spec_tol(s)
+                d = float((other['ref'].to(torch.float64) - s['ref']).abs().max())
+                assert d >= R.SENSITIVITY * tol * sc, (fn, cid, what, d / sc, tol)
+                got = dict(R.fake_outputs(specs), **{name: other['ref'].float().to(R.fake_outputs(specs)[name].dtype)})
+            with pytest.raises(AssertionError):
+                R.judge(fn, cid, specs, got)
+                pytest.fail(f'{fn}[{cid}]: the judge let a kernel without "{what}" pass')
+            seen.add((fn, what))
+    assert seen == {('keep_layernorm', 'residual'), ('keep_layernorm', 'pos'), ('keep_layernorm', 'out2 is not out'), ('keep_layernorm_amax', 'residual'),
+                    ('keep_norm_finalize', 'gamma'), ('keep_norm_finalize', 'beta'), ('keep_group_stats', 'gamma'), ('keep_group_stats', 'beta'),
+                    ('keep_norm_act_bf16', 'scale / shift'), ('keep_gm_join', 'sa'), ('keep_gm_join', 'ha'),
+                    ('keep_token_linear', 'bias'), ('keep_dwconv3x3', 'bias'), ('keep_affine_act', 'activation'), ('keep_dwconv3x3', 'activation'),
+                    ('keep_act_inplace', 'activation'), ('keep_norm_act_bf16', 'activation'), ('keep_add_bcast', 'alpha'), ('keep_nchw_to_nhwc', 'mode'),
+                    ('keep_slice_copy', 'up'), ('keep_sep_filter', 'classes + lut'), ('keep_paste_face', 'mask_border'),
+                    ('keep_warp_affine_u8', 'border colour'), ('keep_yolo_letterbox_u8', 'swap_rb')}, sorted(seen)
+
+
+def test_flat_table_inputs_respect_the_caps_of_the_judge():
+    """The caps of the index / selection rules hold for the table's own inputs, computed from the float64 references alone: the vq margin
+    rule leaves out no row (cap 1 %); every score of the two selectors sits farther than 1e-6 from its threshold; the `aligned` cases hold
+    every frame's survivors and the `ragged_overflow` cases hold at least one frame beside at least one that overflows."""
+    import flat_ref as R
+    for fn, cid, params, t, regions, specs in _flat_case_refs():
+        for s in specs.values():
+            if s['kind'] == 'argmin':
+                top2 = torch.topk(s['d'], 2, dim=1, largest=False).values
+                clear = (top2[:, 1] - top2[:, 0]) > R.VQ_MARGIN * float(s['d'].abs().max())
+                assert 1.0 - float(clear.float().mean()) <= R.VQ_MAX_SKIPPED and bool(clear.all()), (fn, cid)
+            if s['kind'] == 'dets':
+                assert float((s['score'] - s['thr']).abs().min()) > 100 * R.THRESHOLD_BAND, (fn, cid)
+                cnt = s['alive'].sum(1).tolist()
+                fits = [c <= s['cap'] for c in cnt]
+                assert all(c > 0 for c in cnt)
+                assert all(c < s['cap'] for c in cnt) if cid == 'aligned' else (any(fits) and not all(fits)), (fn, cid, cnt, s['cap'])
