@@ -18,6 +18,7 @@
 #include <type_traits>
 
 #include "keep_common.h"
+#include "../../include/keep_cv_hip.h"   // keep_attention_plan
 
 // cache policy of the x3 attention kernel's output rows: default (nt stores measured 3 ms slower per step: the merge GEMM that follows
 // reads them back at once)
@@ -68,6 +69,8 @@ struct AttnPlan {
   bool masked;   // ATTN_BF16IN: the region-mask instantiation (shifted windows)
   size_t lds;    // dynamic LDS bytes of the form's (last) launch
   int64_t scratch;  // bytes of `workspace` the form writes; 0: none
+  int nq;        // attn_x3_kernel forms: the NQ template argument (8 / 16; 0: Q re-staged per chunk)
+  bool win_tables;  // attn_x3_kernel forms: `lds` holds the mode-2 window tables (the kernel's `tab`)
 };
 
 // KEEP_MMA_X3 range scaling (same rule as keep_conv_common.h): power of two s with amax * s in [2^14, 2^15), and 1/s
@@ -2334,7 +2337,7 @@ static int plan_attention(const keep_attention_args& a, int64_t scratch_avail, A
   const int dvt = a.Dv <= 32 ? 1 : (a.Dv <= 64 ? 2 : 4);
   p.nslices = cdiv(a.Dv, dvt * 32);
   // one wave per block for tiny query counts (temporal attention over T frames), else 4 (one per SIMD)
-  pl = AttnPlan{ATTN_F32, a.Lq <= 32 ? 1 : 4, dvt, false, 0, 0};
+  pl = AttnPlan{ATTN_F32, a.Lq <= 32 ? 1 : 4, dvt, false, 0, 0, 0, false};
 
   // rows of a tensor start on 16-byte boundaries: base pointer, and every stride a multiple of `n` elements
   auto rows16 = [](const void* base, int64_t bs, int64_t ts, int64_t hs, int n) {
@@ -2358,7 +2361,9 @@ static int plan_attention(const keep_attention_args& a, int64_t scratch_avail, A
                    (long long)need, (long long)scratch_avail);
     pl.form = ATTN_X1_PACKED;
     pl.waves = 4;
-    pl.lds = (size_t)(32 * (a.D + 8) + dvt * 32 * 40) * 2 + (a.mode == 2 && a.Lk <= 4096 ? win_tables : 0);
+    pl.nq = 8;
+    pl.win_tables = a.mode == 2 && a.Lk <= 4096;
+    pl.lds = (size_t)(32 * (a.D + 8) + dvt * 32 * 40) * 2 + (pl.win_tables ? win_tables : 0);
     pl.scratch = need;
     return KEEP_OK;
   }
@@ -2394,7 +2399,9 @@ static int plan_attention(const keep_attention_args& a, int64_t scratch_avail, A
   auto x3_lds = [&](int waves, int nq) {
     const int dc = nq == 0 ? 128 : (a.D < 16 * nq ? a.D : 16 * nq);
     const size_t lds = (size_t)(((nq ? 0 : waves * 32) + 32) * (2 * dc + 8) + dvt * 32 * 72) * 2;
-    return lds + (waves == 4 && nq && a.mode == 2 && a.Lk <= 4096 ? win_tables : 0);
+    pl.nq = nq;
+    pl.win_tables = waves == 4 && nq && a.mode == 2 && a.Lk <= 4096;
+    return lds + (pl.win_tables ? win_tables : 0);
   };
   // small heads over at most 256 keys (the code transformer's MultiheadAttention): the latency form wins over everything
   if (a.mode == 0 && a.D == 64 && a.Dv == 64 && a.Lk <= 256 && a.Lq >= 64 && v16 && o16 && !(a.flags & KEEP_ATTN_NO_SMALL)) {
@@ -2464,6 +2471,56 @@ extern "C" int64_t keep_attention_workspace_bytes(const keep_attention_args* a_i
   return pl.scratch;
 }
 
+// The instantiation(s) the `switch` of keep_attention launches for plan `pl`, as rocprofv3 prints them (every template argument, the
+// defaulted ones included); a two-kernel form names both in launch order.  Reads the plan alone: the rules live in plan_attention.
+static void attn_plan_kernel_name(const AttnPlan& pl, char* out, size_t n) {
+  const int dvs = pl.dvt * 32;
+  switch (pl.form) {
+    case ATTN_F32: snprintf(out, n, "attn_f32_kernel<%d, %d>", pl.waves, pl.dvt); return;
+    case ATTN_BF16: snprintf(out, n, "attn_bf16_kernel<%d, %d>", pl.waves, pl.dvt); return;
+    case ATTN_BF16IN: snprintf(out, n, "attn_bf16in_kernel<%d, %s>", pl.dvt, pl.masked ? "true" : "false"); return;
+    case ATTN_X3_NQ8:
+    case ATTN_X3_NQ16:
+    case ATTN_X3_NQ0: snprintf(out, n, "attn_x3_kernel<%d, %d, %d, false, false>", pl.waves, pl.dvt, pl.nq); return;
+    case ATTN_X3_PACKED:
+      snprintf(out, n, "attn_pack_kv_x3_kernel<%d, %d, false> + attn_x3_kernel<4, %d, %d, true, false>", 16 * pl.nq, dvs, pl.dvt, pl.nq);
+      return;
+    case ATTN_X1_PACKED:
+      snprintf(out, n, "attn_pack_kv_x3_kernel<%d, %d, true> + attn_x3_kernel<4, %d, %d, true, true>", 16 * pl.nq, dvs, pl.dvt, pl.nq);
+      return;
+    case ATTN_X3_SMALL: snprintf(out, n, "attn_x3_small_kernel"); return;
+    case ATTN_X3_TWO_PASS: snprintf(out, n, "attn_scores_x3l_kernel + attn_pv_x3l_kernel"); return;
+    case ATTN_X3_SFULL: snprintf(out, n, "attn_x3_sfull_kernel<%d>", pl.dvt); return;
+    case ATTN_X3_SFULL2: snprintf(out, n, "attn_x3_sfull2_kernel"); return;
+  }
+  snprintf(out, n, "?");
+}
+
+// keep_cv_hip.h: what keep_attention would launch for exactly these arguments (host only: no pointer is dereferenced, nothing launched)
+extern "C" int32_t keep_attention_plan(const keep_attention_args* a_in, keep_attention_plan_out* out) {
+  KEEP_REQUIRE(out != nullptr, "keep_attention_plan: null out");
+  memset(out, 0, sizeof(*out));
+  keep_attention_args a;
+  const int rc_in = attn_args_in(a_in, a);
+  if (rc_in != KEEP_OK) return rc_in;
+  AttnP p;
+  AttnPlan pl;
+  const bool ws_ok = a.workspace && (uintptr_t)a.workspace % 16 == 0;
+  const int rc = plan_attention(a, ws_ok ? a.workspace_bytes : 0, p, pl);
+  if (rc != KEEP_OK) return rc;
+  out->waves = pl.waves;
+  out->dvt = pl.dvt;
+  out->nslices = p.nslices;
+  out->masked = pl.masked;
+  out->win_tables = pl.win_tables;
+  out->lds_bytes = (int64_t)pl.lds;
+  AttnP p_all;
+  AttnPlan pl_all;      // the same call with unlimited scratch: the answer of keep_attention_workspace_bytes
+  out->scratch_bytes = plan_attention(a, INT64_MAX, p_all, pl_all) == KEEP_OK ? pl_all.scratch : 0;
+  attn_plan_kernel_name(pl, out->kernel, sizeof(out->kernel));
+  return KEEP_OK;
+}
+
 extern "C" int32_t keep_attention(const keep_attention_args* a_in, void* stream) {
   keep_attention_args a;
   const int rc_in = attn_args_in(a_in, a);
@@ -2498,7 +2555,7 @@ extern "C" int32_t keep_attention(const keep_attention_args* a_in, void* stream)
     case ATTN_X3_PACKED:
       p.kv_pack = (const _Float16*)a.workspace;
       return with_dvt(pl.dvt, [&](auto dvt) {
-        return p.D == 128 ? launch_attn_x3_packed<decltype(dvt)::value, 8>(p, pl, st) : launch_attn_x3_packed<decltype(dvt)::value, 16>(p, pl, st);
+        return pl.nq == 8 ? launch_attn_x3_packed<decltype(dvt)::value, 8>(p, pl, st) : launch_attn_x3_packed<decltype(dvt)::value, 16>(p, pl, st);
       });
     case ATTN_X1_PACKED:
       p.kv_pack = (const _Float16*)a.workspace;

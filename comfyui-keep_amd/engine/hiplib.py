@@ -59,6 +59,12 @@ class AttnArgs(C.Structure):
                [('q_amax', _vp), ('k_amax', _vp), ('v_amax', _vp), ('workspace', _vp), ('workspace_bytes', _i64)]
 
 
+class AttnPlanOut(C.Structure):
+    # include/keep_cv_hip.h:keep_attention_plan_out
+    _fields_ = [('waves', _i32), ('dvt', _i32), ('nslices', _i32), ('masked', _i32), ('win_tables', _i32), ('lds_bytes', _i64), ('scratch_bytes', _i64),
+                ('kernel', C.c_char * 96)]
+
+
 # name -> argtypes (restype is always int32 status); every symbol include/keep_hip.h declares
 _SIGNATURES = {
     'keep_conv2d': [C.POINTER(ConvArgs), _vp],
@@ -128,6 +134,7 @@ _CV_SIGNATURES = {
     'keep_area_tables': [_i32, _i32, _i32, _vp, _vp, _vp],                 # (host-only: no stream argument)
     'keep_resize_area_u8': [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     'keep_resize_linear_u8': [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
+    'keep_attention_plan': [C.POINTER(AttnArgs), C.POINTER(AttnPlanOut)],  # (host-only: no stream argument)
 }
 CV_EXPORTED_SYMBOLS = ['keep_cv_abi_version'] + list(_CV_SIGNATURES)
 
@@ -232,6 +239,15 @@ def conv2d_plan(a):
 def attention_workspace_bytes(a):
     """keep_attention_workspace_bytes: scratch the library can use for this call (0 = none; -1 = MMA_X1 | ATTN_X1 refuses the call)."""
     return int(load(check_device=False).keep_attention_workspace_bytes(C.byref(a)))
+
+
+def attention_plan(a):
+    """keep_attention_plan: what keep_attention would launch for exactly these arguments (instantiation, LDS, scratch); a refused call raises
+    KeepHipError with the library's code and reason.  Needs no device."""
+    lib = load(check_device=False)
+    out = AttnPlanOut()
+    _check(lib.keep_attention_plan(C.byref(a), C.byref(out)), 'keep_attention_plan')
+    return out
 
 
 def attn_args(**kw):

@@ -14,6 +14,8 @@
 
 #include <stdint.h>
 
+#include "keep_hip.h" /* keep_attention_args */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -52,6 +54,31 @@ int32_t keep_resize_area_u8(const uint8_t* src, uint8_t* dst, int32_t N, int32_t
  * (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2, saturated to 0..255.  H == 2 * H2 && W == 2 * W2 is the case
  * cv2.resize hands to INTER_AREA's 2 x 2 integer path: (a + b + c + d + 2) >> 2 per channel. */
 int32_t keep_resize_linear_u8(const uint8_t* src, uint8_t* dst, int32_t N, int32_t H, int32_t W, int32_t H2, int32_t W2, void* stream);
+
+/* ---- what one attention call of keep_hip.h would launch: HOST-only C (no device, no stream; no pointer of `a` is dereferenced, they are
+ * tested for alignment only, so aligned made-up addresses do).  The arguments go through the same two steps as the launch -- the
+ * struct_size check and the one planning function -- and scratch counts as available exactly as there: `workspace` given, 16-byte
+ * aligned, `workspace_bytes` large enough for the form.  Returns what the launch would return for a refused call (KEEP_EINVAL, or
+ * KEEP_EUNSUP for KEEP_MMA_X1 | KEEP_ATTN_X1) with the same message; `out` is zeroed then.
+ *
+ *   waves / dvt / nslices   32-query waves per block (1 or 4), 32-column tiles of one block's dv slice (1 / 2 / 4), dv slices per head
+ *   masked                  the bf16-input kernel's region-mask instantiation (mode 2 with shift > 0)
+ *   win_tables              the launch stages the mode-2 window tables (token -> pixel, region ids) of all keys in LDS
+ *   lds_bytes               dynamic LDS of the form's last launch (0: the kernel has static LDS only)
+ *   scratch_bytes           what the workspace query of keep_hip.h answers for these arguments: the scratch the library could use,
+ *                           whether or not the call brings it (`kernel` names the form planned with the scratch the call does bring)
+ *   kernel                  the template instantiation as a profiler prints it, every template argument spelled out; a form of two
+ *                           launches names both in launch order, joined by " + " (pack + flash, scores + pv)
+ *
+ * Tests use it to prove that their case tables reach every instantiation; it is no part of the product path. */
+typedef struct {
+  int32_t waves, dvt, nslices;
+  int32_t masked;
+  int32_t win_tables;
+  int64_t lds_bytes, scratch_bytes;
+  char kernel[96];
+} keep_attention_plan_out;
+int32_t keep_attention_plan(const keep_attention_args* a, keep_attention_plan_out* out);
 
 #ifdef __cplusplus
 }

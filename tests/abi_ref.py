@@ -382,8 +382,10 @@ def attention_ref(c, q, k, v, remove=None):
         assert H == 1 and B == n * ks * ks and Lq == Lk == (h // ks) * (w // ks)
         img = lambda t: t.reshape(n, h * w, -1)  # noqa: E731
         shift = c['shift'] > 0
-        ow = win_ref(img(q), img(k), img(v), h, w, ks, shift, 0 if remove == 'kv_rot' else c['kv_rot'], torch.arange(Lq),
-                     mask_value=0.0 if remove == 'mask' else -100.0, scale=scale, roll=remove != 'roll')
+        # (query rows in blocks of 1024: the float64 scores of a 4224-token window frame would be 0.6 GB at once)
+        ow = torch.cat([win_ref(img(q), img(k), img(v), h, w, ks, shift, 0 if remove == 'kv_rot' else c['kv_rot'], rows,
+                                mask_value=0.0 if remove == 'mask' else -100.0, scale=scale, roll=remove != 'roll')
+                        for rows in torch.arange(Lq).split(1024)], dim=1)
         o = win_merge(ow, h, w, ks, *win_shift(h, w, ks, shift))
     else:
         raise ValueError(f"mode {c['mode']}")

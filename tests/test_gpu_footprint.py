@@ -6,7 +6,8 @@ judged by tests/test_gpu_case_values.py against the float64 restatement of the t
 points by tests/test_gpu_flat_values.py against the restatements in tests/flat_ref.py.
 
 The case tables are plain data, importable without a GPU: tests/test_host_logic.py asks ``keep_conv2d_plan`` (host C) for every
-convolution case and checks that the tables reach every kernel family and name every launcher of include/keep_hip.h.
+convolution case and ``keep_attention_plan`` for every attention case, and checks that the tables reach every convolution kernel
+family and every template instantiation keep_attention can launch, and name every launcher of include/keep_hip.h.
 """
 import ctypes
 import inspect
@@ -283,6 +284,7 @@ def _attn(name, *, mma, B, H, Lq, Lk, D, Dv=None, mode=0, packed=False, o_ld=Non
                 kv_rot=kv_rot, n_img=n_img, lk_rows=lk_rows, scale_mul=scale_mul, amp=amp)
 
 
+_BF = dict(scale_mul=8.0, amp=4.0)      # the bf16 class's data: peaked scores and large values, so that every optional input is felt
 ATTN_CASES = [
     _attn('f32_ragged', mma=F_, B=2, H=2, Lq=250, Lk=200, D=32, o_ld=72, o_off=4),
     _attn('f32_dv', mma=F_, B=1, H=1, Lq=250, Lk=200, D=64, Dv=2),
@@ -305,35 +307,80 @@ ATTN_CASES = [
     _attn('x3_mode2_shift', mma=X_, B=8, H=1, Lq=24, Lk=24, D=32, mode=2, img_h=8, img_w=12, ksplit=2, shift=2, kv_rot=1, n_img=2),
     _attn('f32_mode2_shift', mma=F_, B=8, H=1, Lq=24, Lk=24, D=32, mode=2, img_h=8, img_w=12, ksplit=2, shift=2, kv_rot=1, n_img=2),
     _attn('x3_mode2', mma=X_, B=8, H=1, Lq=24, Lk=24, D=32, mode=2, img_h=8, img_w=12, ksplit=2, shift=0, kv_rot=0, n_img=2),
+    # ---- every remaining instantiation plan_attention can send a call to (tests/test_host_logic.py:
+    # test_attention_table_reaches_every_instantiation asks keep_attention_plan for each case and for the whole universe)
+    # exact-f32: <4,2>, <4,4> on the chunked D > 128 staging, <1,2>, <1,4> with two dv slices; four waves on shifted windows
+    _attn('f32_w4_dv2', mma=F_, B=1, H=2, Lq=250, Lk=200, D=64),
+    _attn('f32_w4_dv4_chunked', mma=F_, B=1, H=1, Lq=100, Lk=77, D=256, Dv=128, o_ld=136, o_off=4),
+    _attn('f32_w1_dv2', mma=F_, B=3, H=2, Lq=20, Lk=50, D=48),
+    _attn('f32_w1_dv4', mma=F_, B=1, H=1, Lq=20, Lk=50, D=128, Dv=160),
+    _attn('f32_w4_mode2_shift', mma=F_, B=8, H=1, Lq=48, Lk=48, D=32, mode=2, img_h=12, img_w=16, ksplit=2, shift=3, kv_rot=1, n_img=2),
+    # bf16 operands on fp32 inputs: the same four shapes, one wave and four waves on shifted windows
+    _attn('bf16_w4_dv2', mma=B_, B=1, H=2, Lq=250, Lk=200, D=64, **_BF),
+    _attn('bf16_w4_dv4_chunked', mma=B_, B=1, H=1, Lq=100, Lk=77, D=256, Dv=128, o_ld=136, o_off=4, **_BF),
+    _attn('bf16_w1_dv2', mma=B_, B=3, H=2, Lq=20, Lk=50, D=48, **_BF),
+    _attn('bf16_w1_dv4', mma=B_, B=1, H=1, Lq=20, Lk=50, D=128, Dv=160, **_BF),
+    _attn('bf16_w1_mode2_shift', mma=B_, B=8, H=1, Lq=24, Lk=24, D=32, mode=2, img_h=8, img_w=12, ksplit=2, shift=2, kv_rot=1, n_img=2, **_BF),
+    _attn('bf16_w4_mode2_shift', mma=B_, B=8, H=1, Lq=48, Lk=48, D=32, mode=2, img_h=12, img_w=16, ksplit=2, shift=3, kv_rot=1, n_img=2, **_BF),
+    # bf16 inputs: <1|4, false>, the region-mask instantiation <1|2|4, true> on shifted 48-token windows, mode 1
+    _attn('bf16in_dv1', mma=B_, B=1, H=2, Lq=250, Lk=200, D=32, Dv=8, in_bf16=True, **_BF),
+    _attn('bf16in_dv4', mma=B_, B=1, H=1, Lq=100, Lk=77, D=128, in_bf16=True, **_BF),
+    _attn('bf16in_masked_dv1', mma=B_, B=8, H=1, Lq=48, Lk=48, D=32, mode=2, img_h=12, img_w=16, ksplit=2, shift=3, kv_rot=1, n_img=2, in_bf16=True, **_BF),
+    _attn('bf16in_masked_dv2', mma=B_, B=8, H=1, Lq=48, Lk=48, D=64, mode=2, img_h=12, img_w=16, ksplit=2, shift=3, kv_rot=1, n_img=2, in_bf16=True, **_BF),
+    _attn('bf16in_masked_dv4', mma=B_, B=8, H=1, Lq=48, Lk=48, D=128, mode=2, img_h=12, img_w=16, ksplit=2, shift=3, kv_rot=1, n_img=2, in_bf16=True, **_BF),
+    _attn('bf16in_mode1', mma=B_, B=3, H=2, Lq=100, Lk=200, D=32, mode=1, T=3, seg_len=100, lk_rows=100, in_bf16=True, **_BF),
+    # x3, Q in registers (D <= 128): <4,4>, <1,2> with range probes, <1,4>; four waves on shifted windows with the window tables in LDS
+    _attn('x3_nq8_w4_dv4', mma=X_, B=1, H=1, Lq=200, Lk=77, D=128),
+    _attn('x3_nq8_w1_dv2', mma=X_, B=3, H=2, Lq=20, Lk=50, D=48, amax=True),
+    _attn('x3_nq8_w1_dv4', mma=X_, B=1, H=1, Lq=20, Lk=50, D=128),
+    _attn('x3_nq8_w4_mode2_shift', mma=X_, B=8, H=1, Lq=48, Lk=48, D=32, mode=2, img_h=12, img_w=16, ksplit=2, shift=3, kv_rot=1, n_img=2),
+    # x3, D = 256 under 256 queries: 16 Q steps in registers
+    _attn('x3_nq16_dv1', mma=X_, B=1, H=1, Lq=100, Lk=77, D=256, Dv=2),
+    _attn('x3_nq16_dv2', mma=X_, B=1, H=2, Lq=100, Lk=77, D=256, Dv=64),
+    _attn('x3_nq16_dv4_amax', mma=X_, B=2, H=1, Lq=100, Lk=77, D=256, amax=True, o_ld=264, o_off=4),
+    _attn('x3_nq16_mode1', mma=X_, B=3, H=2, Lq=100, Lk=200, D=256, Dv=32, mode=1, T=3, seg_len=100, packed=True, lk_rows=100),
+    _attn('x3_nq16_mode2_shift', mma=X_, B=8, H=1, Lq=48, Lk=48, D=256, Dv=64, mode=2, img_h=12, img_w=16, ksplit=2, shift=3, kv_rot=1, n_img=2),
+    # x3, D >= 384 over more than 256 keys or in mode 1 / 2: Q and K re-staged per 128-wide chunk
+    _attn('x3_nq0_dv1', mma=X_, B=1, H=2, Lq=40, Lk=300, D=384, Dv=32),
+    _attn('x3_nq0_dv4_amax', mma=X_, B=2, H=1, Lq=40, Lk=300, D=384, amax=True, o_ld=392, o_off=4),
+    _attn('x3_nq0_d512_dv2', mma=X_, B=1, H=1, Lq=40, Lk=300, D=512, Dv=64),
+    _attn('x3_nq0_mode1', mma=X_, B=3, H=1, Lq=40, Lk=80, D=384, Dv=32, mode=1, T=3, seg_len=40, packed=True, lk_rows=40),
+    _attn('x3_nq0_mode2_shift', mma=X_, B=8, H=1, Lq=48, Lk=48, D=384, Dv=32, mode=2, img_h=12, img_w=16, ksplit=2, shift=3, kv_rot=1, n_img=2),
+    # x3 on pre-packed K / V^T (>= 256 queries, D = 128 or 256); the GMFlow product form: 270-token windows, D = Dv = 128, tables in LDS
+    _attn('x3_packed_dv1', mma=X_, B=1, H=2, Lq=300, Lk=77, D=128, Dv=32),
+    _attn('x3_packed_gmflow', mma=X_, B=8, H=1, Lq=270, Lk=270, D=128, mode=2, img_h=36, img_w=30, ksplit=2, shift=9, kv_rot=1, n_img=2),
+    _attn('x3_packed_mode1', mma=X_, B=3, H=1, Lq=256, Lk=512, D=128, Dv=64, mode=1, T=3, seg_len=256, packed=True, lk_rows=256),
+    _attn('x3_packed_d256_dv1', mma=X_, B=1, H=1, Lq=256, Lk=77, D=256, Dv=2),
+    _attn('x3_packed_d256_dv2', mma=X_, B=1, H=1, Lq=300, Lk=200, D=256, Dv=64),
+    _attn('x3_packed_d256_dv4_amax', mma=X_, B=2, H=1, Lq=270, Lk=77, D=256, amax=True, o_ld=264, o_off=4),
+    # x3 over at most 256 keys, D >= 384: all scores of a block in LDS, ragged key and query counts
+    _attn('x3_sfull_dv1', mma=X_, B=1, H=1, Lq=100, Lk=77, D=512, Dv=2),
+    _attn('x3_sfull_dv2', mma=X_, B=1, H=2, Lq=100, Lk=200, D=384, Dv=64),
+    _attn('x3_sfull_dv4_amax', mma=X_, B=2, H=1, Lq=100, Lk=77, D=384, amax=True),
+    _attn('x3_sfull2_ragged', mma=X_, B=1, H=1, Lq=100, Lk=77, D=512, Dv=4),
+    _attn('x3_small_lower_edge', mma=X_, B=1, H=2, Lq=64, Lk=33, D=64),
+    # shifted windows of more than 4096 tokens: a four-wave launch WITHOUT the window tables (pixels and regions recomputed per key tile)
+    _attn('x3_mode2_no_tables', mma=X_, B=4, H=1, Lq=4224, Lk=4224, D=32, mode=2, img_h=132, img_w=128, ksplit=2, shift=33, n_img=1, scale_mul=8.0),
 ]
-# one attention step touches at most a 128-query tile of q / o and a 32-key tile of k / v rows (<= 3 * 512 floats wide here)
+# one attention step touches at most a 128-query tile of q / o and a 32-key tile of k / v rows (<= 3 * 512 floats wide here: the widest
+# row is the 1096-float q | k | v row of 'x3_nq16_mode1')
 ATTN_TILE_BYTES = 128 * 3 * 512 * 4
 
 
-def attn_case_launch(case):
-    """(regions, launch) of one attention case: the operands with their real strides, the output slice, the range maxima and the
-    scratch the library asks for."""
-    c = dict(case)
+def _attn_case_args(c):
+    """``args(t)``: the keep_attention_args of case ``c`` on the tensors (or made-up addresses) ``t``; and the scratch the library asks for
+    with these shapes (0 for a case that passes none)."""
     B, H, Lq, Lk, D, Dv = c['B'], c['H'], c['Lq'], c['Lk'], c['D'], c['Dv']
-    name, tb = 'at' + c['name'], ATTN_TILE_BYTES
-    idt = BF16 if c['in_bf16'] else F32
     krows = c['lk_rows'] or Lk                                 # rows of k / v per batch in memory (mode 1: seg_len; keys come from two frames)
-    q, k, v = rnd(name + 'q', (B, Lq, H * D), dtype=idt), rnd(name + 'k', (B, krows, H * D), dtype=idt), rnd(name + 'v', (B, krows, H * Dv), c['amp'], dtype=idt)
-    if c['packed']:        # one [rows, q | k | v] buffer with 4 gap columns on either side: each operand is nobody's surroundings
+    if c['packed']:        # one [rows, q | k | v] buffer with 4 gap columns on either side
         assert krows == Lq
         ld = 2 * H * D + H * Dv + 8
-        R = [FP.Region(B * Lq, ld, {'q': (4, H * D, q), 'k': (4 + H * D, H * D, k), 'v': (4 + 2 * H * D, H * Dv, v)}, idt, 'r', tb)]
         qs = ks = vs = (Lq * ld, ld)
     else:
-        R = [FP.single('q', q, tile_bytes=tb), FP.single('k', k, tile_bytes=tb), FP.single('v', v, tile_bytes=tb)]
         qs, ks, vs = (Lq * H * D, H * D), (krows * H * D, H * D), (krows * H * Dv, H * Dv)
     o_ld = c['o_ld'] or H * Dv
     per_b = c['ksplit'] ** 2 if c['mode'] == 2 else 1          # mode 2: [n_img, img_h * img_w, C] tensors, batch stride = image stride
     qs, ks, vs = ((s_[0] * per_b, s_[1]) for s_ in (qs, ks, vs))
-    R.append(FP.output('o', (B * Lq, H * Dv), ld=o_ld, off=c['o_off'], tile_bytes=tb))
-    if c['amax']:
-        for n_, t_ in (('q_amax', q), ('k_amax', k), ('v_amax', v)):
-            R.append(FP.single(n_, t_.float().reshape(B, -1).abs().amax(1).reshape(1, B), tile_bytes=tb))
 
     def args(t):
         a = L.AttnArgs()
@@ -346,9 +393,44 @@ def attn_case_launch(case):
             setattr(a, f, val.data_ptr() if isinstance(val, torch.Tensor) else val)
         return a
 
-    # the scratch the library asks for with these shapes (pointers do not enter), embedded at exactly that size
-    fake = {n_: 0x10000 for n_ in ('q', 'k', 'v', 'o') + (('q_amax', 'k_amax', 'v_amax') if c['amax'] else ())}
-    need = L.attention_workspace_bytes(args(fake)) if c['ws'] else 0
+    # the scratch the library asks for with these shapes (pointers do not enter)
+    need = L.attention_workspace_bytes(args(_attn_fake(c))) if c['ws'] else 0
+    return args, need
+
+
+def _attn_fake(c):
+    return {n_: 0x10000 for n_ in ('q', 'k', 'v', 'o') + (('q_amax', 'k_amax', 'v_amax') if c['amax'] else ())}
+
+
+def attn_case_plan(case):
+    """keep_attention_plan (host C) for one attention case as ``attn_case_launch`` launches it: the case's own arguments on made-up
+    aligned addresses, with the workspace the case really passes."""
+    args, need = _attn_case_args(case)
+    a = args(_attn_fake(case))
+    if need:
+        a.workspace, a.workspace_bytes = 0x10000, need
+    return L.attention_plan(a)
+
+
+def attn_case_launch(case):
+    """(regions, launch) of one attention case: the operands with their real strides, the output slice, the range maxima and the
+    scratch the library asks for, embedded at exactly that size."""
+    c = dict(case)
+    B, H, Lq, Lk, D, Dv = c['B'], c['H'], c['Lq'], c['Lk'], c['D'], c['Dv']
+    name, tb = 'at' + c['name'], ATTN_TILE_BYTES
+    idt = BF16 if c['in_bf16'] else F32
+    krows = c['lk_rows'] or Lk
+    q, k, v = rnd(name + 'q', (B, Lq, H * D), dtype=idt), rnd(name + 'k', (B, krows, H * D), dtype=idt), rnd(name + 'v', (B, krows, H * Dv), c['amp'], dtype=idt)
+    if c['packed']:        # each operand of the q | k | v buffer is nobody's surroundings
+        ld = 2 * H * D + H * Dv + 8
+        R = [FP.Region(B * Lq, ld, {'q': (4, H * D, q), 'k': (4 + H * D, H * D, k), 'v': (4 + 2 * H * D, H * Dv, v)}, idt, 'r', tb)]
+    else:
+        R = [FP.single('q', q, tile_bytes=tb), FP.single('k', k, tile_bytes=tb), FP.single('v', v, tile_bytes=tb)]
+    R.append(FP.output('o', (B * Lq, H * Dv), ld=c['o_ld'] or H * Dv, off=c['o_off'], tile_bytes=tb))
+    if c['amax']:
+        for n_, t_ in (('q_amax', q), ('k_amax', k), ('v_amax', v)):
+            R.append(FP.single(n_, t_.float().reshape(B, -1).abs().amax(1).reshape(1, B), tile_bytes=tb))
+    args, need = _attn_case_args(c)
     if need:
         R.append(FP.output('ws', (1, (need + 3) // 4), tile_bytes=tb, compare=False))
 

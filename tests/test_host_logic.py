@@ -942,6 +942,177 @@ def test_footprint_conv_table_reaches_every_kernel_family():
     assert auto_split, 'no case where the library itself chooses split-K'
 
 
+# ------------------------------------------------------------------------------------------------ keep_attention: the table is complete
+# instantiations keep_attention_plan can name that no table case can reach (must stay empty unless one truly is unreachable)
+UNREACHABLE_ATTN_KERNELS = set()
+# the forms of the requirements below, by the kernel string keep_attention_plan prints
+ATTN_FORMS = {
+    'f32 4-wave': r'attn_f32_kernel<4, \d>', 'bf16 4-wave': r'attn_bf16_kernel<4, \d>', 'bf16 1-wave': r'attn_bf16_kernel<1, \d>',
+    'bf16in': r'attn_bf16in_kernel<\d, (true|false)>', 'NQ8 4-wave': r'attn_x3_kernel<4, \d, 8, false, false>',
+    'NQ8 1-wave': r'attn_x3_kernel<1, \d, 8, false, false>', 'NQ16': r'attn_x3_kernel<4, \d, 16, false, false>',
+    'NQ0': r'attn_x3_kernel<4, \d, 0, false, false>', 'packed': r'attn_pack_kv_x3_kernel<\d+, \d+, false> \+ attn_x3_kernel<4, \d, \d+, true, false>',
+    'sfull': r'attn_x3_sfull_kernel<\d>', 'sfull2': r'attn_x3_sfull2_kernel', 'small': r'attn_x3_small_kernel',
+}
+
+
+def _attn_form(kernel):
+    hit = [f for f, pat in ATTN_FORMS.items() if re.fullmatch(pat, kernel)]
+    return hit[0] if hit else None
+
+
+def _attention_universe():
+    """Every (kernel string, lds_bytes) keep_attention_plan answers over the grid of the docstring below; checks scratch_bytes against
+    keep_attention_workspace_bytes at every admitted point on the way."""
+    from comfyui_keep_amd.engine import hiplib as L
+    lib = L.load(check_device=False)
+    a, out = L.AttnArgs(), L.AttnPlanOut()
+    a.struct_size = ctypes.sizeof(L.AttnArgs)
+    a.q = a.k = a.v = a.o = 0x10000
+    a.H, a.scale = 1, 1.0
+    pa, po = ctypes.byref(a), ctypes.byref(out)
+    no_bits = (0, L.ATTN_NO_PACK, L.ATTN_NO_SFULL2, L.ATTN_NO_X3, L.ATTN_NO_SMALL, L.ATTN_NO_TWO_PASS)
+    found, points = {}, 0
+    for mma, x1 in ((L.MMA_F32, 0), (L.MMA_BF16, 0), (L.MMA_X3, 0), (L.MMA_X1, L.ATTN_X1)):
+        for in_dtype in (L.F32, L.BF16):
+            for mode in (0, 1, 2):
+                # mode 2: Lq == Lk == the window, so both length axes give windows (2 rows of L / 2 tokens, unshifted and shifted)
+                lengths = [(Lq, Lk, sh) for Lq in (20, 24, 200, 256, 300) for Lk in (200, 256, 300, 4224) for sh in (0,)] if mode != 2 else \
+                          [(L_, L_, sh) for L_ in (20, 24, 200, 256, 300, 4224) for sh in (0, 1)]
+                for Lq, Lk, shift in lengths:
+                    a.mma, a.in_dtype, a.mode, a.Lq, a.Lk, a.shift = mma, in_dtype, mode, Lq, Lk, shift
+                    a.B = a.T = 2 if mode == 1 else 1
+                    a.seg_len = Lk // 2
+                    a.img_h, a.img_w, a.ksplit, a.n_img = 2, Lk // 2, 1, 1
+                    for D in (32, 48, 64, 128, 256, 384, 512):
+                        for Dv in (2, 8, 32, 64, 128, 256, 384, 512):
+                            a.D, a.Dv = D, Dv
+                            a.q_ts = a.k_ts = a.q_hs = a.k_hs = D
+                            a.v_ts = a.o_ts = a.v_hs = a.o_hs = Dv
+                            a.q_bs, a.k_bs, a.v_bs, a.o_bs = Lq * D, Lk * D, Lk * Dv, Lq * Dv
+                            for flags in no_bits:
+                                a.flags = flags | x1
+                                for amax in (0, 0x10000):
+                                    a.q_amax = a.k_amax = a.v_amax = amax
+                                    a.workspace, a.workspace_bytes = None, 0
+                                    need = lib.keep_attention_workspace_bytes(pa)
+                                    for ws in (False, True):
+                                        if ws:
+                                            if need <= 0:
+                                                break                   # nothing to bring: the same point again
+                                            a.workspace, a.workspace_bytes = 0x10000, need
+                                        if lib.keep_attention_plan(pa, po) != 0:
+                                            continue                    # a refused combination
+                                        points += 1
+                                        assert out.scratch_bytes == need, (out.kernel, out.scratch_bytes, need)
+                                        kernel = out.kernel.decode()
+                                        found[kernel] = max(found.get(kernel, 0), out.lds_bytes)
+    return found, points
+
+
+def test_attention_table_reaches_every_instantiation():
+    """tests/test_gpu_footprint.py's attention table against keep_attention_plan (host C), as the convolution table is held against
+    keep_conv2d_plan above.
+
+    Universe: the distinct `kernel` strings the library answers over mma {F32, BF16, X3, X1 | ATTN_X1} x in_dtype {F32, BF16} x mode {0, 1, 2}
+    x D {32 .. 512} x Dv {2 .. 512} x Lq {20, 24, 200, 256, 300} x Lk {200, 256, 300, 4224} (mode 2: windows of each of these lengths,
+    unshifted and shifted) x workspace {absent, the size the library asks for} x {no flag, each ATTN_NO_* bit} x range probes {off, on};
+    refused combinations are skipped.  Its size is pinned to the count of the `switch` in keep_attention (csrc/keep_attn.hip):
+        attn_f32_kernel<1|4, 1|2|4> 6 + attn_bf16_kernel<1|4, 1|2|4> 6 + attn_bf16in_kernel<1|2|4, false|true> 6
+        + attn_x3_kernel<1|4, 1|2|4, 8> 6 + <4, 1|2|4, 16> 3 + <4, 1|2|4, 0> 3 + packed <4, 1|2|4, 8|16, true> 6 + its single-fp16 twin 1
+        + attn_x3_small_kernel 1 + the two-pass pair 1 + attn_x3_sfull_kernel<1|2|4> 3 + attn_x3_sfull2_kernel 1 = 43.
+    Reach: the strings of ATTN_CASES (each planned from its own arguments with the workspace it really passes) and of the single-fp16
+    cases of tests/test_gpu_attn_x1.py are exactly the universe.  Then, per flash form: modes 0, 1 and 2-with-shift; mode 2 with and
+    without the LDS window tables, the tables once on a plain four-wave launch and once on the packed form, and a four-wave launch of a
+    form that has tables running WITHOUT them (windows of more than 4096 tokens); range probes on every x3 form that takes them;
+    key AND query counts that are no multiples of 32 on the forms that had none.  Every universe member fits the CU's 160 KiB of LDS and
+    scratch_bytes equals keep_attention_workspace_bytes at every point of the sweep."""
+    import test_gpu_attn_x1 as TX
+    import test_gpu_footprint as T
+    from comfyui_keep_amd.engine import hiplib as L
+    universe, points = _attention_universe()
+    assert points > 50000, points
+    assert len(universe) == 43, sorted(universe)
+    for kernel, lds in universe.items():
+        assert 0 <= lds <= 160 * 1024, (kernel, lds)
+        assert kernel.count(' + ') == (1 if kernel.startswith(('attn_pack_kv_x3_kernel', 'attn_scores_x3l_kernel')) else 0), kernel
+
+    rows = []                                   # (case, kernel, plan) of every table case
+    for c in T.ATTN_CASES:
+        plan = T.attn_case_plan(c)
+        rows.append((c, plan.kernel.decode(), plan))
+        assert (plan.scratch_bytes > 0) == (plan.kernel.count(b' + ') == 1) or not c['ws'] or c['flags'] & L.ATTN_NO_PACK, c['name']
+    reached = {k for _, k, _ in rows}
+    for name, make in TX.CASES.items():         # the single-fp16 cases, as test_gpu_attn_x1.call builds them
+        kw = make()['kw']
+        a = L.attn_args(q=0x10000, k=0x10000, v=0x10000, o=0x10000, in_dtype=L.F32, **dict(kw, **TX.X1))
+        a.workspace, a.workspace_bytes = 0x10000, L.attention_workspace_bytes(a)
+        assert a.workspace_bytes == TX.x1_bytes(kw['B'], kw['Lk'])
+        reached.add(L.attention_plan(a).kernel.decode())
+    assert reached == set(universe) - UNREACHABLE_ATTN_KERNELS, (sorted(set(universe) - reached), sorted(reached - set(universe)))
+    assert not UNREACHABLE_ATTN_KERNELS
+
+    by_form = {}
+    for c, kernel, plan in rows:
+        by_form.setdefault(_attn_form(kernel), []).append((c, plan))
+    assert set(ATTN_FORMS) <= set(by_form), sorted(set(ATTN_FORMS) - set(by_form))
+    has = lambda form, pred: any(pred(c, plan) for c, plan in by_form[form])  # noqa: E731
+    for form in ('f32 4-wave', 'bf16 4-wave', 'bf16in', 'NQ8 4-wave', 'NQ16', 'NQ0', 'packed'):
+        for mode in (0, 1):
+            assert has(form, lambda c, _: c['mode'] == mode), (form, mode)
+        assert has(form, lambda c, _: c['mode'] == 2 and c['shift'] > 0), (form, 'mode 2 with shift')
+    mode2 = [(c, kernel, plan) for c, kernel, plan in rows if c['mode'] == 2]
+    assert {plan.win_tables for _, _, plan in mode2} == {0, 1}
+    assert any(plan.win_tables and _attn_form(k) in ('NQ8 4-wave', 'NQ16') for _, k, plan in mode2)
+    assert any(plan.win_tables and _attn_form(k) == 'packed' for _, k, plan in mode2)
+    assert any(not plan.win_tables and plan.waves == 4 and c['Lk'] > 4096 and c['shift'] > 0 and _attn_form(k) == 'NQ8 4-wave' for c, k, plan in mode2)
+    assert all(plan.masked == (c['mode'] == 2 and c['shift'] > 0) for c, plan in by_form['bf16in'])
+    for form in ('NQ8 1-wave', 'NQ16', 'NQ0', 'packed', 'sfull', 'sfull2', 'small'):
+        assert has(form, lambda c, _: c['amax']), (form, 'range probes')
+    for form in ('sfull', 'sfull2', 'small', 'NQ16', 'NQ0', 'packed', 'bf16 4-wave', 'bf16 1-wave', 'bf16in'):
+        assert has(form, lambda c, _: c['Lk'] % 32 and c['Lq'] % 32), (form, 'ragged key and query counts')
+    # the slices and edges the table lacked: several dv slices per head, the chunked D > 128 staging of the f32 / bf16 kernels, the small
+    # form at its lower edge (Lq = 64, one key past a tile)
+    for form in ('f32 4-wave', 'bf16 4-wave'):
+        assert has(form, lambda c, _: c['D'] > 128), (form, 'D > 128')
+    for form in ('NQ16', 'NQ0', 'packed', 'sfull'):
+        assert has(form, lambda c, plan: plan.nslices > 1), (form, 'dv slices')
+    assert has('small', lambda c, _: c['Lq'] == 64 and c['Lk'] == 33)
+
+
+def test_attention_plan_query_is_host_c_and_follows_the_launch():
+    """keep_attention_plan (include/keep_cv_hip.h): header, binding and library agree on the struct; a refusal is the launch's own, code and
+    text; scratch counts exactly as in the launch (given, 16-byte aligned, large enough), and `scratch_bytes` is the workspace query's answer
+    either way."""
+    from comfyui_keep_amd.engine import hiplib as L
+    header = open(os.path.join(ROOT, 'include', 'keep_cv_hip.h')).read()
+    assert [n for n, _ in L.AttnPlanOut._fields_] == _header_struct_fields(header, 'keep_attention_plan_out')
+    assert ctypes.sizeof(L.AttnPlanOut) == 5 * 4 + 4 + 2 * 8 + 96
+    lib = L.load(check_device=False)
+
+    def args(**kw):
+        base = dict(q=0x10000, k=0x10000, v=0x10000, o=0x10000, B=1, H=1, Lq=300, Lk=77, D=128, Dv=128, scale=1.0, mma=L.MMA_X3, q_bs=300 * 128, q_ts=128,
+                    q_hs=128, k_bs=77 * 128, k_ts=128, k_hs=128, v_bs=77 * 128, v_ts=128, v_hs=128, o_bs=300 * 128, o_ts=128, o_hs=128)
+        return L.attn_args(**dict(base, **kw))
+    flash, packed = 'attn_x3_kernel<4, 4, 8, false, false>', 'attn_pack_kv_x3_kernel<128, 128, false> + attn_x3_kernel<4, 4, 8, true, false>'
+    need = L.attention_workspace_bytes(args())
+    assert need > 0
+    for ws, nbytes, want in ((None, 0, flash), (0x10000, need, packed), (0x10000, need - 16, flash), (0x10008, need, flash)):
+        plan = L.attention_plan(args(workspace=ws, workspace_bytes=nbytes))
+        assert (plan.kernel.decode(), plan.scratch_bytes, plan.waves, plan.dvt, plan.nslices) == (want, need, 4, 4, 1), (ws, nbytes, plan.kernel)
+    out = L.AttnPlanOut()
+    out.waves = 7
+    for kw, code, text in ((dict(D=130), L.EINVAL, b'D=130 must be even'), (dict(mode=3), L.EINVAL, b'bad mode'),
+                           (dict(mma=L.MMA_X1, flags=L.ATTN_X1), L.EUNSUP, b'KEEP_MMA_X1 needs a 16-byte aligned workspace'),
+                           (dict(struct_size=8), L.EINVAL, b'struct_size')):
+        assert lib.keep_attention_plan(ctypes.byref(args(**kw)), ctypes.byref(out)) == code, kw
+        assert text in lib.keep_last_error() and lib.keep_last_error().startswith(b'keep_attention'), lib.keep_last_error()
+        assert out.waves == 0 and out.kernel == b''
+    assert lib.keep_attention_plan(None, ctypes.byref(out)) == L.EINVAL and lib.keep_attention_plan(ctypes.byref(args()), None) == L.EINVAL
+    with pytest.raises(L.KeepHipError, match='bad mode') as e:
+        L.attention_plan(args(mode=3))
+    assert e.value.code == L.EINVAL
+
+
 def test_footprint_tables_name_every_launcher():
     """Every keep_* entry point include/keep_hip.h declares is either host-only or has footprint cases (>= 2 each for the flat ops)."""
     import test_gpu_footprint as T
@@ -971,12 +1142,22 @@ def _conv_case_refs():
             yield name, plan.kernel.decode(), g, plan, t, A.conv2d_ref(g, t)
 
 
-def _attn_case_refs():
+_ATTN_REFS = {}        # (case name, removal or None) -> float64 reference: computed once, shared by the tests below, never modified
+
+
+def _attn_ref(c, t, remove=None):
     import abi_ref as A
+    key = (c['name'], remove)
+    if key not in _ATTN_REFS:
+        _ATTN_REFS[key] = A.attention_ref(c, t['q'], t['k'], t['v'], remove=remove)
+    return _ATTN_REFS[key]
+
+
+def _attn_case_refs():
     import test_gpu_footprint as T
     for c in T.ATTN_CASES:
         t = _payloads(T.attn_case_launch(c)[0])
-        yield c, t, A.attention_ref(c, t['q'], t['k'], t['v'])
+        yield c, t, _attn_ref(c, t)
 
 
 def test_abi_ref_restates_the_bindings_constants():
@@ -1038,7 +1219,7 @@ def test_case_value_references_feel_every_optional_input():
     for c, t, ref in _attn_case_refs():
         tol, sc = A.attn_tol(A.attn_class(c)), max(1.0, float(ref.abs().max()))
         for what in A.attn_case_removals(c):
-            d = float((A.attention_ref(c, t['q'], t['k'], t['v'], remove=what) - ref).abs().max())
+            d = float((_attn_ref(c, t, what) - ref).abs().max())
             assert d >= A.SENSITIVITY * tol * sc, (c['name'], what, d / sc, tol)
             seen.add(what)
     assert seen == set(A.ATTN_REMOVALS), seen
@@ -1093,7 +1274,7 @@ def test_case_value_judge_bites(capsys):
         A.judge_attn(c, ref.float(), ref, twin)
         moved = ref.clone()
         moved.view(-1)[moved.numel() // 2] += 10 * A.attn_tol(klass) * max(1.0, float(ref.abs().max()))
-        wrong = [('one element', moved)] + [(what, A.attention_ref(c, t['q'], t['k'], t['v'], remove=what)) for what in A.attn_case_removals(c)]
+        wrong = [('one element', moved)] + [(what, _attn_ref(c, t, what)) for what in A.attn_case_removals(c)]
         for what, got in wrong:
             with pytest.raises(AssertionError):
                 A.judge_attn(c, got.float(), ref, twin)
