@@ -6,7 +6,10 @@
 // Arithmetic follows OpenCV's published algorithms operation by operation (fixed-point warp coordinates: AB_BITS 10, INTER_BITS
 // 5; every float product / sum rounded separately, no FMA contraction: __fmul_rn / __fadd_rn) so that the result equals the
 // numpy restatement oracle/paste_oracle.py bit for bit.  All kernels are HBM / latency bound (a 1080p frame is 6 MB).
+#include <cmath>
+
 #include "keep_common.h"
+#include "../../include/keep_cv_hip.h"
 
 // HIP's __fmul_rn / __fadd_rn are plain operators: without this the compiler contracts them into FMAs (hipcc defaults to
 // -ffp-contract=fast) and the results drift from the separately rounded restatement by an ulp.
@@ -115,28 +118,34 @@ struct WarpP {
   int b0, b1, b2;
 };
 
-__global__ void warp_affine_u8_kernel(WarpP p) {
-  const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
-  if (x >= p.dw || y >= p.dh) return;
-  const long adelta = llrint(dmul_rn(dmul_rn(p.m00, (double)x), 1024.0));
-  const long bdelta = llrint(dmul_rn(dmul_rn(p.m10, (double)x), 1024.0));
-  const long X0 = llrint(dmul_rn(dadd_rn(dmul_rn(p.m01, (double)y), p.m02), 1024.0)) + 16;
-  const long Y0 = llrint(dmul_rn(dadd_rn(dmul_rn(p.m11, (double)y), p.m12), 1024.0)) + 16;
+// One destination pixel (x, y) of the crop warp: the arithmetic of both crop-warp kernels below (they cannot drift apart).
+__device__ __forceinline__ void warp_affine_u8_pixel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, double m00, double m01, double m02,
+                                                     double m10, double m11, double m12, int H, int W, int dw, int b0, int b1, int b2, int x, int y) {
+  const long adelta = llrint(dmul_rn(dmul_rn(m00, (double)x), 1024.0));
+  const long bdelta = llrint(dmul_rn(dmul_rn(m10, (double)x), 1024.0));
+  const long X0 = llrint(dmul_rn(dadd_rn(dmul_rn(m01, (double)y), m02), 1024.0)) + 16;
+  const long Y0 = llrint(dmul_rn(dadd_rn(dmul_rn(m11, (double)y), m12), 1024.0)) + 16;
   const long X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;
   long sxl = X >> 5, syl = Y >> 5;
   sxl = sxl < -32768 ? -32768 : (sxl > 32767 ? 32767 : sxl);
   syl = syl < -32768 ? -32768 : (syl > 32767 ? 32767 : syl);
   const int sx = (int)sxl, sy = (int)syl, fx = (int)(X & 31), fy = (int)(Y & 31);
   const int i00 = (32 - fx) * (32 - fy) * 32, i01 = fx * (32 - fy) * 32, i10 = (32 - fx) * fy * 32, i11 = fx * fy * 32;
-  const int bv[3] = {p.b0, p.b1, p.b2};
+  const int bv[3] = {b0, b1, b2};
   auto at = [&](int yy, int xx, int c) -> int {
-    if (xx < 0 || xx >= p.W || yy < 0 || yy >= p.H) return bv[c];
-    return p.src[((long)yy * p.W + xx) * 3 + c];
+    if (xx < 0 || xx >= W || yy < 0 || yy >= H) return bv[c];
+    return src[((long)yy * W + xx) * 3 + c];
   };
-  uint8_t* d = p.dst + ((long)y * p.dw + x) * 3;
+  uint8_t* d = dst + ((long)y * dw + x) * 3;
 #pragma unroll
   for (int c = 0; c < 3; ++c)
     d[c] = (uint8_t)((at(sy, sx, c) * i00 + at(sy, sx + 1, c) * i01 + at(sy + 1, sx, c) * i10 + at(sy + 1, sx + 1, c) * i11 + (1 << 14)) >> 15);
+}
+
+__global__ void warp_affine_u8_kernel(WarpP p) {
+  const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
+  if (x >= p.dw || y >= p.dh) return;
+  warp_affine_u8_pixel(p.src, p.dst, p.m00, p.m01, p.m02, p.m10, p.m11, p.m12, p.H, p.W, p.dw, p.b0, p.b1, p.b2, x, y);
 }
 
 extern "C" int32_t keep_warp_affine_u8(const uint8_t* src, int32_t H, int32_t W, uint8_t* dst, int32_t dh, int32_t dw,
@@ -149,6 +158,78 @@ extern "C" int32_t keep_warp_affine_u8(const uint8_t* src, int32_t H, int32_t W,
   p.H = H; p.W = W; p.dh = dh; p.dw = dw; p.b0 = border_b & 255; p.b1 = border_g & 255; p.b2 = border_r & 255;
   hipLaunchKernelGGL(warp_affine_u8_kernel, dim3(cdiv(dw, 32), cdiv(dh, 8)), dim3(256), 0, (hipStream_t)stream, p);
   KEEP_LAUNCH_CHECK("keep_warp_affine_u8");
+  return KEEP_OK;
+}
+
+// ---- the crop warp of a whole chunk of frames: F faces taken from N resident frames [N,H,W,3] -> [F,dh,dw,3], at most
+// WARP_BATCH_FACES faces per launch, blockIdx.z = the face within the launch.  The per-face data (frame index, destination -> source
+// map) travels in the kernel arguments: nothing is staged in device memory, so the launcher neither allocates nor synchronises.  Frame
+// index -1: the black crop of align_warp_face's `None` matrix (face_restoration_helper.py:309-311).
+#define WARP_BATCH_FACES 32
+struct WarpBatchP {
+  const uint8_t* src;                    // [N,H,W,3]
+  uint8_t* dst;                          // the first crop of this launch
+  double m[WARP_BATCH_FACES][6];         // destination -> source map per face
+  int frame[WARP_BATCH_FACES];
+  int H, W, dh, dw;
+  int b0, b1, b2;
+};
+
+__global__ void warp_affine_batch_u8_kernel(WarpBatchP p) {
+  const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
+  if (x >= p.dw || y >= p.dh) return;
+  const int f = blockIdx.z, frame = p.frame[f];
+  uint8_t* dst = p.dst + (long)f * p.dh * p.dw * 3;
+  if (frame < 0) {
+    uint8_t* d = dst + ((long)y * p.dw + x) * 3;
+    d[0] = 0; d[1] = 0; d[2] = 0;
+    return;
+  }
+  const double* m = p.m[f];
+  warp_affine_u8_pixel(p.src + (long)frame * p.H * p.W * 3, dst, m[0], m[1], m[2], m[3], m[4], m[5], p.H, p.W, p.dw, p.b0, p.b1, p.b2, x, y);
+}
+
+// launch g of F faces covers faces [first, first + count): false behind the last launch
+static inline bool warp_batch_group(int F, int g, int* first, int* count) {
+  if (g < 0 || (long)g * WARP_BATCH_FACES >= F) return false;
+  *first = g * WARP_BATCH_FACES;
+  *count = F - *first < WARP_BATCH_FACES ? F - *first : WARP_BATCH_FACES;
+  return true;
+}
+
+extern "C" int32_t keep_warp_batch_group(int32_t F, int32_t g, int32_t* first, int32_t* count) {
+  KEEP_REQUIRE(first && count && F > 0, "keep_warp_batch_group: bad arguments");
+  int a = 0, n = 0;
+  KEEP_REQUIRE(warp_batch_group(F, g, &a, &n), "keep_warp_batch_group: %d faces have no launch %d", F, g);
+  *first = a; *count = n;
+  return KEEP_OK;
+}
+
+extern "C" int32_t keep_warp_affine_batch_u8(const uint8_t* frames, int32_t N, int32_t H, int32_t W, uint8_t* dst, int32_t F, int32_t dh,
+                                             int32_t dw, const int32_t* frame_of, const double* dst_to_src, int32_t border_b,
+                                             int32_t border_g, int32_t border_r, void* stream) {
+  KEEP_REQUIRE(frames && dst && frame_of && dst_to_src, "keep_warp_affine_batch_u8: null pointer");
+  KEEP_REQUIRE(N > 0 && F > 0 && H > 0 && W > 0 && dh > 0 && dw > 0 && H < 32768 && W < 32768,
+               "keep_warp_affine_batch_u8: bad sizes N %d F %d H %d W %d dh %d dw %d", N, F, H, W, dh, dw);
+  for (int f = 0; f < F; ++f) {            // everything is judged before anything is launched
+    KEEP_REQUIRE(frame_of[f] >= -1 && frame_of[f] < N, "keep_warp_affine_batch_u8: face %d names frame %d of %d", f, frame_of[f], N);
+    for (int k = 0; k < 6; ++k)
+      KEEP_REQUIRE(std::isfinite(dst_to_src[(long)f * 6 + k]), "keep_warp_affine_batch_u8: face %d has a non-finite matrix entry", f);
+  }
+  WarpBatchP p;
+  p.src = frames;
+  p.H = H; p.W = W; p.dh = dh; p.dw = dw; p.b0 = border_b & 255; p.b1 = border_g & 255; p.b2 = border_r & 255;
+  int first = 0, count = 0;
+  for (int g = 0; warp_batch_group(F, g, &first, &count); ++g) {
+    p.dst = dst + (long)first * dh * dw * 3;
+    for (int f = 0; f < WARP_BATCH_FACES; ++f) {
+      const bool live = f < count;
+      p.frame[f] = live ? frame_of[first + f] : -1;
+      for (int k = 0; k < 6; ++k) p.m[f][k] = live ? dst_to_src[(long)(first + f) * 6 + k] : 0.0;
+    }
+    hipLaunchKernelGGL(warp_affine_batch_u8_kernel, dim3(cdiv(dw, 32), cdiv(dh, 8), count), dim3(256), 0, (hipStream_t)stream, p);
+    KEEP_LAUNCH_CHECK("keep_warp_affine_batch_u8");
+  }
   return KEEP_OK;
 }
 

@@ -80,6 +80,34 @@ def crop_faces(frame_u8, affine_matrices, face_size=(512, 512), device='cuda', b
     return out
 
 
+def crop_faces_batch(frames_dev, frame_of, affine_matrices, out, face_size=(512, 512), border=ALIGN_BORDER_BGR):
+    """``crop_faces`` for the faces of a whole chunk of frames that is resident on the device: uint8 [N,H,W,3] contiguous frames,
+    ``frame_of[f]`` the frame face f is taken from, its frame -> crop similarity matrix (None, or frame -1: the black crop) ->
+    ``out`` uint8 [F,fh,fw,3], contiguous, on the same device (a slice of a larger crop tensor), written by ONE
+    ``keep_warp_affine_batch_u8`` call on the current stream (the library launches once per 32 faces; frame indices and matrices travel
+    in the kernel arguments).  Returns ``out``."""
+    fw, fh = face_size
+    F = len(affine_matrices)
+    if len(frame_of) != F:
+        raise ValueError(f"crop_faces_batch: {len(frame_of)} frame indices for {F} matrices")
+    if (frames_dev.dtype != torch.uint8 or frames_dev.dim() != 4 or frames_dev.shape[3] != 3 or not frames_dev.is_cuda
+            or not frames_dev.is_contiguous()):
+        raise ValueError("crop_faces_batch: frames must be a contiguous uint8 [N,H,W,3] device tensor")
+    if (out.dtype != torch.uint8 or tuple(out.shape) != (F, fh, fw, 3) or out.device != frames_dev.device or not out.is_contiguous()):
+        raise ValueError(f"crop_faces_batch: out must be a contiguous uint8 {(F, fh, fw, 3)} tensor on {frames_dev.device}")
+    if F == 0:
+        return out
+    N, H, W, _ = frames_dev.shape
+    idx = (C.c_int32 * F)(*[-1 if M is None else int(t) for t, M in zip(frame_of, affine_matrices)])
+    d2s = (C.c_double * (6 * F))()
+    for f, M in enumerate(affine_matrices):
+        if M is not None:
+            d2s[6 * f:6 * f + 6] = invert_affine(M).reshape(-1).tolist()
+    with torch.cuda.device(frames_dev.device):
+        L.call('keep_warp_affine_batch_u8', frames_dev, N, H, W, out, F, fh, fw, idx, d2s, int(border[0]), int(border[1]), int(border[2]))
+    return out
+
+
 class GpuPaster:
     """Device buffers are cached per frame size; one instance per processor."""
 

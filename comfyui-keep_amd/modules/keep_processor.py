@@ -30,6 +30,12 @@ for bit (tests/test_gpu_paste.py::test_streamed_sequence_equals_the_per_frame_pa
 Aligned inputs (``has_aligned``): a frame that is not 512 x 512 is brought there by the INTER_LINEAR resize on the device
 (``_aligned_face``, KEEP_AMD_GPU_ALIGNED_RESIZE), and an aligned sequence stays on the device from upload to output
 (``_aligned_streamed``), equal to the per-frame path bit for bit (tests/test_gpu_aligned.py).
+
+Detected sequences: where the streamed paste applies, every frame is uploaded ONCE -- the detection pre-pass copies each chunk into a
+device tensor that stays (``_FrameStore``): the detector resize reads it (or it is the detector batch), one ``keep_warp_affine_batch_u8``
+call per chunk warps its faces into the sequence's crop tensor, whose views are the clips, and the paste-back takes its backgrounds
+from it (``_stored_sequence``; KEEP_AMD_FRAME_STORE=0 keeps the three uploads per frame, KEEP_AMD_FRAME_STORE_GB caps the store).  Equal
+to that path bit for bit (tests/test_gpu_frame_store.py).
 """
 import os
 
@@ -307,6 +313,81 @@ def frames_from_comfy(seq, device):
     return [comfy_image_to_cv2(seq[i].unsqueeze(0)) for i in range(seq.shape[0])]
 
 
+FRAME_STORE_DEFAULT_GB = 16.0     # KEEP_AMD_FRAME_STORE_GB: a policy (the store must not crowd out the clip batches sized from free HBM), not a measurement
+
+
+def frame_store_plan(frames, cap_bytes, chunk):
+    """The chunk spans [(start, stop)] of a device-resident frame store over ``frames``, or None where there is none: an empty
+    sequence, frames that are not uint8 [H,W,3] host arrays of ONE size, or more than ``cap_bytes`` in all (n * H * W * 3; exactly the cap
+    still applies).  A sequence over the cap takes the present path entirely: no partial stores.  ``chunk``: frames per chunk (the
+    detector's batch axis); the spans cover 0 .. n without overlap.  Pure: needs no device."""
+    n = len(frames)
+    if n == 0 or chunk < 1:
+        return None
+    if isinstance(frames, _ConvertedFrames):            # uint8 [H,W,3] by construction (asking a frame would wait for its conversion)
+        h, w = frames.H, frames.W
+    else:
+        shape = tuple(getattr(frames[0], 'shape', ()))
+        if len(shape) != 3 or shape[2] != 3:
+            return None
+        if any(not isinstance(f, np.ndarray) or f.dtype != np.uint8 or tuple(f.shape) != shape for f in frames):
+            return None
+        h, w = shape[:2]
+    if h <= 0 or w <= 0 or n * h * w * 3 > cap_bytes:
+        return None
+    return [(s, min(s + chunk, n)) for s in range(0, n, chunk)]
+
+
+class _FrameStore:
+    """The frames of one detected sequence on the device, one uint8 [m,H,W,3] tensor per chunk of the detection pre-pass, from the
+    pre-pass (which fills it and detects on it) over the crop warp to the paste-back (which reads the backgrounds from it).  Every
+    fill is followed by an event on the filling stream; a stream other than that one waits for it before its first read of the
+    chunk (``frame``).  A chunk is let go once its last frame has been emitted (``release``): the caching allocator is told which
+    stream read it last, so the memory is not handed out again before that stream has passed the read."""
+
+    def __init__(self, spans, h, w, device):
+        self.spans, self.h, self.w, self.device = list(spans), int(h), int(w), device
+        self.chunk = self.spans[0][1] - self.spans[0][0]
+        self.bufs = [None] * len(self.spans)
+        self.events = [None] * len(self.spans)
+        self._waited = [False] * len(self.spans)
+        self.dead = False                 # a frame ``read_image`` changed, or a failure: the sequence takes the present path
+
+    def fill(self, k, frames):
+        a, b = self.spans[k]
+        if len(frames) != b - a:
+            raise ValueError(f"frame store: chunk {k} holds frames {a} .. {b - 1}, got {len(frames)}")
+        with torch.cuda.device(self.device):
+            buf = torch.empty((b - a, self.h, self.w, 3), dtype=torch.uint8, device=self.device)
+            for i, fr in enumerate(frames):
+                buf[i].copy_(torch.from_numpy(np.ascontiguousarray(fr)), non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        self.bufs[k], self.events[k] = buf, ev
+        return buf
+
+    def complete(self):
+        return all(b is not None for b in self.bufs)
+
+    def frame(self, t, stream):
+        """Frame t, uint8 [H,W,3], for work queued on ``stream`` (which waits for the chunk's fill first)."""
+        k = t // self.chunk
+        if not self._waited[k]:
+            stream.wait_event(self.events[k])
+            self._waited[k] = True
+        return self.bufs[k][t - self.spans[k][0]]
+
+    def release(self, k, stream=None):
+        buf = self.bufs[k]
+        if buf is not None and stream is not None:
+            buf.record_stream(stream)
+        self.bufs[k] = None
+
+    def drop(self, stream=None):
+        for k in range(len(self.spans)):
+            self.release(k, stream)
+
+
 def split_clips(num_faces: int, max_clip_length: int):
     """[(start, end)] chunk boundaries of the flat crop list (keep_processor.py:263-264)."""
     return [(s, min(s + max_clip_length, num_faces)) for s in range(0, num_faces, max_clip_length)]
@@ -358,6 +439,10 @@ class KEEPFaceProcessor:
         env = os.environ.get('KEEP_AMD_GPU_ALIGNED_RESIZE')
         self.gpu_aligned_resize = {'1': True, '0': False}.get(env, None)
         self._linear_resizer = None
+        # the detected-face sequence path keeps every frame on the device from the detection pre-pass to the paste-back (``_FrameStore``,
+        # ``_stored_sequence``) where the streamed paste applies.  KEEP_AMD_FRAME_STORE=0 (read per call): off; KEEP_AMD_FRAME_STORE_GB: the cap.  A failure
+        # while filling or warping turns it off for this processor (``frame_store = False``).
+        self.frame_store = True
         self.detect_resize = 640        # the sequence pre-pass's ``resize`` of get_face_landmarks_5 (keep_processor.py:207-213 of the reference)
 
     # ------------------------------------------------------------------ net invocation
@@ -500,6 +585,14 @@ class KEEPFaceProcessor:
             buf = torch.empty((len(imgs), h, w, 3), dtype=torch.uint8, device=dev)
             for i, im in enumerate(imgs):
                 buf[i].copy_(im if isinstance(im, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(im)), non_blocking=True)
+            return self._area_resizer.resize_u8(buf, w2, h2)
+
+    def _detect_resize_stored(self, buf, w2, h2):
+        """``_detect_resize_device`` over a chunk that is on the device already (the frame store's tensor): the launch alone."""
+        if self._area_resizer is None:
+            from ..engine.resize import AreaResizer
+            self._area_resizer = AreaResizer(self.device)
+        with torch.cuda.device(buf.device):
             return self._area_resizer.resize_u8(buf, w2, h2)
 
     def _detect_resize_applies(self, imgs, resize):
@@ -713,14 +806,7 @@ class KEEPFaceProcessor:
         job, the GPU cv path (``_gpu_cv_path``), the parse-mask composite with ParseNet on the engine, no face upsampler, uint8
         colour frames of one size and 512 x 512 crops -- i.e. the configuration ``_gpu_paste_applies`` admits frame by frame, decided
         once for the sequence.  ``KEEP_AMD_STREAM_PASTE=0`` keeps the per-frame path."""
-        net = self.keep_net
-        if os.environ.get('KEEP_AMD_STREAM_PASTE', '1') == '0' or not getattr(net, 'supports_sink', False):
-            return False
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
-            return False
-        if self.face_upscale_model is not None or not getattr(helper, 'use_parse', False):
-            return False
-        if getattr(getattr(helper, 'face_parse', None), 'engine', None) is None or not self._gpu_cv_path():
+        if not self._stream_config_applies(helper):
             return False
         f0 = frames_bgr[0]
         if any(not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape != f0.shape or f.shape[2] != 3
@@ -730,8 +816,21 @@ class KEEPFaceProcessor:
             return False
         return crops is None or all(tuple(c.shape) == (512, 512, 3) for c in crops)
 
+    def _stream_config_applies(self, helper):
+        """What ``_stream_applies`` asks of the configuration (everything but the frames and the crops)."""
+        net = self.keep_net
+        if os.environ.get('KEEP_AMD_STREAM_PASTE', '1') == '0' or not getattr(net, 'supports_sink', False):
+            return False
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            return False
+        if self.face_upscale_model is not None or not getattr(helper, 'use_parse', False):
+            return False
+        if getattr(getattr(helper, 'face_parse', None), 'engine', None) is None or not self._gpu_cv_path():
+            return False
+        return tuple(getattr(helper, 'face_size', (512, 512))) == (512, 512)
+
     def _restore_and_paste_streamed(self, frames_bgr, crops, affines, faces_per_frame, max_clip_length, factor, draw_box, pbar,
-                                    as_u8):
+                                    as_u8, store=None):
         """Steps 3 and 4 of ``process_image_sequence`` (keep_processor.py:263-304) as ONE pipeline on the GPU.
 
         ``run_clips_u8(sink=...)`` restores the clips in batch groups and hands each finished, range-checked group over as device
@@ -739,7 +838,11 @@ class KEEPFaceProcessor:
         have all their faces, they are processed on a second stream: ParseNet over up to 32 faces across frames, then per frame the
         reference's arithmetic in the reference's order -- inverse affine from the helper (``get_inverse_affine``), face after face
         blended into the background (engine/paste.py) -- and the download of the finished frame (converted to the ComfyUI float RGB
-        layout on the device unless ``as_u8``).  The compute stream meanwhile runs the next group's forward."""
+        layout on the device unless ``as_u8``).  The compute stream meanwhile runs the next group's forward.
+
+        With ``store`` (``_stored_sequence``) ``crops`` is the [n_crops,512,512,3] device tensor the batched warp wrote and the clips are
+        views of it; the background of frame t is the store's frame (resized on the paste stream at ``factor != 1``), also for frames
+        without faces, and a chunk of the store is released once its last frame has been emitted."""
         from ..engine import hiplib as L
         from ..engine.paste import GpuPaster
         helper, net, dev = self.face_helper, self.keep_net, torch.device(self.device)
@@ -756,7 +859,9 @@ class KEEPFaceProcessor:
         clips = []
         for s, e in spans:
             part = crops[s:e]
-            if all(isinstance(c, torch.Tensor) and c.is_cuda for c in part):
+            if store is not None:
+                clips.append(part)                                    # a view of the sequence's crop tensor
+            elif all(isinstance(c, torch.Tensor) and c.is_cuda for c in part):
                 clips.append(torch.stack(part))                       # warped on this GPU: restored without leaving it
             else:
                 clips.append([c.cpu().numpy() if isinstance(c, torch.Tensor) else np.asarray(c) for c in part])
@@ -805,10 +910,16 @@ class KEEPFaceProcessor:
                     for k, i in enumerate(idx):
                         classes[i] = cl[k]
                 for t in range(f0, f1):
-                    bg = self._final_background(frames_bgr[t], factor, on_device=True)   # (factor != 1: resized on this stream)
+                    if store is not None:
+                        bg = store.frame(t, ps)
+                        bg = self._lanczos(bg, int(bg.shape[1] * factor), int(bg.shape[0] * factor), on_device=True)
+                    else:
+                        bg = self._final_background(frames_bgr[t], factor, on_device=True)   # (factor != 1: resized on this stream)
                     k = faces_per_frame[t]
                     if k == 0:
                         emit(t, bg if isinstance(bg, torch.Tensor) else on_dev(np.ascontiguousarray(bg)))
+                        if store is not None and t + 1 == store.spans[t // store.chunk][1]:
+                            store.release(t // store.chunk, ps)
                         continue
                     helper.affine_matrices = affines[st['aff']:st['aff'] + k]
                     helper.upscale_factor = factor
@@ -819,6 +930,8 @@ class KEEPFaceProcessor:
                     cls = torch.stack([on_dev(classes[i]) for i in ids])
                     emit(t, paster.paste(bg, faces, list(helper.inverse_affine_matrices), cls, factor, draw_box))
                     pbar.update(1)
+                    if store is not None and t + 1 == store.spans[t // store.chunk][1]:
+                        store.release(t // store.chunk, ps)             # (the allocator waits for this stream's reads)
                 if not keep_restored:                                  # a long video must not hold every restored crop in HBM until the end
                     for i in range(first[f0], first[f1]):
                         ready[i], classes[i] = _EMITTED, None
@@ -984,7 +1097,92 @@ class KEEPFaceProcessor:
         return st['out']
 
     # ------------------------------------------------------------------ sequence
-    def _detect_all(self, frames_bgr, only_center_face):
+    def _frame_store_begin(self, frames_bgr):
+        """An empty ``_FrameStore`` for this sequence where the store applies, else None: where the streamed paste applies
+        (``_stream_config_applies``) without a worker pool and without a background upscale model, with the device crop warp of
+        ``_align_warp`` (no pad_blur, a face template), a detector that takes batches, uniform uint8 frames within the cap
+        (``frame_store_plan``).  KEEP_AMD_FRAME_STORE=0 or an earlier failure of this processor: None."""
+        if os.environ.get('KEEP_AMD_FRAME_STORE', '1') == '0' or not self.frame_store:
+            return None
+        helper, net = self.face_helper, self.keep_net
+        use_batch, chunk = self._detect_batching(getattr(helper, 'face_detector', None), len(frames_bgr))
+        if not use_batch or getattr(net, 'pool', None) is not None or self.bg_upscale_model is not None:
+            return None
+        if getattr(helper, 'pad_blur', False) or not hasattr(helper, 'face_template') or not self._stream_config_applies(helper):
+            return None
+        try:
+            cap = float(os.environ.get('KEEP_AMD_FRAME_STORE_GB', '') or FRAME_STORE_DEFAULT_GB) * 1e9
+        except ValueError:
+            cap = FRAME_STORE_DEFAULT_GB * 1e9
+        spans = frame_store_plan(frames_bgr, int(cap), chunk)
+        if spans is None:
+            return None
+        dev = torch.device(self.device)
+        if dev.type != 'cuda':
+            return None
+        if dev.index is None:
+            dev = torch.device('cuda', torch.cuda.current_device())
+        f0 = frames_bgr if isinstance(frames_bgr, _ConvertedFrames) else None
+        h, w = (f0.H, f0.W) if f0 is not None else frames_bgr[0].shape[:2]
+        return _FrameStore(spans, h, w, dev)
+
+    def _frame_store_failed(self, store, err):
+        """A raised error while filling the store or in the batched warp (nothing has been restored yet): logged once, the store is off
+        for this processor from here on, and the sequence takes the present path."""
+        import logging
+        logging.getLogger('ComfyUI-KEEP').warning("keeping the frames on the device failed (%s): the per-frame upload path", err)
+        self.frame_store = False
+        store.dead = True
+        store.drop()
+
+    def _stored_sequence(self, store, frames_bgr, tracks, max_clip_length, factor, draw_box, pbar, as_u8):
+        """Steps 2 - 4 of a detected sequence over its frame store: the similarity matrices are fitted on the host as in ``_align_warp``
+        (``read_image`` is not called again: the pre-pass showed that it leaves these frames as they are), ONE ``keep_warp_affine_batch_u8``
+        call per chunk writes that chunk's crops straight into the sequence's [n_crops,512,512,3] crop tensor, and
+        ``_restore_and_paste_streamed`` restores views of that tensor and pastes onto the stored frames.  None -- the present path takes
+        the sequence -- when no frame has a face or when the warp fails (``_frame_store_failed``)."""
+        helper = self.face_helper
+        n_frames = len(frames_bgr)
+        try:
+            from ..engine.paste import crop_faces_batch
+            fit = getattr(helper, 'estimate_similarity', None)      # (a helper may bring its own fit: bench.py's cv2-free stand-in)
+            cv2 = _cv2() if fit is None else None
+            per_frame = []
+            for i in tqdm(range(n_frames), desc="Cropping and aligning faces"):
+                active = [seq[i] for seq in tracks.values() if not np.isnan(seq[i]).any()]
+                per_frame.append([fit(lm) if fit is not None else cv2.estimateAffinePartial2D(lm, helper.face_template, method=cv2.LMEDS)[0]
+                                  for lm in active])
+            faces_per_frame = [len(m) for m in per_frame]
+            n_crops = sum(faces_per_frame)
+            if n_crops == 0:
+                store.drop()
+                return None
+            with torch.cuda.device(store.device):
+                crops = torch.empty((n_crops, 512, 512, 3), dtype=torch.uint8, device=store.device)
+                off = 0
+                for k, (a, b) in enumerate(store.spans):
+                    frame_of = [t - a for t in range(a, b) for _ in per_frame[t]]
+                    mats = [M for t in range(a, b) for M in per_frame[t]]
+                    if mats:
+                        crop_faces_batch(store.bufs[k], frame_of, mats, crops[off:off + len(mats)], (512, 512))
+                        off += len(mats)
+        except Exception as e:
+            self._frame_store_failed(store, e)
+            return None
+        affines = [M for ms in per_frame for M in ms]
+        try:
+            return self._restore_and_paste_streamed(frames_bgr, crops, affines, faces_per_frame, max_clip_length, factor, draw_box, pbar,
+                                                    as_u8, store=store)
+        finally:
+            store.drop(getattr(self, '_paste_stream', None))        # (nothing is left after ``ps.synchronize()``; an error's way out: the paste stream may still read)
+
+    def _detect_batching(self, det, n):
+        """(whether the pre-pass runs the detector over batches, frames per chunk)"""
+        helper = self.face_helper
+        use_batch = hasattr(det, 'detect_batch') and getattr(helper, 'det_model', 'retinaface') != 'dlib' and n > 0
+        return use_batch, (max(1, int(getattr(getattr(det, 'engine', None), 'max_frames', 32))) if use_batch else 1)
+
+    def _detect_all(self, frames_bgr, only_center_face, store=None):
         """Landmarks of every frame (keep_processor.py:207-213: one ``get_face_landmarks_5`` call -- one detector forward and
         one host round trip -- per frame).  With the engine's detector (engine/retinaface.py, ``detect_batch``) the network
         runs over the video in chunks of the detector's batch axis (``KEEP_AMD_DETECT_BATCH`` frames: the host never holds more
@@ -997,8 +1195,7 @@ class KEEPFaceProcessor:
         raw = []
         helper = self.face_helper
         det = getattr(helper, 'face_detector', None)
-        use_batch = hasattr(det, 'detect_batch') and getattr(helper, 'det_model', 'retinaface') != 'dlib' and len(frames_bgr) > 0
-        chunk = max(1, int(getattr(getattr(det, 'engine', None), 'max_frames', 32))) if use_batch else 1
+        use_batch, chunk = self._detect_batching(det, len(frames_bgr))
         bar = tqdm(total=len(frames_bgr), desc="Detecting face landmarks")
         starts = list(range(0, len(frames_bgr), chunk))
         gpus = self._detection_pool(det, len(starts)) if use_batch else None
@@ -1016,7 +1213,9 @@ class KEEPFaceProcessor:
             from concurrent.futures import ThreadPoolExecutor
             pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix='keep-detect')
         try:
-            prepared = self._prep_detect_chunk(frames_bgr[starts[0]:starts[0] + chunk], self.detect_resize) if use_batch else None
+            # with a frame store (``_frame_store_begin``: same chunks) every chunk's frames stay on the device behind its detector input
+            skw = (lambda k: {}) if store is None else (lambda k: dict(store=store, k=k))
+            prepared = self._prep_detect_chunk(frames_bgr[starts[0]:starts[0] + chunk], self.detect_resize, **skw(0)) if use_batch else None
             for k, s in enumerate(starts):
                 part = frames_bgr[s:s + chunk]
                 states, batched = None, None
@@ -1028,7 +1227,7 @@ class KEEPFaceProcessor:
                         if fut is None:
                             batched = det.detect_batch(batch, 0.97)
                     if k + 1 < len(starts):                                # host work of the next chunk, under this chunk's forward
-                        prepared = self._prep_detect_chunk(frames_bgr[starts[k + 1]:starts[k + 1] + chunk], self.detect_resize)
+                        prepared = self._prep_detect_chunk(frames_bgr[starts[k + 1]:starts[k + 1] + chunk], self.detect_resize, **skw(k + 1))
                     if fut is not None:
                         batched = fut.result()
                 self._replay_chunk(det, part, states, batched, only_center_face, raw, bar)
@@ -1113,13 +1312,18 @@ class KEEPFaceProcessor:
             if thread is not None:
                 thread.shutdown(wait=True)
 
-    def _prep_detect_chunk(self, frames_bgr, resize, device_resize=True):
+    def _prep_detect_chunk(self, frames_bgr, resize, device_resize=True, store=None, k=None):
         """One chunk of frames: the helper state ``read_image`` leaves behind per frame (input image, grey flag) and the detector inputs
         ``get_face_landmarks_5`` would build from it (face_restoration_helper.py:206-216: frames whose short side exceeds ``resize`` are
         scaled down with INTER_AREA), stacked -> (states, batch).  ``batch`` is None when the frames differ in size or are not uint8
         (16-bit sources become float64 in ``read_image``: the per-frame path converts them the way the reference does).  Who resizes: a
         helper's own ``resize_for_detector`` first; else, with ``device_resize``, the HIP area resize over the whole chunk
-        (``_detect_resize_applies``: the batch is then a device tensor); else ``_resize`` (cv2, on the host) frame by frame."""
+        (``_detect_resize_applies``: the batch is then a device tensor); else ``_resize`` (cv2, on the host) frame by frame.
+
+        ``store`` / ``k``: the sequence's frame store and this chunk's index in it.  Where ``read_image`` left every frame as it was, the
+        frames are copied into the store's tensor of the chunk, which then is what the device resize reads, or -- frames that need no
+        resize -- the detector batch itself.  A frame ``read_image`` changed ends the store quietly (the present path takes the
+        sequence); a failing copy is logged and turns the store off for this processor."""
         helper = self.face_helper
         own = getattr(helper, 'resize_for_detector', None)          # (a helper may bring its own resize: bench.py's cv2-free stand-in)
         states = []
@@ -1128,14 +1332,25 @@ class KEEPFaceProcessor:
             helper.read_image(frame)
             states.append((helper.input_img, getattr(helper, 'is_gray', False)))
         imgs = [img for img, _ in states]
+        buf = None
+        if store is not None and not store.dead:
+            if all(img is fr for img, fr in zip(imgs, frames_bgr)):
+                try:
+                    buf = store.fill(k, imgs)
+                except Exception as e:
+                    self._frame_store_failed(store, e)
+            else:
+                store.dead = True
         target = self._detect_resize_applies(imgs, resize) if own is None and device_resize else None
         if target is not None:
             try:
-                return states, self._detect_resize_device(imgs, *target)
+                return states, (self._detect_resize_device(imgs, *target) if buf is None else self._detect_resize_stored(buf, *target))
             except Exception as e:                      # logged, and the present path takes the chunk (and every later one)
                 import logging
                 logging.getLogger('ComfyUI-KEEP').warning("device resize of the detector inputs failed (%s): cv2.resize", e)
                 self.gpu_detect_resize = False
+        if buf is not None and (resize is None or min(imgs[0].shape[:2]) <= resize):
+            return states, buf                          # no detector resize: the stored chunk is the detector batch
         for i, img in enumerate(imgs):
             h, w = img.shape[:2]
             if resize is not None and min(h, w) > resize:
@@ -1185,9 +1400,13 @@ class KEEPFaceProcessor:
         helper = self.face_helper
 
         # -- 1. landmarks per frame -> temporally smoothed tracks
-        tracks = {}
+        tracks, store = {}, None
         if not has_aligned_frames:
-            raw = self._detect_all(frames_bgr, only_center_face)
+            store = self._frame_store_begin(frames_bgr)
+            raw = self._detect_all(frames_bgr, only_center_face, store=store)
+            if store is not None and (store.dead or not store.complete()):
+                store.drop()
+                store = None
             pbar.update(n_frames)
             tracks = smooth_center_face(raw) if only_center_face else smooth_tracked_faces(raw)
             pbar.update(n_frames)
@@ -1198,6 +1417,12 @@ class KEEPFaceProcessor:
         if has_aligned_frames and n_frames and self._aligned_stream_applies(frames_bgr, final_upscale_factor):
             out = self._aligned_streamed(frames_bgr, max_clip_length, final_upscale_factor, pbar, as_u8)
             if out is not None:                         # (None: the device resize failed and turned itself off)
+                return out
+
+        # -- 2 - 4 of a detected sequence whose frames the pre-pass left on the device
+        if store is not None:
+            out = self._stored_sequence(store, frames_bgr, tracks, max_clip_length, final_upscale_factor, draw_box, pbar, as_u8)
+            if out is not None:                         # (None: no faces at all, or the batched warp failed and turned the store off)
                 return out
 
         # -- 2. crops, flat and frame-major

@@ -55,6 +55,24 @@ int32_t keep_resize_area_u8(const uint8_t* src, uint8_t* dst, int32_t N, int32_t
  * cv2.resize hands to INTER_AREA's 2 x 2 integer path: (a + b + c + d + 2) >> 2 per channel. */
 int32_t keep_resize_linear_u8(const uint8_t* src, uint8_t* dst, int32_t N, int32_t H, int32_t W, int32_t H2, int32_t W2, void* stream);
 
+/* ---- the aligned crops of a chunk of frames (face_restoration_helper.py:316-318): cv2.warpAffine(frame, M, (dw, dh), INTER_LINEAR,
+ * BORDER_CONSTANT, borderValue) for F faces taken from N resident frames, uint8, 3 channels -- per pixel the arithmetic of keep_hip.h's
+ * single-frame crop warp (one shared device function): 1/1024 fixed-point coordinates from separately rounded double multiplies, 5-bit
+ * fractions, 15-bit weights, the border colour for taps outside the source.
+ *
+ * keep_warp_affine_batch_u8: `frames` [N,H,W,3] and `dst` [F,dh,dw,3] are contiguous DEVICE memory; `frame_of` [F] and `dst_to_src` [F*6]
+ * (the destination -> source map of face f, row-major 2 x 3) are HOST arrays, read before the call returns: they travel in the kernel
+ * arguments, at most 32 faces per launch, so F faces are ceil(F / 32) launches on `stream`.  frame_of[f] == -1 writes a black crop (the
+ * `None` matrix of align_warp_face, :309-311); its matrix is not used but must be finite.  KEEP_EINVAL, before anything is launched: a null
+ * pointer; N, F, H, W, dh or dw <= 0; H or W >= 32768; a frame index outside -1 .. N - 1; a non-finite matrix entry.
+ *
+ * keep_warp_batch_group: HOST-only C (no device, no stream): launch g of F faces covers faces first .. first + count - 1 -- the rule the
+ * launcher itself loops over; KEEP_EINVAL for a g that F faces have no launch for. */
+int32_t keep_warp_batch_group(int32_t F, int32_t g, int32_t* first, int32_t* count);
+int32_t keep_warp_affine_batch_u8(const uint8_t* frames, int32_t N, int32_t H, int32_t W, uint8_t* dst, int32_t F, int32_t dh, int32_t dw,
+                                  const int32_t* frame_of /*host [F]*/, const double* dst_to_src /*host [F*6]*/, int32_t border_b,
+                                  int32_t border_g, int32_t border_r, void* stream);
+
 /* ---- what one attention call of keep_hip.h would launch: HOST-only C (no device, no stream; no pointer of `a` is dereferenced, they are
  * tested for alignment only, so aligned made-up addresses do).  The arguments go through the same two steps as the launch -- the
  * struct_size check and the one planning function -- and scratch counts as available exactly as there: `workspace` given, 16-byte
