@@ -405,7 +405,9 @@ void keep_conv_stats_replica(const ConvP& p, int n_img, hipStream_t st);
 static inline int persistent_grid(int n_items, int n_cu) { return n_items < 2 * n_cu ? n_items : 2 * n_cu; }
 
 // The kernel a plan reports (keep_conv2d_plan_out.kernel, as rocprofv3 prints the instantiation), keyed by path and form.  FORM_X3_HALO
-// reports the 256-pixel kernel of the plan also where the launch takes the 64-pixel blocks for the real N.
+// reports the 256-pixel kernel of the plan also where the launch takes the 64-pixel blocks for the real N.  The streaming kernel is named by
+// its prologue form alone: with an epilogue activation the launch is conv3x3_halo_x3s_act_kernel<PRO, AFF, X1, EACT> (the same body), and
+// the plan keeps the form's name -- the precision policies and their tests key on it (engine/ops.py: X3_STREAM_KERNEL).
 static inline void plan_kernel_name(const keep_conv2d_args* a, ConvPlan& pl) {
   const char* tile = pl.tile == 0 ? "4, 1, 1, 1" : (pl.tile == 1 ? "2, 2, 1, 1" : "2, 2, 2, 2");
   const char* in_bf16 = a->dtype == KEEP_BF16 ? "true" : "false";

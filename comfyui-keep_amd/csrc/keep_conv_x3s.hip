@@ -67,8 +67,12 @@ __device__ __forceinline__ float xs_xor32_sum(float x) {
 // waits are those of the x3 prologue forms: vmcnt(2) / (18) in front of the first ring barrier, vmcnt(4) at the end of a step.  Under the
 // swish a piece costs 28 VALU instructions (8 of them transcendental) + the request + the ds_write against ~4 free issue slots per gap
 // beside the fragment read: the VALU work exceeds the MFMA shadow by about one instruction per gap and is accepted.
-template <int PRO, bool AFF, bool X1 = false>
-__global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int tiles_x, int tiles_y, int ncb, int n_items) {
+// EACT: the epilogue activation (KEEP_ACT_*), a compile-time constant -- the layers of the KEEP network have none, and a run-time test of
+// p.epi_act per element of the unrolled epilogue put 34 000 instructions between two step bodies.  The body is shared by two kernels:
+// conv3x3_halo_x3s_kernel<PRO, AFF, X1> (no activation: the names the plans and the profiles carry) and
+// conv3x3_halo_x3s_act_kernel<PRO, AFF, X1, EACT>, instantiated for every activation with every form (keep_conv2d_x3_stream).
+template <int PRO, bool AFF, bool X1, int EACT>
+__device__ __forceinline__ void conv3x3_halo_x3s_body(const ConvP& p, int tiles_x, int tiles_y, int ncb, int n_items) {
   static_assert(AFF || PRO == KEEP_PRO_NONE, "an activation prologue comes with its GroupNorm affine");
   constexpr int WB = X1 ? 2 : 4;               // bytes per weight of p.wx3
   __shared__ __attribute__((aligned(16))) unsigned char lds_raw[XS_LDS];
@@ -81,6 +85,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
     const unsigned long long b = (unsigned long long)ptr;
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)b), hi = __builtin_amdgcn_readfirstlane((unsigned)(b >> 32));
     return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, bytes, 0x00020000);
+  };
+  // The pipeline's working set fills the register file: what only the item transitions and the epilogue use is recomputed there from an
+  // OPAQUE copy of the thread index (as in keep_conv_up2s.inc) -- left to itself the compiler keeps the / 34 quotients and remainders of
+  // setup_F alive across the MFMA loops, in scratch, and reloads them behind full vector-memory waits at every item transition
+  auto opaque = [](int x) __attribute__((always_inline)) {
+    asm volatile("" : "+v"(x));
+    return x;
   };
   const __amdgpu_buffer_rsrc_t null_rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, 0, 0x00020000);   // every offset out of range: zeros, no traffic
   const __amdgpu_buffer_rsrc_t w_rsrc = make_rsrc(p.wx3, p.Cout * 9 * p.Cin * WB);
@@ -121,9 +132,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
   const int items_per_z = n_items;
 
   auto setup_F = [&]() __attribute__((always_inline)) {                       // itF -> h_voff, in_rsrc, sc_voff, amaxF
+    const int t_ = opaque(tid), g = t_ & 3;    // (shadows the kernel's: see `opaque`)
 #pragma unroll
     for (int k = 0; k < HALO_IT; ++k) {
-      const int hp = (tid >> 2) + k * 64;
+      const int hp = (t_ >> 2) + k * 64;
       h_voff[k] = -16;
       if (hp < XS_PIX) {
         const int hy = hp / XS_HW, hx = hp - hy * XS_HW;
@@ -143,6 +155,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
     padmask = 0;
 #pragma unroll
     for (int k = 0; k < HALO_IT; ++k) padmask |= (h_voff[k] < 0 ? 1u : 0u) << k;
+    const int t_ = opaque(tid), lane = t_ & 63, wave = t_ >> 6;      // (shadow the kernel's: see `opaque`)
     const int lp = (lane & 3) ^ ((lane >> 4) & 3);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -427,6 +440,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
   // ---- epilogue of item itM: 16 pixel rows at a time through the halo buffer the item's last chunk just released
   auto epilogue_t = [&](int hb, auto res_c) __attribute__((always_inline)) {
     constexpr bool HAS_RES = decltype(res_c)::value;
+    const int t_ = opaque(tid);
+    const int lane = t_ & 63, wave = t_ >> 6, l31 = lane & 31, lhi = lane >> 5;      // (shadow the kernel's: see `opaque`)
     float* et = reinterpret_cast<float*>(lds_raw + hb) + wave * 16 * XS_EP;
     const float asc = p.acc_scale * in_invM;
     const int c4 = (lane & 15) * 4, prow = lane >> 4;
@@ -468,9 +483,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
         const float4 v = *reinterpret_cast<const float4*>(et + (u * 4 + prow) * XS_EP + c4);
         float e[4] = {__builtin_fmaf(v.x, asc, bias4.x), __builtin_fmaf(v.y, asc, bias4.y), __builtin_fmaf(v.z, asc, bias4.z),
                       __builtin_fmaf(v.w, asc, bias4.w)};
-        if (p.epi_act != KEEP_ACT_NONE) {       // (uniform; the activation comes before the residual: keep_conv_common.h epilogue_one)
+        if constexpr (EACT != KEEP_ACT_NONE) {  // (the activation comes before the residual: keep_conv_common.h epilogue_one)
 #pragma unroll
-          for (int q = 0; q < 4; ++q) e[q] = p.fast ? act_apply_fast(e[q], p.epi_act) : act_apply(e[q], p.epi_act);
+          for (int q = 0; q < 4; ++q) e[q] = p.fast ? act_apply_fast(e[q], EACT) : act_apply(e[q], EACT);
         }
         if (HAS_RES) {
           const u32x4 r4 = rpre[HAS_RES ? rd * 4 + u : 0];
@@ -563,11 +578,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
   int amax_n = -1;                             // image of the max |out| this wave has committed or seen
   float amax_run = 0.f;
   // one pipeline step; HB: byte offset of the halo buffer holding chunk M (compile time: folded into the DS offsets).  true: done
+  // (One copy of the epilogue and the item transition behind a run-time HB, shared by both buffers' MFMA loops, was built and dropped: the
+  // join of the two loops' register assignments spilled 143 VGPRs of <1, true, false>, with reloads inside the MFMA loops.)
   auto step = [&](auto hb_c) __attribute__((always_inline)) -> bool {
     constexpr int HB = decltype(hb_c)::value;
     const bool last = chM == nch - 1;          // the item's last chunk: its epilogue follows
     if (last) {                                // the bias of the item's cout block lands under the MFMAs
-      const int co = itM.n0 + (lane & 15) * 4;
+      const int co = itM.n0 + (opaque(tid) & 15) * 4;
       biasM = make_float4(0.f, 0.f, 0.f, 0.f);
       if (p.bias && co < p.Cout) biasM = *reinterpret_cast<const float4*>(p.bias + co);
     }
@@ -590,6 +607,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
           amax_run = 0.f;
         }
         if (__builtin_amdgcn_ballot_w64(amx > amax_run) != 0ull) {
+          const int lane = opaque(tid) & 63;
           unsigned b = __float_as_uint(amx);
 #pragma unroll
           for (int o = 32; o > 0; o >>= 1) b = max(b, (unsigned)__shfl_xor((int)b, o));
@@ -638,6 +656,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int t
     if (step(std::integral_constant<int, 0>{})) break;
     if (step(std::integral_constant<int, XS_HBUF>{})) break;
   }
+}
+
+template <int PRO, bool AFF, bool X1 = false>
+__global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_kernel(ConvP p, int tiles_x, int tiles_y, int ncb, int n_items) {
+  conv3x3_halo_x3s_body<PRO, AFF, X1, KEEP_ACT_NONE>(p, tiles_x, tiles_y, ncb, n_items);
+}
+template <int PRO, bool AFF, bool X1, int EACT>
+__global__ __launch_bounds__(256, 2) void conv3x3_halo_x3s_act_kernel(ConvP p, int tiles_x, int tiles_y, int ncb, int n_items) {
+  static_assert(EACT != KEEP_ACT_NONE, "no activation: conv3x3_halo_x3s_kernel");
+  conv3x3_halo_x3s_body<PRO, AFF, X1, EACT>(p, tiles_x, tiles_y, ncb, n_items);
 }
 
 // ------------------------------------------------------------------------------------------------ x2 phases, streaming
@@ -754,7 +782,7 @@ void keep_conv_stats_replica(const ConvP& p, int n_img, hipStream_t st) {
 // conv3x3_halo_x3_kernel.  flags & KEEP_CONV_NO_STREAM: round 3's kernel everywhere (kernel-vs-kernel tests, A/B runs).
 bool keep_conv_x3_stream_ok(const keep_conv2d_args* a, const ConvP& p, int split_k) {
   const bool off = (a->flags & KEEP_CONV_NO_STREAM) != 0;
-  const bool simple = split_k == 1 && !a->aux;      // (an epilogue activation is one uniform branch per row here: ParseNet's LeakyReLU)
+  const bool simple = split_k == 1 && !a->aux;      // (an epilogue activation is a template argument here: keep_conv2d_x3_stream)
   const bool aff = a->pro_scale != nullptr;
   return !off && simple && a->Ho % 8 == 0 && a->Wo % 32 == 0 && a->Cin >= 32 && a->upsample != KEEP_UPSAMPLE_X2_PHASES &&
          (a->pro_act == KEEP_PRO_NONE || (aff && (a->pro_act == KEEP_PRO_RELU || (a->pro_act == KEEP_PRO_SWISH && p.fast)))) &&
@@ -798,28 +826,44 @@ int keep_conv2d_x3_up2_stream(const keep_conv2d_args* a, ConvP& p, bool x1, hipS
   return KEEP_OK;
 }
 
+// one prologue form with the call's epilogue activation; false: an activation this kernel has no instantiation for
+template <int PRO, bool AFF, bool X1>
+static bool x3s_launch(int epi_act, dim3 grid, dim3 block, hipStream_t st, const ConvP& p, int tiles_x, int tiles_y, int ncb, int n_items) {
+#define X3S_ACT(A) \
+  case A: hipLaunchKernelGGL((conv3x3_halo_x3s_act_kernel<PRO, AFF, X1, A>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items); return true;
+  switch (epi_act) {
+    case KEEP_ACT_NONE: hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<PRO, AFF, X1>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items); return true;
+    X3S_ACT(KEEP_ACT_RELU)
+    X3S_ACT(KEEP_ACT_LRELU02)
+    X3S_ACT(KEEP_ACT_GELU)
+    X3S_ACT(KEEP_ACT_SIGMOID)
+    X3S_ACT(KEEP_ACT_LRELU01)
+    X3S_ACT(KEEP_ACT_SILU)
+    default: return false;
+  }
+#undef X3S_ACT
+}
+
 int keep_conv2d_x3_stream(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st) {
   const int tiles_x = a->Wo / 32, tiles_y = a->Ho / 8, ncb = (a->Cout + 63) / 64;
   const int n_items = a->N * tiles_x * tiles_y * ncb;
   dim3 grid(persistent_grid(n_items, keep_num_cu())), block(256);
   const bool aff = a->pro_scale != nullptr;
-  if (pl.form == FORM_X1_STREAM) {    // (keep_conv_x1_stream_ok: Cin % 32 == 0, the prologue forms of the x3 instantiations below)
-    if (a->pro_act == KEEP_PRO_SWISH)
-      hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_SWISH, true, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
-    else if (a->pro_act == KEEP_PRO_RELU)
-      hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_RELU, true, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
-    else if (aff)
-      hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_NONE, true, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
-    else
-      hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_NONE, false, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
-  } else if (a->pro_act == KEEP_PRO_SWISH)
-    hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_SWISH, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
+  const bool x1 = pl.form == FORM_X1_STREAM;      // (keep_conv_x1_stream_ok: Cin % 32 == 0, the prologue forms of the x3 instantiations)
+  bool ok;
+#define X3S_FORM(PRO, AFF) \
+  (x1 ? x3s_launch<PRO, AFF, true>(a->epi_act, grid, block, st, p, tiles_x, tiles_y, ncb, n_items) \
+      : x3s_launch<PRO, AFF, false>(a->epi_act, grid, block, st, p, tiles_x, tiles_y, ncb, n_items))
+  if (a->pro_act == KEEP_PRO_SWISH)
+    ok = X3S_FORM(KEEP_PRO_SWISH, true);
   else if (a->pro_act == KEEP_PRO_RELU)
-    hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_RELU, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
+    ok = X3S_FORM(KEEP_PRO_RELU, true);
   else if (aff)
-    hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_NONE, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
+    ok = X3S_FORM(KEEP_PRO_NONE, true);
   else
-    hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<KEEP_PRO_NONE, false>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
+    ok = X3S_FORM(KEEP_PRO_NONE, false);
+#undef X3S_FORM
+  if (!ok) return KEEP_EUNSUP;      // (an epilogue activation without an instantiation: never launch a kernel that would drop it)
   KEEP_LAUNCH_CHECK("keep_conv2d(halo x3, streaming)");
   return KEEP_OK;
 }

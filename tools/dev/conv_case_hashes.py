@@ -27,6 +27,16 @@ EXTRA = {
     'x1_stream_affine': dict(mma=X1, N=1, H=8, W=32, Cin=32, Cout=32, pro=True),
     'x1_stream_relu': dict(mma=X1, N=1, H=8, W=32, Cin=32, Cout=32, pro=True, pro_act=L.PRO_RELU),
     'x1_stream_swish': dict(mma=X1, N=1, H=8, W=32, Cin=32, Cout=32, pro=True, pro_act=L.PRO_SWISH),
+    # the streaming kernel with an epilogue activation (conv3x3_halo_x3s_act_kernel): the detectors' SiLU / LeakyReLU(0.1), ReLU, one behind a prologue;
+    # CONV_NO_SMALL_PARTIALS keeps launches of so few items on the 256-pixel kernel
+    'x3s_silu': dict(mma=X3, N=2, H=8, W=32, Cin=32, Cout=64, act=L.ACT_SILU, split_k=1, stats=True, flags=L.CONV_NO_SMALL_PARTIALS),
+    'x3s_relu': dict(mma=X3, N=1, H=8, W=32, Cin=32, Cout=64, act=L.ACT_RELU, split_k=1, stats=True, flags=L.CONV_NO_SMALL_PARTIALS),
+    'x3s_lrelu01': dict(mma=X3, N=1, H=8, W=32, Cin=48, Cout=64, act=L.ACT_LRELU01, split_k=1, flags=L.CONV_NO_SMALL_PARTIALS),
+    'x3s_gelu': dict(mma=X3, N=1, H=8, W=32, Cin=32, Cout=64, act=L.ACT_GELU, split_k=1, flags=L.CONV_NO_SMALL_PARTIALS),
+    'x3s_swish_lrelu01': dict(mma=X3, N=1, H=8, W=32, Cin=32, Cout=64, pro=True, pro_act=L.PRO_SWISH, act=L.ACT_LRELU01, split_k=1, stats=True,
+                              flags=L.CONV_NO_SMALL_PARTIALS),
+    'x1_stream_silu': dict(mma=X1, N=2, H=8, W=32, Cin=32, Cout=64, act=L.ACT_SILU),
+    'x1_stream_relu': dict(mma=X1, N=1, H=8, W=32, Cin=32, Cout=64, act=L.ACT_RELU),
     'x1_halo16': dict(mma=X1, N=16, H=16, W=16, Cin=32, Cout=32, flags=L.CONV_X1_HALO16),
     'x1_halo16_act': dict(mma=X1, N=16, H=16, W=16, Cin=32, Cout=32, flags=L.CONV_X1_HALO16, act=L.ACT_SILU),
     'x1_im2col_s2': dict(mma=X1, N=2, H=16, W=16, Cin=32, Cout=64, stride=2),
