@@ -8,6 +8,12 @@
 //   * H == 2 * H2 && W == 2 * W2: cv2.resize turns INTER_LINEAR into INTER_AREA, whose 2 x 2 integer path is (a + b + c + d + 2) >> 2.
 // All of it is integer arithmetic behind two double operations per coefficient (rounded separately: __dmul_rn / __dadd_rn, and the
 // file is built with FMA contraction off like the other two resizes).  Declared in include/keep_cv_hip.h.
+//
+// cv2.resize(src, (0, 0), fx=, fy=, interpolation=INTER_LINEAR) -- read_image's enlargement of a frame whose short side is below 512
+// (face_restoration_helper.py:182-184) -- is the second entry, keep_resize_linear_fxy_u8: the destination size is the rounded product
+// S * f (ties to even), but the coordinate scale is 1.0 / f ITSELF, not recomputed from the rounded size.  Same kernel, same pixel
+// arithmetic (rl_value); only the two scales in LinearP differ.  The 2 x 2 substitution cannot occur where a frame is enlarged; the one
+// pair of factors at which cv2.resize would make it (a scale of exactly 2 on both axes) is refused, not restated.
 #include <math.h>
 
 #include "keep_common.h"
@@ -34,10 +40,17 @@ struct LinearP {
   const uint8_t* src;
   uint8_t* dst;
   int H, W, H2, W2;
-  double scale_x, scale_y;             // 1. / ((double)W2 / W), 1. / ((double)H2 / H), as OpenCV forms them
+  double scale_x, scale_y;             // dsize form: 1. / ((double)W2 / W), 1. / ((double)H2 / H), as OpenCV forms them; fx / fy form: 1. / fx, 1. / fy
   int area2;                           // the exact 2x shrink: (a + b + c + d + 2) >> 2
   int rcap, ccap, srow;                // STAGED: rows / pixels per row / bytes per row of the staged rectangle (capacity)
 };
+
+// One output value of both entries from its 2 x 2 source values, the column weights (a0, a1) and the row weights (b0, b1).
+__device__ __forceinline__ int rl_value(int p00, int p01, int p10, int p11, int a0, int a1, int b0, int b1, int area2) {
+  if (area2) return (p00 + p01 + p10 + p11 + 2) >> 2;
+  const int h0 = p00 * a0 + p01 * a1, h1 = p10 * a0 + p11 * a1;
+  return min(255, max(0, (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2));
+}
 
 template <bool STAGED>
 __global__ void __launch_bounds__(256) resize_linear_u8_kernel(LinearP p) {
@@ -129,14 +142,7 @@ __global__ void __launch_bounds__(256) resize_linear_u8_kernel(LinearP p) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         const int p00 = s0[c0 + c], p01 = s0[c1 + c], p10 = s1[c0 + c], p11 = s1[c1 + c];
-        int v;
-        if (p.area2) {
-          v = (p00 + p01 + p10 + p11 + 2) >> 2;
-        } else {
-          const int h0 = p00 * a0 + p01 * a1, h1 = p10 * a0 + p11 * a1;
-          v = min(255, max(0, (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2));
-        }
-        o[j * 3 + c] = (uint8_t)v;
+        o[j * 3 + c] = (uint8_t)rl_value(p00, p01, p10, p11, a0, a1, b0, b1, p.area2);
       }
     }
   }
@@ -163,20 +169,18 @@ __global__ void __launch_bounds__(256) resize_linear_u8_kernel(LinearP p) {
   }
 }
 
-extern "C" int32_t keep_resize_linear_u8(const uint8_t* src, uint8_t* dst, int32_t N, int32_t H, int32_t W, int32_t H2, int32_t W2,
-                                         void* stream) {
-  KEEP_REQUIRE(src && dst, "keep_resize_linear_u8: null pointer");
-  KEEP_REQUIRE(N > 0 && H > 0 && W > 0 && H2 > 0 && W2 > 0,
-               "keep_resize_linear_u8: sizes must be positive (N=%d H=%d W=%d H2=%d W2=%d)", N, H, W, H2, W2);
-  KEEP_REQUIRE(W <= INT32_MAX / 3 && W2 <= INT32_MAX / 3, "keep_resize_linear_u8: W * 3 overflows int32 (W=%d W2=%d)", W, W2);
-  KEEP_REQUIRE(N <= 65535, "keep_resize_linear_u8: at most 65535 frames per call, got %d", N);
+// The launch of both entries: `name` opens the error messages; the arguments have been checked for null and non-positive sizes.
+static int32_t resize_linear_launch(const char* name, const uint8_t* src, uint8_t* dst, int32_t N, int32_t H, int32_t W, int32_t H2,
+                                    int32_t W2, double scale_x, double scale_y, int area2, void* stream) {
+  KEEP_REQUIRE(W <= INT32_MAX / 3 && W2 <= INT32_MAX / 3, "%s: W * 3 overflows int32 (W=%d W2=%d)", name, W, W2);
+  KEEP_REQUIRE(N <= 65535, "%s: at most 65535 frames per call, got %d", name, N);
   const int gx = cdiv(W2, RL_TW), gy = cdiv(H2, RL_TH);
-  KEEP_REQUIRE(gy <= 65535, "keep_resize_linear_u8: output too tall (H2=%d)", H2);
+  KEEP_REQUIRE(gy <= 65535, "%s: output too tall (H2=%d)", name, H2);
   LinearP p;
   p.src = src; p.dst = dst; p.H = H; p.W = W; p.H2 = H2; p.W2 = W2;
-  p.scale_x = 1.0 / ((double)W2 / (double)W);
-  p.scale_y = 1.0 / ((double)H2 / (double)H);
-  p.area2 = (H == 2 * H2 && W == 2 * W2) ? 1 : 0;
+  p.scale_x = scale_x;
+  p.scale_y = scale_y;
+  p.area2 = area2;
   // the rectangle of a tile: its t outputs of an axis are (t - 1) * scale source pixels apart, floor and the right / lower neighbour add
   // two, one more for the float rounding of the coordinates; never more than the frame
   p.rcap = (int)fmin((double)H, floor(RL_TH * p.scale_y) + 4.0);
@@ -189,6 +193,39 @@ extern "C" int32_t keep_resize_linear_u8(const uint8_t* src, uint8_t* dst, int32
     p.rcap = p.ccap = p.srow = 0;
     hipLaunchKernelGGL(resize_linear_u8_kernel<false>, dim3(gx, gy, N), dim3(256), RL_FIXED_LDS, (hipStream_t)stream, p);
   }
-  KEEP_LAUNCH_CHECK("keep_resize_linear_u8");
+  KEEP_LAUNCH_CHECK(name);
   return KEEP_OK;
+}
+
+extern "C" int32_t keep_resize_linear_u8(const uint8_t* src, uint8_t* dst, int32_t N, int32_t H, int32_t W, int32_t H2, int32_t W2,
+                                         void* stream) {
+  KEEP_REQUIRE(src && dst, "keep_resize_linear_u8: null pointer");
+  KEEP_REQUIRE(N > 0 && H > 0 && W > 0 && H2 > 0 && W2 > 0,
+               "keep_resize_linear_u8: sizes must be positive (N=%d H=%d W=%d H2=%d W2=%d)", N, H, W, H2, W2);
+  return resize_linear_launch("keep_resize_linear_u8", src, dst, N, H, W, H2, W2, 1.0 / ((double)W2 / (double)W), 1.0 / ((double)H2 / (double)H),
+                              (H == 2 * H2 && W == 2 * W2) ? 1 : 0, stream);
+}
+
+// OpenCV's saturate_cast<int>(double): round to nearest, ties to even (lrint under the default rounding mode), saturated.
+static inline bool fxy_size(int32_t S, double f, int32_t& D) {
+  const double v = nearbyint((double)S * f);
+  if (!(v >= 1.0 && v <= (double)INT32_MAX)) return false;
+  D = (int32_t)v;
+  return true;
+}
+
+extern "C" int32_t keep_resize_linear_fxy_u8(const uint8_t* src, uint8_t* dst, int32_t N, int32_t H, int32_t W, int32_t H2, int32_t W2,
+                                             double fx, double fy, void* stream) {
+  KEEP_REQUIRE(src && dst, "keep_resize_linear_fxy_u8: null pointer");
+  KEEP_REQUIRE(N > 0 && H > 0 && W > 0 && H2 > 0 && W2 > 0,
+               "keep_resize_linear_fxy_u8: sizes must be positive (N=%d H=%d W=%d H2=%d W2=%d)", N, H, W, H2, W2);
+  KEEP_REQUIRE(isfinite(fx) && isfinite(fy) && fx > 0.0 && fy > 0.0,
+               "keep_resize_linear_fxy_u8: factors must be finite and positive (fx=%g fy=%g)", fx, fy);
+  int32_t w2 = 0, h2 = 0;
+  KEEP_REQUIRE(fxy_size(W, fx, w2) && fxy_size(H, fy, h2) && w2 == W2 && h2 == H2,
+               "keep_resize_linear_fxy_u8: H2 x W2 must be the rounded products H * fy x W * fx (H=%d W=%d fx=%g fy=%g H2=%d W2=%d)", H, W, fx, fy,
+               H2, W2);
+  KEEP_REQUIRE(!(1.0 / fx == 2.0 && 1.0 / fy == 2.0),
+               "keep_resize_linear_fxy_u8: fx = fy = 0.5 is the exact 2x shrink cv2.resize hands to INTER_AREA, which this entry does not restate");
+  return resize_linear_launch("keep_resize_linear_fxy_u8", src, dst, N, H, W, H2, W2, 1.0 / fx, 1.0 / fy, 0, stream);
 }

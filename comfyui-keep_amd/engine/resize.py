@@ -17,6 +17,12 @@ tests/cv_area_ref.py is its restatement, and the processor's ``opencv_agrees_wit
 is the third: ``LinearResizer`` (``keep_resize_linear_u8``, csrc/keep_resize_linear.hip), any geometry, no tables: OpenCV's 11-bit fixed
 point, and the 2 x 2 integer average cv2.resize substitutes at an exact 2x shrink.  tests/cv_linear_ref.py is its restatement, and
 ``opencv_agrees_with_gpu_aligned_resize`` decides on an installation.
+
+``cv2.resize(img, (0, 0), fx=f, fy=f, interpolation=cv2.INTER_LINEAR)`` -- ``read_image``'s enlargement of a frame whose short side is
+below 512 (face_restoration_helper.py:182-184) -- is the same kernel behind a second entry: ``LinearResizer.enlarge_u8``
+(``keep_resize_linear_fxy_u8``).  The destination size is the rounded product, the coordinate scale is ``1 / f`` itself and there is no
+2 x 2 substitution.  tests/cv_linear_fxy_ref.py is its restatement, and ``opencv_agrees_with_gpu_small_frame_resize`` decides on an
+installation.
 """
 import ctypes as C
 import sys
@@ -196,4 +202,41 @@ class LinearResizer:
         if N > 0:
             with torch.cuda.device(self.device):
                 L.call('keep_resize_linear_u8', x, y, N, H, W, H2, W2)
+        return y if batched else y[0]
+
+    @staticmethod
+    def enlarged_size(H, W, fx, fy):
+        """(W2, H2) of ``cv2.resize(img [H,W], (0, 0), fx=fx, fy=fy)``: ``saturate_cast<int>(S * f)`` per axis, i.e. round to nearest with
+        ties to even -- Python's ``round``.  The one place that turns factors into a size."""
+        return int(round(W * float(fx))), int(round(H * float(fy)))
+
+    def enlarge_u8(self, frames, fx, fy, out=None):
+        """``cv2.resize(frame, (0, 0), fx=fx, fy=fy, interpolation=INTER_LINEAR)`` over uint8 frames [H,W,3] or [N,H,W,3] (numpy or tensor)
+        -> uint8 [H2,W2,3] / [N,H2,W2,3] on the device, one launch on the current stream; (W2, H2) = ``enlarged_size``.  Unlike
+        ``resize_u8`` nothing is special at identity: the kernel's arithmetic copies.  ``out``: as in ``resize_u8``."""
+        fx, fy = float(fx), float(fy)
+        shape = tuple(frames.shape)
+        if len(shape) not in (3, 4) or shape[-1] != 3:
+            raise ValueError(f"enlarge_u8: expected [H,W,3] or [N,H,W,3] uint8 frames, got shape {shape}")
+        if not (np.isfinite(fx) and np.isfinite(fy) and fx > 0 and fy > 0):
+            raise ValueError(f"enlarge_u8: factors must be finite and positive, got fx={fx} fy={fy}")
+        H, W = shape[-3], shape[-2]
+        W2, H2 = self.enlarged_size(H, W, fx, fy)
+        if H <= 0 or W <= 0 or H2 <= 0 or W2 <= 0:
+            raise ValueError(f"enlarge_u8: empty source or destination ({W}x{H} -> {W2}x{H2})")
+        want = shape[:-3] + (H2, W2, 3)
+        if out is not None and (tuple(out.shape) != want or out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous()):
+            raise ValueError(f"enlarge_u8: out must be a contiguous uint8 {want} tensor on {self.device}")
+        x = torch.as_tensor(frames)
+        if x.dtype != torch.uint8:
+            raise ValueError(f"enlarge_u8: expected uint8 frames, got {x.dtype}")
+        x = x.to(self.device, non_blocking=True).contiguous()
+        batched = x.dim() == 4
+        if not batched:
+            x = x[None]
+        N = x.shape[0]
+        y = torch.empty((N, H2, W2, 3), dtype=torch.uint8, device=self.device) if out is None else out.view(N, H2, W2, 3)
+        if N > 0:
+            with torch.cuda.device(self.device):
+                L.call('keep_resize_linear_fxy_u8', x, y, N, H, W, H2, W2, fx, fy)
         return y if batched else y[0]

@@ -36,6 +36,12 @@ device tensor that stays (``_FrameStore``): the detector resize reads it (or it 
 call per chunk warps its faces into the sequence's crop tensor, whose views are the clips, and the paste-back takes its backgrounds
 from it (``_stored_sequence``; KEEP_AMD_FRAME_STORE=0 keeps the three uploads per frame, KEEP_AMD_FRAME_STORE_GB caps the store).  Equal
 to that path bit for bit (tests/test_gpu_frame_store.py).
+
+Small frames: a helper whose ``read_image`` enlarges every frame with a short side below 512 (face_restoration_helper.py:182-184) used to end
+the store.  Where the first frame's ``read_image`` shows that enlargement, the store keeps each chunk twice -- the original frames and
+their enlargement by one ``keep_resize_linear_fxy_u8`` launch, which is the detector batch and the source of the crop warp -- and the
+paste-back resizes the originals to the enlarged size (KEEP_AMD_GPU_SMALL_FRAMES; tests/test_gpu_small_frames.py).  Without the store the
+streamed paste brings each background to the size ``read_image`` made before it composites.
 """
 import os
 
@@ -154,6 +160,28 @@ def opencv_agrees_with_gpu_aligned_resize(device):
         img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
         ref = cv2.resize(img, (512, 512), interpolation=cv2.INTER_LINEAR)
         if not np.array_equal(rz.resize_u8(img, 512, 512).cpu().numpy(), ref):
+            return False
+    return True
+
+
+def small_frame_factor(h, w):
+    """``f`` of ``read_image``'s enlargement (face_restoration_helper.py:182-184) for an [h,w] frame, or None where it does not enlarge."""
+    return 512.0 / min(h, w) if 0 < min(h, w) < 512 else None
+
+
+def opencv_agrees_with_gpu_small_frame_resize(device):
+    """True iff the HIP bilinear enlargement (engine/resize.py:LinearResizer.enlarge_u8) reproduces ``cv2.resize(img, (0, 0), fx=f, fy=f,
+    interpolation=cv2.INTER_LINEAR)`` with ``f = 512.0 / min(h, w)`` bit for bit on this installation: landscape, portrait and a
+    one-pixel-high source.  Raises ImportError without cv2."""
+    import cv2
+    from ..engine.resize import LinearResizer
+    rz = LinearResizer(device)
+    rng = np.random.default_rng(0)
+    for h, w in ((360, 480), (480, 270), (240, 426), (1, 7)):
+        img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+        f = 512.0 / min(h, w)
+        ref = cv2.resize(img, (0, 0), fx=f, fy=f, interpolation=cv2.INTER_LINEAR)
+        if not np.array_equal(rz.enlarge_u8(img, f, f).cpu().numpy(), ref):
             return False
     return True
 
@@ -343,10 +371,17 @@ class _FrameStore:
     pre-pass (which fills it and detects on it) over the crop warp to the paste-back (which reads the backgrounds from it).  Every
     fill is followed by an event on the filling stream; a stream other than that one waits for it before its first read of the
     chunk (``frame``).  A chunk is let go once its last frame has been emitted (``release``): the caching allocator is told which
-    stream read it last, so the memory is not handed out again before that stream has passed the read."""
+    stream read it last, so the memory is not handed out again before that stream has passed the read.
 
-    def __init__(self, spans, h, w, device):
+    Small frames (``small = (f, H2, W2)``, set by the pre-pass when ``read_image`` enlarges the first frame): a chunk is kept twice, the
+    original frames (``bufs``: the paste-back's backgrounds) and their enlargement (``ebufs``, ``enlarge``: the detector batch and what the
+    crop warp reads, let go after that warp)."""
+
+    def __init__(self, spans, h, w, device, cap_bytes=None):
         self.spans, self.h, self.w, self.device = list(spans), int(h), int(w), device
+        self.cap_bytes = cap_bytes
+        self.small = None
+        self.ebufs = [None] * len(self.spans)
         self.chunk = self.spans[0][1] - self.spans[0][0]
         self.bufs = [None] * len(self.spans)
         self.events = [None] * len(self.spans)
@@ -366,6 +401,20 @@ class _FrameStore:
         self.bufs[k], self.events[k] = buf, ev
         return buf
 
+    def enlarge(self, k, resizer):
+        """Chunk k's frames through ``read_image``'s enlargement: one launch on the current stream, behind the fill."""
+        f = self.small[0]
+        with torch.cuda.device(self.device):
+            ebuf = resizer.enlarge_u8(self.bufs[k], f, f)
+            ev = torch.cuda.Event()
+            ev.record()
+        self.ebufs[k], self.events[k] = ebuf, ev
+        return ebuf
+
+    def warp_source(self, k):
+        """What the crop warp of chunk k reads: the frames the landmarks live in."""
+        return self.bufs[k] if self.small is None else self.ebufs[k]
+
     def complete(self):
         return all(b is not None for b in self.bufs)
 
@@ -381,7 +430,7 @@ class _FrameStore:
         buf = self.bufs[k]
         if buf is not None and stream is not None:
             buf.record_stream(stream)
-        self.bufs[k] = None
+        self.bufs[k] = self.ebufs[k] = None             # (the enlarged chunk is read on the stream that made it)
 
     def drop(self, stream=None):
         for k in range(len(self.spans)):
@@ -439,6 +488,12 @@ class KEEPFaceProcessor:
         env = os.environ.get('KEEP_AMD_GPU_ALIGNED_RESIZE')
         self.gpu_aligned_resize = {'1': True, '0': False}.get(env, None)
         self._linear_resizer = None
+        # read_image's enlargement of frames whose short side is below 512 (face_restoration_helper.py:182-184) on the device
+        # (LinearResizer.enlarge_u8; ``_small_frames_probe``): such a sequence keeps its frame store.  KEEP_AMD_GPU_SMALL_FRAMES: '1' on,
+        # '0' off; unset = auto, decided like the three above: with cv2 by ``opencv_agrees_with_gpu_small_frame_resize`` once per
+        # processor, without cv2 the device path.
+        env = os.environ.get('KEEP_AMD_GPU_SMALL_FRAMES')
+        self.gpu_small_frames = {'1': True, '0': False}.get(env, None)
         # the detected-face sequence path keeps every frame on the device from the detection pre-pass to the paste-back (``_FrameStore``,
         # ``_stored_sequence``) where the streamed paste applies.  KEEP_AMD_FRAME_STORE=0 (read per call): off; KEEP_AMD_FRAME_STORE_GB: the cap.  A failure
         # while filling or warping turns it off for this processor (``frame_store = False``).
@@ -658,6 +713,68 @@ class KEEPFaceProcessor:
                 self.gpu_aligned_resize = False
         return _resize(img, 512, 512, 'INTER_LINEAR')
 
+    def _gpu_small_frames_path(self):
+        """Whether the HIP enlargement stands in for ``read_image``'s INTER_LINEAR cv2.resize of small frames: forced by
+        KEEP_AMD_GPU_SMALL_FRAMES, else decided once per processor -- by comparing it with cv2 itself where cv2 imports, and on without
+        cv2."""
+        if self.gpu_small_frames is None:
+            import logging
+            log = logging.getLogger('ComfyUI-KEEP')
+            try:
+                _cv2()
+            except ImportError:
+                log.info("cv2 is not installed: small frames are enlarged on the device (KEEP_AMD_GPU_SMALL_FRAMES)")
+                self.gpu_small_frames = True
+                return True
+            try:
+                self.gpu_small_frames = bool(opencv_agrees_with_gpu_small_frame_resize(self.device))
+            except Exception as e:                      # no GPU / no library / any surprise: cv2
+                log.info("device enlargement self-check failed (%s): cv2.resize", e)
+                self.gpu_small_frames = False
+        return self.gpu_small_frames
+
+    def _enlarged_hw(self, h, w):
+        """(H2, W2) ``read_image`` gives an [h,w] frame whose short side is below 512, else None."""
+        f = small_frame_factor(h, w)
+        if f is None:
+            return None
+        from ..engine.resize import LinearResizer
+        w2, h2 = LinearResizer.enlarged_size(h, w, f, f)
+        return h2, w2
+
+    def _small_frames_probe(self, store, n_frames, frame, img):
+        """The probe of a sequence, on its first frame: ``read_image`` turned ``frame`` (uint8 [h,w,3], short side below 512) into ``img``,
+        uint8 [rint(h f), rint(w f), 3].  Then -- the knob allowing, the Lanczos resize of the backgrounds on the device, both copies of
+        the sequence within the store's cap -- the store takes the small-frame form (``store.small``) and True comes back."""
+        if self.gpu_small_frames is False or frame.ndim != 3:
+            return False
+        h, w = frame.shape[:2]
+        hw2 = self._enlarged_hw(h, w)
+        if hw2 is None or not isinstance(img, np.ndarray) or img.dtype != np.uint8 or tuple(img.shape) != hw2 + (3,):
+            return False
+        if store.cap_bytes is not None and n_frames * (h * w + hw2[0] * hw2[1]) * 3 > store.cap_bytes:
+            return False
+        if not self._gpu_resize_path() or not self._gpu_small_frames_path():
+            return False
+        store.small = (small_frame_factor(h, w),) + hw2
+        return True
+
+    def _prep_small_chunk(self, store, k, frames_bgr):
+        """``_prep_detect_chunk`` of the small-frame form: the chunk's original frames are uploaded, one launch enlarges them, and the
+        enlarged chunk is the detector batch (short side 512: no detector resize).  ``read_image`` is not called: the state it would leave
+        is the enlarged frame -- here its device view, of which ``_replay_chunk`` needs the shape -- and the grey flag of the frame as it
+        came.  None after a failure (``_frame_store_failed``): the present handling takes this chunk and the rest."""
+        try:
+            if self._linear_resizer is None:
+                from ..engine.resize import LinearResizer
+                self._linear_resizer = LinearResizer(self.device)
+            store.fill(k, frames_bgr)
+            ebuf = store.enlarge(k, self._linear_resizer)
+        except Exception as e:
+            self._frame_store_failed(store, e)
+            return None
+        return [(ebuf[j], _is_gray(fr, threshold=10)) for j, fr in enumerate(frames_bgr)], ebuf
+
     # ------------------------------------------------------------------ single image
     @torch.no_grad()
     def process_image(self, cv2_image_orig: np.ndarray, final_upscale_factor: float, has_aligned: bool,
@@ -691,7 +808,7 @@ class KEEPFaceProcessor:
 
         if not has_aligned:
             helper.get_inverse_affine(None)
-            out = self._paste(helper, bg_img_final, draw_box)
+            out = self._paste(helper, bg_img_final, draw_box, src_hw=tuple(cv2_image_orig.shape[:2]))
         else:
             out = helper.restored_faces[0]
             if self.face_upscale_model:
@@ -701,14 +818,24 @@ class KEEPFaceProcessor:
         return out if out is not None else _host(bg_img_final)
 
     # ------------------------------------------------------------------ paste-back
-    def _paste(self, helper, bg, draw_box):
+    def _paste(self, helper, bg, draw_box, src_hw=None):
         """``helper.paste_faces_to_input_image(upsample_img=bg, draw_box=..., face_upsampler=...)`` behind one call
         (face_restoration_helper.py:346-475).  With ``gpu_paste`` and the configuration the loader builds (use_parse=True,
         colour frame already at the output size, no box, no face upsampler, every crop at the helper's face size) the
         per-face masks, warps and the blend run on the MI355X (engine/paste.py); every other configuration -- and every
-        helper that is not the reference's -- goes to the helper's own method."""
-        if self._gpu_cv_path() and self._gpu_paste_applies(helper, bg, draw_box):
-            return self._paste_gpu(helper, bg, draw_box)
+        helper that is not the reference's -- goes to the helper's own method.
+
+        ``src_hw``: the size of the frame the background was made from.  Where ``read_image`` enlarged that frame (short side below 512)
+        the background fails the size test alone; with the device resizes on it is brought to the enlarged size times the factor here
+        (:357-358) and the GPU paste keeps the frame."""
+        if self._gpu_cv_path():
+            if self._gpu_paste_applies(helper, bg, draw_box):
+                return self._paste_gpu(helper, bg, draw_box)
+            hw2 = self._enlarged_hw(*src_hw) if src_hw is not None and self.gpu_small_frames is not False else None
+            if (hw2 is not None and tuple(getattr(getattr(helper, 'input_img', None), 'shape', ())[:2]) == hw2
+                    and self._gpu_paste_applies(helper, bg, draw_box, size_test=False) and self._gpu_resize_path()):
+                up = getattr(helper, 'upscale_factor', 1)
+                return self._paste_gpu(helper, self._lanczos(bg, int(hw2[1] * up), int(hw2[0] * up), on_device=True), draw_box)
         return helper.paste_faces_to_input_image(upsample_img=_host(bg), draw_box=draw_box, face_upsampler=self.face_upscale_model)
 
     def _gpu_cv_path(self):
@@ -741,7 +868,7 @@ class KEEPFaceProcessor:
             crops = crops.cpu().numpy()
             helper.cropped_faces.extend(crops[i] for i in range(len(mats)))
 
-    def _gpu_paste_applies(self, helper, bg, draw_box):
+    def _gpu_paste_applies(self, helper, bg, draw_box, size_test=True):
         faces, mats = getattr(helper, 'restored_faces', None), getattr(helper, 'inverse_affine_matrices', None)
         if self.face_upscale_model is not None:            # (draw_box is on the device since round 4: keep_draw_box)
             return False
@@ -762,7 +889,7 @@ class KEEPFaceProcessor:
             return False
         h, w = getattr(helper, 'input_img', bg).shape[:2]
         up = getattr(helper, 'upscale_factor', 1)
-        if (int(h * up), int(w * up)) != tuple(bg.shape[:2]):   # :355-356 would resize the background first
+        if size_test and (int(h * up), int(w * up)) != tuple(bg.shape[:2]):   # :355-356 would resize the background first
             return False
         fw, fh = getattr(helper, 'face_size', (512, 512))
         # grey sources (is_gray: add_restored_face stored bgr2gray + AdaIN faces, [512,512]): the reference replicates the channel
@@ -830,7 +957,7 @@ class KEEPFaceProcessor:
         return tuple(getattr(helper, 'face_size', (512, 512))) == (512, 512)
 
     def _restore_and_paste_streamed(self, frames_bgr, crops, affines, faces_per_frame, max_clip_length, factor, draw_box, pbar,
-                                    as_u8, store=None):
+                                    as_u8, store=None, input_hw=None):
         """Steps 3 and 4 of ``process_image_sequence`` (keep_processor.py:263-304) as ONE pipeline on the GPU.
 
         ``run_clips_u8(sink=...)`` restores the clips in batch groups and hands each finished, range-checked group over as device
@@ -842,7 +969,12 @@ class KEEPFaceProcessor:
 
         With ``store`` (``_stored_sequence``) ``crops`` is the [n_crops,512,512,3] device tensor the batched warp wrote and the clips are
         views of it; the background of frame t is the store's frame (resized on the paste stream at ``factor != 1``), also for frames
-        without faces, and a chunk of the store is released once its last frame has been emitted."""
+        without faces, and a chunk of the store is released once its last frame has been emitted.  A small-frame store
+        (``store.small``) holds the original frames: the background is brought to the enlarged size times the factor behind that.
+
+        ``input_hw`` (without a store): per frame with faces the size ``read_image`` gave it.  Where that is not the frame's own -- small
+        frames, enlarged at :182-184 -- the inverse affines live in the enlarged frame, and the background is resized to that size times
+        the factor before the composite, the helper's own :357-358."""
         from ..engine import hiplib as L
         from ..engine.paste import GpuPaster
         helper, net, dev = self.face_helper, self.keep_net, torch.device(self.device)
@@ -913,8 +1045,13 @@ class KEEPFaceProcessor:
                     if store is not None:
                         bg = store.frame(t, ps)
                         bg = self._lanczos(bg, int(bg.shape[1] * factor), int(bg.shape[0] * factor), on_device=True)
+                        if store.small is not None:
+                            bg = self._lanczos(bg, int(store.small[2] * factor), int(store.small[1] * factor), on_device=True)
                     else:
                         bg = self._final_background(frames_bgr[t], factor, on_device=True)   # (factor != 1: resized on this stream)
+                        hw = input_hw[t] if input_hw is not None else None
+                        if hw is not None and tuple(hw) != tuple(frames_bgr[t].shape[:2]):
+                            bg = self._lanczos(bg, int(hw[1] * factor), int(hw[0] * factor), on_device=True)
                     k = faces_per_frame[t]
                     if k == 0:
                         emit(t, bg if isinstance(bg, torch.Tensor) else on_dev(np.ascontiguousarray(bg)))
@@ -1124,7 +1261,7 @@ class KEEPFaceProcessor:
             dev = torch.device('cuda', torch.cuda.current_device())
         f0 = frames_bgr if isinstance(frames_bgr, _ConvertedFrames) else None
         h, w = (f0.H, f0.W) if f0 is not None else frames_bgr[0].shape[:2]
-        return _FrameStore(spans, h, w, dev)
+        return _FrameStore(spans, h, w, dev, cap_bytes=int(cap))
 
     def _frame_store_failed(self, store, err):
         """A raised error while filling the store or in the batched warp (nothing has been restored yet): logged once, the store is off
@@ -1137,10 +1274,12 @@ class KEEPFaceProcessor:
 
     def _stored_sequence(self, store, frames_bgr, tracks, max_clip_length, factor, draw_box, pbar, as_u8):
         """Steps 2 - 4 of a detected sequence over its frame store: the similarity matrices are fitted on the host as in ``_align_warp``
-        (``read_image`` is not called again: the pre-pass showed that it leaves these frames as they are), ONE ``keep_warp_affine_batch_u8``
+        (``read_image`` is not called again: the pre-pass showed that it leaves these frames as they are, or enlarges them the way the store
+        did), ONE ``keep_warp_affine_batch_u8``
         call per chunk writes that chunk's crops straight into the sequence's [n_crops,512,512,3] crop tensor, and
         ``_restore_and_paste_streamed`` restores views of that tensor and pastes onto the stored frames.  None -- the present path takes
-        the sequence -- when no frame has a face or when the warp fails (``_frame_store_failed``)."""
+        the sequence -- when no frame has a face or when the warp fails (``_frame_store_failed``), and for small frames when ANY frame has
+        no face: that frame's output has the original size, the others the enlarged one, which is the present path's to deal with."""
         helper = self.face_helper
         n_frames = len(frames_bgr)
         try:
@@ -1154,7 +1293,7 @@ class KEEPFaceProcessor:
                                   for lm in active])
             faces_per_frame = [len(m) for m in per_frame]
             n_crops = sum(faces_per_frame)
-            if n_crops == 0:
+            if n_crops == 0 or (store.small is not None and 0 in faces_per_frame):
                 store.drop()
                 return None
             with torch.cuda.device(store.device):
@@ -1164,8 +1303,9 @@ class KEEPFaceProcessor:
                     frame_of = [t - a for t in range(a, b) for _ in per_frame[t]]
                     mats = [M for t in range(a, b) for M in per_frame[t]]
                     if mats:
-                        crop_faces_batch(store.bufs[k], frame_of, mats, crops[off:off + len(mats)], (512, 512))
+                        crop_faces_batch(store.warp_source(k), frame_of, mats, crops[off:off + len(mats)], (512, 512))
                         off += len(mats)
+                    store.ebufs[k] = None                # (an enlarged chunk has no reader behind its warp, which ran on its own stream)
         except Exception as e:
             self._frame_store_failed(store, e)
             return None
@@ -1323,14 +1463,25 @@ class KEEPFaceProcessor:
         ``store`` / ``k``: the sequence's frame store and this chunk's index in it.  Where ``read_image`` left every frame as it was, the
         frames are copied into the store's tensor of the chunk, which then is what the device resize reads, or -- frames that need no
         resize -- the detector batch itself.  A frame ``read_image`` changed ends the store quietly (the present path takes the
-        sequence); a failing copy is logged and turns the store off for this processor."""
+        sequence); a failing copy is logged and turns the store off for this processor.  The first frame of chunk 0 is the sequence's
+        probe for small frames (``_small_frames_probe``): where ``read_image`` enlarged it the way :182-184 do, this chunk and every later
+        one take ``_prep_small_chunk`` and ``read_image`` is not called again."""
         helper = self.face_helper
         own = getattr(helper, 'resize_for_detector', None)          # (a helper may bring its own resize: bench.py's cv2-free stand-in)
+        if store is not None and not store.dead and store.small is not None:
+            small = self._prep_small_chunk(store, k, frames_bgr)
+            if small is not None:
+                return small
         states = []
-        for frame in frames_bgr:
+        for j, frame in enumerate(frames_bgr):
             helper.clean_all()
             helper.read_image(frame)
             states.append((helper.input_img, getattr(helper, 'is_gray', False)))
+            if (j == 0 and k == 0 and store is not None and not store.dead and helper.input_img is not frame
+                    and self._small_frames_probe(store, sum(b - a for a, b in store.spans), frame, helper.input_img)):
+                small = self._prep_small_chunk(store, 0, frames_bgr)
+                if small is not None:
+                    return small
         imgs = [img for img, _ in states]
         buf = None
         if store is not None and not store.dead:
@@ -1426,7 +1577,7 @@ class KEEPFaceProcessor:
                 return out
 
         # -- 2. crops, flat and frame-major
-        crops, affines, faces_per_frame = [], [], []
+        crops, affines, faces_per_frame, input_hw = [], [], [], [None] * n_frames
         stream_ok = (not has_aligned_frames) and self._stream_applies(helper, frames_bgr, None, draw_box)
         for i in tqdm(range(n_frames), desc="Cropping and aligning faces"):
             if has_aligned_frames:
@@ -1437,6 +1588,7 @@ class KEEPFaceProcessor:
                 if active:
                     helper.clean_all()
                     helper.read_image(frames_bgr[i])
+                    input_hw[i] = tuple(getattr(helper.input_img, 'shape', ())[:2]) or None
                     helper.all_landmarks_5 = active
                     self._align_warp(helper, keep_on_device=stream_ok)
                     frame_crops = list(helper.cropped_faces)
@@ -1448,7 +1600,7 @@ class KEEPFaceProcessor:
         # -- 3 + 4 streamed: restore group g+1 while group g is parsed, pasted and downloaded (round 5)
         if crops and not has_aligned_frames and self._stream_applies(helper, frames_bgr, crops, draw_box):
             return self._restore_and_paste_streamed(frames_bgr, crops, affines, faces_per_frame, max_clip_length,
-                                                    final_upscale_factor, draw_box, pbar, as_u8)
+                                                    final_upscale_factor, draw_box, pbar, as_u8, input_hw=input_hw)
 
         # -- 3. restore: the hot path
         crops = [c.cpu().numpy() if isinstance(c, torch.Tensor) else c for c in crops]
@@ -1485,7 +1637,7 @@ class KEEPFaceProcessor:
             helper.affine_matrices = affines[aff_ptr:aff_ptr + k]
             helper.upscale_factor = final_upscale_factor
             helper.get_inverse_affine(None)
-            out_frames.append(self._paste(helper, bg, draw_box))
+            out_frames.append(self._paste(helper, bg, draw_box, src_hw=tuple(frames_bgr[i].shape[:2])))
             face_ptr += k
             aff_ptr += k
             pbar.update(1)

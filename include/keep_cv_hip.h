@@ -55,6 +55,18 @@ int32_t keep_resize_area_u8(const uint8_t* src, uint8_t* dst, int32_t N, int32_t
  * cv2.resize hands to INTER_AREA's 2 x 2 integer path: (a + b + c + d + 2) >> 2 per channel. */
 int32_t keep_resize_linear_u8(const uint8_t* src, uint8_t* dst, int32_t N, int32_t H, int32_t W, int32_t H2, int32_t W2, void* stream);
 
+/* ---- read_image's enlargement of a small frame (face_restoration_helper.py:182-184): cv2.resize(frame, (0, 0), fx=fx, fy=fy,
+ * interpolation=INTER_LINEAR), uint8, 3 channels -- the form of cv2.resize with an empty dsize.
+ *
+ * keep_resize_linear_fxy_u8: as keep_resize_linear_u8 (one launch, DEVICE pointers, no tables, the same kernel and pixel arithmetic) with
+ * two differences: the per-axis scale is 1.0 / fx (1.0 / fy) ITSELF, not recomputed from the sizes, and there is no 2 x 2 substitution: an
+ * enlargement never meets it, and the one pair of factors at which cv2.resize makes it (1.0 / fx == 2 && 1.0 / fy == 2) is refused.  The
+ * caller passes the destination size OpenCV computes, W2 = saturate_cast<int>(W * fx), H2 = saturate_cast<int>(H * fy): round to nearest,
+ * ties to even.  KEEP_EINVAL, before anything is launched: a null pointer; N, H, W, H2 or W2 <= 0; a factor that is not finite or not
+ * positive; H2 / W2 other than those rounded products; fx == fy == 0.5; and the size limits of keep_resize_linear_u8. */
+int32_t keep_resize_linear_fxy_u8(const uint8_t* src, uint8_t* dst, int32_t N, int32_t H, int32_t W, int32_t H2, int32_t W2, double fx,
+                                  double fy, void* stream);
+
 /* ---- the aligned crops of a chunk of frames (face_restoration_helper.py:316-318): cv2.warpAffine(frame, M, (dw, dh), INTER_LINEAR,
  * BORDER_CONSTANT, borderValue) for F faces taken from N resident frames, uint8, 3 channels -- per pixel the arithmetic of keep_hip.h's
  * single-frame crop warp (one shared device function): 1/1024 fixed-point coordinates from separately rounded double multiplies, 5-bit
