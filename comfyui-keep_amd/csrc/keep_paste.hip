@@ -6,7 +6,9 @@
 // Arithmetic follows OpenCV's published algorithms operation by operation (fixed-point warp coordinates: AB_BITS 10, INTER_BITS
 // 5; every float product / sum rounded separately, no FMA contraction: __fmul_rn / __fadd_rn) so that the result equals the
 // numpy restatement oracle/paste_oracle.py bit for bit.  All kernels are HBM / latency bound (a 1080p frame is 6 MB).
+#include <algorithm>
 #include <cmath>
+#include <vector>
 
 #include "keep_common.h"
 #include "../../include/keep_cv_hip.h"
@@ -164,13 +166,15 @@ extern "C" int32_t keep_warp_affine_u8(const uint8_t* src, int32_t H, int32_t W,
 // ---- the crop warp of a whole chunk of frames: F faces taken from N resident frames [N,H,W,3] -> [F,dh,dw,3], at most
 // WARP_BATCH_FACES faces per launch, blockIdx.z = the face within the launch.  The per-face data (frame index, destination -> source
 // map) travels in the kernel arguments: nothing is staged in device memory, so the launcher neither allocates nor synchronises.  Frame
-// index -1: the black crop of align_warp_face's `None` matrix (face_restoration_helper.py:309-311).
+// index -1: the black crop of align_warp_face's `None` matrix (face_restoration_helper.py:309-311).  Face f of a launch is written to crop
+// `slot[f]` behind `dst`: the launch's own order for keep_warp_affine_batch_u8, the caller's slots for keep_warp_affine_batch_scatter_u8.
 #define WARP_BATCH_FACES 32
 struct WarpBatchP {
   const uint8_t* src;                    // [N,H,W,3]
-  uint8_t* dst;                          // the first crop of this launch
+  uint8_t* dst;                          // crop 0 of the slots of this launch
   double m[WARP_BATCH_FACES][6];         // destination -> source map per face
   int frame[WARP_BATCH_FACES];
+  int slot[WARP_BATCH_FACES];            // where face f goes, in crops behind dst
   int H, W, dh, dw;
   int b0, b1, b2;
 };
@@ -179,7 +183,7 @@ __global__ void warp_affine_batch_u8_kernel(WarpBatchP p) {
   const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
   if (x >= p.dw || y >= p.dh) return;
   const int f = blockIdx.z, frame = p.frame[f];
-  uint8_t* dst = p.dst + (long)f * p.dh * p.dw * 3;
+  uint8_t* dst = p.dst + (long)p.slot[f] * p.dh * p.dw * 3;
   if (frame < 0) {
     uint8_t* d = dst + ((long)y * p.dw + x) * 3;
     d[0] = 0; d[1] = 0; d[2] = 0;
@@ -205,6 +209,28 @@ extern "C" int32_t keep_warp_batch_group(int32_t F, int32_t g, int32_t* first, i
   return KEEP_OK;
 }
 
+// The one launcher of both entries: the arguments have been judged.  `slot_of` == nullptr: face f goes to crop f.
+static int32_t warp_batch_launch(const char* name, const uint8_t* frames, int H, int W, uint8_t* dst, int F, int dh, int dw,
+                                 const int32_t* frame_of, const int32_t* slot_of, const double* dst_to_src, int border_b, int border_g,
+                                 int border_r, void* stream) {
+  WarpBatchP p;
+  p.src = frames;
+  p.H = H; p.W = W; p.dh = dh; p.dw = dw; p.b0 = border_b & 255; p.b1 = border_g & 255; p.b2 = border_r & 255;
+  int first = 0, count = 0;
+  for (int g = 0; warp_batch_group(F, g, &first, &count); ++g) {
+    p.dst = slot_of ? dst : dst + (long)first * dh * dw * 3;
+    for (int f = 0; f < WARP_BATCH_FACES; ++f) {
+      const bool live = f < count;
+      p.frame[f] = live ? frame_of[first + f] : -1;
+      p.slot[f] = live ? (slot_of ? slot_of[first + f] : f) : 0;     // (a face past `count` has no block: never read)
+      for (int k = 0; k < 6; ++k) p.m[f][k] = live ? dst_to_src[(long)(first + f) * 6 + k] : 0.0;
+    }
+    hipLaunchKernelGGL(warp_affine_batch_u8_kernel, dim3(cdiv(dw, 32), cdiv(dh, 8), count), dim3(256), 0, (hipStream_t)stream, p);
+    KEEP_LAUNCH_CHECK(name);
+  }
+  return KEEP_OK;
+}
+
 extern "C" int32_t keep_warp_affine_batch_u8(const uint8_t* frames, int32_t N, int32_t H, int32_t W, uint8_t* dst, int32_t F, int32_t dh,
                                              int32_t dw, const int32_t* frame_of, const double* dst_to_src, int32_t border_b,
                                              int32_t border_g, int32_t border_r, void* stream) {
@@ -216,21 +242,35 @@ extern "C" int32_t keep_warp_affine_batch_u8(const uint8_t* frames, int32_t N, i
     for (int k = 0; k < 6; ++k)
       KEEP_REQUIRE(std::isfinite(dst_to_src[(long)f * 6 + k]), "keep_warp_affine_batch_u8: face %d has a non-finite matrix entry", f);
   }
-  WarpBatchP p;
-  p.src = frames;
-  p.H = H; p.W = W; p.dh = dh; p.dw = dw; p.b0 = border_b & 255; p.b1 = border_g & 255; p.b2 = border_r & 255;
-  int first = 0, count = 0;
-  for (int g = 0; warp_batch_group(F, g, &first, &count); ++g) {
-    p.dst = dst + (long)first * dh * dw * 3;
-    for (int f = 0; f < WARP_BATCH_FACES; ++f) {
-      const bool live = f < count;
-      p.frame[f] = live ? frame_of[first + f] : -1;
-      for (int k = 0; k < 6; ++k) p.m[f][k] = live ? dst_to_src[(long)(first + f) * 6 + k] : 0.0;
-    }
-    hipLaunchKernelGGL(warp_affine_batch_u8_kernel, dim3(cdiv(dw, 32), cdiv(dh, 8), count), dim3(256), 0, (hipStream_t)stream, p);
-    KEEP_LAUNCH_CHECK("keep_warp_affine_batch_u8");
+  return warp_batch_launch("keep_warp_affine_batch_u8", frames, H, W, dst, F, dh, dw, frame_of, nullptr, dst_to_src, border_b, border_g,
+                           border_r, stream);
+}
+
+// ---- the same warp with every face written to a slot of the caller's choosing: face f -> dst + slot_of[f] * dh * dw * 3, dst
+// [n_slots,dh,dw,3].  Slots no face names are not touched.
+extern "C" int32_t keep_warp_affine_batch_scatter_u8(const uint8_t* frames, int32_t N, int32_t H, int32_t W, uint8_t* dst, int32_t n_slots,
+                                                     int32_t F, int32_t dh, int32_t dw, const int32_t* frame_of, const int32_t* slot_of,
+                                                     const double* dst_to_src, int32_t border_b, int32_t border_g, int32_t border_r,
+                                                     void* stream) {
+  KEEP_REQUIRE(frames && dst && frame_of && slot_of && dst_to_src, "keep_warp_affine_batch_scatter_u8: null pointer");
+  KEEP_REQUIRE(N > 0 && F > 0 && H > 0 && W > 0 && dh > 0 && dw > 0 && H < 32768 && W < 32768,
+               "keep_warp_affine_batch_scatter_u8: bad sizes N %d F %d H %d W %d dh %d dw %d", N, F, H, W, dh, dw);
+  KEEP_REQUIRE(n_slots >= F, "keep_warp_affine_batch_scatter_u8: %d faces do not fit %d slots", F, n_slots);
+  for (int f = 0; f < F; ++f) {            // everything is judged before anything is launched
+    KEEP_REQUIRE(frame_of[f] >= -1 && frame_of[f] < N, "keep_warp_affine_batch_scatter_u8: face %d names frame %d of %d", f, frame_of[f], N);
+    KEEP_REQUIRE(slot_of[f] >= 0 && slot_of[f] < n_slots, "keep_warp_affine_batch_scatter_u8: face %d names slot %d of %d", f, slot_of[f],
+                 n_slots);
+    for (int k = 0; k < 6; ++k)
+      KEEP_REQUIRE(std::isfinite(dst_to_src[(long)f * 6 + k]), "keep_warp_affine_batch_scatter_u8: face %d has a non-finite matrix entry", f);
   }
-  return KEEP_OK;
+  {                                        // a slot named twice: two faces would race for one crop
+    std::vector<int32_t> sorted(slot_of, slot_of + F);
+    std::sort(sorted.begin(), sorted.end());
+    for (int f = 1; f < F; ++f)
+      KEEP_REQUIRE(sorted[f] != sorted[f - 1], "keep_warp_affine_batch_scatter_u8: slot %d is named twice", sorted[f]);
+  }
+  return warp_batch_launch("keep_warp_affine_batch_scatter_u8", frames, H, W, dst, F, dh, dw, frame_of, slot_of, dst_to_src, border_b,
+                           border_g, border_r, stream);
 }
 
 // ---- use_parse=False soft mask (face_restoration_helper.py:386-415): coverage of the warped face square, rectangular erosions,

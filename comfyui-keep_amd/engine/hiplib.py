@@ -137,6 +137,7 @@ _CV_SIGNATURES = {
     'keep_resize_linear_fxy_u8': [_vp, _vp, _i32, _i32, _i32, _i32, _i32, C.c_double, C.c_double, _vp],
     'keep_warp_batch_group': [_i32, _i32, _vp, _vp],                       # (host-only: no stream argument)
     'keep_warp_affine_batch_u8': [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp],
+    'keep_warp_affine_batch_scatter_u8': [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp],
     'keep_attention_plan': [C.POINTER(AttnArgs), C.POINTER(AttnPlanOut)],  # (host-only: no stream argument)
 }
 CV_EXPORTED_SYMBOLS = ['keep_cv_abi_version'] + list(_CV_SIGNATURES)

@@ -80,20 +80,29 @@ def crop_faces(frame_u8, affine_matrices, face_size=(512, 512), device='cuda', b
     return out
 
 
-def crop_faces_batch(frames_dev, frame_of, affine_matrices, out, face_size=(512, 512), border=ALIGN_BORDER_BGR):
+def crop_faces_batch(frames_dev, frame_of, affine_matrices, out, face_size=(512, 512), border=ALIGN_BORDER_BGR, slot_of=None):
     """``crop_faces`` for the faces of a whole chunk of frames that is resident on the device: uint8 [N,H,W,3] contiguous frames,
     ``frame_of[f]`` the frame face f is taken from, its frame -> crop similarity matrix (None, or frame -1: the black crop) ->
     ``out`` uint8 [F,fh,fw,3], contiguous, on the same device (a slice of a larger crop tensor), written by ONE
     ``keep_warp_affine_batch_u8`` call on the current stream (the library launches once per 32 faces; frame indices and matrices travel
-    in the kernel arguments).  Returns ``out``."""
+    in the kernel arguments).  Returns ``out``.
+
+    ``slot_of`` (track clips): ``out`` is the WHOLE crop tensor uint8 [n_slots,fh,fw,3] and face f is written to ``out[slot_of[f]]`` by
+    one ``keep_warp_affine_batch_scatter_u8`` call; slots no face names keep what they hold."""
     fw, fh = face_size
     F = len(affine_matrices)
     if len(frame_of) != F:
         raise ValueError(f"crop_faces_batch: {len(frame_of)} frame indices for {F} matrices")
+    if slot_of is not None and len(slot_of) != F:
+        raise ValueError(f"crop_faces_batch: {len(slot_of)} slots for {F} matrices")
     if (frames_dev.dtype != torch.uint8 or frames_dev.dim() != 4 or frames_dev.shape[3] != 3 or not frames_dev.is_cuda
             or not frames_dev.is_contiguous()):
         raise ValueError("crop_faces_batch: frames must be a contiguous uint8 [N,H,W,3] device tensor")
-    if (out.dtype != torch.uint8 or tuple(out.shape) != (F, fh, fw, 3) or out.device != frames_dev.device or not out.is_contiguous()):
+    if slot_of is not None:
+        if (out.dtype != torch.uint8 or out.dim() != 4 or tuple(out.shape[1:]) != (fh, fw, 3) or out.shape[0] < F
+                or out.device != frames_dev.device or not out.is_contiguous()):
+            raise ValueError(f"crop_faces_batch: out must be a contiguous uint8 [n_slots >= {F},{fh},{fw},3] tensor on {frames_dev.device}")
+    elif (out.dtype != torch.uint8 or tuple(out.shape) != (F, fh, fw, 3) or out.device != frames_dev.device or not out.is_contiguous()):
         raise ValueError(f"crop_faces_batch: out must be a contiguous uint8 {(F, fh, fw, 3)} tensor on {frames_dev.device}")
     if F == 0:
         return out
@@ -104,7 +113,12 @@ def crop_faces_batch(frames_dev, frame_of, affine_matrices, out, face_size=(512,
         if M is not None:
             d2s[6 * f:6 * f + 6] = invert_affine(M).reshape(-1).tolist()
     with torch.cuda.device(frames_dev.device):
-        L.call('keep_warp_affine_batch_u8', frames_dev, N, H, W, out, F, fh, fw, idx, d2s, int(border[0]), int(border[1]), int(border[2]))
+        if slot_of is None:
+            L.call('keep_warp_affine_batch_u8', frames_dev, N, H, W, out, F, fh, fw, idx, d2s, int(border[0]), int(border[1]), int(border[2]))
+        else:
+            slots = (C.c_int32 * F)(*[int(s) for s in slot_of])
+            L.call('keep_warp_affine_batch_scatter_u8', frames_dev, N, H, W, out, int(out.shape[0]), F, fh, fw, idx, slots, d2s,
+                   int(border[0]), int(border[1]), int(border[2]))
     return out
 
 

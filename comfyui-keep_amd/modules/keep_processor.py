@@ -42,6 +42,11 @@ the store.  Where the first frame's ``read_image`` shows that enlargement, the s
 their enlargement by one ``keep_resize_linear_fxy_u8`` launch, which is the detector batch and the source of the crop warp -- and the
 paste-back resizes the originals to the enlarged size (KEEP_AMD_GPU_SMALL_FRAMES; tests/test_gpu_small_frames.py).  Without the store the
 streamed paste brings each background to the size ``read_image`` made before it composites.
+
+Track clips (``KEEP_AMD_TRACK_CLIPS``, off by default): the repaired form of P1 and P3 -- every clip holds consecutive frames of one face
+track (``clip_plan.py``), every face of a single image is a clip of its own.  Crop numbering and the paste order stay; the frame store lays
+its crop tensor out by clip (``keep_warp_affine_batch_scatter_u8``) so the clips remain views.  With the knob off nothing plans, permutes or
+scatters.  No reference to compare with: each face equals its track restored on its own, bit for bit (tests/test_gpu_track_clips.py).
 """
 import os
 
@@ -459,6 +464,11 @@ class KEEPFaceProcessor:
         # and then returns the *input* frames.  Default: bug-compatible.  KEEP_AMD_RETURN_RESTORED_ALIGNED=1 (or setting
         # the attribute) returns the restored faces instead.
         self.return_restored_aligned = os.environ.get('KEEP_AMD_RETURN_RESTORED_ALIGNED', '0') == '1'
+        # reference quirks P1 / P3: with several faces in the picture the flat frame-major crop list is cut into clips, so a clip
+        # interleaves identities (A0 B0 C0 A1 ...), and the single-image node makes ONE clip of all its faces.  Default: bug-compatible.
+        # KEEP_AMD_TRACK_CLIPS=1 (or setting the attribute): every clip holds consecutive frames of one track (``clip_plan.py``), every
+        # face of a single image is a clip of its own.  With one face per frame the clips are the default's.
+        self.track_clips = os.environ.get('KEEP_AMD_TRACK_CLIPS', '0') == '1'
         # paste-back compositing on the GPU (engine/paste.py).  Opt-in: its arithmetic restates OpenCV's and
         # could not be checked against cv2 itself in the build image.
         # KEEP_AMD_GPU_PASTE: '1' on, '0' off; unset = 'auto': the first paste runs ``opencv_agrees_with_gpu_paste`` -- the HIP
@@ -501,6 +511,25 @@ class KEEPFaceProcessor:
         self.detect_resize = 640        # the sequence pre-pass's ``resize`` of get_face_landmarks_5 (keep_processor.py:207-213 of the reference)
 
     # ------------------------------------------------------------------ net invocation
+    def _restore_member_clips(self, crops_tensor, members):
+        """``_restore_clips`` over clips given as lists of crop indices (track clips): the outputs go back to crop order."""
+        clips = []
+        for m in members:
+            clip = crops_tensor[:, m]
+            if len(m) == 1 and not getattr(self.keep_net, 'supports_single_frame', False):
+                clip = torch.cat([clip, clip], dim=1)    # the reference net needs T>=2 (KP:173-178); frame 0 is kept
+            clips.append(clip)
+        run_clips = getattr(self.keep_net, 'run_clips', None)
+        if run_clips is not None:
+            outs = run_clips(clips, need_upscale=False)
+        else:
+            outs = [self.keep_net(c, need_upscale=False) for c in tqdm(clips, desc="Restoring faces with KEEP")]
+        restored = [None] * crops_tensor.shape[1]
+        for m, o in zip(members, outs):
+            for k, i in enumerate(m):
+                restored[i] = o[0, k]
+        return torch.stack(restored)
+
     def _restore_clips(self, crops_tensor, max_clip_length):
         """crops_tensor [1,N,3,512,512] on device -> [N,3,512,512] restored (fp32, unclamped)."""
         n = crops_tensor.shape[1]
@@ -521,20 +550,35 @@ class KEEPFaceProcessor:
             kept.append(o[:, 0:1] if e - s == 1 else o)
         return torch.cat(kept, dim=1).squeeze(0)
 
-    def _restore_crops_u8(self, crops, max_clip_length):
+    def _restore_crops_u8(self, crops, max_clip_length, members=None):
         """list of uint8 BGR [512,512,3] crops -> list of restored uint8 BGR crops (same order).
 
         Same chunking as ``_restore_clips`` (keep_processor.py:263-270); when the net offers ``run_clips_u8`` the
         uint8<->fp32 conversions of keep_processor.py:258-259,272-273 run on the GPU and only uint8 crosses PCIe,
-        otherwise the host converters are used (reference behaviour)."""
+        otherwise the host converters are used (reference behaviour).
+
+        ``members`` (track clips): the clips as lists of crop indices (``plan_track_clips``) instead of the cut of the flat list; every
+        crop is in exactly one of them, the lone-crop rule applies per clip and the outputs are scattered back to crop order."""
         run_u8 = getattr(self.keep_net, 'run_clips_u8', None)
         if run_u8 is None:
             x = crops_to_net_input(crops).unsqueeze(0).to(self.device)
-            return [net_output_to_bgr_u8(f) for f in self._restore_clips(x, max_clip_length)]
+            restored = self._restore_clips(x, max_clip_length) if members is None else self._restore_member_clips(x, members)
+            return [net_output_to_bgr_u8(f) for f in restored]
         crops = [np.asarray(c) for c in crops]
+        t1_ok = getattr(self.keep_net, 'supports_single_frame', False)
+        if members is not None:
+            clips = [[crops[i] for i in m] * (2 if len(m) == 1 and not t1_ok else 1) for m in members]   # (T >= 2: KP:173-178, frame 0 kept)
+            outs = run_u8(clips)
+            if outs is None:      # a non-root rank of a run sharded over several GPUs
+                return None
+            faces = [None] * len(crops)
+            for m, o in zip(members, outs):
+                o = o.numpy()
+                for k, i in enumerate(m):
+                    faces[i] = np.ascontiguousarray(o[k])
+            return faces
         spans = split_clips(len(crops), max_clip_length)
         clips = []
-        t1_ok = getattr(self.keep_net, 'supports_single_frame', False)
         for s, e in spans:
             clip = crops[s:e]                            # a clip = a list of crops: the engine copies them straight into its
             if e - s == 1 and not t1_ok:                 # pinned upload buffer (no stacked intermediate)
@@ -800,7 +844,11 @@ class KEEPFaceProcessor:
                 return _host(bg_img_final)
 
         # one face -> T=2 duplicate, keep frame 0; several faces -> one "clip" of T=#faces (KP:173-178)
-        faces = self._restore_crops_u8(crops, max_clip_length=max(len(crops), 1))
+        # (track clips: the faces of one picture are no sequence -- each is a clip of its own, restored like a lone face)
+        if self.track_clips and len(crops) > 1:
+            faces = self._restore_crops_u8(crops, max_clip_length=1, members=[[i] for i in range(len(crops))])
+        else:
+            faces = self._restore_crops_u8(crops, max_clip_length=max(len(crops), 1))
         if faces is None:
             return None
         self.last_restored_faces = faces
@@ -957,7 +1005,7 @@ class KEEPFaceProcessor:
         return tuple(getattr(helper, 'face_size', (512, 512))) == (512, 512)
 
     def _restore_and_paste_streamed(self, frames_bgr, crops, affines, faces_per_frame, max_clip_length, factor, draw_box, pbar,
-                                    as_u8, store=None, input_hw=None):
+                                    as_u8, store=None, input_hw=None, plan=None):
         """Steps 3 and 4 of ``process_image_sequence`` (keep_processor.py:263-304) as ONE pipeline on the GPU.
 
         ``run_clips_u8(sink=...)`` restores the clips in batch groups and hands each finished, range-checked group over as device
@@ -974,7 +1022,11 @@ class KEEPFaceProcessor:
 
         ``input_hw`` (without a store): per frame with faces the size ``read_image`` gave it.  Where that is not the frame's own -- small
         frames, enlarged at :182-184 -- the inverse affines live in the enlarged frame, and the background is resized to that size times
-        the factor before the composite, the helper's own :357-358."""
+        the factor before the composite, the helper's own :357-358.
+
+        ``plan`` (track clips): ``plan_track_clips``' (clips, slot_of) instead of the cut of the flat list.  Crop numbering, ``first``,
+        ``affines`` and the paste order stay; a clip's position k is crop ``clips[c][k]``.  With a store the crop tensor is laid out by
+        slot (``_stored_sequence``), so the clips still are views of it."""
         from ..engine import hiplib as L
         from ..engine.paste import GpuPaster
         helper, net, dev = self.face_helper, self.keep_net, torch.device(self.device)
@@ -984,11 +1036,22 @@ class KEEPFaceProcessor:
             self._paster = GpuPaster(dev)
         paster, engine = self._paster, helper.face_parse.engine
         n_frames, n_crops = len(frames_bgr), len(crops)
-        spans = split_clips(n_crops, max_clip_length)
         first = [0]
         for k in faces_per_frame:
             first.append(first[-1] + k)
         clips = []
+        if plan is None:
+            spans, members = split_clips(n_crops, max_clip_length), None
+        else:
+            from .clip_plan import clip_slot_spans
+            spans, members = [], plan[0]
+            for m, (s0, s1) in zip(members, clip_slot_spans(members)):
+                if store is not None:
+                    clips.append(crops[s0:s1])                            # a view of the crop tensor, which is laid out by slot
+                elif all(isinstance(crops[i], torch.Tensor) and crops[i].is_cuda for i in m):
+                    clips.append(torch.stack([crops[i] for i in m]))
+                else:
+                    clips.append([crops[i].cpu().numpy() if isinstance(crops[i], torch.Tensor) else np.asarray(crops[i]) for i in m])
         for s, e in spans:
             part = crops[s:e]
             if store is not None:
@@ -1083,6 +1146,16 @@ class KEEPFaceProcessor:
                         classes[s + k] = classes_list[j][k]
             advance()
 
+        def sink_members(ids, crops_list, classes_list):
+            for j, cid in enumerate(ids):
+                for k, i in enumerate(members[cid]):
+                    ready[i] = crops_list[j][k]
+                    if classes_list is not None:
+                        classes[i] = classes_list[j][k]
+            advance()
+
+        if members is not None:
+            sink = sink_members
         max_b = None
         groups = int(os.environ.get('KEEP_AMD_STREAM_GROUPS', '0') or 0)      # >= 2: at least that many batch groups (more overlap, smaller batches)
         if groups >= 2 and hasattr(net, 'clips_per_call'):
@@ -1296,13 +1369,18 @@ class KEEPFaceProcessor:
             if n_crops == 0 or (store.small is not None and 0 in faces_per_frame):
                 store.drop()
                 return None
+            plan = self._track_plan([[key for key, seq in tracks.items() if not np.isnan(seq[i]).any()] for i in range(n_frames)],
+                                    max_clip_length) if self.track_clips else None
             with torch.cuda.device(store.device):
                 crops = torch.empty((n_crops, 512, 512, 3), dtype=torch.uint8, device=store.device)
                 off = 0
                 for k, (a, b) in enumerate(store.spans):
                     frame_of = [t - a for t in range(a, b) for _ in per_frame[t]]
                     mats = [M for t in range(a, b) for M in per_frame[t]]
-                    if mats:
+                    if mats and plan is not None:        # track clips: the crop tensor is laid out by slot, crop i lives in slot_of[i]
+                        crop_faces_batch(store.warp_source(k), frame_of, mats, crops, (512, 512), slot_of=plan[1][off:off + len(mats)])
+                        off += len(mats)
+                    elif mats:
                         crop_faces_batch(store.warp_source(k), frame_of, mats, crops[off:off + len(mats)], (512, 512))
                         off += len(mats)
                     store.ebufs[k] = None                # (an enlarged chunk has no reader behind its warp, which ran on its own stream)
@@ -1312,9 +1390,14 @@ class KEEPFaceProcessor:
         affines = [M for ms in per_frame for M in ms]
         try:
             return self._restore_and_paste_streamed(frames_bgr, crops, affines, faces_per_frame, max_clip_length, factor, draw_box, pbar,
-                                                    as_u8, store=store)
+                                                    as_u8, store=store, plan=plan)
         finally:
             store.drop(getattr(self, '_paste_stream', None))        # (nothing is left after ``ps.synchronize()``; an error's way out: the paste stream may still read)
+
+    def _track_plan(self, presence, max_clip_length):
+        """``plan_track_clips`` for a sequence (``track_clips`` only): (clips as crop-index lists, slot of every crop)."""
+        from .clip_plan import plan_track_clips
+        return plan_track_clips(presence, max_clip_length)
 
     def _detect_batching(self, det, n):
         """(whether the pre-pass runs the detector over batches, frames per chunk)"""
@@ -1579,12 +1662,17 @@ class KEEPFaceProcessor:
         # -- 2. crops, flat and frame-major
         crops, affines, faces_per_frame, input_hw = [], [], [], [None] * n_frames
         stream_ok = (not has_aligned_frames) and self._stream_applies(helper, frames_bgr, None, draw_box)
+        presence = [] if self.track_clips else None      # track clips: the keys of the tracks behind every frame's crops, in face order
         for i in tqdm(range(n_frames), desc="Cropping and aligning faces"):
             if has_aligned_frames:
                 frame_crops, frame_aff = [self._aligned_face(frames_bgr[i])], []
+                if presence is not None:
+                    presence.append([0])                 # (one track on every frame: the plan is the cut of the flat list)
             else:
                 frame_crops, frame_aff = [], []
                 active = [seq[i] for seq in tracks.values() if not np.isnan(seq[i]).any()]
+                if presence is not None:
+                    presence.append([key for key, seq in tracks.items() if not np.isnan(seq[i]).any()])
                 if active:
                     helper.clean_all()
                     helper.read_image(frames_bgr[i])
@@ -1596,17 +1684,21 @@ class KEEPFaceProcessor:
             faces_per_frame.append(len(frame_crops))
             crops.extend(frame_crops)
             affines.extend(frame_aff)
+            if presence is not None and len(presence[i]) != len(frame_crops):
+                raise RuntimeError(f"track clips: frame {i} has {len(frame_crops)} crops for {len(presence[i])} tracks")
+        plan = self._track_plan(presence, max_clip_length) if presence is not None else None
 
         # -- 3 + 4 streamed: restore group g+1 while group g is parsed, pasted and downloaded (round 5)
         if crops and not has_aligned_frames and self._stream_applies(helper, frames_bgr, crops, draw_box):
             return self._restore_and_paste_streamed(frames_bgr, crops, affines, faces_per_frame, max_clip_length,
-                                                    final_upscale_factor, draw_box, pbar, as_u8, input_hw=input_hw)
+                                                    final_upscale_factor, draw_box, pbar, as_u8, input_hw=input_hw, plan=plan)
 
         # -- 3. restore: the hot path
         crops = [c.cpu().numpy() if isinstance(c, torch.Tensor) else c for c in crops]
         restored_faces = []
         if crops:
-            restored_faces = self._restore_crops_u8(crops, max_clip_length)
+            restored_faces = (self._restore_crops_u8(crops, max_clip_length) if plan is None
+                              else self._restore_crops_u8(crops, max_clip_length, members=plan[0]))
             if restored_faces is None:          # non-root rank of a sharded multi-GPU run (engine/dist.py): nothing to paste here
                 return None
         self.last_restored_faces = restored_faces

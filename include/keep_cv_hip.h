@@ -79,11 +79,20 @@ int32_t keep_resize_linear_fxy_u8(const uint8_t* src, uint8_t* dst, int32_t N, i
  * pointer; N, F, H, W, dh or dw <= 0; H or W >= 32768; a frame index outside -1 .. N - 1; a non-finite matrix entry.
  *
  * keep_warp_batch_group: HOST-only C (no device, no stream): launch g of F faces covers faces first .. first + count - 1 -- the rule the
- * launcher itself loops over; KEEP_EINVAL for a g that F faces have no launch for. */
+ * launcher itself loops over; KEEP_EINVAL for a g that F faces have no launch for.
+ *
+ * keep_warp_affine_batch_scatter_u8: the same warp (the same kernel, launches and pixel arithmetic) with every face written to a slot of
+ * the caller's choosing: `dst` is [n_slots,dh,dw,3] and face f goes to dst + slot_of[f] * dh * dw * 3; `slot_of` [F] is a HOST array like
+ * `frame_of`.  A slot no face names is not written.  KEEP_EINVAL, before anything is launched: everything keep_warp_affine_batch_u8
+ * refuses; n_slots < F; a slot outside 0 .. n_slots - 1; a slot named twice. */
 int32_t keep_warp_batch_group(int32_t F, int32_t g, int32_t* first, int32_t* count);
 int32_t keep_warp_affine_batch_u8(const uint8_t* frames, int32_t N, int32_t H, int32_t W, uint8_t* dst, int32_t F, int32_t dh, int32_t dw,
                                   const int32_t* frame_of /*host [F]*/, const double* dst_to_src /*host [F*6]*/, int32_t border_b,
                                   int32_t border_g, int32_t border_r, void* stream);
+int32_t keep_warp_affine_batch_scatter_u8(const uint8_t* frames, int32_t N, int32_t H, int32_t W, uint8_t* dst, int32_t n_slots, int32_t F,
+                                          int32_t dh, int32_t dw, const int32_t* frame_of /*host [F]*/, const int32_t* slot_of /*host [F]*/,
+                                          const double* dst_to_src /*host [F*6]*/, int32_t border_b, int32_t border_g, int32_t border_r,
+                                          void* stream);
 
 /* ---- what one attention call of keep_hip.h would launch: HOST-only C (no device, no stream; no pointer of `a` is dereferenced, they are
  * tested for alignment only, so aligned made-up addresses do).  The arguments go through the same two steps as the launch -- the
