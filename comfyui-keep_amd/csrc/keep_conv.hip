@@ -11,9 +11,13 @@
 // is fetched into registers while tile k is on the matrix cores (one barrier per K step).
 // Small-spatial layers (16x16 .. 64x64 maps) under-fill 256 CUs with output tiles alone -> deterministic split-K
 // over the (tap, Cin-chunk) steps into a caller workspace + a reduce/epilogue kernel.
+#include <cxxabi.h>
 #include <stdlib.h>
 
+#include <string>
+
 #include "keep_conv_common.h"
+#include "../../include/keep_cv_hip.h"   // keep_conv2d_launch_plan
 
 // PLAIN (host-checked): no prologue, no upsample, Cin % 16 == 0 and 16-byte aligned rows: the K loop carries none of
 // those uniform branches (token GEMMs, 1x1 convs, plain strided convs).
@@ -1763,7 +1767,10 @@ static void fill_conv_params(const keep_conv2d_args* a, ConvP& p) {
   p.wb = (const unsigned short*)a->weight_bf16;
   p.wx3 = (const unsigned short*)a->weight_x3;
   p.acc_scale = a->x3_acc_scale;
-  p.in_amax = a->x3_in_amax;
+  // KEEP_MMA_X3 behind a prologue ACTIVATION: the x3 kernels split the activated values as they are (swish / ReLU of a normalised input is
+  // bounded, the host never probes it), so the range scale must not be undone on the accumulators either -- the probe is not used at all.
+  // (Before, such a call came back multiplied by the inverse scale.)  KEEP_MMA_X1 scales the prologue's result in every form.
+  p.in_amax = (a->mma == KEEP_MMA_X3 && a->pro_act != KEEP_PRO_NONE) ? nullptr : a->x3_in_amax;
   p.in2 = (const float*)a->in2;
   p.cin1 = a->in2_cin1;
   p.out_amax = nullptr;
@@ -2217,7 +2224,34 @@ extern "C" int32_t keep_conv2d_plan(const keep_conv2d_args* a_in, keep_conv2d_pl
   return KEEP_OK;
 }
 
-extern "C" int32_t keep_conv2d(const keep_conv2d_args* a_in, void* stream) {
+// launch-or-name (keep_conv_common.h): one instantiation's device symbol, demangled, without the return type and the parameter list
+void keep_conv_trace_add(ConvTrace* tr, const char* mangled) {
+  int status = 0;
+  char* full = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);
+  std::string name = (status == 0 && full) ? full : mangled;
+  free(full);
+  int depth = 0;
+  for (size_t i = 0; i < name.size(); ++i) {      // cut at the parameter list: the first '(' outside the template arguments
+    if (name[i] == '<') ++depth;
+    if (name[i] == '>') --depth;
+    if (name[i] == '(' && depth == 0) {
+      name.resize(i);
+      break;
+    }
+  }
+  if (name.compare(0, 5, "void ") == 0) name.erase(0, 5);
+  const int n = snprintf(tr->buf + tr->len, (size_t)(tr->cap - tr->len), "%s%s", tr->len ? " + " : "", name.c_str());
+  if (n < 0 || n >= tr->cap - tr->len) {
+    tr->overflow = true;
+    tr->buf[tr->len] = 0;
+    return;
+  }
+  tr->len += n;
+  ++tr->count;
+}
+
+// keep_conv2d (tr == NULL) and keep_conv2d_launch_plan (a trace: every KEEP_CONV_LAUNCH names its kernel instead of launching it)
+static int conv_launch(const keep_conv2d_args* a_in, void* stream, ConvTrace* tr) {
   keep_conv2d_args a_local;
   ConvP p;
   ConvPlan pl;
@@ -2241,8 +2275,8 @@ extern "C" int32_t keep_conv2d(const keep_conv2d_args* a_in, void* stream) {
   if (a->x3_out_amax) {
     KEEP_REQUIRE(pl.amax_ok, "keep_conv2d: x3_out_amax is not available for this call (keep_conv2d_plan: out_amax_ok)");
     if (!a->x3_out_amax_zeroed) {
-      hipLaunchKernelGGL(zero_u32_kernel, dim3(cdiv(a->N, 256)), dim3(256), 0, st, reinterpret_cast<unsigned*>(a->x3_out_amax), a->N);
-      KEEP_LAUNCH_CHECK("keep_conv2d(zero x3_out_amax)");
+      KEEP_CONV_LAUNCH(tr, dim3(cdiv(a->N, 256)), dim3(256), st, (reinterpret_cast<unsigned*>(a->x3_out_amax), a->N), zero_u32_kernel);
+      KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(zero x3_out_amax)");
     }
     p.out_amax = reinterpret_cast<unsigned*>(a->x3_out_amax);
   }
@@ -2252,31 +2286,31 @@ extern "C" int32_t keep_conv2d(const keep_conv2d_args* a_in, void* stream) {
   dim3 block(256);
   const int tw = pl.wide ? 32 : 16, th = 256 / tw;
   const int tiles_x = a->Wo / tw, tiles_y = a->Ho / th, ncb = (a->Cout + 63) / 64;
-  const int n_cu = keep_num_cu();
+  const int n_cu = conv_num_cu(tr);
   switch (pl.path) {
     case PATH_COUT4: {
       dim3 grid((a->Ho / SC_TH) * (a->Wo / SC_TW), a->N);
-      hipLaunchKernelGGL(conv3x3_cout4_kernel, grid, block, 0, st, p);
-      KEEP_LAUNCH_CHECK("keep_conv2d(cout<=4)");
+      KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv3x3_cout4_kernel);
+      KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(cout<=4)");
       return KEEP_OK;
     }
     case PATH_C3: {
       const int tx = a->Wo / 32, ty = a->Ho / 8;
       const int n_items = a->N * tx * ty * ncb;
-      hipLaunchKernelGGL(conv3x3_c3_kernel, dim3(persistent_grid(n_items, n_cu)), block, 0, st, p, tx, ty, ncb, n_items);
-      KEEP_LAUNCH_CHECK("keep_conv2d(Cin<=3)");
+      KEEP_CONV_LAUNCH(tr, dim3(persistent_grid(n_items, n_cu)), block, st, (p, tx, ty, ncb, n_items), conv3x3_c3_kernel);
+      KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(Cin<=3)");
       return KEEP_OK;
     }
     case PATH_C3_X3:
-      rc = keep_conv2d_x3_c3(a, p, st);
+      rc = keep_conv2d_x3_c3(a, p, st, tr);
       if (rc != KEEP_OK) return rc;
       break;
     case PATH_HALO_X3:
-      rc = keep_conv2d_x3_halo(a, p, pl, st);
+      rc = keep_conv2d_x3_halo(a, p, pl, st, tr);
       if (rc != KEEP_OK) return rc;
       break;
     case PATH_GATHER_X3:
-      rc = pl.form == FORM_GEMM_LAT ? keep_conv2d_x3_gemm_lat(a, p, pl, st) : keep_conv2d_x3_gather(a, p, pl, st);
+      rc = pl.form == FORM_GEMM_LAT ? keep_conv2d_x3_gemm_lat(a, p, pl, st, tr) : keep_conv2d_x3_gather(a, p, pl, st, tr);
       if (rc != KEEP_OK) return rc;
       break;
     case PATH_HALO_F32: {
@@ -2284,18 +2318,18 @@ extern "C" int32_t keep_conv2d(const keep_conv2d_args* a_in, void* stream) {
       dim3 gridf(persistent_grid(n_items, n_cu));
 #define KEEP_LAUNCH_HF(TWV)                                                                                                  \
   if (a->pro_act == KEEP_PRO_SWISH)                                                                                          \
-    hipLaunchKernelGGL((conv3x3_halo_f32_kernel<TWV, KEEP_PRO_SWISH>), gridf, block, 0, st, p, tiles_x, tiles_y, ncb, n_items); \
+    KEEP_CONV_LAUNCH(tr, gridf, block, st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_halo_f32_kernel<TWV, KEEP_PRO_SWISH>); \
   else if (a->pro_act == KEEP_PRO_RELU)                                                                                      \
-    hipLaunchKernelGGL((conv3x3_halo_f32_kernel<TWV, KEEP_PRO_RELU>), gridf, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);  \
+    KEEP_CONV_LAUNCH(tr, gridf, block, st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_halo_f32_kernel<TWV, KEEP_PRO_RELU>);  \
   else                                                                                                                       \
-    hipLaunchKernelGGL((conv3x3_halo_f32_kernel<TWV, KEEP_PRO_NONE>), gridf, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
+    KEEP_CONV_LAUNCH(tr, gridf, block, st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_halo_f32_kernel<TWV, KEEP_PRO_NONE>);
       if (pl.wide) {
         KEEP_LAUNCH_HF(32)
       } else {
         KEEP_LAUNCH_HF(16)
       }
 #undef KEEP_LAUNCH_HF
-      KEEP_LAUNCH_CHECK("keep_conv2d(halo f32)");
+      KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(halo f32)");
       break;
     }
     case PATH_HALO_BF16: {
@@ -2304,9 +2338,9 @@ extern "C" int32_t keep_conv2d(const keep_conv2d_args* a_in, void* stream) {
       const bool simple = p.split_k == 1 && !a->aux && a->epi_act == KEEP_ACT_NONE;
 #define KEEP_LAUNCH_H3(INB, TWV)                                                                                          \
   if (simple)                                                                                                             \
-    hipLaunchKernelGGL((conv3x3_halo3_kernel<INB, TWV, true>), grid3, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);   \
+    KEEP_CONV_LAUNCH(tr, grid3, block, st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_halo3_kernel<INB, TWV, true>);   \
   else                                                                                                                    \
-    hipLaunchKernelGGL((conv3x3_halo3_kernel<INB, TWV, false>), grid3, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
+    KEEP_CONV_LAUNCH(tr, grid3, block, st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_halo3_kernel<INB, TWV, false>);
       if (p.in_bf16 && pl.wide) {
         KEEP_LAUNCH_H3(true, 32)
       } else if (p.in_bf16) {
@@ -2317,62 +2351,62 @@ extern "C" int32_t keep_conv2d(const keep_conv2d_args* a_in, void* stream) {
         KEEP_LAUNCH_H3(false, 16)
       }
 #undef KEEP_LAUNCH_H3
-      KEEP_LAUNCH_CHECK("keep_conv2d(halo v3)");
+      KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(halo v3)");
       break;
     }
     case PATH_HALO_BF16_V1: {
       dim3 grid(a->N * tiles_x * tiles_y * ncb, 1, p.split_k);
       if (p.in_bf16 && pl.wide)
-        hipLaunchKernelGGL((conv3x3_halo_kernel<true, 32>), grid, block, 0, st, p, tiles_x, tiles_y, ncb);
+        KEEP_CONV_LAUNCH(tr, grid, block, st, (p, tiles_x, tiles_y, ncb), conv3x3_halo_kernel<true, 32>);
       else if (p.in_bf16)
-        hipLaunchKernelGGL((conv3x3_halo_kernel<true, 16>), grid, block, 0, st, p, tiles_x, tiles_y, ncb);
+        KEEP_CONV_LAUNCH(tr, grid, block, st, (p, tiles_x, tiles_y, ncb), conv3x3_halo_kernel<true, 16>);
       else if (pl.wide)
-        hipLaunchKernelGGL((conv3x3_halo_kernel<false, 32>), grid, block, 0, st, p, tiles_x, tiles_y, ncb);
+        KEEP_CONV_LAUNCH(tr, grid, block, st, (p, tiles_x, tiles_y, ncb), conv3x3_halo_kernel<false, 32>);
       else
-        hipLaunchKernelGGL((conv3x3_halo_kernel<false, 16>), grid, block, 0, st, p, tiles_x, tiles_y, ncb);
-      KEEP_LAUNCH_CHECK("keep_conv2d(halo v1)");
+        KEEP_CONV_LAUNCH(tr, grid, block, st, (p, tiles_x, tiles_y, ncb), conv3x3_halo_kernel<false, 16>);
+      KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(halo v1)");
       break;
     }
     case PATH_GATHER_BF16: {
       if (pl.tile == 0) {
         dim3 grid(cdiv(M, 128), cdiv(a->Cout, 32), p.split_k);
-        hipLaunchKernelGGL((conv_bf16_kernel<4, 1, 1, 1, 64, 1>), grid, block, 0, st, p);
+        KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_bf16_kernel<4, 1, 1, 1, 64, 1>);
       } else if (pl.tile == 1) {
         dim3 grid(cdiv(M, 64), cdiv(a->Cout, 64), p.split_k);
         if (pl.bk256)
-          hipLaunchKernelGGL((conv_bf16_kernel<2, 2, 1, 1, 256, 1>), grid, block, 0, st, p);
+          KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_bf16_kernel<2, 2, 1, 1, 256, 1>);
         else if (pl.plain)
-          hipLaunchKernelGGL((conv_bf16_kernel<2, 2, 1, 1, 64, 1, true>), grid, block, 0, st, p);
+          KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_bf16_kernel<2, 2, 1, 1, 64, 1, true>);
         else
-          hipLaunchKernelGGL((conv_bf16_kernel<2, 2, 1, 1, 64, 1>), grid, block, 0, st, p);
+          KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_bf16_kernel<2, 2, 1, 1, 64, 1>);
       } else {
         dim3 grid(cdiv(M, 128), cdiv(a->Cout, 128), p.split_k);
         if (pl.plain)
-          hipLaunchKernelGGL((conv_bf16_kernel<2, 2, 2, 2, 64, 1, true>), grid, block, 0, st, p);
+          KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_bf16_kernel<2, 2, 2, 2, 64, 1, true>);
         else
-          hipLaunchKernelGGL((conv_bf16_kernel<2, 2, 2, 2, 64, 1>), grid, block, 0, st, p);
+          KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_bf16_kernel<2, 2, 2, 2, 64, 1>);
       }
-      KEEP_LAUNCH_CHECK("keep_conv2d(gather bf16)");
+      KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(gather bf16)");
       break;
     }
     case PATH_GATHER_F32: {
       if (pl.tile == 0) {
         dim3 grid(cdiv(M, 128), cdiv(a->Cout, 32), p.split_k);
-        hipLaunchKernelGGL((conv_f32_kernel<4, 1, 1, 1>), grid, block, 0, st, p);
+        KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_f32_kernel<4, 1, 1, 1>);
       } else if (pl.tile == 1) {
         dim3 grid(cdiv(M, 64), cdiv(a->Cout, 64), p.split_k);
         if (pl.plain)
-          hipLaunchKernelGGL((conv_f32_kernel<2, 2, 1, 1, true>), grid, block, 0, st, p);
+          KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_f32_kernel<2, 2, 1, 1, true>);
         else
-          hipLaunchKernelGGL((conv_f32_kernel<2, 2, 1, 1>), grid, block, 0, st, p);
+          KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_f32_kernel<2, 2, 1, 1>);
       } else {
         dim3 grid(cdiv(M, 128), cdiv(a->Cout, 128), p.split_k);
         if (pl.plain)
-          hipLaunchKernelGGL((conv_f32_kernel<2, 2, 2, 2, true>), grid, block, 0, st, p);
+          KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_f32_kernel<2, 2, 2, 2, true>);
         else
-          hipLaunchKernelGGL((conv_f32_kernel<2, 2, 2, 2>), grid, block, 0, st, p);
+          KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_f32_kernel<2, 2, 2, 2>);
       }
-      KEEP_LAUNCH_CHECK("keep_conv2d(gather f32)");
+      KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(gather f32)");
       break;
     }
     case PATH_NEEDS_PRENORM: break;      // (refused above, before anything was launched; no default: a new path must get an arm)
@@ -2382,14 +2416,31 @@ extern "C" int32_t keep_conv2d(const keep_conv2d_args* a_in, void* stream) {
     if (p.vec_epi) {
       int blocks = cdiv(total / 4, 256);
       if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(conv_splitk_reduce4_kernel, dim3(blocks), dim3(256), 0, st, p);
-      KEEP_LAUNCH_CHECK("keep_conv2d(split-K reduce)");
+      KEEP_CONV_LAUNCH(tr, dim3(blocks), dim3(256), st, (p), conv_splitk_reduce4_kernel);
+      KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(split-K reduce)");
       return KEEP_OK;
     }
     int blocks = cdiv(total, 256);
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, p);
-    KEEP_LAUNCH_CHECK("keep_conv2d(split-K reduce)");
+    KEEP_CONV_LAUNCH(tr, dim3(blocks), dim3(256), st, (p), conv_splitk_reduce_kernel);
+    KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(split-K reduce)");
   }
   return KEEP_OK;
+}
+
+extern "C" int32_t keep_conv2d(const keep_conv2d_args* a_in, void* stream) { return conv_launch(a_in, stream, nullptr); }
+
+extern "C" int32_t keep_conv2d_launch_plan(const keep_conv2d_args* a_in, keep_conv2d_launch_plan_out* out) {
+  KEEP_REQUIRE(out != nullptr, "keep_conv2d_launch_plan: null output");
+  memset(out, 0, sizeof(*out));
+  ConvTrace tr = {out->kernels, (int)sizeof(out->kernels), 0, 0, false};
+  const int rc = conv_launch(a_in, nullptr, &tr);
+  if (rc == KEEP_OK && tr.overflow) {
+    memset(out, 0, sizeof(*out));
+    keep_set_error("keep_conv2d_launch_plan: the kernel names do not fit keep_conv2d_launch_plan_out.kernels");
+    return KEEP_EINVAL;
+  }
+  if (rc != KEEP_OK) memset(out, 0, sizeof(*out));
+  else out->n_kernels = tr.count;
+  return rc;
 }

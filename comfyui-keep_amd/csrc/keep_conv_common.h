@@ -390,20 +390,53 @@ int keep_gemm_x3l_waves(const keep_conv2d_args* a);
 bool keep_conv_x3p_ok(const keep_conv2d_args* a, const ConvP& p, int split_k);
 bool keep_conv_x3q_ok(const keep_conv2d_args* a, const ConvP& p, int split_k);
 bool keep_conv_x3p_full_ok(const keep_conv2d_args* a, const ConvP& p, int split_k);
-// launchers
-int keep_conv2d_x3_c3(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
-int keep_conv2d_x3_halo(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st);
-int keep_conv2d_x3_stream(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st);
-int keep_conv2d_x3_up2_stream(const keep_conv2d_args* a, ConvP& p, bool x1, hipStream_t st);
-int keep_conv2d_x3_partials(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
-int keep_conv2d_x3_small_full(const keep_conv2d_args* a, ConvP& p, hipStream_t st);
-int keep_conv2d_x3_gather(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st);
-int keep_conv2d_x3_gemm_lat(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st);
-void keep_conv_stats_replica(const ConvP& p, int n_img, hipStream_t st);
+struct ConvTrace;
+// launchers (`tr`: NULL launches; a trace names what would be launched -- "launch or name" below)
+int keep_conv2d_x3_c3(const keep_conv2d_args* a, ConvP& p, hipStream_t st, ConvTrace* tr);
+int keep_conv2d_x3_halo(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st, ConvTrace* tr);
+int keep_conv2d_x3_stream(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st, ConvTrace* tr);
+int keep_conv2d_x3_up2_stream(const keep_conv2d_args* a, ConvP& p, bool x1, hipStream_t st, ConvTrace* tr);
+int keep_conv2d_x3_partials(const keep_conv2d_args* a, ConvP& p, hipStream_t st, ConvTrace* tr);
+int keep_conv2d_x3_small_full(const keep_conv2d_args* a, ConvP& p, hipStream_t st, ConvTrace* tr);
+int keep_conv2d_x3_gather(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st, ConvTrace* tr);
+int keep_conv2d_x3_gemm_lat(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st, ConvTrace* tr);
+void keep_conv_stats_replica(const ConvP& p, int n_img, hipStream_t st, ConvTrace* tr);
 
 // persistent kernels: two blocks per CU walk the items with a grid stride
 static inline int persistent_grid(int n_items, int n_cu) { return n_items < 2 * n_cu ? n_items : 2 * n_cu; }
 
+// ------------------------------------------------------------------------------------------------ launch or name (host)
+// keep_conv2d_launch_plan (keep_cv_hip.h) answers "what would this call launch?" by walking the launch itself: keep_conv2d and the plan
+// query run the SAME dispatch code, and every launch site goes through KEEP_CONV_LAUNCH below, which with a ConvTrace appends the
+// instantiation's name instead of launching it.  A decision of a launcher is therefore read once, at one place, by the launch and by the
+// name; nothing restates it.  The name is the device symbol the compiler gives the very template-id the launch names, demangled: what a
+// profiler prints, without the return type and the parameter list.  With a trace nothing touches the device: no launch, no launch check,
+// no query of the CU count (which sizes grids and selects nothing).
+struct ConvTrace {
+  char* buf;      // " + "-joined names in launch order
+  int cap, len, count;
+  bool overflow;
+};
+void keep_conv_trace_add(ConvTrace* tr, const char* mangled);
+static inline int conv_num_cu(const ConvTrace* tr) { return tr ? 256 : keep_num_cu(); }
+
+#define KEEP_CONV_ARGS(...) __VA_ARGS__
+// KEEP_CONV_LAUNCH(trace, grid, block, stream, (kernel arguments), kernel template-id): all conv kernels take static LDS only
+#define KEEP_CONV_LAUNCH(TR, GRID, BLOCK, ST, ARGS, ...)                                      \
+  do {                                                                                        \
+    if (TR)                                                                                   \
+      keep_conv_trace_add(TR, __builtin_get_device_side_mangled_name(__VA_ARGS__));           \
+    else                                                                                      \
+      hipLaunchKernelGGL((__VA_ARGS__), GRID, BLOCK, 0, ST, KEEP_CONV_ARGS ARGS);             \
+  } while (0)
+#define KEEP_CONV_LAUNCH_CHECK(TR, NAME)   \
+  do {                                     \
+    if (!(TR)) KEEP_LAUNCH_CHECK(NAME);    \
+  } while (0)
+
+// A convolution has a name at two levels.  FAMILY: the string below, what keep_conv2d_plan reports -- the form's name, stable under everything
+// a launcher decides later.  LAUNCHED INSTANTIATION: what keep_conv2d_launch_plan reports -- the template-id the launch takes for the real N,
+// the flags, the chunk count and the activations, written by the launch sites themselves ("launch or name" above).
 // The kernel a plan reports (keep_conv2d_plan_out.kernel, as rocprofv3 prints the instantiation), keyed by path and form.  FORM_X3_HALO
 // reports the 256-pixel kernel of the plan also where the launch takes the 64-pixel blocks for the real N.  The streaming kernel is named by
 // its prologue form alone: with an epilogue activation the launch is conv3x3_halo_x3s_act_kernel<PRO, AFF, X1, EACT> (the same body), and

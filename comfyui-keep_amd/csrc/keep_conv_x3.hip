@@ -1313,11 +1313,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c3_x3_kernel(ConvP p, int tile
   }
 }
 
-int keep_conv2d_x3_c3(const keep_conv2d_args* a, ConvP& p, hipStream_t st) {
+int keep_conv2d_x3_c3(const keep_conv2d_args* a, ConvP& p, hipStream_t st, ConvTrace* tr) {
   const int tx = a->Wo / 32, ty = a->Ho / 8, ncb = (a->Cout + 63) / 64;
   const int n_items = a->N * tx * ty * ncb;
-  hipLaunchKernelGGL(conv3x3_c3_x3_kernel, dim3(persistent_grid(n_items, keep_num_cu())), dim3(256), 0, st, p, tx, ty, ncb, n_items);
-  KEEP_LAUNCH_CHECK("keep_conv2d(Cin<=3, x3)");
+  KEEP_CONV_LAUNCH(tr, dim3(persistent_grid(n_items, conv_num_cu(tr))), dim3(256), st, (p, tx, ty, ncb, n_items), conv3x3_c3_x3_kernel);
+  KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(Cin<=3, x3)");
   return KEEP_OK;
 }
 
@@ -1392,36 +1392,36 @@ static HaloRun x3_halo_run(const keep_conv2d_args* a, const ConvP& p, const Conv
   return RUN_HALO;
 }
 
-int keep_conv2d_x3_halo(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st) {
-  const int n_cu = keep_num_cu();
+int keep_conv2d_x3_halo(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st, ConvTrace* tr) {
+  const int n_cu = conv_num_cu(tr);
   dim3 block(256);
-  if (pl.form == FORM_X1_STREAM) return keep_conv2d_x3_stream(a, p, pl, st);      // keep_conv_x3s.hip
+  if (pl.form == FORM_X1_STREAM) return keep_conv2d_x3_stream(a, p, pl, st, tr);      // keep_conv_x3s.hip
   if (pl.form == FORM_HALO_UP2) {      // four 2x2-tap phase convolutions on the source grid (kernel comment: UP2)
-    if (pl.stream) return keep_conv2d_x3_up2_stream(a, p, false, st);      // keep_conv_x3s.hip: the same values, two phases per staged halo
+    if (pl.stream) return keep_conv2d_x3_up2_stream(a, p, false, st, tr);      // keep_conv_x3s.hip: the same values, two phases per staged halo
     const int tx = a->W / 32, ty = a->H / 8, ncbv = 4 * (a->Cout / 64);
     const int n_items = a->N * tx * ty * ncbv;
     p.upsample = 0;                                    // the kernel addresses the source like a plain 3x3 convolution
     dim3 grid(persistent_grid(n_items, n_cu));
-    hipLaunchKernelGGL((conv3x3_halo_x3_kernel<32, KEEP_PRO_NONE, true, true, true, true>), grid, block, 0, st, p, tx, ty, ncbv, n_items);
-    KEEP_LAUNCH_CHECK("keep_conv2d(halo x3, x2 phases)");
+    KEEP_CONV_LAUNCH(tr, grid, block, st, (p, tx, ty, ncbv, n_items), conv3x3_halo_x3_kernel<32, KEEP_PRO_NONE, true, true, true, true>);
+    KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(halo x3, x2 phases)");
     return KEEP_OK;
   }
-  if (pl.form == FORM_X1_UP2) return keep_conv2d_x3_up2_stream(a, p, true, st);      // the hi-only phase twin on the same pipeline
+  if (pl.form == FORM_X1_UP2) return keep_conv2d_x3_up2_stream(a, p, true, st, tr);      // the hi-only phase twin on the same pipeline
   if (pl.form == FORM_X1_HALO16) {      // 16 x 16 tiles, raw input, zero padding, un-split
     const int tiles_x = a->Wo / 16, tiles_y = a->Ho / 16, ncb = (a->Cout + 63) / 64;
     const int n_items = a->N * tiles_x * tiles_y * ncb;
     dim3 grid(persistent_grid(n_items, n_cu));
     if (pl.simple_epi)
-      hipLaunchKernelGGL((conv3x3_halo_x3_kernel<16, KEEP_PRO_NONE, true, true, true, false, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
+      KEEP_CONV_LAUNCH(tr, grid, block, st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_halo_x3_kernel<16, KEEP_PRO_NONE, true, true, true, false, true>);
     else
-      hipLaunchKernelGGL((conv3x3_halo_x3_kernel<16, KEEP_PRO_NONE, false, true, true, false, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
-    KEEP_LAUNCH_CHECK("keep_conv2d(halo x1, 16 x 16 tiles)");
+      KEEP_CONV_LAUNCH(tr, grid, block, st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_halo_x3_kernel<16, KEEP_PRO_NONE, false, true, true, false, true>);
+    KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(halo x1, 16 x 16 tiles)");
     return KEEP_OK;
   }
   switch (x3_halo_run(a, p, pl)) {      // FORM_X3_HALO
-    case RUN_SMALL_PARTIALS: return keep_conv2d_x3_partials(a, p, st);      // keep_conv_x3p.hip
-    case RUN_SMALL_FULL: return keep_conv2d_x3_small_full(a, p, st);
-    case RUN_STREAM: return keep_conv2d_x3_stream(a, p, pl, st);      // keep_conv_x3s.hip
+    case RUN_SMALL_PARTIALS: return keep_conv2d_x3_partials(a, p, st, tr);      // keep_conv_x3p.hip
+    case RUN_SMALL_FULL: return keep_conv2d_x3_small_full(a, p, st, tr);
+    case RUN_STREAM: return keep_conv2d_x3_stream(a, p, pl, st, tr);      // keep_conv_x3s.hip
     case RUN_HALO: break;
   }
   const bool wide = pl.wide;
@@ -1433,15 +1433,15 @@ int keep_conv2d_x3_halo(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl,
   // weights by LDS-DMA; the exact-activation form below keeps the VGPR-staged weights
 #define KEEP_LAUNCH_HX2(TWV, PROV)                                                                                          \
   if (simple)                                                                                                              \
-    hipLaunchKernelGGL((conv3x3_halo_x3_kernel<TWV, PROV, true, true, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);  \
+    KEEP_CONV_LAUNCH(tr, grid, block, st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_halo_x3_kernel<TWV, PROV, true, true, true>);  \
   else                                                                                                                     \
-    hipLaunchKernelGGL((conv3x3_halo_x3_kernel<TWV, PROV, false, true, true>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);
+    KEEP_CONV_LAUNCH(tr, grid, block, st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_halo_x3_kernel<TWV, PROV, false, true, true>);
 #define KEEP_LAUNCH_HX(TWV)                                       \
   if (a->pro_act == KEEP_PRO_SWISH && !p.fast) {                  \
     if (simple)                                                   \
-      hipLaunchKernelGGL((conv3x3_halo_x3_kernel<TWV, KEEP_PRO_SWISH, true, false>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items);  \
+      KEEP_CONV_LAUNCH(tr, grid, block, st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_halo_x3_kernel<TWV, KEEP_PRO_SWISH, true, false>);  \
     else                                                          \
-      hipLaunchKernelGGL((conv3x3_halo_x3_kernel<TWV, KEEP_PRO_SWISH, false, false>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items); \
+      KEEP_CONV_LAUNCH(tr, grid, block, st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_halo_x3_kernel<TWV, KEEP_PRO_SWISH, false, false>); \
   } else if (a->pro_act == KEEP_PRO_SWISH) {                      \
     KEEP_LAUNCH_HX2(TWV, KEEP_PRO_SWISH)                          \
   } else if (a->pro_act == KEEP_PRO_RELU) {                       \
@@ -1456,7 +1456,7 @@ int keep_conv2d_x3_halo(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl,
   }
 #undef KEEP_LAUNCH_HX
 #undef KEEP_LAUNCH_HX2
-  KEEP_LAUNCH_CHECK("keep_conv2d(halo x3)");
+  KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(halo x3)");
   return KEEP_OK;
 }
 
@@ -1519,7 +1519,7 @@ __global__ __launch_bounds__(256) void conv_x3_gather_stats_replica_kernel(ConvP
 
 static constexpr long KEEP_GATHER_SMALL_ROWS = 4096;      // rows in flight up to which a launch planned for the 128 x 128 tile runs the 64 x 64 tile
 // The plan's form picks the kernel variant; its tile follows the reference batch because the statistics partition does.
-int keep_conv2d_x3_gather(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st) {
+int keep_conv2d_x3_gather(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st, ConvTrace* tr) {
   const long M = p.M;
   const bool ln = pl.form == FORM_GEMM_LN, x1 = pl.form == FORM_X1_IM2COL || pl.form == FORM_X1_GEMM;
   // a launch WITHOUT statistics may take the small tile when the real row count is small (one clip in flight: 4 x the blocks) -- the K
@@ -1541,25 +1541,25 @@ int keep_conv2d_x3_gather(const keep_conv2d_args* a, ConvP& p, const ConvPlan& p
   const bool one = pl.gemm;
 #define KEEP_LAUNCH_GX(A, B, C, D)                                                                 \
   if (x1 && one)                                                                                   \
-    hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, true, true, false, true, false, true>), grid, block, 0, st, p); \
+    KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_x3_kernel<A, B, C, D, true, true, false, true, false, true>); \
   else if (x1)                                                                                     \
-    hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, true, false, false, true, false, true>), grid, block, 0, st, p); \
+    KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_x3_kernel<A, B, C, D, true, false, false, true, false, true>); \
   else if (p.kslice_steps == 4 && plain && C * D == 1 && steps % 4 == 0)                                \
-    hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, true, true, true, true, C * D == 1>), grid, block, 0, st, p); \
+    KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_x3_kernel<A, B, C, D, true, true, true, true, C * D == 1>); \
   else if (p.kslice_steps > 0 && plain)                                                            \
-    hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, true, true, true>), grid, block, 0, st, p);     \
+    KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_x3_kernel<A, B, C, D, true, true, true>);     \
   else if (p.kslice_steps > 0)                                                                     \
-    hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, false, true, true>), grid, block, 0, st, p);    \
+    KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_x3_kernel<A, B, C, D, false, true, true>);    \
   else if (plain && one)                                                                           \
-    hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, true, true>), grid, block, 0, st, p);           \
+    KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_x3_kernel<A, B, C, D, true, true>);           \
   else if (plain && C * D == 1 && M > 262144)                                                      \
-    hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, true, false, false, false>), grid, block, 0, st, p); \
+    KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_x3_kernel<A, B, C, D, true, false, false, false>); \
   else if (plain)                                                                                  \
-    hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, true, false>), grid, block, 0, st, p);          \
+    KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_x3_kernel<A, B, C, D, true, false>);          \
   else if (one)                                                                                    \
-    hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, false, true>), grid, block, 0, st, p);          \
+    KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_x3_kernel<A, B, C, D, false, true>);          \
   else                                                                                             \
-    hipLaunchKernelGGL((conv_x3_kernel<A, B, C, D, false, false>), grid, block, 0, st, p);
+    KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_x3_kernel<A, B, C, D, false, false>);
   // several column blocks and many row blocks: row-block-major order on a 1-D grid
   const int bt = big_tile ? 128 : 64;
   const long gx = cdiv(M, bt), gy = cdiv(a->Cout, bt);
@@ -1567,18 +1567,18 @@ int keep_conv2d_x3_gather(const keep_conv2d_args* a, ConvP& p, const ConvPlan& p
   p.tile_cols = rowmajor ? (int)gy : 0;
   dim3 grid(rowmajor ? (unsigned)(gx * gy) : (unsigned)gx, rowmajor ? 1u : (unsigned)gy, p.split_k);
   if (ln) {
-    hipLaunchKernelGGL((conv_x3_kernel<4, 1, 1, 4, true, true>), grid, block, 0, st, p);
+    KEEP_CONV_LAUNCH(tr, grid, block, st, (p), conv_x3_kernel<4, 1, 1, 4, true, true>);
   } else if (!big_tile) {
     KEEP_LAUNCH_GX(2, 2, 1, 1)
   } else {
     KEEP_LAUNCH_GX(2, 2, 2, 2)
   }
 #undef KEEP_LAUNCH_GX
-  KEEP_LAUNCH_CHECK("keep_conv2d(gather x3)");
+  KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(gather x3)");
   if (replica_stats) {
     p.stats = replica_stats;
-    hipLaunchKernelGGL(conv_x3_gather_stats_replica_kernel, dim3((unsigned)(M / 128), (unsigned)cdiv(a->Cout, 128)), dim3(256), 0, st, p);
-    KEEP_LAUNCH_CHECK("keep_conv2d(gather x3, statistics replica)");
+    KEEP_CONV_LAUNCH(tr, dim3((unsigned)(M / 128), (unsigned)cdiv(a->Cout, 128)), dim3(256), st, (p), conv_x3_gather_stats_replica_kernel);
+    KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(gather x3, statistics replica)");
   }
   return KEEP_OK;
 }

@@ -738,7 +738,7 @@ bool keep_conv_x3p_full_ok(const keep_conv2d_args* a, const ConvP& p, int split_
          (a->pro_act == KEEP_PRO_NONE || (a->pro_act == KEEP_PRO_SWISH && p.fast)) && !(a->flags & KEEP_CONV_NO_SMALL_PARTIALS);
 }
 
-int keep_conv2d_x3_partials(const keep_conv2d_args* a, ConvP& p, hipStream_t st) {
+int keep_conv2d_x3_partials(const keep_conv2d_args* a, ConvP& p, hipStream_t st, ConvTrace* tr) {
   const int tiles_x = a->Wo / 16, tiles_y = a->Ho / 4, ncb = a->Cout / 64;
   const int n_items = a->N * tiles_x * tiles_y * ncb * p.split_k;
   const bool sc = a->pro_scale != nullptr;
@@ -746,18 +746,18 @@ int keep_conv2d_x3_partials(const keep_conv2d_args* a, ConvP& p, hipStream_t st)
   const int nch = (nchunks % p.split_k == 0 && (per == 4 || per == 8 || per == 16)) ? per : 0;      // every z walks `per` chunks
 #define KEEP_LAUNCH_XP(PROV, SCV)                                                                                                     \
   {                                                                                                                                   \
-    if (nch == 4) hipLaunchKernelGGL((conv3x3_x3p_kernel<PROV, SCV, 4>), dim3(n_items), dim3(256), 0, st, p, tiles_x, tiles_y, ncb, n_items);        \
-    else if (nch == 8) hipLaunchKernelGGL((conv3x3_x3p_kernel<PROV, SCV, 8>), dim3(n_items), dim3(256), 0, st, p, tiles_x, tiles_y, ncb, n_items);   \
-    else if (nch == 16) hipLaunchKernelGGL((conv3x3_x3p_kernel<PROV, SCV, 16>), dim3(n_items), dim3(256), 0, st, p, tiles_x, tiles_y, ncb, n_items); \
-    else hipLaunchKernelGGL((conv3x3_x3p_kernel<PROV, SCV, 0>), dim3(n_items), dim3(256), 0, st, p, tiles_x, tiles_y, ncb, n_items);                 \
+    if (nch == 4) KEEP_CONV_LAUNCH(tr, dim3(n_items), dim3(256), st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_x3p_kernel<PROV, SCV, 4>);        \
+    else if (nch == 8) KEEP_CONV_LAUNCH(tr, dim3(n_items), dim3(256), st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_x3p_kernel<PROV, SCV, 8>);   \
+    else if (nch == 16) KEEP_CONV_LAUNCH(tr, dim3(n_items), dim3(256), st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_x3p_kernel<PROV, SCV, 16>); \
+    else KEEP_CONV_LAUNCH(tr, dim3(n_items), dim3(256), st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_x3p_kernel<PROV, SCV, 0>);                 \
   }
   if (a->pro_act == KEEP_PRO_SWISH && sc) KEEP_LAUNCH_XP(KEEP_PRO_SWISH, true)
   else if (a->pro_act == KEEP_PRO_SWISH) KEEP_LAUNCH_XP(KEEP_PRO_SWISH, false)
   else if (sc) KEEP_LAUNCH_XP(KEEP_PRO_NONE, true)
   else KEEP_LAUNCH_XP(KEEP_PRO_NONE, false)
 #undef KEEP_LAUNCH_XP
-  KEEP_LAUNCH_CHECK("keep_conv2d(halo x3, small-tile partials)");
-  if (p.split_k == 1 && p.stats) keep_conv_stats_replica(p, a->N, st);      // (the full-epilogue form: keep_conv_x3p_full_ok)
+  KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(halo x3, small-tile partials)");
+  if (p.split_k == 1 && p.stats) keep_conv_stats_replica(p, a->N, st, tr);      // (the full-epilogue form: keep_conv_x3p_full_ok)
   return KEEP_OK;
 }
 
@@ -774,7 +774,7 @@ bool keep_conv_x3q_ok(const keep_conv2d_args* a, const ConvP& p, int split_k) {
          !(a->flags & (KEEP_CONV_NO_SMALL_PARTIALS | KEEP_CONV_NO_STREAM));
 }
 
-int keep_conv2d_x3_small_full(const keep_conv2d_args* a, ConvP& p, hipStream_t st) {
+int keep_conv2d_x3_small_full(const keep_conv2d_args* a, ConvP& p, hipStream_t st, ConvTrace* tr) {
   const int tiles_x = a->Wo / 16, tiles_y = a->Ho / 4, ncb = a->Cout / 64;
   const int n_items = a->N * tiles_x * tiles_y * ncb;
   const bool aff = a->pro_scale != nullptr;
@@ -782,17 +782,17 @@ int keep_conv2d_x3_small_full(const keep_conv2d_args* a, ConvP& p, hipStream_t s
   const int nch = (nchunks == 4 || nchunks == 8 || nchunks == 16 || nchunks == 32) ? nchunks : 0;
 #define KEEP_LAUNCH_XQ(PROV, AFFV)                                                                                                    \
   {                                                                                                                                   \
-    if (nch == 4) hipLaunchKernelGGL((conv3x3_x3q_kernel<PROV, AFFV, 4>), dim3(n_items), dim3(256), 0, st, p, tiles_x, tiles_y, ncb, n_items);        \
-    else if (nch == 8) hipLaunchKernelGGL((conv3x3_x3q_kernel<PROV, AFFV, 8>), dim3(n_items), dim3(256), 0, st, p, tiles_x, tiles_y, ncb, n_items);   \
-    else if (nch == 16) hipLaunchKernelGGL((conv3x3_x3q_kernel<PROV, AFFV, 16>), dim3(n_items), dim3(256), 0, st, p, tiles_x, tiles_y, ncb, n_items); \
-    else if (nch == 32) hipLaunchKernelGGL((conv3x3_x3q_kernel<PROV, AFFV, 32>), dim3(n_items), dim3(256), 0, st, p, tiles_x, tiles_y, ncb, n_items); \
-    else hipLaunchKernelGGL((conv3x3_x3q_kernel<PROV, AFFV, 0>), dim3(n_items), dim3(256), 0, st, p, tiles_x, tiles_y, ncb, n_items);                 \
+    if (nch == 4) KEEP_CONV_LAUNCH(tr, dim3(n_items), dim3(256), st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_x3q_kernel<PROV, AFFV, 4>);        \
+    else if (nch == 8) KEEP_CONV_LAUNCH(tr, dim3(n_items), dim3(256), st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_x3q_kernel<PROV, AFFV, 8>);   \
+    else if (nch == 16) KEEP_CONV_LAUNCH(tr, dim3(n_items), dim3(256), st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_x3q_kernel<PROV, AFFV, 16>); \
+    else if (nch == 32) KEEP_CONV_LAUNCH(tr, dim3(n_items), dim3(256), st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_x3q_kernel<PROV, AFFV, 32>); \
+    else KEEP_CONV_LAUNCH(tr, dim3(n_items), dim3(256), st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_x3q_kernel<PROV, AFFV, 0>);                 \
   }
   if (a->pro_act == KEEP_PRO_SWISH) KEEP_LAUNCH_XQ(KEEP_PRO_SWISH, true)
   else if (aff) KEEP_LAUNCH_XQ(KEEP_PRO_NONE, true)
   else KEEP_LAUNCH_XQ(KEEP_PRO_NONE, false)
 #undef KEEP_LAUNCH_XQ
-  KEEP_LAUNCH_CHECK("keep_conv2d(halo x3, small tiles)");
-  if (p.stats) keep_conv_stats_replica(p, a->N, st);
+  KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(halo x3, small tiles)");
+  if (p.stats) keep_conv_stats_replica(p, a->N, st, tr);
   return KEEP_OK;
 }

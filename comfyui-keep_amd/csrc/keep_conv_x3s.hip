@@ -768,9 +768,9 @@ __global__ __launch_bounds__(256) void conv_stats_replica_kernel(ConvP p, int ti
   }
 }
 
-void keep_conv_stats_replica(const ConvP& p, int n_img, hipStream_t st) {
+void keep_conv_stats_replica(const ConvP& p, int n_img, hipStream_t st, ConvTrace* tr) {
   const int tiles_x = p.Wo / 32, tiles_y = p.Ho / 8, ncb = (p.Cout + 63) / 64;
-  hipLaunchKernelGGL(conv_stats_replica_kernel, dim3(n_img * tiles_x * tiles_y * ncb), dim3(256), 0, st, p, tiles_x, tiles_y, ncb);
+  KEEP_CONV_LAUNCH(tr, dim3(n_img * tiles_x * tiles_y * ncb), dim3(256), st, (p, tiles_x, tiles_y, ncb), conv_stats_replica_kernel);
 }
 
 // ------------------------------------------------------------------------------------------------ dispatch
@@ -809,30 +809,30 @@ bool keep_conv_x1_up2_ok(const keep_conv2d_args* a) {
   return keep_conv_x3_up2_ok(a) && keep_conv_x3_up2_stream_ok(a) && a->Cin % 32 == 0 && !a->in2 && !a->ln_gamma;
 }
 
-int keep_conv2d_x3_up2_stream(const keep_conv2d_args* a, ConvP& p, bool x1, hipStream_t st) {
+int keep_conv2d_x3_up2_stream(const keep_conv2d_args* a, ConvP& p, bool x1, hipStream_t st, ConvTrace* tr) {
   const int tiles_x = a->W / 32, tiles_y = a->H / 8, ncb = a->Cout / 64;
   const int n_items = a->N * tiles_x * tiles_y * 2 * ncb;      // (source tile, row parity, cout block)
   p.upsample = 0;                                              // the kernel addresses the source like a plain 3x3 convolution
-  const dim3 grid(persistent_grid(n_items, keep_num_cu()));
+  const dim3 grid(persistent_grid(n_items, conv_num_cu(tr)));
   if (x1)      // FORM_X1_UP2: the hi-only phase twin (keep_conv_x1_up2_ok: Cin % 32 == 0)
-    hipLaunchKernelGGL(conv3x3_up2_x1s_kernel, grid, dim3(256), 0, st, p, tiles_x, tiles_y, ncb, n_items);
+    KEEP_CONV_LAUNCH(tr, grid, dim3(256), st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_up2_x1s_kernel);
   else
-    hipLaunchKernelGGL(conv3x3_up2_x3s_kernel, grid, dim3(256), 0, st, p, tiles_x, tiles_y, ncb, n_items);
+    KEEP_CONV_LAUNCH(tr, grid, dim3(256), st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_up2_x3s_kernel);
   if (x1) {
-    KEEP_LAUNCH_CHECK("keep_conv2d(halo x1, x2 phases, streaming)");
+    KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(halo x1, x2 phases, streaming)");
   } else {
-    KEEP_LAUNCH_CHECK("keep_conv2d(halo x3, x2 phases, streaming)");
+    KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(halo x3, x2 phases, streaming)");
   }
   return KEEP_OK;
 }
 
 // one prologue form with the call's epilogue activation; false: an activation this kernel has no instantiation for
 template <int PRO, bool AFF, bool X1>
-static bool x3s_launch(int epi_act, dim3 grid, dim3 block, hipStream_t st, const ConvP& p, int tiles_x, int tiles_y, int ncb, int n_items) {
+static bool x3s_launch(int epi_act, dim3 grid, dim3 block, hipStream_t st, ConvTrace* tr, const ConvP& p, int tiles_x, int tiles_y, int ncb, int n_items) {
 #define X3S_ACT(A) \
-  case A: hipLaunchKernelGGL((conv3x3_halo_x3s_act_kernel<PRO, AFF, X1, A>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items); return true;
+  case A: KEEP_CONV_LAUNCH(tr, grid, block, st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_halo_x3s_act_kernel<PRO, AFF, X1, A>); return true;
   switch (epi_act) {
-    case KEEP_ACT_NONE: hipLaunchKernelGGL((conv3x3_halo_x3s_kernel<PRO, AFF, X1>), grid, block, 0, st, p, tiles_x, tiles_y, ncb, n_items); return true;
+    case KEEP_ACT_NONE: KEEP_CONV_LAUNCH(tr, grid, block, st, (p, tiles_x, tiles_y, ncb, n_items), conv3x3_halo_x3s_kernel<PRO, AFF, X1>); return true;
     X3S_ACT(KEEP_ACT_RELU)
     X3S_ACT(KEEP_ACT_LRELU02)
     X3S_ACT(KEEP_ACT_GELU)
@@ -844,16 +844,16 @@ static bool x3s_launch(int epi_act, dim3 grid, dim3 block, hipStream_t st, const
 #undef X3S_ACT
 }
 
-int keep_conv2d_x3_stream(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st) {
+int keep_conv2d_x3_stream(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st, ConvTrace* tr) {
   const int tiles_x = a->Wo / 32, tiles_y = a->Ho / 8, ncb = (a->Cout + 63) / 64;
   const int n_items = a->N * tiles_x * tiles_y * ncb;
-  dim3 grid(persistent_grid(n_items, keep_num_cu())), block(256);
+  dim3 grid(persistent_grid(n_items, conv_num_cu(tr))), block(256);
   const bool aff = a->pro_scale != nullptr;
   const bool x1 = pl.form == FORM_X1_STREAM;      // (keep_conv_x1_stream_ok: Cin % 32 == 0, the prologue forms of the x3 instantiations)
   bool ok;
 #define X3S_FORM(PRO, AFF) \
-  (x1 ? x3s_launch<PRO, AFF, true>(a->epi_act, grid, block, st, p, tiles_x, tiles_y, ncb, n_items) \
-      : x3s_launch<PRO, AFF, false>(a->epi_act, grid, block, st, p, tiles_x, tiles_y, ncb, n_items))
+  (x1 ? x3s_launch<PRO, AFF, true>(a->epi_act, grid, block, st, tr, p, tiles_x, tiles_y, ncb, n_items) \
+      : x3s_launch<PRO, AFF, false>(a->epi_act, grid, block, st, tr, p, tiles_x, tiles_y, ncb, n_items))
   if (a->pro_act == KEEP_PRO_SWISH)
     ok = X3S_FORM(KEEP_PRO_SWISH, true);
   else if (a->pro_act == KEEP_PRO_RELU)
@@ -864,6 +864,6 @@ int keep_conv2d_x3_stream(const keep_conv2d_args* a, ConvP& p, const ConvPlan& p
     ok = X3S_FORM(KEEP_PRO_NONE, false);
 #undef X3S_FORM
   if (!ok) return KEEP_EUNSUP;      // (an epilogue activation without an instantiation: never launch a kernel that would drop it)
-  KEEP_LAUNCH_CHECK("keep_conv2d(halo x3, streaming)");
+  KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(halo x3, streaming)");
   return KEEP_OK;
 }

@@ -234,7 +234,7 @@ int keep_gemm_x3l_waves(const keep_conv2d_args* a) { return a->Cin >= 1024 ? 8 :
 // The sums are defined by the K slicing; WHICH kernel evaluates them follows the real row count (bit-neutral): the latency form while
 // its 32 x 32 tiles leave CUs idle, conv_x3_kernel with canonical slices (p.kslice_steps: 64 x 64 or 128 x 128 block tiles, operands
 // staged through LDS -- 4 x less L2 -> CU traffic per FLOP) beyond.
-int keep_conv2d_x3_gemm_lat(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st) {
+int keep_conv2d_x3_gemm_lat(const keep_conv2d_args* a, ConvP& p, const ConvPlan& pl, hipStream_t st, ConvTrace* tr) {
   const long M = p.M;
   const bool plain = pl.plain;
   const int nw = keep_gemm_x3l_waves(a);
@@ -245,22 +245,22 @@ int keep_conv2d_x3_gemm_lat(const keep_conv2d_args* a, ConvP& p, const ConvPlan&
     ConvPlan tiles = pl;      // 64 x 64 tiles at every row count: the slice totals of a 128 x 128 tile leave one block per CU
     tiles.form = FORM_X3_GATHER;
     tiles.tile = 1;
-    return keep_conv2d_x3_gather(a, p, tiles, st);
+    return keep_conv2d_x3_gather(a, p, tiles, st, tr);
   }
   const int gm = cdiv(M, 32), gn = a->Cout / 32;
   const int m_fast = (long)M > (long)a->Cout ? 1 : 0;       // the faster index walks the LARGER operand: each XCD sees 1/8 of it
   dim3 grid(m_fast ? gm : gn, m_fast ? gn : gm);
 #define KEEP_LAUNCH_GL(NWV)                                                                                \
   if (!plain)                                                                                              \
-    hipLaunchKernelGGL((gemm_x3l_kernel<NWV, 1, false>), grid, dim3(NWV * 64), 0, st, p, m_fast);          \
+    KEEP_CONV_LAUNCH(tr, grid, dim3(NWV * 64), st, (p, m_fast), gemm_x3l_kernel<NWV, 1, false>);          \
   else                                                                                                     \
-    hipLaunchKernelGGL((gemm_x3l_kernel<NWV, 1, true>), grid, dim3(NWV * 64), 0, st, p, m_fast);
+    KEEP_CONV_LAUNCH(tr, grid, dim3(NWV * 64), st, (p, m_fast), gemm_x3l_kernel<NWV, 1, true>);
   if (nw == 8) {
     KEEP_LAUNCH_GL(8)
   } else {
     KEEP_LAUNCH_GL(4)
   }
 #undef KEEP_LAUNCH_GL
-  KEEP_LAUNCH_CHECK("keep_conv2d(gemm x3 latency form)");
+  KEEP_CONV_LAUNCH_CHECK(tr, "keep_conv2d(gemm x3 latency form)");
   return KEEP_OK;
 }

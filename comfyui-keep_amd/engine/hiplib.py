@@ -65,6 +65,11 @@ class AttnPlanOut(C.Structure):
                 ('kernel', C.c_char * 96)]
 
 
+class ConvLaunchPlanOut(C.Structure):
+    # include/keep_cv_hip.h:keep_conv2d_launch_plan_out
+    _fields_ = [('n_kernels', _i32), ('kernels', C.c_char * 508)]
+
+
 # name -> argtypes (restype is always int32 status); every symbol include/keep_hip.h declares
 _SIGNATURES = {
     'keep_conv2d': [C.POINTER(ConvArgs), _vp],
@@ -139,6 +144,7 @@ _CV_SIGNATURES = {
     'keep_warp_affine_batch_u8': [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp],
     'keep_warp_affine_batch_scatter_u8': [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp],
     'keep_attention_plan': [C.POINTER(AttnArgs), C.POINTER(AttnPlanOut)],  # (host-only: no stream argument)
+    'keep_conv2d_launch_plan': [C.POINTER(ConvArgs), C.POINTER(ConvLaunchPlanOut)],  # (host-only: no stream argument)
 }
 CV_EXPORTED_SYMBOLS = ['keep_cv_abi_version'] + list(_CV_SIGNATURES)
 
@@ -238,6 +244,16 @@ def conv2d_plan(a):
     out = ConvPlanOut()
     _check(lib.keep_conv2d_plan(C.byref(a), C.byref(out)), 'keep_conv2d_plan')
     return out
+
+
+def conv2d_launch_plan(a):
+    """keep_conv2d_launch_plan: the template instantiations keep_conv2d would launch for exactly these arguments, in launch order, joined
+    by " + " (keep_conv2d_plan names the form; this names what the launch takes for the real N, flags and activations); a refused call
+    raises KeepHipError with the library's code and reason.  Needs no device."""
+    lib = load(check_device=False)
+    out = ConvLaunchPlanOut()
+    _check(lib.keep_conv2d_launch_plan(C.byref(a), C.byref(out)), 'keep_conv2d_launch_plan')
+    return out.kernels.decode()
 
 
 def attention_workspace_bytes(a):

@@ -119,6 +119,26 @@ typedef struct {
 } keep_attention_plan_out;
 int32_t keep_attention_plan(const keep_attention_args* a, keep_attention_plan_out* out);
 
+/* ---- what one keep_conv2d call of keep_hip.h would launch: HOST-only C (no device, no stream; no pointer of `a` is dereferenced, they are
+ * tested for presence and alignment only, so aligned made-up addresses do).  It is the launch itself with the launches taken out: the
+ * arguments go through keep_conv2d's own code -- the struct_size check, validation, the plan (what keep_conv2d_plan reports), the tensor
+ * and workspace requirements of a launch, and every launch-time decision that follows from the real N, the flags, the chunk count and the
+ * activations -- and each place that would launch a kernel writes that kernel's name instead.  Returns what keep_conv2d would return for
+ * a refused call, with the same message; `out` is zeroed then.
+ *
+ *   n_kernels   kernels the call launches
+ *   kernels     their template instantiations as a profiler prints them (every template argument spelled out, without the return type
+ *               and the parameter list), in launch order, joined by " + ": zero_u32_kernel first when x3_out_amax is given and not
+ *               zeroed, then the convolution, then what follows it (a split-K reducer, a statistics replica kernel)
+ *
+ * keep_conv2d_plan names a call's FORM (engine policies key on that name); this names the INSTANTIATION the launch takes for it.  Tests
+ * use it to prove that their case tables reach every instantiation; it is no part of the product path. */
+typedef struct {
+  int32_t n_kernels;
+  char kernels[508];
+} keep_conv2d_launch_plan_out;
+int32_t keep_conv2d_launch_plan(const keep_conv2d_args* a, keep_conv2d_launch_plan_out* out);
+
 #ifdef __cplusplus
 }
 #endif

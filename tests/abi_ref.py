@@ -4,10 +4,13 @@ the CPU only: no GPU, no library.  tests/test_gpu_case_values.py feeds the judge
 doctored references (it must bite) and checks that every optional input of every case moves the reference by far more than the
 tolerance (a kernel that ignores an input cannot pass).
 
-Tolerances (chosen by the kernel family the plan names, not by the `mma` requested):
+Tolerances (chosen by the kernel instantiation the launch takes, not by the `mma` requested):
 
     exact-f32 kernels   err <= 2e-4 * scale                                   (TOL of the GPU modules)
     x3 kernels          err_x3 <= max(3 * err_f32, 2e-6 * scale), err_f32 <= 2e-4 * scale   (``yardstick``; err_f32: the exact-f32 twin)
+    x1 kernels          per output: err <= (2^-10 + 2e-6) * sum |x| |w|  (single fp16: both operands rounded once, relative 2^-11 each,
+                        the range scales are powers of two; x is what enters the product, behind the prologue; 2e-6: the x3 bound
+                        of the fp32 accumulation and epilogue -- tests/test_gpu_conv_x3s_schedule.py derives the same from the format)
     bf16 kernels        against the reference on bf16-rounded operands: 2e-5 * scale, 2e-3 * scale with a prologue activation
                         (a fast-exp swish moves a bf16 rounding of the activated input), 6e-3 * scale for attention (P is
                         rounded too); a bf16 OUTPUT adds one bf16 ulp at scale, 2^-8 * scale, against the unrounded reference
@@ -24,11 +27,12 @@ import keep_oracle as O
 
 TOL = 2e-4
 BF16_TOL, BF16_TOL_PRO_ACT, BF16_TOL_ATTN, BF16_ULP = 2e-5, 2e-3, 6e-3, 2.0 ** -8
+X1_TOL = 2.0 ** -10 + 2e-6   # per output, times sum |x| |w|
 SENSITIVITY = 100.0          # an optional input removed must move the reference by >= SENSITIVITY * tol * scale
 AUX_W, LN_EPS = 0.5, 1e-5    # the constants the table passes as keep_conv2d_args.aux_w / ln_eps
 
 # numeric values of include/keep_hip.h (engine/hiplib.py carries the same; tests/test_host_logic.py compares them)
-MMA_F32, MMA_BF16, MMA_X3 = 0, 1, 2
+MMA_F32, MMA_BF16, MMA_X3, MMA_X1 = 0, 1, 2, 3
 PRO_NONE, PRO_SWISH, PRO_RELU = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_LRELU02, ACT_GELU, ACT_SIGMOID, ACT_LRELU01, ACT_SILU = 0, 1, 2, 3, 4, 5, 6
 ATTN_NO_X3 = 4
@@ -63,7 +67,7 @@ def yardstick(what, e3, e32, sc, e3np=None):
 # every attribute a _Geom of the table can carry: the table's keys and the sizes _Geom derives from them
 GEOM_KEYS = {'mma', 'N', 'H', 'W', 'Cin', 'Cout', 'k', 'stride', 'pad', 'pad_t', 'pad_l', 'Ho', 'Wo', 'in_ld', 'in_off', 'out_ld', 'out_off',
              'res_ld', 'aux', 'pro', 'pro_act', 'act', 'split_k', 'stats', 'amax', 'in_amax', 'in2_cin1', 'reflect', 'upsample', 'in_bf16',
-             'out_bf16', 'bk256', 'ln', 'flags', 'launch', 'cin1', 'x3', 'pro_amp', 'bias_amp'}
+             'out_bf16', 'bk256', 'ln', 'flags', 'launch', 'cin1', 'x3', 'x1', 'amax_stale', 'pro_amp', 'bias_amp', 'w_amp', 'w_peak', 'w_floor', 'x_amp', 'act_after_res'}
 
 
 def _act_pro(x, kind):
@@ -92,40 +96,50 @@ def _act(x, kind):
     raise ValueError(f'epilogue activation {kind}')
 
 
-def conv2d_ref(g, t):
+def conv2d_ref(g, t, linear=None):
     """keep_conv2d of include/keep_hip.h in float64.  ``g``: a ``_Geom`` of the table; ``t``: name -> PAYLOAD tensor (x [N,H,W,cin1],
     w [Cout, k*k*Cin], bias, pro_scale / pro_shift [N,Cin], res / aux [N*Ho*Wo, Cout], x2, ln_gamma / ln_beta, wb); an absent
     optional tensor is the identity of its step.  Returns out [N*Ho*Wo, Cout], the per-(n, c) sum / sum of squares of it
-    (``stats_sum`` / ``stats_sumsq`` [N, Cout]), ``amax`` [N], and ``out_rounded`` (RNE bf16) for a bf16 output."""
+    (``stats_sum`` / ``stats_sumsq`` [N, Cout]), ``amax`` [N], ``absdot`` (sum |x| |w| of every output, x behind the prologue: what the x1
+    bound scales with) and ``out_rounded`` (RNE bf16) for a bf16 output.  ``g.act_after_res`` (no table case sets it): the activation
+    applied to conv + residual instead of before the residual -- a deliberately wrong variant for the sensitivity checks.
+    ``linear``: the ``linear`` entry of an earlier answer for the same inputs, prologue and padding (the convolution before the bias
+    and its sum |x| |w|), for a variant that differs behind it only."""
     unknown = set(vars(g)) - GEOM_KEYS
     if unknown:
         raise KeyError(f'conv2d_ref: geometry keys it does not know: {sorted(unknown)}')
     N, H, W, Cin, Cout, k = g.N, g.H, g.W, g.Cin, g.Cout, g.k
-    bf = g.mma == MMA_BF16
-    x = t['x'].to(torch.float64).reshape(N, H, W, g.cin1)
-    if g.in2_cin1:
-        x = torch.cat([x, t['x2'].to(torch.float64).reshape(N, H, W, Cin - g.cin1)], dim=-1)
-    if t.get('pro_scale') is not None:
-        x = x * t['pro_scale'].to(torch.float64).reshape(N, 1, 1, Cin)
-    if t.get('pro_shift') is not None:
-        x = x + t['pro_shift'].to(torch.float64).reshape(N, 1, 1, Cin)
-    x = _act_pro(x, g.pro_act)
-    w = (t['wb'] if bf and t.get('wb') is not None else t['w']).to(torch.float64).reshape(Cout, k, k, Cin)
-    if bf:                                     # operands RNE-rounded to bf16 when staged (a bf16 tensor is unchanged by it)
-        x, w = bf16r(x), bf16r(w)
-    x = x.permute(0, 3, 1, 2)
-    if g.upsample:                             # 1 and KEEP_UPSAMPLE_X2_PHASES: nearest x2
-        x = x.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
-    Hv, Wv = x.shape[2:]
-    if g.reflect:
-        assert g.pad_t == g.pad_l < min(Hv, Wv)
-        x = F.pad(x, (g.pad_l, g.pad_l, g.pad_t, g.pad_t), mode='reflect')
-    else:                                      # the caller's Ho / Wo decide how far the window runs: missing bottom / right taps are zeros
-        need_h, need_w = (g.Ho - 1) * g.stride + k, (g.Wo - 1) * g.stride + k
-        x = F.pad(x, (g.pad_l, max(0, need_w - Wv - g.pad_l), g.pad_t, max(0, need_h - Hv - g.pad_t)))
-    v = F.conv2d(x, w.permute(0, 3, 1, 2), None, stride=g.stride)[:, :, :g.Ho, :g.Wo]
-    assert v.shape[2:] == (g.Ho, g.Wo), (tuple(v.shape), g.Ho, g.Wo)
-    v = v.permute(0, 2, 3, 1).reshape(N * g.Ho * g.Wo, Cout)
+    if linear is None:
+        bf = g.mma == MMA_BF16
+        x = t['x'].to(torch.float64).reshape(N, H, W, g.cin1)
+        if g.in2_cin1:
+            x = torch.cat([x, t['x2'].to(torch.float64).reshape(N, H, W, Cin - g.cin1)], dim=-1)
+        if t.get('pro_scale') is not None:
+            x = x * t['pro_scale'].to(torch.float64).reshape(N, 1, 1, Cin)
+        if t.get('pro_shift') is not None:
+            x = x + t['pro_shift'].to(torch.float64).reshape(N, 1, 1, Cin)
+        x = _act_pro(x, g.pro_act)
+        w = (t['wb'] if bf and t.get('wb') is not None else t['w']).to(torch.float64).reshape(Cout, k, k, Cin)
+        if bf:                                     # operands RNE-rounded to bf16 when staged (a bf16 tensor is unchanged by it)
+            x, w = bf16r(x), bf16r(w)
+        x = x.permute(0, 3, 1, 2)
+        if g.upsample:                             # 1 and KEEP_UPSAMPLE_X2_PHASES: nearest x2
+            x = x.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3)
+        Hv, Wv = x.shape[2:]
+        if g.reflect:
+            assert g.pad_t == g.pad_l < min(Hv, Wv)
+            x = F.pad(x, (g.pad_l, g.pad_l, g.pad_t, g.pad_t), mode='reflect')
+        else:                                      # the caller's Ho / Wo decide how far the window runs: missing bottom / right taps are zeros
+            need_h, need_w = (g.Ho - 1) * g.stride + k, (g.Wo - 1) * g.stride + k
+            x = F.pad(x, (g.pad_l, max(0, need_w - Wv - g.pad_l), g.pad_t, max(0, need_h - Hv - g.pad_t)))
+        rows = lambda y: y[:, :, :g.Ho, :g.Wo].permute(0, 2, 3, 1).reshape(N * g.Ho * g.Wo, Cout)  # noqa: E731
+        v = F.conv2d(x, w.permute(0, 3, 1, 2), None, stride=g.stride)
+        assert v.shape[2] >= g.Ho and v.shape[3] >= g.Wo, (tuple(v.shape), g.Ho, g.Wo)
+        v = rows(v)
+        absdot = rows(F.conv2d(x.abs(), w.abs().permute(0, 3, 1, 2), None, stride=g.stride))
+    else:
+        v, absdot = linear
+    linear = (v, absdot)
     if t.get('bias') is not None:
         v = v + t['bias'].to(torch.float64).reshape(1, Cout)
     if g.ln:                                   # biased variance, before the residual
@@ -135,9 +149,13 @@ def conv2d_ref(g, t):
             v = v * t['ln_gamma'].to(torch.float64).reshape(1, Cout)
         if t.get('ln_beta') is not None:
             v = v + t['ln_beta'].to(torch.float64).reshape(1, Cout)
-    a = _act(v, g.act)
+    after = getattr(g, 'act_after_res', False)
+    a = v if after else _act(v, g.act)
     r = t['res'].to(torch.float64).reshape(-1, Cout) if t.get('res') is not None else None
-    if t.get('aux') is not None:
+    if after:
+        assert r is not None and t.get('aux') is None
+        out = _act(a + r, g.act)
+    elif t.get('aux') is not None:
         r0 = 0.0 if r is None else r
         out = r0 + AUX_W * (r0 * t['aux'].to(torch.float64).reshape(-1, Cout) + a)
     elif r is not None:
@@ -145,32 +163,62 @@ def conv2d_ref(g, t):
     else:
         out = a
     per = out.reshape(N, g.Ho * g.Wo, Cout)
-    res = dict(out=out, stats_sum=per.sum(1), stats_sumsq=(per * per).sum(1), amax=per.abs().amax((1, 2)))
+    res = dict(out=out, stats_sum=per.sum(1), stats_sumsq=(per * per).sum(1), amax=per.abs().amax((1, 2)), absdot=absdot, linear=linear)
     if g.out_bf16:
         res['out_rounded'] = bf16r(out)
     return res
 
 
+CONV_FOLLOW_UPS = ('conv_splitk_reduce4_kernel', 'conv_splitk_reduce_kernel', 'conv_stats_replica_kernel', 'conv_x3_gather_stats_replica_kernel')
+# template position of the single-fp16 flag X1 in the kernels that have one (keep_conv2d_launch_plan spells every argument out)
+_X1_ARG = {'conv3x3_halo_x3s_kernel': (3, 2), 'conv3x3_halo_x3s_act_kernel': (4, 2), 'conv3x3_halo_x3_kernel': (7, 6), 'conv_x3_kernel': (10, 9)}
+
+
+def conv_kernel(launched):
+    """The convolution kernel of a string keep_conv2d_launch_plan answers: without the zero-fill of the amax slots before it and the
+    follow-up kernels behind it (a split-K reducer, a statistics replica), which are judged through what they write."""
+    parts = [p for p in launched.split(' + ') if p not in ('zero_u32_kernel', 'LayerNorm') and p not in CONV_FOLLOW_UPS]      # ('+ LayerNorm': the plan's name of that form)
+    assert len(parts) == 1, launched
+    return parts[0]
+
+
 def conv_class(kernel):
-    """Tolerance class of the kernel family keep_conv2d_plan names: 'f32', 'x3', 'bf16', or 'plan-only' for a plan that launches
-    nothing.  Anything else raises: a new family must be classified before its cases can be judged."""
-    if kernel.startswith(('conv_f32_kernel<', 'conv3x3_halo_f32_kernel<')) or kernel == 'conv3x3_cout4_kernel':
-        return 'f32'
-    if kernel.startswith(('conv3x3_halo_x3_kernel<', 'gemm_x3l_kernel<', 'conv_x3_kernel<')) or kernel in ('conv3x3_c3_x3_kernel', 'conv3x3_halo_x3s_kernel'):
-        return 'x3'
-    if kernel.startswith(('conv3x3_halo3_kernel<', 'conv_bf16_kernel<')) or kernel == 'conv3x3_c3_kernel':
-        return 'bf16'
+    """Tolerance class -- 'f32', 'x3', 'x1', 'bf16', or 'plan-only' for a plan that launches nothing -- of a kernel string: the launched
+    instantiation keep_conv2d_launch_plan names (follow-up kernels included) or the family string of keep_conv2d_plan.  Anything else
+    raises: a new instantiation must be classified before its cases can be judged."""
     if kernel == '(keep_norm_act_bf16 first)':
         return 'plan-only'
-    raise KeyError(f'no tolerance class for kernel family {kernel!r}')
+    kernel = conv_kernel(kernel)
+    name, _, rest = kernel.partition('<')
+    args = [a.strip() for a in rest.rstrip('>').split(',')] if rest else []
+    if name in ('conv_f32_kernel', 'conv3x3_halo_f32_kernel', 'conv3x3_cout4_kernel'):
+        return 'f32'
+    if name in ('conv3x3_halo3_kernel', 'conv3x3_halo_kernel', 'conv_bf16_kernel', 'conv3x3_c3_kernel'):
+        return 'bf16'
+    if name == 'conv3x3_up2_x1s_kernel' or args == ['32', 'x2 phases', 'true']:
+        return 'x1'
+    if name in _X1_ARG and len(args) == _X1_ARG[name][0]:
+        return 'x1' if args[_X1_ARG[name][1]] in ('true', '1') else 'x3'
+    if name in ('conv3x3_halo_x3_kernel', 'gemm_x3l_kernel', 'conv_x3_kernel', 'conv3x3_c3_x3_kernel', 'conv3x3_halo_x3s_kernel', 'conv3x3_x3p_kernel',
+                'conv3x3_x3q_kernel', 'conv3x3_up2_x3s_kernel'):      # (the shorter argument lists of the plan's family strings: x3 forms)
+        return 'x3'
+    raise KeyError(f'no tolerance class for kernel {kernel!r}')
 
 
 def conv_tol(klass, g):
-    """Element tolerance of a convolution case, relative to scale (x3: the ceiling of its yardstick's f32 leg)."""
+    """Element tolerance of a convolution case, relative to scale (x3: the ceiling of its yardstick's f32 leg).  The x1 class has none:
+    its bound is per output (``conv_bound``)."""
     if klass in ('f32', 'x3'):
         return TOL
     assert klass == 'bf16', klass
     return (BF16_TOL_PRO_ACT if g.pro_act != PRO_NONE else BF16_TOL) + (BF16_ULP if g.out_bf16 else 0.0)
+
+
+def conv_bound(klass, g, ref):
+    """What |out - reference| may reach per output element: a [N*Ho*Wo, Cout] tensor for x1, else tolerance x scale."""
+    if klass == 'x1':
+        return X1_TOL * ref['absdot']
+    return torch.full_like(ref['out'], conv_tol(klass, g) * max(1.0, float(ref['out'].abs().max())))
 
 
 def conv_twin_kw(kw):
@@ -211,10 +259,20 @@ def judge_conv(name, kernel, g, got, ref, twin_out=None, stats_P=0):
         print(f'{line} err_f32 {e32:.3e}')
         yardstick(f'conv {name}', err, e32, sc)
         bound = max(3.0 * e32, 2e-6 * sc)
+    elif klass == 'x1':      # per output, against its own sum |x| |w|
+        lim = conv_bound(klass, g, ref)
+        d = (out.detach().cpu().to(torch.float64) - ref['out']).abs()
+        d = torch.where(torch.isfinite(d), d, torch.full_like(d, math.inf))
+        over = (d / lim).reshape(-1)
+        pos = int(over.argmax())
+        bound = float(lim.max())
+        print(f'{line} bound {bound:.3e} worst err / (sum|x||w|) {float(over[pos]) * X1_TOL:.3e} of {X1_TOL:.3e}')
+        assert float(over[pos]) <= 1.0, (f'conv {name} ({kernel}): err {float(d.reshape(-1)[pos]):.3e} > {float(lim.reshape(-1)[pos]):.3e} = '
+                                         f'{X1_TOL:.3e} x sum|x||w| at {_where(pos, g)}')
     else:
         bound = conv_tol(klass, g) * sc
         print(f'{line} bound {bound:.3e}')
-    assert err <= bound, f'conv {name} ({kernel}): err {err:.3e} > {bound:.3e} (scale {sc:.3g}), worst at {_where(pos, g)}'
+    assert klass == 'x1' or err <= bound, f'conv {name} ({kernel}): err {err:.3e} > {bound:.3e} (scale {sc:.3g}), worst at {_where(pos, g)}'
     N, HW, Cout = g.N, g.Ho * g.Wo, g.Cout
     if g.amax:
         per = out.detach().cpu().float().reshape(N, -1).abs().amax(1)
@@ -224,7 +282,7 @@ def judge_conv(name, kernel, g, got, ref, twin_out=None, stats_P=0):
             assert not got[side].detach().cpu().view(torch.int32).any(), f"conv {name}: a neighbouring amax slot was written: {side} = {got[side].tolist()}"
     if g.stats:
         assert stats_P > 0
-        base = bound if klass == 'x3' else conv_tol(klass, dict_view(g, out_bf16=False)) * sc      # statistics are taken before a bf16 rounding
+        base = bound if klass in ('x3', 'x1') else conv_tol(klass, dict_view(g, out_bf16=False)) * sc      # statistics are taken before a bf16 rounding
         part = got['stats'].detach().cpu().to(torch.float64).reshape(N, stats_P, Cout, 2).sum(1)
         absum = ref['out'].abs().reshape(N, HW, Cout).sum(1)
         for what, have, want, lim in (('sum', part[..., 0], ref['stats_sum'], HW * base + HW * 2.0 ** -24 * absum),
@@ -269,6 +327,29 @@ def conv_removals(g, t):
     if g.ln:
         yield 'ln_gamma', g, drop('ln_gamma')
         yield 'ln_beta', g, drop('ln_beta')
+
+
+def conv_neighbours(g, t, ref):
+    """(what, `out`) of the case as a NEIGHBOURING instantiation or a wrong epilogue order would compute it -- what a wrong arm of a launch
+    macro gives: every other epilogue activation of the seven; every other prologue activation, and the affine dropped; the activation
+    applied after the residual instead of before it; zero padding in place of reflection padding and the other way round (where the
+    convolution pads at all).  ``ref``: the case's own answer (its linear part is reused where the variant differs behind it only)."""
+    for act in (ACT_NONE, ACT_RELU, ACT_LRELU02, ACT_GELU, ACT_SIGMOID, ACT_LRELU01, ACT_SILU):
+        if act != g.act:
+            yield f'epi_act {act}', conv2d_ref(dict_view(g, act=act), t, ref['linear'])['out']
+    # (bf16 tensors: conv3x3_halo3_kernel / conv_bf16_kernel carry no PRO template argument -- a bf16 input admits no prologue at all, and
+    # a bf16 output is judged to one bf16 ulp at scale, which no prologue variant of these cases clears a hundredfold beside its bias)
+    pro_forms = not (g.in_bf16 or g.out_bf16)
+    for pact in (PRO_NONE, PRO_SWISH, PRO_RELU):
+        if pact != g.pro_act and pro_forms:
+            yield f'pro_act {pact}', conv2d_ref(dict_view(g, pro_act=pact), t)['out']
+    if g.pro and pro_forms:
+        yield 'affine dropped', conv2d_ref(g, {k_: v for k_, v in t.items() if k_ not in ('pro_scale', 'pro_shift')})['out']
+    if g.res_ld and g.act != ACT_NONE and not g.aux:
+        yield 'activation after the residual', conv2d_ref(dict_view(g, act_after_res=True), t, ref['linear'])['out']
+    Hv, Wv = (2 * g.H, 2 * g.W) if g.upsample else (g.H, g.W)
+    if g.k > 1 and g.pad_t == g.pad_l == g.k // 2 and g.pad_t < min(Hv, Wv) and g.mma != MMA_BF16:      # (KEEP_MMA_BF16 refuses KEEP_PAD_REFLECT: no such neighbour)
+        yield ('zero padding' if g.reflect else 'reflection padding'), conv2d_ref(dict_view(g, reflect=not g.reflect), t)['out']
 
 
 # ------------------------------------------------------------------------------------------------ keep_attention: mode 2

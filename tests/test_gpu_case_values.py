@@ -5,7 +5,8 @@ once with exactly sized buffers (footprint.plain) and is compared with the float
 * ``out`` against ``conv2d_ref`` / ``attention_ref`` under the tolerance class of the kernel family the plan names (abi_ref's
   docstring lists them); an x3 kernel under the suite's yardstick against its exact-f32 twin -- the same case with KEEP_MMA_F32 and
   the x3-only inputs cleared, and for the three features without an f32 kernel the decompositions the kernel tests use (LayerNorm
-  epilogue: GEMM + keep_layernorm; in2: GEMM on the concatenation; x2 phases: upsample = 1 with the plain weights);
+  epilogue: GEMM + keep_layernorm; in2: GEMM on the concatenation; x2 phases: upsample = 1 with the plain weights); a single-fp16 (x1)
+  kernel per output against (2^-10 + 2e-6) sum |x| |w|;
 * the amax slots: bit-equal to max |out[n]| of the device output, the other eight slots of the arena still zero;
 * the statistics partials, summed over P: the per-(n, c) sum / sum of squares of the reference within what the element tolerance
   allows (HoWo * tol * scale, plus HoWo * 2^-24 * sum |ref| of float32 summation).
@@ -25,7 +26,7 @@ from comfyui_keep_amd.engine import ops
 
 pytestmark = pytest.mark.gpu
 
-LAUNCHED_CONV = [n for n, (_, kw) in T.CONV_CASES.items() if kw.get('launch', True)]
+LAUNCHED_CONV = [n for n, (_, _, kw) in T.CONV_CASES.items() if kw.get('launch', True)]
 
 
 def payloads(regions):
@@ -48,7 +49,7 @@ def with_amax_neighbours(regions, N):
 
 def conv_twin_regions(name, t):
     """_conv_regions of the exact-f32 twin of x3 case ``name`` (``t``: the case's payloads)."""
-    _, kw = T.CONV_CASES[name]
+    _, _, kw = T.CONV_CASES[name]
     g = T._Geom(kw)
     x = None
     if g.in2_cin1:

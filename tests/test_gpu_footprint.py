@@ -5,9 +5,12 @@ zero / NaN / 3e38 surroundings of everything that is read, finite, and equal to 
 judged by tests/test_gpu_case_values.py against the float64 restatement of the two ABIs in tests/abi_ref.py, those of the flat entry
 points by tests/test_gpu_flat_values.py against the restatements in tests/flat_ref.py.
 
-The case tables are plain data, importable without a GPU: tests/test_host_logic.py asks ``keep_conv2d_plan`` (host C) for every
-convolution case and ``keep_attention_plan`` for every attention case, and checks that the tables reach every convolution kernel
-family and every template instantiation keep_attention can launch, and name every launcher of include/keep_hip.h.
+The case tables are plain data, importable without a GPU.  A convolution case names its kernel at two levels: the FAMILY string
+``keep_conv2d_plan`` reports (the form's name, which the engine's precision policies key on) and the LAUNCHED instantiation
+``keep_conv2d_launch_plan`` reports (what the launch takes for the real N, the flags, the chunk count and the activations, follow-up
+kernels joined with " + ").  tests/test_host_logic.py asks both (host C) for every convolution case and ``keep_attention_plan`` for every
+attention case, and checks that the tables reach every convolution kernel family, every template instantiation keep_conv2d and
+keep_attention can launch, and name every launcher of include/keep_hip.h.
 """
 import ctypes
 import inspect
@@ -37,103 +40,293 @@ def rnd(name, shape, scale=1.0, dtype=F32):
 
 
 # ------------------------------------------------------------------------------------------------ keep_conv2d
-# name -> (expected family string of keep_conv2d_plan, arguments).  Geometry keys: N H W Cin Cout k stride pad (or pad_t/pad_l) Ho Wo
+# name -> (expected family string of keep_conv2d_plan, expected launched string of keep_conv2d_launch_plan, arguments).  Geometry keys: N H W Cin Cout k stride pad (or pad_t/pad_l) Ho Wo
 # (default: same-size for stride 1, the symmetric-padding size otherwise) in_ld in_off out_ld out_off res_ld aux pro pro_act act split_k
-# stats amax in_amax in2_cin1 reflect upsample in_bf16 out_bf16 bk256 ln flags launch (False: plan-only); data keys: pro_amp (prologue rows are
-# 1 +- pro_amp / +- pro_amp, default 0.2) and bias_amp (default 1): raised where a coarse tolerance class would otherwise let a
-# kernel that ignores the input pass (tests/test_host_logic.py: every optional input moves the reference by >= 100 x the tolerance).
-def _c(expect, mma, **kw):
-    return expect, dict(mma=mma, **kw)
+# stats amax amax_stale (the amax slots hold stale values and the call says so: x3_out_amax_zeroed = 0) in_amax in2_cin1 reflect upsample
+# in_bf16 out_bf16 bk256 ln flags launch (False: plan-only); data keys: pro_amp (prologue rows are 1 +- pro_amp / +- pro_amp, default 0.2),
+# bias_amp (default 1), x_amp (input, default 2), w_amp (weights, default 0.05) and w_peak (every w_peak-th input channel's weights at w_amp, the others at w_amp /
+# w_peak, or at w_amp * w_floor where that is given; default 1: all alike): set where a tolerance class would otherwise let a kernel that ignores an input,
+# or takes a neighbouring activation, pass (tests/test_host_logic.py: every such change moves the reference by >= 100 x the tolerance).
+def _c(expect, launched, mma, **kw):
+    return expect, launched, dict(mma=mma, **kw)
 
 
-F_, B_, X_ = L.MMA_F32, L.MMA_BF16, L.MMA_X3
+F_, B_, X_, X1_ = L.MMA_F32, L.MMA_BF16, L.MMA_X3, L.MMA_X1
 CONV_CASES = {
     # ---- <= 4 output channels, every policy (exact-fp32 VALU kernel): N = 3, strided input slice, prologue
-    'cout4_f32': _c('conv3x3_cout4_kernel', F_, N=3, H=8, W=32, Cin=16, Cout=3, in_ld=24, in_off=4, out_ld=5, out_off=1, pro=True,
+    'cout4_f32': _c('conv3x3_cout4_kernel',
+                    'conv3x3_cout4_kernel', F_, N=3, H=8, W=32, Cin=16, Cout=3, in_ld=24, in_off=4, out_ld=5, out_off=1, pro=True,
                     pro_act=L.PRO_SWISH),
-    'cout4_x3': _c('conv3x3_cout4_kernel', X_, N=1, H=16, W=32, Cin=32, Cout=2, act=L.ACT_SIGMOID),
+    'cout4_x3': _c('conv3x3_cout4_kernel',
+                   'conv3x3_cout4_kernel', X_, N=1, H=16, W=32, Cin=32, Cout=2, act=L.ACT_SIGMOID),
     # ---- RGB first convolutions (rows of 3 floats inside rows of 4: the 4th float is a gap)
-    'c3_bf16': _c('conv3x3_c3_kernel', B_, N=3, H=8, W=32, Cin=3, Cout=32, in_ld=4, stats=True),
-    'c3_x3': _c('conv3x3_c3_x3_kernel', X_, N=1, H=16, W=32, Cin=3, Cout=48, out_ld=64, out_off=8, in_amax=True, amax=True),
-    'c3_x3_dense': _c('conv3x3_c3_x3_kernel', X_, N=3, H=8, W=32, Cin=2, Cout=32, in_amax=True, amax=True, stats=True),
+    'c3_bf16': _c('conv3x3_c3_kernel',
+                  'conv3x3_c3_kernel', B_, N=3, H=8, W=32, Cin=3, Cout=32, in_ld=4, stats=True),
+    'c3_x3': _c('conv3x3_c3_x3_kernel',
+                'conv3x3_c3_x3_kernel', X_, N=1, H=16, W=32, Cin=3, Cout=48, out_ld=64, out_off=8, in_amax=True, amax=True),
+    'c3_x3_dense': _c('conv3x3_c3_x3_kernel',
+                      'conv3x3_c3_x3_kernel', X_, N=3, H=8, W=32, Cin=2, Cout=32, in_amax=True, amax=True, stats=True),
     # ---- x3 halo kernels
-    'up2_phases': _c('conv3x3_halo_x3_kernel<32, x2 phases>', X_, N=1, H=8, W=32, Cin=16, Cout=64, upsample=2, in_ld=20, in_off=4,
+    'up2_phases': _c('conv3x3_halo_x3_kernel<32, x2 phases>',
+                     'conv3x3_halo_x3_kernel<32, 0, true, true, true, true, false>', X_, N=1, H=8, W=32, Cin=16, Cout=64, upsample=2, in_ld=20, in_off=4,
                      res_ld=72, in_amax=True, amax=True),
-    'up2_phases_n3': _c('conv3x3_halo_x3_kernel<32, x2 phases>', X_, N=3, H=8, W=32, Cin=48, Cout=64, upsample=2, out_ld=80, out_off=12,
+    'up2_phases_n3': _c('conv3x3_halo_x3_kernel<32, x2 phases>',
+                        'conv3x3_up2_x3s_kernel', X_, N=3, H=8, W=32, Cin=48, Cout=64, upsample=2, out_ld=80, out_off=12,
                         in_amax=True),
-    'x3s_plain': _c('conv3x3_halo_x3s_kernel', X_, N=3, H=8, W=32, Cin=32, Cout=32, in_ld=40, in_off=8, out_ld=48, out_off=8, res_ld=36,
+    'x3s_plain': _c('conv3x3_halo_x3s_kernel',
+                    'conv3x3_halo_x3s_kernel<0, false, false>', X_, N=3, H=8, W=32, Cin=32, Cout=32, in_ld=40, in_off=8, out_ld=48, out_off=8, res_ld=36,
                     in_amax=True, amax=True),
-    'x3s_pro': _c('conv3x3_halo_x3s_kernel', X_, N=1, H=16, W=32, Cin=48, Cout=96, pro=True, pro_act=L.PRO_SWISH, stats=True, amax=True),
-    'x3s_reflect': _c('conv3x3_halo_x3s_kernel', X_, N=1, H=8, W=32, Cin=32, Cout=32, reflect=True, act=L.ACT_LRELU02, in_amax=True),
-    'x3s_up': _c('conv3x3_halo_x3s_kernel', X_, N=1, H=8, W=16, Cin=32, Cout=32, upsample=1, in_amax=True),
-    'halo_x3_16': _c('conv3x3_halo_x3_kernel<16>', X_, N=3, H=16, W=16, Cin=48, Cout=96, pro=True, pro_act=L.PRO_RELU, stats=True,
+    'x3s_pro': _c('conv3x3_halo_x3s_kernel',
+                  'conv3x3_halo_x3s_kernel<1, true, false>', X_, N=1, H=16, W=32, Cin=48, Cout=96, pro=True, pro_act=L.PRO_SWISH, stats=True, amax=True),
+    'x3s_reflect': _c('conv3x3_halo_x3s_kernel',
+                      'conv3x3_halo_x3s_act_kernel<0, false, false, 2>', X_, N=1, H=8, W=32, Cin=32, Cout=32, reflect=True, act=L.ACT_LRELU02, in_amax=True),
+    'x3s_up': _c('conv3x3_halo_x3s_kernel',
+                 'conv3x3_halo_x3s_kernel<0, false, false>', X_, N=1, H=8, W=16, Cin=32, Cout=32, upsample=1, in_amax=True),
+    'halo_x3_16': _c('conv3x3_halo_x3_kernel<16>',
+                     'conv3x3_halo_x3_kernel<16, 2, true, true, true, false, false>', X_, N=3, H=16, W=16, Cin=48, Cout=96, pro=True, pro_act=L.PRO_RELU, stats=True,
                      amax=True, in_ld=52, in_off=4),
-    'halo_x3_16_aux': _c('conv3x3_halo_x3_kernel<16>', X_, N=1, H=16, W=16, Cin=16, Cout=32, res_ld=40, aux=True, in_amax=True),
-    'halo_x3_32_split': _c('conv3x3_halo_x3_kernel<32>', X_, N=1, H=8, W=32, Cin=48, Cout=32, split_k=3, in_amax=True, res_ld=32),
-    'halo_x3_16_autosplit': _c('conv3x3_halo_x3_kernel<16>', X_, N=1, H=16, W=16, Cin=128, Cout=32, pro=True, pro_act=L.PRO_SWISH),
+    'halo_x3_16_aux': _c('conv3x3_halo_x3_kernel<16>',
+                         'conv3x3_halo_x3_kernel<16, 0, false, true, true, false, false>', X_, N=1, H=16, W=16, Cin=16, Cout=32, res_ld=40, aux=True, in_amax=True),
+    'halo_x3_32_split': _c('conv3x3_halo_x3_kernel<32>',
+                           'conv3x3_halo_x3_kernel<32, 0, false, true, true, false, false> + conv_splitk_reduce4_kernel', X_, N=1, H=8, W=32, Cin=48, Cout=32, split_k=3, in_amax=True, res_ld=32),
+    'halo_x3_16_autosplit': _c('conv3x3_halo_x3_kernel<16>',
+                               'conv3x3_halo_x3_kernel<16, 1, false, true, true, false, false> + conv_splitk_reduce4_kernel', X_, N=1, H=16, W=16, Cin=128, Cout=32, pro=True, pro_act=L.PRO_SWISH),
     # ---- the 64-pixel-block x3 kernels of keep_conv_x3p.hip.  keep_conv2d_plan prints them under the halo names (it names the family whose
     # values they reproduce); the dispatch takes them for few-item launches with Cout % 64 == 0 (keep_conv_x3p_ok / _full_ok / x3q_ok):
     # conv3x3_x3p_kernel<.., 4> as split-K producer, conv3x3_x3p_kernel with the full epilogue (16-wide map, aux), conv3x3_x3q_kernel
-    'x3p_partials': _c('conv3x3_halo_x3_kernel<16>', X_, N=3, H=16, W=16, Cin=128, Cout=64, split_k=2, pro=True, in_ld=132, in_off=4, res_ld=72),
-    'x3p_full_aux': _c('conv3x3_halo_x3_kernel<16>', X_, N=1, H=16, W=16, Cin=64, Cout=64, split_k=1, res_ld=68, aux=True, act=L.ACT_LRELU02,
+    'x3p_partials': _c('conv3x3_halo_x3_kernel<16>',
+                       'conv3x3_x3p_kernel<0, true, 4> + conv_splitk_reduce4_kernel', X_, N=3, H=16, W=16, Cin=128, Cout=64, split_k=2, pro=True, in_ld=132, in_off=4, res_ld=72),
+    'x3p_full_aux': _c('conv3x3_halo_x3_kernel<16>',
+                       'conv3x3_x3p_kernel<0, false, 4>', X_, N=1, H=16, W=16, Cin=64, Cout=64, split_k=1, res_ld=68, aux=True, act=L.ACT_LRELU02,
                        in_amax=True, amax=True, out_ld=72, out_off=4),
-    'x3q_small': _c('conv3x3_halo_x3s_kernel', X_, N=3, H=8, W=32, Cin=32, Cout=64, split_k=1, in_ld=40, in_off=8, res_ld=68, act=L.ACT_LRELU02,
+    'x3q_small': _c('conv3x3_halo_x3s_kernel',
+                    'conv3x3_x3q_kernel<0, false, 0> + conv_stats_replica_kernel', X_, N=3, H=8, W=32, Cin=32, Cout=64, split_k=1, in_ld=40, in_off=8, res_ld=68, act=L.ACT_LRELU02,
                     stats=True, in_amax=True, amax=True),
     # ---- x3 GEMM / gather kernels
-    'gemm_x3l_4': _c('gemm_x3l_kernel<4>', X_, N=3, H=64, W=1, Cin=256, Cout=32, k=1, in_ld=260, in_off=4, out_ld=40, out_off=4,
+    'gemm_x3l_4': _c('gemm_x3l_kernel<4>',
+                     'gemm_x3l_kernel<4, 1, true>', X_, N=3, H=64, W=1, Cin=256, Cout=32, k=1, in_ld=260, in_off=4, out_ld=40, out_off=4,
                      res_ld=36, in_amax=True, amax=True, act=L.ACT_GELU),
-    'gemm_x3l_8': _c('gemm_x3l_kernel<8>', X_, N=1, H=192, W=1, Cin=1024, Cout=96, k=1, in_amax=True, amax=True),
-    'x3_ln': _c('conv_x3_kernel<4, 1, 1, 4, true, true> + LayerNorm', X_, N=3, H=128, W=1, Cin=48, Cout=128, k=1, ln=True, res_ld=132,
+    'gemm_x3l_8': _c('gemm_x3l_kernel<8>',
+                     'gemm_x3l_kernel<8, 1, true>', X_, N=1, H=192, W=1, Cin=1024, Cout=96, k=1, in_amax=True, amax=True),
+    'x3_ln': _c('conv_x3_kernel<4, 1, 1, 4, true, true> + LayerNorm',
+                'conv_x3_kernel<4, 1, 1, 4, true, true, false, true, false, false>', X_, N=3, H=128, W=1, Cin=48, Cout=128, k=1, ln=True, res_ld=132,
                 in_ld=56, in_off=4, in_amax=True, amax=True),
-    'x3_gemm_small': _c('conv_x3_kernel<2, 2, 1, 1, true, true>', X_, N=1, H=300, W=1, Cin=80, Cout=48, k=1, in_ld=96, in_off=8, out_ld=56,
+    'x3_gemm_small': _c('conv_x3_kernel<2, 2, 1, 1, true, true>',
+                        'conv_x3_kernel<2, 2, 1, 1, true, true, false, true, false, false>', X_, N=1, H=300, W=1, Cin=80, Cout=48, k=1, in_ld=96, in_off=8, out_ld=56,
                         out_off=4, res_ld=52, in_amax=True),
-    'x3_gemm_in2': _c('conv_x3_kernel<2, 2, 1, 1, true, true>', X_, N=1, H=200, W=1, Cin=80, Cout=48, k=1, in2_cin1=32, in_ld=36),
-    'x3_gemm_big': _c('conv_x3_kernel<2, 2, 2, 2, true, true>', X_, N=1, H=777, W=1, Cin=48, Cout=96, k=1, in_amax=True, act=L.ACT_GELU),
-    'x3_gemm_pro_amax': _c('conv_x3_kernel<2, 2, 1, 1, false, true>', X_, N=3, H=8, W=8, Cin=48, Cout=48, k=1, pro=True, stats=True, amax=True),
-    'x3_gemm_split': _c('conv_x3_kernel<2, 2, 1, 1, true, true>', X_, N=1, H=300, W=1, Cin=512, Cout=48, k=1, in_amax=True, flags=L.CONV_NO_GEMM_LAT),
-    'x3_gather_down': _c('conv_x3_kernel<2, 2, 1, 1, true, false>', X_, N=3, H=10, W=14, Cin=16, Cout=48, stride=2, pad_t=0, pad_l=0,
+    'x3_gemm_in2': _c('conv_x3_kernel<2, 2, 1, 1, true, true>',
+                      'conv_x3_kernel<2, 2, 1, 1, true, true, false, true, false, false>', X_, N=1, H=200, W=1, Cin=80, Cout=48, k=1, in2_cin1=32, in_ld=36),
+    'x3_gemm_big': _c('conv_x3_kernel<2, 2, 2, 2, true, true>',
+                      'conv_x3_kernel<2, 2, 1, 1, true, true, false, true, false, false>', X_, N=1, H=777, W=1, Cin=48, Cout=96, k=1, in_amax=True, act=L.ACT_GELU),
+    'x3_gemm_pro_amax': _c('conv_x3_kernel<2, 2, 1, 1, false, true>',
+                           'conv_x3_kernel<2, 2, 1, 1, false, true, false, true, false, false>', X_, N=3, H=8, W=8, Cin=48, Cout=48, k=1, pro=True, stats=True, amax=True),
+    'x3_gemm_split': _c('conv_x3_kernel<2, 2, 1, 1, true, true>',
+                        'conv_x3_kernel<2, 2, 1, 1, true, true, false, true, false, false> + conv_splitk_reduce4_kernel', X_, N=1, H=300, W=1, Cin=512, Cout=48, k=1, in_amax=True, flags=L.CONV_NO_GEMM_LAT),
+    'x3_gather_down': _c('conv_x3_kernel<2, 2, 1, 1, true, false>',
+                         'conv_x3_kernel<2, 2, 1, 1, true, false, false, true, false, false> + conv_splitk_reduce4_kernel', X_, N=3, H=10, W=14, Cin=16, Cout=48, stride=2, pad_t=0, pad_l=0,
                          Ho=5, Wo=7, in_amax=True),
-    'x3_gather_7x7': _c('conv_x3_kernel<2, 2, 1, 1, false, false>', X_, N=1, H=5, W=7, Cin=144, Cout=48, k=7, pad=3, pro=True,
+    'x3_gather_7x7': _c('conv_x3_kernel<2, 2, 1, 1, false, false>',
+                        'conv_x3_kernel<2, 2, 1, 1, false, false, false, true, false, false> + conv_splitk_reduce4_kernel', X_, N=1, H=5, W=7, Cin=144, Cout=48, k=7, pad=3, pro=True,
                         pro_act=L.PRO_RELU, split_k=5),
-    'x3_gather_reflect': _c('conv_x3_kernel<2, 2, 2, 2, true, false>', X_, N=1, H=18, W=18, Cin=16, Cout=96, reflect=True, in_amax=True),
+    'x3_gather_reflect': _c('conv_x3_kernel<2, 2, 2, 2, true, false>',
+                            'conv_x3_kernel<2, 2, 1, 1, true, false, false, true, false, false> + conv_splitk_reduce4_kernel', X_, N=1, H=18, W=18, Cin=16, Cout=96, reflect=True, in_amax=True),
     # ---- exact-f32 halo kernel
-    'halo_f32_32': _c('conv3x3_halo_f32_kernel<32>', F_, N=3, H=8, W=32, Cin=16, Cout=32, in_ld=24, in_off=4, out_ld=48, out_off=8,
+    'halo_f32_32': _c('conv3x3_halo_f32_kernel<32>',
+                      'conv3x3_halo_f32_kernel<32, 1>', F_, N=3, H=8, W=32, Cin=16, Cout=32, in_ld=24, in_off=4, out_ld=48, out_off=8,
                       res_ld=40, pro=True, pro_act=L.PRO_SWISH),
-    'halo_f32_16': _c('conv3x3_halo_f32_kernel<16>', F_, N=1, H=16, W=16, Cin=48, Cout=96, stats=True, act=L.ACT_LRELU02),
-    'halo_f32_16_split': _c('conv3x3_halo_f32_kernel<16>', F_, N=1, H=16, W=16, Cin=48, Cout=96, split_k=3, res_ld=100, aux=True),
-    'halo_f32_up_auto': _c('conv3x3_halo_f32_kernel<16>', F_, N=1, H=8, W=8, Cin=128, Cout=32, upsample=1),
+    'halo_f32_16': _c('conv3x3_halo_f32_kernel<16>',
+                      'conv3x3_halo_f32_kernel<16, 0>', F_, N=1, H=16, W=16, Cin=48, Cout=96, stats=True, act=L.ACT_LRELU02),
+    'halo_f32_16_split': _c('conv3x3_halo_f32_kernel<16>',
+                            'conv3x3_halo_f32_kernel<16, 0> + conv_splitk_reduce4_kernel', F_, N=1, H=16, W=16, Cin=48, Cout=96, split_k=3, res_ld=100, aux=True),
+    'halo_f32_up_auto': _c('conv3x3_halo_f32_kernel<16>',
+                           'conv3x3_halo_f32_kernel<16, 0> + conv_splitk_reduce4_kernel', F_, N=1, H=8, W=8, Cin=128, Cout=32, upsample=1),
     # ---- bf16 halo kernels
-    'halo3_f32in_32': _c('conv3x3_halo3_kernel<false, 32>', B_, N=1, H=8, W=32, Cin=32, Cout=32, in_ld=40, in_off=8, out_ld=48, out_off=8,
+    'halo3_f32in_32': _c('conv3x3_halo3_kernel<false, 32>',
+                         'conv3x3_halo3_kernel<false, 32, true>', B_, N=1, H=8, W=32, Cin=32, Cout=32, in_ld=40, in_off=8, out_ld=48, out_off=8,
                          res_ld=36),
-    'halo3_bf16in_16': _c('conv3x3_halo3_kernel<true, 16>', B_, N=3, H=16, W=16, Cin=32, Cout=64, in_bf16=True, out_bf16=True, bias_amp=2.0),
-    'halo3_bf16in_split': _c('conv3x3_halo3_kernel<true, 32>', B_, N=1, H=8, W=32, Cin=96, Cout=96, in_bf16=True, split_k=3, act=L.ACT_GELU),
-    'halo_bf16_pro_fused': _c('conv3x3_halo3_kernel<false, 16>', B_, N=1, H=16, W=16, Cin=32, Cout=64, pro=True, pro_act=L.PRO_SWISH, stats=True, pro_amp=0.8),
-    'halo_bf16_needs_prenorm': _c('(keep_norm_act_bf16 first)', B_, N=1, H=16, W=16, Cin=32, Cout=64, in_bf16=True, pro=True, launch=False),
+    'halo3_bf16in_16': _c('conv3x3_halo3_kernel<true, 16>',
+                          'conv3x3_halo3_kernel<true, 16, true>', B_, N=3, H=16, W=16, Cin=32, Cout=64, in_bf16=True, out_bf16=True, bias_amp=2.0),
+    'halo3_bf16in_split': _c('conv3x3_halo3_kernel<true, 32>',
+                             'conv3x3_halo3_kernel<true, 32, false> + conv_splitk_reduce4_kernel', B_, N=1, H=8, W=32, Cin=96, Cout=96, in_bf16=True, split_k=3, act=L.ACT_GELU),
+    'halo_bf16_pro_fused': _c('conv3x3_halo3_kernel<false, 16>',
+                              'conv3x3_halo_kernel<false, 16>', B_, N=1, H=16, W=16, Cin=32, Cout=64, pro=True, pro_act=L.PRO_SWISH, stats=True, pro_amp=0.8, x_amp=0.7, w_amp=0.1),
+    'halo_bf16_needs_prenorm': _c('(keep_norm_act_bf16 first)',
+                                  '', B_, N=1, H=16, W=16, Cin=32, Cout=64, in_bf16=True, pro=True, launch=False),
     # ---- bf16 gather kernels
-    'bf16_t0': _c('conv_bf16_kernel<4, 1, 1, 1, 64, 1, false>', B_, N=3, H=5, W=7, Cin=24, Cout=20, stride=2, in_ld=28, in_off=4),
-    'bf16_t1_plain': _c('conv_bf16_kernel<2, 2, 1, 1, 64, 1, true>', B_, N=1, H=300, W=1, Cin=80, Cout=48, k=1, in_ld=96, in_off=8, out_ld=56,
+    'bf16_t0': _c('conv_bf16_kernel<4, 1, 1, 1, 64, 1, false>',
+                  'conv_bf16_kernel<4, 1, 1, 1, 64, 1, false> + conv_splitk_reduce4_kernel', B_, N=3, H=5, W=7, Cin=24, Cout=20, stride=2, in_ld=28, in_off=4),
+    'bf16_t1_plain': _c('conv_bf16_kernel<2, 2, 1, 1, 64, 1, true>',
+                        'conv_bf16_kernel<2, 2, 1, 1, 64, 1, true>', B_, N=1, H=300, W=1, Cin=80, Cout=48, k=1, in_ld=96, in_off=8, out_ld=56,
                         out_off=4, res_ld=52, out_bf16=False),
-    'bf16_t1_pro': _c('conv_bf16_kernel<2, 2, 1, 1, 64, 1, false>', B_, N=1, H=5, W=7, Cin=130, Cout=48, k=7, pad=3, pro=True, pro_act=L.PRO_RELU, pro_amp=1.5,
-                      bias_amp=3.0),
-    'bf16_t1_bf16out': _c('conv_bf16_kernel<2, 2, 1, 1, 64, 1, true>', B_, N=1, H=250, W=1, Cin=48, Cout=64, k=1, out_bf16=True),
-    'bf16_t1_bk256': _c('conv_bf16_kernel<2, 2, 1, 1, 256, 1, false>', B_, N=1, H=100, W=1, Cin=512, Cout=64, k=1, bk256=True),
-    'bf16_t2': _c('conv_bf16_kernel<2, 2, 2, 2, 64, 1, true>', B_, N=1, H=4133, W=1, Cin=16, Cout=96, k=1, stats=False),
-    'bf16_t2_up': _c('conv_bf16_kernel<2, 2, 2, 2, 64, 1, false>', B_, N=1, H=33, W=35, Cin=16, Cout=96, upsample=1),
-    'bf16_flatk': _c('conv_bf16_kernel<2, 2, 1, 1, 64, 1, false>', B_, N=1, H=5, W=7, Cin=3, Cout=48),
+    'bf16_t1_pro': _c('conv_bf16_kernel<2, 2, 1, 1, 64, 1, false>',
+                      'conv_bf16_kernel<2, 2, 1, 1, 64, 1, false> + conv_splitk_reduce4_kernel', B_, N=1, H=5, W=7, Cin=130, Cout=48, k=7, pad=3, pro=True, pro_act=L.PRO_RELU, pro_amp=0.8,
+                      bias_amp=1.5, x_amp=0.5),
+    'bf16_t1_bf16out': _c('conv_bf16_kernel<2, 2, 1, 1, 64, 1, true>',
+                          'conv_bf16_kernel<2, 2, 1, 1, 64, 1, true>', B_, N=1, H=250, W=1, Cin=48, Cout=64, k=1, out_bf16=True),
+    'bf16_t1_bk256': _c('conv_bf16_kernel<2, 2, 1, 1, 256, 1, false>',
+                        'conv_bf16_kernel<2, 2, 1, 1, 256, 1, false>', B_, N=1, H=100, W=1, Cin=512, Cout=64, k=1, bk256=True),
+    'bf16_t2': _c('conv_bf16_kernel<2, 2, 2, 2, 64, 1, true>',
+                  'conv_bf16_kernel<2, 2, 2, 2, 64, 1, true>', B_, N=1, H=4133, W=1, Cin=16, Cout=96, k=1, stats=False),
+    'bf16_t2_up': _c('conv_bf16_kernel<2, 2, 2, 2, 64, 1, false>',
+                     'conv_bf16_kernel<2, 2, 2, 2, 64, 1, false> + conv_splitk_reduce4_kernel', B_, N=1, H=33, W=35, Cin=16, Cout=96, upsample=1),
+    'bf16_flatk': _c('conv_bf16_kernel<2, 2, 1, 1, 64, 1, false>',
+                     'conv_bf16_kernel<2, 2, 1, 1, 64, 1, false>', B_, N=1, H=5, W=7, Cin=3, Cout=48),
     # ---- exact-f32 gather kernels
-    'f32_t0_7x7': _c('conv_f32_kernel<4, 1, 1, 1>', F_, N=1, H=5, W=7, Cin=130, Cout=32, k=7, pad=3, in_ld=132),
-    'f32_t0_down': _c('conv_f32_kernel<4, 1, 1, 1>', F_, N=3, H=10, W=14, Cin=24, Cout=20, stride=2, pad_t=0, pad_l=0, Ho=5, Wo=7,
+    'f32_t0_7x7': _c('conv_f32_kernel<4, 1, 1, 1>',
+                     'conv_f32_kernel<4, 1, 1, 1, false> + conv_splitk_reduce4_kernel', F_, N=1, H=5, W=7, Cin=130, Cout=32, k=7, pad=3, in_ld=132),
+    'f32_t0_down': _c('conv_f32_kernel<4, 1, 1, 1>',
+                      'conv_f32_kernel<4, 1, 1, 1, false> + conv_splitk_reduce_kernel', F_, N=3, H=10, W=14, Cin=24, Cout=20, stride=2, pad_t=0, pad_l=0, Ho=5, Wo=7,
                       pro=True, pro_act=L.PRO_SWISH, out_ld=23, out_off=2),
-    'f32_t1': _c('conv_f32_kernel<2, 2, 1, 1>', F_, N=1, H=300, W=1, Cin=80, Cout=48, k=1, in_ld=96, in_off=8, out_ld=56, out_off=4,
+    'f32_t1': _c('conv_f32_kernel<2, 2, 1, 1>',
+                 'conv_f32_kernel<2, 2, 1, 1, true>', F_, N=1, H=300, W=1, Cin=80, Cout=48, k=1, in_ld=96, in_off=8, out_ld=56, out_off=4,
                  res_ld=52, act=L.ACT_GELU),
-    'f32_t1_split': _c('conv_f32_kernel<2, 2, 1, 1>', F_, N=1, H=5, W=7, Cin=48, Cout=48, split_k=4, res_ld=50, aux=True),
-    'f32_t1_autosplit': _c('conv_f32_kernel<2, 2, 1, 1>', F_, N=1, H=8, W=8, Cin=512, Cout=64, k=1),
-    'f32_t1_stats': _c('conv_f32_kernel<2, 2, 1, 1>', F_, N=3, H=8, W=8, Cin=24, Cout=48, k=1, stats=True),
-    'f32_t1_reflect_up': _c('conv_f32_kernel<2, 2, 1, 1>', F_, N=1, H=5, W=7, Cin=10, Cout=40, reflect=True, upsample=1),
-    'f32_t1_flatk': _c('conv_f32_kernel<2, 2, 1, 1>', F_, N=3, H=9, W=11, Cin=3, Cout=36, stride=2),
-    'f32_t2': _c('conv_f32_kernel<2, 2, 2, 2>', F_, N=1, H=777, W=1, Cin=48, Cout=96, k=1, res_ld=96),
-    'f32_t2_x3_fallback': _c('conv_f32_kernel<2, 2, 2, 2>', X_, N=1, H=777, W=1, Cin=40, Cout=130, k=1, in_amax=False),
+    'f32_t1_split': _c('conv_f32_kernel<2, 2, 1, 1>',
+                       'conv_f32_kernel<2, 2, 1, 1, true> + conv_splitk_reduce_kernel', F_, N=1, H=5, W=7, Cin=48, Cout=48, split_k=4, res_ld=50, aux=True),
+    'f32_t1_autosplit': _c('conv_f32_kernel<2, 2, 1, 1>',
+                           'conv_f32_kernel<2, 2, 1, 1, true> + conv_splitk_reduce4_kernel', F_, N=1, H=8, W=8, Cin=512, Cout=64, k=1),
+    'f32_t1_stats': _c('conv_f32_kernel<2, 2, 1, 1>',
+                       'conv_f32_kernel<2, 2, 1, 1, false>', F_, N=3, H=8, W=8, Cin=24, Cout=48, k=1, stats=True),
+    'f32_t1_reflect_up': _c('conv_f32_kernel<2, 2, 1, 1>',
+                            'conv_f32_kernel<2, 2, 1, 1, false> + conv_splitk_reduce4_kernel', F_, N=1, H=5, W=7, Cin=10, Cout=40, reflect=True, upsample=1),
+    'f32_t1_flatk': _c('conv_f32_kernel<2, 2, 1, 1>',
+                       'conv_f32_kernel<2, 2, 1, 1, false>', F_, N=3, H=9, W=11, Cin=3, Cout=36, stride=2),
+    'f32_t2': _c('conv_f32_kernel<2, 2, 2, 2>',
+                 'conv_f32_kernel<2, 2, 2, 2, true>', F_, N=1, H=777, W=1, Cin=48, Cout=96, k=1, res_ld=96),
+    'f32_t2_x3_fallback': _c('conv_f32_kernel<2, 2, 2, 2>',
+                             'conv_f32_kernel<2, 2, 2, 2, false>', X_, N=1, H=777, W=1, Cin=40, Cout=130, k=1, in_amax=False),
 }
+
+# ------------------------------------------------------------------------------------------------ the table, grown to the universe
+# Every instantiation keep_conv2d can launch (tests/test_host_logic.py: test_conv_table_reaches_every_instantiation) has a case: the
+# families below are dealt out arm by arm, each case at the smallest shape that still takes its arm -- one or two 256-pixel tiles, N <= 3,
+# the smallest Cin that gives the chunk count -- with the launched string spelled from the case's own parameters.
+_ACT_NAMES = {L.ACT_NONE: 'none', L.ACT_RELU: 'relu', L.ACT_LRELU02: 'lrelu02', L.ACT_GELU: 'gelu', L.ACT_SIGMOID: 'sigmoid',
+              L.ACT_LRELU01: 'lrelu01', L.ACT_SILU: 'silu'}
+_NSP, _EXACT, _NOSTREAM = L.CONV_NO_SMALL_PARTIALS, L.CONV_X3_EXACT_ACT, L.CONV_NO_STREAM
+
+
+def _b(v):
+    return 'true' if v else 'false'
+
+
+def _awkward(i, Cin, Cout, fused=True):
+    """The table's awkwardness, dealt round-robin over a family: a strided input slice, a strided output, res_ld != Cout, N = 3 with
+    per-image maxima, statistics (``fused`` = False: a form that cannot emit amax / statistics takes N = 3 / N = 2 plain)."""
+    return [dict(in_ld=Cin + 8, in_off=8), dict(out_ld=Cout + 16, out_off=8), dict(res_ld=Cout + 4),
+            dict(N=3, in_amax=True, amax=True) if fused else dict(N=3, in_amax=True),
+            dict(stats=True, amax=True) if fused else dict(N=2)][i % 5]
+
+
+# The single-fp16 bound is per output, (2^-10 + 2e-6) sum |x| |w|: with 288 like terms a neighbouring activation moves an output by less than
+# 100 x that.  The x1 cases therefore sum few dominant terms (one input channel in 32 at full weight) behind a wide prologue, and the
+# sigmoid cases -- whose slope of at most 1/4 the bound does not know -- keep the other channels at 1/1024 and the outputs near zero.
+_X1_DATA = dict(w_peak=32, pro_amp=1.0, w_amp=0.02)
+_X1_SIGMOID = dict(w_peak=16, w_floor=1.0 / 1024, pro_amp=0.8, w_amp=0.05, bias_amp=0.15, x_amp=1.2)
+
+
+def _grow(cases):
+    i = 0
+    # ---- the streaming kernel: <PRO, AFF, X1> x the epilogue activation, x3 and single fp16 (x3 launches of so few items stay on it under
+    # CONV_NO_SMALL_PARTIALS; the x1 form has no 64-pixel twin)
+    pro_forms = {'raw': (L.PRO_NONE, False), 'aff': (L.PRO_NONE, True), 'affswish': (L.PRO_SWISH, True), 'affrelu': (L.PRO_RELU, True)}
+    for x1 in (False, True):
+        for pname, (pact, aff) in pro_forms.items():
+            for act, aname in _ACT_NAMES.items():
+                targs = f'{pact}, {_b(aff)}, {_b(x1)}'
+                launched = f'conv3x3_halo_x3s_kernel<{targs}>' if act == L.ACT_NONE else f'conv3x3_halo_x3s_act_kernel<{targs}, {act}>'
+                expect = f'conv3x3_halo_x3s_kernel<{pact}, {_b(aff)}, true>' if x1 else 'conv3x3_halo_x3s_kernel'
+                kw = dict(N=1, H=8, W=32, Cin=32, Cout=64, pro=aff, pro_act=pact, act=act, split_k=1, flags=0 if x1 else _NSP)
+                if x1:
+                    kw.update(_X1_SIGMOID if act == L.ACT_SIGMOID else _X1_DATA)
+                cases[f"{'x1s' if x1 else 'x3s'}_{pname}_{aname}"] = _c(expect, launched, X1_ if x1 else X_, **dict(kw, **_awkward(i, 32, 64)))
+                i += 1
+    # ---- the stage-barrier halo kernel: <TW, PRO, SIMPLE_EPI, FASTACT, WDMA, UP2 = false, X1 = false>.  16-wide maps always run it; 32-wide
+    # maps under CONV_NO_STREAM, or with the exact swish (the streaming kernel has the fast form only).  Cout = 96: no 64-pixel blocks.
+    for tw, (H, W) in ((16, (16, 16)), (32, (8, 32))):
+        for pname, (pact, aff, exact) in {'raw': (L.PRO_NONE, False, False), 'relu': (L.PRO_RELU, True, False), 'swish': (L.PRO_SWISH, False, False),
+                                          'swish_exact': (L.PRO_SWISH, True, True)}.items():
+            for simple in (True, False):
+                launched = f'conv3x3_halo_x3_kernel<{tw}, {pact}, {_b(simple)}, {_b(not exact)}, {_b(not exact)}, false, false>'
+                kw = dict(N=1, H=H, W=W, Cin=32, Cout=96, pro=aff, pro_act=pact, act=L.ACT_NONE if simple else (L.ACT_GELU if exact else L.ACT_LRELU02),
+                          split_k=1, flags=(_EXACT if exact else 0) | (_NOSTREAM if tw == 32 and not exact else 0))
+                cases[f"halo_x3_{tw}_{pname}_{'simple' if simple else 'act'}"] = _c(f'conv3x3_halo_x3_kernel<{tw}>', launched, X_, **dict(kw, **_awkward(i, 32, 96)))
+                i += 1
+    # ---- its single-fp16 16 x 16 form (CONV_X1_HALO16): <16, 0, SIMPLE_EPI, true, true, false, true>
+    for simple in (True, False):
+        k_ = f'conv3x3_halo_x3_kernel<16, 0, {_b(simple)}, true, true, false, true>'
+        cases[f"x1_halo16_{'simple' if simple else 'act'}"] = _c(k_, k_, X1_, N=3, H=16, W=16, Cin=32, Cout=32, act=L.ACT_NONE if simple else L.ACT_SILU,
+                                                                  flags=L.CONV_X1_HALO16, in_amax=True, amax=True, stats=simple, res_ld=0 if simple else 36, **_X1_DATA)
+    # ---- the 64-pixel split-K producer: <PRO, SC, NCH>, NCH = chunks per K range where every range has 4, 8 or 16 (else 0)
+    for pname, (pact, sc) in {'raw': (L.PRO_NONE, False), 'aff': (L.PRO_NONE, True), 'swish': (L.PRO_SWISH, False), 'affswish': (L.PRO_SWISH, True)}.items():
+        for nch, Cin in ((0, 96), (4, 128), (8, 256), (16, 512)):
+            launched = f'conv3x3_x3p_kernel<{pact}, {_b(sc)}, {nch}> + conv_splitk_reduce4_kernel'
+            kw = dict(N=1, H=16, W=16, Cin=Cin, Cout=64, pro=sc, pro_act=pact, split_k=2)
+            cases[f'x3p_{pname}_nch{nch}'] = _c('conv3x3_halo_x3_kernel<16>', launched, X_, **dict(kw, **_awkward(i, Cin, 64, fused=False)))
+            i += 1
+    # ---- the 64-pixel blocks with the streaming kernel's values: <PRO, AFF, NCH>, NCH = Cin / 16 where that is 4, 8, 16 or 32 (else 0)
+    for pname, (pact, aff) in {'raw': (L.PRO_NONE, False), 'aff': (L.PRO_NONE, True), 'affswish': (L.PRO_SWISH, True)}.items():
+        for nch, Cin in ((0, 48), (4, 64), (8, 128), (16, 256), (32, 512)):
+            kw = dict(dict(N=1, H=8, W=32, Cin=Cin, Cout=64, pro=aff, pro_act=pact, split_k=1), **_awkward(i, Cin, 64))
+            launched = f'conv3x3_x3q_kernel<{pact}, {_b(aff)}, {nch}>' + (' + conv_stats_replica_kernel' if kw.get('stats') else '')
+            cases[f'x3q_{pname}_nch{nch}'] = _c('conv3x3_halo_x3s_kernel', launched, X_, **kw)
+            i += 1
+    # ---- exact-f32 halo kernel <TW, PRO>, bf16 halo kernel <IN_BF16, TW, SIMPLE_EPI>
+    for tw, (H, W) in ((16, (16, 16)), (32, (8, 32))):
+        for pact, pname in ((L.PRO_NONE, 'raw'), (L.PRO_SWISH, 'swish'), (L.PRO_RELU, 'relu')):
+            kw = dict(N=1, H=H, W=W, Cin=16, Cout=32, pro=pact != L.PRO_NONE, pro_act=pact, split_k=1)
+            cases[f'halo_f32_{tw}_{pname}'] = _c(f'conv3x3_halo_f32_kernel<{tw}>', f'conv3x3_halo_f32_kernel<{tw}, {pact}>', F_, **dict(kw, **_awkward(i, 16, 32, fused=False)))
+            i += 1
+        for inb in (False, True):
+            for simple in (True, False):
+                kw = dict(N=1, H=H, W=W, Cin=32, Cout=64, in_bf16=inb, act=L.ACT_NONE if simple else L.ACT_LRELU02, split_k=1)
+                cases[f"halo3_{'bf16in' if inb else 'f32in'}_{tw}_{'simple' if simple else 'act'}"] = _c(
+                    f'conv3x3_halo3_kernel<{_b(inb)}, {tw}>', f'conv3x3_halo3_kernel<{_b(inb)}, {tw}, {_b(simple)}>', B_, **dict(kw, **_awkward(i, 32, 64, fused=False)))
+                i += 1
+
+
+_grow(CONV_CASES)
+CONV_CASES.update({
+    # ---- the first bf16 halo kernel on a 32-wide map (the prologue fused into its staging step)
+    'halo_bf16_pro_fused_32': _c('conv3x3_halo3_kernel<false, 32>', 'conv3x3_halo_kernel<false, 32>', B_, N=3, H=8, W=32, Cin=32, Cout=64, pro=True,
+                                 pro_act=L.PRO_SWISH, split_k=1, pro_amp=0.8, x_amp=0.7, w_amp=0.1),
+    # ---- the single-fp16 phase kernel (CONV_X1_UP2), and a call whose amax slots hold stale values: the launch zeroes them first
+    'up2_x1s': _c('conv3x3_halo_x3_kernel<32, x2 phases, true>', 'conv3x3_up2_x1s_kernel', X1_, N=3, H=8, W=32, Cin=32, Cout=64, upsample=2, in_amax=True,
+                  amax=True, flags=L.CONV_X1_UP2, out_ld=80, out_off=12),
+    'x3s_stale_amax': _c('conv3x3_halo_x3s_kernel', 'zero_u32_kernel + conv3x3_halo_x3s_kernel<0, false, false>', X_, N=3, H=8, W=32, Cin=32, Cout=64,
+                         split_k=1, in_amax=True, amax=True, amax_stale=True, flags=_NSP),
+    # ---- conv_x3_kernel<tile, PLAIN, ONE, KSL, DEEP, KAL, X1>: canonical K slices on the block-tile kernel (CONV_GEMM_LAT_TILES: two K steps per
+    # slice, then the four-step form of Cin = 512 and of Cin = 1024 on eight slices)
+    'x3_gemm_kslice2': _c('gemm_x3l_kernel<4>', 'conv_x3_kernel<2, 2, 1, 1, true, true, true, true, false, false>', X_, N=3, H=64, W=1, Cin=256, Cout=32, k=1,
+                          in_ld=264, in_off=4, res_ld=36, in_amax=True, amax=True, flags=L.CONV_GEMM_LAT_TILES),
+    'x3_gemm_kslice4': _c('gemm_x3l_kernel<4>', 'conv_x3_kernel<2, 2, 1, 1, true, true, true, true, true, false>', X_, N=1, H=128, W=1, Cin=512, Cout=96, k=1,
+                          out_ld=104, out_off=4, act=L.ACT_GELU, in_amax=True, flags=L.CONV_GEMM_LAT_TILES),
+    'x3_gemm_kslice4_deep': _c('gemm_x3l_kernel<8>', 'conv_x3_kernel<2, 2, 1, 1, true, true, true, true, true, false>', X_, N=1, H=64, W=1, Cin=1024, Cout=32, k=1,
+                               in_amax=True, amax=True, flags=L.CONV_GEMM_LAT_TILES),
+    # ---- the 128 x 128 tile: a launch of few rows keeps it only with statistics it must emit itself (CONV_NO_SMALL_PARTIALS: no replica kernel)
+    'x3_t2_gemm': _c('conv_x3_kernel<2, 2, 2, 2, true, true>', 'conv_x3_kernel<2, 2, 2, 2, true, true, false, true, false, false>', X_, N=1, H=384, W=1, Cin=48,
+                     Cout=96, k=1, split_k=1, stats=True, amax=True, in_amax=True, in_ld=56, in_off=4, flags=_NSP),
+    'x3_t2_gemm_pro': _c('conv_x3_kernel<2, 2, 2, 2, false, true>', 'conv_x3_kernel<2, 2, 2, 2, false, true, false, true, false, false>', X_, N=2, H=384, W=1, Cin=48,
+                         Cout=96, k=1, split_k=1, pro=True, pro_act=L.PRO_SWISH, stats=True, flags=_NSP),
+    'x3_t2_gather': _c('conv_x3_kernel<2, 2, 2, 2, true, false>', 'conv_x3_kernel<2, 2, 2, 2, true, false, false, true, false, false>', X_, N=1, H=32, W=48, Cin=16,
+                       Cout=96, stride=2, split_k=1, stats=True, res_ld=100, flags=_NSP),
+    'x3_t2_gather_pro': _c('conv_x3_kernel<2, 2, 2, 2, false, false>', 'conv_x3_kernel<2, 2, 2, 2, false, false, false, true, false, false>', X_, N=1, H=32, W=48,
+                           Cin=16, Cout=128, stride=2, split_k=1, pro=True, pro_act=L.PRO_RELU, stats=True, act=L.ACT_LRELU02, flags=_NSP),
+    'x3_t2_stats_replica': _c('conv_x3_kernel<2, 2, 2, 2, true, false>',
+                              'conv_x3_kernel<2, 2, 1, 1, true, false, false, true, false, false> + conv_x3_gather_stats_replica_kernel', X_, N=3, H=32, W=48,
+                              Cin=16, Cout=96, stride=2, split_k=1, stats=True, amax=True, in_amax=True),
+    # ---- ... and the one form that cannot be small: more than 262144 output rows on the 64 x 64 tile take the shallow pipeline
+    'x3_gather_shallow': _c('conv_x3_kernel<2, 2, 1, 1, true, false>', 'conv_x3_kernel<2, 2, 1, 1, true, false, false, false, false, false>', X_, N=1, H=1026, W=1026,
+                            Cin=16, Cout=48, stride=2, in_amax=True),
+    # ---- the single-fp16 forms of conv_x3_kernel: im2col and (CONV_X1_GEMM) the 1x1 GEMM, on both tiles
+    'x1_im2col': _c('conv_x3_kernel<2, 2, 1, 1, true, 0, 0, 1, 0, 1>', 'conv_x3_kernel<2, 2, 1, 1, true, false, false, true, false, true>', X1_, N=3, H=16, W=16,
+                    Cin=32, Cout=64, stride=2, split_k=1, in_amax=True, amax=True, stats=True),
+    'x1_gemm': _c('conv_x3_kernel<2, 2, 1, 1, true, 1, 0, 1, 0, 1>', 'conv_x3_kernel<2, 2, 1, 1, true, true, false, true, false, true>', X1_, N=1, H=100, W=1, Cin=64,
+                  Cout=48, k=1, split_k=1, in_ld=72, in_off=4, out_ld=56, out_off=4, res_ld=52, act=L.ACT_LRELU01, flags=L.CONV_X1_GEMM),
+    'x1_t2_im2col': _c('conv_x3_kernel<2, 2, 2, 2, true, 0, 0, 1, 0, 1>', 'conv_x3_kernel<2, 2, 2, 2, true, false, false, true, false, true>', X1_, N=1, H=32, W=48,
+                       Cin=32, Cout=96, stride=2, split_k=1, stats=True, flags=_NSP),
+    'x1_t2_gemm': _c('conv_x3_kernel<2, 2, 2, 2, true, 1, 0, 1, 0, 1>', 'conv_x3_kernel<2, 2, 2, 2, true, true, false, true, false, true>', X1_, N=2, H=384, W=1,
+                     Cin=64, Cout=96, k=1, split_k=1, stats=True, amax=True, in_amax=True, flags=L.CONV_X1_GEMM | _NSP),
+})
 
 
 class _Geom:
@@ -142,7 +335,7 @@ class _Geom:
     def __init__(self, kw):
         g = dict(k=3, stride=1, in_off=0, out_off=0, res_ld=0, aux=False, pro=False, pro_act=L.PRO_NONE, act=L.ACT_NONE, split_k=0,
                  stats=False, amax=False, in_amax=False, in2_cin1=0, reflect=False, upsample=0, in_bf16=False, out_bf16=False,
-                 bk256=False, ln=False, flags=0, launch=True, pro_amp=0.2, bias_amp=1.0)
+                 bk256=False, ln=False, flags=0, launch=True, pro_amp=0.2, bias_amp=1.0, w_amp=0.05, w_peak=1, w_floor=0.0, x_amp=2.0, amax_stale=False)
         g.update(kw)
         self.__dict__.update(g)
         k = self.k
@@ -154,7 +347,8 @@ class _Geom:
         self.cin1 = self.in2_cin1 if self.in2_cin1 else self.Cin           # channels read from `in`
         self.in_ld = g.get('in_ld', self.cin1)
         self.out_ld = g.get('out_ld', self.Cout)
-        self.x3 = self.mma == L.MMA_X3 and self.Cin % 16 == 0
+        self.x1 = self.mma == L.MMA_X1                                     # weight_x3 is the hi-only fp16 twin
+        self.x3 = self.mma in (L.MMA_X3, L.MMA_X1) and self.Cin % 16 == 0  # the call brings weight_x3
 
 
 def _conv_args(g, t):
@@ -169,17 +363,14 @@ def _conv_args(g, t):
         epi_act=g.act, aux_w=AUX_W, split_k=g.split_k, dtype=L.BF16 if g.in_bf16 else L.F32, mma=g.mma, weight_bf16=p('wb'),
         stats_out=p('stats'), stats_P=t.get('stats_P', 0), bk256=int(g.bk256), out_dtype=L.BF16 if g.out_bf16 else L.F32,
         weight_x3=p('wx3'), x3_acc_scale=float(t.get('acc_scale', 1.0)), x3_in_amax=p('in_amax'), x3_out_amax=p('amax'),
-        x3_out_amax_zeroed=1 if g.amax else 0, in2=p('x2'), in2_cin1=g.in2_cin1, pad_mode=L.PAD_REFLECT if g.reflect else L.PAD_ZERO,
+        x3_out_amax_zeroed=1 if g.amax and not g.amax_stale else 0, in2=p('x2'), in2_cin1=g.in2_cin1, pad_mode=L.PAD_REFLECT if g.reflect else L.PAD_ZERO,
         ln_gamma=p('ln_gamma'), ln_beta=p('ln_beta'), ln_eps=LN_EPS if g.ln else 0.0, flags=g.flags, plan_ref_images=0)
     return a
 
 
-def conv_case_plan(name, kw=None):
-    """keep_conv2d_plan of a table case without a GPU: pointers only contribute their alignment, so every tensor gets the
-    address it will have modulo 16 (allocations are 16-byte aligned, slices start ``off`` elements in).  ``kw``: a variant of the
-    case's geometry (the exact-f32 twin of an x3 case, tests/test_gpu_case_values.py) instead of the table's own."""
-    expect, kw0 = CONV_CASES[name]
-    g = _Geom(kw0 if kw is None else kw)
+def _fake_tensors(g):
+    """name -> the address modulo 16 every tensor of geometry ``g`` will have (allocations are 16-byte aligned, slices start ``off``
+    elements in): all the host-only plan queries look at."""
     base = 0x10000
     isz = 2 if g.in_bf16 else 4
     t = {'x': base + g.in_off * isz, 'w': base, 'bias': base, 'out': base + g.out_off * (2 if g.out_bf16 else 4)}
@@ -201,12 +392,36 @@ def conv_case_plan(name, kw=None):
         t['ln_gamma'] = t['ln_beta'] = base
     if g.split_k > 1:
         t['ws'] = base
-    return expect, g, L.conv2d_plan(_conv_args(g, t))
+    return t
+
+
+def conv_case_plan(name, kw=None):
+    """keep_conv2d_plan of a table case without a GPU: pointers only contribute their alignment.  ``kw``: a variant of the
+    case's geometry (the exact-f32 twin of an x3 case, tests/test_gpu_case_values.py) instead of the table's own."""
+    expect, _, kw0 = CONV_CASES[name]
+    g = _Geom(kw0 if kw is None else kw)
+    return expect, g, L.conv2d_plan(_conv_args(g, _fake_tensors(g)))
+
+
+def conv_case_launched(name):
+    """keep_conv2d_launch_plan of a table case without a GPU, for the arguments the tests launch: the plan's split-K with its workspace,
+    the statistics partials and amax slots the case asks for."""
+    _, g, plan = conv_case_plan(name)
+    t = _fake_tensors(g)
+    if plan.split_k > 1:
+        t['ws'] = 0x10000
+    if g.stats:
+        t['stats'], t['stats_P'] = 0x10000, plan.stats_P
+    if g.amax:
+        t['amax'] = 0x10000 + 12
+    a = _conv_args(g, t)
+    a.split_k = plan.split_k
+    return L.conv2d_launch_plan(a)
 
 
 def conv_case_x(name, g):
     """The input payload of case ``name`` (channels [0, cin1) of `in`)."""
-    return rnd(name + 'x', (g.N, g.H, g.W, g.cin1), 2.0) + 0.3
+    return rnd(name + 'x', (g.N, g.H, g.W, g.cin1), g.x_amp) + 0.3
 
 
 def _conv_regions(name, kw=None, x=None):
@@ -218,7 +433,9 @@ def _conv_regions(name, kw=None, x=None):
     idt = BF16 if g.in_bf16 else F32
     N, Cin, Cout = g.N, g.Cin, g.Cout
     x = conv_case_x(name, g) if x is None else x
-    w = rnd(name + 'w', (Cout, g.k, g.k, Cin), 0.05)
+    w = rnd(name + 'w', (Cout, g.k, g.k, Cin), g.w_amp)
+    if g.w_peak > 1:      # every w_peak-th input channel at full amplitude, the others at 1 / w_peak of it: a sum of few dominant terms
+        w = w * torch.where(torch.arange(Cin) % g.w_peak == 0, 1.0, g.w_floor or 1.0 / g.w_peak)
     R = [FP.single('x', x.to(idt), ld=g.in_ld, off=g.in_off, tile_bytes=tb), FP.single('w', w.reshape(Cout, -1), tile_bytes=tb),
          FP.single('bias', rnd(name + 'b', (1, Cout)) * g.bias_amp, tile_bytes=tb),
          FP.output('out', (N * g.Ho * g.Wo, Cout), BF16 if g.out_bf16 else F32, ld=g.out_ld, off=g.out_off, tile_bytes=tb)]
@@ -235,11 +452,15 @@ def _conv_regions(name, kw=None, x=None):
     if g.x3:
         wsrc = ops.up2_phase_weights(w) if g.upsample == L.UPSAMPLE_X2_PHASES else w
         sc = ops.x3_scale_for(float(wsrc.abs().max()))
-        wx3 = ops.split_x3(wsrc.reshape(-1, Cin), sc)
+        wx3 = (wsrc.reshape(-1, Cin) * sc).to(torch.float16).view(torch.int16) if g.x1 else ops.split_x3(wsrc.reshape(-1, Cin), sc)
         R.append(FP.single('wx3', wx3.reshape(wx3.shape[0], -1), tile_bytes=tb))
         extra['acc_scale'] = 1.0 / sc
     if g.in_amax:      # (any upper bound of max |x| per image works: the true one, in [N] floats with nothing behind it)
-        R.append(FP.single('in_amax', x.reshape(N, -1).abs().amax(1).reshape(1, N), tile_bytes=tb))
+        xin = x.float()
+        if g.pro:      # x3_in_amax bounds what enters the product: the input behind the GroupNorm affine (an activation never raises it)
+            rows = {n: d for r in R for n, (_, _, d) in r.windows.items() if n in ('pro_scale', 'pro_shift')}
+            xin = xin * rows['pro_scale'].reshape(N, 1, 1, Cin) + rows['pro_shift'].reshape(N, 1, 1, Cin)
+        R.append(FP.single('in_amax', xin.reshape(N, -1).abs().amax(1).reshape(1, N), tile_bytes=tb))
     if g.in2_cin1:
         R.append(FP.single('x2', rnd(name + 'x2', (N * g.H * g.W, Cin - g.cin1)), tile_bytes=tb))
     if g.ln:
@@ -254,13 +475,14 @@ def _conv_regions(name, kw=None, x=None):
         extra['stats_P'] = plan.stats_P
     if g.amax:         # slots 3 .. 3 + N of an 11-slot arena the caller zeroed: the neighbours are other launches' maxima
         assert plan.out_amax_ok, (name, 'the case asks for x3_out_amax the plan cannot fill')
-        R.append(FP.Region(1, 11, {'amax': (3, N, torch.zeros(1, N))}, F32, 'rw', tb))
+        R.append(FP.Region(1, 11, {'amax': (3, N, torch.full((1, N), AMAX_STALE if g.amax_stale else 0.0))}, F32, 'rw', tb))
     return g, plan, R, extra
 
 
-@pytest.mark.parametrize('name', [n for n, (_, kw) in CONV_CASES.items() if kw.get('launch', True)])
+@pytest.mark.parametrize('name', [n for n, (_, _, kw) in CONV_CASES.items() if kw.get('launch', True)])
 def test_conv2d_footprint(name):
     g, plan, regions, extra = _conv_regions(name)
+    launched = CONV_CASES[name][1]
 
     def launch(t):
         a = _conv_args(g, {**t, **extra})
@@ -268,6 +490,7 @@ def test_conv2d_footprint(name):
         sig = (pl.kernel, pl.split_k, pl.workspace_bytes, pl.stats_P, pl.out_amax_ok)
         assert sig == (plan.kernel, plan.split_k, plan.workspace_bytes, plan.stats_P, plan.out_amax_ok), (name, sig)
         a.split_k = pl.split_k
+        assert L.conv2d_launch_plan(a) == launched, (name, L.conv2d_launch_plan(a), launched)      # of the very arguments launched below
         L.conv2d_launch(a)
         return sig
 

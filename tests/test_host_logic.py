@@ -916,7 +916,7 @@ def test_footprint_conv_table_reaches_every_kernel_family():
     declared = {_family(f) for f in re.findall(r'snprintf\(pl\.kernel, sizeof\(pl\.kernel\), "([^"]+)"', src)}
     assert len(declared) >= 14, declared
     reached, variants, auto_split = set(), set(), []
-    for name, (expect, kw) in T.CONV_CASES.items():
+    for name, (expect, _, kw) in T.CONV_CASES.items():
         _, g, plan = T.conv_case_plan(name)
         got = plan.kernel.decode()
         assert got == expect, (name, got, expect)
@@ -940,6 +940,143 @@ def test_footprint_conv_table_reaches_every_kernel_family():
               'conv_bf16_kernel<2, 2, 2, 2, 64, 1, true>'):
         assert v in variants, v
     assert auto_split, 'no case where the library itself chooses split-K'
+
+
+# ------------------------------------------------------------------------------------------------ keep_conv2d: the table is complete
+# launched instantiations that no table case reaches (must stay empty; only what no argument struct reaches may ever be listed, with the
+# condition quoted)
+UNREACHABLE_CONV_KERNELS = set()
+# instantiations the launch macros COMPILE that no argument struct can reach, each with the condition that keeps it away
+COMPILED_BUT_UNREACHABLE = {
+    # keep_conv.hip plan_bf16: `if (p.in_bf16 && !g.no_pro) { pl.path = PATH_NEEDS_PRENORM; ...` comes before PATH_HALO_BF16_V1, whose only
+    # reason is a prologue (`pl.path = g.no_pro ? PATH_HALO_BF16 : PATH_HALO_BF16_V1`): the first halo kernel never sees a bf16 input
+    'conv3x3_halo_kernel<true, 16>', 'conv3x3_halo_kernel<true, 32>',
+    # keep_gemm_x3l.hip keep_gemm_x3l_ok: `!a->pro_scale && a->pro_act == KEEP_PRO_NONE` -- FORM_GEMM_LAT is planned with plain == true only,
+    # so neither the latency kernel nor the K-slice arm of KEEP_LAUNCH_GX (`p.kslice_steps > 0` without `plain`) runs its prologue form
+    'gemm_x3l_kernel<4, 1, false>', 'gemm_x3l_kernel<8, 1, false>',
+    'conv_x3_kernel<2, 2, 1, 1, false, true, true, true, false, false>', 'conv_x3_kernel<2, 2, 2, 2, false, true, true, true, false, false>',
+    # keep_gemm_x3l.hip keep_conv2d_x3_gemm_lat: `tiles.tile = 1;` -- p.kslice_steps is set on the 64 x 64 tile alone, and KEEP_LAUNCH_GX's
+    # `p.kslice_steps == 4 && plain && C * D == 1` arm is instantiated for C * D == 4 too (there it is the plain K-slice form again)
+    'conv_x3_kernel<2, 2, 2, 2, true, true, true, true, false, false>',
+    # keep_conv_x3.hip KEEP_LAUNCH_GX: `plain && C * D == 1 && M > 262144` is false at run time on the 128 x 128 tile, whose macro expansion
+    # still instantiates the shallow pipeline
+    'conv_x3_kernel<2, 2, 2, 2, true, false, false, false, false, false>',
+}
+# KEEP_CONV_LAUNCH sites per source: a new arm of a launch macro changes a count and must come with its cases
+CONV_LAUNCH_SITES = {'keep_conv.hip': 25, 'keep_conv_x3.hip': 20, 'keep_conv_x3s.hip': 5, 'keep_conv_x3p.hip': 9, 'keep_gemm_x3l.hip': 2}
+CONV_FAMILIES = {      # convolution instantiations per kernel template that a launch can take
+    'conv3x3_c3_kernel': 1, 'conv3x3_c3_x3_kernel': 1, 'conv3x3_cout4_kernel': 1, 'conv3x3_halo3_kernel': 8, 'conv3x3_halo_f32_kernel': 6,
+    'conv3x3_halo_kernel': 2, 'conv3x3_halo_x3_kernel': 19, 'conv3x3_halo_x3s_act_kernel': 48, 'conv3x3_halo_x3s_kernel': 8, 'conv3x3_up2_x1s_kernel': 1,
+    'conv3x3_up2_x3s_kernel': 1, 'conv3x3_x3p_kernel': 16, 'conv3x3_x3q_kernel': 15, 'conv_bf16_kernel': 6, 'conv_f32_kernel': 5, 'conv_x3_kernel': 16,
+    'gemm_x3l_kernel': 2,
+}
+
+
+def test_conv_table_reaches_every_instantiation():
+    """tests/test_gpu_footprint.py's convolution table against keep_conv2d_launch_plan (host C: keep_conv2d's own dispatch code with every
+    launch replaced by the launched kernel's name), as the attention table is held against keep_attention_plan below.
+
+    Universe (tests/conv_universe.py: universe): the distinct strings the library answers over every mma (KEEP_MMA_X1 with no, each and all
+    of its opt-in bits) x input / output dtype x k {1, 3, 7} x stride {1, 2} x every pro_act with and without pro_scale x the seven epi_act x
+    {no residual, residual, residual + aux} x in2 x LayerNorm x {zero, reflect} padding x upsample {0, 1, x2 phases} x requested split_k
+    {0 .. 4} x statistics x amax slots {none, zeroed, stale} x N {1, 3, 48} x maps {8x32, 16x16, 16x64, 64x64, 5x7, 64x128, 128x128,
+    1026x1026 (stride 2: more than 262144 rows)} x Cin {3 .. 2048} x Cout {3 .. 128} x {aligned, out_ld off, pointers off} x {no flag, each
+    KEEP_CONV_* selection flag} x bk256, as the union of full products over the axes one launcher reads together; refused points are
+    skipped.  A launched string is `[zero_u32_kernel + ] convolution [+ split-K reducer | + statistics replica]`; the universe of
+    CONVOLUTION instantiations is pinned at 156 (per template: CONV_FAMILIES).
+    Census (conv_universe.census): the kernel handles in the built library's symbol table, restricted to the __global__ names of the five
+    convolution sources -- an answer that does not go through keep_conv2d_launch_plan.  universe - census is empty; census - universe is
+    COMPILED_BUT_UNREACHABLE, 8 instantiations, each with the condition that keeps every argument struct away from it.
+    Reach: the launched strings of CONV_CASES, each asked for the very arguments the GPU tests launch, equal the expectation the table
+    carries, and their convolutions are exactly the universe -- UNREACHABLE_CONV_KERNELS is empty -- and so are the follow-up kernels and
+    the zero-fill.  Every family keeps the table's awkwardness where its kernels admit it: a strided input slice, a strided output,
+    res_ld != Cout, N = 3 with per-image maxima, statistics."""
+    import abi_ref as A
+    import conv_universe as U
+    import test_gpu_footprint as T
+    found, points, refused = U.universe()
+    assert points > 500000 and refused > 0, (points, refused)
+    universe = {U.convolution(s) for s in found}
+    by_template = {}
+    for k in universe:
+        by_template[k.split('<')[0]] = by_template.get(k.split('<')[0], 0) + 1
+    assert by_template == CONV_FAMILIES and len(universe) == 156, by_template
+    pieces = {p for s in found for p in s.split(' + ')}
+    assert pieces - universe == set(U.FOLLOW_UPS) | {'zero_u32_kernel'}, sorted(pieces - universe)
+    for s in found:      # the zero-fill comes first, at most one follow-up kernel comes last
+        parts = s.split(' + ')
+        assert 'zero_u32_kernel' not in parts[1:] and sum(p in U.FOLLOW_UPS for p in parts) <= 1 and not set(parts[:-1]) & set(U.FOLLOW_UPS), s
+
+    census = U.census()
+    assert U.launch_sites() == CONV_LAUNCH_SITES, U.launch_sites()
+    assert len(census) == 169, len(census)
+    assert pieces <= census, sorted(pieces - census)
+    assert census - pieces == COMPILED_BUT_UNREACHABLE and len(COMPILED_BUT_UNREACHABLE) == 8, (sorted(census - pieces - COMPILED_BUT_UNREACHABLE),
+                                                                                                sorted(COMPILED_BUT_UNREACHABLE - census))
+
+    rows = []                                   # (name, geometry, launched string) of every launched table case
+    for name, (_, expect, kw) in T.CONV_CASES.items():
+        if kw.get('launch', True):
+            got = T.conv_case_launched(name)
+            assert got == expect, (name, got, expect)
+            assert set(got.split(' + ')) <= pieces, (name, got)
+            rows.append((name, T._Geom(kw), got))
+    reached = {A.conv_kernel(s) for _, _, s in rows}
+    assert reached == universe - UNREACHABLE_CONV_KERNELS, (sorted(universe - reached), sorted(reached - universe))
+    assert not UNREACHABLE_CONV_KERNELS
+    assert {p for _, _, s in rows for p in s.split(' + ')} == pieces
+    by_family = {}
+    for name, g, s in rows:
+        by_family.setdefault(A.conv_kernel(s).split('<')[0], []).append(g)
+    has = lambda fam, pred: any(pred(g) for g in by_family[fam])  # noqa: E731
+    strided_in = lambda g: g.in_ld != g.cin1 and g.in_off  # noqa: E731
+    strided_out = lambda g: g.out_ld != g.Cout and g.out_off  # noqa: E731
+    res_ld = lambda g: g.res_ld and g.res_ld != g.Cout  # noqa: E731
+    n3_amax = lambda g: g.N == 3 and g.amax  # noqa: E731
+    everything = ('conv3x3_halo_x3s_kernel', 'conv3x3_halo_x3s_act_kernel', 'conv3x3_halo_x3_kernel', 'conv3x3_x3q_kernel', 'conv_x3_kernel')
+    for fam in everything:
+        for what, pred in (('strided input', strided_in), ('strided output', strided_out), ('res_ld', res_ld), ('N = 3 with amax', n3_amax),
+                           ('statistics', lambda g: g.stats)):
+            assert has(fam, pred), (fam, what)
+    for fam in ('conv3x3_x3p_kernel', 'conv3x3_halo_f32_kernel', 'conv3x3_halo3_kernel', 'gemm_x3l_kernel'):      # (no amax / statistics on a split or bf16 launch)
+        for what, pred in (('strided input', strided_in), ('strided output', strided_out), ('res_ld', res_ld), ('N = 3', lambda g: g.N == 3)):
+            assert has(fam, pred), (fam, what)
+
+
+def test_conv_launch_plan_query_is_host_c_and_follows_the_launch():
+    """keep_conv2d_launch_plan (include/keep_cv_hip.h): header, binding and library agree on the struct; a refusal is the launch's own, code
+    and text, and zeroes the answer; keep_conv2d_plan's family string stays what it was where the launch takes another instantiation."""
+    import test_gpu_footprint as T
+    from comfyui_keep_amd.engine import hiplib as L
+    header = open(os.path.join(ROOT, 'include', 'keep_cv_hip.h')).read()
+    assert [n for n, _ in L.ConvLaunchPlanOut._fields_] == _header_struct_fields(header, 'keep_conv2d_launch_plan_out')
+    assert ctypes.sizeof(L.ConvLaunchPlanOut) == 4 + 508
+    lib = L.load(check_device=False)
+    _, g, plan = T.conv_case_plan('x3q_small')
+    assert plan.kernel == b'conv3x3_halo_x3s_kernel' and T.conv_case_launched('x3q_small') == 'conv3x3_x3q_kernel<0, false, 0> + conv_stats_replica_kernel'
+    out = L.ConvLaunchPlanOut()
+    t = T._fake_tensors(g)
+
+    def refused(code, text, **over):
+        a = T._conv_args(g, {**t, **{k: v for k, v in over.items() if k in ('x', 'ws', 'stats', 'amax')}})
+        for k, v in over.items():
+            if k not in ('x', 'ws', 'stats', 'amax'):
+                setattr(a, k, v)
+        out.n_kernels = 7
+        assert lib.keep_conv2d_launch_plan(ctypes.byref(a), ctypes.byref(out)) == code, over
+        assert text in lib.keep_last_error() and lib.keep_last_error().startswith(b'keep_conv2d'), lib.keep_last_error()
+        assert out.n_kernels == 0 and out.kernels == b''
+    refused(L.EINVAL, b'struct_size', struct_size=8)
+    refused(L.EINVAL, b'null tensor pointer', x=None)
+    refused(L.EINVAL, b'split_k>1 requires a workspace', split_k=2)
+    refused(L.EINVAL, b'stats_P=', stats=0x10000, stats_P=5)
+    refused(L.EINVAL, b'bad mma', mma=9)
+    assert lib.keep_conv2d_launch_plan(None, ctypes.byref(out)) == L.EINVAL and lib.keep_conv2d_launch_plan(ctypes.byref(T._conv_args(g, t)), None) == L.EINVAL
+    with pytest.raises(L.KeepHipError, match='bad mma') as e:
+        a = T._conv_args(g, t)
+        a.mma = 9
+        L.conv2d_launch_plan(a)
+    assert e.value.code == L.EINVAL
 
 
 # ------------------------------------------------------------------------------------------------ keep_attention: the table is complete
@@ -1135,7 +1272,7 @@ def _conv_case_refs():
     """(name, kernel, geometry, plan, payloads, reference) of every launched convolution case of the footprint table."""
     import abi_ref as A
     import test_gpu_footprint as T
-    for name, (_, kw) in T.CONV_CASES.items():
+    for name, (_, _, kw) in T.CONV_CASES.items():
         if kw.get('launch', True):
             g, plan, regions, _ = T._conv_regions(name)
             t = _payloads(regions)
@@ -1168,6 +1305,9 @@ def test_abi_ref_restates_the_bindings_constants():
         assert getattr(A, n) == getattr(L, n), n
 
 
+CONV_CLASS_COUNTS = {'f32': 22, 'x3': 111, 'x1': 35, 'bf16': 22, 'plan-only': 1}      # table cases per tolerance class
+
+
 def test_case_value_references_refuse_unknown_keys_and_classify_every_case():
     """conv2d_ref / attention_ref raise on a key they do not know (a key added to the table later cannot be silently ignored); every
     table case maps to exactly one tolerance class through the kernel name its plan reports, a family nobody classified raises, and
@@ -1184,17 +1324,23 @@ def test_case_value_references_refuse_unknown_keys_and_classify_every_case():
     with pytest.raises(KeyError):
         A.conv_class('conv_fp8_kernel<2, 2>')
     classes = {}
-    for name, (expect, kw) in T.CONV_CASES.items():
+    for name, (expect, _, kw) in T.CONV_CASES.items():
         _, g, plan = T.conv_case_plan(name)
         klass = A.conv_class(plan.kernel.decode())
         assert (klass == 'plan-only') == (not g.launch), name
+        if g.launch:      # the class is the launched instantiation's; the family string of the plan says the same
+            assert A.conv_class(T.CONV_CASES[name][1]) == klass == A.conv_class(T.conv_case_launched(name)), name
         classes.setdefault(klass, []).append(name)
         if klass == 'x3':
             _, _, twin = T.conv_case_plan(name, A.conv_twin_kw(kw))
             assert A.conv_class(twin.kernel.decode()) == 'f32', (name, twin.kernel.decode())
+        elif klass == 'x1':
+            assert g.mma == A.MMA_X1 and A.X1_TOL == 2.0 ** -10 + 2e-6, name
         elif klass != 'plan-only':
             assert A.conv_tol(klass, g) in (2e-4, 2e-5, 2e-3, 2e-5 + 2.0 ** -8), name
-    assert {k_: len(v) for k_, v in classes.items()} == {'f32': 16, 'x3': 26, 'bf16': 13, 'plan-only': 1}, classes
+    assert {k_: len(v) for k_, v in classes.items()} == CONV_CLASS_COUNTS, {k_: len(v) for k_, v in classes.items()}
+    for k_ in COMPILED_BUT_UNREACHABLE:      # (no instantiation the library holds is unclassified)
+        assert A.conv_class(k_) in ('x3', 'bf16'), k_
     # 'f32_t2_x3_fallback' asks for x3 and runs on an f32 kernel: the class follows the kernel, not the request
     assert 'f32_t2_x3_fallback' in classes['f32'] and 'cout4_x3' in classes['f32']
     assert sorted({A.attn_class(c) for c in T.ATTN_CASES}) == ['bf16', 'f32', 'x3']
@@ -1208,10 +1354,10 @@ def test_case_value_references_feel_every_optional_input():
     import abi_ref as A
     seen = set()
     for name, kernel, g, plan, t, ref in _conv_case_refs():
-        tol, sc = A.conv_tol(A.conv_class(kernel), g), max(1.0, float(ref['out'].abs().max()))
+        lim = A.conv_bound(A.conv_class(kernel), g, ref)      # (per element; uniform tolerance x scale in every class but x1)
         for what, g2, t2 in A.conv_removals(g, t):
-            d = float((A.conv2d_ref(g2, t2)['out'] - ref['out']).abs().max())
-            assert d >= A.SENSITIVITY * tol * sc, (name, what, d / sc, tol)
+            d = float(((A.conv2d_ref(g2, t2)['out'] - ref['out']).abs() / lim).max())
+            assert d >= A.SENSITIVITY, (name, what, d)
             seen.add(what)
     assert seen == {'bias', 'pro_scale', 'pro_shift', 'per-image prologue rows', 'prologue activation', 'epilogue activation', 'residual', 'aux',
                     'reflect', 'in2', 'ln_gamma', 'ln_beta'}, seen
@@ -1223,6 +1369,24 @@ def test_case_value_references_feel_every_optional_input():
             assert d >= A.SENSITIVITY * tol * sc, (c['name'], what, d / sc, tol)
             seen.add(what)
     assert seen == set(A.ATTN_REMOVALS), seen
+
+
+def test_case_value_judge_tells_neighbouring_instantiations_apart():
+    """The risk of a dispatch of 156 instantiations is the NEIGHBOURING one: a wrong arm of a launch macro picks another EACT, another
+    prologue form, the other padding.  For every launched case the float64 reference, computed as such a neighbour would compute it, misses
+    the case's tolerance by at least abi_ref.SENSITIVITY: with any other epi_act of the seven; with any other pro_act, and with the affine
+    dropped; with the activation applied after the residual instead of before it; with zero padding in place of reflection padding and
+    the other way round.  A condition on the table's inputs (bias_amp, pro_amp, x_amp, w_amp, w_peak), checked before a GPU is touched."""
+    import abi_ref as A
+    seen, n = set(), 0
+    for name, kernel, g, plan, t, ref in _conv_case_refs():
+        lim = A.conv_bound(A.conv_class(kernel), g, ref)
+        for what, out in A.conv_neighbours(g, t, ref):
+            d = float(((out - ref['out']).abs() / lim).max())
+            assert d >= A.SENSITIVITY, (name, what, d)
+            seen.add(what.split()[0])
+            n += 1
+    assert seen == {'epi_act', 'pro_act', 'affine', 'activation', 'zero', 'reflection'} and n >= 1700, (seen, n)
 
 
 def _fake_device_conv(g, P, out64, stats_from=None):
@@ -1251,7 +1415,7 @@ def test_case_value_judge_bites(capsys):
         twin = ref['out'].float() if klass == 'x3' else None
         A.judge_conv(name, kernel, g, _fake_device_conv(g, P, ref['out']), ref, twin, P)
         moved = ref['out'].clone()
-        moved.view(-1)[moved.numel() // 2] += 10 * A.conv_tol(klass, g) * sc
+        moved.view(-1)[moved.numel() // 2] += 10 * float(A.conv_bound(klass, g, ref).view(-1)[moved.numel() // 2])
         wrong = [('one element', _fake_device_conv(g, P, moved))]
         removed = {what: A.conv2d_ref(g2, t2)['out'] for what, g2, t2 in A.conv_removals(g, t)}
         wrong += [(what, _fake_device_conv(g, P, o)) for what, o in removed.items()]

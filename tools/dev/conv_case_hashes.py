@@ -101,7 +101,7 @@ def sha(t):
 
 def main():
     rows = {}
-    for name, (_, kw) in T.CONV_CASES.items():
+    for name, (_, _, kw) in T.CONV_CASES.items():
         if not kw.get('launch', True): continue
         g, plan, regions, extra = T._conv_regions(name)
         for r in regions: r.compare = True      # (the split-K workspace too)
