@@ -145,6 +145,8 @@ _CV_SIGNATURES = {
     'keep_warp_affine_batch_scatter_u8': [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp],
     'keep_attention_plan': [C.POINTER(AttnArgs), C.POINTER(AttnPlanOut)],  # (host-only: no stream argument)
     'keep_conv2d_launch_plan': [C.POINTER(ConvArgs), C.POINTER(ConvLaunchPlanOut)],  # (host-only: no stream argument)
+    'keep_gm_ffn_x1_plan': [_i32, _i32, _i32, _i32, _i32],                 # (host-only: no stream argument)
+    'keep_gm_ffn_x1': [_vp, _vp, _vp, _f32, _vp, _f32, _vp, _vp, _f32, _vp, _i64, _i32, _i32, _i32, _vp],
 }
 CV_EXPORTED_SYMBOLS = ['keep_cv_abi_version'] + list(_CV_SIGNATURES)
 
@@ -287,6 +289,15 @@ def attention_x1_plan(**kw):
     if need < 0:
         raise KeepHipError(f"keep_attention plan failed (code -2): {_lib.keep_last_error().decode()}", code=EUNSUP)
     return need
+
+
+def gm_ffn_x1_plan(C_, hidden, io_misalign=0, weight_misalign=0, ln_misalign=0):
+    """keep_gm_ffn_x1_plan: the library's answer to `the fused GMFlow FFN on single fp16 for this per-token shape?` -- True, or KeepHipError
+    with the library's code (``EUNSUP``: stay on keep_gm_ffn_x3) and reason.  The alignment classes are `address % 16` OR-ed over
+    src / msg / out, the weight twins, gamma / beta.  Needs no device."""
+    lib = load(check_device=False)
+    _check(lib.keep_gm_ffn_x1_plan(int(C_), int(hidden), int(io_misalign), int(weight_misalign), int(ln_misalign)), 'keep_gm_ffn_x1_plan')
+    return True
 
 
 def conv2d_launch(a):

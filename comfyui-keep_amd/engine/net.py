@@ -63,7 +63,13 @@ FLOW_PRECISION_ENV = 'KEEP_AMD_FLOW_PRECISION'
 # where the library admits them (KEEP_CONV_X1_UP2); needs an x3-grade base
 UPSAMPLE_PRECISIONS = ('x3', 'f16')
 UPSAMPLE_PRECISION_ENV = 'KEEP_AMD_UPSAMPLE_PRECISION'
-KNOB_OFF = {'flow_precision': 'x3', 'upsample_precision': 'x3'}      # the opt-in knobs beside `precision`, each with its `as if it did not exist`
+# KEEP_AMD_FLOW_FFN_PRECISION: the knob of GMFlow's fused feed-forward block alone (keep_gm_ffn_x3, 12 launches per pass), independent of
+# KEEP_AMD_PRECISION and of KEEP_AMD_FLOW_PRECISION (whose 'f16' leaves it on x3).  'x3' (default): as if the knob did not exist.  'f16': the
+# block runs as keep_gm_ffn_x1 on single-fp16 operands where the library admits it; needs an x3-grade base
+FLOW_FFN_PRECISIONS = ('x3', 'f16')
+FLOW_FFN_PRECISION_ENV = 'KEEP_AMD_FLOW_FFN_PRECISION'
+# the opt-in knobs beside `precision`, each with its `as if it did not exist`
+KNOB_OFF = {'flow_precision': 'x3', 'upsample_precision': 'x3', 'flow_ffn_precision': 'x3'}
 
 
 ROCTX = os.environ.get('KEEP_AMD_ROCTX', '0') == '1'      # per-stage roctx ranges (rocprofv3 --marker-trace / --kernel-trace timelines)
@@ -153,6 +159,8 @@ class KeepNet:
         self.set_flow_precision(os.environ.get(FLOW_PRECISION_ENV) or 'x3')
         self.upsample_precision = 'x3'
         self.set_upsample_precision(os.environ.get(UPSAMPLE_PRECISION_ENV) or 'x3')
+        self.flow_ffn_precision = 'x3'
+        self.set_flow_ffn_precision(os.environ.get(FLOW_FFN_PRECISION_ENV) or 'x3')
 
     # ------------------------------------------------------------------ nn.Module-like surface
     def load_state_dict(self, state_dict, strict=True):
@@ -209,8 +217,9 @@ class KeepNet:
         flow-propagation q / k projections go through a second ``Ops`` that substitutes single-fp16 operands wherever the library's plan
         admits them: un-split 3x3 / im2col / 1x1 GEMM convolutions with Cin % 32 == 0 and the 128-wide window attention.  The global
         correlation and flow-propagation attentions (probabilities times pixel coordinates), the convex upsampler, the fused FFN
-        (``keep_gm_ffn_x3`` has no single-fp16 form), the LayerNorm-epilogue GEMMs, the 16-channel stem and split plans stay x3.  An
-        opt-in speed mode outside the 1e-3 parity tolerance, never a default."""
+        (its single-fp16 form ``keep_gm_ffn_x1`` has a knob of its own, ``set_flow_ffn_precision``: this one leaves the block on
+        ``keep_gm_ffn_x3``), the LayerNorm-epilogue GEMMs, the 16-channel stem and split plans stay x3.  An opt-in speed mode outside the
+        1e-3 parity tolerance, never a default."""
         if precision not in FLOW_PRECISIONS:
             raise ValueError(f"{FLOW_PRECISION_ENV} (set_flow_precision) must be one of {FLOW_PRECISIONS}, got {precision!r}")
         self.flow_precision = precision
@@ -227,6 +236,37 @@ class KeepNet:
             raise ValueError(f"{UPSAMPLE_PRECISION_ENV} (set_upsample_precision) must be one of {UPSAMPLE_PRECISIONS}, got {precision!r}")
         self.upsample_precision = precision
         return self
+
+    def set_flow_ffn_precision(self, precision):
+        """The knob of GMFlow's fused feed-forward block (``KEEP_AMD_FLOW_FFN_PRECISION``).  'x3' (default): as if the knob did not exist --
+        no plan query, no extra twin, the same launches.  'f16': on an 'x3' or 'f16' base (anything else raises when the policy is
+        activated), the 12 ``LayerNorm(W2 . gelu(W0 . cat[src | msg])) + src`` launches per pass run as ``keep_gm_ffn_x1`` -- operands
+        rounded once to fp16, one MFMA per product, GELU / LayerNorm / residual in fp32 -- wherever ``keep_gm_ffn_x1_plan`` admits the
+        shape.  Independent of ``set_flow_precision``.  An opt-in speed mode outside the 1e-3 parity tolerance, never a default
+        (DESIGN 4.7); batch invariance and the fp16-range fallback are x3's."""
+        if precision not in FLOW_FFN_PRECISIONS:
+            raise ValueError(f"{FLOW_FFN_PRECISION_ENV} (set_flow_ffn_precision) must be one of {FLOW_FFN_PRECISIONS}, got {precision!r}")
+        self.flow_ffn_precision = precision
+        return self
+
+    def flow_ffn_names(self):
+        """(mlp.0, mlp.2) weight names of the GMFlow layers the fused FFN runs: those that get hi-only twins under the FFN knob."""
+        idx = self._index or {}
+        return [(n[:-len('2.weight')] + '0.weight', n) for n, (_, shape) in idx.items()
+                if n.startswith('flownet.') and n.endswith('.mlp.2.weight') and shape[0] == 128 and n[:-len('2.weight')] + '0.weight' in idx]
+
+    def _activate_flow_ffn_precision(self):
+        """``self.o.ffn_x1`` follows the knob; the hi-only FFN twins are built here, never inside a stream capture."""
+        if self.flow_ffn_precision != 'f16':
+            self.o.ffn_x1 = False
+            return
+        if self.precision not in X3_GRADE:
+            raise ValueError(f"{FLOW_FFN_PRECISION_ENV}=f16 needs the base precision 'x3' or 'f16', not {self.precision!r}")
+        if FUSED_GM_FFN_X3 and self.w is not None:
+            for n0, n2 in self.flow_ffn_names():
+                self.o.ffn_w0_x1_twin(self.w[n0])
+                self.o.ffn_w2_x1_twin(self.w[n2])
+        self.o.ffn_x1 = True
 
     def up2_x1_names(self):
         """Names of the Upsample convolution weights that get a hi-only phase twin: those whose source map (square, ``img_size`` / 2^levels
@@ -291,11 +331,13 @@ class KeepNet:
         n = int(self._dev_blob.numel()) if self._dev_blob is not None else (0 if self._blob is None else int(self._blob.size))
         on = precision in X3_GRADE
         up = 0 if self._index is None else sum(8 * int(np.prod(self._index[m][1])) for m in self.up2_x1_names())      # four phase kernels, 2 bytes per weight
+        ffn = 0 if self._index is None else sum(2 * int(np.prod(self._index[m][1])) for pair in self.flow_ffn_names() for m in pair)      # hi-only: 2 bytes per weight
         rows = (('bf16', precision == 'bf16', 2 * n, self._dev_blob16 is not None),
                 ('x3', on, 4 * n, self._dev_blobx3 is not None),
                 ('x1', precision == 'f16', 2 * n, self._dev_blobx1 is not None),      # hi-only: 2 bytes per blob element
                 ('flow', on and self.flow_precision == 'f16', 2 * n, self._dev_blobx1f is not None),      # likewise the flownet twin
-                ('up2', on and self.upsample_precision == 'f16', up, bool(self.o.up2_x1)))      # the hi-only phase twins of ``up2_x1_names``
+                ('up2', on and self.upsample_precision == 'f16', up, bool(self.o.up2_x1)),      # the hi-only phase twins of ``up2_x1_names``
+                ('ffn', on and self.flow_ffn_precision == 'f16', ffn, bool(self.o.ffn_x1)))      # the hi-only twins of ``flow_ffn_names``
         return {k: (b, built) for k, held, b, built in rows if held}
 
     def twin_bytes(self, precision=None):
@@ -325,6 +367,7 @@ class KeepNet:
         self._activate_base_precision()
         self._activate_flow_precision()
         self._activate_upsample_precision()
+        self._activate_flow_ffn_precision()
 
     def _activate_base_precision(self):
         if self.precision == 'bf16':
@@ -750,7 +793,7 @@ class KeepNet:
             m = ops.layernorm(self.of.linear(o, w[f'{p}.merge.weight'], bounded=True, n_img=n_img), n1[0], n1[1])
         if (self.o.mma == L.MMA_X3 and C == 128 and FUSED_GM_FFN_X3 and self.o.x3_twin(w[f'{p}.mlp.0.weight']) is not None):
             # mlp.0 -> GELU -> mlp.2 -> norm2 -> + src as ONE launch: the [M, 8C] intermediate (10 GB at 16 clips) stays in registers
-            return self.o.gm_ffn_x3(src, m, w[f'{p}.mlp.0.weight'], w[f'{p}.mlp.2.weight'], w[f'{p}.norm2.weight'], w[f'{p}.norm2.bias'], 1e-5)
+            return self.o.gm_ffn(src, m, w[f'{p}.mlp.0.weight'], w[f'{p}.mlp.2.weight'], w[f'{p}.norm2.weight'], w[f'{p}.norm2.bias'], 1e-5)
         if self.o.mma == L.MMA_BF16 and C == 128 and FUSED_GM_MLP:
             m2 = self.o.gm_mlp(src, m, w[f'{p}.mlp.0.weight'], w[f'{p}.mlp.2.weight'])      # [M,8C] never leaves the CU
         else:
@@ -943,7 +986,7 @@ class KeepNet:
         the host code between launches only computes shapes, so the replay is bit-identical to the eager run."""
         self.o.ensure_arena(self.device)
         key = (B, T, H, Wd, self.precision, self._dev_blob.data_ptr(), self.o.arena_generation, self.o.flags, self.o.attn_flags,
-               self.o.plan_ref_images, self.upsample_precision)
+               self.o.plan_ref_images, self.upsample_precision, self.flow_ffn_precision)
         if self.of is not self.o:
             self.of.ensure_arena(self.device)
             key += (self.flow_precision, self.of.arena_generation)

@@ -129,6 +129,11 @@ class Ops:
         # base's.  True: the up2 branch of conv() asks the library once per plan key (_route) and runs the call on the hi-only phase twin
         # (up2_x1_twin) where admitted -- KeepNet's KEEP_AMD_UPSAMPLE_PRECISION=f16
         self.up2_x1 = False
+        # single-fp16 fused GMFlow FFN (keep_gm_ffn_x1): off by default -- gm_ffn() is then gm_ffn_x3(), no plan query.  True: gm_ffn() asks the
+        # library once per token shape and alignment class (_route, keep_gm_ffn_x1_plan) and runs the block on the hi-only twins
+        # (ffn_w0_x1_twin / ffn_w2_x1_twin) where admitted -- KeepNet's KEEP_AMD_FLOW_FFN_PRECISION=f16
+        self.ffn_x1 = False
+        self._ffn_x1_route = {}      # (C, hidden, alignment classes) -> True | False
 
     def begin_forward(self, device):
         """Zero this forward's bookkeeping words with ONE fill launch: the status word (non-finite logits / tensors, see
@@ -157,7 +162,7 @@ class Ops:
         self._x3_table = ([a for a, _, _ in x3_scales], list(x3_scales)) if x3_scales else None
         self.mma = self.attn_mma = mma
         self.set_x1_twin()      # ('f16' re-attaches its twin after every policy change)
-        self._forget_routes(self._x1_route, self._up2_x1_route, self._attn_x1_route)
+        self._forget_routes(self._x1_route, self._up2_x1_route, self._attn_x1_route, self._ffn_x1_route)
         if blobx3 is not None and (blob32 is not self._up2_src[0] or blobx3 is not self._up2_src[1]):
             # phase kernels of the Upsample convolutions (up2_twin): derived from THESE blob objects -- a new upload, even one that lands
             # on the same addresses, starts from an empty cache; a policy switch on the same blobs keeps it (captured x3 graphs hold
@@ -286,6 +291,61 @@ class Ops:
             e0.record()
         L.call('keep_gm_ffn_x3', src, msg, self.x3_twin(w0), float(self.x3_scale_of(w0)), w2p, float(asc2), gamma, beta, float(eps), out,
                M, C, w0.shape[0], 1 if (self.flags & L.CONV_X3_EXACT_ACT) else 0)
+        if self.profile is not None:
+            self.profile[-1][4].record()
+        return out.view(src.shape)
+
+    def ffn_w0_x1_twin(self, w0):
+        """(hi-only fp16 twin, acc_scale) of ``w0`` [hidden, 2C] for ``keep_gm_ffn_x1``: fp16(w0 * 2^e) as plain row-major bit patterns with
+        the x3 twin's power of two (``x3_scale_of``) -- the numbers of the x3 twin's hi half.  Built once per weight tensor (outside any
+        stream capture: ``KeepNet._activate_precision``) and kept with the up2 twins for the lifetime of the blob."""
+        key = ('ffn_w0_x1', w0.data_ptr(), tuple(w0.shape))
+        tw = self._up2.get(key)
+        if tw is None:
+            asc = float(self.x3_scale_of(w0))
+            tw = self._up2[key] = ((w0.float() * (1.0 / asc)).to(torch.float16).view(torch.int16).view(-1), asc)
+        return tw
+
+    def ffn_w2_x1_twin(self, w2):
+        """(hi-only fp16 twin, acc_scale) of ``w2`` [C, hidden] for ``keep_gm_ffn_x1``: fp16(ffn_w2_perm(w2) * 2^e) as [C, hidden] bit
+        patterns with ``ffn_w2_twin``'s power of two -- the numbers of that twin's hi half.  Built and kept like ``ffn_w0_x1_twin``."""
+        key = ('ffn_w2_x1', w2.data_ptr(), tuple(w2.shape))
+        tw = self._up2.get(key)
+        if tw is None:
+            wp = ffn_w2_perm(w2)
+            sc = x3_scale_for(float(wp.abs().max()))
+            tw = self._up2[key] = ((wp * sc).to(torch.float16).view(torch.int16).view(-1), 1.0 / sc)
+        return tw
+
+    def gm_ffn(self, src, msg, w0, w2, gamma, beta, eps):
+        """The fused GMFlow FFN of the x3 policy under the substitution rule ``ffn_x1``.  Off (default): ``gm_ffn_x3``, nothing else.  On:
+        the library is asked once per (C, hidden, alignment classes) -- never M: a clip's route does not depend on its batch-mates -- whether
+        it has the single-fp16 form (_route, keep_gm_ffn_x1_plan); where it has, the block runs as ``keep_gm_ffn_x1`` on the hi-only twins
+        with the x3 twins' scales; KEEP_EUNSUP keeps the call on ``gm_ffn_x3``; any other failure raises."""
+        if not self.ffn_x1:
+            return self.gm_ffn_x3(src, msg, w0, w2, gamma, beta, eps)
+        C = src.shape[-1]
+        M = src.numel() // C
+        Hd = w0.shape[0]
+        out = empty((M, C), src)
+        w0x, asc0 = self.ffn_w0_x1_twin(w0)
+        w2x, asc2 = self.ffn_w2_x1_twin(w2)
+
+        def mis(*ts):
+            r = 0
+            for t in ts:
+                r |= t.data_ptr() % 16
+            return r
+        key = (C, Hd, mis(src, msg, out), mis(w0x, w2x), mis(gamma, beta))
+        if not self._route(self._ffn_x1_route, key, lambda: L.gm_ffn_x1_plan(*key)):
+            return self.gm_ffn_x3(src, msg, w0, w2, gamma, beta, eps)
+        if self.profile is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            self.profile.append(('gm_ffn_x1_kernel', 2.0 * M * (2 * C * Hd + Hd * C), 1, e0, e1,
+                                 3 * M * C * 4 + (2 * C * Hd + Hd * C) * 2, (M // 4096 if M % 4096 == 0 else 1, M, 1, 2 * C, C, 1, 1, 0, False)))
+            e0.record()
+        L.call('keep_gm_ffn_x1', src, msg, w0x, float(asc0), w2x, float(asc2), gamma, beta, float(eps), out,
+               M, C, Hd, 1 if (self.flags & L.CONV_X3_EXACT_ACT) else 0)
         if self.profile is not None:
             self.profile[-1][4].record()
         return out.view(src.shape)

@@ -139,6 +139,29 @@ typedef struct {
 } keep_conv2d_launch_plan_out;
 int32_t keep_conv2d_launch_plan(const keep_conv2d_args* a, keep_conv2d_launch_plan_out* out);
 
+/* ---- the GMFlow feed-forward block of keep_hip.h's fused x3 entry on SINGLE fp16 operands (opt-in speed form, outside the 1e-3 parity
+ * tolerance):
+ *
+ *     out = LayerNorm( W2 . gelu( W0 . cat[src | msg] ) ; gamma, beta, eps ) + src          src, msg, out [M, C] fp32,  C = 128
+ *
+ * cat[src | msg] is rounded once to fp16 (the conversion of the x3 `hi` half), every GELU output once more in front of the second product;
+ * one fp16 MFMA per product, fp32 accumulation; scale, GELU (exact_act != 0: erff, else the fast form), LayerNorm and + src in fp32 on the
+ * unrounded src.  The argument list is the x3 entry's; the weights are hi-only twins, ONE fp16 bit pattern per weight, with the x3
+ * twins' power-of-two scales (w0_acc_scale / w2_acc_scale = 2^-e):
+ *   w0_x1    [hidden][2C]   fp16(W0 * 2^e0), plain row-major
+ *   w2p_x1   [C][hidden]    fp16(W2p * 2^e2), W2p = W2 with every group of 16 hidden units in the order [0-3, 8-11, 4-7, 12-15]
+ * -- the numbers of the x3 twins' hi halves.  KEEP_EINVAL before anything is launched, the message naming the function: a null pointer,
+ * M <= 0, C != 128, hidden <= 0 or hidden % 32 != 0, a pointer that is not 16-byte aligned, weight tensors of 2 GB or more.
+ *
+ * keep_gm_ffn_x1_plan: HOST-only C (no device, no stream): does the library have the single-fp16 form for this per-token shape?  The
+ * alignment classes are `address % 16` OR-ed over the tensors of a class -- src / msg / out, the two weight twins, gamma / beta -- 0 when
+ * all are 16-byte aligned.  KEEP_OK, or KEEP_EUNSUP with the reason as the thread's last error message -- the caller stays on the x3 entry; KEEP_EINVAL
+ * for a non-positive C / hidden or a negative class.  M is no argument: the answer never depends on the token count. */
+int32_t keep_gm_ffn_x1_plan(int32_t C, int32_t hidden, int32_t io_misalign, int32_t weight_misalign, int32_t ln_misalign);
+int32_t keep_gm_ffn_x1(const float* src, const float* msg, const void* w0_x1, float w0_acc_scale, const void* w2p_x1, float w2_acc_scale,
+                       const float* ln_gamma, const float* ln_beta, float ln_eps, float* out, int64_t M, int32_t C, int32_t hidden,
+                       int32_t exact_act, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
