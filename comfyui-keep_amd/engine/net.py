@@ -107,6 +107,79 @@ class _FrameList:
         self.dtype = torch.uint8
 
 
+class ClipState:
+    """What ``KEEP.forward``'s recurrence hands from one frame to the next, for a batch of B clips after one of their frames (device
+    tensors, fp32): ``frame`` [B,3,H,W] the input frame as the net saw it (the seam pair of GMFlow), ``prev_out`` [B,H,W,3] the restored
+    frame (NHWC), ``cross_prev[s]`` [B,s,s,C] the CFA features of every size in ``cfa_list`` with ``cross_amax[s]`` [B], their per-image
+    max |.| (None where the policy carries none: the consumer probes, the same value).  ``KeepNet(x, carry=state)`` runs frame 0 of x as
+    the frame that follows; ``select`` / ``cat`` regroup clips between calls (``run_clips_u8(after=...)``)."""
+    __slots__ = ('frame', 'prev_out', 'cross_prev', 'cross_amax')
+
+    def __init__(self, frame, prev_out, cross_prev, cross_amax):
+        self.frame, self.prev_out, self.cross_prev, self.cross_amax = frame, prev_out, dict(cross_prev), dict(cross_amax)
+
+    @property
+    def batch(self):
+        return int(self.frame.shape[0])
+
+    def _map(self, fn):
+        return ClipState(fn(self.frame), fn(self.prev_out), {s: fn(v) for s, v in self.cross_prev.items()},
+                         {s: (None if v is None else fn(v)) for s, v in self.cross_amax.items()})
+
+    def select(self, rows):
+        """The state of the clips ``rows`` (a list of batch indices, or a slice), as tensors of its own."""
+        if isinstance(rows, slice):
+            return self._map(lambda t: t[rows].clone())
+        rows = [int(r) for r in rows]
+        if rows == list(range(rows[0], rows[0] + len(rows))):
+            return self._map(lambda t: t[rows[0]:rows[0] + len(rows)].clone())
+        return self._map(lambda t: torch.stack([t[r] for r in rows]))
+
+    @staticmethod
+    def cat(states):
+        states = list(states)
+        if len(states) == 1:
+            return states[0]
+        s0 = states[0]
+        amax = {}
+        for s in s0.cross_prev:      # a maximum only where every part has one (None: the consumer's probe finds the same value)
+            parts = [st.cross_amax.get(s) for st in states]
+            amax[s] = None if any(p is None for p in parts) else torch.cat(parts)
+        return ClipState(torch.cat([st.frame for st in states]), torch.cat([st.prev_out for st in states]),
+                         {s: torch.cat([st.cross_prev[s] for st in states]) for s in s0.cross_prev}, amax)
+
+
+def carry_schedule(keys, after, cap):
+    """The order in which clips with predecessors run: ``keys[j]`` the grouping key of clip j (its shape), ``after[j]`` the clip that
+    clip j continues or None, ``cap(key)`` the most clips of that key in one call -> [(key, carried, [clip indices])].
+
+    A clip is ready once its predecessor has run.  Ready clips are grouped by (key, carried) in index order, at most ``cap`` a group, and
+    of the ready groups the one whose first clip has the lowest index runs next -- clips leave roughly in list (= time) order.  Pure."""
+    n = len(keys)
+    succ = {}
+    for j, p in enumerate(after):
+        if p is None:
+            continue
+        if not (0 <= int(p) < n) or int(p) == j:
+            raise ValueError(f"after[{j}] = {p!r} names no other clip")
+        if int(p) in succ:
+            raise ValueError(f"clips {succ[int(p)]} and {j} both continue clip {p}")
+        succ[int(p)] = j
+    ready = sorted(j for j, p in enumerate(after) if p is None)
+    done, out = 0, []
+    while ready:
+        head = ready[0]
+        gk = (keys[head], after[head] is not None)
+        grp = [j for j in ready if (keys[j], after[j] is not None) == gk][:max(1, int(cap(keys[head])))]
+        out.append((keys[head], gk[1], grp))
+        done += len(grp)
+        taken = set(grp)
+        ready = sorted([j for j in ready if j not in taken] + [succ[j] for j in grp if j in succ])
+    if done != n:
+        raise ValueError("after: the predecessors form a cycle")
+    return out
+
+
 class KeepNet:
     def __init__(self, **arch):
         unknown = set(arch) - _KNOWN_KW
@@ -908,7 +981,14 @@ class KeepNet:
 
     # ------------------------------------------------------------------ KEEP.forward
     @torch.no_grad()
-    def __call__(self, x, need_upscale=False, force_indices=None, return_aux=False, force_flows=None, _defer_check=False):
+    def __call__(self, x, need_upscale=False, force_indices=None, return_aux=False, force_flows=None, _defer_check=False,
+                 carry=None, return_state=False, force_gains=None):
+        """``carry`` (a ``ClipState`` of these B clips' predecessors): frame 0 is restored as the frame that FOLLOWS the state -- warped
+        previous output over the seam flow, Kalman update with ``gains[:, 0]``, CFA against the carried features: the launches of an
+        interior frame -- instead of from the LQ encoder alone.  ``return_state``: the result is followed by the ``ClipState`` after the
+        last frame (last in the returned tuple).  A carried 1-frame clip runs as the reference's T = 2 duplicate (keep_processor.py:173-178), frame 0
+        kept, and hands on the state after frame 0.  ``force_gains`` [B,T,...]: a test hook like ``force_flows``, used instead of K3's.
+        With none of the three this is the call it always was: the same launches, the same bits."""
         if self.w is None:
             raise RuntimeError("KeepNet: weights are not on a device (load_state_dict + .to('cuda') first)")
         if x.dim() != 5 or x.shape[2] != 3:
@@ -926,6 +1006,8 @@ class KeepNet:
         B, T, _, H, Wd = x.shape
         if H % 32 or Wd % 32:
             raise ValueError("H and W must be multiples of 32")
+        if carry is not None or return_state or force_gains is not None:
+            return self._call_carried(x, B, T, H, Wd, force_indices, return_aux, force_flows, _defer_check, carry, return_state, force_gains)
         with torch.cuda.device(self.device):
             self._activate_precision()
             plain = force_indices is None and force_flows is None and not return_aux and self.o.profile is None
@@ -941,11 +1023,48 @@ class KeepNet:
             del res                                  # the x3 result goes back to the allocator before the f32 re-run
             return self._checked(None, x, B, T, H, Wd, force_indices, return_aux, force_flows, bits=bits)
 
+    def _call_carried(self, x, B, T, H, Wd, force_indices, return_aux, force_flows, _defer_check, carry, return_state, force_gains):
+        """``__call__`` with a state in and / or out (or forced gains): always the eager form -- a call that takes or returns a state is
+        never captured into a hipGraph -- and the same range check, re-run from the SAME incoming state.  The result is the tuple
+        (out[, aux][, state]), or out alone."""
+        if carry is not None:
+            if not isinstance(carry, ClipState) or carry.batch != B or tuple(carry.frame.shape[1:]) != (3, H, Wd):
+                raise ValueError(f"carry: expected the ClipState of {B} clip(s) of 3 x {H} x {Wd} frames")
+            if set(carry.cross_prev) != set(self.cfg['cfa_list']):
+                raise ValueError("carry: the state holds other CFA sizes than this net's cfa_list")
+        keep = None                                  # frames of the result to hand back (a carried 1-frame clip: frame 0 of its duplicate)
+        kw = dict(carry=carry, return_state=return_state, state_at=T - 1, force_gains=force_gains)
+        if carry is not None and T == 1:
+            dup = lambda t: None if t is None else torch.cat([t, t], dim=1)      # noqa: E731
+            x, force_indices, force_gains = dup(x), dup(force_indices), dup(force_gains)
+            if force_flows is not None:
+                raise ValueError("force_flows with a carried 1-frame clip: give the duplicate (T = 2) yourself")
+            T, keep = 2, 1
+            kw.update(state_at=0, force_gains=force_gains)
+
+        def trim(res):
+            if keep is None:
+                return res
+            parts = list(res) if isinstance(res, tuple) else [res]
+            parts[0] = parts[0][:, :keep].contiguous()
+            return tuple(parts) if isinstance(res, tuple) else parts[0]
+        with torch.cuda.device(self.device):
+            self._activate_precision()
+            res = self._forward(x, B, T, H, Wd, force_indices, return_aux, force_flows, **kw)
+            if _defer_check or self.precision not in X3_GRADE or not CHECK_X3_RANGE:
+                return trim(res)
+            bits = self._status_bits()
+            if bits == 0:
+                return trim(res)
+            del res
+            return trim(self._checked(None, x, B, T, H, Wd, force_indices, return_aux, force_flows, bits=bits, **kw))
+
     def _status_bits(self):
         """This forward's status word (KEEP_STATUS_*): one 4-byte device -> host read."""
         return int(self.o.status.item())
 
-    def _checked(self, res, x, B, T, H, Wd, force_indices=None, return_aux=False, force_flows=None, bits=None):
+    def _checked(self, res, x, B, T, H, Wd, force_indices=None, return_aux=False, force_flows=None, bits=None,
+                 carry=None, return_state=False, state_at=None, force_gains=None):
         """x3 policy: fp16 halves top out at 65504.  Raw-stream operands are range-probed, `bounded` ones are not; an operand
         beyond the range turns into NaN in everything it touches and every op between there and the output propagates it --
         including the discrete ones: the arg-max raises KEEP_STATUS_NONFINITE_LOGITS (it would otherwise select code 0 and the
@@ -967,6 +1086,18 @@ class KeepNet:
         try:
             self._activate_precision()
             res = None                               # (callers drop their reference to the x3 result before calling: the re-run needs the room)
+            if carry is not None or return_state or force_gains is not None:
+                # a carried call: re-run from the same incoming state (the caller kept it alive); the state handed on is the re-run's
+                kw = dict(return_state=return_state, state_at=T - 1 if state_at is None else state_at)
+                part = max(1, min(16, self.clips_per_call(T, H, Wd)))
+                if B <= part or return_aux or force_indices is not None or force_flows is not None or force_gains is not None:
+                    return self._forward(x, B, T, H, Wd, force_indices, return_aux, force_flows, carry=carry, force_gains=force_gains, **kw)
+                parts = [self._forward(x[b0:b0 + part].contiguous(), min(part, B - b0), T, H, Wd, None, False,
+                                       carry=None if carry is None else carry.select(slice(b0, b0 + part)), **kw)
+                         for b0 in range(0, B, part)]
+                if not return_state:
+                    return torch.cat(parts, 0)
+                return torch.cat([p[0] for p in parts], 0), ClipState.cat([p[1] for p in parts])
             if not return_aux and force_indices is None and force_flows is None:
                 # the exact-f32 policy holds 0.36 GB per frame against 0.22: a call sized for x3 (by free HBM, up to 48 clips) re-runs in
                 # parts sized by what is free NOW under the f32 footprint (per-image plans: same bits as one call)
@@ -1019,8 +1150,14 @@ class KeepNet:
         """[B,T,...] -> frame i as a contiguous [B,...] (free view when B == 1)."""
         return t5[:, i].contiguous()
 
-    def _forward(self, x, B, T, H, Wd, force_indices, return_aux, force_flows=None):
+    def _forward(self, x, B, T, H, Wd, force_indices, return_aux, force_flows=None, carry=None, return_state=False, state_at=None,
+                 force_gains=None):
         cfg = self.cfg
+        # a carried clip (``carry``: the ClipState of its predecessor): the pairs of K1 start at the seam (state.frame, x[:, 0]), so frame
+        # i reads pair i instead of pair i - 1, and frame 0 takes the branch of an interior frame
+        off = 0 if carry is None else 1
+        P = T - 1 + off                                                  # flow pairs
+        xf = x if carry is None else torch.cat([carry.frame.unsqueeze(1), x], dim=1)
         self.o.begin_forward(self.device)
         if self.of is not self.o:      # the flow Ops hands out its own max|out| slots
             self.of.begin_forward(self.device)
@@ -1033,25 +1170,25 @@ class KeepNet:
         # fenced by an event the frame loop waits for just before its first use -- the batched stages fill the CUs the chain leaves
         # empty.  Same kernels on the same data (per-image arithmetic and plans: chunking the pair batch changes no bit), so the
         # result is bit-identical to the one-stream order; hipGraph capture records the fork / join.
-        overlap = (STREAM_OVERLAP_MAX_CLIPS >= B and T > 2 and force_flows is None and not ops.DEBUG_SYNC and self.o.profile is None)
+        overlap = (STREAM_OVERLAP_MAX_CLIPS >= B and P > 1 and force_flows is None and not ops.DEBUG_SYNC and self.o.profile is None)
         flow_parts, ev_gain, side, main = None, None, None, None
         if force_flows is not None:      # parity tests: inject the oracle's flows [B,T-1,2,H,W] (isolates GMFlow drift)
             flows = force_flows.to(device=self.device, dtype=torch.float32).permute(0, 1, 3, 4, 2).contiguous()
-        elif T > 1 and not overlap:
+        elif P > 0 and not overlap:
             with _Range('K1 gmflow'):
-                flows = self._gmflow_clip(x)
-            flows = flows.view(B, T - 1, H, Wd, 2)
-        elif T > 1:
+                flows = self._gmflow_clip(xf)
+            flows = flows.view(B, P, H, Wd, 2)
+        elif P > 0:
             main = torch.cuda.current_stream()
             side = self._side_stream = getattr(self, '_side_stream', None) or torch.cuda.Stream(device=self.device)
             side.wait_stream(main)                                       # fork (also orders the side pool's reuse behind the last forward)
-            cuts = [0] + list(range(min(STREAM_OVERLAP_FIRST, T - 1), T - 1, STREAM_OVERLAP_CHUNK)) + [T - 1]
+            cuts = [0] + list(range(min(STREAM_OVERLAP_FIRST, P), P, STREAM_OVERLAP_CHUNK)) + [P]
             cuts = sorted(set(cuts))
             flow_parts = []                                              # (first pair, one past the last, flows [B,n,H,W,2], event)
 
             def flow_chunk(a, b):
                 with torch.cuda.stream(side), _Range('K1 gmflow (side stream)'):
-                    f = self._gmflow_clip(x[:, a:b + 1]).view(B, b - a, H, Wd, 2)
+                    f = self._gmflow_clip(xf[:, a:b + 1]).view(B, b - a, H, Wd, 2)
                     ev = torch.cuda.Event()
                     ev.record(side)
                 flow_parts.append((a, b, f, ev))
@@ -1069,7 +1206,12 @@ class KeepNet:
         zc = z.view(B, T, *z.shape[1:])
         # K3: Kalman gains over the whole clip.  They only enter frames i >= 1 (KA:1067-1070), so a T = 1 "clip" (the
         # single-image fast path: frame 0 depends on neither the flows nor the gains nor the other frames) skips them.
-        if side is not None:
+        if force_gains is not None:      # a test hook like force_flows: [B,T,...] gains instead of K3's (a cut clip with the whole clip's gains)
+            gains = force_gains.to(device=self.device, dtype=torch.float32).reshape(B, T, -1).contiguous()
+            if side is not None:
+                for a, b in zip(cuts[1:-1], cuts[2:]):
+                    flow_chunk(a, b)
+        elif side is not None:
             ev_z = torch.cuda.Event()
             ev_z.record(main)
             with torch.cuda.stream(side), _Range('K3 kalman_gain (side stream)'):
@@ -1089,25 +1231,30 @@ class KeepNet:
         idx_all, margin_all = [], []
         cross_prev, cross_prev_amax = {}, {}
         prev_out = None
+        if carry is not None:
+            prev_out, cross_prev, cross_prev_amax = carry.prev_out, dict(carry.cross_prev), dict(carry.cross_amax)
+        state = None
+        if state_at is None:
+            state_at = T - 1
         fi = None
         if force_indices is not None:
             fi = force_indices.to(device=self.device, dtype=torch.int32).contiguous()
         for i in range(T):
             z_i = self._frame(zc, i)
-            if i == 0:
+            if i == 0 and carry is None:
                 z_hat = z_i
             else:                                                        # K4 (KA:1067-1070)
                 with _Range('K4 warp + hq_encoder + kalman_update'):
                     warped = torch.empty_like(prev_out)
                     if flow_parts is not None:                           # two-stream order: this pair's chunk (and, once, the gains)
-                        a, b, fpart, ev = next(p for p in flow_parts if p[0] <= i - 1 < p[1])
-                        if i - 1 == a:
+                        a, b, fpart, ev = next(p for p in flow_parts if p[0] <= i - 1 + off < p[1])
+                        if i - 1 + off == a:
                             main.wait_event(ev)
-                        if i == 1:
+                        if i == 1 - off and ev_gain is not None:
                             main.wait_event(ev_gain)
-                        flow_i = self._frame(fpart, i - 1 - a)
+                        flow_i = self._frame(fpart, i - 1 + off - a)
                     else:
-                        flow_i = self._frame(flows, i - 1)
+                        flow_i = self._frame(flows, i - 1 + off)
                     L.call('keep_flow_warp', prev_out, flow_i, warped, B, H, Wd, 3)
                     z_prime, _ = self._vq_stack(warped, 'hq_encoder', encoder_blocks(cfg))
                     z_hat = torch.empty_like(z_i)
@@ -1127,7 +1274,7 @@ class KeepNet:
                 if j in cfa_at:
                     s = cfa_at[j]
                     y_amax = None if yst is None else yst.amax                 # (frame 0: the producing convolution's fused max|out|)
-                    if i > 0:
+                    if i > 0 or carry is not None:
                         (y, y_amax), yst = self._cfa(y, cross_prev[s], f'cfa.{s}', y_amax, cross_prev_amax.get(s), want_amax=True), None
                     cross_prev[s], cross_prev_amax[s] = y, y_amax
                 return y, yst
@@ -1136,6 +1283,8 @@ class KeepNet:
                 y, _ = self._vq_stack(quant, 'generator', gblocks, hook=hook)
             prev_out = y
             out_nhwc[:, i].copy_(y)
+            if return_state and i == state_at:      # (the maxima live in the per-forward arena: copied out; the maps are this frame's own tensors)
+                state = ClipState(x[:, i].clone(memory_format=torch.contiguous_format), y, cross_prev, {s: (None if v is None else v.clone()) for s, v in cross_prev_amax.items()})
         if side is not None:
             main.wait_stream(side)                                       # join (every chunk has been waited for; this closes a capture)
             if return_aux:
@@ -1147,8 +1296,8 @@ class KeepNet:
             aux = {'indices': torch.stack(idx_all, 1), 'margins': torch.stack(margin_all, 1), 'gains': gains,
                    'flows': flows, 'z_codes': zc, 'logit_top1': torch.stack(self._aux_top1, 1)}
             self.last_aux = aux
-            return out, aux
-        return out
+            return (out, aux, state) if return_state else (out, aux)
+        return (out, state) if return_state else out
 
     # ------------------------------------------------------------------ independent clips (hot loop #1)
     def clips_per_call(self, T, H=512, Wd=512):
@@ -1174,13 +1323,58 @@ class KeepNet:
             free -= todo['x3'] + twins.get('up2', (0,))[0]
         return max(1, min(cap, int(0.8 * free / (per_frame * max(T, 1)))))
 
-    def run_clips(self, clips, need_upscale=False, max_b=None):
+    def _chains_apply(self, after, n):
+        """``after`` as a list of n entries, or None: where there is nothing to carry, and -- with one logged warning -- where the clips
+        of a call do not all run in this process (a worker pool, a torch.distributed job): chains do not cross processes."""
+        if after is None:
+            return None
+        if len(after) != n:
+            raise ValueError(f"after: {len(after)} entries for {n} clips")
+        if all(p is None for p in after):
+            return None
+        grouped = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
+        if (self.pool is not None and self.shard_across_ranks) or (grouped and self.shard_across_ranks):
+            if not getattr(self, '_carry_warned', False):
+                self._carry_warned = True
+                import logging
+                logging.getLogger('ComfyUI-KEEP').warning(
+                    "carried clips (after=...) run in one process only; with a worker pool or a torch.distributed job every clip starts "
+                    "from nothing, as without the option")
+            return None
+        return [None if p is None else int(p) for p in after]
+
+    def run_clips(self, clips, need_upscale=False, max_b=None, after=None):
         """list of [1,T_i,3,H,W] -> list of restored clips.  Clips share no state (KA:1050,1064,1113), so equal-length
         clips are stacked on the batch axis (as many as free HBM allows, ``clips_per_call``).  A clip's result does not
         depend on its batch-mates AT ALL under the parity policies: kernel tiles, split-K factors and statistics partitions
         follow the per-image geometry and a fixed reference batch (``keep_conv2d_plan``, DESIGN.md section 6 "batch
         invariance"), so batched == sequential bit for bit (tests/test_gpu_net.py::test_batched_clips_equal_sequential,
-        ``torch.equal``)."""
+        ``torch.equal``).
+
+        ``after[j]``: the index of the clip that clip j continues (its frame 0 follows that clip's last frame), or None: clip j then
+        starts from its predecessor's state (``carry``) and runs once that one has (``carry_schedule``); a state is dropped as soon as
+        its successor has consumed it."""
+        after = self._chains_apply(after, len(clips))
+        if after is not None:
+            if need_upscale:
+                raise ValueError("run_clips(after=...): need_upscale is not supported for carried clips")
+            has_succ = {p for p in after if p is not None}
+            outs, states = [None] * len(clips), {}
+            for (T, H, Wd), carried, grp in carry_schedule(
+                    [(c.shape[1], c.shape[3], c.shape[4]) for c in clips], after,
+                    lambda k: self.clips_per_call(max(k[0], 2), k[1], k[2]) if max_b is None else max_b):
+                carry = ClipState.cat([states.pop(after[n]) for n in grp]) if carried else None
+                want = any(n in has_succ for n in grp)
+                res = self(torch.cat([clips[n] for n in grp], dim=0), carry=carry, return_state=want)
+                del carry
+                if want:
+                    res, st = res
+                    for k, n in enumerate(grp):
+                        if n in has_succ:
+                            states[n] = st.select([k]) if len(grp) > 1 else st
+                for k, n in enumerate(grp):
+                    outs[n] = res[k:k + 1]
+            return outs
         order = {}
         for n, c in enumerate(clips):
             order.setdefault((c.shape[1], c.shape[3], c.shape[4]), []).append(n)
@@ -1195,7 +1389,7 @@ class KeepNet:
         return outs
 
     # ------------------------------------------------------------------ device-side pre/post
-    def run_clips_u8(self, clips_u8, max_b=None, gather='root', sink=None, parse=False):
+    def run_clips_u8(self, clips_u8, max_b=None, gather='root', sink=None, parse=False, after=None):
         """list of uint8 BGR crops [T_i,H,W,3] (host or device) -> list of restored uint8 BGR [T_i,H,W,3] on the host.
 
         Replaces the per-frame host conversions either side of the clip loop -- ``img2tensor(face/255., bgr2rgb) +
@@ -1216,7 +1410,10 @@ class KeepNet:
         ``ids``: the clip indices, ``crops``: the matching list of restored uint8 [T,H,W,3] tensors, ON THIS PROCESS'S GPU for the
         groups it ran itself (no download at all) and in host memory for a pool worker's, ``classes``: None, or the ParseNet class
         maps uint8 [T,H,W] a worker computed for its crops (``GpuPool.set_parser``).  The call then returns None.  The processor's
-        sequence path pastes frames from it while the next group is being restored (modules/keep_processor.py)."""
+        sequence path pastes frames from it while the next group is being restored (modules/keep_processor.py).
+
+        ``after[j]``: the index of the clip that clip j continues, or None (``run_clips``): such a clip starts from its predecessor's
+        state.  One process only: with a worker pool or a torch.distributed job the argument is ignored with one logged warning."""
         if self.w is None:
             raise RuntimeError("KeepNet: weights are not on a device (load_state_dict + .to('cuda') first)")
         from . import dist as kdist
@@ -1224,6 +1421,10 @@ class KeepNet:
         for c in clips_u8:
             if len(c.shape) != 4 or c.shape[-1] != 3 or c.dtype != torch.uint8:
                 raise ValueError(f"expected uint8 [T,H,W,3], got {c.dtype} {tuple(c.shape)}")
+        after = self._chains_apply(after, len(clips_u8))
+        if after is not None:
+            local = self._run_clips_u8_local(dict(enumerate(clips_u8)), max_b, sink=sink, after=after)
+            return None if sink is not None else [torch.from_numpy(local[i]) for i in range(len(clips_u8))]
         if self.pool is not None and self.shard_across_ranks and len(clips_u8) > 1:
             # single-process product (a ComfyUI node): this process is the root of a worker pool, one worker per additional GPU
             return self.pool.run(self, clips_u8, max_b, sink=sink, parse=bool(parse) and sink is not None)
@@ -1251,7 +1452,7 @@ class KeepNet:
             buf = self._pinned_in[key] = torch.empty(shape, dtype=torch.uint8, pin_memory=True)
         return buf
 
-    def _run_clips_u8_local(self, mine, max_b=None, sink=None):
+    def _run_clips_u8_local(self, mine, max_b=None, sink=None, after=None):
         """{clip index: uint8 [T,H,W,3]} -> {clip index: restored uint8 numpy [T,H,W,3]} on this rank's GPU.
 
         Three-stage pipeline over the batch groups, two HIP streams: while group g runs its forward on the compute stream,
@@ -1259,16 +1460,31 @@ class KeepNet:
         pinned memory.  The x3 range check of a group (one int32, ``_checked``) is read after its download has been queued,
         i.e. the host never waits inside a forward; a flagged group is re-run on the f32 kernels before it is handed back.
         Clips that already live on this GPU (device tensors) skip the staging and the upload.  With ``sink`` nothing is downloaded:
-        a finished (range-checked) group is handed to ``sink(ids, [uint8 device tensors], None)`` and {} is returned."""
-        order = {}
-        for n, c in mine.items():
-            order.setdefault(tuple(c.shape[:3]), []).append(n)
-        groups = []
-        for (T, H, Wd), ids in order.items():
-            b = self.clips_per_call(T, H, Wd) if max_b is None else max_b
-            if sink is not None and max_b is None:
-                b = min(b, 16)      # streamed paste-back: several groups, so that the paste of group k runs under the forward of group k + 1
-            groups += [(T, H, Wd, ids[s:s + b]) for s in range(0, len(ids), b)]
+        a finished (range-checked) group is handed to ``sink(ids, [uint8 device tensors], None)`` and {} is returned.
+
+        ``after`` (``mine`` then holds clips 0 .. n - 1): the groups are those of ``carry_schedule``; a group with a predecessor starts from
+        the states its predecessors returned.  A group that hands a state on is range-checked BEFORE the next group is queued -- its
+        successor must start from the re-run's state, never from a flagged one -- so only groups at the end of their chains keep the
+        deferred check."""
+        groups, carried_of = [], {}
+        if after is None:
+            order = {}
+            for n, c in mine.items():
+                order.setdefault(tuple(c.shape[:3]), []).append(n)
+            for (T, H, Wd), ids in order.items():
+                b = self.clips_per_call(T, H, Wd) if max_b is None else max_b
+                if sink is not None and max_b is None:
+                    b = min(b, 16)      # streamed paste-back: several groups, so that the paste of group k runs under the forward of group k + 1
+                groups += [(T, H, Wd, ids[s:s + b]) for s in range(0, len(ids), b)]
+        else:
+            def cap(k):
+                b = self.clips_per_call(max(k[0], 2), k[1], k[2]) if max_b is None else max_b
+                return min(b, 16) if (sink is not None and max_b is None) else b
+            for (T, H, Wd), carried, ids in carry_schedule([tuple(mine[n].shape[:3]) for n in range(len(mine))], after, cap):
+                carried_of[len(groups)] = carried
+                groups.append((T, H, Wd, ids))
+        has_succ = set() if after is None else {p for p in after if p is not None}
+        states = {}                                             # clip index -> the ClipState its successor starts from
         local = {}
         if not groups:
             return local
@@ -1306,12 +1522,21 @@ class KeepNet:
 
             def finish(job):
                 """download queued -> wait for it, check the group's status word, hand the frames back"""
-                gi, x, r8_host, st_host, ev_done = job
+                gi, x, r8_host, st_host, ev_done, carry, want = job
                 ev_done.synchronize()
                 T, H, Wd, grp = groups[gi]
                 bits = int(st_host.item())
                 if bits and x is not None:
-                    o = self._checked(None, x, len(grp), T, H, Wd, bits=bits)
+                    if carry is not None or want:              # re-run from the same incoming state; the state handed on is the re-run's
+                        lone = carry is not None and T == 1    # (a carried 1-frame clip ran as its T = 2 duplicate, frame 0 kept)
+                        o = self._checked(None, torch.cat([x, x], dim=1) if lone else x, len(grp), 2 if lone else T, H, Wd, bits=bits,
+                                          carry=carry, return_state=want, state_at=0 if lone else T - 1)
+                        if want:
+                            o, st = o
+                            hand_on(grp, st)
+                        o = o[:, :T].contiguous()
+                    else:
+                        o = self._checked(None, x, len(grp), T, H, Wd, bits=bits)
                     y = ops.nchw_to_nhwc(o.view(len(grp) * T, 3, H, Wd))
                     r8 = torch.empty((len(grp) * T, H, Wd, 3), dtype=torch.uint8, device=self.device)
                     L.call('keep_tensor2img', y, r8, len(grp) * T * H * Wd)
@@ -1327,6 +1552,11 @@ class KeepNet:
                 for k, n in enumerate(grp):
                     local[n] = arr[k]
 
+            def hand_on(grp, st):
+                for k, n in enumerate(grp):
+                    if n in has_succ:
+                        states[n] = st.select([k]) if len(grp) > 1 else st
+
             nxt = upload(0)
             pending = None
             for gi, (T, H, Wd, grp) in enumerate(groups):
@@ -1338,7 +1568,17 @@ class KeepNet:
                 L.call('keep_img2tensor', u8, f, len(grp) * T * H * Wd)
                 x = ops.nhwc_to_nchw(f).view(len(grp), T, 3, H, Wd)
                 del f, u8
-                o = self(x, _defer_check=True)
+                carry, want = None, False
+                if after is None:
+                    o = self(x, _defer_check=True)
+                else:
+                    want = any(n in has_succ for n in grp)
+                    carry = ClipState.cat([states.pop(after[n]) for n in grp]) if carried_of[gi] else None
+                    o = self(x, _defer_check=True, carry=carry, return_state=want)
+                    if want:
+                        o, st = o
+                        hand_on(grp, st)
+                        del st
                 y = ops.nchw_to_nhwc(o.view(len(grp) * T, 3, H, Wd))
                 r8 = torch.empty((len(grp) * T, H, Wd, 3), dtype=torch.uint8, device=self.device)
                 L.call('keep_tensor2img', y, r8, len(grp) * T * H * Wd)
@@ -1360,6 +1600,12 @@ class KeepNet:
                 if pending is not None:
                     finish(pending)          # group g-1: its download ran under group g's launches
                 # x is kept only for the (rare) f32 re-run; precision 'x3' is the only policy that can ask for one
-                pending = (gi, x if (self.precision in X3_GRADE and CHECK_X3_RANGE) else None, r8_host, st_host, ev_done)
-            finish(pending)
+                recheck = self.precision in X3_GRADE and CHECK_X3_RANGE
+                pending = (gi, x if recheck else None, r8_host, st_host, ev_done, carry if recheck else None, want)
+                del carry
+                if want and recheck:         # its successor starts from this group's state: the check comes first
+                    finish(pending)
+                    pending = None
+            if pending is not None:
+                finish(pending)
         return local

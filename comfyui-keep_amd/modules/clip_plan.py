@@ -20,6 +20,15 @@ def plan_track_clips(presence, max_clip_length):
       after clip: a crop tensor laid out by slot has every clip as a contiguous view.
 
     One track present on every frame gives the spans of ``split_clips`` and the identity permutation."""
+    clips, slot_of, _ = plan_track_chains(presence, max_clip_length)
+    return clips, slot_of
+
+
+def plan_track_chains(presence, max_clip_length):
+    """``plan_track_clips`` plus, per clip, the clip it continues (``KEEP_AMD_TRACK_CARRY``) -> ``(clips, slot_of, after)``.
+
+    ``after[c]``: the index in ``clips`` of the previous piece of the same run of the same track -- the clip whose last frame is the frame
+    before clip c's first -- or None where clip c starts a run.  A gap in a track starts a new run, so no state is carried across it."""
     L = int(max_clip_length)
     if L < 1:
         raise ValueError(f"plan_track_clips: max_clip_length {max_clip_length} < 1")
@@ -41,18 +50,20 @@ def plan_track_clips(presence, max_clip_length):
         open_run = still
         n_crops += len(keys)
     pieces = []
-    for t0, r, members in runs:
+    for n_run, (t0, r, members) in enumerate(runs):
         for s in range(0, len(members), L):
-            pieces.append((t0 + s, r, members[s:s + L]))
+            pieces.append((t0 + s, r, members[s:s + L], (n_run, s // L)))
     pieces.sort(key=lambda p: (p[0], p[1]))
-    clips = [m for _, _, m in pieces]
+    clips = [m for _, _, m, _ in pieces]
+    where = {pid: c for c, (_, _, _, pid) in enumerate(pieces)}
+    after = [where.get((n_run, k - 1)) for _, _, _, (n_run, k) in pieces]
     slot_of = [None] * n_crops
     slot = 0
     for m in clips:
         for i in m:
             slot_of[i] = slot
             slot += 1
-    return clips, slot_of
+    return clips, slot_of, after
 
 
 def clip_slot_spans(clips):

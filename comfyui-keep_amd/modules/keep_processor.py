@@ -47,6 +47,10 @@ Track clips (``KEEP_AMD_TRACK_CLIPS``, off by default): the repaired form of P1 
 track (``clip_plan.py``), every face of a single image is a clip of its own.  Crop numbering and the paste order stay; the frame store lays
 its crop tensor out by clip (``keep_warp_affine_batch_scatter_u8``) so the clips remain views.  With the knob off nothing plans, permutes or
 scatters.  No reference to compare with: each face equals its track restored on its own, bit for bit (tests/test_gpu_track_clips.py).
+
+Carried clips (``KEEP_AMD_TRACK_CARRY``, off by default, implies track clips): a clip that continues a run of its track starts from the state
+its predecessor left instead of from nothing (``clip_plan.plan_track_chains`` names the predecessor, ``run_clips_u8(after=...)`` hands the
+state over), on every path a sequence takes; an aligned sequence is one track.  One process only (tests/test_gpu_track_carry.py).
 """
 import os
 
@@ -469,6 +473,11 @@ class KEEPFaceProcessor:
         # KEEP_AMD_TRACK_CLIPS=1 (or setting the attribute): every clip holds consecutive frames of one track (``clip_plan.py``), every
         # face of a single image is a clip of its own.  With one face per frame the clips are the default's.
         self.track_clips = os.environ.get('KEEP_AMD_TRACK_CLIPS', '0') == '1'
+        # ``max_clip_length`` bounds memory, yet every clip starts the net's recurrence from nothing: frame 0 of a clip is decoded without
+        # warp, Kalman update or CFA.  KEEP_AMD_TRACK_CARRY=1 (or setting the attribute; implies track clips): a clip that continues a track's
+        # run starts from the state its predecessor left (``plan_track_chains``, ``KeepNet.run_clips_u8(after=...)``), so the cut into
+        # clips no longer shows in a track's pixels.  No parity mode -- the reference never does this.  One process only.
+        self.track_carry = os.environ.get('KEEP_AMD_TRACK_CARRY', '0') == '1'
         # paste-back compositing on the GPU (engine/paste.py).  Opt-in: its arithmetic restates OpenCV's and
         # could not be checked against cv2 itself in the build image.
         # KEEP_AMD_GPU_PASTE: '1' on, '0' off; unset = 'auto': the first paste runs ``opencv_agrees_with_gpu_paste`` -- the HIP
@@ -550,7 +559,7 @@ class KEEPFaceProcessor:
             kept.append(o[:, 0:1] if e - s == 1 else o)
         return torch.cat(kept, dim=1).squeeze(0)
 
-    def _restore_crops_u8(self, crops, max_clip_length, members=None):
+    def _restore_crops_u8(self, crops, max_clip_length, members=None, after=None):
         """list of uint8 BGR [512,512,3] crops -> list of restored uint8 BGR crops (same order).
 
         Same chunking as ``_restore_clips`` (keep_processor.py:263-270); when the net offers ``run_clips_u8`` the
@@ -558,7 +567,8 @@ class KEEPFaceProcessor:
         otherwise the host converters are used (reference behaviour).
 
         ``members`` (track clips): the clips as lists of crop indices (``plan_track_clips``) instead of the cut of the flat list; every
-        crop is in exactly one of them, the lone-crop rule applies per clip and the outputs are scattered back to crop order."""
+        crop is in exactly one of them, the lone-crop rule applies per clip and the outputs are scattered back to crop order.  ``after``
+        (``track_carry``): per clip the clip it continues (``plan_track_chains``), handed to the net where it can carry a state."""
         run_u8 = getattr(self.keep_net, 'run_clips_u8', None)
         if run_u8 is None:
             x = crops_to_net_input(crops).unsqueeze(0).to(self.device)
@@ -567,8 +577,10 @@ class KEEPFaceProcessor:
         crops = [np.asarray(c) for c in crops]
         t1_ok = getattr(self.keep_net, 'supports_single_frame', False)
         if members is not None:
-            clips = [[crops[i] for i in m] * (2 if len(m) == 1 and not t1_ok else 1) for m in members]   # (T >= 2: KP:173-178, frame 0 kept)
-            outs = run_u8(clips)
+            kw = self._carry_kw(run_u8, after)
+            dup = 1 if (t1_ok or kw) else 2      # (a net that takes ``after`` takes 1-frame clips as they are: it hands on the state after frame 0)
+            clips = [[crops[i] for i in m] * (dup if len(m) == 1 else 1) for m in members]   # (T >= 2: KP:173-178, frame 0 kept)
+            outs = run_u8(clips, **kw)
             if outs is None:      # a non-root rank of a run sharded over several GPUs
                 return None
             faces = [None] * len(crops)
@@ -845,7 +857,7 @@ class KEEPFaceProcessor:
 
         # one face -> T=2 duplicate, keep frame 0; several faces -> one "clip" of T=#faces (KP:173-178)
         # (track clips: the faces of one picture are no sequence -- each is a clip of its own, restored like a lone face)
-        if self.track_clips and len(crops) > 1:
+        if self._per_track and len(crops) > 1:      # (a single image has nothing to carry)
             faces = self._restore_crops_u8(crops, max_clip_length=1, members=[[i] for i in range(len(crops))])
         else:
             faces = self._restore_crops_u8(crops, max_clip_length=max(len(crops), 1))
@@ -1168,6 +1180,8 @@ class KEEPFaceProcessor:
             params = {}
         takes_all = any(p.kind == inspect.Parameter.VAR_KEYWORD for p in params.values())
         kw = {k: v for k, v in (('max_b', max_b), ('parse', True)) if takes_all or k in params}    # decided by capability, not by catching
+        if plan is not None and len(plan) > 2:                         # track carry: per clip the clip it continues
+            kw.update(self._carry_kw(net.run_clips_u8, plan[2]))
         net.run_clips_u8(clips, sink=sink, **kw)                                                     # a TypeError from inside the forward
         advance()                                                      # frames without faces behind the last restored one
         ps.synchronize()
@@ -1249,6 +1263,8 @@ class KEEPFaceProcessor:
                 frames_dev.append(buf if keep_frames else None)
         spans = split_clips(n, max_clip_length)
         t1_ok = getattr(net, 'supports_single_frame', False)
+        carry_kw = self._carry_kw(net.run_clips_u8, [None] + list(range(len(spans) - 1)))      # track carry: one track, its spans chained in order
+        t1_ok = t1_ok or bool(carry_kw)
         clips = [crops[s:e] if (e - s > 1 or t1_ok) else torch.cat([crops[s:e], crops[s:e]]) for s, e in spans]   # (T >= 2: KP:173-178)
         restored = [None] * n
         keep_restored = self.keep_restored_faces
@@ -1298,7 +1314,7 @@ class KEEPFaceProcessor:
                     restored[s + k] = crops_list[j][k]
             advance()
 
-        net.run_clips_u8(clips, sink=sink)
+        net.run_clips_u8(clips, sink=sink, **carry_kw)
         torch.cuda.current_stream(dev).synchronize()
         if st['next'] != n:
             raise RuntimeError(f"streamed aligned sequence: {n - st['next']} frame(s) never became ready")
@@ -1370,7 +1386,7 @@ class KEEPFaceProcessor:
                 store.drop()
                 return None
             plan = self._track_plan([[key for key, seq in tracks.items() if not np.isnan(seq[i]).any()] for i in range(n_frames)],
-                                    max_clip_length) if self.track_clips else None
+                                    max_clip_length) if self._per_track else None
             with torch.cuda.device(store.device):
                 crops = torch.empty((n_crops, 512, 512, 3), dtype=torch.uint8, device=store.device)
                 off = 0
@@ -1395,9 +1411,38 @@ class KEEPFaceProcessor:
             store.drop(getattr(self, '_paste_stream', None))        # (nothing is left after ``ps.synchronize()``; an error's way out: the paste stream may still read)
 
     def _track_plan(self, presence, max_clip_length):
-        """``plan_track_clips`` for a sequence (``track_clips`` only): (clips as crop-index lists, slot of every crop)."""
-        from .clip_plan import plan_track_clips
+        """``plan_track_clips`` for a sequence (``track_clips`` only): (clips as crop-index lists, slot of every crop); with
+        ``track_carry`` ``plan_track_chains``: the same two and, per clip, the clip it continues."""
+        from .clip_plan import plan_track_chains, plan_track_clips
+        if self.track_carry:
+            return plan_track_chains(presence, max_clip_length)
         return plan_track_clips(presence, max_clip_length)
+
+    @property
+    def _per_track(self):
+        """Clips hold one track each: ``track_clips``, which ``track_carry`` implies."""
+        return bool(self.track_clips or self.track_carry)
+
+    def _carry_kw(self, run, after):
+        """{'after': after} where ``track_carry`` is on, some clip has a predecessor and ``run`` (the net's ``run_clips_u8``) takes the
+        argument -- decided by capability; a net that cannot carry restores every clip from nothing, with one logged warning.  A net
+        that takes ``after`` MUST take T = 1 clips, carried or not, whatever its ``supports_single_frame`` says: it is handed 1-frame
+        clips as they are, never the host-side T = 2 duplicate: the duplicate rule is the net's
+        then (``KeepNet``: carried 1-frame clips run as their duplicate inside the call), so the state handed on is the one after frame 0."""
+        if not self.track_carry or after is None or all(p is None for p in after):
+            return {}
+        import inspect
+        try:
+            params = inspect.signature(run).parameters
+        except (TypeError, ValueError):
+            params = {}
+        if 'after' in params or any(p.kind == inspect.Parameter.VAR_KEYWORD for p in params.values()):
+            return {'after': list(after)}
+        if not getattr(self, '_carry_warned', False):
+            self._carry_warned = True
+            import logging
+            logging.getLogger('ComfyUI-KEEP').warning("KEEP_AMD_TRACK_CARRY: this net cannot start a clip from a state; clips start from nothing")
+        return {}
 
     def _detect_batching(self, det, n):
         """(whether the pre-pass runs the detector over batches, frames per chunk)"""
@@ -1662,7 +1707,7 @@ class KEEPFaceProcessor:
         # -- 2. crops, flat and frame-major
         crops, affines, faces_per_frame, input_hw = [], [], [], [None] * n_frames
         stream_ok = (not has_aligned_frames) and self._stream_applies(helper, frames_bgr, None, draw_box)
-        presence = [] if self.track_clips else None      # track clips: the keys of the tracks behind every frame's crops, in face order
+        presence = [] if self._per_track else None      # track clips: the keys of the tracks behind every frame's crops, in face order
         for i in tqdm(range(n_frames), desc="Cropping and aligning faces"):
             if has_aligned_frames:
                 frame_crops, frame_aff = [self._aligned_face(frames_bgr[i])], []
@@ -1698,7 +1743,7 @@ class KEEPFaceProcessor:
         restored_faces = []
         if crops:
             restored_faces = (self._restore_crops_u8(crops, max_clip_length) if plan is None
-                              else self._restore_crops_u8(crops, max_clip_length, members=plan[0]))
+                              else self._restore_crops_u8(crops, max_clip_length, members=plan[0], after=plan[2] if len(plan) > 2 else None))
             if restored_faces is None:          # non-root rank of a sharded multi-GPU run (engine/dist.py): nothing to paste here
                 return None
         self.last_restored_faces = restored_faces
