@@ -147,6 +147,7 @@ _CV_SIGNATURES = {
     'keep_conv2d_launch_plan': [C.POINTER(ConvArgs), C.POINTER(ConvLaunchPlanOut)],  # (host-only: no stream argument)
     'keep_gm_ffn_x1_plan': [_i32, _i32, _i32, _i32, _i32],                 # (host-only: no stream argument)
     'keep_gm_ffn_x1': [_vp, _vp, _vp, _f32, _vp, _f32, _vp, _vp, _f32, _vp, _i64, _i32, _i32, _i32, _vp],
+    'keep_frame_signature_u8': [_vp, _i32, _i32, _i32, _vp, _vp],
 }
 CV_EXPORTED_SYMBOLS = ['keep_cv_abi_version'] + list(_CV_SIGNATURES)
 

@@ -74,14 +74,38 @@ def _smooth(landmark_seq):
     return gaussian_filter1d(arr, sigma=2, axis=0).reshape(arr.shape[0], 5, 2)
 
 
-def smooth_center_face(raw_landmarks_per_frame):
-    """only_center_face: at most one face per frame, no association needed (KP:216-222)."""
+def _per_segment(smooth, raw_landmarks_per_frame, cuts):
+    """``smooth`` over every scene of the video on its own, exactly as if the scene were the whole video (scene_cuts.py:segments): the
+    tracks of scene s come back under the keys ``(s, key)``, NaN outside the scene.  A scene without any detection yields no track -- its
+    frames pass through unrestored; the whole-video interpolation would carry a neighbouring scene's landmarks into it."""
+    from .scene_cuts import segments
+    n = len(raw_landmarks_per_frame)
+    out = {}
+    for s, (a, b) in enumerate(segments(n, cuts)):
+        part = raw_landmarks_per_frame[a:b]
+        if not any(part):
+            continue
+        for key, seq in smooth(part).items():
+            full = np.full((n, 5, 2), np.nan)
+            full[a:b] = seq
+            out[(s, key)] = full
+    return out
+
+
+def smooth_center_face(raw_landmarks_per_frame, cuts=None):
+    """only_center_face: at most one face per frame, no association needed (KP:216-222).  ``cuts`` (KEEP_AMD_SCENE_CUTS): the frames
+    that open a scene; every scene is smoothed on its own (``_per_segment``).  None / empty: the video is one scene, today's result."""
+    if cuts:
+        return _per_segment(smooth_center_face, raw_landmarks_per_frame, cuts)
     seq = [(f[0] if f else _NAN_LM()).reshape(10) for f in raw_landmarks_per_frame]
     return {0: _smooth(seq)}
 
 
-def smooth_tracked_faces(raw_landmarks_per_frame):
-    """multi-face: Hungarian tracks, each smoothed independently (KP:223-231)."""
+def smooth_tracked_faces(raw_landmarks_per_frame, cuts=None):
+    """multi-face: Hungarian tracks, each smoothed independently (KP:223-231).  ``cuts``: as in ``smooth_center_face`` -- every scene is
+    tracked and smoothed on its own, so no track crosses a cut."""
+    if cuts:
+        return _per_segment(smooth_tracked_faces, raw_landmarks_per_frame, cuts)
     out = {}
     if not any(raw_landmarks_per_frame):
         return out

@@ -51,6 +51,11 @@ scatters.  No reference to compare with: each face equals its track restored on 
 Carried clips (``KEEP_AMD_TRACK_CARRY``, off by default, implies track clips): a clip that continues a run of its track starts from the state
 its predecessor left instead of from nothing (``clip_plan.plan_track_chains`` names the predecessor, ``run_clips_u8(after=...)`` hands the
 state over), on every path a sequence takes; an aligned sequence is one track.  One process only (tests/test_gpu_track_carry.py).
+
+Scene cuts (``KEEP_AMD_SCENE_CUTS``, off by default, implies track clips): consecutive frames whose signatures (``scene_cuts.py``: a grid of
+luma histograms; ``keep_frame_signature_u8`` on the chunks the frame store holds, the host restatement elsewhere -- the same integers) are
+at least ``scene_cut_threshold`` apart are a hard cut: every scene is tracked and smoothed on its own, no clip spans a cut and no state
+is carried across one.  A video of scenes A then B equals A and B processed as two videos, bit for bit (tests/test_gpu_scene_cuts.py).
 """
 import os
 
@@ -390,6 +395,7 @@ class _FrameStore:
         self.spans, self.h, self.w, self.device = list(spans), int(h), int(w), device
         self.cap_bytes = cap_bytes
         self.small = None
+        self.sig = None                   # scene cuts: int32 [n_frames,256] on the device, row t the signature of frame t (``fill`` writes it)
         self.ebufs = [None] * len(self.spans)
         self.chunk = self.spans[0][1] - self.spans[0][0]
         self.bufs = [None] * len(self.spans)
@@ -405,6 +411,14 @@ class _FrameStore:
             buf = torch.empty((b - a, self.h, self.w, 3), dtype=torch.uint8, device=self.device)
             for i, fr in enumerate(frames):
                 buf[i].copy_(torch.from_numpy(np.ascontiguousarray(fr)), non_blocking=True)
+            if self.sig is not None:      # the chunk's signatures: one launch behind its copies, on the frames as they came
+                try:
+                    from ..engine import hiplib as L
+                    L.call('keep_frame_signature_u8', buf, b - a, self.h, self.w, self.sig[a:b])
+                except Exception as e:    # the opt-in mode's trouble is not the store's: logged, and the host function takes the signatures
+                    import logging
+                    logging.getLogger('ComfyUI-KEEP').warning("frame signatures on the device failed (%s): the host function", e)
+                    self.sig = None
             ev = torch.cuda.Event()
             ev.record()
         self.bufs[k], self.events[k] = buf, ev
@@ -478,6 +492,17 @@ class KEEPFaceProcessor:
         # run starts from the state its predecessor left (``plan_track_chains``, ``KeepNet.run_clips_u8(after=...)``), so the cut into
         # clips no longer shows in a track's pixels.  No parity mode -- the reference never does this.  One process only.
         self.track_carry = os.environ.get('KEEP_AMD_TRACK_CARRY', '0') == '1'
+        # tracking, smoothing and the carried state all assume that consecutive frames show one scene; edited video has hard cuts.
+        # KEEP_AMD_SCENE_CUTS=1 (or setting the attribute; implies track clips): frames whose signatures (``scene_cuts.py``) are at least
+        # ``scene_cut_threshold`` apart (KEEP_AMD_SCENE_CUT_THRESHOLD, default 0.4: a setting, not a measured optimum) open a new scene,
+        # every scene is tracked and smoothed on its own, no clip spans a cut and nothing is carried across one.  A false cut costs one
+        # state reset, which every clip boundary causes by default anyway; a missed cut leaves today's behaviour.  After a call with the
+        # knob on ``last_scene_cuts`` (list of int) and ``last_scene_distances`` (float [n - 1]) say what was found.
+        self.scene_cuts = os.environ.get('KEEP_AMD_SCENE_CUTS', '0') == '1'
+        try:
+            self.scene_cut_threshold = float(os.environ.get('KEEP_AMD_SCENE_CUT_THRESHOLD', '') or 0.4)
+        except ValueError:
+            self.scene_cut_threshold = 0.4
         # paste-back compositing on the GPU (engine/paste.py).  Opt-in: its arithmetic restates OpenCV's and
         # could not be checked against cv2 itself in the build image.
         # KEEP_AMD_GPU_PASTE: '1' on, '0' off; unset = 'auto': the first paste runs ``opencv_agrees_with_gpu_paste`` -- the HIP
@@ -1220,7 +1245,7 @@ class KEEPFaceProcessor:
             return False
         return (h, w) == (512, 512) or bool(self._gpu_aligned_resize_path())
 
-    def _aligned_streamed(self, frames_bgr, max_clip_length, factor, pbar, as_u8):
+    def _aligned_streamed(self, frames_bgr, max_clip_length, factor, pbar, as_u8, scene=False):
         """Steps 2 - 4 of an aligned sequence (keep_processor.py:250-291 of the reference) with the frames resident on the GPU.
 
         The frames are uploaded in chunks of at most ``KEEP_AMD_DETECT_BATCH``, each frame copied straight into the chunk's [n,H,W,3]
@@ -1231,7 +1256,10 @@ class KEEPFaceProcessor:
         Lanczos launch per chunk; with ``return_restored_aligned`` the restored crops at ``int(512 * factor)``, one launch per run.
         All of it is queued on the stream the forward runs on -- the restored crops are consumed on their producing stream -- and
         only the finished output crosses PCIe (float RGB via ``keep_bgr_u8_to_comfy`` unless ``as_u8``).  Returns None, before anything
-        was restored, when the device resize fails."""
+        was restored, when the device resize fails.
+
+        ``scene`` (scene cuts): every uploaded chunk's signatures are taken on the device, from the frames as given, and the spans are
+        cut per scene; nothing is carried across a cut."""
         from ..engine import hiplib as L
         net, dev = self.keep_net, torch.device(self.device)
         if dev.index is None:
@@ -1246,12 +1274,20 @@ class KEEPFaceProcessor:
         keep_frames = not restored_out            # P2: the output is made of the input frames
         with torch.cuda.device(dev):
             crops = torch.empty((n, 512, 512, 3), dtype=torch.uint8, device=dev)
+            sig_dev = torch.empty((n, 256), dtype=torch.int32, device=dev) if scene else None
             frames_dev = []                       # per chunk: its [m,H,W,3] input frames on the device (None once emitted / unused)
             for a in starts:
                 part = frames_bgr[a:a + chunk]
                 buf = crops[a:a + len(part)] if (h, w) == (512, 512) else torch.empty((len(part), h, w, 3), dtype=torch.uint8, device=dev)
                 for i, fr in enumerate(part):
                     buf[i].copy_(torch.from_numpy(np.ascontiguousarray(fr)), non_blocking=True)
+                if sig_dev is not None:
+                    try:
+                        L.call('keep_frame_signature_u8', buf, len(part), h, w, sig_dev[a:a + len(part)])
+                    except Exception as e:              # logged, and the host function takes the signatures: the same integers
+                        import logging
+                        logging.getLogger('ComfyUI-KEEP').warning("frame signatures on the device failed (%s): the host function", e)
+                        sig_dev = None
                 if (h, w) != (512, 512):
                     try:
                         self._aligned_resize_device(buf, out=crops[a:a + len(part)])
@@ -1262,8 +1298,17 @@ class KEEPFaceProcessor:
                         return None
                 frames_dev.append(buf if keep_frames else None)
         spans = split_clips(n, max_clip_length)
+        chain = [None] + list(range(len(spans) - 1))                                          # track carry: one track, its spans chained in order
+        cuts = self._scene_cuts_of(frames_bgr, sig_dev) if scene else None
+        if cuts:                                                                              # per scene: its own spans, its own chain
+            from .scene_cuts import segments
+            spans, chain = [], []
+            for a, b in segments(n, cuts):
+                for j, (s, e) in enumerate(split_clips(b - a, max_clip_length)):
+                    chain.append(None if j == 0 else len(spans) - 1)
+                    spans.append((a + s, a + e))
         t1_ok = getattr(net, 'supports_single_frame', False)
-        carry_kw = self._carry_kw(net.run_clips_u8, [None] + list(range(len(spans) - 1)))      # track carry: one track, its spans chained in order
+        carry_kw = self._carry_kw(net.run_clips_u8, chain)
         t1_ok = t1_ok or bool(carry_kw)
         clips = [crops[s:e] if (e - s > 1 or t1_ok) else torch.cat([crops[s:e], crops[s:e]]) for s, e in spans]   # (T >= 2: KP:173-178)
         restored = [None] * n
@@ -1420,8 +1465,60 @@ class KEEPFaceProcessor:
 
     @property
     def _per_track(self):
-        """Clips hold one track each: ``track_clips``, which ``track_carry`` implies."""
-        return bool(self.track_clips or self.track_carry)
+        """Clips hold one track each: ``track_clips``, which ``track_carry`` and ``scene_cuts`` imply (in the flat frame-major cut a
+        clip spans the scene boundary whatever the tracks do)."""
+        return bool(self.track_clips or self.track_carry or getattr(self, 'scene_cuts', False))
+
+    # ------------------------------------------------------------------ scene cuts
+    def _scene_cuts_apply(self, frames_bgr):
+        """Whether this call looks for scene cuts: the knob, more than one frame, uniform uint8 [h,w,3] frames.  Anything else ignores the
+        knob, with one logged warning."""
+        if not getattr(self, 'scene_cuts', False):
+            return False
+        n = len(frames_bgr)
+        if n < 2:
+            self.last_scene_cuts, self.last_scene_distances = [], np.zeros((0,), np.float64)
+            return False
+        ok = isinstance(frames_bgr, _ConvertedFrames)            # uint8 [H,W,3] by construction
+        if not ok:
+            shape = tuple(getattr(frames_bgr[0], 'shape', ()))
+            ok = (len(shape) == 3 and shape[2] == 3 and shape[0] > 0 and shape[1] > 0
+                  and all(isinstance(f, np.ndarray) and f.dtype == np.uint8 and tuple(f.shape) == shape for f in frames_bgr))
+        if not ok:
+            if not getattr(self, '_scene_warned', False):
+                self._scene_warned = True
+                import logging
+                logging.getLogger('ComfyUI-KEEP').warning("KEEP_AMD_SCENE_CUTS: the frames are not uint8 [h,w,3] of one size; no scene cuts")
+            self.last_scene_cuts, self.last_scene_distances = [], np.zeros((0,), np.float64)
+        return ok
+
+    def _store_signatures(self, store, n_frames):
+        """The device tensor the frame store's fills write their chunks' signatures into (``_FrameStore.fill``).  An allocation that
+        fails leaves the store as it is: the host function takes the sequence."""
+        try:
+            with torch.cuda.device(store.device):
+                store.sig = torch.empty((n_frames, 256), dtype=torch.int32, device=store.device)
+        except Exception:
+            store.sig = None
+
+    def _scene_cuts_of(self, frames_bgr, sig_dev=None):
+        """The cuts of this sequence -> sorted list of frames that open a scene; sets ``last_scene_cuts`` / ``last_scene_distances``.
+        ``sig_dev``: the signatures where the kernel wrote them (ONE download), else ``frame_signature_host`` frame by frame: the same
+        integers either way."""
+        from .scene_cuts import find_cuts, frame_signature_host, signature_distances
+        sigs = None
+        if sig_dev is not None:
+            try:
+                sigs = sig_dev.cpu().numpy()
+            except Exception as e:
+                import logging
+                logging.getLogger('ComfyUI-KEEP').warning("reading the frame signatures back failed (%s): the host function", e)
+        if sigs is None:
+            sigs = np.stack([frame_signature_host(frames_bgr[i]) for i in range(len(frames_bgr))])
+        h, w = frames_bgr[0].shape[:2]
+        self.last_scene_distances = signature_distances(sigs, h * w)
+        self.last_scene_cuts = find_cuts(sigs, h * w, self.scene_cut_threshold)
+        return self.last_scene_cuts
 
     def _carry_kw(self, run, after):
         """{'after': after} where ``track_carry`` is on, some clip has a predecessor and ``run`` (the net's ``run_clips_u8``) takes the
@@ -1680,21 +1777,28 @@ class KEEPFaceProcessor:
 
         # -- 1. landmarks per frame -> temporally smoothed tracks
         tracks, store = {}, None
+        scene = self._scene_cuts_apply(frames_bgr)      # (False with the knob off: nothing below computes, launches or writes anything new)
+        cuts = None
         if not has_aligned_frames:
             store = self._frame_store_begin(frames_bgr)
+            if scene and store is not None:
+                self._store_signatures(store, n_frames)
             raw = self._detect_all(frames_bgr, only_center_face, store=store)
             if store is not None and (store.dead or not store.complete()):
                 store.drop()
                 store = None
             pbar.update(n_frames)
-            tracks = smooth_center_face(raw) if only_center_face else smooth_tracked_faces(raw)
+            if scene:
+                cuts = self._scene_cuts_of(frames_bgr, store.sig if store is not None else None)
+            smooth = smooth_center_face if only_center_face else smooth_tracked_faces
+            tracks = smooth(raw, cuts) if cuts else smooth(raw)             # (no cuts: today's call, argument for argument)
             pbar.update(n_frames)
         else:
             pbar.update(n_frames * 2)
 
         # -- 2 - 4 of an aligned sequence with its frames resident on the device
         if has_aligned_frames and n_frames and self._aligned_stream_applies(frames_bgr, final_upscale_factor):
-            out = self._aligned_streamed(frames_bgr, max_clip_length, final_upscale_factor, pbar, as_u8)
+            out = self._aligned_streamed(frames_bgr, max_clip_length, final_upscale_factor, pbar, as_u8, scene=scene)
             if out is not None:                         # (None: the device resize failed and turned itself off)
                 return out
 
@@ -1708,11 +1812,15 @@ class KEEPFaceProcessor:
         crops, affines, faces_per_frame, input_hw = [], [], [], [None] * n_frames
         stream_ok = (not has_aligned_frames) and self._stream_applies(helper, frames_bgr, None, draw_box)
         presence = [] if self._per_track else None      # track clips: the keys of the tracks behind every frame's crops, in face order
+        scene_of = None
+        if scene and has_aligned_frames:                # an aligned sequence is one track per scene: its key is the scene's index
+            from .scene_cuts import segments
+            scene_of = [s for s, (a, b) in enumerate(segments(n_frames, self._scene_cuts_of(frames_bgr))) for _ in range(a, b)]
         for i in tqdm(range(n_frames), desc="Cropping and aligning faces"):
             if has_aligned_frames:
                 frame_crops, frame_aff = [self._aligned_face(frames_bgr[i])], []
                 if presence is not None:
-                    presence.append([0])                 # (one track on every frame: the plan is the cut of the flat list)
+                    presence.append([0 if scene_of is None else scene_of[i]])   # (one track on every frame: the plan is the cut of the flat list)
             else:
                 frame_crops, frame_aff = [], []
                 active = [seq[i] for seq in tracks.values() if not np.isnan(seq[i]).any()]

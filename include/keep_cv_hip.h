@@ -162,6 +162,20 @@ int32_t keep_gm_ffn_x1(const float* src, const float* msg, const void* w0_x1, fl
                        const float* ln_gamma, const float* ln_beta, float ln_eps, float* out, int64_t M, int32_t C, int32_t hidden,
                        int32_t exact_act, void* stream);
 
+/* ---- the scene-cut signature of a frame (modules/scene_cuts.py: frame_signature_host is the same arithmetic on the host): a 4 x 4 grid of
+ * 16-bin luma histograms, integers throughout.  Per pixel (x, y) of frame n:
+ *
+ *     Y = (29 * B + 150 * G + 77 * R + 128) >> 8      (the weights sum to 256: Y <= 255)
+ *     sig[n][(((y * 4) / H) * 4 + (x * 4) / W) * 16 + (Y >> 4)] += 1
+ *
+ * so the 256 counters of a frame sum to H * W.  keep_frame_signature_u8: `frames` [N,H,W,3] uint8 BGR and `sig` [N,256] int32 are
+ * contiguous DEVICE memory; `frames` needs NO alignment (a view into a larger buffer does).  `sig` is OVERWRITTEN: its zero-fill is
+ * queued on `stream` in front of the counting kernel, which adds one total per (block, counter) with vector global atomics on integers.
+ * A frame's counters therefore depend neither on N, on the frames beside it, on the launch geometry nor on the run.  KEEP_EINVAL, before
+ * anything is launched: a null pointer; N, H or W <= 0; H or W >= 32768. */
+int32_t keep_frame_signature_u8(const uint8_t* frames /*device [N,H,W,3] BGR*/, int32_t N, int32_t H, int32_t W,
+                                int32_t* sig /*device [N,256]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
