@@ -397,6 +397,7 @@ struct PasteP {
   double m00, m01, m02, m10, m11, m12;   // destination -> source map (inverse of the matrix given to cv2.warpAffine)
   int H, W, fh, fw, x0, y0, bw, bh, border;
   const float* frame_mask;   // use_parse=False: the soft mask already in FRAME space [H,W] (FH:411-415); then `mask` is unused
+  float opacity;             // the face's weight in the blend, [0, 1]: soft mask * opacity (keep_paste_face_w; 1.0f: the reference's blend)
 };
 
 __device__ __forceinline__ float mask_at(const PasteP& p, int sy, int sx) {
@@ -436,6 +437,7 @@ __global__ void paste_face_kernel(PasteP p) {
     soft = add_rn(soft, mul_rn(mask_at(p, sy + 1, sx), w10));
     soft = add_rn(soft, mul_rn(mask_at(p, sy + 1, sx + 1), w11));
   }
+  soft = mul_rn(soft, p.opacity);                                                        // (x * 1.0f == x: keep_paste_face is what it was)
   const float inv = sub_rn(1.f, soft);
   // face: 15-bit integer weights, (sum + 2^14) >> 15
   const int i00 = (32 - fx) * (32 - fy) * 32, i01 = fx * (32 - fy) * 32, i10 = (32 - fx) * fy * 32, i11 = fx * fy * 32;
@@ -448,12 +450,14 @@ __global__ void paste_face_kernel(PasteP p) {
   }
 }
 
-extern "C" int32_t keep_paste_face(float* frame, int32_t H, int32_t W, const uint8_t* face, const float* mask, int32_t fh, int32_t fw,
-                                   const double* dst_to_src, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t mask_border,
-                                   void* stream) {
-  KEEP_REQUIRE(frame && face && mask && dst_to_src && H > 0 && W > 0 && fh > 1 && fw > 1, "keep_paste_face: bad arguments");
+// The one launcher of both entries: `name` opens the messages.
+static int32_t paste_face_launch(const char* name, float* frame, int32_t H, int32_t W, const uint8_t* face, const float* mask, int32_t fh,
+                                 int32_t fw, const double* dst_to_src, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t mask_border,
+                                 float opacity, void* stream) {
+  KEEP_REQUIRE(frame && face && mask && dst_to_src && H > 0 && W > 0 && fh > 1 && fw > 1, "%s: bad arguments", name);
   // mask_border < 0: `mask` is a FRAME-space soft mask [H,W] (use_parse=False path), sampled at the destination pixel
-  KEEP_REQUIRE(x0 >= 0 && y0 >= 0 && x1 <= W && y1 <= H, "keep_paste_face: box outside the frame");
+  KEEP_REQUIRE(x0 >= 0 && y0 >= 0 && x1 <= W && y1 <= H, "%s: box outside the frame", name);
+  KEEP_REQUIRE(opacity >= 0.f && opacity <= 1.f, "%s: opacity must lie in [0, 1], got %f", name, (double)opacity);   // (NaN fails both)
   if (x1 <= x0 || y1 <= y0) return KEEP_OK;        // the face does not touch the frame
   PasteP p;
   p.acc = frame; p.face = face; p.mask = mask;
@@ -462,7 +466,22 @@ extern "C" int32_t keep_paste_face(float* frame, int32_t H, int32_t W, const uin
   p.H = H; p.W = W; p.fh = fh; p.fw = fw; p.x0 = x0; p.y0 = y0; p.bw = x1 - x0; p.bh = y1 - y0;
   p.border = mask_border < 0 ? 0 : mask_border;
   p.frame_mask = mask_border < 0 ? mask : nullptr;
+  p.opacity = opacity;
   hipLaunchKernelGGL(paste_face_kernel, dim3(cdiv(p.bw, 32), cdiv(p.bh, 8)), dim3(256), 0, (hipStream_t)stream, p);
-  KEEP_LAUNCH_CHECK("keep_paste_face");
+  KEEP_LAUNCH_CHECK(name);
   return KEEP_OK;
+}
+
+extern "C" int32_t keep_paste_face(float* frame, int32_t H, int32_t W, const uint8_t* face, const float* mask, int32_t fh, int32_t fw,
+                                   const double* dst_to_src, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t mask_border,
+                                   void* stream) {
+  return paste_face_launch("keep_paste_face", frame, H, W, face, mask, fh, fw, dst_to_src, x0, y0, x1, y1, mask_border, 1.0f, stream);
+}
+
+// ---- the same composite with the face's weight scaled: soft = soft mask * opacity before the blend (track lifetimes: a face fades in and
+// out at the ends of its lifetime).  opacity 1.0f is keep_paste_face bit for bit; 0.0f leaves the frame as it is (0 * v + 1 * x).
+extern "C" int32_t keep_paste_face_w(float* frame, int32_t H, int32_t W, const uint8_t* face, const float* mask, int32_t fh, int32_t fw,
+                                     const double* dst_to_src, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t mask_border,
+                                     float opacity, void* stream) {
+  return paste_face_launch("keep_paste_face_w", frame, H, W, face, mask, fh, fw, dst_to_src, x0, y0, x1, y1, mask_border, opacity, stream);
 }

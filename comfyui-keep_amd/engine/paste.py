@@ -169,16 +169,27 @@ class GpuPaster:
         L.call('keep_sep_filter', a, None, None, tmp, b, 1, H, W, kern, blur)
         return b
 
-    def paste(self, frame_u8, faces_u8, inverse_affines, parse_classes=None, upscale_factor=1.0, draw_box=False):
+    def paste(self, frame_u8, faces_u8, inverse_affines, parse_classes=None, upscale_factor=1.0, draw_box=False, weights=None):
         """frame_u8: uint8 [H,W,3] (numpy or tensor; the background at the output size), faces_u8: uint8 [F,fh,fw,3],
         inverse_affines: F crop -> frame matrices (``get_inverse_affine``; None entries are skipped), parse_classes: uint8
         [F,fh,fw] (``use_parse=True``) or None (``use_parse=False``: the erosion mask above, ``upscale_factor`` as the helper's).
+        ``weights`` (track lifetimes: a face fades at the ends of its lifetime): per face its weight in [0, 1]; the soft mask is multiplied
+        by it before the blend (``keep_paste_face_w``).  None, or a weight of 1.0, takes ``keep_paste_face``; ``draw_box`` ignores it.
         Returns the composited uint8 [H,W,3] tensor on the device, or None when a face needs a blur wider than the kernels take
         (the caller falls back to the helper)."""
         frame = torch.as_tensor(frame_u8).to(self.device, non_blocking=True).contiguous()
         faces = torch.as_tensor(faces_u8).to(self.device, non_blocking=True).contiguous()
         H, W, _ = frame.shape
         F, fh, fw, _ = faces.shape
+        if weights is not None and len(weights) != F:
+            raise ValueError(f"GpuPaster.paste: {len(weights)} weights for {F} faces")
+
+        def blend(i, mask, d2s, box, border):
+            w = 1.0 if weights is None else float(weights[i])
+            if w == 1.0:
+                L.call('keep_paste_face', acc, H, W, faces[i], mask, fh, fw, d2s, *box, border)
+            else:
+                L.call('keep_paste_face_w', acc, H, W, faces[i], mask, fh, fw, d2s, *box, border, C.c_float(w))
         with torch.cuda.device(self.device):
             masks = None
             if parse_classes is not None:
@@ -195,9 +206,9 @@ class GpuPaster:
                     fm = self.erosion_mask(d2s, H, W, fh, fw, upscale_factor)
                     if fm is None:
                         return None
-                    L.call('keep_paste_face', acc, H, W, faces[i], fm, fh, fw, d2s, x0, y0, x1, y1, -1)
+                    blend(i, fm, d2s, (x0, y0, x1, y1), -1)
                     continue
-                L.call('keep_paste_face', acc, H, W, faces[i], masks[i], fh, fw, d2s, x0, y0, x1, y1, PARSE_BORDER)
+                blend(i, masks[i], d2s, (x0, y0, x1, y1), PARSE_BORDER)
             out = torch.empty((H, W, 3), dtype=torch.uint8, device=self.device)
             L.call('keep_f32_round_u8', acc, out, acc.numel())
             if draw_box:            # :393-400,467-475: green borders over the finished frame, one warped border mask per face

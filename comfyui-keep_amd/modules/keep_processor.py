@@ -56,6 +56,12 @@ Scene cuts (``KEEP_AMD_SCENE_CUTS``, off by default, implies track clips): conse
 luma histograms; ``keep_frame_signature_u8`` on the chunks the frame store holds, the host restatement elsewhere -- the same integers) are
 at least ``scene_cut_threshold`` apart are a hard cut: every scene is tracked and smoothed on its own, no clip spans a cut and no state
 is carried across one.  A video of scenes A then B equals A and B processed as two videos, bit for bit (tests/test_gpu_scene_cuts.py).
+
+Track lifetimes (``KEEP_AMD_TRACK_LIFETIMES``, off by default, implies track clips): the reference's smoothing holds a track's end values
+over the whole video, so every track has a face on every frame, and one detector miss ends a track and starts a duplicate.  With the knob
+the raw tracks are stitched over gaps of at most ``track_max_gap`` frames and a track lives from its first to its last detection
+(``face_tracks.py``); outside it nothing is cropped, restored or pasted.  A lifetime equals its frames processed as a video of their own,
+bit for bit (tests/test_gpu_track_lifetimes.py).  ``track_fade`` ramps the paste weight at a lifetime's ends (``keep_paste_face_w``).
 """
 import os
 
@@ -64,7 +70,7 @@ import torch
 from tqdm import tqdm
 
 from .utils import comfy_image_to_cv2, crops_to_net_input, cv2_to_comfy_image, net_output_to_bgr_u8
-from .face_tracks import smooth_center_face, smooth_tracked_faces
+from .face_tracks import fade_weights, smooth_center_face, smooth_tracked_faces
 
 try:  # ComfyUI runtime
     from comfy.utils import ProgressBar, tiled_scale
@@ -503,6 +509,23 @@ class KEEPFaceProcessor:
             self.scene_cut_threshold = float(os.environ.get('KEEP_AMD_SCENE_CUT_THRESHOLD', '') or 0.4)
         except ValueError:
             self.scene_cut_threshold = 0.4
+        # the reference's gap interpolation holds a track's end values (np.interp), so a face seen on 10 of 300 frames is cropped, restored
+        # and pasted on all 300, and a track that misses one detection dies and is doubled by the new track of the same person.
+        # KEEP_AMD_TRACK_LIFETIMES=1 (or setting the attribute; implies track clips): raw tracks are stitched over gaps of at most
+        # ``track_max_gap`` frames (KEEP_AMD_TRACK_MAX_GAP, default 10: a setting, not a measured optimum) and a track lives from its first to
+        # its last detection (``face_tracks.py``).  ``track_fade`` (KEEP_AMD_TRACK_FADE, default 0 frames): the paste weight ramps over that
+        # many frames at an end of a lifetime that is not an end of the video or of a scene.  No parity mode and no re-identification
+        # tracker.  A single image and an aligned sequence ignore the knob.  After a call with the knob on ``last_track_lifetimes`` lists
+        # (key, first_frame, last_frame, n_detections).
+        self.track_lifetimes = os.environ.get('KEEP_AMD_TRACK_LIFETIMES', '0') == '1'
+        try:
+            self.track_max_gap = max(0, int(os.environ.get('KEEP_AMD_TRACK_MAX_GAP', '') or 10))
+        except ValueError:
+            self.track_max_gap = 10
+        try:
+            self.track_fade = max(0, int(os.environ.get('KEEP_AMD_TRACK_FADE', '') or 0))
+        except ValueError:
+            self.track_fade = 0
         # paste-back compositing on the GPU (engine/paste.py).  Opt-in: its arithmetic restates OpenCV's and
         # could not be checked against cv2 itself in the build image.
         # KEEP_AMD_GPU_PASTE: '1' on, '0' off; unset = 'auto': the first paste runs ``opencv_agrees_with_gpu_paste`` -- the HIP
@@ -903,7 +926,7 @@ class KEEPFaceProcessor:
         return out if out is not None else _host(bg_img_final)
 
     # ------------------------------------------------------------------ paste-back
-    def _paste(self, helper, bg, draw_box, src_hw=None):
+    def _paste(self, helper, bg, draw_box, src_hw=None, weights=None):
         """``helper.paste_faces_to_input_image(upsample_img=bg, draw_box=..., face_upsampler=...)`` behind one call
         (face_restoration_helper.py:346-475).  With ``gpu_paste`` and the configuration the loader builds (use_parse=True,
         colour frame already at the output size, no box, no face upsampler, every crop at the helper's face size) the
@@ -912,16 +935,28 @@ class KEEPFaceProcessor:
 
         ``src_hw``: the size of the frame the background was made from.  Where ``read_image`` enlarged that frame (short side below 512)
         the background fails the size test alone; with the device resizes on it is brought to the enlarged size times the factor here
-        (:357-358) and the GPU paste keeps the frame."""
+        (:357-358) and the GPU paste keeps the frame.
+
+        ``weights`` (track lifetimes with ``track_fade``): per face its weight in the composite, which only the GPU paste takes
+        (``keep_paste_face_w``); where the helper's own paste takes the frame a fade is ignored, with one logged warning."""
+        wkw = {} if weights is None else {'weights': weights}        # (without a fade: today's calls, argument for argument)
         if self._gpu_cv_path():
             if self._gpu_paste_applies(helper, bg, draw_box):
-                return self._paste_gpu(helper, bg, draw_box)
+                return self._paste_gpu(helper, bg, draw_box, **wkw)
             hw2 = self._enlarged_hw(*src_hw) if src_hw is not None and self.gpu_small_frames is not False else None
             if (hw2 is not None and tuple(getattr(getattr(helper, 'input_img', None), 'shape', ())[:2]) == hw2
                     and self._gpu_paste_applies(helper, bg, draw_box, size_test=False) and self._gpu_resize_path()):
                 up = getattr(helper, 'upscale_factor', 1)
-                return self._paste_gpu(helper, self._lanczos(bg, int(hw2[1] * up), int(hw2[0] * up), on_device=True), draw_box)
+                return self._paste_gpu(helper, self._lanczos(bg, int(hw2[1] * up), int(hw2[0] * up), on_device=True), draw_box, **wkw)
+        self._fade_ignored(weights)
         return helper.paste_faces_to_input_image(upsample_img=_host(bg), draw_box=draw_box, face_upsampler=self.face_upscale_model)
+
+    def _fade_ignored(self, weights):
+        """The helper's own paste has no per-face weight: a fade is dropped there, with one logged warning per processor."""
+        if weights is not None and any(w != 1.0 for w in weights) and not getattr(self, '_fade_warned', False):
+            self._fade_warned = True
+            import logging
+            logging.getLogger('ComfyUI-KEEP').warning("KEEP_AMD_TRACK_FADE: the helper's own paste takes this frame; faces are pasted without a fade")
 
     def _gpu_cv_path(self):
         """Whether the OpenCV-arithmetic kernels (paste-back, crop warp) may stand in for cv2: forced by KEEP_AMD_GPU_PASTE, else
@@ -983,7 +1018,7 @@ class KEEPFaceProcessor:
                                               for f in faces)
 
     @torch.no_grad()
-    def _paste_gpu(self, helper, bg, draw_box=False):
+    def _paste_gpu(self, helper, bg, draw_box=False, weights=None):
         from ..engine import hiplib as L
         from ..engine.paste import GpuPaster
         if self._paster is None:
@@ -991,9 +1026,11 @@ class KEEPFaceProcessor:
         faces = torch.from_numpy(np.ascontiguousarray(np.stack(
             [np.asarray(f) if np.asarray(f).ndim == 3 else np.repeat(np.asarray(f)[:, :, None], 3, axis=2)      # GRAY2BGR
              for f in helper.restored_faces]))).to(self.device)
+        wkw = {} if weights is None else {'weights': list(weights)}
         if not getattr(helper, 'use_parse', False):       # :386-415 erosion mask instead of the parse mask
-            out = self._paster.paste(bg, faces, list(helper.inverse_affine_matrices), None, getattr(helper, 'upscale_factor', 1), draw_box)
+            out = self._paster.paste(bg, faces, list(helper.inverse_affine_matrices), None, getattr(helper, 'upscale_factor', 1), draw_box, **wkw)
             if out is None:                                # a face larger than the blur kernel takes: the helper's own path
+                self._fade_ignored(weights)
                 return helper.paste_faces_to_input_image(upsample_img=_host(bg), draw_box=draw_box, face_upsampler=None)
             return out.cpu().numpy()
         # :418-424  BGR uint8 -> RGB float (x/255 - 0.5)/0.5, one face per ParseNet call like the reference
@@ -1009,7 +1046,7 @@ class KEEPFaceProcessor:
                 logits = helper.face_parse(x[i:i + 1].permute(0, 3, 1, 2).contiguous())[0]
                 classes.append(logits.argmax(dim=1).squeeze(0).to(torch.uint8))
             classes = torch.stack(classes)
-        out = self._paster.paste(bg, faces, list(helper.inverse_affine_matrices), classes, getattr(helper, 'upscale_factor', 1), draw_box)
+        out = self._paster.paste(bg, faces, list(helper.inverse_affine_matrices), classes, getattr(helper, 'upscale_factor', 1), draw_box, **wkw)
         return out.cpu().numpy()
 
     # ------------------------------------------------------------------ streamed restore + paste (round 5)
@@ -1042,7 +1079,7 @@ class KEEPFaceProcessor:
         return tuple(getattr(helper, 'face_size', (512, 512))) == (512, 512)
 
     def _restore_and_paste_streamed(self, frames_bgr, crops, affines, faces_per_frame, max_clip_length, factor, draw_box, pbar,
-                                    as_u8, store=None, input_hw=None, plan=None):
+                                    as_u8, store=None, input_hw=None, plan=None, weights=None):
         """Steps 3 and 4 of ``process_image_sequence`` (keep_processor.py:263-304) as ONE pipeline on the GPU.
 
         ``run_clips_u8(sink=...)`` restores the clips in batch groups and hands each finished, range-checked group over as device
@@ -1063,7 +1100,10 @@ class KEEPFaceProcessor:
 
         ``plan`` (track clips): ``plan_track_clips``' (clips, slot_of) instead of the cut of the flat list.  Crop numbering, ``first``,
         ``affines`` and the paste order stay; a clip's position k is crop ``clips[c][k]``.  With a store the crop tensor is laid out by
-        slot (``_stored_sequence``), so the clips still are views of it."""
+        slot (``_stored_sequence``), so the clips still are views of it.
+
+        ``weights`` (track lifetimes with ``track_fade``): per crop, in the order of ``affines``, the weight of its face in the composite
+        (``GpuPaster.paste(weights=...)``); None: every face at 1.0, today's calls."""
         from ..engine import hiplib as L
         from ..engine.paste import GpuPaster
         helper, net, dev = self.face_helper, self.keep_net, torch.device(self.device)
@@ -1161,11 +1201,12 @@ class KEEPFaceProcessor:
                     helper.affine_matrices = affines[st['aff']:st['aff'] + k]
                     helper.upscale_factor = factor
                     helper.get_inverse_affine(None)
+                    wkw = {} if weights is None else {'weights': weights[st['aff']:st['aff'] + k]}
                     st['aff'] += k
                     ids = range(first[t], first[t + 1])
                     faces = torch.stack([on_dev(ready[i]) for i in ids])
                     cls = torch.stack([on_dev(classes[i]) for i in ids])
-                    emit(t, paster.paste(bg, faces, list(helper.inverse_affine_matrices), cls, factor, draw_box))
+                    emit(t, paster.paste(bg, faces, list(helper.inverse_affine_matrices), cls, factor, draw_box, **wkw))
                     pbar.update(1)
                     if store is not None and t + 1 == store.spans[t // store.chunk][1]:
                         store.release(t // store.chunk, ps)             # (the allocator waits for this stream's reads)
@@ -1406,7 +1447,7 @@ class KEEPFaceProcessor:
         store.dead = True
         store.drop()
 
-    def _stored_sequence(self, store, frames_bgr, tracks, max_clip_length, factor, draw_box, pbar, as_u8):
+    def _stored_sequence(self, store, frames_bgr, tracks, max_clip_length, factor, draw_box, pbar, as_u8, fade=None):
         """Steps 2 - 4 of a detected sequence over its frame store: the similarity matrices are fitted on the host as in ``_align_warp``
         (``read_image`` is not called again: the pre-pass showed that it leaves these frames as they are, or enlarges them the way the store
         did), ONE ``keep_warp_affine_batch_u8``
@@ -1451,9 +1492,17 @@ class KEEPFaceProcessor:
         affines = [M for ms in per_frame for M in ms]
         try:
             return self._restore_and_paste_streamed(frames_bgr, crops, affines, faces_per_frame, max_clip_length, factor, draw_box, pbar,
-                                                    as_u8, store=store, plan=plan)
+                                                    as_u8, store=store, plan=plan, weights=self._fade_of(tracks, fade, n_frames))
         finally:
             store.drop(getattr(self, '_paste_stream', None))        # (nothing is left after ``ps.synchronize()``; an error's way out: the paste stream may still read)
+
+    @staticmethod
+    def _fade_of(tracks, fade, n_frames):
+        """``fade`` (``fade_weights``: per track key the weight of every frame) -> the paste weight of every crop, frame-major and in face
+        order like ``affines``; None without a fade."""
+        if fade is None:
+            return None
+        return [float(fade[key][i]) for i in range(n_frames) for key, seq in tracks.items() if not np.isnan(seq[i]).any()]
 
     def _track_plan(self, presence, max_clip_length):
         """``plan_track_clips`` for a sequence (``track_clips`` only): (clips as crop-index lists, slot of every crop); with
@@ -1465,9 +1514,9 @@ class KEEPFaceProcessor:
 
     @property
     def _per_track(self):
-        """Clips hold one track each: ``track_clips``, which ``track_carry`` and ``scene_cuts`` imply (in the flat frame-major cut a
-        clip spans the scene boundary whatever the tracks do)."""
-        return bool(self.track_clips or self.track_carry or getattr(self, 'scene_cuts', False))
+        """Clips hold one track each: ``track_clips``, which ``track_carry``, ``scene_cuts`` and ``track_lifetimes`` imply (in the flat
+        frame-major cut a clip spans the scene boundary, or the end of a lifetime, whatever the tracks do)."""
+        return bool(self.track_clips or self.track_carry or getattr(self, 'scene_cuts', False) or getattr(self, 'track_lifetimes', False))
 
     # ------------------------------------------------------------------ scene cuts
     def _scene_cuts_apply(self, frames_bgr):
@@ -1776,7 +1825,7 @@ class KEEPFaceProcessor:
         helper = self.face_helper
 
         # -- 1. landmarks per frame -> temporally smoothed tracks
-        tracks, store = {}, None
+        tracks, store, fade = {}, None, None             # fade (track lifetimes with ``track_fade``): per track key the paste weight of every frame
         scene = self._scene_cuts_apply(frames_bgr)      # (False with the knob off: nothing below computes, launches or writes anything new)
         cuts = None
         if not has_aligned_frames:
@@ -1791,7 +1840,13 @@ class KEEPFaceProcessor:
             if scene:
                 cuts = self._scene_cuts_of(frames_bgr, store.sig if store is not None else None)
             smooth = smooth_center_face if only_center_face else smooth_tracked_faces
-            tracks = smooth(raw, cuts) if cuts else smooth(raw)             # (no cuts: today's call, argument for argument)
+            life = {}
+            if getattr(self, 'track_lifetimes', False):                     # (off: today's call, argument for argument)
+                self.last_track_lifetimes = []
+                life = {'lifetimes': max(0, int(self.track_max_gap)), 'report': self.last_track_lifetimes}
+            tracks = smooth(raw, cuts, **life) if cuts else smooth(raw, **life)
+            if life and int(getattr(self, 'track_fade', 0) or 0) > 0:
+                fade = fade_weights(n_frames, self.last_track_lifetimes, int(self.track_fade), cuts)
             pbar.update(n_frames)
         else:
             pbar.update(n_frames * 2)
@@ -1804,7 +1859,7 @@ class KEEPFaceProcessor:
 
         # -- 2 - 4 of a detected sequence whose frames the pre-pass left on the device
         if store is not None:
-            out = self._stored_sequence(store, frames_bgr, tracks, max_clip_length, final_upscale_factor, draw_box, pbar, as_u8)
+            out = self._stored_sequence(store, frames_bgr, tracks, max_clip_length, final_upscale_factor, draw_box, pbar, as_u8, fade=fade)
             if out is not None:                         # (None: no faces at all, or the batched warp failed and turned the store off)
                 return out
 
@@ -1812,6 +1867,7 @@ class KEEPFaceProcessor:
         crops, affines, faces_per_frame, input_hw = [], [], [], [None] * n_frames
         stream_ok = (not has_aligned_frames) and self._stream_applies(helper, frames_bgr, None, draw_box)
         presence = [] if self._per_track else None      # track clips: the keys of the tracks behind every frame's crops, in face order
+        weights = self._fade_of(tracks, fade, n_frames)     # None without a fade: per crop, in the order of ``affines``, its paste weight
         scene_of = None
         if scene and has_aligned_frames:                # an aligned sequence is one track per scene: its key is the scene's index
             from .scene_cuts import segments
@@ -1842,9 +1898,12 @@ class KEEPFaceProcessor:
         plan = self._track_plan(presence, max_clip_length) if presence is not None else None
 
         # -- 3 + 4 streamed: restore group g+1 while group g is parsed, pasted and downloaded (round 5)
-        if crops and not has_aligned_frames and self._stream_applies(helper, frames_bgr, crops, draw_box):
+        # (small frames with a faceless frame: that frame keeps its size, the others are enlarged -- the streamed paste writes ONE output
+        # tensor, so the per-frame path takes the sequence; with track lifetimes faceless frames are common)
+        mixed = 0 in faces_per_frame and any(hw is not None and tuple(hw) != tuple(frames_bgr[i].shape[:2]) for i, hw in enumerate(input_hw))
+        if crops and not has_aligned_frames and not mixed and self._stream_applies(helper, frames_bgr, crops, draw_box):
             return self._restore_and_paste_streamed(frames_bgr, crops, affines, faces_per_frame, max_clip_length,
-                                                    final_upscale_factor, draw_box, pbar, as_u8, input_hw=input_hw, plan=plan)
+                                                    final_upscale_factor, draw_box, pbar, as_u8, input_hw=input_hw, plan=plan, weights=weights)
 
         # -- 3. restore: the hot path
         crops = [c.cpu().numpy() if isinstance(c, torch.Tensor) else c for c in crops]
@@ -1882,7 +1941,8 @@ class KEEPFaceProcessor:
             helper.affine_matrices = affines[aff_ptr:aff_ptr + k]
             helper.upscale_factor = final_upscale_factor
             helper.get_inverse_affine(None)
-            out_frames.append(self._paste(helper, bg, draw_box, src_hw=tuple(frames_bgr[i].shape[:2])))
+            wkw = {} if weights is None else {'weights': weights[aff_ptr:aff_ptr + k]}      # (without a fade: today's call)
+            out_frames.append(self._paste(helper, bg, draw_box, src_hw=tuple(frames_bgr[i].shape[:2]), **wkw))
             face_ptr += k
             aff_ptr += k
             pbar.update(1)

@@ -176,6 +176,19 @@ int32_t keep_gm_ffn_x1(const float* src, const float* msg, const void* w0_x1, fl
 int32_t keep_frame_signature_u8(const uint8_t* frames /*device [N,H,W,3] BGR*/, int32_t N, int32_t H, int32_t W,
                                 int32_t* sig /*device [N,256]*/, void* stream);
 
+/* ---- the paste-back composite of one face with a weight (track lifetimes: a face fades in and out at the ends of its lifetime).  The
+ * arguments, the two mask forms (mask_border >= 0: the blurred parse mask in face space; mask_border < 0: a soft mask in frame space) and
+ * every operation are those of the core header's keep_paste_face -- one kernel serves both entries -- with one float32 product added:
+ *
+ *     soft = soft * opacity            (directly after the soft mask value is formed, rounded on its own)
+ *     frame = soft * face + (1 - soft) * frame
+ *
+ * opacity 1.0f is the core entry bit for bit, 0.0f leaves `frame` bit-identical.  KEEP_EINVAL, before anything is launched: the core
+ * entry's refusals, and an opacity outside [0, 1] or NaN. */
+int32_t keep_paste_face_w(float* frame /*device [H,W,3]*/, int32_t H, int32_t W, const uint8_t* face /*device [fh,fw,3]*/,
+                          const float* mask /*device*/, int32_t fh, int32_t fw, const double* dst_to_src /*host [6]*/, int32_t x0, int32_t y0,
+                          int32_t x1, int32_t y1, int32_t mask_border, float opacity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
