@@ -189,6 +189,28 @@ int32_t keep_paste_face_w(float* frame /*device [H,W,3]*/, int32_t H, int32_t W,
                           const float* mask /*device*/, int32_t fh, int32_t fw, const double* dst_to_src /*host [6]*/, int32_t x0, int32_t y0,
                           int32_t x1, int32_t y1, int32_t mask_border, float opacity, void* stream);
 
+/* ---- tone match of restored faces (engine/tone.py): the restored face keeps its high band and takes the low band of the crop it was made
+ * from,  out = rst + lowpass(src - rst),  a separable Gaussian in integers throughout.  Per channel, indices clamped at the borders
+ * (replicate), taps t[-R .. R]:
+ *
+ *     d  = src - rst                                  [-255, 255]
+ *     hh = sum_k t[k] * d[y, clamp(x + k, 0, w - 1)]  int32
+ *     h4 = (hh + 128) >> 8                            (arithmetic shift = floor) |h4| <= 4080: int16, 4 fractional bits
+ *     v  = sum_k t[k] * h4[clamp(y + k, 0, h - 1), x] int32
+ *     out = clamp(rst + ((v + 32768) >> 16), 0, 255)
+ *
+ * No float and no atomic: the result depends neither on the summation order, the launch geometry nor F.  src == rst gives out == rst;
+ * src == rst + c without saturation gives out == src.
+ *
+ * keep_tone_match_u8: `src`, `rst`, `out` [F,h,w,3] uint8 and `scratch` (F*h*w*3 int16, contents afterwards unspecified) are contiguous
+ * DEVICE memory of any alignment; `taps` [2R+1] is a HOST array, read and validated before the call returns -- the int32 bounds above rest
+ * on that check -- and travels in the kernel arguments: no allocation, no copy.  Two kernels per launch group on `stream`, F split where a
+ * grid extent would pass 2^31.  KEEP_EINVAL, before anything is launched: a null pointer; F, h or w <= 0; h or w >= 32768; R outside
+ * 1 .. 128; a negative tap; taps that do not sum to 4096; `out` or `scratch` overlapping `src`, `rst` or each other as byte ranges (a block
+ * reads its neighbours' pixels through the halo: in place is a race). */
+int32_t keep_tone_match_u8(const uint8_t* src, const uint8_t* rst, uint8_t* out, int16_t* scratch, int32_t F, int32_t h, int32_t w,
+                           const int16_t* taps /*host [2R+1]*/, int32_t R, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
