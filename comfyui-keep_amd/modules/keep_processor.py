@@ -62,15 +62,30 @@ over the whole video, so every track has a face on every frame, and one detector
 the raw tracks are stitched over gaps of at most ``track_max_gap`` frames and a track lives from its first to its last detection
 (``face_tracks.py``); outside it nothing is cropped, restored or pasted.  A lifetime equals its frames processed as a video of their own,
 bit for bit (tests/test_gpu_track_lifetimes.py).  ``track_fade`` ramps the paste weight at a lifetime's ends (``keep_paste_face_w``).
+
+One form of each thing: the clips of a crop list are lists of crop indices everywhere -- the flat cut is the plan whose clip c is
+``range(start, end)`` of span c (``_restore_crops_u8``, ``_restore_clips``, ``_restore_and_paste_streamed``); every device path that stands
+in for a cv2 call is decided by ``_gate`` from a row of ``opencv_checks.GATES``; both streamed paths write their output through
+``_HostOutput``.  The self-checks against cv2 live in ``opencv_checks.py``, the frame containers (``_ConvertedFrames``, ``_FrameStore``) in
+``frames.py``; their names are importable from here as before.
 """
+import logging
 import os
 
 import numpy as np
 import torch
 from tqdm import tqdm
 
+from . import opencv_checks
+from .frames import (FRAME_STORE_DEFAULT_GB, _ConvertedFrames, _FrameStore, cuda_device, frame_store_plan,  # noqa: F401  (the containers
+                     frames_from_comfy, uniform_u8_frames)                                                 # are read from here too)
+from .opencv_checks import (opencv_agrees_with_gpu_aligned_resize, opencv_agrees_with_gpu_detect_resize,  # noqa: F401  (read from here by
+                            opencv_agrees_with_gpu_paste, opencv_agrees_with_gpu_resize,                  # tests and tools; the gate itself
+                            opencv_agrees_with_gpu_small_frame_resize)                                    # asks ``opencv_checks``)
 from .utils import comfy_image_to_cv2, crops_to_net_input, cv2_to_comfy_image, net_output_to_bgr_u8
 from .face_tracks import fade_weights, smooth_center_face, smooth_tracked_faces
+
+log = logging.getLogger('ComfyUI-KEEP')
 
 try:  # ComfyUI runtime
     from comfy.utils import ProgressBar, tiled_scale
@@ -106,109 +121,60 @@ def _is_gray(img, threshold=10):
     return bool(d <= threshold)
 
 
-def opencv_agrees_with_gpu_paste(device):
-    """True iff the HIP paste-back (engine/paste.py) reproduces OpenCV bit for bit on this installation: the composite
-    of engine/synth.py's 1080p / 3-face case computed with cv2 calls in the order of face_restoration_helper.py:382,426-468
-    against ``GpuPaster.paste``, and the :316-318 crop warp against ``crop_faces``.  Raises ImportError without cv2."""
-    import cv2
-    from ..engine import paste as gp
-    from ..engine import synth
-    frame, faces, mats, classes = synth.synth_paste_case()
-    H, W = frame.shape[:2]
-    up = frame
-    lut = np.asarray(gp.MASK_COLORMAP, np.float32)
-    for face, M, cls in zip(faces, mats, classes):
-        inv_restored = cv2.warpAffine(face, M, (W, H))
-        m = lut[cls.astype(np.int64)]
-        m = cv2.GaussianBlur(cv2.GaussianBlur(m, (101, 101), 11), (101, 101), 11)
-        t = gp.PARSE_BORDER
-        m[:t, :] = 0; m[-t:, :] = 0; m[:, :t] = 0; m[:, -t:] = 0
-        soft = cv2.warpAffine(m / np.float32(255.0), M, (W, H))[:, :, None]
-        up = soft * inv_restored + (1 - soft) * up
-    ref = np.round(np.clip(up, 0, 255)).astype(np.uint8)
-    got = gp.GpuPaster(device).paste(frame, faces, list(mats), torch.from_numpy(classes)).cpu().numpy()
-    if not np.array_equal(got, ref):
-        return False
-    fwd = cv2.invertAffineTransform(mats[2])
-    crop = cv2.warpAffine(frame, fwd, (512, 512), borderMode=cv2.BORDER_CONSTANT, borderValue=gp.ALIGN_BORDER_BGR)
-    return bool(np.array_equal(gp.crop_faces(frame, [fwd], device=device)[0].cpu().numpy(), crop))
-
-
-def opencv_agrees_with_gpu_resize(device):
-    """True iff the HIP Lanczos resize (engine/resize.py) reproduces ``cv2.resize(..., INTER_LANCZOS4)`` bit for bit on this
-    installation: up- and down-scales of random frames, odd sizes, a geometry whose source coordinates land on whole pixels (the
-    1e30 branch of interpolateLanczos4) and a one-pixel-wide output.  Raises ImportError without cv2."""
-    import cv2
-    from ..engine.resize import Lanczos4Resizer
-    rz = Lanczos4Resizer(device)
-    rng = np.random.default_rng(0)
-    for (h, w), (h2, w2) in (((90, 160), (180, 320)), ((37, 53), (48, 68)), ((120, 200), (84, 140)), ((300, 9), (100, 3)),
-                             ((64, 64), (256, 256)), ((31, 17), (15, 1))):
-        img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
-        ref = cv2.resize(img, (w2, h2), interpolation=cv2.INTER_LANCZOS4)
-        if not np.array_equal(rz.resize_u8(img, w2, h2).cpu().numpy(), ref):
-            return False
-    return True
-
-
-def opencv_agrees_with_gpu_detect_resize(device):
-    """True iff the HIP area resize (engine/resize.py:AreaResizer) reproduces ``cv2.resize(..., INTER_AREA)`` bit for bit on this
-    installation: the detector-input geometries of 1080p and 720p video (short side to 640) and small frames with 2-3 taps, a scale
-    below 1.2 and a whole-number scale on one axis only.  Raises ImportError without cv2."""
-    import cv2
-    from ..engine.resize import AreaResizer
-    rz = AreaResizer(device)
-    rng = np.random.default_rng(0)
-    for (h, w), (h2, w2) in (((1080, 1920), (640, 1137)), ((720, 1280), (640, 1137)), ((54, 96), (32, 56)), ((45, 80), (40, 71)),
-                             ((48, 64), (16, 21)), ((270, 480), (160, 284))):
-        img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
-        ref = cv2.resize(img, (w2, h2), interpolation=cv2.INTER_AREA)
-        if not np.array_equal(rz.resize_u8(img, w2, h2).cpu().numpy(), ref):
-            return False
-    return True
-
-
-def opencv_agrees_with_gpu_aligned_resize(device):
-    """True iff the HIP bilinear resize (engine/resize.py:LinearResizer) reproduces ``cv2.resize(..., INTER_LINEAR)`` bit for bit on this
-    installation, at the aligned-face target of 512 x 512: an enlargement, a fractional shrink, the exact 2x shrink (INTER_AREA's 2 x 2
-    path inside cv2.resize), a non-square source and a one-pixel-wide source.  Raises ImportError without cv2."""
-    import cv2
-    from ..engine.resize import LinearResizer
-    rz = LinearResizer(device)
-    rng = np.random.default_rng(0)
-    for h, w in ((256, 256), (720, 720), (1024, 1024), (300, 400), (64, 1)):
-        img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
-        ref = cv2.resize(img, (512, 512), interpolation=cv2.INTER_LINEAR)
-        if not np.array_equal(rz.resize_u8(img, 512, 512).cpu().numpy(), ref):
-            return False
-    return True
-
-
 def small_frame_factor(h, w):
     """``f`` of ``read_image``'s enlargement (face_restoration_helper.py:182-184) for an [h,w] frame, or None where it does not enlarge."""
     return 512.0 / min(h, w) if 0 < min(h, w) < 512 else None
 
 
-def opencv_agrees_with_gpu_small_frame_resize(device):
-    """True iff the HIP bilinear enlargement (engine/resize.py:LinearResizer.enlarge_u8) reproduces ``cv2.resize(img, (0, 0), fx=f, fy=f,
-    interpolation=cv2.INTER_LINEAR)`` with ``f = 512.0 / min(h, w)`` bit for bit on this installation: landscape, portrait and a
-    one-pixel-high source.  Raises ImportError without cv2."""
-    import cv2
-    from ..engine.resize import LinearResizer
-    rz = LinearResizer(device)
-    rng = np.random.default_rng(0)
-    for h, w in ((360, 480), (480, 270), (240, 426), (1, 7)):
-        img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
-        f = 512.0 / min(h, w)
-        ref = cv2.resize(img, (0, 0), fx=f, fy=f, interpolation=cv2.INTER_LINEAR)
-        if not np.array_equal(rz.enlarge_u8(img, f, f).cpu().numpy(), ref):
-            return False
-    return True
-
-
 def _host(img):
     """A background / face that leaves the device path (the helper's own paste, a frame returned as it is): a host array."""
     return img.cpu().numpy() if isinstance(img, torch.Tensor) else img
+
+
+def _env_number(name, default, cast):
+    """The environment's ``name`` as ``cast`` (int / float); unset, empty or not a number: ``default``."""
+    try:
+        return cast(os.environ.get(name, '') or default)
+    except ValueError:
+        return default
+
+
+def _env_tristate(name):
+    """The environment's ``name``: '1' True, '0' False, anything else None (auto: ``KEEPFaceProcessor._gate`` decides)."""
+    return {'1': True, '0': False}.get(os.environ.get(name))
+
+
+def _sink_streaming(net):
+    """What both streamed paths ask first: ``KEEP_AMD_STREAM_PASTE`` is not 0, the net is the engine's (``run_clips_u8`` with ``sink``),
+    and the call is not inside a torch.distributed job."""
+    if os.environ.get('KEEP_AMD_STREAM_PASTE', '1') == '0' or not getattr(net, 'supports_sink', False):
+        return False
+    return not (torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1)
+
+
+class _HostOutput:
+    """The output tensor of a streamed path, [n,H',W',3] in host memory: uint8 BGR (``as_u8``) or ComfyUI's float RGB.  Allocated by the
+    first ``emit``, which knows the frame size."""
+
+    def __init__(self, n, as_u8, device):
+        self.n, self.as_u8, self.device, self.out = n, as_u8, device, None
+
+    def emit(self, f0, frames_dev):
+        """finished frames f0 .. (uint8 BGR [m,H',W',3] on the device) -> the output tensor, queued on the current stream"""
+        if self.out is None:
+            shape, dtype = (self.n,) + tuple(frames_dev.shape[1:]), torch.uint8 if self.as_u8 else torch.float32
+            try:
+                self.out = torch.empty(shape, dtype=dtype, pin_memory=True)
+            except RuntimeError:                                  # more than the host will pin: pageable memory, slower copies
+                self.out = torch.empty(shape, dtype=dtype)
+        dst = self.out[f0:f0 + frames_dev.shape[0]]
+        if self.as_u8:
+            dst.copy_(frames_dev, non_blocking=True)
+        else:                                                      # cv2_to_comfy_image on the device (keep_bgr_u8_to_comfy: one IEEE division)
+            from ..engine import hiplib as L
+            ff = torch.empty(frames_dev.shape, dtype=torch.float32, device=self.device)
+            L.call('keep_bgr_u8_to_comfy', frames_dev.contiguous(), ff, frames_dev.numel() // 3)
+            dst.copy_(ff, non_blocking=True)
 
 
 class _ReplayDetector:
@@ -243,227 +209,6 @@ class _DeviceFaces:
 
 
 _EMITTED = object()   # placeholder of a restored crop whose frame has been composited (streamed path)
-_PINNED_U8 = {}      # one cached pinned frame buffer per shape (hipHostMalloc of 0.8 GB costs ~0.1 s; frames never outlive the node call)
-
-
-class _ConvertedFrames:
-    """The node's IMAGE batch as uint8 BGR frames -- ``comfy_image_to_cv2`` (utils.py:155-160) for the whole sequence, on the device
-    (``keep_comfy_to_bgr_u8``: x * 255 in float32, truncating cast, RGB -> BGR) instead of three numpy passes per frame on one host
-    core: a worker thread uploads the float frames in chunks (pageable -> device), converts them and downloads the uint8 frames into
-    ONE pinned buffer; ``frames[i]`` / ``frames[a:b]`` wait only for the chunks they touch, so the detection pre-pass of the first
-    frames runs under the conversion of the rest.  Items are numpy views of the pinned buffer (what the helper and cv2 take)."""
-
-    def __init__(self, seq, device, chunk_bytes=128 << 20):
-        import threading
-        self.n, self.H, self.W = int(seq.shape[0]), int(seq.shape[1]), int(seq.shape[2])
-        self._seq, self._dev = seq, device
-        per = self.H * self.W * 3
-        self._chunk = max(1, min(self.n, chunk_bytes // (per * 4)))
-        self._nchunks = -(-self.n // self._chunk)
-        self._done = [threading.Event() for _ in range(self._nchunks)]
-        self._ready = threading.Event()          # the pinned buffer exists
-        self._err = None
-        self._arr = None
-        self._thread = threading.Thread(target=self._run, name='keep-comfy-convert', daemon=True)
-        self._thread.start()
-
-    def _run(self):
-        try:
-            from ..engine import hiplib as L
-            shape = (self.n, self.H, self.W, 3)
-            buf = _PINNED_U8.get(shape)
-            if buf is None:
-                _PINNED_U8.clear()
-                try:
-                    buf = torch.empty(shape, dtype=torch.uint8, pin_memory=True)
-                    _PINNED_U8[shape] = buf
-                except RuntimeError:                                  # more than the host will pin
-                    buf = torch.empty(shape, dtype=torch.uint8)
-            self._buf, self._arr = buf, buf.numpy()
-            self._ready.set()
-            with torch.cuda.device(self._dev):
-                st = torch.cuda.Stream(device=self._dev)
-                pend = None
-                with torch.cuda.stream(st):
-                    for c in range(self._nchunks):
-                        a, b = c * self._chunk, min(self.n, (c + 1) * self._chunk)
-                        src = self._seq[a:b]
-                        if not src.is_contiguous():
-                            src = src.contiguous()
-                        d = src.to(self._dev, non_blocking=True)      # (a pageable source: the call returns when the chunk is staged)
-                        u = torch.empty((b - a, self.H, self.W, 3), dtype=torch.uint8, device=self._dev)
-                        L.call('keep_comfy_to_bgr_u8', d, u, (b - a) * self.H * self.W)
-                        buf[a:b].copy_(u, non_blocking=True)
-                        ev = torch.cuda.Event()
-                        ev.record(st)
-                        if pend is not None:                           # chunk c - 1 finished under this chunk's upload
-                            pend[1].synchronize()
-                            self._done[pend[0]].set()
-                        pend = (c, ev)
-                    pend[1].synchronize()
-                    self._done[pend[0]].set()
-        except BaseException as e:                                     # (out of memory, a lost device ...): the host converter, loudly
-            import logging
-            logging.getLogger('ComfyUI-KEEP').warning("device-side IMAGE conversion failed (%s); converting on the host", e)
-            try:
-                self._arr = np.stack([comfy_image_to_cv2(self._seq[i].unsqueeze(0)) for i in range(self.n)])
-            except BaseException as e2:                                # surfaced by the first access
-                self._err = e2
-            self._ready.set()
-            for d in self._done:
-                d.set()
-
-    def _wait(self, a, b):
-        self._ready.wait()
-        for c in range(a // self._chunk, min(self._nchunks, -(-b // self._chunk))):
-            self._done[c].wait()
-        if self._err is not None:
-            raise self._err
-
-    def __len__(self):
-        return self.n
-
-    def __getitem__(self, i):
-        if isinstance(i, slice):
-            a, b, step = i.indices(self.n)
-            if step != 1:
-                return [self[j] for j in range(a, b, step)]
-            if b <= a:
-                return []
-            self._wait(a, b)
-            return [self._arr[j] for j in range(a, b)]
-        if i < 0:
-            i += self.n
-        if not 0 <= i < self.n:
-            raise IndexError(i)
-        self._wait(i, i + 1)
-        return self._arr[i]
-
-    def __iter__(self):
-        return (self[i] for i in range(self.n))
-
-
-def frames_from_comfy(seq, device):
-    """IMAGE batch [N,H,W,3] float32 (host or device) -> N uint8 BGR frames.  On the device when there is one and the library loads
-    (``_ConvertedFrames``); ``KEEP_AMD_DEVICE_CONVERT=0``, another dtype / layout, or no GPU: the per-frame host converter."""
-    dev = torch.device(device)
-    if (os.environ.get('KEEP_AMD_DEVICE_CONVERT', '1') != '0' and dev.type == 'cuda' and torch.cuda.is_available()
-            and isinstance(seq, torch.Tensor) and seq.dtype == torch.float32 and seq.dim() == 4 and seq.shape[-1] == 3
-            and seq.shape[0] > 0 and seq.shape[1] > 0 and seq.shape[2] > 0):
-        try:
-            from ..engine import hiplib as L
-            L.load()
-            if dev.index is None:
-                dev = torch.device('cuda', torch.cuda.current_device())
-            return _ConvertedFrames(seq, dev)
-        except Exception:
-            pass
-    return [comfy_image_to_cv2(seq[i].unsqueeze(0)) for i in range(seq.shape[0])]
-
-
-FRAME_STORE_DEFAULT_GB = 16.0     # KEEP_AMD_FRAME_STORE_GB: a policy (the store must not crowd out the clip batches sized from free HBM), not a measurement
-
-
-def frame_store_plan(frames, cap_bytes, chunk):
-    """The chunk spans [(start, stop)] of a device-resident frame store over ``frames``, or None where there is none: an empty
-    sequence, frames that are not uint8 [H,W,3] host arrays of ONE size, or more than ``cap_bytes`` in all (n * H * W * 3; exactly the cap
-    still applies).  A sequence over the cap takes the present path entirely: no partial stores.  ``chunk``: frames per chunk (the
-    detector's batch axis); the spans cover 0 .. n without overlap.  Pure: needs no device."""
-    n = len(frames)
-    if n == 0 or chunk < 1:
-        return None
-    if isinstance(frames, _ConvertedFrames):            # uint8 [H,W,3] by construction (asking a frame would wait for its conversion)
-        h, w = frames.H, frames.W
-    else:
-        shape = tuple(getattr(frames[0], 'shape', ()))
-        if len(shape) != 3 or shape[2] != 3:
-            return None
-        if any(not isinstance(f, np.ndarray) or f.dtype != np.uint8 or tuple(f.shape) != shape for f in frames):
-            return None
-        h, w = shape[:2]
-    if h <= 0 or w <= 0 or n * h * w * 3 > cap_bytes:
-        return None
-    return [(s, min(s + chunk, n)) for s in range(0, n, chunk)]
-
-
-class _FrameStore:
-    """The frames of one detected sequence on the device, one uint8 [m,H,W,3] tensor per chunk of the detection pre-pass, from the
-    pre-pass (which fills it and detects on it) over the crop warp to the paste-back (which reads the backgrounds from it).  Every
-    fill is followed by an event on the filling stream; a stream other than that one waits for it before its first read of the
-    chunk (``frame``).  A chunk is let go once its last frame has been emitted (``release``): the caching allocator is told which
-    stream read it last, so the memory is not handed out again before that stream has passed the read.
-
-    Small frames (``small = (f, H2, W2)``, set by the pre-pass when ``read_image`` enlarges the first frame): a chunk is kept twice, the
-    original frames (``bufs``: the paste-back's backgrounds) and their enlargement (``ebufs``, ``enlarge``: the detector batch and what the
-    crop warp reads, let go after that warp)."""
-
-    def __init__(self, spans, h, w, device, cap_bytes=None):
-        self.spans, self.h, self.w, self.device = list(spans), int(h), int(w), device
-        self.cap_bytes = cap_bytes
-        self.small = None
-        self.sig = None                   # scene cuts: int32 [n_frames,256] on the device, row t the signature of frame t (``fill`` writes it)
-        self.ebufs = [None] * len(self.spans)
-        self.chunk = self.spans[0][1] - self.spans[0][0]
-        self.bufs = [None] * len(self.spans)
-        self.events = [None] * len(self.spans)
-        self._waited = [False] * len(self.spans)
-        self.dead = False                 # a frame ``read_image`` changed, or a failure: the sequence takes the present path
-
-    def fill(self, k, frames):
-        a, b = self.spans[k]
-        if len(frames) != b - a:
-            raise ValueError(f"frame store: chunk {k} holds frames {a} .. {b - 1}, got {len(frames)}")
-        with torch.cuda.device(self.device):
-            buf = torch.empty((b - a, self.h, self.w, 3), dtype=torch.uint8, device=self.device)
-            for i, fr in enumerate(frames):
-                buf[i].copy_(torch.from_numpy(np.ascontiguousarray(fr)), non_blocking=True)
-            if self.sig is not None:      # the chunk's signatures: one launch behind its copies, on the frames as they came
-                try:
-                    from ..engine import hiplib as L
-                    L.call('keep_frame_signature_u8', buf, b - a, self.h, self.w, self.sig[a:b])
-                except Exception as e:    # the opt-in mode's trouble is not the store's: logged, and the host function takes the signatures
-                    import logging
-                    logging.getLogger('ComfyUI-KEEP').warning("frame signatures on the device failed (%s): the host function", e)
-                    self.sig = None
-            ev = torch.cuda.Event()
-            ev.record()
-        self.bufs[k], self.events[k] = buf, ev
-        return buf
-
-    def enlarge(self, k, resizer):
-        """Chunk k's frames through ``read_image``'s enlargement: one launch on the current stream, behind the fill."""
-        f = self.small[0]
-        with torch.cuda.device(self.device):
-            ebuf = resizer.enlarge_u8(self.bufs[k], f, f)
-            ev = torch.cuda.Event()
-            ev.record()
-        self.ebufs[k], self.events[k] = ebuf, ev
-        return ebuf
-
-    def warp_source(self, k):
-        """What the crop warp of chunk k reads: the frames the landmarks live in."""
-        return self.bufs[k] if self.small is None else self.ebufs[k]
-
-    def complete(self):
-        return all(b is not None for b in self.bufs)
-
-    def frame(self, t, stream):
-        """Frame t, uint8 [H,W,3], for work queued on ``stream`` (which waits for the chunk's fill first)."""
-        k = t // self.chunk
-        if not self._waited[k]:
-            stream.wait_event(self.events[k])
-            self._waited[k] = True
-        return self.bufs[k][t - self.spans[k][0]]
-
-    def release(self, k, stream=None):
-        buf = self.bufs[k]
-        if buf is not None and stream is not None:
-            buf.record_stream(stream)
-        self.bufs[k] = self.ebufs[k] = None             # (the enlarged chunk is read on the stream that made it)
-
-    def drop(self, stream=None):
-        for k in range(len(self.spans)):
-            self.release(k, stream)
 
 
 def split_clips(num_faces: int, max_clip_length: int):
@@ -505,10 +250,7 @@ class KEEPFaceProcessor:
         # state reset, which every clip boundary causes by default anyway; a missed cut leaves today's behaviour.  After a call with the
         # knob on ``last_scene_cuts`` (list of int) and ``last_scene_distances`` (float [n - 1]) say what was found.
         self.scene_cuts = os.environ.get('KEEP_AMD_SCENE_CUTS', '0') == '1'
-        try:
-            self.scene_cut_threshold = float(os.environ.get('KEEP_AMD_SCENE_CUT_THRESHOLD', '') or 0.4)
-        except ValueError:
-            self.scene_cut_threshold = 0.4
+        self.scene_cut_threshold = _env_number('KEEP_AMD_SCENE_CUT_THRESHOLD', 0.4, float)
         # the reference's gap interpolation holds a track's end values (np.interp), so a face seen on 10 of 300 frames is cropped, restored
         # and pasted on all 300, and a track that misses one detection dies and is doubled by the new track of the same person.
         # KEEP_AMD_TRACK_LIFETIMES=1 (or setting the attribute; implies track clips): raw tracks are stitched over gaps of at most
@@ -518,49 +260,36 @@ class KEEPFaceProcessor:
         # tracker.  A single image and an aligned sequence ignore the knob.  After a call with the knob on ``last_track_lifetimes`` lists
         # (key, first_frame, last_frame, n_detections).
         self.track_lifetimes = os.environ.get('KEEP_AMD_TRACK_LIFETIMES', '0') == '1'
-        try:
-            self.track_max_gap = max(0, int(os.environ.get('KEEP_AMD_TRACK_MAX_GAP', '') or 10))
-        except ValueError:
-            self.track_max_gap = 10
-        try:
-            self.track_fade = max(0, int(os.environ.get('KEEP_AMD_TRACK_FADE', '') or 0))
-        except ValueError:
-            self.track_fade = 0
+        self.track_max_gap = max(0, _env_number('KEEP_AMD_TRACK_MAX_GAP', 10, int))
+        self.track_fade = max(0, _env_number('KEEP_AMD_TRACK_FADE', 0, int))
         # paste-back compositing on the GPU (engine/paste.py).  Opt-in: its arithmetic restates OpenCV's and
         # could not be checked against cv2 itself in the build image.
         # KEEP_AMD_GPU_PASTE: '1' on, '0' off; unset = 'auto': the first paste runs ``opencv_agrees_with_gpu_paste`` -- the HIP
         # path against cv2 itself on a synthetic 1080p / 3-face frame, bit for bit -- and switches the GPU path on only if that
         # holds on this installation (cv2 is a hard dependency of the reference helper, so it exists wherever this code pastes).
-        env = os.environ.get('KEEP_AMD_GPU_PASTE')
-        self.gpu_paste = {'1': True, '0': False}.get(env, None)
-        self._gpu_paste_forced = env == '1'        # the erosion-mask branch (use_parse=False) is not part of the cv2 self-check
+        self.gpu_paste = _env_tristate('KEEP_AMD_GPU_PASTE')
+        self._gpu_paste_forced = os.environ.get('KEEP_AMD_GPU_PASTE') == '1'        # the erosion-mask branch (use_parse=False) is not part of the cv2 self-check
         self._paster = None
+        self._resizers = {}             # ``_resizer``: one per class of engine/resize.py, built on first use
         # final_upscale_factor != 1: the INTER_LANCZOS4 resize of the background (and of aligned outputs) on the device
         # (engine/resize.py).  KEEP_AMD_GPU_RESIZE: '1' on, '0' off (cv2.resize on the host); unset = auto: with cv2 the first resize
         # runs ``opencv_agrees_with_gpu_resize`` and the device path is used only if it is bit-equal to cv2; without cv2 the device
         # path is the only one there is.
-        env = os.environ.get('KEEP_AMD_GPU_RESIZE')
-        self.gpu_resize = {'1': True, '0': False}.get(env, None)
-        self._resizer = None
+        self.gpu_resize = _env_tristate('KEEP_AMD_GPU_RESIZE')
         # the INTER_AREA resize of the detector inputs (face_restoration_helper.py:206-216) on the device (engine/resize.py:AreaResizer;
         # ``_prep_detect_chunk``).  KEEP_AMD_GPU_DETECT_RESIZE: '1' on, '0' off; unset = auto, decided like KEEP_AMD_GPU_RESIZE: with cv2
         # by ``opencv_agrees_with_gpu_detect_resize`` once per processor, without cv2 the device path.
-        env = os.environ.get('KEEP_AMD_GPU_DETECT_RESIZE')
-        self.gpu_detect_resize = {'1': True, '0': False}.get(env, None)
-        self._area_resizer = None
+        self.gpu_detect_resize = _env_tristate('KEEP_AMD_GPU_DETECT_RESIZE')
         # has_aligned: the INTER_LINEAR resize of a frame that is not 512 x 512 already (keep_processor.py:158,250 of the reference) on the
         # device (engine/resize.py:LinearResizer; ``_aligned_face``, ``_aligned_streamed``).  KEEP_AMD_GPU_ALIGNED_RESIZE: '1' on, '0' off;
         # unset = auto, decided like the two above: with cv2 by ``opencv_agrees_with_gpu_aligned_resize`` once per processor, without cv2
         # the device path.
-        env = os.environ.get('KEEP_AMD_GPU_ALIGNED_RESIZE')
-        self.gpu_aligned_resize = {'1': True, '0': False}.get(env, None)
-        self._linear_resizer = None
+        self.gpu_aligned_resize = _env_tristate('KEEP_AMD_GPU_ALIGNED_RESIZE')
         # read_image's enlargement of frames whose short side is below 512 (face_restoration_helper.py:182-184) on the device
         # (LinearResizer.enlarge_u8; ``_small_frames_probe``): such a sequence keeps its frame store.  KEEP_AMD_GPU_SMALL_FRAMES: '1' on,
         # '0' off; unset = auto, decided like the three above: with cv2 by ``opencv_agrees_with_gpu_small_frame_resize`` once per
         # processor, without cv2 the device path.
-        env = os.environ.get('KEEP_AMD_GPU_SMALL_FRAMES')
-        self.gpu_small_frames = {'1': True, '0': False}.get(env, None)
+        self.gpu_small_frames = _env_tristate('KEEP_AMD_GPU_SMALL_FRAMES')
         # the detected-face sequence path keeps every frame on the device from the detection pre-pass to the paste-back (``_FrameStore``,
         # ``_stored_sequence``) where the streamed paste applies.  KEEP_AMD_FRAME_STORE=0 (read per call): off; KEEP_AMD_FRAME_STORE_GB: the cap.  A failure
         # while filling or warping turns it off for this processor (``frame_store = False``).
@@ -568,16 +297,17 @@ class KEEPFaceProcessor:
         self.detect_resize = 640        # the sequence pre-pass's ``resize`` of get_face_landmarks_5 (keep_processor.py:207-213 of the reference)
 
     # ------------------------------------------------------------------ net invocation
-    def _restore_member_clips(self, crops_tensor, members):
-        """``_restore_clips`` over clips given as lists of crop indices (track clips): the outputs go back to crop order."""
+    def _restore_clips(self, crops_tensor, members):
+        """crops_tensor [1,N,3,512,512] on device, the clips as crop indices (a range or a list per clip; every crop in exactly one)
+        -> [N,3,512,512] restored (fp32, unclamped), in crop order."""
         clips = []
         for m in members:
-            clip = crops_tensor[:, m]
+            clip = crops_tensor[:, m.start:m.stop] if isinstance(m, range) else crops_tensor[:, m]    # (a span of the flat cut: a view)
             if len(m) == 1 and not getattr(self.keep_net, 'supports_single_frame', False):
                 clip = torch.cat([clip, clip], dim=1)    # the reference net needs T>=2 (KP:173-178); frame 0 is kept
             clips.append(clip)
         run_clips = getattr(self.keep_net, 'run_clips', None)
-        if run_clips is not None:
+        if run_clips is not None:                        # engine: batch / shard independent clips
             outs = run_clips(clips, need_upscale=False)
         else:
             outs = [self.keep_net(c, need_upscale=False) for c in tqdm(clips, desc="Restoring faces with KEEP")]
@@ -587,71 +317,69 @@ class KEEPFaceProcessor:
                 restored[i] = o[0, k]
         return torch.stack(restored)
 
-    def _restore_clips(self, crops_tensor, max_clip_length):
-        """crops_tensor [1,N,3,512,512] on device -> [N,3,512,512] restored (fp32, unclamped)."""
-        n = crops_tensor.shape[1]
-        clips = []
-        for s, e in split_clips(n, max_clip_length):
-            clip = crops_tensor[:, s:e]
-            if clip.shape[1] == 1 and not getattr(self.keep_net, 'supports_single_frame', False):
-                clip = torch.cat([clip, clip], dim=1)    # the reference net needs T>=2 (KP:173-178); frame 0 is kept
-            clips.append(clip)
-        run_clips = getattr(self.keep_net, 'run_clips', None)
-        if run_clips is not None:                        # engine: batch / shard independent clips
-            outs = run_clips(clips, need_upscale=False)
-        else:
-            outs = [self.keep_net(c, need_upscale=False)
-                    for c in tqdm(clips, desc="Restoring faces with KEEP")]
-        kept = []
-        for (s, e), o in zip(split_clips(n, max_clip_length), outs):
-            kept.append(o[:, 0:1] if e - s == 1 else o)
-        return torch.cat(kept, dim=1).squeeze(0)
-
     def _restore_crops_u8(self, crops, max_clip_length, members=None, after=None):
         """list of uint8 BGR [512,512,3] crops -> list of restored uint8 BGR crops (same order).
 
-        Same chunking as ``_restore_clips`` (keep_processor.py:263-270); when the net offers ``run_clips_u8`` the
-        uint8<->fp32 conversions of keep_processor.py:258-259,272-273 run on the GPU and only uint8 crosses PCIe,
+        The clips are the cut of the flat list into chunks of ``max_clip_length`` (keep_processor.py:263-270); when the net offers
+        ``run_clips_u8`` the uint8<->fp32 conversions of keep_processor.py:258-259,272-273 run on the GPU and only uint8 crosses PCIe,
         otherwise the host converters are used (reference behaviour).
 
-        ``members`` (track clips): the clips as lists of crop indices (``plan_track_clips``) instead of the cut of the flat list; every
-        crop is in exactly one of them, the lone-crop rule applies per clip and the outputs are scattered back to crop order.  ``after``
-        (``track_carry``): per clip the clip it continues (``plan_track_chains``), handed to the net where it can carry a state."""
+        ``members`` (track clips): the clips as lists of crop indices (``plan_track_clips``) instead of that cut -- which is the plan whose
+        clip c is ``range(start, end)`` of span c; every crop is in exactly one of them, the lone-crop rule applies per clip and the outputs
+        are scattered back to crop order.  ``after`` (``track_carry``): per clip the clip it continues (``plan_track_chains``), handed to
+        the net where it can carry a state; the flat cut has none."""
+        if members is None:
+            members = [range(s, e) for s, e in split_clips(len(crops), max_clip_length)]
         run_u8 = getattr(self.keep_net, 'run_clips_u8', None)
         if run_u8 is None:
             x = crops_to_net_input(crops).unsqueeze(0).to(self.device)
-            restored = self._restore_clips(x, max_clip_length) if members is None else self._restore_member_clips(x, members)
-            return [net_output_to_bgr_u8(f) for f in restored]
+            return [net_output_to_bgr_u8(f) for f in self._restore_clips(x, members)]
         crops = [np.asarray(c) for c in crops]
-        t1_ok = getattr(self.keep_net, 'supports_single_frame', False)
-        if members is not None:
-            kw = self._carry_kw(run_u8, after)
-            dup = 1 if (t1_ok or kw) else 2      # (a net that takes ``after`` takes 1-frame clips as they are: it hands on the state after frame 0)
-            clips = [[crops[i] for i in m] * (dup if len(m) == 1 else 1) for m in members]   # (T >= 2: KP:173-178, frame 0 kept)
-            outs = run_u8(clips, **kw)
-            if outs is None:      # a non-root rank of a run sharded over several GPUs
-                return None
-            faces = [None] * len(crops)
-            for m, o in zip(members, outs):
-                o = o.numpy()
-                for k, i in enumerate(m):
-                    faces[i] = np.ascontiguousarray(o[k])
-            return faces
-        spans = split_clips(len(crops), max_clip_length)
-        clips = []
-        for s, e in spans:
-            clip = crops[s:e]                            # a clip = a list of crops: the engine copies them straight into its
-            if e - s == 1 and not t1_ok:                 # pinned upload buffer (no stacked intermediate)
-                clip = clip + clip                       # the reference net needs T>=2 (KP:173-178): duplicate, keep frame 0
-            clips.append(clip)                           # (the engine restores a lone frame as T=1: same frame 0, half the work)
-        outs = run_u8(clips)
+        kw = self._carry_kw(run_u8, after)
+        # the reference net needs T>=2 (KP:173-178): a lone crop is duplicated and frame 0 kept.  The engine restores a lone frame as T=1
+        # (same frame 0, half the work), and a net that takes ``after`` takes 1-frame clips as they are: it hands on the state after frame 0
+        dup = 1 if (getattr(self.keep_net, 'supports_single_frame', False) or kw) else 2
+        # (a clip = a list of crops: the engine copies them straight into its pinned upload buffer, no stacked intermediate)
+        clips = [[crops[i] for i in m] * (dup if len(m) == 1 else 1) for m in members]
+        outs = run_u8(clips, **kw)
         if outs is None:          # a non-root rank of a run sharded over several GPUs: rank 0 holds the frames and pastes
             return None
-        faces = []
-        for (s, e), o in zip(spans, outs):
+        faces = [None] * len(crops)
+        for m, o in zip(members, outs):
             o = o.numpy()
-            faces.extend(o[k] for k in range(e - s))
-        return [np.ascontiguousarray(f) for f in faces]
+            for k, i in enumerate(m):
+                faces[i] = np.ascontiguousarray(o[k])
+        return faces
+
+    def _resizer(self, name):
+        """The processor's resizer of class ``name`` (engine/resize.py: Lanczos4Resizer, AreaResizer, LinearResizer), built on first use."""
+        rz = self._resizers.get(name)
+        if rz is None:
+            from ..engine import resize
+            rz = self._resizers[name] = getattr(resize, name)(self.device)
+        return rz
+
+    def _gate(self, name):
+        """Whether the HIP path ``name`` (a row of ``opencv_checks.GATES``, and the attribute of that name) stands in for cv2: forced by
+        its environment variable or by whoever set the attribute, else decided once per processor -- by comparing the kernel with cv2
+        itself where cv2 imports, and by the row's verdict without cv2."""
+        if getattr(self, name) is None:
+            check, without_cv2, no_cv2_text, failed_text = opencv_checks.GATES[name]
+            try:
+                _cv2()
+            except ImportError:
+                if no_cv2_text:
+                    log.info(no_cv2_text)
+                setattr(self, name, without_cv2)
+                return without_cv2
+            try:
+                verdict = bool(getattr(opencv_checks, check)(self.device))
+            except Exception as e:                      # no GPU / no library / any surprise: cv2 (the paste: the helper's own path)
+                if failed_text:
+                    log.info(failed_text, e)
+                verdict = False
+            setattr(self, name, verdict)
+        return getattr(self, name)
 
     def _run_upscaler(self, model, cv2_image):
         if model is None:
@@ -670,89 +398,40 @@ class KEEPFaceProcessor:
 
     def _lanczos(self, img, w, h, on_device=False):
         """``_resize(img, w, h, 'INTER_LANCZOS4')``: identity returns ``img``; uint8 3-channel images go to the device kernel when
-        ``_gpu_resize_path`` allows it, everything else (grey / 4-channel / other dtypes, an empty target) to cv2."""
+        ``_gate('gpu_resize')`` allows it, everything else (grey / 4-channel / other dtypes, an empty target) to cv2."""
         if img.shape[0] == h and img.shape[1] == w:
             return img
         if (w > 0 and h > 0 and len(img.shape) == 3 and img.shape[2] == 3 and img.dtype in (np.uint8, torch.uint8)
-                and self._gpu_resize_path()):
-            if self._resizer is None:
-                from ..engine.resize import Lanczos4Resizer
-                self._resizer = Lanczos4Resizer(self.device)
-            out = self._resizer.resize_u8(img, w, h)
+                and self._gate('gpu_resize')):
+            out = self._resizer('Lanczos4Resizer').resize_u8(img, w, h)
             return out if on_device else out.cpu().numpy()
         return _resize(_host(img), w, h, 'INTER_LANCZOS4')
 
     def _lanczos_batch(self, frames, w, h):
         """``_lanczos`` over a uint8 [m,H,W,3] device batch that stays on the device: one launch on the current stream, identity returns
-        ``frames``.  For callers that have settled ``_gpu_resize_path`` already (``_aligned_stream_applies``)."""
+        ``frames``.  For callers that have settled ``_gate('gpu_resize')`` already (``_aligned_stream_applies``)."""
         if frames.shape[1] == h and frames.shape[2] == w:
             return frames
-        if self._resizer is None:
-            from ..engine.resize import Lanczos4Resizer
-            self._resizer = Lanczos4Resizer(self.device)
-        return self._resizer.resize_u8(frames, w, h)
-
-    def _gpu_resize_path(self):
-        """Whether the HIP Lanczos resize stands in for cv2.resize: forced by KEEP_AMD_GPU_RESIZE, else decided once per processor --
-        by comparing it with cv2 itself where cv2 imports, and on without cv2 (no other path can run there)."""
-        if self.gpu_resize is None:
-            import logging
-            log = logging.getLogger('ComfyUI-KEEP')
-            try:
-                import cv2  # noqa: F401
-            except ImportError:
-                log.info("cv2 is not installed: final_upscale_factor resizes run on the device (KEEP_AMD_GPU_RESIZE)")
-                self.gpu_resize = True
-                return True
-            try:
-                self.gpu_resize = bool(opencv_agrees_with_gpu_resize(self.device))
-            except Exception as e:                      # no GPU / no library / any surprise: cv2
-                log.info("device Lanczos resize self-check failed (%s): cv2.resize", e)
-                self.gpu_resize = False
-        return self.gpu_resize
-
-    def _gpu_detect_resize_path(self):
-        """Whether the HIP area resize stands in for the INTER_AREA cv2.resize of the detector inputs: forced by
-        KEEP_AMD_GPU_DETECT_RESIZE, else decided once per processor -- by comparing it with cv2 itself where cv2 imports, and on without
-        cv2 (a frame above the detector size has no other resize there)."""
-        if self.gpu_detect_resize is None:
-            import logging
-            log = logging.getLogger('ComfyUI-KEEP')
-            try:
-                _cv2()
-            except ImportError:
-                log.info("cv2 is not installed: detector inputs are resized on the device (KEEP_AMD_GPU_DETECT_RESIZE)")
-                self.gpu_detect_resize = True
-                return True
-            try:
-                self.gpu_detect_resize = bool(opencv_agrees_with_gpu_detect_resize(self.device))
-            except Exception as e:                      # no GPU / no library / any surprise: cv2
-                log.info("device area resize self-check failed (%s): cv2.resize", e)
-                self.gpu_detect_resize = False
-        return self.gpu_detect_resize
+        return self._resizer('Lanczos4Resizer').resize_u8(frames, w, h)
 
     def _detect_resize_device(self, imgs, w2, h2):
         """uint8 [H,W,3] frames of one size -> the uint8 [n,h2,w2,3] detector batch on the device: every frame is copied straight into one
         [n,H,W,3] device tensor (no host stack; frames of the pinned conversion buffer copy asynchronously) and all of them are resized
         by one ``keep_resize_area_u8`` launch on the device's current stream.  The resized frames never exist on the host."""
-        if self._area_resizer is None:
-            from ..engine.resize import AreaResizer
-            self._area_resizer = AreaResizer(self.device)
-        dev = self._area_resizer.device
+        rz = self._resizer('AreaResizer')
+        dev = rz.device
         h, w = imgs[0].shape[:2]
         with torch.cuda.device(dev):
             buf = torch.empty((len(imgs), h, w, 3), dtype=torch.uint8, device=dev)
             for i, im in enumerate(imgs):
                 buf[i].copy_(im if isinstance(im, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(im)), non_blocking=True)
-            return self._area_resizer.resize_u8(buf, w2, h2)
+            return rz.resize_u8(buf, w2, h2)
 
     def _detect_resize_stored(self, buf, w2, h2):
         """``_detect_resize_device`` over a chunk that is on the device already (the frame store's tensor): the launch alone."""
-        if self._area_resizer is None:
-            from ..engine.resize import AreaResizer
-            self._area_resizer = AreaResizer(self.device)
+        rz = self._resizer('AreaResizer')
         with torch.cuda.device(buf.device):
-            return self._area_resizer.resize_u8(buf, w2, h2)
+            return rz.resize_u8(buf, w2, h2)
 
     def _detect_resize_applies(self, imgs, resize):
         """(w2, h2) when the device resize takes this chunk's detector inputs -- every frame uint8 [H,W,3] of one size whose short side
@@ -769,73 +448,29 @@ class KEEPFaceProcessor:
         h, w = first[:2]
         scale = resize / min(h, w)
         w2, h2 = int(w * scale), int(h * scale)
-        if area_geometry_refused(h, w, h2, w2) or not self._gpu_detect_resize_path():
+        if area_geometry_refused(h, w, h2, w2) or not self._gate('gpu_detect_resize'):
             return None
         return w2, h2
-
-    def _gpu_aligned_resize_path(self):
-        """Whether the HIP bilinear resize stands in for the INTER_LINEAR cv2.resize of aligned inputs: forced by
-        KEEP_AMD_GPU_ALIGNED_RESIZE, else decided once per processor -- by comparing it with cv2 itself where cv2 imports, and on without
-        cv2 (an aligned frame that is not 512 x 512 has no other resize there)."""
-        if self.gpu_aligned_resize is None:
-            import logging
-            log = logging.getLogger('ComfyUI-KEEP')
-            try:
-                _cv2()
-            except ImportError:
-                log.info("cv2 is not installed: aligned inputs are resized on the device (KEEP_AMD_GPU_ALIGNED_RESIZE)")
-                self.gpu_aligned_resize = True
-                return True
-            try:
-                self.gpu_aligned_resize = bool(opencv_agrees_with_gpu_aligned_resize(self.device))
-            except Exception as e:                      # no GPU / no library / any surprise: cv2
-                log.info("device bilinear resize self-check failed (%s): cv2.resize", e)
-                self.gpu_aligned_resize = False
-        return self.gpu_aligned_resize
 
     def _aligned_resize_device(self, frames, out=None):
         """uint8 [H,W,3] / [n,H,W,3] (host or device) -> the 512 x 512 crops on the device: one ``keep_resize_linear_u8`` launch on the
         current stream (into ``out`` where given)."""
-        if self._linear_resizer is None:
-            from ..engine.resize import LinearResizer
-            self._linear_resizer = LinearResizer(self.device)
-        return self._linear_resizer.resize_u8(frames, 512, 512, out=out)
+        return self._resizer('LinearResizer').resize_u8(frames, 512, 512, out=out)
 
     def _aligned_face(self, img):
         """``_resize(img, 512, 512, 'INTER_LINEAR')`` of an aligned input: identity returns ``img``; a uint8 [H,W,3] image goes to the
-        device kernel when ``_gpu_aligned_resize_path`` allows it and comes back as a host array; everything else (grey / 4-channel /
+        device kernel when ``_gate('gpu_aligned_resize')`` allows it and comes back as a host array; everything else (grey / 4-channel /
         other dtypes, an empty image, the path off) goes to cv2.  A device failure is logged and turns the path off."""
         if img.shape[0] == 512 and img.shape[1] == 512:
             return img
         if (len(img.shape) == 3 and img.shape[2] == 3 and img.dtype == np.uint8 and img.shape[0] > 0 and img.shape[1] > 0
-                and self._gpu_aligned_resize_path()):
+                and self._gate('gpu_aligned_resize')):
             try:
                 return self._aligned_resize_device(img).cpu().numpy()
             except Exception as e:
-                import logging
-                logging.getLogger('ComfyUI-KEEP').warning("device resize of the aligned input failed (%s): cv2.resize", e)
+                log.warning("device resize of the aligned input failed (%s): cv2.resize", e)
                 self.gpu_aligned_resize = False
         return _resize(img, 512, 512, 'INTER_LINEAR')
-
-    def _gpu_small_frames_path(self):
-        """Whether the HIP enlargement stands in for ``read_image``'s INTER_LINEAR cv2.resize of small frames: forced by
-        KEEP_AMD_GPU_SMALL_FRAMES, else decided once per processor -- by comparing it with cv2 itself where cv2 imports, and on without
-        cv2."""
-        if self.gpu_small_frames is None:
-            import logging
-            log = logging.getLogger('ComfyUI-KEEP')
-            try:
-                _cv2()
-            except ImportError:
-                log.info("cv2 is not installed: small frames are enlarged on the device (KEEP_AMD_GPU_SMALL_FRAMES)")
-                self.gpu_small_frames = True
-                return True
-            try:
-                self.gpu_small_frames = bool(opencv_agrees_with_gpu_small_frame_resize(self.device))
-            except Exception as e:                      # no GPU / no library / any surprise: cv2
-                log.info("device enlargement self-check failed (%s): cv2.resize", e)
-                self.gpu_small_frames = False
-        return self.gpu_small_frames
 
     def _enlarged_hw(self, h, w):
         """(H2, W2) ``read_image`` gives an [h,w] frame whose short side is below 512, else None."""
@@ -858,7 +493,7 @@ class KEEPFaceProcessor:
             return False
         if store.cap_bytes is not None and n_frames * (h * w + hw2[0] * hw2[1]) * 3 > store.cap_bytes:
             return False
-        if not self._gpu_resize_path() or not self._gpu_small_frames_path():
+        if not self._gate('gpu_resize') or not self._gate('gpu_small_frames'):
             return False
         store.small = (small_frame_factor(h, w),) + hw2
         return True
@@ -869,11 +504,9 @@ class KEEPFaceProcessor:
         is the enlarged frame -- here its device view, of which ``_replay_chunk`` needs the shape -- and the grey flag of the frame as it
         came.  None after a failure (``_frame_store_failed``): the present handling takes this chunk and the rest."""
         try:
-            if self._linear_resizer is None:
-                from ..engine.resize import LinearResizer
-                self._linear_resizer = LinearResizer(self.device)
+            rz = self._resizer('LinearResizer')
             store.fill(k, frames_bgr)
-            ebuf = store.enlarge(k, self._linear_resizer)
+            ebuf = store.enlarge(k, rz)
         except Exception as e:
             self._frame_store_failed(store, e)
             return None
@@ -940,12 +573,12 @@ class KEEPFaceProcessor:
         ``weights`` (track lifetimes with ``track_fade``): per face its weight in the composite, which only the GPU paste takes
         (``keep_paste_face_w``); where the helper's own paste takes the frame a fade is ignored, with one logged warning."""
         wkw = {} if weights is None else {'weights': weights}        # (without a fade: today's calls, argument for argument)
-        if self._gpu_cv_path():
+        if self._gate('gpu_paste'):
             if self._gpu_paste_applies(helper, bg, draw_box):
                 return self._paste_gpu(helper, bg, draw_box, **wkw)
             hw2 = self._enlarged_hw(*src_hw) if src_hw is not None and self.gpu_small_frames is not False else None
             if (hw2 is not None and tuple(getattr(getattr(helper, 'input_img', None), 'shape', ())[:2]) == hw2
-                    and self._gpu_paste_applies(helper, bg, draw_box, size_test=False) and self._gpu_resize_path()):
+                    and self._gpu_paste_applies(helper, bg, draw_box, size_test=False) and self._gate('gpu_resize')):
                 up = getattr(helper, 'upscale_factor', 1)
                 return self._paste_gpu(helper, self._lanczos(bg, int(hw2[1] * up), int(hw2[0] * up), on_device=True), draw_box, **wkw)
         self._fade_ignored(weights)
@@ -955,24 +588,13 @@ class KEEPFaceProcessor:
         """The helper's own paste has no per-face weight: a fade is dropped there, with one logged warning per processor."""
         if weights is not None and any(w != 1.0 for w in weights) and not getattr(self, '_fade_warned', False):
             self._fade_warned = True
-            import logging
-            logging.getLogger('ComfyUI-KEEP').warning("KEEP_AMD_TRACK_FADE: the helper's own paste takes this frame; faces are pasted without a fade")
-
-    def _gpu_cv_path(self):
-        """Whether the OpenCV-arithmetic kernels (paste-back, crop warp) may stand in for cv2: forced by KEEP_AMD_GPU_PASTE, else
-        decided once per processor by comparing them with cv2 itself on this installation."""
-        if self.gpu_paste is None:
-            try:
-                self.gpu_paste = bool(opencv_agrees_with_gpu_paste(self.device))
-            except Exception:                            # no cv2 / no GPU / any surprise: the helper's own path
-                self.gpu_paste = False
-        return self.gpu_paste
+            log.warning("KEEP_AMD_TRACK_FADE: the helper's own paste takes this frame; faces are pasted without a fade")
 
     def _align_warp(self, helper, keep_on_device=False):
         """``helper.align_warp_face()`` (face_restoration_helper.py:256-320).  With the GPU cv path and the default configuration
         (no pad_blur, constant border) only the similarity fit stays on the host (``cv2.estimateAffinePartial2D``, :305); the
         ``cv2.warpAffine`` that produces the 512 x 512 crops (:316-318) runs on the device (``keep_warp_affine_u8``)."""
-        if (not self._gpu_cv_path() or getattr(helper, 'pad_blur', False) or not hasattr(helper, 'face_template')
+        if (not self._gate('gpu_paste') or getattr(helper, 'pad_blur', False) or not hasattr(helper, 'face_template')
                 or getattr(helper.input_img, 'dtype', None) != np.uint8):       # (16-bit sources are float64 after read_image)
             return helper.align_warp_face()
         from ..engine.paste import crop_faces
@@ -1052,14 +674,10 @@ class KEEPFaceProcessor:
     # ------------------------------------------------------------------ streamed restore + paste (round 5)
     def _stream_applies(self, helper, frames_bgr, crops, draw_box):
         """The streamed form of steps 3 + 4 needs: the engine's net (``run_clips_u8`` with ``sink``), not inside a torch.distributed
-        job, the GPU cv path (``_gpu_cv_path``), the parse-mask composite with ParseNet on the engine, no face upsampler, uint8
+        job, the GPU cv path (``_gate('gpu_paste')``), the parse-mask composite with ParseNet on the engine, no face upsampler, uint8
         colour frames of one size and 512 x 512 crops -- i.e. the configuration ``_gpu_paste_applies`` admits frame by frame, decided
         once for the sequence.  ``KEEP_AMD_STREAM_PASTE=0`` keeps the per-frame path."""
-        if not self._stream_config_applies(helper):
-            return False
-        f0 = frames_bgr[0]
-        if any(not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape != f0.shape or f.shape[2] != 3
-               for f in frames_bgr):
+        if not self._stream_config_applies(helper) or uniform_u8_frames(frames_bgr) is None:
             return False
         if tuple(getattr(helper, 'face_size', (512, 512))) != (512, 512):
             return False
@@ -1067,14 +685,11 @@ class KEEPFaceProcessor:
 
     def _stream_config_applies(self, helper):
         """What ``_stream_applies`` asks of the configuration (everything but the frames and the crops)."""
-        net = self.keep_net
-        if os.environ.get('KEEP_AMD_STREAM_PASTE', '1') == '0' or not getattr(net, 'supports_sink', False):
-            return False
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        if not _sink_streaming(self.keep_net):
             return False
         if self.face_upscale_model is not None or not getattr(helper, 'use_parse', False):
             return False
-        if getattr(getattr(helper, 'face_parse', None), 'engine', None) is None or not self._gpu_cv_path():
+        if getattr(getattr(helper, 'face_parse', None), 'engine', None) is None or not self._gate('gpu_paste'):
             return False
         return tuple(getattr(helper, 'face_size', (512, 512))) == (512, 512)
 
@@ -1106,9 +721,8 @@ class KEEPFaceProcessor:
         (``GpuPaster.paste(weights=...)``); None: every face at 1.0, today's calls."""
         from ..engine import hiplib as L
         from ..engine.paste import GpuPaster
-        helper, net, dev = self.face_helper, self.keep_net, torch.device(self.device)
-        if dev.index is None:
-            dev = torch.device('cuda', torch.cuda.current_device())
+        from .clip_plan import clip_slot_spans
+        helper, net, dev = self.face_helper, self.keep_net, cuda_device(self.device)
         if self._paster is None:
             self._paster = GpuPaster(dev)
         paster, engine = self._paster, helper.face_parse.engine
@@ -1116,27 +730,16 @@ class KEEPFaceProcessor:
         first = [0]
         for k in faces_per_frame:
             first.append(first[-1] + k)
+        # the clips as crop indices: the plan's, or the cut of the flat list -- the plan whose slots are the crop numbers themselves
+        members = plan[0] if plan is not None else [range(s, e) for s, e in split_clips(n_crops, max_clip_length)]
         clips = []
-        if plan is None:
-            spans, members = split_clips(n_crops, max_clip_length), None
-        else:
-            from .clip_plan import clip_slot_spans
-            spans, members = [], plan[0]
-            for m, (s0, s1) in zip(members, clip_slot_spans(members)):
-                if store is not None:
-                    clips.append(crops[s0:s1])                            # a view of the crop tensor, which is laid out by slot
-                elif all(isinstance(crops[i], torch.Tensor) and crops[i].is_cuda for i in m):
-                    clips.append(torch.stack([crops[i] for i in m]))
-                else:
-                    clips.append([crops[i].cpu().numpy() if isinstance(crops[i], torch.Tensor) else np.asarray(crops[i]) for i in m])
-        for s, e in spans:
-            part = crops[s:e]
+        for m, (s0, s1) in zip(members, clip_slot_spans(members)):
             if store is not None:
-                clips.append(part)                                    # a view of the sequence's crop tensor
-            elif all(isinstance(c, torch.Tensor) and c.is_cuda for c in part):
-                clips.append(torch.stack(part))                       # warped on this GPU: restored without leaving it
+                clips.append(crops[s0:s1])                            # a view of the sequence's crop tensor, which is laid out by slot
+            elif all(isinstance(crops[i], torch.Tensor) and crops[i].is_cuda for i in m):
+                clips.append(torch.stack([crops[i] for i in m]))      # warped on this GPU: restored without leaving it
             else:
-                clips.append([c.cpu().numpy() if isinstance(c, torch.Tensor) else np.asarray(c) for c in part])
+                clips.append([crops[i].cpu().numpy() if isinstance(crops[i], torch.Tensor) else np.asarray(crops[i]) for i in m])
         pool = getattr(net, 'pool', None)
         if pool is not None and hasattr(pool, 'set_parser'):          # the workers parse what they restore
             pool.set_parser(engine)
@@ -1145,25 +748,10 @@ class KEEPFaceProcessor:
         ps = getattr(self, '_paste_stream', None)
         if ps is None:
             ps = self._paste_stream = torch.cuda.Stream(device=dev)
-        st = {'next': 0, 'out': None, 'aff': 0}
+        st, out = {'next': 0, 'aff': 0}, _HostOutput(n_frames, as_u8, dev)
 
         def on_dev(t):
             return t if (isinstance(t, torch.Tensor) and t.is_cuda) else torch.as_tensor(t).to(dev, non_blocking=True)
-
-        def emit(t, frame_dev):
-            """finished frame t (uint8 BGR [H,W,3] on the device) -> the output tensor in host memory"""
-            if st['out'] is None:
-                shape = (n_frames,) + tuple(frame_dev.shape)
-                try:
-                    st['out'] = torch.empty(shape, dtype=torch.uint8 if as_u8 else torch.float32, pin_memory=True)
-                except RuntimeError:                                  # more than the host will pin: pageable memory, slower copies
-                    st['out'] = torch.empty(shape, dtype=torch.uint8 if as_u8 else torch.float32)
-            if as_u8:
-                st['out'][t].copy_(frame_dev, non_blocking=True)
-            else:                                                      # cv2_to_comfy_image on the device (keep_bgr_u8_to_comfy: one IEEE division)
-                ff = torch.empty(frame_dev.shape, dtype=torch.float32, device=dev)
-                L.call('keep_bgr_u8_to_comfy', frame_dev.contiguous(), ff, frame_dev.numel() // 3)
-                st['out'][t].copy_(ff, non_blocking=True)
 
         def advance():
             f0 = f1 = st['next']
@@ -1194,7 +782,7 @@ class KEEPFaceProcessor:
                             bg = self._lanczos(bg, int(hw[1] * factor), int(hw[0] * factor), on_device=True)
                     k = faces_per_frame[t]
                     if k == 0:
-                        emit(t, bg if isinstance(bg, torch.Tensor) else on_dev(np.ascontiguousarray(bg)))
+                        out.emit(t, (bg if isinstance(bg, torch.Tensor) else on_dev(np.ascontiguousarray(bg)))[None])
                         if store is not None and t + 1 == store.spans[t // store.chunk][1]:
                             store.release(t // store.chunk, ps)
                         continue
@@ -1206,7 +794,7 @@ class KEEPFaceProcessor:
                     ids = range(first[t], first[t + 1])
                     faces = torch.stack([on_dev(ready[i]) for i in ids])
                     cls = torch.stack([on_dev(classes[i]) for i in ids])
-                    emit(t, paster.paste(bg, faces, list(helper.inverse_affine_matrices), cls, factor, draw_box, **wkw))
+                    out.emit(t, paster.paste(bg, faces, list(helper.inverse_affine_matrices), cls, factor, draw_box, **wkw)[None])
                     pbar.update(1)
                     if store is not None and t + 1 == store.spans[t // store.chunk][1]:
                         store.release(t // store.chunk, ps)             # (the allocator waits for this stream's reads)
@@ -1217,23 +805,12 @@ class KEEPFaceProcessor:
 
         def sink(ids, crops_list, classes_list):
             for j, cid in enumerate(ids):
-                s, e = spans[cid]
-                for k in range(e - s):
-                    ready[s + k] = crops_list[j][k]
-                    if classes_list is not None:
-                        classes[s + k] = classes_list[j][k]
-            advance()
-
-        def sink_members(ids, crops_list, classes_list):
-            for j, cid in enumerate(ids):
                 for k, i in enumerate(members[cid]):
                     ready[i] = crops_list[j][k]
                     if classes_list is not None:
                         classes[i] = classes_list[j][k]
             advance()
 
-        if members is not None:
-            sink = sink_members
         max_b = None
         groups = int(os.environ.get('KEEP_AMD_STREAM_GROUPS', '0') or 0)      # >= 2: at least that many batch groups (more overlap, smaller batches)
         if groups >= 2 and hasattr(net, 'clips_per_call'):
@@ -1257,34 +834,29 @@ class KEEPFaceProcessor:
         # the restored crops stay on the GPU only on request (tests / tools: ``keep_restored_faces``, KEEP_AMD_KEEP_RESTORED=1); by default
         # each crop is released once its frame has been composited and nothing of the sequence outlives the call in HBM
         self.last_restored_faces = _DeviceFaces(ready) if keep_restored else []
-        return st['out']
+        return out.out
 
     # ------------------------------------------------------------------ streamed aligned sequence
     def _aligned_stream_applies(self, frames_bgr, factor):
         """The device-resident form of an aligned sequence (``_aligned_streamed``) needs: the engine's net (``run_clips_u8`` with
         ``sink``) in one process without a worker pool (a pool worker's share arrives in host memory: the per-frame path keeps that
         case), not inside a torch.distributed job, no face / background upscale model, uint8 colour frames of one size, and the device
-        path of every resize the call makes: ``_gpu_resize_path`` when the output size differs from its source's,
-        ``_gpu_aligned_resize_path`` when the frames are not 512 x 512.  ``KEEP_AMD_STREAM_PASTE=0`` keeps the per-frame path."""
+        path of every resize the call makes: ``_gate('gpu_resize')`` when the output size differs from its source's,
+        ``_gate('gpu_aligned_resize')`` when the frames are not 512 x 512.  ``KEEP_AMD_STREAM_PASTE=0`` keeps the per-frame path."""
         net = self.keep_net
-        if os.environ.get('KEEP_AMD_STREAM_PASTE', '1') == '0' or not getattr(net, 'supports_sink', False):
-            return False
-        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+        if not _sink_streaming(net):
             return False
         if getattr(net, 'pool', None) is not None or self.face_upscale_model is not None or self.bg_upscale_model is not None:
             return False
-        f0 = frames_bgr[0]
-        if any(not isinstance(f, np.ndarray) or f.dtype != np.uint8 or f.ndim != 3 or f.shape != f0.shape or f.shape[2] != 3
-               for f in frames_bgr):
+        hw = uniform_u8_frames(frames_bgr)
+        if hw is None or hw[0] <= 0 or hw[1] <= 0:
             return False
-        h, w = f0.shape[:2]
-        if h <= 0 or w <= 0:
-            return False
+        h, w = hw
         src = (512, 512) if self.return_restored_aligned else (w, h)
         dst = (int(src[0] * factor), int(src[1] * factor))
-        if dst[0] <= 0 or dst[1] <= 0 or (dst != src and not self._gpu_resize_path()):
+        if dst[0] <= 0 or dst[1] <= 0 or (dst != src and not self._gate('gpu_resize')):
             return False
-        return (h, w) == (512, 512) or bool(self._gpu_aligned_resize_path())
+        return (h, w) == (512, 512) or bool(self._gate('gpu_aligned_resize'))
 
     def _aligned_streamed(self, frames_bgr, max_clip_length, factor, pbar, as_u8, scene=False):
         """Steps 2 - 4 of an aligned sequence (keep_processor.py:250-291 of the reference) with the frames resident on the GPU.
@@ -1302,9 +874,7 @@ class KEEPFaceProcessor:
         ``scene`` (scene cuts): every uploaded chunk's signatures are taken on the device, from the frames as given, and the spans are
         cut per scene; nothing is carried across a cut."""
         from ..engine import hiplib as L
-        net, dev = self.keep_net, torch.device(self.device)
-        if dev.index is None:
-            dev = torch.device('cuda', torch.cuda.current_device())
+        net, dev = self.keep_net, cuda_device(self.device)
         n = len(frames_bgr)
         h, w = frames_bgr[0].shape[:2]
         restored_out = bool(self.return_restored_aligned)
@@ -1326,15 +896,13 @@ class KEEPFaceProcessor:
                     try:
                         L.call('keep_frame_signature_u8', buf, len(part), h, w, sig_dev[a:a + len(part)])
                     except Exception as e:              # logged, and the host function takes the signatures: the same integers
-                        import logging
-                        logging.getLogger('ComfyUI-KEEP').warning("frame signatures on the device failed (%s): the host function", e)
+                        log.warning("frame signatures on the device failed (%s): the host function", e)
                         sig_dev = None
                 if (h, w) != (512, 512):
                     try:
                         self._aligned_resize_device(buf, out=crops[a:a + len(part)])
                     except Exception as e:              # logged, and the per-frame path (cv2) takes the sequence and every later one
-                        import logging
-                        logging.getLogger('ComfyUI-KEEP').warning("device resize of the aligned frames failed (%s): cv2.resize", e)
+                        log.warning("device resize of the aligned frames failed (%s): cv2.resize", e)
                         self.gpu_aligned_resize = False
                         return None
                 frames_dev.append(buf if keep_frames else None)
@@ -1354,23 +922,7 @@ class KEEPFaceProcessor:
         clips = [crops[s:e] if (e - s > 1 or t1_ok) else torch.cat([crops[s:e], crops[s:e]]) for s, e in spans]   # (T >= 2: KP:173-178)
         restored = [None] * n
         keep_restored = self.keep_restored_faces
-        st = {'next': 0, 'out': None}
-
-        def emit(f0, frames_dev_out):
-            """finished frames f0 .. (uint8 BGR [m,H',W',3] on the device) -> the output tensor in host memory"""
-            m = frames_dev_out.shape[0]
-            if st['out'] is None:
-                shape = (n, out_h, out_w, 3)
-                try:
-                    st['out'] = torch.empty(shape, dtype=torch.uint8 if as_u8 else torch.float32, pin_memory=True)
-                except RuntimeError:                                  # more than the host will pin: pageable memory, slower copies
-                    st['out'] = torch.empty(shape, dtype=torch.uint8 if as_u8 else torch.float32)
-            if as_u8:
-                st['out'][f0:f0 + m].copy_(frames_dev_out, non_blocking=True)
-            else:                                                      # cv2_to_comfy_image on the device (keep_bgr_u8_to_comfy)
-                ff = torch.empty(frames_dev_out.shape, dtype=torch.float32, device=dev)
-                L.call('keep_bgr_u8_to_comfy', frames_dev_out.contiguous(), ff, frames_dev_out.numel() // 3)
-                st['out'][f0:f0 + m].copy_(ff, non_blocking=True)
+        st, out = {'next': 0}, _HostOutput(n, as_u8, dev)
 
         def advance():
             f0 = f1 = st['next']
@@ -1381,11 +933,11 @@ class KEEPFaceProcessor:
             with torch.cuda.device(dev):           # (the current stream: the one the forward that produced the crops was queued on)
                 if restored_out:
                     faces = torch.stack([restored[i] for i in range(f0, f1)])
-                    emit(f0, self._lanczos_batch(faces, out_w, out_h))
+                    out.emit(f0, self._lanczos_batch(faces, out_w, out_h))
                 else:
                     for c in range(f0 // chunk, (f1 - 1) // chunk + 1):
                         a, b = max(f0, c * chunk), min(f1, (c + 1) * chunk)
-                        emit(a, self._lanczos_batch(frames_dev[c][a - c * chunk:b - c * chunk], out_w, out_h))
+                        out.emit(a, self._lanczos_batch(frames_dev[c][a - c * chunk:b - c * chunk], out_w, out_h))
                         if b == min(n, (c + 1) * chunk):
                             frames_dev[c] = None                       # the chunk's frames are released once all of them are out
             if not keep_restored:
@@ -1406,7 +958,7 @@ class KEEPFaceProcessor:
             raise RuntimeError(f"streamed aligned sequence: {n - st['next']} frame(s) never became ready")
         pbar.update(n)
         self.last_restored_faces = _DeviceFaces(restored) if keep_restored else []
-        return st['out']
+        return out.out
 
     # ------------------------------------------------------------------ sequence
     def _frame_store_begin(self, frames_bgr):
@@ -1422,27 +974,17 @@ class KEEPFaceProcessor:
             return None
         if getattr(helper, 'pad_blur', False) or not hasattr(helper, 'face_template') or not self._stream_config_applies(helper):
             return None
-        try:
-            cap = float(os.environ.get('KEEP_AMD_FRAME_STORE_GB', '') or FRAME_STORE_DEFAULT_GB) * 1e9
-        except ValueError:
-            cap = FRAME_STORE_DEFAULT_GB * 1e9
-        spans = frame_store_plan(frames_bgr, int(cap), chunk)
-        if spans is None:
+        cap = int(_env_number('KEEP_AMD_FRAME_STORE_GB', FRAME_STORE_DEFAULT_GB, float) * 1e9)
+        spans = frame_store_plan(frames_bgr, cap, chunk)
+        if spans is None or torch.device(self.device).type != 'cuda':
             return None
-        dev = torch.device(self.device)
-        if dev.type != 'cuda':
-            return None
-        if dev.index is None:
-            dev = torch.device('cuda', torch.cuda.current_device())
-        f0 = frames_bgr if isinstance(frames_bgr, _ConvertedFrames) else None
-        h, w = (f0.H, f0.W) if f0 is not None else frames_bgr[0].shape[:2]
-        return _FrameStore(spans, h, w, dev, cap_bytes=int(cap))
+        h, w = uniform_u8_frames(frames_bgr)            # (not None: the plan asked the same)
+        return _FrameStore(spans, h, w, cuda_device(self.device), cap_bytes=cap)
 
     def _frame_store_failed(self, store, err):
         """A raised error while filling the store or in the batched warp (nothing has been restored yet): logged once, the store is off
         for this processor from here on, and the sequence takes the present path."""
-        import logging
-        logging.getLogger('ComfyUI-KEEP').warning("keeping the frames on the device failed (%s): the per-frame upload path", err)
+        log.warning("keeping the frames on the device failed (%s): the per-frame upload path", err)
         self.frame_store = False
         store.dead = True
         store.drop()
@@ -1528,16 +1070,12 @@ class KEEPFaceProcessor:
         if n < 2:
             self.last_scene_cuts, self.last_scene_distances = [], np.zeros((0,), np.float64)
             return False
-        ok = isinstance(frames_bgr, _ConvertedFrames)            # uint8 [H,W,3] by construction
-        if not ok:
-            shape = tuple(getattr(frames_bgr[0], 'shape', ()))
-            ok = (len(shape) == 3 and shape[2] == 3 and shape[0] > 0 and shape[1] > 0
-                  and all(isinstance(f, np.ndarray) and f.dtype == np.uint8 and tuple(f.shape) == shape for f in frames_bgr))
+        hw = uniform_u8_frames(frames_bgr)
+        ok = hw is not None and hw[0] > 0 and hw[1] > 0
         if not ok:
             if not getattr(self, '_scene_warned', False):
                 self._scene_warned = True
-                import logging
-                logging.getLogger('ComfyUI-KEEP').warning("KEEP_AMD_SCENE_CUTS: the frames are not uint8 [h,w,3] of one size; no scene cuts")
+                log.warning("KEEP_AMD_SCENE_CUTS: the frames are not uint8 [h,w,3] of one size; no scene cuts")
             self.last_scene_cuts, self.last_scene_distances = [], np.zeros((0,), np.float64)
         return ok
 
@@ -1560,8 +1098,7 @@ class KEEPFaceProcessor:
             try:
                 sigs = sig_dev.cpu().numpy()
             except Exception as e:
-                import logging
-                logging.getLogger('ComfyUI-KEEP').warning("reading the frame signatures back failed (%s): the host function", e)
+                log.warning("reading the frame signatures back failed (%s): the host function", e)
         if sigs is None:
             sigs = np.stack([frame_signature_host(frames_bgr[i]) for i in range(len(frames_bgr))])
         h, w = frames_bgr[0].shape[:2]
@@ -1586,8 +1123,7 @@ class KEEPFaceProcessor:
             return {'after': list(after)}
         if not getattr(self, '_carry_warned', False):
             self._carry_warned = True
-            import logging
-            logging.getLogger('ComfyUI-KEEP').warning("KEEP_AMD_TRACK_CARRY: this net cannot start a clip from a state; clips start from nothing")
+            log.warning("KEEP_AMD_TRACK_CARRY: this net cannot start a clip from a state; clips start from nothing")
         return {}
 
     def _detect_batching(self, det, n):
@@ -1771,8 +1307,7 @@ class KEEPFaceProcessor:
             try:
                 return states, (self._detect_resize_device(imgs, *target) if buf is None else self._detect_resize_stored(buf, *target))
             except Exception as e:                      # logged, and the present path takes the chunk (and every later one)
-                import logging
-                logging.getLogger('ComfyUI-KEEP').warning("device resize of the detector inputs failed (%s): cv2.resize", e)
+                log.warning("device resize of the detector inputs failed (%s): cv2.resize", e)
                 self.gpu_detect_resize = False
         if buf is not None and (resize is None or min(imgs[0].shape[:2]) <= resize):
             return states, buf                          # no detector resize: the stored chunk is the detector batch
@@ -1786,11 +1321,6 @@ class KEEPFaceProcessor:
         if any(tuple(im.shape) != tuple(imgs[0].shape) or im.dtype not in (np.uint8, torch.uint8) for im in imgs):
             return states, None
         return states, (torch.stack(imgs) if isinstance(imgs[0], torch.Tensor) else np.stack(imgs))
-
-    def _detect_batched(self, det, frames_bgr, resize):
-        """``_prep_detect_chunk`` + the detector's batched forward with the helper's 0.97 confidence threshold (:221): (states, detections)."""
-        states, batch = self._prep_detect_chunk(frames_bgr, resize)
-        return states, (None if batch is None else det.detect_batch(batch, 0.97))
 
     @torch.no_grad()
     def process_image_sequence(self, image_sequence_tensor: torch.Tensor, final_upscale_factor: float,

@@ -201,7 +201,7 @@ def test_unset_knob_decides_once_by_cv2(monkeypatch):
         KP, proc, log = _processor(monkeypatch, None)
         asked = []
         monkeypatch.setattr(KP, '_cv2', lambda: object())
-        monkeypatch.setattr(KP, 'opencv_agrees_with_gpu_detect_resize', lambda dev: (asked.append(dev), verdict)[1])
+        monkeypatch.setattr(KP.opencv_checks, 'opencv_agrees_with_gpu_detect_resize', lambda dev: (asked.append(dev), verdict)[1])
         proc._prep_detect_chunk(frames, 64)
         proc._prep_detect_chunk(frames, 64)
         assert asked == [torch.device('cpu')] and proc.gpu_detect_resize is verdict
@@ -209,7 +209,7 @@ def test_unset_knob_decides_once_by_cv2(monkeypatch):
     # a self-check that cannot run (no GPU, no library, ...) settles on cv2
     KP, proc, log = _processor(monkeypatch, None)
     monkeypatch.setattr(KP, '_cv2', lambda: object())
-    monkeypatch.setattr(KP, 'opencv_agrees_with_gpu_detect_resize', lambda dev: (_ for _ in ()).throw(RuntimeError('no device')))
+    monkeypatch.setattr(KP.opencv_checks, 'opencv_agrees_with_gpu_detect_resize', lambda dev: (_ for _ in ()).throw(RuntimeError('no device')))
     proc._prep_detect_chunk(frames, 64)
     assert proc.gpu_detect_resize is False and not log['device'] and len(log['host']) == 2
 

@@ -169,7 +169,7 @@ def test_unset_knob_decides_once_by_cv2(monkeypatch):
         KP, proc, log = _processor(monkeypatch, None)
         asked = []
         monkeypatch.setattr(KP, '_cv2', lambda: object())
-        monkeypatch.setattr(KP, 'opencv_agrees_with_gpu_aligned_resize', lambda dev: (asked.append(dev), verdict)[1])
+        monkeypatch.setattr(KP.opencv_checks, 'opencv_agrees_with_gpu_aligned_resize', lambda dev: (asked.append(dev), verdict)[1])
         proc._aligned_face(img)
         proc._aligned_face(img)
         assert asked == [torch.device('cpu')] and proc.gpu_aligned_resize is verdict
@@ -177,7 +177,7 @@ def test_unset_knob_decides_once_by_cv2(monkeypatch):
     # a self-check that cannot run (no GPU, no library, ...) settles on cv2
     KP, proc, log = _processor(monkeypatch, None)
     monkeypatch.setattr(KP, '_cv2', lambda: object())
-    monkeypatch.setattr(KP, 'opencv_agrees_with_gpu_aligned_resize', lambda dev: (_ for _ in ()).throw(RuntimeError('no device')))
+    monkeypatch.setattr(KP.opencv_checks, 'opencv_agrees_with_gpu_aligned_resize', lambda dev: (_ for _ in ()).throw(RuntimeError('no device')))
     proc._aligned_face(img)
     assert proc.gpu_aligned_resize is False and not log['device'] and len(log['host']) == 1
 
@@ -204,7 +204,7 @@ def test_grey_four_channel_and_16_bit_images_go_to_the_host(monkeypatch):
 def test_identity_never_resizes(monkeypatch):
     for env in ('1', '0', None):
         KP, proc, log = _processor(monkeypatch, env)
-        monkeypatch.setattr(KP, 'opencv_agrees_with_gpu_aligned_resize', lambda dev: pytest.fail('self-check at identity'))
+        monkeypatch.setattr(KP.opencv_checks, 'opencv_agrees_with_gpu_aligned_resize', lambda dev: pytest.fail('self-check at identity'))
         for img in (image(512, 512), np.zeros((512, 512), np.uint8), np.zeros((512, 512, 4), np.uint16)):
             assert proc._aligned_face(img) is img
         assert log == {'device': [], 'host': []} and proc.gpu_aligned_resize is {'1': True, '0': False, None: None}[env]

@@ -310,17 +310,17 @@ def test_unset_knob_decides_once_by_cv2(monkeypatch):
         KP, proc = _processor(monkeypatch, _Helper(True), env=None)
         asked = []
         monkeypatch.setattr(KP, '_cv2', lambda: object())
-        monkeypatch.setattr(KP, 'opencv_agrees_with_gpu_small_frame_resize', lambda dev: (asked.append(dev), verdict)[1])
+        monkeypatch.setattr(KP.opencv_checks, 'opencv_agrees_with_gpu_small_frame_resize', lambda dev: (asked.append(dev), verdict)[1])
         assert proc._small_frames_probe(_Store([(0, 1)]), 1, frame, big) is verdict
         assert proc._small_frames_probe(_Store([(0, 1)]), 1, frame, big) is verdict
         assert asked == [torch.device('cuda', 0)] and proc.gpu_small_frames is verdict
     KP, proc = _processor(monkeypatch, _Helper(True), env=None)
     monkeypatch.setattr(KP, '_cv2', lambda: object())
-    monkeypatch.setattr(KP, 'opencv_agrees_with_gpu_small_frame_resize', lambda dev: (_ for _ in ()).throw(RuntimeError('no device')))
+    monkeypatch.setattr(KP.opencv_checks, 'opencv_agrees_with_gpu_small_frame_resize', lambda dev: (_ for _ in ()).throw(RuntimeError('no device')))
     assert not proc._small_frames_probe(_Store([(0, 1)]), 1, frame, big) and proc.gpu_small_frames is False
     # a frame the probe does not take never runs the self-check
     KP, proc = _processor(monkeypatch, _Helper(True), env=None)
-    monkeypatch.setattr(KP, 'opencv_agrees_with_gpu_small_frame_resize', lambda dev: pytest.fail('self-check'))
+    monkeypatch.setattr(KP.opencv_checks, 'opencv_agrees_with_gpu_small_frame_resize', lambda dev: pytest.fail('self-check'))
     assert not proc._small_frames_probe(_Store([(0, 1)]), 1, image(600, 800), image(600, 800))
     assert not proc._small_frames_probe(_Store([(0, 1)]), 1, frame, big[:-1])
     assert not proc._small_frames_probe(_Store([(0, 1)]), 1, frame, big.astype(np.float64))
