@@ -56,6 +56,7 @@ enum AttnForm {
   ATTN_X3_NQ16,      // attn_x3_kernel<4, dvt, 16>: D <= 256
   ATTN_X3_NQ0,       // attn_x3_kernel<4, dvt, 0>: Q and K re-staged per 128-wide chunk
   ATTN_X3_PACKED,    // attn_pack_kv_x3_kernel into the scratch + attn_x3_kernel<4, dvt, D / 16, true>
+  ATTN_X3_PRESPLIT,  // attn_x3_presplit_kernel: K / V already split by the projection GEMM (kv_split), no pack launch, no scratch
   ATTN_X1_PACKED,    // KEEP_MMA_X1 + KEEP_ATTN_X1: the single-fp16 instantiation of the same two kernels (<.., true> as their last argument)
   ATTN_X3_SMALL,     // attn_x3_small_kernel
   ATTN_X3_TWO_PASS,  // attn_scores_x3l_kernel into the scratch + attn_pv_x3l_kernel
@@ -615,6 +616,13 @@ static int launch_attn_bf16(const AttnP& p, const AttnPlan& pl, hipStream_t st) 
 typedef _Float16 af16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 af16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 af16x2 __attribute__((ext_vector_type(2)));
+typedef short as16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int au32x4 __attribute__((ext_vector_type(4)));
+
+// gfx950's transposed LDS read (ds_read_b64_tr_b16): needs EXEC all ones -- never call it from divergent code
+__device__ __forceinline__ af16x4 lds_tr_read(const char* lds) {
+  return __builtin_bit_cast(af16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) as16x4*)lds));
+}
 
 // PF: register prefetch of the next key tile (4-wave blocks); QREG: D <= 128, the wave's Q fragments (hi + lo, 8 x 16-d
 // steps) live in registers for the whole kernel -- loaded straight from global, never staged -- so a block's LDS is one
@@ -628,9 +636,17 @@ typedef _Float16 af16x2 __attribute__((ext_vector_type(2)));
 // and P are each rounded ONCE to fp16 and every product is one MFMA.  The rows lose their lo half: K pitch DC + 8 (17 16-byte slots) and
 // V^T pitch 40 (5 slots) are odd slot counts like 2 DC + 8 (33) and 72 (9), so the 16 rows one ds_read_b128 phase touches still fall on 16
 // different slots of the 64 banks.  1184 16-byte pieces per key tile instead of 2208; scores, softmax and accumulators unchanged.
-template <int WAVES, int DVT, int NQ, bool PACKED = false, bool X1 = false>
-__global__ __launch_bounds__(64 * WAVES, ((WAVES == 4 && NQ != 16) ? 2 : 1)) void attn_x3_kernel(AttnP p) {
+// KVS (keep_attention_kv_split; PACKED, WAVES 4, NQ 8, DVT 4, mode 2 with the LDS window tables, whole key tiles): K and V arrive pre-split from the
+// projection GEMM (keep_conv2d_split) in the natural token layout, a token's 512 bytes holding [hi x 128 | lo x 128] fp16 -- no pack
+// pass.  A key row is byte for byte a row of the K image above, fetched through `tpix`.  V stays row-major: two [32 keys][128 halves] tiles
+// (hi, then lo) of 8-row x 32-column subtiles, 16-byte chunk `ch` of a row at 2048 (row >> 3) + 512 (ch >> 2) + 64 (row & 7) +
+// 16 ((ch & 3) ^ ((row >> 2) & 3)), and the B operands of P.V are two ds_read_b64_tr_b16 each: keys 16 st + 4 lhi + 0..3 and + 8 of the
+// lane's dv column -- the key of every k slot is the one vt_pos puts there.  Every read of a 32-lane half covers 256 contiguous bytes and
+// every 8-lane phase of a ds_write_b128 128 of them: no bank conflicts.  2048 16-byte pieces per key tile instead of 2208.
+template <int WAVES, int DVT, int NQ, bool PACKED, bool X1, bool KVS>
+__device__ __forceinline__ void attn_x3_body(const AttnP p) {
   static_assert(!X1 || (PACKED && WAVES == 4 && NQ == 8), "the single-fp16 form exists for the packed D = 128 kernel only");
+  static_assert(!KVS || (PACKED && !X1 && WAVES == 4 && NQ == 8 && DVT == 4), "the pre-split form exists for the packed D = Dv = 128 kernel only");
   constexpr bool QREG = NQ > 0;             // NQ 16-wide d steps of Q live in registers (NQ = 16: D <= 256, one block per CU)
   constexpr int NQA = QREG ? NQ : 1;
   extern __shared__ __attribute__((aligned(16))) _Float16 smemx[];
@@ -841,9 +857,18 @@ __global__ __launch_bounds__(64 * WAVES, ((WAVES == 4 && NQ != 16) ? 2 : 1)) voi
   constexpr int PKK = PACKED ? 32 * ((X1 ? 1 : 2) * 16 * NQA + 8) / 8 : 1;   // 16-byte pieces of the K image (D == 16 NQ)
   constexpr int PKV = PACKED ? DVS * VP / 8 : 1;                      // ... of one V^T slice
   constexpr int PK16 = PKK + PKV;
-  constexpr int PKN = PACKED ? (PK16 + NT - 1) / NT : 1;
+  constexpr int PKN = (PACKED && !KVS) ? (PK16 + NT - 1) / NT : 1;
   uint4 preg[PKN];
+  au32x4 kq[KVS ? 4 : 1], vq[KVS ? 4 : 1];      // KVS: four K and four V pieces per thread and key tile
   auto pk_issue = [&](int kt) {
+    if constexpr (KVS) {      // K: piece (tid & 31) of rows (tid >> 5) + 8 u; V: rows 8 u + ((tid >> 2) & 7), half tid >> 7, chunk ((tid >> 5) & 3) * 4 + (tid & 3)
+      const au32x4* kb = reinterpret_cast<const au32x4*>(p.k + (long)wc.img_kv * p.k_bs + kh) + (tid & 31);
+      const au32x4* vb = reinterpret_cast<const au32x4*>(p.v + (long)wc.img_kv * p.v_bs + vh) + ((tid >> 7) << 4) + (((tid >> 5) & 3) << 2) + (tid & 3);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) kq[u] = kb[(long)tpix[kt * 32 + (tid >> 5) + 8 * u] * (p.k_ts >> 2)];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) vq[u] = vb[(long)tpix[kt * 32 + 8 * u + ((tid >> 2) & 7)] * (p.v_ts >> 2)];
+    } else {
     const long tile = ((long)b * p.H + head) * ((p.Lk + 31) >> 5) + kt;
     const uint4* src = reinterpret_cast<const uint4*>(p.kv_pack) + tile * (PKK + p.nslices * PKV);
     const int vs = PKK + (dv0 / DVS) * PKV;
@@ -853,14 +878,36 @@ __global__ __launch_bounds__(64 * WAVES, ((WAVES == 4 && NQ != 16) ? 2 : 1)) voi
       preg[u] = make_uint4(0u, 0u, 0u, 0u);
       if (i < PK16) preg[u] = src[i < PKK ? i : vs + (i - PKK)];
     }
-  };
-  auto pk_commit = [&]() {
-#pragma unroll
-    for (int u = 0; u < PKN; ++u) {
-      const int i = tid + u * NT;
-      if (i < PK16) reinterpret_cast<uint4*>(Ks)[i] = preg[u];
     }
   };
+  auto pk_commit = [&]() {
+    if constexpr (KVS) {
+      const int r7 = (tid >> 2) & 7;
+      char* vimg = reinterpret_cast<char*>(Vt) + (tid >> 7) * 8192 + ((tid >> 5) & 3) * 512 + r7 * 64;
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        reinterpret_cast<au32x4*>(Ks)[((tid >> 5) + 8 * u) * (PKK / 32) + (tid & 31)] = kq[u];
+        *reinterpret_cast<au32x4*>(vimg + u * 2048 + 16 * ((tid & 3) ^ (((u & 1) << 1) | (r7 >> 2)))) = vq[u];      // ((row >> 2) & 3 of row 8 u + r7)
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < PKN; ++u) {
+        const int i = tid + u * NT;
+        if (i < PK16) reinterpret_cast<uint4*>(Ks)[i] = preg[u];
+      }
+    }
+  };
+  // KVS: the lane's two transposed-read addresses in the V image (T = ds_read_b64_tr_b16: lane 4 q + pp of a 16-lane group supplies row q, columns
+  // 4 pp .. 4 pp + 3 of a 4-row x 16-column block and receives column (lane & 15) of the four rows): rows 4 lhi + q (+ 8) of a 16-key step,
+  // columns 16 gg .. + 15 of a 32-wide dv block; step, dv block and hi / lo are immediate offsets (4096 st + 512 j + 8192 half)
+  [[maybe_unused]] const char* vtr0 = reinterpret_cast<const char*>(Vt);
+  [[maybe_unused]] const char* vtr1 = vtr0;
+  if constexpr (KVS) {
+    const int q = (lane >> 2) & 3, pp = lane & 3, gg = (lane >> 4) & 1;
+    const int ro = 64 * (4 * lhi + q) + 8 * (pp & 1), cx = 2 * gg + (pp >> 1);
+    vtr0 += ro + 16 * (cx ^ lhi);
+    vtr1 += 2048 + ro + 16 * (cx ^ (2 | lhi));
+  }
 
   const int my_q = q0 + wave * 32 + l31;
   // ---- Q fragments of this lane: row my_q, d in [16*step + 8*lhi, +8), split once
@@ -1024,6 +1071,15 @@ __global__ __launch_bounds__(64 * WAVES, ((WAVES == 4 && NQ != 16) ? 2 : 1)) voi
       }
 #pragma unroll
       for (int j = 0; j < DVT; ++j) {
+        if constexpr (KVS) {
+          const int vo = 4096 * st + 512 * j;
+          const af16x8 vh8 = __builtin_shufflevector(lds_tr_read(vtr0 + vo), lds_tr_read(vtr1 + vo), 0, 1, 2, 3, 4, 5, 6, 7);
+          const af16x8 vl8 = __builtin_shufflevector(lds_tr_read(vtr0 + 8192 + vo), lds_tr_read(vtr1 + 8192 + vo), 0, 1, 2, 3, 4, 5, 6, 7);
+          o[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pl, vh8, o[j], 0, 0, 0);
+          o[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph, vl8, o[j], 0, 0, 0);
+          o[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph, vh8, o[j], 0, 0, 0);
+          continue;
+        }
         const _Float16* vrow = Vt + (j * 32 + l31) * VP + (st * 2 + lhi) * 8;
         const af16x8 vh8 = *reinterpret_cast<const af16x8*>(vrow);
         if (!X1) {
@@ -1065,6 +1121,14 @@ __global__ __launch_bounds__(64 * WAVES, ((WAVES == 4 && NQ != 16) ? 2 : 1)) voi
     }
   }
 }
+
+template <int WAVES, int DVT, int NQ, bool PACKED = false, bool X1 = false>
+__global__ __launch_bounds__(64 * WAVES, ((WAVES == 4 && NQ != 16) ? 2 : 1)) void attn_x3_kernel(AttnP p) {
+  attn_x3_body<WAVES, DVT, NQ, PACKED, X1, false>(p);
+}
+
+// the pre-split form (KVS above): D = Dv = 128, four waves, two blocks per CU
+__global__ __launch_bounds__(256, 2) void attn_x3_presplit_kernel(AttnP p) { attn_x3_body<4, 4, 8, true, false, true>(p); }
 
 // K / V^T tile images for the PACKED variant above: one block per (key tile, head, batch) gathers the tile's 32 key rows
 // (window / sparse-causal index math once per element instead of once per query block), applies the range scales, splits,
@@ -1144,6 +1208,15 @@ static int launch_attn_x3_packed(const AttnP& p, const AttnPlan& pl, hipStream_t
   dim3 grid(cdiv(p.Lq, 128), p.H * p.nslices, p.B);
   hipLaunchKernelGGL((attn_x3_kernel<4, DVT, NQ, true, X1>), grid, dim3(256), pl.lds, st, p);
   KEEP_LAUNCH_CHECK("keep_attention(x3 packed)");
+  return KEEP_OK;
+}
+
+static int launch_attn_x3_presplit(const AttnP& p, const AttnPlan& pl, hipStream_t st) {
+  const int rc = keep_raise_lds_limit<attn_x3_presplit_kernel>("keep_attention");
+  if (rc != KEEP_OK) return rc;
+  dim3 grid(p.Lq / 128, p.nslices, p.B);
+  hipLaunchKernelGGL(attn_x3_presplit_kernel, grid, dim3(256), pl.lds, st, p);
+  KEEP_LAUNCH_CHECK("keep_attention(x3 pre-split)");
   return KEEP_OK;
 }
 
@@ -2288,7 +2361,7 @@ static int attn_args_in(const keep_attention_args* src, keep_attention_args& a) 
 // and the plan `pl`.  keep_attention_workspace_bytes asks with unlimited scratch and keep_attention with the caller's, so the
 // two cannot disagree; a form whose scratch need exceeds `scratch_avail` is skipped.  Pointers are only tested for
 // alignment, never dereferenced (the query is called without tensors).
-static int plan_attention(const keep_attention_args& a, int64_t scratch_avail, AttnP& p, AttnPlan& pl) {
+static int plan_attention(const keep_attention_args& a, int64_t scratch_avail, AttnP& p, AttnPlan& pl, bool kv_split = false) {
   KEEP_REQUIRE(a.B > 0 && a.H > 0 && a.Lq > 0 && a.Lk > 0 && a.D > 0 && a.Dv > 0, "keep_attention: bad dims");
   KEEP_REQUIRE(a.D % 2 == 0 && (a.D <= 128 || a.D % 128 == 0), "keep_attention: D=%d must be even and (<= 128 or a multiple of 128)", a.D);
   KEEP_REQUIRE(a.mode >= 0 && a.mode <= 2, "keep_attention: bad mode %d", a.mode);
@@ -2347,6 +2420,25 @@ static int plan_attention(const keep_attention_args& a, int64_t scratch_avail, A
   const size_t ntl = (size_t)(a.Lk + 31) / 32;                // key tiles
   const size_t win_tables = ntl * 32 * 4 + ntl * 16 + ntl * 32;    // window tables: pixel per key, packed + byte region ids
 
+  // kv_split: k / v hold the projection GEMM's split-fp16 halves -- ONE form reads them; whatever else is asked for is refused, and the caller
+  // then does not ask the GEMM for the split output
+  if (kv_split) {
+    const bool ok = a.mma == KEEP_MMA_X3 && a.in_dtype == KEEP_F32 && a.mode == 2 && a.D == 128 && a.Dv == 128 && a.H == 1 && a.Lq % 128 == 0 &&
+                    a.Lk % 32 == 0 && a.Lk <= 4096 && !a.q_amax && !(a.flags & KEEP_ATTN_NO_X3) && rows16(a.q, a.q_bs, a.q_ts, a.q_hs, 4) &&
+                    rows16(a.k, a.k_bs, a.k_ts, 0, 128) && rows16(a.v, a.v_bs, a.v_ts, 0, 128);
+    if (!ok) {
+      keep_set_error("keep_attention_kv_split: kv_split (k / v as the projection GEMM's split-fp16 halves) needs KEEP_MMA_X3 on fp32 tensors, mode 2, "
+                     "D = Dv = 128, H = 1, Lq %% 128 == 0, Lk %% 32 == 0, Lk <= 4096, no range probes, 16-byte aligned q rows and k / v "
+                     "strides that are multiples of 128");
+      return KEEP_EUNSUP;
+    }
+    pl.form = ATTN_X3_PRESPLIT;
+    pl.waves = 4;
+    pl.nq = 8;
+    pl.win_tables = true;
+    pl.lds = (size_t)(32 * (2 * 128 + 8) + 128 * 72) * 2 + win_tables;      // the packed form's layout: the V image takes 16 KB of the V^T area
+    return KEEP_OK;
+  }
   if (x1) {
     // the packed form of KEEP_MMA_X3 on hi halves alone: attn_pack_kv_x3_kernel<128, 128, true> + attn_x3_kernel<4, 4, 8, true, true>
     ATTN_X1_ADMITS(a.in_dtype == KEEP_F32, "keep_attention: KEEP_MMA_X1 needs fp32 q / k / v (in_dtype KEEP_F32)");
@@ -2485,6 +2577,7 @@ static void attn_plan_kernel_name(const AttnPlan& pl, char* out, size_t n) {
     case ATTN_X3_PACKED:
       snprintf(out, n, "attn_pack_kv_x3_kernel<%d, %d, false> + attn_x3_kernel<4, %d, %d, true, false>", 16 * pl.nq, dvs, pl.dvt, pl.nq);
       return;
+    case ATTN_X3_PRESPLIT: snprintf(out, n, "attn_x3_presplit_kernel"); return;
     case ATTN_X1_PACKED:
       snprintf(out, n, "attn_pack_kv_x3_kernel<%d, %d, true> + attn_x3_kernel<4, %d, %d, true, true>", 16 * pl.nq, dvs, pl.dvt, pl.nq);
       return;
@@ -2497,7 +2590,7 @@ static void attn_plan_kernel_name(const AttnPlan& pl, char* out, size_t n) {
 }
 
 // keep_cv_hip.h: what keep_attention would launch for exactly these arguments (host only: no pointer is dereferenced, nothing launched)
-extern "C" int32_t keep_attention_plan(const keep_attention_args* a_in, keep_attention_plan_out* out) {
+static int attention_plan_out(const keep_attention_args* a_in, bool kv_split, keep_attention_plan_out* out) {
   KEEP_REQUIRE(out != nullptr, "keep_attention_plan: null out");
   memset(out, 0, sizeof(*out));
   keep_attention_args a;
@@ -2506,7 +2599,7 @@ extern "C" int32_t keep_attention_plan(const keep_attention_args* a_in, keep_att
   AttnP p;
   AttnPlan pl;
   const bool ws_ok = a.workspace && (uintptr_t)a.workspace % 16 == 0;
-  const int rc = plan_attention(a, ws_ok ? a.workspace_bytes : 0, p, pl);
+  const int rc = plan_attention(a, ws_ok ? a.workspace_bytes : 0, p, pl, kv_split);
   if (rc != KEEP_OK) return rc;
   out->waves = pl.waves;
   out->dvt = pl.dvt;
@@ -2516,12 +2609,21 @@ extern "C" int32_t keep_attention_plan(const keep_attention_args* a_in, keep_att
   out->lds_bytes = (int64_t)pl.lds;
   AttnP p_all;
   AttnPlan pl_all;      // the same call with unlimited scratch: the answer of keep_attention_workspace_bytes
-  out->scratch_bytes = plan_attention(a, INT64_MAX, p_all, pl_all) == KEEP_OK ? pl_all.scratch : 0;
+  out->scratch_bytes = plan_attention(a, INT64_MAX, p_all, pl_all, kv_split) == KEEP_OK ? pl_all.scratch : 0;
   attn_plan_kernel_name(pl, out->kernel, sizeof(out->kernel));
   return KEEP_OK;
 }
 
-extern "C" int32_t keep_attention(const keep_attention_args* a_in, void* stream) {
+extern "C" int32_t keep_attention_plan(const keep_attention_args* a_in, keep_attention_plan_out* out) {
+  return attention_plan_out(a_in, false, out);
+}
+
+// keep_cv_hip.h: what keep_attention_kv_split would launch (KEEP_EUNSUP where it would refuse)
+extern "C" int32_t keep_attention_kv_split_plan(const keep_attention_args* a_in, keep_attention_plan_out* out) {
+  return attention_plan_out(a_in, true, out);
+}
+
+static int attention_launch(const keep_attention_args* a_in, bool kv_split, void* stream) {
   keep_attention_args a;
   const int rc_in = attn_args_in(a_in, a);
   if (rc_in != KEEP_OK) return rc_in;
@@ -2529,7 +2631,7 @@ extern "C" int32_t keep_attention(const keep_attention_args* a_in, void* stream)
   AttnP p;
   AttnPlan pl;
   const bool ws_ok = a.workspace && (uintptr_t)a.workspace % 16 == 0;
-  const int rc = plan_attention(a, ws_ok ? a.workspace_bytes : 0, p, pl);
+  const int rc = plan_attention(a, ws_ok ? a.workspace_bytes : 0, p, pl, kv_split);
   if (rc != KEEP_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
   const bool one_wave = pl.waves == 1;
@@ -2557,6 +2659,8 @@ extern "C" int32_t keep_attention(const keep_attention_args* a_in, void* stream)
       return with_dvt(pl.dvt, [&](auto dvt) {
         return pl.nq == 8 ? launch_attn_x3_packed<decltype(dvt)::value, 8>(p, pl, st) : launch_attn_x3_packed<decltype(dvt)::value, 16>(p, pl, st);
       });
+    case ATTN_X3_PRESPLIT:
+      return launch_attn_x3_presplit(p, pl, st);
     case ATTN_X1_PACKED:
       p.kv_pack = (const _Float16*)a.workspace;
       return launch_attn_x3_packed<4, 8, true>(p, pl, st);
@@ -2572,6 +2676,11 @@ extern "C" int32_t keep_attention(const keep_attention_args* a_in, void* stream)
   keep_set_error("keep_attention: no kernel form planned");
   return KEEP_EINVAL;
 }
+
+extern "C" int32_t keep_attention(const keep_attention_args* a_in, void* stream) { return attention_launch(a_in, false, stream); }
+
+// keep_cv_hip.h: keep_attention on k / v that keep_conv2d_split wrote as split-fp16 halves (attn_x3_presplit_kernel; no workspace)
+extern "C" int32_t keep_attention_kv_split(const keep_attention_args* a_in, void* stream) { return attention_launch(a_in, true, stream); }
 
 // ------------------------------------------------------------------------------------------------ fused GMFlow FFN
 // GM/transformer.py:139-142,182: message = Linear(8C -> C)( GELU( Linear(2C -> 8C)( cat[source, message] ) ) ), no biases,

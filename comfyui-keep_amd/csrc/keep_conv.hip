@@ -1781,6 +1781,7 @@ static void fill_conv_params(const keep_conv2d_args* a, ConvP& p) {
   p.ln_beta = a->ln_beta;
   p.ln_eps = a->ln_eps;
   p.kslice_steps = 0;
+  p.split_c0 = p.split_c1 = 0;
   p.bias = a->bias;
   p.out = (float*)a->out;
   p.pro_scale = a->pro_scale;
@@ -2159,11 +2160,31 @@ static int plan_form(const keep_conv2d_args* a, ConvP& p, const ConvGeom& g, Con
   return plan_f32(a, p, g, pl);
 }
 
-static int plan_conv(const keep_conv2d_args* a, ConvP& p, ConvPlan& pl) {
+// The output columns keep_conv2d_split writes as split-fp16 halves (keep_cv_hip.h); {0, 0}: none -- keep_conv2d itself.
+struct ConvSplit {
+  int c0, c1;
+};
+
+static int plan_conv(const keep_conv2d_args* a, ConvP& p, ConvPlan& pl, ConvSplit sp) {
   memset(&pl, 0, sizeof(pl));
   fill_conv_params(a, p);
   pl.wide = (a->Ho % 8 == 0 && a->Wo % 32 == 0);
   const int rc = plan_form(a, p, conv_geom(a), pl);
+  // split-fp16 output columns: the full-row epilogue of the un-sliced x3 GEMM form writes them (x3_gather_epilogue), nothing else does
+  if (rc == KEEP_OK && (sp.c0 || sp.c1)) {
+    const bool ok = a->mma == KEEP_MMA_X3 && pl.path == PATH_GATHER_X3 && pl.form == FORM_X3_GATHER && pl.gemm && pl.plain && pl.split_k == 1 &&
+                    a->out_dtype == KEEP_F32 && a->epi_act == KEEP_ACT_NONE && !a->residual && !a->aux && !a->stats_out && !a->ln_gamma &&
+                    a->Cout % 128 == 0 && a->out_ld % 128 == 0 && sp.c0 >= 0 && sp.c0 < sp.c1 && sp.c1 <= a->Cout &&
+                    sp.c0 % 128 == 0 && sp.c1 % 128 == 0 && p.M % 128 == 0 && (long)a->out_ld * 4 * 128 < (1L << 30);
+    if (!ok) {
+      keep_set_error("keep_conv2d_split: split_c0 / split_c1 (split-fp16 output columns) need the KEEP_MMA_X3 GEMM form (1x1, stride 1, no prologue / "
+                     "activation / residual / aux / split-K / statistics / LayerNorm), fp32 output, Cout, out_ld and both bounds multiples of 128 "
+                     "and N*Ho*Wo %% 128 == 0");
+      return KEEP_EUNSUP;
+    }
+    p.split_c0 = sp.c0;
+    p.split_c1 = sp.c1;
+  }
   if (rc == KEEP_OK) plan_kernel_name(a, pl);
   return rc;
 }
@@ -2187,7 +2208,7 @@ extern "C" int32_t keep_sizeof_conv2d_args(void) { return (int32_t)sizeof(keep_c
 
 // What keep_conv2d_plan and keep_conv2d share: the caller's struct in this library's layout, validated and planned (`launch`: with the
 // tensors a launch reads)
-static int conv_prelude(const keep_conv2d_args* a_in, bool launch, keep_conv2d_args& a, ConvP& p, ConvPlan& pl) {
+static int conv_prelude(const keep_conv2d_args* a_in, bool launch, keep_conv2d_args& a, ConvP& p, ConvPlan& pl, ConvSplit sp = {0, 0}) {
   int rc = conv_args_in(a_in, a);
   if (rc != KEEP_OK) return rc;
   rc = validate_conv(&a);
@@ -2198,15 +2219,15 @@ static int conv_prelude(const keep_conv2d_args* a_in, bool launch, keep_conv2d_a
     KEEP_REQUIRE(!a.pro_scale || ((uintptr_t)a.pro_scale % 16 == 0 && (uintptr_t)a.pro_shift % 16 == 0),
                  "keep_conv2d: pro_scale/pro_shift must be 16-byte aligned");
   }
-  return plan_conv(&a, p, pl);
+  return plan_conv(&a, p, pl, sp);
 }
 
-extern "C" int32_t keep_conv2d_plan(const keep_conv2d_args* a_in, keep_conv2d_plan_out* out) {
+static int conv_plan_out(const keep_conv2d_args* a_in, ConvSplit sp, keep_conv2d_plan_out* out) {
   KEEP_REQUIRE(out != nullptr, "keep_conv2d_plan: null output");
   keep_conv2d_args a_local;
   ConvP p;
   ConvPlan pl;
-  const int rc = conv_prelude(a_in, false, a_local, p, pl);
+  const int rc = conv_prelude(a_in, false, a_local, p, pl, sp);
   if (rc != KEEP_OK) return rc;
   const keep_conv2d_args* a = &a_local;
   memset(out, 0, sizeof(*out));
@@ -2222,6 +2243,14 @@ extern "C" int32_t keep_conv2d_plan(const keep_conv2d_args* a_in, keep_conv2d_pl
   out->path = (int32_t)pl.path;
   strncpy(out->kernel, pl.kernel, sizeof(out->kernel) - 1);
   return KEEP_OK;
+}
+
+extern "C" int32_t keep_conv2d_plan(const keep_conv2d_args* a_in, keep_conv2d_plan_out* out) { return conv_plan_out(a_in, {0, 0}, out); }
+
+// keep_cv_hip.h: the plan of keep_conv2d_split for these arguments and this column range (KEEP_EUNSUP where the launch would refuse)
+extern "C" int32_t keep_conv2d_split_plan(const keep_conv2d_args* a_in, int32_t split_c0, int32_t split_c1, keep_conv2d_plan_out* out) {
+  KEEP_REQUIRE(split_c0 || split_c1, "keep_conv2d_split: empty column range");
+  return conv_plan_out(a_in, {split_c0, split_c1}, out);
 }
 
 // launch-or-name (keep_conv_common.h): one instantiation's device symbol, demangled, without the return type and the parameter list
@@ -2251,11 +2280,11 @@ void keep_conv_trace_add(ConvTrace* tr, const char* mangled) {
 }
 
 // keep_conv2d (tr == NULL) and keep_conv2d_launch_plan (a trace: every KEEP_CONV_LAUNCH names its kernel instead of launching it)
-static int conv_launch(const keep_conv2d_args* a_in, void* stream, ConvTrace* tr) {
+static int conv_launch(const keep_conv2d_args* a_in, void* stream, ConvTrace* tr, ConvSplit sp = {0, 0}) {
   keep_conv2d_args a_local;
   ConvP p;
   ConvPlan pl;
-  int rc = conv_prelude(a_in, true, a_local, p, pl);
+  int rc = conv_prelude(a_in, true, a_local, p, pl, sp);
   if (rc != KEEP_OK) return rc;
   const keep_conv2d_args* a = &a_local;
   if (pl.path == PATH_NEEDS_PRENORM) {
@@ -2429,6 +2458,12 @@ static int conv_launch(const keep_conv2d_args* a_in, void* stream, ConvTrace* tr
 }
 
 extern "C" int32_t keep_conv2d(const keep_conv2d_args* a_in, void* stream) { return conv_launch(a_in, stream, nullptr); }
+
+// keep_cv_hip.h: keep_conv2d with output columns [split_c0, split_c1) written as split-fp16 halves (x3_gather_epilogue of the x3 GEMM form)
+extern "C" int32_t keep_conv2d_split(const keep_conv2d_args* a_in, int32_t split_c0, int32_t split_c1, void* stream) {
+  KEEP_REQUIRE(split_c0 || split_c1, "keep_conv2d_split: empty column range");
+  return conv_launch(a_in, stream, nullptr, {split_c0, split_c1});
+}
 
 extern "C" int32_t keep_conv2d_launch_plan(const keep_conv2d_args* a_in, keep_conv2d_launch_plan_out* out) {
   KEEP_REQUIRE(out != nullptr, "keep_conv2d_launch_plan: null output");

@@ -63,6 +63,8 @@ struct ConvP {
   const float* ln_beta;
   float ln_eps;
   int kslice_steps;           // x3 GEMM form: K steps (of 32 channels) per canonical slice of keep_gemm_x3l.hip's sums; 0 = one sequential sum
+  int split_c0, split_c1;     // x3 GEMM form, full row tiles: output columns [split_c0, split_c1) (multiples of 128) are stored as fp16 halves,
+                              // [hi x 128 | lo x 128] in the 512 bytes of each 128-column group (keep_conv2d_split: keep_attention_kv_split's operands); equal: none
 };
 
 

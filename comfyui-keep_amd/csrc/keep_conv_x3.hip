@@ -578,7 +578,10 @@ __device__ __forceinline__ void x3_gather_epilogue(const ConvP& p, f32x16 (&acc)
   const bool cok = co < p.Cout;
   const int row0 = wm * WR + prow;                       // row of iteration 0 inside the block tile
   const __amdgpu_buffer_rsrc_t out_rsrc = make_rsrc(p.out + m0 * p.out_ld, BM * p.out_ld * 4);
-  const int v_out = cok ? (row0 * p.out_ld + co) * 4 : (int)0x80000000;
+  // split-fp16 output columns (ConvP.split_c0 / split_c1): the lane's four values go out as 4 hi + 4 lo halves, hi at byte
+  // (co / 128) * 512 + (co % 128) * 2 of the row and lo 256 bytes further on, instead of 16 bytes of fp32 at co * 4
+  const bool split = SIMPLE && n0 >= p.split_c0 && n0 < p.split_c1;
+  const int v_out = !cok ? (int)0x80000000 : split ? row0 * p.out_ld * 4 + (co >> 7) * 512 + (co & 127) * 2 : (row0 * p.out_ld + co) * 4;
   __amdgpu_buffer_rsrc_t res_rsrc = out_rsrc, aux_rsrc = out_rsrc, ws_rsrc = out_rsrc;
   int v_res = (int)0x80000000, v_aux = (int)0x80000000, v_ws = (int)0x80000000;
   if (p.res) {
@@ -657,7 +660,16 @@ __device__ __forceinline__ void x3_gather_epilogue(const ConvP& p, f32x16 (&acc)
         for (int q = 0; q < 4; ++q) e[q] += rr[q];
       }
     }
-    {
+    if (SIMPLE && split) {      // (block-uniform: the range is cut at multiples of 128 columns, a block tile is 64 or 128 wide)
+      f16x4 h4, l4;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        h4[q] = (_Float16)e[q];
+        l4[q] = (_Float16)(e[q] - (float)h4[q]);
+      }
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, h4), out_rsrc, v_out + it * RPI * p.out_ld * 4, 0, KEEP_ST_AUX_GEMM);
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, l4), out_rsrc, v_out + it * RPI * p.out_ld * 4 + 256, 0, KEEP_ST_AUX_GEMM);
+    } else {
       u32x4 o;
       o.x = __float_as_uint(e[0]); o.y = __float_as_uint(e[1]); o.z = __float_as_uint(e[2]); o.w = __float_as_uint(e[3]);
       __builtin_amdgcn_raw_buffer_store_b128(o, out_rsrc, v_out + it * RPI * p.out_ld * 4, 0, KEEP_ST_AUX_GEMM);

@@ -150,6 +150,10 @@ _CV_SIGNATURES = {
     'keep_frame_signature_u8': [_vp, _i32, _i32, _i32, _vp, _vp],
     'keep_paste_face_w': [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp],
     'keep_tone_match_u8': [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp],
+    'keep_conv2d_split': [C.POINTER(ConvArgs), _i32, _i32, _vp],
+    'keep_conv2d_split_plan': [C.POINTER(ConvArgs), _i32, _i32, C.POINTER(ConvPlanOut)],      # (host-only: no stream argument)
+    'keep_attention_kv_split': [C.POINTER(AttnArgs), _vp],
+    'keep_attention_kv_split_plan': [C.POINTER(AttnArgs), C.POINTER(AttnPlanOut)],            # (host-only: no stream argument)
 }
 CV_EXPORTED_SYMBOLS = ['keep_cv_abi_version'] + list(_CV_SIGNATURES)
 
@@ -251,6 +255,14 @@ def conv2d_plan(a):
     return out
 
 
+def conv2d_split_plan(a, split_cols):
+    """keep_conv2d_split_plan: ``conv2d_plan`` for a launch that writes output columns ``split_cols = (c0, c1)`` as split-fp16 halves."""
+    lib = load(check_device=False)
+    out = ConvPlanOut()
+    _check(lib.keep_conv2d_split_plan(C.byref(a), int(split_cols[0]), int(split_cols[1]), C.byref(out)), 'keep_conv2d_split_plan')
+    return out
+
+
 def conv2d_launch_plan(a):
     """keep_conv2d_launch_plan: the template instantiations keep_conv2d would launch for exactly these arguments, in launch order, joined
     by " + " (keep_conv2d_plan names the form; this names what the launch takes for the real N, flags and activations); a refused call
@@ -266,11 +278,15 @@ def attention_workspace_bytes(a):
     return int(load(check_device=False).keep_attention_workspace_bytes(C.byref(a)))
 
 
-def attention_plan(a):
+def attention_plan(a, kv_split=False):
     """keep_attention_plan: what keep_attention would launch for exactly these arguments (instantiation, LDS, scratch); a refused call raises
-    KeepHipError with the library's code and reason.  Needs no device."""
+    KeepHipError with the library's code and reason.  Needs no device.  ``kv_split``: keep_attention_kv_split_plan, the same for k / v
+    that keep_conv2d_split wrote as split-fp16 halves."""
     lib = load(check_device=False)
     out = AttnPlanOut()
+    if kv_split:
+        _check(lib.keep_attention_kv_split_plan(C.byref(a), C.byref(out)), 'keep_attention_kv_split_plan')
+        return out
     _check(lib.keep_attention_plan(C.byref(a), C.byref(out)), 'keep_attention_plan')
     return out
 
@@ -307,13 +323,20 @@ def conv2d_launch(a):
     _check(load().keep_conv2d(C.byref(a), _stream()), 'keep_conv2d')
 
 
+def conv2d_split_launch(a, split_cols):
+    _check(load().keep_conv2d_split(C.byref(a), int(split_cols[0]), int(split_cols[1]), _stream()), 'keep_conv2d_split')
+
+
 def conv2d(**kw):
     conv2d_launch(conv_args(**kw))
 
 
-def attention(**kw):
+def attention(kv_split=False, **kw):
     lib = load()
     a = attn_args(**kw)
+    if kv_split:      # k / v are keep_conv2d_split's halves: one launch, no workspace
+        _check(lib.keep_attention_kv_split(C.byref(a), _stream()), 'keep_attention_kv_split')
+        return
     need = int(lib.keep_attention_workspace_bytes(C.byref(a)))       # the library asks; the host only allocates
     if need > 0:                                                     # (-1: a refused MMA_X1 call -- keep_attention below says why)
         ws = torch.empty((need + 3) // 4, dtype=torch.float32, device=kw['q'].device)   # stream-ordered free after the call

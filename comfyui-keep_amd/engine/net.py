@@ -841,18 +841,23 @@ class KeepNet:
         Ltok = h8 * w8
         wqkv = w[f'{p}.qkv.weight']
         o = torch.empty_like(src)
+        sq, skv = ((Ltok * 3 * C, 3 * C, 0),) * 2 if tgt is src else ((Ltok * C, C, 0), (Ltok * 2 * C, 2 * C, 0))
+        # x3 policy: the projection writes k and v as the split-fp16 halves the attention kernel keeps in LDS, so no pack pass runs between
+        # the two (keep_conv2d_split, keep_attention_kv_split) -- where the library's plan takes the attention call that way
+        cols = (C, 3 * C) if tgt is src else (0, 2 * C)
+        split = (self.of.mma == L.MMA_X3 and self.of.x3_twin(wqkv) is not None and
+                 self.of.kv_split_ok(B=n_img * 4, Lq=Ltok // 4, Lk=Ltok // 4, D=C, Dv=C, q_str=sq, k_str=skv, v_str=skv, img_h=h8, img_w=w8,
+                                     ksplit=2, shift=shift, n_img=n_img, gemm=(Ltok, C, cols[1], cols)))
         if tgt is src:
-            qkv = self.of.linear(src, wqkv, out_bf16=True, bounded=True, n_img=n_img)
+            qkv = self.of.linear(src, wqkv, out_bf16=True, bounded=True, n_img=n_img, split_cols=cols if split else None)
             q, k, v = qkv, ops.offset(qkv, C), ops.offset(qkv, 2 * C)
-            sq = skv = (Ltok * 3 * C, 3 * C, 0)
         else:
             q = self.of.linear(src, wqkv[:C], out_bf16=True, bounded=True, n_img=n_img)
-            kv = self.of.linear(tgt, wqkv[C:], out_bf16=True, bounded=True, n_img=n_img)
+            kv = self.of.linear(tgt, wqkv[C:], out_bf16=True, bounded=True, n_img=n_img, split_cols=cols if split else None)
             k, v = kv, ops.offset(kv, C)
-            sq, skv = (Ltok * C, C, 0), (Ltok * 2 * C, 2 * C, 0)
         self.of.attention(q, k, v, o, B=n_img * 4, H=1, Lq=Ltok // 4, Lk=Ltok // 4, D=C, Dv=C, scale=1.0 / (C ** 0.5),
                       q_str=sq, k_str=skv, v_str=skv, o_str=(Ltok * C, C, 0), mode=2, img_h=h8, img_w=w8, ksplit=2,
-                      shift=shift, kv_rot=kv_rot, n_img=n_img)
+                      shift=shift, kv_rot=kv_rot, n_img=n_img, kv_split=split)
         n1 = (w[f'{p}.norm1.weight'], w[f'{p}.norm1.bias'], 1e-5)
         fuse = self.of.ln_fusable(w[f'{p}.merge.weight'], Ltok)      # LayerNorm in the GEMM's epilogue (keep_conv2d ln_gamma, ABI v16)
         if not ffn:

@@ -19,6 +19,7 @@ from . import hiplib as L
 
 TOKEN_LINEAR = os.environ.get('KEEP_NO_TOKEN_LINEAR') is None   # dev switch: streaming GEMM for the GMFlow projections
 UP2_PHASES = os.environ.get('KEEP_X3_UP2', '1') != '0'      # x3 policy: nearest x2 + 3x3 as four 2x2-tap phase convolutions (A/B: 0)
+ATTN_PRESPLIT = os.environ.get('KEEP_X3_ATTN_PRESPLIT', '1') != '0'   # x3 policy: GMFlow's k / v projections write split-fp16 halves, no pack pass (A/B: 0)
 FUSE_LN = os.environ.get('KEEP_X3_FUSE_LN', '1') != '0'      # x3 policy: GMFlow `merge -> norm1` / `mlp.2 -> norm2` LayerNorms in the GEMM epilogue (A/B: 0)
 USE_BK256 = bool(int(os.environ.get('KEEP_BK256', '0')))   # measured slower than BK=64 + split-K at B<=4 (kept for A/B)
 # bf16 policy: inputs of fewer pixels (N*H*W) than this skip the normalise+activate -> bf16 pass in front of the halo
@@ -60,12 +61,12 @@ class Stats:
         self.part, self.P, self.amax = part, P, amax
 
 
-def _plan(a, key):
+def _plan(a, key, split_cols=None):
     """keep_conv2d_plan for these arguments, cached by everything the decision can depend on (shapes, flags, which
-    optional tensors exist, pointer alignment class) -- never by values."""
+    optional tensors exist, pointer alignment class) -- never by values.  ``split_cols`` (part of ``key``): keep_conv2d_split_plan."""
     pl = _PLAN_CACHE.get(key)
     if pl is None:
-        pl = _PLAN_CACHE[key] = Plan(L.conv2d_plan(a))
+        pl = _PLAN_CACHE[key] = Plan(L.conv2d_plan(a) if split_cols is None else L.conv2d_split_plan(a, split_cols))
     return pl
 
 
@@ -118,6 +119,7 @@ class Ops:
         # what the library answered to `this call under L.MMA_X1?` (_route), per rule: the blob twin and the phase twin (``up2_x1``): base
         # plan key -> the call's X1 Plan | False; ``attn_x1``: shape key -> True | False
         self._x1_route, self._up2_x1_route, self._attn_x1_route = {}, {}, {}
+        self._kv_split_route = {}      # shape key -> True | False: the library's answer to `this attention call with kv_split?`
         self.x1_flags = L.CONV_X1_GEMM      # opt-in form bits OR-ed into the X1 plan query and launch
         self.x1_base = L.MMA_X3             # the policy a call without a twin, or one the library refuses, stays on
         self.x1_base_kernel = None          # restriction: substitute only where the base plan is this kernel, un-split (None: everywhere)
@@ -162,7 +164,7 @@ class Ops:
         self._x3_table = ([a for a, _, _ in x3_scales], list(x3_scales)) if x3_scales else None
         self.mma = self.attn_mma = mma
         self.set_x1_twin()      # ('f16' re-attaches its twin after every policy change)
-        self._forget_routes(self._x1_route, self._up2_x1_route, self._attn_x1_route, self._ffn_x1_route)
+        self._forget_routes(self._x1_route, self._up2_x1_route, self._attn_x1_route, self._ffn_x1_route, self._kv_split_route)
         if blobx3 is not None and (blob32 is not self._up2_src[0] or blobx3 is not self._up2_src[1]):
             # phase kernels of the Upsample convolutions (up2_twin): derived from THESE blob objects -- a new upload, even one that lands
             # on the same addresses, starts from an empty cache; a policy switch on the same blobs keeps it (captured x3 graphs hold
@@ -371,7 +373,7 @@ class Ops:
     def conv(self, x, w, bias=None, *, stride=1, pad=1, ksize=3, down=False, upsample=False, pro=None, pro_act=L.PRO_NONE,
              act=L.ACT_NONE, residual=None, aux=None, aux_w=1.0, cin=None, in_off=0, out=None, split_k=None, wb=None,
              wx3=None, x3_acc_scale=None, mma=None, stats=False, out_bf16=False, bounded=False, x_amax=None, x2=None,
-             reflect=False, out_ld=None, ln=None, out_hw=None):
+             reflect=False, out_ld=None, ln=None, out_hw=None, split_cols=None):
         """x [N,H,W,ld] -> [N,Ho,Wo,Cout].  ``w`` packed [Cout,KH,KW,Cin].  ``cin``/``in_off`` select a channel
         slice of a wider input buffer.  ``down`` = VQGAN Downsample geometry (pad right/bottom only, stride 2).
         ``stats=True`` returns ``(out, st)``: ``st`` is a ``Stats`` (epilogue-reduced GroupNorm partials and, under the x3
@@ -382,7 +384,9 @@ class Ops:
         ``x3_acc_scale`` belongs to the caller's ``wx3``: a call that leaves the weight operand to this Ops takes the scale of the twin it runs
         on (the x1 twin's own table where 'f16' routes it to L.MMA_X1).
         ``ln=(gamma, beta, eps)``: LayerNorm over the output channels in the epilogue, BEFORE the residual is added (x3 GEMM form,
-        Cout == 128, rows % 128 == 0: ``ln_fusable``); the library refuses anything else."""
+        Cout == 128, rows % 128 == 0: ``ln_fusable``); the library refuses anything else.
+        ``split_cols=(c0, c1)``: output columns c0 .. c1 are written as the split-fp16 halves ``attention(kv_split=True)`` reads
+        (keep_conv2d_split: x3 GEMM form); the library refuses anything else."""
         # -- geometry
         N, H, W, ld = x.shape
         Cout = w.shape[0]
@@ -459,8 +463,8 @@ class Ops:
             key = (N, H, W, ld, Cin, Cout, KH, stride, pad_t, pad_l, Ho, Wo, out_ld, up_mode, pro_act, act, in_dtype, mma,
                    odt, sk_req, pro is not None, residual is not None, 0 if residual is None else residual.shape[-1],
                    aux is not None, bias is not None, in_off % 8, wx3 is not None, USE_BK256, x2 is not None, bool(reflect),
-                   ln is not None, flags, self.plan_ref_images)
-            return a, _plan(a, key), key
+                   ln is not None, flags, self.plan_ref_images, None if split_cols is None else tuple(split_cols))
+            return a, _plan(a, key, split_cols), key
 
         a, pl, key = planned()
         if (pl.wants_bf16_input and in_off == 0 and Cin == ld and N * H * W >= HALO_PRENORM_MINPIX):
@@ -528,7 +532,10 @@ class Ops:
                   f'aux={aux is not None} statsP={pl.stats_P if stats else 0}', file=sys.stderr, flush=True)
         if self.census is not None:
             self.census[pl.kernel] = self.census.get(pl.kernel, 0) + 1
-        L.conv2d_launch(a)
+        if split_cols is None:
+            L.conv2d_launch(a)
+        else:
+            L.conv2d_split_launch(a, split_cols)
         if DEBUG_SYNC:
             torch.cuda.synchronize()
             if not bool(torch.isfinite(out.float()).all()):
@@ -541,11 +548,12 @@ class Ops:
         return (out, st) if stats else out
 
     def linear(self, x, w, bias=None, *, act=L.ACT_NONE, residual=None, pro=None, pro_act=L.PRO_NONE, cin=None, in_off=0,
-               n_img=None, out_bf16=False, bounded=False, x_amax=None, x2=None, ln=None, want_amax=False):
+               n_img=None, out_bf16=False, bounded=False, x_amax=None, x2=None, ln=None, want_amax=False, split_cols=None):
         """x [M,ld] (or any [...,ld]) @ w[Cout,Cin]^T.  ``n_img``: the rows are n_img independent images (frames, clips) of
         M/n_img rows each -- the unit of the per-image prologue AND of the library's plan (kernel tile / split-K are chosen
         from the per-image row count, so a clip's result never depends on its batch-mates).  Default: the leading axis of a
-        3-D+ input, 1 for a plain [M,ld] matrix (callers that flatten independent images into rows pass it)."""
+        3-D+ input, 1 for a plain [M,ld] matrix (callers that flatten independent images into rows pass it).
+        ``split_cols=(c0, c1)``: see ``conv`` -- the returned fp32 tensor holds fp16 halves in those columns, for ``attention(kv_split=True)`` alone."""
         shp = x.shape
         ld = shp[-1]
         M = x.numel() // ld
@@ -553,14 +561,15 @@ class Ops:
             n_img = shp[0] if x.dim() >= 3 else 1
         assert M % n_img == 0, (tuple(shp), n_img)
         if (TOKEN_LINEAR and self.mma == L.MMA_BF16 and ld == 128 and w.shape[0] in (128, 256, 384) and w.shape[-1] == 128
-                and M >= 65536 and act == L.ACT_NONE and residual is None and pro is None and pro_act == L.PRO_NONE
+                and M >= 65536 and act == L.ACT_NONE and residual is None and pro is None and pro_act == L.PRO_NONE and split_cols is None
                 and cin is None and in_off == 0 and x.dtype == torch.float32 and x.is_contiguous()):
             return self.token_linear(x.view(M, ld), w.view(w.shape[0], 128), bias, out_bf16).reshape(*shp[:-1], w.shape[0])
         x4 = x.reshape(n_img, M // n_img, 1, ld)
         x24 = None if x2 is None else x2.reshape(n_img, M // n_img, 1, x2.shape[-1])
         res4 = None if residual is None else residual.reshape(n_img, M // n_img, 1, residual.shape[-1])
         y = self.conv(x4, w, bias, stride=1, pad=0, ksize=1, pro=pro, pro_act=pro_act, act=act, residual=res4, cin=cin,
-                      in_off=in_off, out_bf16=out_bf16, bounded=bounded, x_amax=x_amax, x2=x24, ln=ln, stats='amax' if want_amax else False)
+                      in_off=in_off, out_bf16=out_bf16, bounded=bounded, x_amax=x_amax, x2=x24, ln=ln, stats='amax' if want_amax else False,
+                      split_cols=split_cols)
         if want_amax:      # (y, per-image max |y| from the GEMM's epilogue, or None where the launch cannot emit it): the range probe of the consumer
             y, st = y
             return y.reshape(*shp[:-1], w.shape[0]), (None if st is None else st.amax)
@@ -644,9 +653,11 @@ class Ops:
 
     # ------------------------------------------------------------------ keep_attention
     def attention(self, q, k, v, o, *, B, H, Lq, Lk, D, Dv, scale, q_str, k_str, v_str, o_str, mode=0, T=0, seg_len=0,
-                  img_h=0, img_w=0, ksplit=0, shift=0, kv_rot=0, n_img=0, mma=None, probe=False, amax=None):
+                  img_h=0, img_w=0, ksplit=0, shift=0, kv_rot=0, n_img=0, mma=None, probe=False, amax=None, kv_split=False):
         """Strides are (batch, token, head) element strides.  ``probe=True`` (x3 policy, mode 0): q / k / v are projections
-        of an un-normalised tensor -- their ranges are probed and the kernel rescales them into the fp16 window."""
+        of an un-normalised tensor -- their ranges are probed and the kernel rescales them into the fp16 window.
+        ``kv_split=True``: k / v are slices of a ``linear(split_cols=...)`` output (``kv_split_ok`` said so); the library refuses what its
+        pre-split form does not cover."""
         mma = self.attn_mma if mma is None else mma
         in_dtype = L.F32
         if q.dtype == torch.bfloat16:
@@ -672,7 +683,9 @@ class Ops:
                   B=B, H=H, Lq=Lq, Lk=Lk, D=D, Dv=Dv, scale=float(scale), mode=mode, T=T, seg_len=seg_len,
                   img_h=img_h, img_w=img_w, ksplit=ksplit, shift=shift, kv_rot=kv_rot, n_img=n_img, mma=mma,
                   in_dtype=in_dtype, q_amax=amax[0], k_amax=amax[1], v_amax=amax[2], flags=self.attn_flags)
-        if self.attn_x1 and mma == self.attn_mma == L.MMA_X3 and in_dtype == L.F32:
+        if kv_split:
+            kw.update(kv_split=True)
+        elif self.attn_x1 and mma == self.attn_mma == L.MMA_X3 and in_dtype == L.F32:
             key = (H, Lq, Lk, D, Dv, mode, ksplit, img_h, img_w, shift, tuple(s % 4 for s in (*q_str, *k_str, *v_str)),
                    tuple(t.data_ptr() % 16 for t in (q, k, v)), amax[0] is not None, self.attn_flags)
             if self._route(self._attn_x1_route, key, lambda: L.attention_x1_plan(**kw) is not None):      # single fp16 where the library admits it, x3 otherwise
@@ -685,6 +698,31 @@ class Ops:
                 print(f'[keep] NON-FINITE attention output; q/k/v absmax {float(q.float().abs().max()):.4g} '
                       f'{float(k.float().abs().max()):.4g} {float(v.float().abs().max()):.4g}', file=sys.stderr, flush=True)
         return o
+
+    def kv_split_ok(self, *, B, Lq, Lk, D, Dv, q_str, k_str, v_str, img_h, img_w, ksplit, shift, n_img, gemm=None):
+        """Does the library take this window-attention call (H = 1, fp32 tensors, 16-byte aligned bases) with ``kv_split`` -- and the projection
+        that feeds it, ``gemm = (rows per image, Cin, Cout, split_cols)`` of a bias-free ``linear(split_cols=...)`` on aligned tensors, with the
+        split output?  The library's own answers (keep_attention_kv_split_plan, keep_conv2d_split_plan), asked once per shape; never under the
+        single-fp16 attention policy, which keeps the pack path."""
+        if not ATTN_PRESPLIT or self.attn_x1 or self.attn_mma != L.MMA_X3:
+            return False
+        key = (Lq, Lk, D, Dv, tuple(q_str), tuple(k_str), tuple(v_str), img_h, img_w, ksplit, shift, self.attn_flags,
+               None if gemm is None else (tuple(gemm[:3]), tuple(gemm[3]), self.mma, self.flags, self.plan_ref_images, USE_BK256))
+
+        def query():
+            a = L.attn_args(q=0x10000, k=0x10000, v=0x10000, o=0x10000, q_bs=q_str[0], q_ts=q_str[1], q_hs=q_str[2], k_bs=k_str[0], k_ts=k_str[1],
+                            k_hs=k_str[2], v_bs=v_str[0], v_ts=v_str[1], v_hs=v_str[2], o_bs=Lq * ksplit * ksplit * Dv, o_ts=Dv, o_hs=0, B=B, H=1,
+                            Lq=Lq, Lk=Lk, D=D, Dv=Dv, scale=1.0, mode=2, img_h=img_h, img_w=img_w, ksplit=ksplit, shift=shift, kv_rot=0,
+                            n_img=n_img, mma=L.MMA_X3, in_dtype=L.F32, flags=self.attn_flags)
+            L.attention_plan(a, kv_split=True)
+            if gemm is not None:      # (one image stands for any number: the form follows the reference batch, the row rule holds per image)
+                rows, cin, cout, cols = gemm
+                g = L.conv_args(inp=0x10000, weight=0x10000, out=0x10000, weight_x3=0x10000, x3_acc_scale=1.0, N=1, H=rows, W=1, Cin=cin, Cout=cout,
+                                KH=1, KW=1, stride=1, Ho=rows, Wo=1, in_ld=cin, out_ld=cout, mma=self.mma, dtype=L.F32, out_dtype=L.F32,
+                                bk256=int(USE_BK256), flags=self.flags, plan_ref_images=self.plan_ref_images)
+                L.conv2d_split_plan(g, cols)
+            return True
+        return self._route(self._kv_split_route, key, query)
 
     def token_linear(self, x, w, bias=None, out_bf16=False):
         """Streaming GEMM for the GMFlow projections (bf16 policy): x [M,128] fp32 @ w[N,128]^T, N in {128,256,384}."""

@@ -139,6 +139,28 @@ typedef struct {
 } keep_conv2d_launch_plan_out;
 int32_t keep_conv2d_launch_plan(const keep_conv2d_args* a, keep_conv2d_launch_plan_out* out);
 
+/* ---- GMFlow window attention without the K / V pack pass (KEEP_MMA_X3).  The projection GEMM writes k and v already split, the attention
+ * kernel reads them as they are: the pack kernel's pass over both tensors (read fp32, split, gather, transpose, write) does not run, and
+ * every product sees the operand bits the packed path gives it -- same results, bit for bit.
+ *
+ * keep_conv2d_split: the core header's convolution entry with output columns [split_c0, split_c1) written as split-fp16 halves: column c of
+ * 128-column group g stores hi = (fp16)y at byte g * 512 + (c % 128) * 2 of the output row and lo = (fp16)(y - (float)hi) 256 bytes further
+ * on -- the same 512 bytes per group, so strides and allocation stay those of the fp32 tensor; columns outside the range stay fp32.  For
+ * the KEEP_MMA_X3 GEMM form only (1x1, stride 1, no prologue / activation / residual / aux / split-K / statistics / LayerNorm): fp32
+ * output, Cout, out_ld and both bounds multiples of 128, N * Ho * Wo a multiple of 128; KEEP_EUNSUP otherwise.  keep_conv2d_split_plan is
+ * the core plan query for such a call (host only).
+ *
+ * keep_attention_kv_split: the core header's attention entry on k / v pointers into such a tensor (per token [hi x 128 | lo x 128] fp16 in
+ * the 512 bytes of the 128 floats; strides stay in fp32 elements).  The kernel gathers the window rows itself and takes V through the
+ * transposed LDS read; `workspace` is not used.  KEEP_MMA_X3, fp32 in_dtype, mode 2, D = Dv = 128, H = 1, Lq a multiple of 128, Lk a
+ * multiple of 32 and <= 4096, no range probes, 16-byte aligned q rows, k / v strides multiples of 128; KEEP_EUNSUP otherwise -- the caller
+ * then keeps the fp32 tensor and the core entry.  keep_attention_kv_split_plan answers without a launch (host only): `kernel` names the
+ * one launch, scratch_bytes is 0. */
+int32_t keep_conv2d_split(const keep_conv2d_args* a, int32_t split_c0, int32_t split_c1, void* stream);
+int32_t keep_conv2d_split_plan(const keep_conv2d_args* a, int32_t split_c0, int32_t split_c1, keep_conv2d_plan_out* out);
+int32_t keep_attention_kv_split(const keep_attention_args* a, void* stream);
+int32_t keep_attention_kv_split_plan(const keep_attention_args* a, keep_attention_plan_out* out);
+
 /* ---- the GMFlow feed-forward block of keep_hip.h's fused x3 entry on SINGLE fp16 operands (opt-in speed form, outside the 1e-3 parity
  * tolerance):
  *
