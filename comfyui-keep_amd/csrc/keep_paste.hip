@@ -485,3 +485,106 @@ extern "C" int32_t keep_paste_face_w(float* frame, int32_t H, int32_t W, const u
                                      float opacity, void* stream) {
   return paste_face_launch("keep_paste_face_w", frame, H, W, face, mask, fh, fw, dst_to_src, x0, y0, x1, y1, mask_border, opacity, stream);
 }
+
+// ---- the alias-free composite of one face (opt-in: GpuPaster.paste(aa=True)).  The bilinear tap above is one crop pixel wide, and a
+// face of 90 .. 250 px is a crop shrunk 2 .. 5.5 times: it aliases, and the pattern crawls with the similarity's sub-pixel motion.  Here
+// every frame pixel of the box is the mean of N x N sub-samples on the N-times finer frame grid (engine/paste.py: ss_affine), each of them
+// the tap arithmetic above -- 1/1024 rounding, 1/32 truncation, +-32768 clamp, face_at / mask_at as they are -- at the INTEGER position
+// (N x + i, N y + j) of that grid with ITS destination -> source map.  Everything summed is an integer, so the order is free:
+//
+//     v_k[c] = (taps . 15-bit weights + 2^14) >> 15              0 .. 255
+//     q_k    = rint(s_k * 65536), half to even, int32            s_k: the float soft mask value of the tap above (parse-mask form)
+//     S_c = sum v_k[c] <= 64 * 255 = 16320,   Q = sum q_k < 2^23 (a blurred 0/255 mask / 255 reaches 1.0000006: q_k <= 65537, N^2 <= 64)
+//     face_c = float(S_c) * (1 / N^2),   soft = float(Q) * (1 / (65536 N^2))          both exact: powers of two, sums below 2^24
+//     soft = soft * opacity;   frame = soft * face_c + (1 - soft) * frame             the separately rounded operations of the blend above
+//
+// In the frame-mask form the soft mask already lives in frame space: soft = frame_mask[y, x], only the face is supersampled.
+// Layout: AaLanes<N> lanes per frame pixel (4 for N = 2, 16 for N = 4 and 8; an N = 8 lane takes 4 sub-samples), consecutive lanes on
+// consecutive sub-samples of a sub-row, so neighbouring lanes read neighbouring crop bytes; the partial sums meet through xor shuffles
+// inside the 64-lane wave; lane 0 of the pixel blends and stores.  No LDS, no atomics.  Below r = 1/8 the sub-samples of N = 8 lie more
+// than one crop pixel apart: residual aliasing, not handled.
+template <int N> struct AaLanes { static constexpr int value = N == 2 ? 4 : 16; };
+template <int N> struct AaTile { static constexpr int w = N == 2 ? 16 : 8, h = 256 / AaLanes<N>::value / w; };   // frame pixels per block
+
+template <int N>
+__global__ void __launch_bounds__(256) paste_aa_kernel(PasteP p) {
+  constexpr int LPP = AaLanes<N>::value, PER_LANE = N * N / LPP, TW = AaTile<N>::w, TH = AaTile<N>::h;
+  const int pix = threadIdx.x / LPP, sub = threadIdx.x % LPP;
+  const int bx = blockIdx.x * TW + pix % TW, by = blockIdx.y * TH + pix / TW;
+  const bool live = bx < p.bw && by < p.bh;          // (a pixel's lanes are live together; nobody leaves before the shuffles)
+  const int x = p.x0 + bx, y = p.y0 + by;
+  int S0 = 0, S1 = 0, S2 = 0, Q = 0;
+  if (live) {
+#pragma unroll
+    for (int k = 0; k < PER_LANE; ++k) {
+      const int s = k * LPP + sub;
+      const long xs = (long)N * x + s % N, ys = (long)N * y + s / N;
+      const long adelta = llrint(dmul_rn(dmul_rn(p.m00, (double)xs), 1024.0));
+      const long bdelta = llrint(dmul_rn(dmul_rn(p.m10, (double)xs), 1024.0));
+      const long X0 = llrint(dmul_rn(dadd_rn(dmul_rn(p.m01, (double)ys), p.m02), 1024.0)) + 16;
+      const long Y0 = llrint(dmul_rn(dadd_rn(dmul_rn(p.m11, (double)ys), p.m12), 1024.0)) + 16;
+      const long X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;
+      long sxl = X >> 5, syl = Y >> 5;
+      sxl = sxl < -32768 ? -32768 : (sxl > 32767 ? 32767 : sxl);
+      syl = syl < -32768 ? -32768 : (syl > 32767 ? 32767 : syl);
+      const int sx = (int)sxl, sy = (int)syl, fx = (int)(X & 31), fy = (int)(Y & 31);
+      if (!p.frame_mask) {
+        const float ax = div_rn((float)fx, 32.f), ay = div_rn((float)fy, 32.f);
+        const float w00 = mul_rn(sub_rn(1.f, ax), sub_rn(1.f, ay)), w01 = mul_rn(ax, sub_rn(1.f, ay));
+        const float w10 = mul_rn(sub_rn(1.f, ax), ay), w11 = mul_rn(ax, ay);
+        float soft = mul_rn(mask_at(p, sy, sx), w00);
+        soft = add_rn(soft, mul_rn(mask_at(p, sy, sx + 1), w01));
+        soft = add_rn(soft, mul_rn(mask_at(p, sy + 1, sx), w10));
+        soft = add_rn(soft, mul_rn(mask_at(p, sy + 1, sx + 1), w11));
+        Q += (int)rintf(mul_rn(soft, 65536.f));
+      }
+      const int i00 = (32 - fx) * (32 - fy) * 32, i01 = fx * (32 - fy) * 32, i10 = (32 - fx) * fy * 32, i11 = fx * fy * 32;
+      int v[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        v[c] = (face_at(p, sy, sx, c) * i00 + face_at(p, sy, sx + 1, c) * i01 + face_at(p, sy + 1, sx, c) * i10 +
+                face_at(p, sy + 1, sx + 1, c) * i11 + (1 << 14)) >> 15;
+      S0 += v[0]; S1 += v[1]; S2 += v[2];
+    }
+  }
+#pragma unroll
+  for (int m = LPP / 2; m >= 1; m >>= 1) {
+    S0 += __shfl_xor(S0, m); S1 += __shfl_xor(S1, m); S2 += __shfl_xor(S2, m); Q += __shfl_xor(Q, m);
+  }
+  if (!live || sub != 0) return;
+  float soft = p.frame_mask ? p.frame_mask[(long)y * p.W + x] : mul_rn((float)Q, 1.f / (65536.f * N * N));
+  soft = mul_rn(soft, p.opacity);
+  const float inv = sub_rn(1.f, soft);
+  float* dst = p.acc + ((long)y * p.W + x) * 3;
+  dst[0] = add_rn(mul_rn(soft, mul_rn((float)S0, 1.f / (N * N))), mul_rn(inv, dst[0]));
+  dst[1] = add_rn(mul_rn(soft, mul_rn((float)S1, 1.f / (N * N))), mul_rn(inv, dst[1]));
+  dst[2] = add_rn(mul_rn(soft, mul_rn((float)S2, 1.f / (N * N))), mul_rn(inv, dst[2]));
+}
+
+template <int N>
+static void paste_aa_launch(const PasteP& p, hipStream_t st) {
+  hipLaunchKernelGGL(paste_aa_kernel<N>, dim3(cdiv(p.bw, AaTile<N>::w), cdiv(p.bh, AaTile<N>::h)), dim3(256), 0, st, p);
+}
+
+extern "C" int32_t keep_paste_face_aa(float* frame, int32_t H, int32_t W, const uint8_t* face, const float* mask, int32_t fh, int32_t fw,
+                                      const double* dst_to_src, int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t mask_border,
+                                      int32_t n, float opacity, void* stream) {
+  KEEP_REQUIRE(frame && face && mask && dst_to_src && H > 0 && W > 0 && fh > 1 && fw > 1, "keep_paste_face_aa: bad arguments");
+  KEEP_REQUIRE(x0 >= 0 && y0 >= 0 && x1 <= W && y1 <= H, "keep_paste_face_aa: box outside the frame");
+  KEEP_REQUIRE(opacity >= 0.f && opacity <= 1.f, "keep_paste_face_aa: opacity must lie in [0, 1], got %f", (double)opacity);   // (NaN fails both)
+  KEEP_REQUIRE(n == 2 || n == 4 || n == 8, "keep_paste_face_aa: n must be 2, 4 or 8, got %d", n);
+  if (x1 <= x0 || y1 <= y0) return KEEP_OK;        // the face does not touch the frame
+  PasteP p;
+  p.acc = frame; p.face = face; p.mask = mask;
+  p.m00 = dst_to_src[0]; p.m01 = dst_to_src[1]; p.m02 = dst_to_src[2];
+  p.m10 = dst_to_src[3]; p.m11 = dst_to_src[4]; p.m12 = dst_to_src[5];
+  p.H = H; p.W = W; p.fh = fh; p.fw = fw; p.x0 = x0; p.y0 = y0; p.bw = x1 - x0; p.bh = y1 - y0;
+  p.border = mask_border < 0 ? 0 : mask_border;
+  p.frame_mask = mask_border < 0 ? mask : nullptr;
+  p.opacity = opacity;
+  if (n == 2) paste_aa_launch<2>(p, (hipStream_t)stream);
+  else if (n == 4) paste_aa_launch<4>(p, (hipStream_t)stream);
+  else paste_aa_launch<8>(p, (hipStream_t)stream);
+  KEEP_LAUNCH_CHECK("keep_paste_face_aa");
+  return KEEP_OK;
+}

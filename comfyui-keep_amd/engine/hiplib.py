@@ -149,6 +149,7 @@ _CV_SIGNATURES = {
     'keep_gm_ffn_x1': [_vp, _vp, _vp, _f32, _vp, _f32, _vp, _vp, _f32, _vp, _i64, _i32, _i32, _i32, _vp],
     'keep_frame_signature_u8': [_vp, _i32, _i32, _i32, _vp, _vp],
     'keep_paste_face_w': [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp],
+    'keep_paste_face_aa': [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp],
     'keep_tone_match_u8': [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp],
     'keep_conv2d_split': [C.POINTER(ConvArgs), _i32, _i32, _vp],
     'keep_conv2d_split_plan': [C.POINTER(ConvArgs), _i32, _i32, C.POINTER(ConvPlanOut)],      # (host-only: no stream argument)

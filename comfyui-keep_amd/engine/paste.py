@@ -60,6 +60,28 @@ def face_box(M_fwd, fw, fh, W, H, margin=2):
     return max(0, x0), max(0, y0), min(W, x1), min(H, y1)
 
 
+def aa_factor(M):
+    """The sub-samples per axis the alias-free paste (``GpuPaster.paste(aa=True)``) takes for a face under the crop -> frame matrix M
+    (``upscale_factor`` is already inside it): the crop -> frame scale r = sqrt(|det|) in float64; 1 (today's single tap) when r is not
+    finite, 0, or >= 1 -- the face is not shrunk --, else 2 for r >= 0.5, 4 for r >= 0.25, 8 below.  Under r = 1/8 the 8 sub-samples lie more
+    than one crop pixel apart: residual aliasing, not handled."""
+    M = np.asarray(M, np.float64)
+    r = math.sqrt(abs(float(M[0, 0] * M[1, 1] - M[0, 1] * M[1, 0])))
+    if not math.isfinite(r) or r == 0 or r >= 1:
+        return 1
+    return 2 if r >= 0.5 else 4 if r >= 0.25 else 8
+
+
+def ss_affine(M, N):
+    """The crop -> frame matrix M on the N-times finer frame grid: pixel (N x + i, N y + j) of that grid is the sub-sample of frame pixel
+    (x, y) at offset ((2 i + 1 - N) / 2 N, (2 j + 1 - N) / 2 N).  N = 1 returns M bit for bit."""
+    M = np.asarray(M, np.float64)
+    if N == 1:
+        return M.copy()
+    o = (N - 1) / 2
+    return np.array([[N * M[0, 0], N * M[0, 1], N * M[0, 2] + o], [N * M[1, 0], N * M[1, 1], N * M[1, 2] + o]], np.float64)
+
+
 ALIGN_BORDER_BGR = (135, 133, 132)          # face_restoration_helper.py:318
 
 
@@ -129,6 +151,7 @@ class GpuPaster:
         self.device = torch.device(device)
         self._kern = torch.from_numpy(gaussian_kernel(PARSE_BLUR_KSIZE, PARSE_BLUR_SIGMA)).to(self.device)
         self._lut = torch.tensor(MASK_COLORMAP, dtype=torch.float32, device=self.device)
+        self.last_aa = None         # after paste(aa=True): per face the sub-samples per axis it took (None: a skipped face)
 
     def soft_masks(self, parse_classes):
         """parse_classes uint8 [F,h,w] on the device (ParseNet arg-max) -> blurred masks float [F,h,w] on the 0..255 scale;
@@ -169,12 +192,15 @@ class GpuPaster:
         L.call('keep_sep_filter', a, None, None, tmp, b, 1, H, W, kern, blur)
         return b
 
-    def paste(self, frame_u8, faces_u8, inverse_affines, parse_classes=None, upscale_factor=1.0, draw_box=False, weights=None):
+    def paste(self, frame_u8, faces_u8, inverse_affines, parse_classes=None, upscale_factor=1.0, draw_box=False, weights=None, aa=False):
         """frame_u8: uint8 [H,W,3] (numpy or tensor; the background at the output size), faces_u8: uint8 [F,fh,fw,3],
         inverse_affines: F crop -> frame matrices (``get_inverse_affine``; None entries are skipped), parse_classes: uint8
         [F,fh,fw] (``use_parse=True``) or None (``use_parse=False``: the erosion mask above, ``upscale_factor`` as the helper's).
         ``weights`` (track lifetimes: a face fades at the ends of its lifetime): per face its weight in [0, 1]; the soft mask is multiplied
         by it before the blend (``keep_paste_face_w``).  None, or a weight of 1.0, takes ``keep_paste_face``; ``draw_box`` ignores it.
+        ``aa`` (alias-free paste-back, no parity with the reference): a face that is shrunk on its way back -- ``aa_factor`` N of its
+        matrix above 1 -- is the mean of N x N sub-samples per frame pixel (``keep_paste_face_aa`` with the map of ``ss_affine``); a face
+        with N = 1 takes the entries above, argument for argument.  ``last_aa`` then lists N per face (None for a skipped face).
         Returns the composited uint8 [H,W,3] tensor on the device, or None when a face needs a blur wider than the kernels take
         (the caller falls back to the helper)."""
         frame = torch.as_tensor(frame_u8).to(self.device, non_blocking=True).contiguous()
@@ -184,9 +210,17 @@ class GpuPaster:
         if weights is not None and len(weights) != F:
             raise ValueError(f"GpuPaster.paste: {len(weights)} weights for {F} faces")
 
+        self.last_aa = [None] * F if aa else None
+
         def blend(i, mask, d2s, box, border):
             w = 1.0 if weights is None else float(weights[i])
-            if w == 1.0:
+            n = aa_factor(inverse_affines[i]) if aa else 1
+            if aa:
+                self.last_aa[i] = n
+            if n > 1:
+                fine = (C.c_double * 6)(*invert_affine(ss_affine(inverse_affines[i], n)).reshape(-1).tolist())
+                L.call('keep_paste_face_aa', acc, H, W, faces[i], mask, fh, fw, fine, *box, border, n, C.c_float(w))
+            elif w == 1.0:
                 L.call('keep_paste_face', acc, H, W, faces[i], mask, fh, fw, d2s, *box, border)
             else:
                 L.call('keep_paste_face_w', acc, H, W, faces[i], mask, fh, fw, d2s, *box, border, C.c_float(w))

@@ -63,6 +63,12 @@ the raw tracks are stitched over gaps of at most ``track_max_gap`` frames and a 
 (``face_tracks.py``); outside it nothing is cropped, restored or pasted.  A lifetime equals its frames processed as a video of their own,
 bit for bit (tests/test_gpu_track_lifetimes.py).  ``track_fade`` ramps the paste weight at a lifetime's ends (``keep_paste_face_w``).
 
+Alias-free paste-back (``KEEP_AMD_PASTE_AA``, off by default): the paste-back takes one bilinear tap of the restored crop per frame pixel,
+which aliases wherever the face is shrunk on its way back -- and real faces are, 2 to 5.5 times.  With the knob the GPU paste area-samples
+every shrunk face (``engine/paste.py``: ``aa_factor``, ``keep_paste_face_aa``); a face that is not shrunk takes today's calls.  The knob is
+one keyword at the three ``paster.paste`` call sites; the network, ParseNet and ``last_restored_faces`` never see it
+(tests/test_gpu_paste_aa_processor.py).  No parity mode.
+
 One form of each thing: the clips of a crop list are lists of crop indices everywhere -- the flat cut is the plan whose clip c is
 ``range(start, end)`` of span c (``_restore_crops_u8``, ``_restore_clips``, ``_restore_and_paste_streamed``); every device path that stands
 in for a cv2 call is decided by ``_gate`` from a row of ``opencv_checks.GATES``; both streamed paths write their output through
@@ -262,6 +268,13 @@ class KEEPFaceProcessor:
         self.track_lifetimes = os.environ.get('KEEP_AMD_TRACK_LIFETIMES', '0') == '1'
         self.track_max_gap = max(0, _env_number('KEEP_AMD_TRACK_MAX_GAP', 10, int))
         self.track_fade = max(0, _env_number('KEEP_AMD_TRACK_FADE', 0, int))
+        # the paste-back takes ONE bilinear tap of the restored 512 x 512 crop per frame pixel (cv2.warpAffine INTER_LINEAR, restated bit for
+        # bit); a face of 90 .. 250 px is that crop shrunk 2 .. 5.5 times, so the tap aliases and the pattern crawls from frame to frame.
+        # KEEP_AMD_PASTE_AA=1 (or setting the attribute): the GPU paste area-samples every shrunk face -- N x N sub-samples per frame pixel,
+        # N from the face's own scale (``engine/paste.py``: ``aa_factor``, ``keep_paste_face_aa``); a face that is not shrunk (N = 1) takes
+        # today's calls.  No parity mode, and nothing below a scale of 1/8.  Where the helper's own paste takes a frame the knob is ignored
+        # with one logged warning.  After a call with the knob on ``last_paste_aa`` is {N: faces pasted with it}.
+        self.paste_aa = os.environ.get('KEEP_AMD_PASTE_AA', '0') == '1'
         # paste-back compositing on the GPU (engine/paste.py).  Opt-in: its arithmetic restates OpenCV's and
         # could not be checked against cv2 itself in the build image.
         # KEEP_AMD_GPU_PASTE: '1' on, '0' off; unset = 'auto': the first paste runs ``opencv_agrees_with_gpu_paste`` -- the HIP
@@ -518,6 +531,7 @@ class KEEPFaceProcessor:
                       only_center_face: bool, draw_box: bool):
         helper = self.face_helper
         helper.upscale_factor = final_upscale_factor
+        self._aa_begin()
         bg_img_final = self._final_background(cv2_image_orig, final_upscale_factor, on_device=not has_aligned)
 
         if has_aligned:
@@ -582,7 +596,34 @@ class KEEPFaceProcessor:
                 up = getattr(helper, 'upscale_factor', 1)
                 return self._paste_gpu(helper, self._lanczos(bg, int(hw2[1] * up), int(hw2[0] * up), on_device=True), draw_box, **wkw)
         self._fade_ignored(weights)
+        self._aa_ignored()
         return helper.paste_faces_to_input_image(upsample_img=_host(bg), draw_box=draw_box, face_upsampler=self.face_upscale_model)
+
+    def _aa_kw(self):
+        """The keyword that turns the alias-free paste on in ``GpuPaster.paste`` -- nothing with the knob off: today's calls, argument for
+        argument."""
+        return {'aa': True} if getattr(self, 'paste_aa', False) else {}
+
+    def _aa_begin(self):
+        """A public call starts: ``last_paste_aa`` counts from nothing (with the knob off nothing is written)."""
+        if getattr(self, 'paste_aa', False):
+            self.last_paste_aa = {}
+
+    def _aa_count(self, paster):
+        """After ``paster.paste(**self._aa_kw())``: its faces into ``last_paste_aa``, {sub-samples per axis: faces}."""
+        if getattr(self, 'paste_aa', False):
+            seen = getattr(self, 'last_paste_aa', None)
+            if seen is None:
+                seen = self.last_paste_aa = {}
+            for n in paster.last_aa or ():
+                if n is not None:
+                    seen[n] = seen.get(n, 0) + 1
+
+    def _aa_ignored(self):
+        """The helper's own paste takes one tap per pixel: the knob is dropped there, with one logged warning per processor."""
+        if getattr(self, 'paste_aa', False) and not getattr(self, '_aa_warned', False):
+            self._aa_warned = True
+            log.warning("KEEP_AMD_PASTE_AA: the helper's own paste takes this frame; faces are pasted with the reference's single tap")
 
     def _fade_ignored(self, weights):
         """The helper's own paste has no per-face weight: a fade is dropped there, with one logged warning per processor."""
@@ -649,11 +690,14 @@ class KEEPFaceProcessor:
             [np.asarray(f) if np.asarray(f).ndim == 3 else np.repeat(np.asarray(f)[:, :, None], 3, axis=2)      # GRAY2BGR
              for f in helper.restored_faces]))).to(self.device)
         wkw = {} if weights is None else {'weights': list(weights)}
+        wkw.update(self._aa_kw())                         # (knob off: nothing is added)
         if not getattr(helper, 'use_parse', False):       # :386-415 erosion mask instead of the parse mask
             out = self._paster.paste(bg, faces, list(helper.inverse_affine_matrices), None, getattr(helper, 'upscale_factor', 1), draw_box, **wkw)
             if out is None:                                # a face larger than the blur kernel takes: the helper's own path
                 self._fade_ignored(weights)
+                self._aa_ignored()
                 return helper.paste_faces_to_input_image(upsample_img=_host(bg), draw_box=draw_box, face_upsampler=None)
+            self._aa_count(self._paster)
             return out.cpu().numpy()
         # :418-424  BGR uint8 -> RGB float (x/255 - 0.5)/0.5, one face per ParseNet call like the reference
         x = torch.empty(faces.shape, dtype=torch.float32, device=self.device)
@@ -669,6 +713,7 @@ class KEEPFaceProcessor:
                 classes.append(logits.argmax(dim=1).squeeze(0).to(torch.uint8))
             classes = torch.stack(classes)
         out = self._paster.paste(bg, faces, list(helper.inverse_affine_matrices), classes, getattr(helper, 'upscale_factor', 1), draw_box, **wkw)
+        self._aa_count(self._paster)
         return out.cpu().numpy()
 
     # ------------------------------------------------------------------ streamed restore + paste (round 5)
@@ -790,11 +835,13 @@ class KEEPFaceProcessor:
                     helper.upscale_factor = factor
                     helper.get_inverse_affine(None)
                     wkw = {} if weights is None else {'weights': weights[st['aff']:st['aff'] + k]}
+                    wkw.update(self._aa_kw())              # (knob off: nothing is added)
                     st['aff'] += k
                     ids = range(first[t], first[t + 1])
                     faces = torch.stack([on_dev(ready[i]) for i in ids])
                     cls = torch.stack([on_dev(classes[i]) for i in ids])
                     out.emit(t, paster.paste(bg, faces, list(helper.inverse_affine_matrices), cls, factor, draw_box, **wkw)[None])
+                    self._aa_count(paster)
                     pbar.update(1)
                     if store is not None and t + 1 == store.spans[t // store.chunk][1]:
                         store.release(t // store.chunk, ps)             # (the allocator waits for this stream's reads)
@@ -1353,6 +1400,7 @@ class KEEPFaceProcessor:
         n_frames = len(frames_bgr)
         pbar = ProgressBar(n_frames * 4)
         helper = self.face_helper
+        self._aa_begin()
 
         # -- 1. landmarks per frame -> temporally smoothed tracks
         tracks, store, fade = {}, None, None             # fade (track lifetimes with ``track_fade``): per track key the paste weight of every frame

@@ -211,6 +211,28 @@ int32_t keep_paste_face_w(float* frame /*device [H,W,3]*/, int32_t H, int32_t W,
                           const float* mask /*device*/, int32_t fh, int32_t fw, const double* dst_to_src /*host [6]*/, int32_t x0, int32_t y0,
                           int32_t x1, int32_t y1, int32_t mask_border, float opacity, void* stream);
 
+/* ---- the alias-free paste-back composite of one face (opt-in, engine/paste.py: GpuPaster.paste(aa=True)).  keep_paste_face takes ONE
+ * bilinear tap per frame pixel, a filter one crop pixel wide; a face that is shrunk on its way back (crop -> frame scale r < 1) aliases.
+ * Here every frame pixel of the box is the mean of n x n sub-samples: `dst_to_src` is the destination -> source map of the n-times finer
+ * frame grid (the inverse of engine/paste.py's ss_affine(M, n)), the box and the frame stay in frame pixels, and sub-sample (i, j) of
+ * frame pixel (x, y) is keep_paste_face's coordinate and tap arithmetic -- 1/1024 rounding, 1/32 truncation, +-32768 clamp, taps outside
+ * the crop read 0, the mask's border zeroing and / 255 -- at the integer position (n x + i, n y + j) with that map:
+ *
+ *     v_k[c] = (taps . 15-bit weights + 2^14) >> 15                       0 .. 255
+ *     q_k    = rint(s_k * 65536), half to even, int32                     s_k: keep_paste_face's float soft mask value (mask_border >= 0)
+ *     S_c = sum_k v_k[c],  Q = sum_k q_k                                  int32: the order is free
+ *     face_c = float(S_c) * (1 / n^2),  soft = float(Q) * (1 / (65536 n^2))
+ *     soft = soft * opacity;  frame = soft * face_c + (1 - soft) * frame  the separately rounded float32 operations of keep_paste_face_w
+ *
+ * Bounds: a blurred 0/255 mask divided by 255 reaches 1.0000006, so q_k <= 65537 and Q < 2^23; S_c <= 64 * 255 = 16320: both
+ * conversions and both power-of-two scalings are exact.  mask_border < 0 (the frame-space soft mask): soft = mask[y, x] as in the core
+ * entry, only the face is supersampled.  Not a restatement of the reference (which aliases); below r = 1/8 the sub-samples of n = 8 lie
+ * more than one crop pixel apart and residual aliasing stays.  KEEP_EINVAL, before anything is launched: everything keep_paste_face_w
+ * refuses, and n outside {2, 4, 8}. */
+int32_t keep_paste_face_aa(float* frame /*device [H,W,3]*/, int32_t H, int32_t W, const uint8_t* face /*device [fh,fw,3]*/,
+                           const float* mask /*device*/, int32_t fh, int32_t fw, const double* dst_to_src /*host [6], of the n-times grid*/,
+                           int32_t x0, int32_t y0, int32_t x1, int32_t y1, int32_t mask_border, int32_t n, float opacity, void* stream);
+
 /* ---- tone match of restored faces (engine/tone.py): the restored face keeps its high band and takes the low band of the crop it was made
  * from,  out = rst + lowpass(src - rst),  a separable Gaussian in integers throughout.  Per channel, indices clamped at the borders
  * (replicate), taps t[-R .. R]:
