@@ -2,6 +2,7 @@
 #include <stdarg.h>
 
 #include "keep_common.h"
+#include "../../include/keep_cv_hip.h"
 
 static thread_local char g_err[512] = "";
 
@@ -13,6 +14,8 @@ void keep_set_error(const char* fmt, ...) {
 }
 
 extern "C" int32_t keep_abi_version(void) { return KEEP_ABI_VERSION; }
+
+extern "C" int32_t keep_cv_abi_version(void) { return KEEP_CV_ABI_VERSION; }
 
 extern "C" const char* keep_last_error(void) { return g_err; }
 

@@ -7,7 +7,7 @@
 // (keep_lanczos4_tables) with OpenCV's own double / float operation sequence, FMA contraction off (Makefile).
 #include <math.h>
 
-#include "keep_common.h"
+#include "keep_resize_tile.h"
 
 #pragma clang fp contract(off)
 
@@ -57,9 +57,7 @@ extern "C" int32_t keep_lanczos4_tables(int32_t S, int32_t D, int32_t* ofs, int1
 // byte phase of its destination, and each tile row leaves in 16-byte stores (single bytes only where the row segment starts or
 // ends inside a 16-byte word).  The host sizes th / tw so that the footprint fits the dynamic LDS it passes (rcap rows of srow
 // bytes); the kernel clamps to those capacities all the same.
-#define RZ_TW 64                       // output pixels per tile row (at most)
 #define RZ_TH 32                       // output rows per tile (at most)
-#define RZ_OROW (RZ_TW * 3 + 16)       // uint8 output tile row in LDS: 192 bytes + the destination's 16-byte phase
 
 struct ResizeP {
   const uint8_t* src;
@@ -73,11 +71,11 @@ struct ResizeP {
   int lg_tw, hs;                       // log2(tw); int32 row stride of the horizontal sums (tw * 3 rounded up to 4)
 };
 
-__global__ void __launch_bounds__(256) resize_lanczos4_u8_kernel(ResizeP p) {
+__global__ void __launch_bounds__(RT_THREADS) resize_lanczos4_u8_kernel(ResizeP p) {
   extern __shared__ __attribute__((aligned(16))) uint8_t rz_dyn[];
-  __shared__ int xo[RZ_TW], yo[RZ_TH];
-  __shared__ __attribute__((aligned(16))) int16_t xc[RZ_TW * 8], yc[RZ_TH * 8];
-  __shared__ __attribute__((aligned(16))) uint8_t ot[RZ_TH * RZ_OROW];
+  __shared__ int xo[RT_TW], yo[RZ_TH];
+  __shared__ __attribute__((aligned(16))) int16_t xc[RT_TW * 8], yc[RZ_TH * 8];
+  __shared__ __attribute__((aligned(16))) uint8_t ot[RZ_TH * RT_OROW];
   const int tid = threadIdx.x;
   const int x0 = blockIdx.x * p.tw, y0 = blockIdx.y * p.th;
   const int tw = min(p.tw, p.W2 - x0), th = min(p.th, p.H2 - y0);
@@ -103,29 +101,17 @@ __global__ void __launch_bounds__(256) resize_lanczos4_u8_kernel(ResizeP p) {
   uint8_t* sb = rz_dyn;                                              // [rcap][srow] staged source bytes
   int* hb = reinterpret_cast<int*>(rz_dyn + (long)p.rcap * p.srow);  // [rcap][hs] horizontal sums
   const int hw = tw * 3, hs = p.hs;
-  // (only the low 4 bits of an address matter for a 16-byte phase: 32-bit arithmetic)
-  const uint32_t src_lo = (uint32_t)reinterpret_cast<uintptr_t>(src), dst_lo = (uint32_t)reinterpret_cast<uintptr_t>(dst);
 
-  // stage: row r of the footprint is source row clamp(sy0 + r); its columns [cx_lo, cx_hi] as the 16-byte words that hold them
-  const int nchunk = p.srow >> 4;
-  for (int i = tid; i < R * nchunk; i += 256) {
-    const int r = i / nchunk, k = i - r * nchunk;
-    const int row = min(max(sy0 + r, 0), p.H - 1);
-    const uint8_t* b0 = src + ((long)row * p.W + cx_lo) * 3;
-    const uint8_t* a0 = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(b0) & ~(uintptr_t)15);
-    // (a word that holds at least one byte of the row segment lies in a page of the buffer: reading all of it cannot fault)
-    if (16 * k < (int)(b0 - a0) + ncol_b)
-      *reinterpret_cast<uint4*>(sb + (long)r * p.srow + 16 * k) = *reinterpret_cast<const uint4*>(a0 + 16 * k);
-  }
+  // stage: row r of the footprint is source row clamp(sy0 + r); its columns [cx_lo, cx_hi]
+  const auto row_of = [&](int r) { return min(max(sy0 + r, 0), p.H - 1); };
+  rt_stage(sb, p.srow, src, p.W, cx_lo, ncol_b, R, row_of);
   __syncthreads();
 
   // horizontal pass: hb[r][x * 3 + c] = sum_i src[row][clamp(xofs[x] - 3 + i)][c] * xcoef[x][i]
   for (int i = tid; i < (R << p.lg_tw); i += 256) {
     const int r = i >> p.lg_tw, x = i & (p.tw - 1);
     if (x >= tw) continue;
-    const int row = min(max(sy0 + r, 0), p.H - 1);
-    const int phase = (int)((src_lo + ((uint32_t)row * (uint32_t)p.W + (uint32_t)cx_lo) * 3u) & 15u);
-    const uint8_t* s = sb + (long)r * p.srow + phase;
+    const uint8_t* s = sb + (long)r * p.srow + rt_phase(src, row_of(r), p.W, cx_lo);
     const int4 cw = *reinterpret_cast<const int4*>(&xc[x * 8]);
     const int16_t* a = reinterpret_cast<const int16_t*>(&cw);
     const int base = xo[x] - 3;
@@ -158,8 +144,7 @@ __global__ void __launch_bounds__(256) resize_lanczos4_u8_kernel(ResizeP p) {
       const int w = b[k];
       v0 += hv.x * w; v1 += hv.y * w; v2 += hv.z * w; v3 += hv.w * w;
     }
-    const int phase = (int)((dst_lo + ((uint32_t)(y0 + y) * (uint32_t)p.W2 + (uint32_t)x0) * 3u) & 15u);
-    uint8_t* o = &ot[y * RZ_OROW + phase + ve];
+    uint8_t* o = &ot[y * RT_OROW + rt_phase(dst, y0 + y, p.W2, x0) + ve];
     o[0] = (uint8_t)min(max((v0 + (1 << 21)) >> 22, 0), 255);
     if (ve + 1 < hw) o[1] = (uint8_t)min(max((v1 + (1 << 21)) >> 22, 0), 255);
     if (ve + 2 < hw) o[2] = (uint8_t)min(max((v2 + (1 << 21)) >> 22, 0), 255);
@@ -167,61 +152,35 @@ __global__ void __launch_bounds__(256) resize_lanczos4_u8_kernel(ResizeP p) {
   }
   __syncthreads();
 
-  // store: per tile row, the 16-byte words that lie wholly inside its destination segment, then the bytes at its two ends
-  const int nw = RZ_OROW >> 4;
-  for (int i = tid; i < th * nw; i += 256) {
-    const int y = i / nw, k = i - y * nw;
-    uint8_t* d0 = dst + ((long)(y0 + y) * p.W2 + x0) * 3;
-    const int phase = (int)(reinterpret_cast<uintptr_t>(d0) & 15);
-    const int lo = 16 * k - phase, hi = lo + 16;                   // the word's bytes relative to the segment start
-    if (lo >= 0 && hi <= hw)
-      *reinterpret_cast<uint4*>(d0 + lo) = *reinterpret_cast<const uint4*>(&ot[y * RZ_OROW + 16 * k]);
-  }
-  for (int i = tid; i < th * 32; i += 256) {
-    const int y = i >> 5, j = i & 31;
-    uint8_t* d0 = dst + ((long)(y0 + y) * p.W2 + x0) * 3;
-    const int phase = (int)(reinterpret_cast<uintptr_t>(d0) & 15);
-    const int head = min((16 - phase) & 15, hw);                   // bytes before the first whole word
-    const int body_end = head + ((hw - head) & ~15);
-    const int e = j < 16 ? j : body_end + (j - 16);                // j < 16: head byte j; else tail byte j - 16
-    if ((j < 16 && e < head) || (j >= 16 && e < hw)) d0[e] = ot[y * RZ_OROW + phase + e];
-  }
+  rt_store_tile(ot, dst, p.W2, x0, y0, th, hw);
 }
 
 extern "C" int32_t keep_resize_lanczos4_u8(const uint8_t* src, uint8_t* dst, int32_t N, int32_t H, int32_t W, int32_t H2,
                                            int32_t W2, const int32_t* xofs, const int16_t* xcoef, const int32_t* yofs,
                                            const int16_t* ycoef, void* stream) {
-  KEEP_REQUIRE(src && dst && xofs && xcoef && yofs && ycoef, "keep_resize_lanczos4_u8: null pointer");
-  KEEP_REQUIRE(N > 0 && H > 0 && W > 0 && H2 > 0 && W2 > 0,
-               "keep_resize_lanczos4_u8: sizes must be positive (N=%d H=%d W=%d H2=%d W2=%d)", N, H, W, H2, W2);
-  KEEP_REQUIRE(W <= INT32_MAX / 3 && W2 <= INT32_MAX / 3, "keep_resize_lanczos4_u8: W * 3 or W2 * 3 overflows int32");
-  KEEP_REQUIRE(N <= 65535, "keep_resize_lanczos4_u8: at most 65535 frames per call, got %d", N);
+  const char* name = "keep_resize_lanczos4_u8";
+  if (int32_t rc = rt_check_args(name, src && dst && xofs && xcoef && yofs && ycoef, N, H, W, H2, W2)) return rc;
   // tile shape: the largest th, tw (powers of two) whose footprint fits 48 KB of dynamic LDS.  Rows of a tile of th output rows:
   // yofs[y0 + th - 1] - yofs[y0] + 8 <= (th - 1) * H / H2 + 10 (each floor adds at most 1; float rounding of the source
   // coordinate is far below the margin of 3 taken here); the same for columns.
   const double sy = (double)H / H2, sx = (double)W / W2;
-  const long lds_cap = 48 << 10;
-  int th = RZ_TH, tw = RZ_TW, rcap = 0, srow = 0;
-  for (;;) {
-    rcap = (int)floor((th - 1) * sy) + 13;
-    const long span = (long)floor((tw - 1) * sx) + 13;
+  int th = RZ_TH, tw = RT_TW, rcap = 0, srow = 0;
+  const auto lds_bytes = [&](int t_h, int t_w) {                     // (leaves rcap / srow of that tile shape)
+    rcap = (int)floor((t_h - 1) * sy) + 13;
+    const long span = (long)floor((t_w - 1) * sx) + 13;
     srow = (int)(((span * 3 + 15) + 15) & ~15L);
-    const long bytes = (long)rcap * srow + (long)rcap * ((tw * 3 + 3) & ~3) * 4;
-    if (bytes <= lds_cap || (th == 1 && tw == 1)) break;
-    if (th > 1 && (th >= tw / 2 || tw == 1)) th >>= 1;
-    else tw >>= 1;
-  }
-  const int gx = cdiv(W2, tw), gy = cdiv(H2, th);
-  KEEP_REQUIRE(gy <= 65535, "keep_resize_lanczos4_u8: output too tall (H2=%d)", H2);
+    return (long)rcap * srow + (long)rcap * rt_hs(t_w) * 4;
+  };
+  rt_fit_tile(th, tw, 48 << 10, lds_bytes);
+  dim3 grid;
+  if (int32_t rc = rt_grid(name, N, H2, W2, th, tw, grid)) return rc;
   ResizeP p;
   p.src = src; p.dst = dst; p.xofs = xofs; p.xcoef = xcoef; p.yofs = yofs; p.ycoef = ycoef;
   p.H = H; p.W = W; p.H2 = H2; p.W2 = W2;
   p.tw = tw; p.th = th; p.rcap = rcap; p.srow = srow;
-  p.lg_tw = 0;
-  while ((1 << p.lg_tw) < tw) ++p.lg_tw;
-  p.hs = (tw * 3 + 3) & ~3;
-  const size_t lds = (size_t)rcap * srow + (size_t)rcap * p.hs * 4;
-  hipLaunchKernelGGL(resize_lanczos4_u8_kernel, dim3(gx, gy, N), dim3(256), lds, (hipStream_t)stream, p);
-  KEEP_LAUNCH_CHECK("keep_resize_lanczos4_u8");
+  p.lg_tw = rt_lg(tw);
+  p.hs = rt_hs(tw);
+  hipLaunchKernelGGL(resize_lanczos4_u8_kernel, grid, dim3(RT_THREADS), (size_t)lds_bytes(th, tw), (hipStream_t)stream, p);
+  KEEP_LAUNCH_CHECK(name);
   return KEEP_OK;
 }

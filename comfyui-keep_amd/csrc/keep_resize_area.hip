@@ -8,12 +8,10 @@
 #include <float.h>
 #include <math.h>
 
-#include "keep_common.h"
+#include "keep_resize_tile.h"
 #include "../../include/keep_cv_hip.h"
 
 #pragma clang fp contract(off)
-
-extern "C" int32_t keep_cv_abi_version(void) { return KEEP_CV_ABI_VERSION; }
 
 // ---- tables (host C: no device needed) ----------------------------------------------------------------------------------
 static inline double area_scale(int S, int D) { return 1.0 / ((double)D / (double)S); }
@@ -88,9 +86,7 @@ extern "C" int32_t keep_area_tables(int32_t S, int32_t D, int32_t cap, int32_t* 
 // Tap counts are data: the host sizes th / tw / the entry capacities to the scale so that everything fits the dynamic LDS it passes,
 // and the kernel clamps every index it reads from a table to those capacities and to the tables' own lengths (xtot / ytot, which the
 // launcher recomputes on the host), so tables that are not keep_area_tables' give wrong pixels, never a stray access.
-#define RA_TW 64                       // output pixels per tile row (at most)
 #define RA_TH 32                       // output rows per tile (at most)
-#define RA_OROW (RA_TW * 3 + 16)       // uint8 output tile row in LDS: 192 bytes + the destination's 16-byte phase
 
 struct AreaP {
   const uint8_t* src;
@@ -107,10 +103,10 @@ struct AreaP {
   int xcap, ycap, xtot, ytot;          // entries of a tile per axis (capacity); entries of the whole tables
 };
 
-__global__ void __launch_bounds__(256) resize_area_u8_kernel(AreaP p) {
+__global__ void __launch_bounds__(RT_THREADS) resize_area_u8_kernel(AreaP p) {
   extern __shared__ __attribute__((aligned(16))) uint8_t ra_dyn[];
-  __shared__ int xs[RA_TW + 1], ys[RA_TH + 1];
-  __shared__ __attribute__((aligned(16))) uint8_t ot[RA_TH * RA_OROW];
+  __shared__ int xs[RT_TW + 1], ys[RA_TH + 1];
+  __shared__ __attribute__((aligned(16))) uint8_t ot[RA_TH * RT_OROW];
   const int tid = threadIdx.x;
   const int x0 = blockIdx.x * p.tw, y0 = blockIdx.y * p.th;
   const int tw = min(p.tw, p.W2 - x0), th = min(p.th, p.H2 - y0);
@@ -152,27 +148,16 @@ __global__ void __launch_bounds__(256) resize_area_u8_kernel(AreaP p) {
     ya[i] = p.yalpha[ye0 + i];
   }
   const int hw = tw * 3, hs = p.hs;
-  // (only the low 4 bits of an address matter for a 16-byte phase: 32-bit arithmetic)
-  const uint32_t src_lo = (uint32_t)reinterpret_cast<uintptr_t>(src), dst_lo = (uint32_t)reinterpret_cast<uintptr_t>(dst);
 
-  // stage: row r of the footprint is source row sy_lo + r; its columns [cx_lo, cx_lo + ncol) as the 16-byte words that hold them
-  const int nchunk = p.srow >> 4;
-  for (int i = tid; i < R * nchunk; i += 256) {
-    const int r = i / nchunk, k = i - r * nchunk;
-    const uint8_t* b0 = src + ((long)(sy_lo + r) * p.W + cx_lo) * 3;
-    const uint8_t* a0 = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(b0) & ~(uintptr_t)15);
-    // (a word that holds at least one byte of the row segment lies in a page of the buffer: reading all of it cannot fault)
-    if (16 * k < (int)(b0 - a0) + ncol_b)
-      *reinterpret_cast<uint4*>(sb + (long)r * p.srow + 16 * k) = *reinterpret_cast<const uint4*>(a0 + 16 * k);
-  }
+  // stage: row r of the footprint is source row sy_lo + r; its columns [cx_lo, cx_lo + ncol)
+  rt_stage(sb, p.srow, src, p.W, cx_lo, ncol_b, R, [&](int r) { return sy_lo + r; });
   __syncthreads();
 
   // horizontal pass: hb[r][x * 3 + c] = buf, the x entries of x in ascending order: buf = buf + (float)src * alpha
   for (int i = tid; i < (R << p.lg_tw); i += 256) {
     const int r = i >> p.lg_tw, x = i & (p.tw - 1);
     if (x >= tw) continue;
-    const int phase = (int)((src_lo + ((uint32_t)(sy_lo + r) * (uint32_t)p.W + (uint32_t)cx_lo) * 3u) & 15u);
-    const uint8_t* s = sb + (long)r * p.srow + phase;
+    const uint8_t* s = sb + (long)r * p.srow + rt_phase(src, sy_lo + r, p.W, cx_lo);
     const int e0 = min(max(xs[x] - xe0, 0), nxe), e1 = min(max(xs[x + 1] - xe0, e0), nxe);
     float b0 = 0.f, b1 = 0.f, b2 = 0.f;
     for (int e = e0; e < e1; ++e) {
@@ -204,8 +189,7 @@ __global__ void __launch_bounds__(256) resize_area_u8_kernel(AreaP p) {
         v2 = __fadd_rn(v2, __fmul_rn(b, hv.z)); v3 = __fadd_rn(v3, __fmul_rn(b, hv.w));
       }
     }
-    const int phase = (int)((dst_lo + ((uint32_t)(y0 + y) * (uint32_t)p.W2 + (uint32_t)x0) * 3u) & 15u);
-    uint8_t* o = &ot[y * RA_OROW + phase + ve];
+    uint8_t* o = &ot[y * RT_OROW + rt_phase(dst, y0 + y, p.W2, x0) + ve];
     o[0] = (uint8_t)min(max(__float2int_rn(v0), 0), 255);
     if (ve + 1 < hw) o[1] = (uint8_t)min(max(__float2int_rn(v1), 0), 255);
     if (ve + 2 < hw) o[2] = (uint8_t)min(max(__float2int_rn(v2), 0), 255);
@@ -213,36 +197,15 @@ __global__ void __launch_bounds__(256) resize_area_u8_kernel(AreaP p) {
   }
   __syncthreads();
 
-  // store: per tile row, the 16-byte words that lie wholly inside its destination segment, then the bytes at its two ends
-  const int nw = RA_OROW >> 4;
-  for (int i = tid; i < th * nw; i += 256) {
-    const int y = i / nw, k = i - y * nw;
-    uint8_t* d0 = dst + ((long)(y0 + y) * p.W2 + x0) * 3;
-    const int phase = (int)(reinterpret_cast<uintptr_t>(d0) & 15);
-    const int lo = 16 * k - phase, hi = lo + 16;                   // the word's bytes relative to the segment start
-    if (lo >= 0 && hi <= hw)
-      *reinterpret_cast<uint4*>(d0 + lo) = *reinterpret_cast<const uint4*>(&ot[y * RA_OROW + 16 * k]);
-  }
-  for (int i = tid; i < th * 32; i += 256) {
-    const int y = i >> 5, j = i & 31;
-    uint8_t* d0 = dst + ((long)(y0 + y) * p.W2 + x0) * 3;
-    const int phase = (int)(reinterpret_cast<uintptr_t>(d0) & 15);
-    const int head = min((16 - phase) & 15, hw);                   // bytes before the first whole word
-    const int body_end = head + ((hw - head) & ~15);
-    const int e = j < 16 ? j : body_end + (j - 16);                // j < 16: head byte j; else tail byte j - 16
-    if ((j < 16 && e < head) || (j >= 16 && e < hw)) d0[e] = ot[y * RA_OROW + phase + e];
-  }
+  rt_store_tile(ot, dst, p.W2, x0, y0, th, hw);
 }
 
 extern "C" int32_t keep_resize_area_u8(const uint8_t* src, uint8_t* dst, int32_t N, int32_t H, int32_t W, int32_t H2, int32_t W2,
                                        const int32_t* xstart, const int32_t* xsi, const float* xalpha, const int32_t* ystart,
                                        const int32_t* ysi, const float* yalpha, void* stream) {
-  KEEP_REQUIRE(src && dst && xstart && xsi && xalpha && ystart && ysi && yalpha, "keep_resize_area_u8: null pointer");
-  KEEP_REQUIRE(N > 0 && H > 0 && W > 0 && H2 > 0 && W2 > 0,
-               "keep_resize_area_u8: sizes must be positive (N=%d H=%d W=%d H2=%d W2=%d)", N, H, W, H2, W2);
+  const char* name = "keep_resize_area_u8";
+  if (int32_t rc = rt_check_args(name, src && dst && xstart && xsi && xalpha && ystart && ysi && yalpha, N, H, W, H2, W2)) return rc;
   KEEP_REQUIRE(H2 < H && W2 < W, "keep_resize_area_u8: INTER_AREA is for shrinking on both axes (H=%d W=%d -> H2=%d W2=%d)", H, W, H2, W2);
-  KEEP_REQUIRE(W <= INT32_MAX / 3, "keep_resize_area_u8: W * 3 overflows int32 (W=%d)", W);
-  KEEP_REQUIRE(N <= 65535, "keep_resize_area_u8: at most 65535 frames per call, got %d", N);
   const double sy = area_scale(H, H2), sx = area_scale(W, W2);
   KEEP_REQUIRE(!(area_scale_is_whole(sx) && area_scale_is_whole(sy)),
                "keep_resize_area_u8: %dx%d -> %dx%d has a whole-number scale on both axes (OpenCV's integer INTER_AREA path, not restated here)",
@@ -251,34 +214,29 @@ extern "C" int32_t keep_resize_area_u8(const uint8_t* src, uint8_t* dst, int32_t
   // 1080p, 720p and 2160p -> 640 x 1137: 32 and 24 KB are 10-16 % faster than 48 KB, profiles/detect_resize_area.txt).  A tile of th output rows starting at
   // y0 reads source rows ceil(y0 * sy) - 1 .. floor((y0 + th) * sy): at most th * sy + 2, one more taken for the rounding of the
   // products; a destination cell has at most floor(sy) + 3 entries (head, floor(sy) + 1 whole pixels, tail).  The same for columns.
-  const long lds_cap = 32 << 10;
-  int th = RA_TH, tw = RA_TW, rcap = 0, ccap = 0, srow = 0, xcap = 0, ycap = 0;
-  for (;;) {
-    rcap = (int)floor(th * sy) + 3;
-    ccap = (int)floor(tw * sx) + 3;
+  int th = RA_TH, tw = RT_TW, rcap = 0, ccap = 0, srow = 0, xcap = 0, ycap = 0;
+  const auto lds_bytes = [&](int t_h, int t_w) {                     // (leaves the capacities of that tile shape)
+    rcap = (int)floor(t_h * sy) + 3;
+    ccap = (int)floor(t_w * sx) + 3;
     srow = (int)((((long)ccap * 3 + 15) + 15) & ~15L);
-    xcap = tw * ((int)floor(sx) + 3);
-    ycap = th * ((int)floor(sy) + 3);
-    const long bytes = (long)rcap * srow + (long)rcap * ((tw * 3 + 3) & ~3) * 4 + 8L * (xcap + ycap);
-    if (bytes <= lds_cap || (th == 1 && tw == 1)) break;
-    if (th > 1 && (th >= tw / 2 || tw == 1)) th >>= 1;
-    else tw >>= 1;
-  }
-  const int hs = (tw * 3 + 3) & ~3;
-  const size_t lds = (size_t)rcap * srow + (size_t)rcap * hs * 4 + 8 * (size_t)(xcap + ycap);
+    xcap = t_w * ((int)floor(sx) + 3);
+    ycap = t_h * ((int)floor(sy) + 3);
+    return (long)rcap * srow + (long)rcap * rt_hs(t_w) * 4 + 8L * (xcap + ycap);
+  };
+  rt_fit_tile(th, tw, 32 << 10, lds_bytes);
+  const size_t lds = (size_t)lds_bytes(th, tw);
   KEEP_REQUIRE(lds <= (size_t)(56 << 10), "keep_resize_area_u8: a one-pixel tile of %dx%d -> %dx%d needs %zu bytes of LDS", W, H, W2, H2, lds);
-  const int gx = cdiv(W2, tw), gy = cdiv(H2, th);
-  KEEP_REQUIRE(gy <= 65535, "keep_resize_area_u8: output too tall (H2=%d)", H2);
+  dim3 grid;
+  if (int32_t rc = rt_grid(name, N, H2, W2, th, tw, grid)) return rc;
   AreaP p;
   p.src = src; p.dst = dst; p.xstart = xstart; p.xsi = xsi; p.xalpha = xalpha; p.ystart = ystart; p.ysi = ysi; p.yalpha = yalpha;
   p.H = H; p.W = W; p.H2 = H2; p.W2 = W2;
   p.tw = tw; p.th = th; p.rcap = rcap; p.ccap = ccap; p.srow = srow;
-  p.lg_tw = 0;
-  while ((1 << p.lg_tw) < tw) ++p.lg_tw;
-  p.hs = hs;
+  p.lg_tw = rt_lg(tw);
+  p.hs = rt_hs(tw);
   p.xcap = xcap; p.ycap = ycap;
   p.xtot = (int)area_entry_count(W, W2); p.ytot = (int)area_entry_count(H, H2);
-  hipLaunchKernelGGL(resize_area_u8_kernel, dim3(gx, gy, N), dim3(256), lds, (hipStream_t)stream, p);
-  KEEP_LAUNCH_CHECK("keep_resize_area_u8");
+  hipLaunchKernelGGL(resize_area_u8_kernel, grid, dim3(RT_THREADS), lds, (hipStream_t)stream, p);
+  KEEP_LAUNCH_CHECK(name);
   return KEEP_OK;
 }

@@ -44,8 +44,17 @@ def lanczos4_tables(S, D):
     return ofs, coef
 
 
-class Lanczos4Resizer:
-    """Device tables cached per (H, W, H2, W2): a video has one geometry, so they are built once.  One instance per processor."""
+def _frame_size(frames, who):
+    """(H, W) of frames [H,W,3] or [N,H,W,3]; ``who`` (the method) opens the error text."""
+    shape = tuple(frames.shape)
+    if len(shape) not in (3, 4) or shape[-1] != 3:
+        raise ValueError(f"{who}: expected [H,W,3] or [N,H,W,3] uint8 frames, got shape {shape}")
+    return shape[-3], shape[-2]
+
+
+class _Resizer:
+    """What the three resizers share: the device, the conversion of a call's frames and output to what a launch takes, and device tables
+    cached per (H, W, H2, W2) -- a video has one geometry, so they are built once."""
 
     def __init__(self, device):
         self.device = torch.device(device)
@@ -57,38 +66,56 @@ class Lanczos4Resizer:
         key = (H, W, H2, W2)
         t = self._tables.get(key)
         if t is None:
-            xo, xc = lanczos4_tables(W, W2)
-            yo, yc = lanczos4_tables(H, H2)
-            t = tuple(torch.from_numpy(a).to(self.device) for a in (xo, xc, yo, yc))
+            t = tuple(torch.from_numpy(a).to(self.device) for a in self._axis_tables(W, W2) + self._axis_tables(H, H2))
             torch.cuda.current_stream(self.device).synchronize()     # (read later from whichever stream resizes)
             self._tables[key] = t
         return t
+
+    def _input(self, frames, who):
+        """(x, batched): frames of a checked shape as a contiguous uint8 [N,H,W,3] tensor on the device; ``batched``: they came with N."""
+        x = torch.as_tensor(frames)
+        if x.dtype != torch.uint8:
+            raise ValueError(f"{who}: expected uint8 frames, got {x.dtype}")
+        x = x.to(self.device, non_blocking=True).contiguous()
+        batched = x.dim() == 4
+        return (x if batched else x[None]), batched
+
+    def _output(self, frames, H2, W2, out, who):
+        """The [N,H2,W2,3] tensor a launch over ``frames`` (of a checked shape) writes: a new one, or ``out`` -- a contiguous uint8 tensor
+        of the result's shape on this device -- seen with its N."""
+        shape = tuple(frames.shape)
+        N = shape[0] if len(shape) == 4 else 1
+        if out is None:
+            return torch.empty((N, H2, W2, 3), dtype=torch.uint8, device=self.device)
+        want = shape[:-3] + (H2, W2, 3)
+        if tuple(out.shape) != want or out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous():
+            raise ValueError(f"{who}: out must be a contiguous uint8 {want} tensor on {self.device}")
+        return out.view(N, H2, W2, 3)
+
+    def _launch(self, entry, x, y, batched, *args):
+        """One launch of ``entry`` over x [N,H,W,3] -> y [N,H2,W2,3] (none for N = 0); the result as the frames came, with or without N."""
+        (N, H, W, _), (H2, W2) = x.shape, y.shape[1:3]
+        if N > 0:
+            with torch.cuda.device(self.device):
+                L.call(entry, x, y, N, H, W, H2, W2, *args)
+        return y if batched else y[0]
+
+
+class Lanczos4Resizer(_Resizer):
+    """``cv2.resize(..., INTER_LANCZOS4)`` for uint8 3-channel frames.  One instance per processor."""
+    _axis_tables = staticmethod(lanczos4_tables)
 
     def resize_u8(self, frames, W2, H2):
         """uint8 BGR frames [H,W,3] or [N,H,W,3] (numpy or tensor) -> uint8 [H2,W2,3] / [N,H2,W2,3] on the device.  At identity the
         input comes back as it is and nothing is launched (cv2.resize copies; ``_resize`` in the processor returns its input)."""
         W2, H2 = int(W2), int(H2)
-        shape = tuple(frames.shape)
-        if len(shape) not in (3, 4) or shape[-1] != 3:
-            raise ValueError(f"resize_u8: expected [H,W,3] or [N,H,W,3] uint8 BGR frames, got shape {shape}")
-        H, W = shape[-3], shape[-2]
+        H, W = _frame_size(frames, 'resize_u8')
         if (H, W) == (H2, W2):
             return frames
-        x = torch.as_tensor(frames)
-        if x.dtype != torch.uint8:
-            raise ValueError(f"resize_u8: expected uint8 frames, got {x.dtype}")
-        x = x.to(self.device, non_blocking=True).contiguous()
-        batched = x.dim() == 4
-        if not batched:
-            x = x[None]
-        N = x.shape[0]
-        out = torch.empty((N, H2, W2, 3), dtype=torch.uint8, device=self.device)
-        if N == 0:
-            return out if batched else out[0]
-        xo, xc, yo, yc = self._device_tables(H, W, H2, W2)
-        with torch.cuda.device(self.device):
-            L.call('keep_resize_lanczos4_u8', x, out, N, H, W, H2, W2, xo, xc, yo, yc)
-        return out if batched else out[0]
+        x, batched = self._input(frames, 'resize_u8')
+        y = self._output(x, H2, W2, None, 'resize_u8')
+        tables = self._device_tables(H, W, H2, W2) if len(x) else ()      # (an empty batch builds none)
+        return self._launch('keep_resize_lanczos4_u8', x, y, batched, *tables)
 
 
 def area_tables(S, D):
@@ -120,60 +147,27 @@ def area_geometry_refused(H, W, H2, W2):
     return _whole_scale(H, H2) and _whole_scale(W, W2)
 
 
-class AreaResizer:
-    """Device tables cached per (H, W, H2, W2), like ``Lanczos4Resizer``.  One instance per processor."""
-
-    def __init__(self, device):
-        self.device = torch.device(device)
-        if self.device.type == 'cuda' and self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
-        self._tables = {}
-
-    def _device_tables(self, H, W, H2, W2):
-        key = (H, W, H2, W2)
-        t = self._tables.get(key)
-        if t is None:
-            t = tuple(torch.from_numpy(a).to(self.device) for a in area_tables(W, W2) + area_tables(H, H2))
-            torch.cuda.current_stream(self.device).synchronize()     # (read later from whichever stream resizes)
-            self._tables[key] = t
-        return t
+class AreaResizer(_Resizer):
+    """``cv2.resize(..., INTER_AREA)`` for uint8 3-channel frames that shrink on both axes.  One instance per processor."""
+    _axis_tables = staticmethod(area_tables)
 
     def resize_u8(self, frames, W2, H2):
         """uint8 frames [H,W,3] or [N,H,W,3] (numpy or tensor) -> uint8 [H2,W2,3] / [N,H2,W2,3] on the device, one launch on the current
         stream.  A refused geometry (``area_geometry_refused``) raises KeepHipError: there is no other path here."""
         W2, H2 = int(W2), int(H2)
-        shape = tuple(frames.shape)
-        if len(shape) not in (3, 4) or shape[-1] != 3:
-            raise ValueError(f"resize_u8: expected [H,W,3] or [N,H,W,3] uint8 frames, got shape {shape}")
-        H, W = shape[-3], shape[-2]
-        x = torch.as_tensor(frames)
-        if x.dtype != torch.uint8:
-            raise ValueError(f"resize_u8: expected uint8 frames, got {x.dtype}")
+        H, W = _frame_size(frames, 'resize_u8')
+        x, batched = self._input(frames, 'resize_u8')
         if area_geometry_refused(H, W, H2, W2):
             raise L.KeepHipError(f"keep_resize_area_u8 refuses {W}x{H} -> {W2}x{H2}: INTER_AREA on the device is for shrinking on both "
                                  f"axes with a scale that is not a whole number on both", code=L.EINVAL)
-        x = x.to(self.device, non_blocking=True).contiguous()
-        batched = x.dim() == 4
-        if not batched:
-            x = x[None]
-        N = x.shape[0]
-        out = torch.empty((N, H2, W2, 3), dtype=torch.uint8, device=self.device)
-        if N == 0:
-            return out if batched else out[0]
-        tables = self._device_tables(H, W, H2, W2)
-        with torch.cuda.device(self.device):
-            L.call('keep_resize_area_u8', x, out, N, H, W, H2, W2, *tables)
-        return out if batched else out[0]
+        y = self._output(x, H2, W2, None, 'resize_u8')
+        tables = self._device_tables(H, W, H2, W2) if len(x) else ()      # (an empty batch builds none)
+        return self._launch('keep_resize_area_u8', x, y, batched, *tables)
 
 
-class LinearResizer:
+class LinearResizer(_Resizer):
     """``cv2.resize(..., INTER_LINEAR)`` for uint8 3-channel frames; the kernel needs no tables, so there is nothing to cache.  One
     instance per processor."""
-
-    def __init__(self, device):
-        self.device = torch.device(device)
-        if self.device.type == 'cuda' and self.device.index is None:
-            self.device = torch.device('cuda', torch.cuda.current_device())
 
     def resize_u8(self, frames, W2, H2, out=None):
         """uint8 frames [H,W,3] or [N,H,W,3] (numpy or tensor) -> uint8 [H2,W2,3] / [N,H2,W2,3] on the device, one launch on the current
@@ -181,28 +175,14 @@ class LinearResizer:
         contiguous uint8 tensor of the result's shape on this device to write into (a slice of a larger batch) instead of a new one; at
         identity the frames are copied into it."""
         W2, H2 = int(W2), int(H2)
-        shape = tuple(frames.shape)
-        if len(shape) not in (3, 4) or shape[-1] != 3:
-            raise ValueError(f"resize_u8: expected [H,W,3] or [N,H,W,3] uint8 frames, got shape {shape}")
-        H, W = shape[-3], shape[-2]
-        want = shape[:-3] + (H2, W2, 3)
-        if out is not None and (tuple(out.shape) != want or out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous()):
-            raise ValueError(f"resize_u8: out must be a contiguous uint8 {want} tensor on {self.device}")
+        H, W = _frame_size(frames, 'resize_u8')
+        if (H, W) == (H2, W2) and out is None:
+            return frames
+        y = self._output(frames, H2, W2, out, 'resize_u8')
         if (H, W) == (H2, W2):
-            return frames if out is None else out.copy_(torch.as_tensor(frames), non_blocking=True)
-        x = torch.as_tensor(frames)
-        if x.dtype != torch.uint8:
-            raise ValueError(f"resize_u8: expected uint8 frames, got {x.dtype}")
-        x = x.to(self.device, non_blocking=True).contiguous()
-        batched = x.dim() == 4
-        if not batched:
-            x = x[None]
-        N = x.shape[0]
-        y = torch.empty((N, H2, W2, 3), dtype=torch.uint8, device=self.device) if out is None else out.view(N, H2, W2, 3)
-        if N > 0:
-            with torch.cuda.device(self.device):
-                L.call('keep_resize_linear_u8', x, y, N, H, W, H2, W2)
-        return y if batched else y[0]
+            return out.copy_(torch.as_tensor(frames), non_blocking=True)
+        x, batched = self._input(frames, 'resize_u8')
+        return self._launch('keep_resize_linear_u8', x, y, batched)
 
     @staticmethod
     def enlarged_size(H, W, fx, fy):
@@ -215,28 +195,12 @@ class LinearResizer:
         -> uint8 [H2,W2,3] / [N,H2,W2,3] on the device, one launch on the current stream; (W2, H2) = ``enlarged_size``.  Unlike
         ``resize_u8`` nothing is special at identity: the kernel's arithmetic copies.  ``out``: as in ``resize_u8``."""
         fx, fy = float(fx), float(fy)
-        shape = tuple(frames.shape)
-        if len(shape) not in (3, 4) or shape[-1] != 3:
-            raise ValueError(f"enlarge_u8: expected [H,W,3] or [N,H,W,3] uint8 frames, got shape {shape}")
+        H, W = _frame_size(frames, 'enlarge_u8')
         if not (np.isfinite(fx) and np.isfinite(fy) and fx > 0 and fy > 0):
             raise ValueError(f"enlarge_u8: factors must be finite and positive, got fx={fx} fy={fy}")
-        H, W = shape[-3], shape[-2]
         W2, H2 = self.enlarged_size(H, W, fx, fy)
         if H <= 0 or W <= 0 or H2 <= 0 or W2 <= 0:
             raise ValueError(f"enlarge_u8: empty source or destination ({W}x{H} -> {W2}x{H2})")
-        want = shape[:-3] + (H2, W2, 3)
-        if out is not None and (tuple(out.shape) != want or out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous()):
-            raise ValueError(f"enlarge_u8: out must be a contiguous uint8 {want} tensor on {self.device}")
-        x = torch.as_tensor(frames)
-        if x.dtype != torch.uint8:
-            raise ValueError(f"enlarge_u8: expected uint8 frames, got {x.dtype}")
-        x = x.to(self.device, non_blocking=True).contiguous()
-        batched = x.dim() == 4
-        if not batched:
-            x = x[None]
-        N = x.shape[0]
-        y = torch.empty((N, H2, W2, 3), dtype=torch.uint8, device=self.device) if out is None else out.view(N, H2, W2, 3)
-        if N > 0:
-            with torch.cuda.device(self.device):
-                L.call('keep_resize_linear_fxy_u8', x, y, N, H, W, H2, W2, fx, fy)
-        return y if batched else y[0]
+        y = self._output(frames, H2, W2, out, 'enlarge_u8')
+        x, batched = self._input(frames, 'enlarge_u8')
+        return self._launch('keep_resize_linear_fxy_u8', x, y, batched, fx, fy)

@@ -669,7 +669,7 @@ def ref_paste_face(p, t, mask_border=None):
 
 
 def ref_lanczos(p, t):
-    n, h, w, h2, w2 = _known(p, 'n', 'h', 'w', 'h2', 'w2')
+    n, h, w, h2, w2, _ = _known(p, 'n', 'h', 'w', 'h2', 'w2', 'unaligned')       # (unaligned: where the buffers lie, not what they hold)
     src = t['src'].numpy().reshape(n, h, w, 3)
     for name, (S, D) in (('x', (w, w2)), ('y', (h, h2))):          # the table's coefficient tables are the restated ones
         ofs, coef = LZ.axis_tables(S, D)

@@ -134,6 +134,14 @@ def output(name, shape, dtype=torch.float32, ld=None, off=0, tile_bytes=0, init=
     return Region(rows, C if ld is None else ld, {name: (off, C, init)}, dtype, 'w', tile_bytes, compare)
 
 
+def unaligned_u8(src, dst_bytes):
+    """The regions 'src' and 'dst' of a uint8 launch whose two base pointers are not 16-byte aligned: ``src`` and the ``dst_bytes`` of the
+    result as one row each, 5 and 11 bytes into a row that is 16 bytes longer (allocations, guards and exactly sized buffers all start on
+    a multiple of 16).  The other 16 bytes of either row are surroundings like the guards."""
+    src = src.reshape(1, -1)
+    return [single('src', src, ld=src.numel() + 16, off=5), output('dst', (1, dst_bytes), torch.uint8, ld=dst_bytes + 16, off=11)]
+
+
 def _first_diff(a, b):
     return int((a != b).nonzero()[0])
 

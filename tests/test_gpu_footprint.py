@@ -1052,7 +1052,7 @@ def _paste_face(h, w, fh, fw, m, box, frame_mask, mask_border=3):
     return R, lambda t: _call('keep_paste_face', t['frame'], h, w, t['face'], t['mask'], fh, fw, _d2s(m), *box, -1 if frame_mask else mask_border)
 
 
-def _lanczos(n, h, w, h2, w2):
+def _lanczos(n, h, w, h2, w2, unaligned=False):
     lib = L.load(check_device=False)
 
     def table(S, D):
@@ -1060,8 +1060,14 @@ def _lanczos(n, h, w, h2, w2):
         assert lib.keep_lanczos4_tables(S, D, ofs.ctypes.data, coef.ctypes.data) == 0
         return torch.from_numpy(ofs).reshape(1, D), torch.from_numpy(coef).reshape(D, 8)
     (xo, xc), (yo, yc) = table(w, w2), table(h, h2)
-    R = [_in('src', u8('lz', (n * h * w, 3))), _in('xo', xo), _in('xc', xc), _in('yo', yo), _in('yc', yc), FP.output('dst', (n * h2 * w2, 3), torch.uint8)]
-    return R, lambda t: _call('keep_resize_lanczos4_u8', t['src'], t['dst'], n, h, w, h2, w2, t['xo'], t['xc'], t['yo'], t['yc'])
+    src = u8('lz', (n * h * w, 3))
+    R = FP.unaligned_u8(src, n * h2 * w2 * 3) if unaligned else [_in('src', src), FP.output('dst', (n * h2 * w2, 3), torch.uint8)]
+    R += [_in('xo', xo), _in('xc', xc), _in('yo', yo), _in('yc', yc)]
+
+    def launch(t):
+        assert (t['src'].data_ptr() % 16, t['dst'].data_ptr() % 16) == ((5, 11) if unaligned else (0, 0))
+        _call('keep_resize_lanczos4_u8', t['src'], t['dst'], n, h, w, h2, w2, t['xo'], t['xc'], t['yo'], t['yc'])
+    return R, launch
 
 
 def _token_linear(m, n_out, out_bf16, k=128, bias=True):
@@ -1193,7 +1199,8 @@ FLAT_CASES = {
     'keep_paste_face': [_k('inside', _paste_face, 16, 16, 8, 8, (1, 0, -2.5, 0, 1, -3.25), (2, 3, 12, 13), False),
                         _k('over_the_edge', _paste_face, 13, 17, 11, 9, _HANG, (0, 0, 17, 13), False),
                         _k('frame_mask', _paste_face, 13, 17, 11, 9, _HANG, (5, 0, 17, 9), True)],
-    'keep_resize_lanczos4_u8': [_k('up', _lanczos, 2, 8, 8, 16, 16), _k('ragged', _lanczos, 3, 5, 7, 3, 100), _k('one_pixel', _lanczos, 1, 5, 7, 1, 1)],
+    'keep_resize_lanczos4_u8': [_k('up', _lanczos, 2, 8, 8, 16, 16), _k('ragged', _lanczos, 3, 5, 7, 3, 100), _k('one_pixel', _lanczos, 1, 5, 7, 1, 1),
+                                _k('unaligned', _lanczos, 3, 5, 7, 3, 100, unaligned=True)],
 }
 # launchers the convolution / attention tables above cover
 STRUCT_LAUNCHERS = {'keep_conv2d': CONV_CASES, 'keep_attention': ATTN_CASES}

@@ -119,24 +119,26 @@ def test_empty_batches_and_bad_arguments_launch_nothing(rz, monkeypatch):
     assert tuple(empty.shape) == (0, 64, 64, 3) and empty.is_cuda
 
 
-def _linear_case(n, h, w, h2, w2):
+def _linear_case(n, h, w, h2, w2, unaligned):
     from comfyui_keep_amd.engine import hiplib as L
     g = torch.Generator().manual_seed(h * 1000 + w)
     src = torch.randint(0, 256, (n * h * w, 3), generator=g, dtype=torch.uint8)
-    regions = [FP.single('src', src), FP.output('dst', (n * h2 * w2, 3), torch.uint8)]
+    regions = FP.unaligned_u8(src, n * h2 * w2 * 3) if unaligned else [FP.single('src', src), FP.output('dst', (n * h2 * w2, 3), torch.uint8)]
 
     def launch(t):
+        assert (t['src'].data_ptr() % 16, t['dst'].data_ptr() % 16) == ((5, 11) if unaligned else (0, 0))
         L.call('keep_resize_linear_u8', t['src'], t['dst'], n, h, w, h2, w2)
     return src, regions, launch
 
 
 @pytest.mark.parametrize('case,n,hw,hw2', [('ragged', 3, (7, 101), (5, 67)), ('one_row', 1, (3, 75), (1, 44)), ('half', 1, (10, 14), (5, 7)),
-                                           ('unstaged', 2, (40, 300), (3, 20))])
+                                           ('unstaged', 2, (40, 300), (3, 20)), ('unaligned', 3, (7, 101), (5, 67))])
 def test_footprint_in_poisoned_surroundings(case, n, hw, hw2):
     """Every buffer of the launch sits between guards the test owns: nothing outside the payloads is written, nothing outside them reaches
-    the result, and the result is the restatement's.  ('unstaged': a 15x shrink, whose tiles read global memory directly.)"""
+    the result, and the result is the restatement's.  ('unstaged': a 15x shrink, whose tiles read global memory directly; 'unaligned': the
+    launch's src and dst start 5 and 11 bytes into a 16-byte word.)"""
     (h, w), (h2, w2) = hw, hw2
-    src, regions, launch = _linear_case(n, h, w, h2, w2)
+    src, regions, launch = _linear_case(n, h, w, h2, w2, case == 'unaligned')
     out = FP.run(launch, regions, 'cuda')['dst'].cpu().numpy().reshape(n, h2, w2, 3)
     x = src.numpy().reshape(n, h, w, 3)
     for i in range(n):
